@@ -45,6 +45,21 @@ PEAK_FP32_TFLOPS = 157.3                  # MI355X f32 FMA / f32-MFMA dense peak
 # power management, not the schedule, bounds the integer matrix cores on real data.  Reported BESIDE the nominal peak, never instead of it.
 SUSTAINED_LIVE_I8_TOPS = 3190.0
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 64 << 20                     # --dump-outputs: at most this much in all (shared among the ranks)
+
+
+def dump_outputs(out_dir, name, used, made, y, budget):
+    """What the caller of the timed path received from its last step: `<name>.npy` = the output frames [made, channels] (float32) and
+    `<name>_counts.npy` = (input frames used, output frames generated) (float64).  Above `budget` bytes the frames are a fixed, seeded
+    sample of whole output frames, in order, whose indices go to `<name>_rows.npy` (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"{name}_counts.npy"), np.array([used, made], np.float64))
+    room = budget - 4096                                  # (the files' .npy headers and the counts)
+    if y.nbytes > room:
+        rows = np.sort(np.random.default_rng(0).choice(y.shape[0], room // (y.shape[1] * 4 + 8), replace=False))
+        np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        y = y[rows]
+    np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(y, np.float32))
 
 
 def cpu_baseline(channels, seconds_budget=12.0):
@@ -259,7 +274,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the config_b / config_c / config_e legs (BASELINE.json configs[1], [2], [4]) behind the headline")
     ap.add_argument("--pmc-json", default=None, help="traffic file written by tools/roofline_report.py from the rocprofv3 --pmc passes of the same lease (tools/refresh_evidence.sh; else the committed profiles/ figure is reported, labelled as such)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline's last timed step returned to DIR/*.npy (output.npy, output_counts.npy; with N ranks output_rank<r>*.npy, "
+                         "each rank its channel slice; at most 64 MB in all, a fixed seeded sample of whole frames beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import audio_resampler_amd as A
@@ -316,13 +336,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_region(blk=None, steps=None):
+    def timed_region(blk=None, steps=None, keep=False):
         """W untimed warmup steps, then EXACTLY K steps between barrier + synchronize on both sides: the clean region `value` is taken
         from — no event is recorded inside it.  Behind it, between barriers of its own, the same K steps once more with HIP events around
         every launch's dominant kernel (on the kernel's own stream): the roofline's per-launch duration.  Events are not free — each is a
         packet in the queue between two kernels, three per launch: measured (tools/micro/host_rate.py) 117.5 against 123.1 us per headline
         call, 27.1 against 32.9 at 65,536 frames — which is why the two regions are separate; the instrumented region's own rate rides in
-        the line as ms_per_step_instrumented."""
+        the line as ms_per_step_instrumented.  keep: the last timed step's result is copied to the host (timed_region.last) once the
+        clock has stopped, before the instrumented steps overwrite it."""
         blk = block if blk is None else blk
         steps = args.steps if steps is None else steps
         cap_b = int(math.floor((blk + TAPS // 2) * ratio + 10))
@@ -337,6 +358,8 @@ def main():
             frames += made
         barrier()
         dt = time.perf_counter() - t0
+        if keep:
+            timed_region.last = (used, made, d_out[:made].cpu().numpy())
         rs.set_timing(True)
         t1 = time.perf_counter()
         for _ in range(steps):
@@ -357,22 +380,18 @@ def main():
     # ("preroll_ms"); --preroll-ms 0 disables it (value == a second cold-ish run then).
     if args.preroll_ms > 0:
         t_pre = time.perf_counter()
-        pre_calls = 0
         while (time.perf_counter() - t_pre) * 1e3 < args.preroll_ms:
             for _ in range(8):
                 rs.process_device(d_in, block, d_out, cap, ratio)
-            pre_calls += 8
             torch.cuda.synchronize()
-        if dist is not None:
-            # (the pre-roll is bounded by time, so ranks make different numbers of calls — and a call's frame count depends on the stream's phase
-            # (1,048,576 x 160 / 147 is not whole): every rank goes on to the longest rank's count, so that all streams enter the timed region at the
-            # same position and the ranks' frame counts agree whatever K is)
-            n_pre = torch.tensor([pre_calls], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
-            dist.all_reduce(n_pre, op=dist.ReduceOp.MAX)
-            for _ in range(int(n_pre.item()) - pre_calls):
-                rs.process_device(d_in, block, d_out, cap, ratio)
-            torch.cuda.synchronize()
-    dt, out_frames, kernel_ms, launches, prep_ms = timed_region()
+    # The pre-roll is bounded by time, so it leaves the stream at a position that differs from run to run and from rank to rank — and a
+    # call's frame count and output bits depend on that position (1,048,576 x 160 / 147 is not whole).  The stream goes back to where it
+    # started (history zeroed, same advance as above; the context's filter bank and kept rows stay): the timed region then runs the same
+    # W + K calls as the cold one, every rank's frame counts agree whatever K is, and the last step's output is the same on every run.
+    rs.reset()
+    rs.advance(TAPS / 2.0)
+    dt, out_frames, kernel_ms, launches, prep_ms = timed_region(keep=args.dump_outputs is not None)
+    last_step = timed_region.last if args.dump_outputs is not None else None
     ms_instrumented = timed_region.instrumented_ms_per_step
     kernel_used = rs.last_kernel()
     fixed_state, fixed_pairs = rs.fixed_point()           # 1: the matrix path ran in fixed point on the integer matrix cores
@@ -590,6 +609,9 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(Cn)
         print(json.dumps(line), flush=True)
+
+    if last_step is not None:
+        dump_outputs(args.dump_outputs, "output" if world == 1 else f"output_rank{rank}", *last_step, DUMP_BYTES // world)
 
     if dist is not None:
         dist.barrier()

@@ -1,7 +1,8 @@
 """Test infrastructure: child processes (bench.py, torch.distributed.run) whose failures must be READABLE in a record taken on
 a box nobody can log into.  `report` keeps the head AND the tail of both streams and pulls the ranks' own tracebacks (tagged by
 bench.py's __main__) to the front; `run_ranks` launches bench.py under torch.distributed.run the way the driver does, pinned to
-the loopback, with one more attempt on a fresh port when a launch failed."""
+the loopback, once: a failed launch is reported, never started again (the ranks hold the GPU, and a launch that failed may have
+left the device in a state no further program should meet)."""
 import os
 import socket
 import subprocess
@@ -47,18 +48,9 @@ def run_bench(args, timeout=600, env=None):
                           env=env or dict(os.environ))
 
 
-def run_ranks(nproc, bench_args, timeout=600, attempts=2, **env_extra):
+def run_ranks(nproc, bench_args, timeout=600, **env_extra):
     """`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...` (the
-    driver's command line).  A failed launch gets ONE more attempt on another port (rendezvous trouble, a port taken between
-    probing and binding); every failed attempt's full report is kept for the assertion message.
-    Returns (CompletedProcess of the last attempt, [reports of the failed attempts])."""
-    failed = []
-    out = None
-    for attempt in range(attempts):
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
-               "--master-port", str(free_port()), os.path.join(ROOT, "bench.py")] + list(bench_args)
-        out = subprocess.run(cmd, env=loopback_env(**env_extra), cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-        if out.returncode == 0:
-            break
-        failed.append(report(out, f"attempt {attempt + 1}"))
-    return out, failed
+    driver's command line).  Returns the CompletedProcess; `report` makes its failure readable."""
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
+           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py")] + list(bench_args)
+    return subprocess.run(cmd, env=loopback_env(**env_extra), cwd=ROOT, capture_output=True, text=True, timeout=timeout)

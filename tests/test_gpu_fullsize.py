@@ -135,3 +135,34 @@ def test_bench_strong_mode_is_one_32_channel_stream():
     assert "STRONG" in d["config"]["workload"] and d["config"]["fir_kernel"] == "mfma-i8 (fixed point)" and d["roofline"]["frac"] <= 1.0
     per_step = d["value"] * 1e6 * d["ms_per_step"] * 1e-3
     assert abs(per_step - 262144 * 32 * 48000 / 44100) / per_step < 0.01
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the headline's last timed step returned, as its caller received it — the same bits as the same W + K
+    calls of a fresh stream on the same input, made here in this process (the timed region starts where the stream started, whatever
+    the time-bounded pre-roll did), so that two runs, and two builds, can be compared output for output"""
+    import json
+    import os
+    torch = pytest.importorskip("torch")
+    import bench
+    from _spawn import run_bench, report
+    block, warmup, steps = 262144, 2, 3
+    out = run_bench(["--steps", str(steps), "--warmup", str(warmup), "--block-frames", str(block), "--preroll-ms", "20", "--no-cpu-baseline",
+                     "--no-other-configs", "--dump-outputs", str(tmp_path)])
+    assert out.returncode == 0, report(out)
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == steps and sorted(os.listdir(tmp_path)) == ["output.npy", "output_counts.npy"]
+    y = np.load(tmp_path / "output.npy")
+    used, made = (int(v) for v in np.load(tmp_path / "output_counts.npy"))
+    assert y.dtype == np.float32 and y.shape == (made, C) and used == block
+    assert abs(d["value"] * 1e6 * d["ms_per_step"] * 1e-3 / (made * C) - 1.0) < 0.01
+    rs = A.Resampler(C, T, T, 0.0, A.BLACKMAN_HARRIS | A.SUBSAMPLE_INTERPOLATE)
+    rs.advance(T / 2.0)
+    rs.set_stream(torch.cuda.current_stream().cuda_stream)
+    d_in = torch.from_numpy(bench.stream_slice(block, 0, C)).cuda()
+    cap = int(math.floor((block + T // 2) * RATIO + 10))
+    d_out = torch.empty(cap, C, device="cuda")
+    for _ in range(warmup + steps):
+        got = rs.process_device(d_in, block, d_out, cap, RATIO)
+    assert tuple(got) == (used, made)
+    assert np.array_equal(d_out[:made].cpu().numpy().view(np.uint32), y.view(np.uint32))

@@ -1377,8 +1377,9 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
  * plans every context's call on the host exactly as the single call does, gathers those the general kernel would run
  * (any ratio per stream, default or EXTEND mode, ordinary call, on the stream of cxts [0]) into one launch per kernel
  * variant — each stream cut into the tiles its own launch would use, so the samples are identical — and simply makes
- * the remaining calls (flushes, strict mode, endpoint extrapolation, calls big enough for the matrix-core path, other
- * streams) one by one.  results [i] is what resampleProcessInterleavedDevice (cxts [i], ...) would have returned. */
+ * the remaining calls (flushes, strict mode, endpoint extrapolation, calls big enough for the matrix-core path, contexts
+ * under the cut-invariant policy, other streams) one by one.  results [i] is what resampleProcessInterleavedDevice
+ * (cxts [i], ...) would have returned. */
 static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, int cap, double ratio, void *lead_stream,
                        ArtFirArgs *a, ArtSegTable *tab, ResampleResult *res, ArtamdPosition *trial)
 {
@@ -1429,6 +1430,10 @@ static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, 
         tab->base [s] = hip->segs [s].base_offset;
     }
     a->n_begin = hip->segs [0].first_output; a->n_end = res->output_generated;
+
+    /* the cut-invariant policy: every launch of a rational-ratio stream anchored on its canonical period, or counted where it cannot be — the
+     * single call decides that, with the context's kept rows (a call shorter than one period is the matrix path's only with them) */
+    if (hip->kernel_pref == ART_KERNEL_INVARIANT && a->period_out && a->mode == ART_MODE_FAST) return 0;
 
     /* would the single call take the matrix-core path?  (it has its counters and scratch whenever the ratio is
      * rational, the mode default and the kernel not pinned: stand-ins suffice for the question) */

@@ -72,7 +72,9 @@ void resampleHipSetKernel (Resample *cxt, int which);
  * arithmetic is chosen per STREAM: every launch of a rational-ratio stream — big, small, shorter than one period, planar or interleaved — runs on the
  * f32 matrix-core streaming kernel, un-split, anchored on the stream's canonical period (an output sits in the same tile row, on the same K chunks
  * and flush points whichever call brought it), and the outputs only a flush can make (the stream's last T/2 x ratio) on the general kernel, whose
- * outputs never depend on the cut either: the same bits for ANY cut into calls, host or device buffers.  A launch that cannot run anchored (a
+ * outputs never depend on the cut either: the same bits for ANY cut into calls, host or device buffers.  (Not yet for the flush of a
+ * stream whose phases do not fit its filters: its interpolating position accumulates each call's rounding, and the flush is evaluated
+ * there — a few samples differ in the last place with the cut; tests/test_gpu_cut_invariance.py.)  A launch that cannot run anchored (a
  * nearest-filter stream with a slot on a half step, a device buffer not aligned to 16 bytes / one frame, a call of several million frames whose
  * position drift exceeds the kernels' tolerance) is given to the general kernel and COUNTED: resampleHipCutInvariantFallbacks () == 0 says the
  * guarantee held for every output so far.  Equivalent: resampleHipSetKernel (cxt, 9), ARTAMD_KERNEL=9.
@@ -116,7 +118,8 @@ ResampleResult resampleProcessAndFlushInterleavedDevice (Resample *cxt, const ar
  * would have produced.  Contexts whose call the general kernel runs (any ratio per context, default or EXTEND mode, an
  * ordinary call, on the stream of cxts [0]) share launches — a service with hundreds of small-block streams is
  * launch-bound one call at a time; all other calls (strict mode, endpoint extrapolation, calls large enough for the
- * matrix-core path, contexts on other streams) are simply made one by one.  A context may appear only once.  Asynchronous
+ * matrix-core path, contexts under the cut-invariant policy, contexts on other streams) are simply made one by one —
+ * a policy context's call, of any size, is the single call, anchored or counted as there.  A context may appear only once.  Asynchronous
  * like the single call: counts are returned at once, the samples land on the stream.  Returns 0, or -1 if a launch failed. */
 int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                                            artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,

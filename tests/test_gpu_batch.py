@@ -2,7 +2,8 @@
 driven one call at a time through resampleProcessInterleavedDevice; counts, samples (bit for bit), kernel choice and the
 final flush must agree, whatever mix of contexts is in the batch: free-ratio streams whose ratio moves every call (ASRC),
 fixed-ratio ones, EXTEND mode, and the kinds that cannot share a launch (strict order, endpoint extrapolation, a block big
-enough for the matrix-core path) and are made one by one inside the same batch call."""
+enough for the matrix-core path, a context under the cut-invariant policy — blocks shorter than one period included) and are
+made one by one inside the same batch call."""
 import numpy as np
 import pytest
 
@@ -24,7 +25,12 @@ STREAMS = [
     (2, 64, 64, BH | IN | A.EXTRAPOLATE_ENDPOINTS, None, 1.25, 900),                    # one by one: extrapolation
     (8, 988, 160, BH | LP, (44100.0, 48000.0), 0.0, 62000),                              # big blocks: matrix-core path
     (9, 16, 7, BH | IN, None, 3.7, 400),
+    (2, 380, 380, BH | IN, (44100.0, 48000.0), 0.0, 1800),                            # the cut-invariant policy (blocks below one period too)
+    (8, 988, 988, BH | IN, (96000.0, 44100.0), 0.0, 2500),                            # the policy, period_in 320
 ]
+# contexts under the cut-invariant policy (resampleHipSetCutInvariant), their twins too: inside a batch they are made one by one, so that a
+# call shorter than one period still runs anchored on the stream's canonical period, as the single call does (and is counted where it cannot)
+POLICY = {11: 147, 12: 320}             # index -> input frames of one period
 
 
 def bits(a, width):
@@ -41,21 +47,26 @@ def test_batched_calls_equal_single_calls(width):
     batch, single = [mk(s) for s in STREAMS], [mk(s) for s in STREAMS]
     for r, s in zip(batch + single, STREAMS + STREAMS):
         r.advance(s[1] / 2)
+    for i in POLICY:
+        batch[i].set_cut_invariant(True); single[i].set_cut_invariant(True)
+    rng_p = np.random.default_rng(7 + width)               # (the policy contexts' own draws: the other streams' blocks stay as they were)
     n = len(STREAMS)
     cap_max = [int(s[6] * max(s[5] if s[4] is None else s[4][1] / s[4][0], 1.0) * 1.02 + 4 * s[1] + 64) for s in STREAMS]
     d_out_b = [torch.zeros(c, s[0], device="cuda", dtype=tdt) for c, s in zip(cap_max, STREAMS)]
     d_out_s = [torch.zeros(c, s[0], device="cuda", dtype=tdt) for c, s in zip(cap_max, STREAMS)]
-    kernels_seen = set()
+    kernels_seen, policy_kernels = set(), set()
     for rnd in range(14):
         d_in, n_in, caps, ratios = [], [], [], []
         for i, s in enumerate(STREAMS):
-            k = int(rng.integers(0, s[6])) if rng.integers(0, 6) else int(rng.integers(0, 3))
+            rg = rng_p if i in POLICY else rng
+            k = int(rg.integers(0, s[6])) if rg.integers(0, 6) else int(rg.integers(0, 3))
             if i == 9: k = s[6] - int(rng.integers(0, 100))                # keep that stream's blocks big
-            x = (rng.random((max(k, 1), s[0])) - 0.5).astype(dt)
+            if i in POLICY and rg.integers(0, 2): k = int(rg.integers(1, POLICY[i]))          # half of them shorter than a period
+            x = (rg.random((max(k, 1), s[0])) - 0.5).astype(dt)
             d_in.append(torch.from_numpy(x).cuda()); n_in.append(k)
-            caps.append(cap_max[i] if rng.integers(0, 5) else int(rng.integers(1, 200)))
+            caps.append(cap_max[i] if rg.integers(0, 5) else int(rg.integers(1, 200)))
             base = s[5] if s[4] is None else s[4][1] / s[4][0]
-            ratios.append(base * (1 + rng.uniform(-3e-4, 3e-4)) if s[4] is None and rng.integers(0, 2) else base)
+            ratios.append(base * (1 + rg.uniform(-3e-4, 3e-4)) if s[4] is None and rg.integers(0, 2) else base)
         got = B.process_batch_device(batch, d_in, n_in, d_out_b, caps, ratios)
         for i in range(n):
             u, g = single[i].process_device(d_in[i], n_in[i], d_out_s[i], caps[i], ratios[i])
@@ -64,7 +75,13 @@ def test_batched_calls_equal_single_calls(width):
             assert batch[i].last_kernel() == single[i].last_kernel(), (rnd, i)
             assert batch[i].state() == single[i].state(), (rnd, i)
             kernels_seen.add((i, single[i].last_kernel()))
+            if i in POLICY and g:
+                policy_kernels.add((i, batch[i].last_kernel()))
     assert (9, 2) in kernels_seen          # the big-block stream did take the matrix-core path inside the batch call
+    for i in POLICY:                       # (the policy contexts: as their twins — and, in the 4-byte build, every call anchored on the matrix cores)
+        assert batch[i].cut_invariant_fallbacks() == single[i].cut_invariant_fallbacks(), i
+        if width == 32:
+            assert batch[i].cut_invariant_fallbacks() == 0 and {k for j, k in policy_kernels if j == i} == {2}, (i, policy_kernels)
     # the contexts are interchangeable afterwards: flush both sides one by one
     for i, s in enumerate(STREAMS):
         ub, gb, yb = batch[i].process(None, 3 * s[1], STREAMS[i][5] or 1.0, flush=True)

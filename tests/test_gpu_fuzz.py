@@ -126,12 +126,17 @@ def test_random_session_fast_is_scale_free(seed, kernel):
         # their spacing doubles.  There a handful of samples per million reach up to twice the bar — the f32 matrix kernels at 7e-6, the
         # reference's own float loop at 3.4e-6 (worst 1.94 x), the library's own choice at 1e-7 over 300 sessions / 8.2 M samples at this level
         # (tools/micro/fuzz_stats.py, profiles/r6_fuzz_stress.txt) — so WHICH seeded session holds one changes with any change of the last
-        # bits (round 6: the anchoring of multi-period tilings moved one into seed 17).  Held to: nothing beyond 2 x the bar, at most 3 samples
-        # (or 3e-5 of the session's) beyond 1 x.
+        # bits (round 6: the anchoring of multi-period tilings moved one into seed 17).  The pinned f32 matrix preferences (2, 6, 8) are held
+        # to what the reference's own float loop does there: nothing beyond 2 x the bar, at most 3 samples (or 3e-5 of the session's) beyond
+        # 1 x.  The library's own choice (0) is held to its record — 1 sample in 8.2 M outside, at 1.50 x: at most 1 sample beyond the bar and
+        # none beyond 1.6 x — so that the relaxed bound cannot hide a regression of the default path.
         e = np.abs(y.astype(np.float64) - yo.astype(np.float64)) / unit
         tol = 2.0 ** -23 * np.maximum(1.0, np.abs(yo.astype(np.float64) / unit))
         outside = int((e > tol).sum())
-        assert float((e / tol).max()) <= 2.0 and outside <= max(3, int(3e-5 * e.size)), (level, worst, rms, outside)
+        if kernel == 0:
+            assert float((e / tol).max()) <= 1.6 and outside <= 1, (level, worst, rms, outside)
+        else:
+            assert float((e / tol).max()) <= 2.0 and outside <= max(3, int(3e-5 * e.size)), (level, worst, rms, outside)
     else:
         assert ok, (level, worst, rms)
 

@@ -3,7 +3,9 @@ period of its stream, and every later launch runs anchored on that period (its f
 call by call over streams of equal and unequal blocks, both numeric forms of the rows (interpolating / nearest filter with pass-through
 slots), every place of a launch inside its period and inside its 4-frame blocks, short periods taken several at a time, position jumps
 that leave the lattice, resets, flushes, channel groups; and against the same stream with ARTAMD_ROWS_CACHE=0 (rows rebuilt by every
-launch from its own positions): the first call bit for bit, the others within a fraction of the bar."""
+launch from its own positions): the first call bit for bit, the others within a fraction of the bar.  Nearest-filter streams whose slots
+sit exactly on half filter steps never run on kept rows (nor, under the cut-invariant policy, anchored: counted), against a control
+without ties that always does."""
 import json, os, subprocess, sys
 
 import numpy as np
@@ -166,3 +168,67 @@ for src, dst, block in ((96000, 44100, 1048576), (96000, 44100, 300000), (48000,
             assert [f[0] for f in fixed] == ["on"] * 9 and [f[2] for f in fixed] == ["BUILD"] + ["hit"] * 8, fixed
         else:
             assert [k for k, r in f32] == ["1"] * 9 and [r for k, r in f32] == ["0"] + ["1"] * 8, f32
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Nearest-filter streams whose slots sit EXACTLY on half filter steps: 44.1 -> 48 kHz is 160 outputs per 147 input frames, and with F = 80
+# filters an output's filter position is (147 n mod 160) / 2 steps past its frame — every odd slot of the period is a tie, rounded (floor (x +
+# 0.5)) whichever way the last bits of its position fall.  Such a slot has no one canonical row: the matrix kernels' launch test
+# (mfma_launch_is_regular) keeps those launches off the streaming kernels and their kept rows, and the rows the one-tile kernel builds from
+# its own positions round each tie as the oracle does.  A tie rounded the other way is filtered with the neighbouring row: orders of
+# magnitude beyond the bar.  F = 32 (a slot (147 n mod 160) / 5 steps on: never a half) is the control: no ties, every launch on kept rows.
+# ------------------------------------------------------------------------------------------------------------------------
+TIE_BLOCKS = (150001, 120000, 160007, 99999, 170000, 140003, 130000)      # 970,010 input frames, ~1.06 M outputs: positions drift
+TIE_STREAMS = [
+    # (channels, taps, filters, flags, fixed-ratio form)
+    (2, 380, 80, BH, False),
+    (8, 988, 80, BH | LOWPASS, False),
+    (2, 380, 80, BH, True),               # resampleFixedRatioInit: 160 phases do not fit 80 filters — the stream stays nearest-filter with F = 80
+]
+TIE_CONTROLS = [(ch, T, 32, fl, fx) for ch, T, F, fl, fx in TIE_STREAMS]
+
+
+def _tie_outputs(stream, make):
+    ch, T, F, flags, fixed = stream
+    r = make(ch, T, F, flags, (44100.0, 48000.0, 0) if fixed else None)
+    c = r.c
+    assert (c.numFilters if hasattr(c, "numFilters") else c.filters) == F and not (flags & INTERP)      # (the resolved count: still nearest filter, still F filters)
+    r.advance(T / 2)
+    x, _ = noise(sum(TIE_BLOCKS) * ch, state=(ch * 1000 + T + F) | 1)
+    x = x.reshape(-1, ch)
+    pos = 0
+    for n in TIE_BLOCKS:
+        u, g, y = r.process(x[pos:pos + n], int(n * 48000 / 44100) + 4000, 0.0 if fixed else 48000 / 44100)
+        assert u == n
+        pos += n
+        yield r, np.array(y).copy()
+
+
+@pytest.mark.parametrize("stream", TIE_STREAMS + TIE_CONTROLS, ids=lambda s: f"{s[0]}ch_{s[1]}x{s[2]}_{'fixed' if s[4] else 'free'}")
+def test_nearest_filter_slots_on_half_steps(stream):
+    ties = stream[2] == 80
+    want = [y for _, y in _tie_outputs(stream, lambda ch, T, F, fl, fx: OracleResampler(ch, T, F, 0.0, fl | PRECISE, fixed=fx))]
+    assert sum(len(y) for y in want) >= 1000000
+    for pref in (0, 2, 6, 9):
+        def make(ch, T, F, fl, fx):
+            r = HipResampler(ch, T, F, 0.0, fl, fixed=fx, kernel=pref if pref != 9 else 0)
+            if pref == 9:
+                r.set_cut_invariant(True)
+            return r
+        kinds, fallbacks, handed = [], [], []
+        for i, (r, y) in enumerate(_tie_outputs(stream, make)):
+            assert y.shape == want[i].shape, (pref, i, y.shape, want[i].shape)
+            ok, worst, rms = tolerance_ok(y, want[i])
+            assert ok, (pref, i, worst, rms)
+            kinds.append(int(r.last_kernel())); fallbacks.append(int(r.cut_invariant_fallbacks())); handed.append(int(r.handed_back()))
+        calls = len(TIE_BLOCKS)
+        if not ties:                          # every call on the matrix kernels' kept rows, under the policy too: nothing handed back, nothing counted
+            assert kinds == [2] * calls and fallbacks == [0] * calls and handed == [0] * calls, (pref, kinds, fallbacks, handed)
+        elif pref == 9:
+            # the policy runs anchored launches only, and a launch with a slot on a half step is not regular (mfma_launch_is_regular): every call is
+            # the general kernel's — whose outputs do not depend on the cut either — and is counted, one launch per call
+            assert kinds == [1] * calls and fallbacks == list(range(1, calls + 1)) and handed == [0] * calls, (kinds, fallbacks, handed)
+        else:
+            # not regular, so not the streaming kernels and not the kept rows: the one-tile matrix kernel, which builds its rows from the launch's own
+            # positions and evaluates every output off its slot's pattern (the ties, rounded the other way in some period) at its exact position
+            assert kinds == [2] * calls and fallbacks == [0] * calls and all(h > 0 for h in handed), (pref, kinds, fallbacks, handed)

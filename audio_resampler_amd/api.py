@@ -29,7 +29,7 @@ def _bind(width):
     smp_np = np.float64 if width == 64 else np.float32
     smp_torch = "float64" if width == 64 else "float32"         # torch dtype name for device tensors
     LIB_PATH = os.environ.get("ARTAMD_LIB64" if width == 64 else "ARTAMD_LIB") or \
-        os.path.join(HERE, "libartamd64.so" if width == 64 else "libartamd.so")     # ARTAMD_LIB*: ablation builds only
+        os.path.join(HERE, "libartamd64.so" if width == 64 else "libartamd.so")     # ARTAMD_LIB*: A/B of two builds only
     f32p = C.POINTER(smp_c)                                      # (name kept from the 4-byte build)
     u8p = C.POINTER(C.c_ubyte)
 

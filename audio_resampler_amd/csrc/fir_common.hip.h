@@ -197,8 +197,6 @@ static inline int artfir_period_multiple (int P, int rows)
 {
     const int tiles = (P + rows - 1) / rows;
     if (tiles * rows * 100 <= P * 115) return 1;
-    static const bool off = [] { const char *e = getenv ("ARTAMD_PERIOD_MULTIPLE"); return e && *e == '0'; } ();     // (A/B runs)
-    if (off) return 1;
     {   // (a multiple that fills whole tiles, if a small one does)
         int a = P, b = rows;
         while (b) { const int t = a % b; a = b; b = t; }

@@ -68,8 +68,7 @@ size_t arthip_fir_pad_bytes (const ArtFirArgs *a, unsigned int outputs)
 // 0: not for this launch (the caller goes on as before); else artfir_matrix's return value for the whole launch
 static int fir_in_groups (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, hipStream_t st)
 {
-    static const bool off = [] { const char *e = getenv ("ARTAMD_NO_GROUPS"); return e && *e && *e != '0'; } ();      // (A/B runs: the generic matrix kernel as before)
-    if (off || !a->pad || !channels_irregular (a->C) || a->in_pitch || a->out_pitch || (a->mode & 3) != ART_MODE_FAST || (!a->in && a->in_frames > 0)) return 0;
+    if (!a->pad || !channels_irregular (a->C) || a->in_pitch || a->out_pitch || (a->mode & 3) != ART_MODE_FAST || (!a->in && a->in_frames > 0)) return 0;
     if (!artfir_takes_matrix_path (a, segs, kernel_pref)) return 0;
     const unsigned int outs = a->n_end - a->n_begin;
     if (arthip_fir_pad_bytes (a, outs) > a->pad_bytes) return 0;

@@ -10,7 +10,7 @@ namespace {
 
 constexpr int GEN_THREADS = 256;
 // (outputs per workgroup tile at most: 32 until round 6 — three passes of the four waves amortise a tile's positions, staging and barriers better than two, four
-// lose again: tools/micro/general_tile_sweep.sh, profiles/r6_config_e.txt.  An output's bits do not depend on its tile.)
+// lose again: profiles/r6_config_e.txt.  An output's bits do not depend on its tile.)
 constexpr int GEN_MAX_TILE = 48;
 
 // General kernel: one workgroup per tile of consecutive output frames; the tile's input span is
@@ -70,7 +70,7 @@ __device__ __forceinline__ void fir_general_body (const ArtFirArgs &a, const Art
     const int lin_lo = s_ip [0] - half + 1;
     const int span = s_ip [cnt - 1] + half + 1 - lin_lo;
 
-    // LEAN == 2 (round 6, stereo streams; tools/micro/general_lean_first.sh): the lean loop with the FIRST round's coefficient loads of the wave's first output issued
+    // LEAN == 2 (round 6, stereo streams): the lean loop with the FIRST round's coefficient loads of the wave's first output issued
     // before the tile's span is staged — they need the filter index only, so that trip to the L2 and the staging's overlap; 2 x R registers, not the 2 x steps
     // of the all-at-once form that lost its occupancy (profiles/r6_config_e.txt).  Same taps, same order: same bits.
     constexpr int RL = CG >= 2 ? 3 : 6;
@@ -453,10 +453,6 @@ bool general_geometry (const ArtFirArgs &a, int *tile_out, size_t *lds_out, dim3
     const int max_span = lds_budget / ((int) sizeof (art_s) * CG);
     int tile = (int) floor ((max_span - a.T - 3) * a.ratio);
     if (tile > GEN_MAX_TILE) tile = GEN_MAX_TILE;
-    {   // (tile-size sweeps: tools/micro/general_tile_sweep.sh)
-        static const int t_env = [] { const char *e = getenv ("ARTAMD_GENERAL_TILE"); return e && *e ? atoi (e) : 0; } ();
-        if (t_env > 0 && t_env < tile) tile = t_env;
-    }
     // small calls: prefer many small tiles (each wave walks its tile's outputs serially, so latency ~ tile/4
     // outputs) over staging efficiency, until there are about four workgroups per CU
     // (`crowd` = launches of this size sharing the grid — the batched entry point: many streams fill the chip together, so
@@ -489,15 +485,16 @@ int launch_general (const ArtFirArgs &a, const ArtSegTable &segs, hipStream_t st
     int tile; size_t lds; dim3 grid;
     if (!general_geometry<CG> (a, &tile, &lds, &grid)) return -1;
     const bool precise = (a.mode & 3) == ART_MODE_PRECISE;
-    static const bool pipe_on = [] { const char *e = getenv ("ARTAMD_GENERAL_PIPE"); return !(e && *e == '0'); } ();      // (A/B runs and the bit-identity test)
 
 #define GO(I, P) do { const int gg = general_group (a.T); if (gg == 16) GO_ (I, P, 16); else if (gg == 32) GO_ (I, P, 32); else GO_ (I, P, 64); } while (0)
-    // (ARTAMD_GENERAL_LEAN: 0 pins the plain loop, 1 round 5's lean loop; default 2 = the lean loop, and for STEREO streams its first round's coefficient loads issued
-    // before the staging — config E 12.5 -> 12.0 us a call, stereo interpolating 16.6 -> 16.4; mono loses (68 -> 78 registers: 11.0 against 10.2 us) and keeps 1:
-    // tools/micro/general_lean_first.sh, profiles/r6_config_e.txt)
-    static const int lean_on = [] { const char *e = getenv ("ARTAMD_GENERAL_LEAN"); return e && *e >= '0' && *e <= '2' ? *e - '0' : 2; } ();
-#define GO_(I, P, GG) do { if (CG >= 4 && a.T >= 512 && pipe_on) GO__ (I, P, GG, (CG >= 4), 0); else if (lean_on == 2 && CG == 2 && sizeof (art_s) == 4) GO__ (I, P, GG, false, (CG == 2 && sizeof (art_s) == 4 ? 2 : 0)); \
-        else if (lean_on && CG <= 2) GO__ (I, P, GG, false, (CG <= 2 ? 1 : 0)); else GO__ (I, P, GG, false, 0); } while (0)
+    // The tap loop (every form takes the same taps in the same order: the same bits; fir_general_batch_kernel runs the plain loop).
+    // Four channels and more: the pipelined loop for long filters, the plain loop below 512 taps.  One and two channels: round 5's
+    // lean loop (LEAN 1), and for 4-byte STEREO streams the lean loop with its first round's coefficient loads issued before the
+    // staging (LEAN 2) — config E 12.5 -> 12.0 us a call, stereo interpolating 16.6 -> 16.4; mono loses (68 -> 78 registers: 11.0
+    // against 10.2 us) and keeps 1: profiles/r6_config_e.txt
+    constexpr int LEAN = CG >= 4 ? 0 : CG == 2 && sizeof (art_s) == 4 ? 2 : 1;
+#define GO_(I, P, GG) do { if constexpr (CG >= 4) { if (a.T >= 512) GO__ (I, P, GG, true, 0); else GO__ (I, P, GG, false, 0); } \
+        else GO__ (I, P, GG, false, LEAN); } while (0)
 #define GO__(I, P, GG, PP, LL) do { auto k = fir_general_kernel<CG, I, P, GG, PP, LL>; \
         if (lds > 48 * 1024) (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); \
         hipLaunchKernelGGL (k, grid, dim3 (GEN_THREADS), lds, st, a, segs, tile); } while (0)

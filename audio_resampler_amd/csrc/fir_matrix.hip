@@ -998,7 +998,7 @@ static int matrix_geometry (const ArtFirArgs *a, MfmaGeom &g)
 // columns.  Measured (profiles/r3_split_k_experiment.txt): cutting K does not cut a part's sample fetch (a tile's 16 periods are
 // 147 frames apart: a quarter of the K range still spans 3/4 of the tile's input), so more than two parts lose; two parts win
 // where half the CUs would otherwise idle through a whole K walk (50-110 tiles: the 32,768-frame call of 8 ch x 988 taps,
-// 21.7 -> 16.2 us) and nowhere else.  Kernel preference 8 forces 2 / 4 / 8 parts (tests, experiments: ARTAMD_SPLIT_KS).
+// 21.7 -> 16.2 us) and nowhere else.  Kernel preference 8 forces 2 / 4 / 8 parts (tests).
 // a launch of a channel count the kernels are not compiled for runs in groups of a compiled width (fir_dispatch.hip, fir_in_groups): what
 // its buffers are sized for is the widest group
 static ArtFirArgs widest_group (const ArtFirArgs *a)
@@ -1023,8 +1023,7 @@ static int matrix_split_parts (const ArtFirArgs *a, const MfmaGeom &g, unsigned 
     const double groups = ceil (periods * C / cols), tiles = g.slot_tiles * groups;
     const int nchunks = g.ktot / MF_KC;
     // As many parts as keep an XCD's items within ONE round of its 32 CUs (a tile walked alone is a chain of ~0.6 us a chunk whatever else the chip does;
-    // a second round of items costs more than the parts save), at most four, four chunks a part at least.  Re-fitted in round 5 (tools/micro/split_sweep.sh,
-    // profiles/r5_split_rule.txt): the rule had been "two parts from 50 to 110 tiles" — which left 8 ch x 988 taps at 12,288 - 16,384 frames (ART's block) and
+    // a second round of items costs more than the parts save), at most four, four chunks a part at least.  Re-fitted in round 5 (profiles/r5_split_rule.txt): the rule had been "two parts from 50 to 110 tiles" — which left 8 ch x 988 taps at 12,288 - 16,384 frames (ART's block) and
     // 32 ch at 4,096 unsplit (22.9 / 25.4 us a call where three parts take 19.2 / 19.9) and split 40,960 - 49,152 frames (9 - 11 period groups: two per XCD,
     // 40 items on 32 CUs) into two rounds (29.5 - 30.1 us where the uncut launch takes 23.6).
     // Long filters only: at 14 chunks a tile (380 taps) three parts LOSE 12 % (16.1 against 14.3 us), at 18 (512 taps) 3 %; at 33 (988 taps) they win 16 - 26 %.
@@ -1037,11 +1036,6 @@ static int matrix_split_parts (const ArtFirArgs *a, const MfmaGeom &g, unsigned 
     }
     if (kernel_pref == 8) {                                   // (forced: the library's own parts where it splits, else as many as fill the chip)
         if (ks == 1) ks = tiles * 8 <= 768 ? 8 : tiles * 4 <= 768 ? 4 : 2;
-        static const int k_env = [] { const char *e = getenv ("ARTAMD_SPLIT_KS"); return e && *e ? atoi (e) : 0; } ();
-        if (k_env > 0) ks = k_env;
-    }
-    {   static const int force = [] { const char *e = getenv ("ARTAMD_SPLIT_FORCE_KS"); return e && *e ? atoi (e) : 0; } ();      // (A/B runs)
-        if (force > 0 && kernel_pref != 8) ks = force;         // (clamped below like any other count: four chunks a part at least)
     }
     while (ks > 1 && nchunks / ks < 4) --ks;
     return ks;
@@ -1105,12 +1099,11 @@ size_t artfir_planes_bytes (const ArtFirArgs *a_, unsigned int outputs, int kern
         const double t_f32 = 7.5 + rounds * (0.45 * nchunks + 1.8);
         const double ks = (double) outputs * a->period_in / a->period_out * Cs * 1e-3;       // thousands of input samples of the call
         const double t_fixed = (20.0 + 0.0145 * ks) * (0.68 + 0.32 * a->T / 988.0);
-        static const bool model_off = [] { const char *e = getenv ("ARTAMD_FIXED_MODEL"); return e && *e == '0'; } ();
         // (streams of a compiled width only: others run as several group launches, which the f32 model does not describe; the stream's width, so that its shards agree)
         const bool one_launch = Cs == 4 || Cs == 8 || Cs == 16 || Cs == 32;
         // (fitted, and used, up to 3 M samples a call: beyond, the slab kernel's slope is lower than this line's and the product rule above stands — a first
         // version without the bound sent 8 ch x 380 taps and 16 ch x 512 taps at 1M frames to the f32 kernel: 81.6 against 75.7 and 197 against 178 us)
-        if (!model_off && one_launch && ks <= 3000.0 && t_f32 < 0.92 * t_fixed) return 0;
+        if (one_launch && ks <= 3000.0 && t_f32 < 0.92 * t_fixed) return 0;
     }
     return cgt ? artfir_i8_bytes (a, g, cgt, outputs) : 0;
 }
@@ -1254,8 +1247,7 @@ int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref
             // workgroups per CU and finishes sooner.  (Measured: 4 channels x 1M frames = 139 tiles per XCD: 0.0888 ms, one tile
             // per workgroup 0.0948, two each 0.110; 8 channels = 280 tiles: the same 94 workgroups as equal shares of three.)
             const int resident = 94;
-            int wgs_per_xcd = tiles_per_xcd < resident ? tiles_per_xcd : resident;
-            { static const int k_env = [] { const char *e = getenv ("ARTAMD_TILES_PER_WG"); return e && *e ? atoi (e) : 0; } (); if (k_env > 0) wgs_per_xcd = (tiles_per_xcd + k_env - 1) / k_env; }
+            const int wgs_per_xcd = tiles_per_xcd < resident ? tiles_per_xcd : resident;
             // launches of few tiles: a tile's K range as several work items (fir_mfma_split_kernel)
             const bool fixup = artfir_pass_fixup_wanted (a);
             // (the rule looks at the launch's own outputs: the slots a launch on kept rows computes in front of its first do not count)

@@ -101,10 +101,7 @@ __device__ __forceinline__ int shift_of_peak (unsigned int bits)
 }
 
 constexpr int I8_STAGE_THREADS = 256;     // workgroup of the two staging passes
-#ifndef I8_STAGE_UNITS
-#define I8_STAGE_UNITS 4
-#endif
-constexpr int I8_STAGE_K = I8_STAGE_UNITS;  // units (4 frames of one channel) per staging thread (-DI8_STAGE_UNITS=n: tools/micro/stage_units_ab.sh)
+constexpr int I8_STAGE_K = 4;             // units (4 frames of one channel) per staging thread
 
 // digits of a fixed-point value as one dword: byte 3 = d0 ... byte 0 = d3, each signed
 __device__ __forceinline__ unsigned int digits_of (int q) { return ((unsigned int) q + 0x80808080u) ^ 0x80808080u; }
@@ -689,9 +686,6 @@ void fir_i8_stream_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
 // drain the DMA in flight.
 // ---------------------------------------------------------------------------------------------------
 typedef __attribute__ ((address_space (3))) void *lds_ptr_t;
-#ifndef I8_DMA_BUFS
-#define I8_DMA_BUFS 3
-#endif
 
 template <int CG, bool PASS>
 __global__ __launch_bounds__ (2 * MF_THREADS) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
@@ -700,7 +694,7 @@ void fir_i8_dma_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
     static_assert (CG >= 4 && I8_COLS % CG == 0, "16-byte vectors of 4 channels");
     constexpr int THREADS = 2 * MF_THREADS;
     constexpr int PPW = I8_COLS / CG;
-    constexpr int NBUF = I8_DMA_BUFS, A_BUF = 4096, B_BUF = 16384;
+    constexpr int NBUF = 3, A_BUF = 4096, B_BUF = 16384;
     __shared__ __attribute__ ((aligned (16))) unsigned char As_ [NBUF * A_BUF];
     __shared__ __attribute__ ((aligned (16))) unsigned char Bs_ [NBUF * B_BUF];
 
@@ -939,13 +933,9 @@ constexpr size_t SL_PART_BYTES = (size_t) 8 * 16 * 64 * 16;      // one part of 
 
 struct I8Slab {
     int wgs_per_xcd;                      // W
-    int tail;                             // 0: the run behind the whole rounds is W + (L mod W) tiles (each tile cut in two at most); 1: L mod W tiles, cut into W pieces
     int live [8];                         // tiles of each XCD's list that hold outputs (they are a prefix of the list)
     unsigned char *parts;                 // [xcd][rank][2] parts of SL_PART_BYTES
     unsigned int *arrivals;               // [xcd][SL_MAX_SK][8 waves], zero between launches
-#ifdef I8_SLAB_TRACE
-    long long *trace;                     // (debug build: per workgroup and wave, cycles spent in each phase of the chunk loop)
-#endif
 };
 
 
@@ -989,7 +979,7 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
     int D, S;
     {
         const int R = L / W, rem = L - R * W;
-        D = rem && !sl.tail ? (R > 0 ? R - 1 : 0) : R;
+        D = rem ? (R > 0 ? R - 1 : 0) : R;
         S = L - D * W;
     }
     const int Ct = S * nch, Weff = S ? (W < Ct ? W : Ct) : 1;
@@ -1017,15 +1007,9 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
     // ---- this wave's share of the staging, per 32-tap image: piece `wave` of the rows' 8 KB; of every X plane, 4-tap blocks
     // 2 (wave & 3) and + 1 of column half wave >> 2 (64 lanes = 2 blocks x 32 column quads = 1 KB, lane-linear in the LDS)
     constexpr int VPF = CG / 4;                               // 16-byte vectors per 4-frame block of the stream
-#ifdef I8_ABL_CONTIG     // (TIMING ONLY: every X piece one contiguous kilobyte — what the DMA path delivers when its 64 lanes read consecutive memory)
-    constexpr unsigned int A_STEP = 8192u, B_STEP = 8192u;
-    const int kb = 2 * (wave & 3) + (lane >> 5), colquad = (wave >> 2) * 32 + (lane & 31), m = colquad / VPF, cv = colquad - m * VPF;
-    const unsigned int boff = (unsigned int)(wave * 1024 + lane * 16) + 0u * (unsigned int)(kb + cv);
-#else
     constexpr unsigned int A_STEP = 8192u, B_STEP = (I8_KC / 4) * CG * 4u;
     const int kb = 2 * (wave & 3) + (lane >> 5), colquad = (wave >> 2) * 32 + (lane & 31), m = colquad / VPF, cv = colquad - m * VPF;
     const unsigned int boff = (unsigned int)((m * q.gq4 + kb) * CG + cv * 4) * 4u;           // (the tile's first block sits in the resource base)
-#endif
     const unsigned int a_off = (unsigned int)(wave * 1024 + lane * 16);
     // a column whose period lies d exponent blocks behind the tile's first column stages from that block's own planes: d regions
     // further on, where the same 4-frame block sits d * eb_step blocks earlier
@@ -1090,43 +1074,16 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
         }
         else { f_ra = make_rsrc (nullptr, 0u); f_rb = f_ra; }
     };
-    // (TIMING-ONLY ablation builds, tools/micro/slab_ablation.sh — wrong samples, the schedule with one ingredient taken out:
-    //  I8_ABL_NO_DMA no staging pieces, I8_ABL_NO_READ no LDS operand reads, I8_ABL_NO_MFMA no products, I8_ABL_NO_XCHG no exchange of parts)
-#ifdef I8_ABL_XRES
-    int abl_n = 0;
-#endif
     auto piece = [&] (int buf, int idx) {
-#ifdef I8_ABL_NO_DMA
-        return;
-#endif
         const int im = idx / 5, pc = idx % 5;
         unsigned char *img = smem_ + buf * SL_BUF + im * SL_IMG;
-#ifdef I8_ABL_XRES
-        // (TIMING ONLY, round 6: the staging traffic of an X-RESIDENT tile of 64 slots x 128 columns cut in two along K between the wave groups —
-        // per image-step of 8 x 17 products TWO images of the rows (16 KB less their zero planes) and 1 / 41 of a 107 KB span of X (one 1 KB piece
-        // per wave every third image) instead of 8 + 32 KB.  Wrong samples.)
-        // (I8_ABL_XRES == 2: ONE image of the rows per step — a 256-column resident tile, which no LDS holds: the floor of the idea)
-        if (pc == 0 || (pc == 1 && I8_ABL_XRES == 1)) __builtin_amdgcn_raw_ptr_buffer_load_lds (f_ra, (lds_ptr_t)(img + pc * SL_A_IMG + wave * 1024), 16, (int)(d_va + (unsigned int)(im + 2 * pc) * A_STEP), d_skip [im], 0, 0);
-        else if (pc == 2 && (abl_n++ % 3) == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds (f_rb, (lds_ptr_t)(img + 2 * SL_A_IMG + wave * 1024), 16, (int)(d_vb + (unsigned int) im * B_STEP), 0, 0, 0);
-        return;
-#endif
-#ifndef I8_SLAB_A_AUX
-#define I8_SLAB_A_AUX 0
-#endif
-#ifndef I8_SLAB_X_AUX
-#define I8_SLAB_X_AUX 0
-#endif
-        if (pc == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds (f_ra, (lds_ptr_t)(img + wave * 1024), 16, (int)(d_va + (unsigned int) im * A_STEP), d_skip [im], 0, I8_SLAB_A_AUX);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds (f_rb, (lds_ptr_t)(img + SL_A_IMG + (pc - 1) * 8192 + wave * 1024), 16, (int)(d_vb + (unsigned int) im * B_STEP), pc == 4 ? (d_skip3 [im] ? d_skip3 [im] : 3 * plane_step) : (pc - 1) * plane_step, 0, I8_SLAB_X_AUX);
+        if (pc == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds (f_ra, (lds_ptr_t)(img + wave * 1024), 16, (int)(d_va + (unsigned int) im * A_STEP), d_skip [im], 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds (f_rb, (lds_ptr_t)(img + SL_A_IMG + (pc - 1) * 8192 + wave * 1024), 16, (int)(d_vb + (unsigned int) im * B_STEP), pc == 4 ? (d_skip3 [im] ? d_skip3 [im] : 3 * plane_step) : (pc - 1) * plane_step, 0, 0);
     };
 
-    {   // the two waves of a SIMD share its matrix pipe: left alone they fall into step (both read, then both multiply);
-        // different issue priorities make them alternate instead
-#ifndef I8_SLAB_PRIO
-#define I8_SLAB_PRIO 1
-#endif
-        if (I8_SLAB_PRIO == 1) { if (wave & 4) __builtin_amdgcn_s_setprio (2); else __builtin_amdgcn_s_setprio (0); }
-    }
+    // the two waves of a SIMD share its matrix pipe: left alone they fall into step (both read, then both multiply);
+    // different issue priorities make them alternate instead
+    if (wave & 4) __builtin_amdgcn_s_setprio (2); else __builtin_amdgcn_s_setprio (0);
     const int col = wave * 32 + (lane & 31);
     const int jl = col / CG, c = col - jl * CG;
     // rows' image [plane][16-tap half][row 0..63][16 taps]; X image [plane][column half][4-tap block][column 0..127][4 taps]
@@ -1148,13 +1105,6 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
 #pragma unroll
     for (int idx = 0; idx < 5; ++idx) piece (1, idx);
     int cur = 0;                                              // LDS buffer of the current chunk
-#ifdef I8_SLAB_TRACE
-    long long tr_ [16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, tp_ = (long long) __builtin_readcyclecounter ();
-    const long long tr_begin = tp_, tr_real = (long long) __builtin_amdgcn_s_memrealtime ();
-#define TR(i) do { const long long n_ = (long long) __builtin_readcyclecounter (); tr_ [i] += n_ - tp_; tp_ = n_; } while (0)
-#else
-#define TR(i) do { } while (0)
-#endif
 
     for (int k = 0; k < nseg; ++k) {
         int within, c0, c1, st, j0;
@@ -1181,14 +1131,7 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
         int shift_v = q.shifts [((j0 + jl * q.g) / q.eb_periods) * CG + c];
 
         i32x4 av [2] [4], bv [4];
-#ifdef I8_ABL_NO_READ
-#pragma unroll
-        for (int pn = 0; pn < 4; ++pn) { av [0] [pn] = i32x4 {lane, pn, 3, 4}; av [1] [pn] = i32x4 {lane, pn, 5, 6}; bv [pn] = i32x4 {pn, lane, 7, 8}; }
-#endif
         auto read_image = [&] (int im, int sub) {
-#ifdef I8_ABL_NO_READ
-            if (im >= 0) { asm volatile ("" : "+v" (av [0] [0]), "+v" (av [1] [0]), "+v" (bv [0])); return; }
-#endif
             const unsigned char *Ab = Ab0 + cur * SL_BUF + im * SL_IMG, *Bb = Bb0 + cur * SL_BUF + im * SL_IMG;
             // (only the digit planes this image multiplies: the rows' first plane lives in 4 of 33 images at 988 taps, the second in 24, and the samples'
             // last plane meets nothing else — the CU's LDS is as busy as its matrix pipes (80 KB of DMA writes and 8 waves x 12 KB of operand reads per
@@ -1199,18 +1142,8 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
             if (l0 | l1) {
                 av [0] [1] = *reinterpret_cast<const i32x4 *> (Ab + 2048);
                 av [1] [1] = *reinterpret_cast<const i32x4 *> (Ab + 2048 + 512);
-#if defined (I8_ABL_XRES) && !defined (I8_ABL_XRES_NOALIGN)
-                {
-                    int d5 [5];
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) d5 [i] = *reinterpret_cast<const int *> (Bb + 3 * 8192 + i * 512);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) bv [3] [i] = (int) __builtin_amdgcn_alignbyte ((unsigned int) d5 [i + 1], (unsigned int) d5 [i], (unsigned int)(lane & 3));
-                }
-#else
 #pragma unroll
                 for (int i = 0; i < 4; ++i) bv [3] [i] = *reinterpret_cast<const int *> (Bb + 3 * 8192 + i * 512);
-#endif
                 if (l0) {
                     av [0] [0] = *reinterpret_cast<const i32x4 *> (Ab);
                     av [1] [0] = *reinterpret_cast<const i32x4 *> (Ab + 512);
@@ -1221,31 +1154,15 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
                 av [0] [pn] = *reinterpret_cast<const i32x4 *> (Ab + pn * 2048);
                 av [1] [pn] = *reinterpret_cast<const i32x4 *> (Ab + pn * 2048 + 512);
             }
-#if defined (I8_ABL_XRES) && !defined (I8_ABL_XRES_NOALIGN)
-            // (a column of a resident span starts at any frame: five dwords and four v_alignbyte_b32 per plane instead of four dwords)
-#pragma unroll
-            for (int pn = 0; pn < 3; ++pn) {
-                int d5 [5];
-#pragma unroll
-                for (int i = 0; i < 5; ++i) d5 [i] = *reinterpret_cast<const int *> (Bb + pn * 8192 + i * 512);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) bv [pn] [i] = (int) __builtin_amdgcn_alignbyte ((unsigned int) d5 [i + 1], (unsigned int) d5 [i], (unsigned int)(lane & 3));
-            }
-#else
 #pragma unroll
             for (int pn = 0; pn < 3; ++pn)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) bv [pn] [i] = *reinterpret_cast<const int *> (Bb + pn * 8192 + i * 512);
-#endif
         };
         // the products of one image, and five DMA pieces of the chunk being issued (pieces first .. first + 4 -> buffer `to`) spread
         // between them, one behind every fourth product or so: issued in a burst the pieces of eight waves queue up in front of the
         // CU's one address unit (~20 cycles a piece), and a wave stuck behind them multiplies nothing
         auto products = [&] (int sub, int to, int first) {
-#ifdef I8_ABL_NO_MFMA
-            for (int i = 0; i < 5; ++i) piece (to, first + i);
-            return;
-#endif
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 int n = 0;                                    // products issued so far in this register tile's block
@@ -1286,48 +1203,36 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
         };
 
         for (int ch = c0; ch < c1; ++ch) {
-            TR (0);                                           // (0: everything between chunks — tile set-up, epilogue, exchange)
             // ---- the chunk's first image
             read_image (0, 2 * ch);
             __builtin_amdgcn_sched_group_barrier (0x100, 16, 0);
             products (2 * ch, cur ^ 1, 5);                    // (with the second five pieces of the chunk announced behind the last barrier)
-            TR (4);
             // ---- its second image (a tile's last chunk may have none): operands now, products behind the barrier
             const bool two = 2 * ch + 1 < nsub;
             if (two) read_image (1, 2 * ch + 1);
             asm volatile ("s_waitcnt lgkmcnt(0)" ::: "memory");       // (the chunk has been read: its buffer may be written again)
             asm volatile ("s_waitcnt vmcnt(0)" ::: "memory");         // (this wave's pieces of the next chunk have landed)
             if (ch == c0) asm volatile ("" : "+v" (shift_v));   // (the exponent's load is waited for here)
-            TR (1);                                           // (1: reading the second image, waiting for this wave's pieces)
             __builtin_amdgcn_s_barrier ();
             asm volatile ("" ::: "memory");
-            TR (2);                                           // (2: the barrier)
             next_chunk ();                                    // the stream's next-but-one chunk -> the buffer just read
             // (moving this scalar upkeep in front of the barrier, where the faster waves wait anyway, was measured: + 1 .. 2 us, profiles/r5_slab_kernel_trims.txt)
-            TR (3);                                           // (3: moving the stream on)
             if (two) products (2 * ch + 1, cur, 0);             // (with the first five pieces)
             else {
 #pragma unroll
                 for (int idx = 0; idx < 5; ++idx) piece (cur, idx);
             }
-            TR (5);
             asm volatile ("" ::: "memory");
             cur ^= 1;
         }
 
         // ---- the tile's outputs.  (In flight: the 10 pieces issued between the last products; they stay in flight.)
-        TR (0);
         long long tot [2] [16];
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int r = 0; r < 16; ++r) tot [h] [r] = i8_total (acc [h] [0] [r], acc [h] [1] [r], acc [h] [2] [r], acc [h] [3] [r], acc [h] [4] [r]);
-        TR (9);
-#ifdef I8_ABL_NO_XCHG
-        if (false) {
-#else
         if (c0 != 0 || c1 != nch) {
-#endif
             // ---- part of a tile: leave the sums, count the arrival; the last wave to arrive goes on with everybody's
             constexpr int COHERENT = 1 | 16;                 // (aux bits of the raw buffer instructions on gfx940+: sc0, sc1)
             const int t = within - D * W;
@@ -1363,7 +1268,7 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
                 if (lane == 0) before = __hip_atomic_fetch_add (count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 before = (unsigned int) __builtin_amdgcn_readfirstlane ((int) before);
             }
-            if (before != (unsigned int)(r_last - r_first)) { TR (10); continue; }
+            if (before != (unsigned int)(r_last - r_first)) continue;
             if (lane == 0) __hip_atomic_store (count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // (for the next launch)
             for (int rr = r_first; rr <= r_last; ++rr) {
                 if (rr == rank) continue;
@@ -1379,7 +1284,6 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
                 }
             }
         }
-        TR (10);
         // rows carry 30 fraction bits, this lane's channel 2^shift in its period's exponent block; the total is in units of
         // 2^-30 x 2^-shift x 2^16 (the class weights 256^(4 - s) are relative to the least significant kept class): scaled by
         // 2^(-14 - shift), a power of two, and rounded ONCE to float
@@ -1409,7 +1313,6 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
         // four lanes of a quad hold four consecutive channels: a 4 x 4 transposition inside the quad (two DPP exchanges) leaves every
         // lane one frame's four channels, 16 contiguous bytes — eight 16-byte stores per tile instead of 32 dword stores, whole
         // 128-byte lines per eight lanes of an 8-channel stream.
-        TR (11);
         {
             int lane_e = lane;                                // (an opaque copy: see q_off below)
             asm volatile ("" : "+v" (lane_e));
@@ -1449,26 +1352,19 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
                     __builtin_amdgcn_raw_buffer_store_b128 (v, rs_out, (int) off, 0, 0);
                 }
         }
-        TR (12);
     }
     asm volatile ("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef I8_SLAB_TRACE
-    TR (0);
-    tr_ [6] = tp_ - tr_begin; tr_ [7] = (long long) total; tr_ [15] = (long long) __builtin_amdgcn_s_memrealtime () - tr_real;
-    if (lane == 0) for (int i = 0; i < 16; ++i) sl.trace [((size_t) blockIdx.x * 8 + wave) * 16 + i] = tr_ [i];
-#endif
-#undef TR
 }
 
 
 } // namespace
 
 // Slabs (fir_i8_slab_kernel: tiles of 64 slots x 256 columns, one workgroup per CU, tiles cut to the launch) for streams whose
-// 4-frame blocks are whole 16-byte vectors.  ARTAMD_I8_SLAB=0 (or ARTAMD_I8_DMA=0) switches them off — the 32-slot kernels then
-// run every launch, and periods are taken so as to fill THEIR tiles (A/B runs; the results are the same bits either way).
+// 4-frame blocks are whole 16-byte vectors.  ARTAMD_I8_SLAB=0 switches them off — the 32-slot kernels then run every launch, and
+// periods are taken so as to fill THEIR tiles (A/B runs; the results are the same bits either way).
 bool artfir_i8_slab_enabled ()
 {
-    static const bool on = [] { const char *e = getenv ("ARTAMD_I8_SLAB"); const char *d = getenv ("ARTAMD_I8_DMA"); return !(e && *e == '0') && !(d && *d == '0'); } ();
+    static const bool on = [] { const char *e = getenv ("ARTAMD_I8_SLAB"); return !(e && *e == '0'); } ();
     return on;
 }
 // slabs per XCD from which a launch is given to the slab kernel (below — measured, tools/micro/slab_sizes.sh — more, smaller tiles
@@ -1707,8 +1603,7 @@ int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const Mfm
     int ep = ++launches;
     if (ep <= 0) { launches = 1; ep = 1; }                             // (the flag word is zero when the buffer is allocated)
     q.epoch = ep;
-    static const bool dma = [] { const char *e = getenv ("ARTAMD_I8_DMA"); return !(e && *e == '0'); } ();
-    if (a->fixed_out) { a->fixed_out [0] = ep; a->fixed_out [1] = q.tiles * q.g * q.tr; a->fixed_out [2] = q.ktot / I8_KC; a->fixed_out [3] = q.tr == 64 ? 3 : (dma && cgt >= 4) ? 2 : 1; }
+    if (a->fixed_out) { a->fixed_out [0] = ep; a->fixed_out [1] = q.tiles * q.g * q.tr; a->fixed_out [2] = q.ktot / I8_KC; a->fixed_out [3] = q.tr == 64 ? 3 : cgt >= 4 ? 2 : 1; }
 
     {   // block of the first tile's window start: the launch's first output's position (the reference's arithmetic, host_locate), or the
         // canonical period's first slot carried to this launch
@@ -1734,10 +1629,9 @@ int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const Mfm
     // workgroups of the same grid, each striding the XCD's tile list; the last, partly filled round then runs with one
     // workgroup per CU and its tiles finish sooner.  (Equal shares — 56 workgroups x 5 tiles for the headline's 280 — kept 8
     // slots idle for the whole launch: 0.1078 ms, 64 workgroups 0.1039, 62 0.1029; 4 and 32 channels, 256k..1M frames,
-    // 96k -> 44.1k: 3..9 % the same way.  ARTAMD_I8_WGS overrides, for experiments.)
+    // 96k -> 44.1k: 3..9 % the same way.)
     const int resident = 62;
-    int wgs_per_xcd = tiles_per_xcd < resident ? tiles_per_xcd : resident;
-    { static const int k_env = [] { const char *e = getenv ("ARTAMD_I8_WGS"); return e && *e ? atoi (e) : 0; } (); if (k_env > 0 && k_env < tiles_per_xcd) wgs_per_xcd = k_env; }
+    const int wgs_per_xcd = tiles_per_xcd < resident ? tiles_per_xcd : resident;
     // (big launches of the nearest-filter mode: the plain instantiation and the pass-through pass behind it, artfir_pass_fixup_wanted)
     const bool fixup = artfir_pass_fixup_wanted (a);
     const bool pass = !a->interpolate && !a->lowpass && !fixup;
@@ -1745,7 +1639,6 @@ int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const Mfm
         // slabs: one eight-wave workgroup per CU (all of its LDS), which also rolls the history and carries the stand-by
         I8Slab sl;
         sl.wgs_per_xcd = SL_WGS;
-        { static const int tail_env = [] { const char *e = getenv ("ARTAMD_I8_SLAB_TAIL"); return e && *e ? atoi (e) : 0; } (); sl.tail = tail_env; }
         sl.parts = q.parts;
         sl.arrivals = (unsigned int *)((char *) a->planes + ART_I8_FLAG_BYTES);
         {   // tiles of each XCD's list that hold outputs: a prefix of the list (a tile holds outputs iff its first column's period does)
@@ -1763,37 +1656,12 @@ int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const Mfm
             }
         }
         const dim3 wgrid ((unsigned int)(8 * SL_WGS));
-#ifdef I8_SLAB_TRACE
-        static long long *d_trace = nullptr;
-        if (!d_trace) (void) hipMalloc (&d_trace, (size_t) 8 * SL_WGS * 8 * 16 * sizeof (long long));
-        sl.trace = d_trace;
-#endif
 #define I8_SLAB(CGT) do { if (pass) hipLaunchKernelGGL ((fir_i8_slab_kernel<CGT, true>), wgrid, dim3 (SL_THREADS), 0, st, *a, g, q, sl); \
                           else hipLaunchKernelGGL ((fir_i8_slab_kernel<CGT, false>), wgrid, dim3 (SL_THREADS), 0, st, *a, g, q, sl); } while (0)
         switch (cgt) { case 32: I8_SLAB (32); break; case 16: I8_SLAB (16); break; case 8: I8_SLAB (8); break; default: I8_SLAB (4); }
 #undef I8_SLAB
         if (a->ev_stop) arthip_event_record (a->ev_stop, (void *) st);
         if (fixup && artfir_pass_fixup (a, g, st)) return -1;
-#ifdef I8_SLAB_TRACE
-        {
-            static int n_launch = 0;
-            if (++n_launch == 40) {
-                static long long h [8 * SL_WGS * 8 * 16];
-                (void) hipStreamSynchronize (st);
-                (void) hipMemcpy (h, d_trace, sizeof (h), hipMemcpyDeviceToHost);
-                const char *names [16] = { "tile set-up", "wait own pieces", "barrier", "stream on", "image 0 (+ pieces)", "image 1", "whole kernel", "chunks",
-                                           "drain before outputs", "totals", "exchange", "round", "stores", "-", "-", "whole kernel (100 MHz)" };
-                for (int wv = 0; wv < 8; wv += 4) {
-                    fprintf (stderr, "slab trace, wave %d, mean over %d workgroups (cycles; per chunk in brackets):\n", wv, 8 * SL_WGS);
-                    double chunks = 0; for (int b = 0; b < 8 * SL_WGS; ++b) chunks += (double) h [((size_t) b * 8 + wv) * 16 + 7];
-                    for (int i = 0; i < 16; ++i) {
-                        double sum = 0, mx = 0; for (int b = 0; b < 8 * SL_WGS; ++b) { const double v = (double) h [((size_t) b * 8 + wv) * 16 + i]; sum += v; if (v > mx) mx = v; }
-                        fprintf (stderr, "   %-20s %10.0f  max %10.0f  [%8.1f]\n", names [i], sum / (8 * SL_WGS), mx, sum / chunks);
-                    }
-                }
-            }
-        }
-#endif
         return 1;
     }
     const dim3 sgrid ((unsigned int)(8 * wgs_per_xcd) + roll_blocks);
@@ -1801,9 +1669,10 @@ int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const Mfm
                         else hipLaunchKernelGGL ((fir_i8_stream_kernel<CGT, false>), sgrid, dim3 (2 * MF_THREADS), 0, st, *a, g, q, wgs_per_xcd); } while (0)
 #define I8_DMA(CGT) do { if (pass) hipLaunchKernelGGL ((fir_i8_dma_kernel<CGT, true>), sgrid, dim3 (2 * MF_THREADS), 0, st, *a, g, q, wgs_per_xcd); \
                          else hipLaunchKernelGGL ((fir_i8_dma_kernel<CGT, false>), sgrid, dim3 (2 * MF_THREADS), 0, st, *a, g, q, wgs_per_xcd); } while (0)
-    // (ARTAMD_I8_DMA=0: the register-staged kernel for every channel count — comparisons; the results are the same bits)
-    if (dma && cgt >= 4) switch (cgt) { case 32: I8_DMA (32); break; case 16: I8_DMA (16); break; case 8: I8_DMA (8); break; default: I8_DMA (4); }
-    else switch (cgt) { case 32: I8_GO (32); break; case 16: I8_GO (16); break; case 8: I8_GO (8); break; case 4: I8_GO (4); break; case 2: I8_GO (2); break; default: I8_GO (1); }
+    // (the register-staged kernel for 1 and 2 channels per column group: the DMA kernel's 16-byte pieces hold 4)
+    if (cgt >= 4) switch (cgt) { case 32: I8_DMA (32); break; case 16: I8_DMA (16); break; case 8: I8_DMA (8); break; default: I8_DMA (4); }
+    else if (cgt == 2) I8_GO (2);
+    else I8_GO (1);
 #undef I8_DMA
 #undef I8_GO
     if (a->ev_stop) arthip_event_record (a->ev_stop, (void *) st);

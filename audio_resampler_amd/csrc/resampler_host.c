@@ -458,8 +458,17 @@ static Resample *init_leaf (int numChannels, int numTaps, int numFilters, double
     cxt->inputIndex = numTaps;
     hip->device = arthip_current_device ();
     // (A/B runs and the PCM-level tests of programs that cannot call resampleHipSetKernel — the reference's own art / artest binaries:
-    // ARTAMD_KERNEL=<n> is the kernel preference every new context starts with, see include/art_hip.h)
-    { const char *env = getenv ("ARTAMD_KERNEL"); if (env && *env) hip->kernel_pref = atoi (env); }
+    // ARTAMD_KERNEL=<n> is the kernel preference every new context starts with, see include/art_hip.h; anything but a documented
+    // preference is ignored, with one warning per process)
+    {
+        const char *env = getenv ("ARTAMD_KERNEL");
+        if (env && *env) {
+            char *end;
+            const long k = strtol (env, &end, 10);
+            if (!*end && (k == 0 || k == 1 || k == 2 || (k >= 5 && k <= 9))) hip->kernel_pref = (int) k;
+            else { static int warned; if (!warned++) fprintf (stderr, "artamd: ARTAMD_KERNEL=%s is not a kernel preference (0, 1, 2, 5-9): ignored\n", env); }
+        }
+    }
     if (private_stream) { hip->stream = arthip_stream_create (); hip->own_stream = hip->stream != NULL; }
 
     /* the bank: shared on the device, a private host copy exposed through the reference's `filters` row-pointer table */
@@ -1723,9 +1732,7 @@ static ResampleResult enqueue_call_layouts (Resample *cxt, const art_s *d_in, lo
      * kernel is 4-7 x slower than the same call interleaved (8 ch x 988 taps, 1M frames: 960 against 140 us).  Such a call goes
      * through the context's interleaved staging buffers — two transposing copies on the device, ~4 % of the call — and so does a
      * call with only one planar side.  (Small calls stay as they are: the general kernel takes planes as they come.) */
-    static int planar_off = -1;
-    if (planar_off < 0) { const char *e = getenv ("ARTAMD_PLANAR_DIRECT"); planar_off = e && *e && *e != '0'; }
-    if ((in_pitch || out_pitch) && !planar_off && nIn > 0 && cap > 0 && d_in && d_out &&
+    if ((in_pitch || out_pitch) && nIn > 0 && cap > 0 && d_in && d_out &&
         ((double) nIn * (hip->stream_channels > cxt->numChannels ? hip->stream_channels : cxt->numChannels) * cxt->numTaps >= 2.0e8 ||       /* (a shard: its whole stream's size) */
          hip->kernel_pref == ART_KERNEL_INVARIANT)) {            /* (the cut-invariant policy: every call, whatever its size, on the same kernel) */
         const int C = cxt->numChannels;
@@ -1877,9 +1884,7 @@ static void host_begin (Resample *cxt, const art_s *input, int in_stride, const 
     TRACE_MARK (2);
     /* small staged calls: the FIR kernels write their output straight into the page-locked buffer (it is mapped into the
      * device's address space; one launch and its dependency gap less than copying it out afterwards) */
-    static long direct_limit = -1;                             /* (ARTAMD_DIRECT_OUT_LIMIT=bytes: A/B runs) */
-    if (direct_limit < 0) { const char *e = getenv ("ARTAMD_DIRECT_OUT_LIMIT"); direct_limit = e && *e ? atol (e) : (long) DIRECT_OUT_LIMIT; }
-    const int direct_out = staged && sizeof (art_s) * out_samples <= (size_t) direct_limit && !hip->nshards;
+    const int direct_out = staged && sizeof (art_s) * out_samples <= DIRECT_OUT_LIMIT && !hip->nshards;
     pend->res = hip->nshards ? sharded_device_call (cxt, hip->d_in, 0, nIn, hip->d_out, 0, cap, ratio)
                              : enqueue_call (cxt, hip->d_in, 0, nIn, direct_out ? hip->h_out : hip->d_out, 0, cap, ratio);
     pend->failed = 0;

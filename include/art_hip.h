@@ -96,7 +96,7 @@ int  resampleHipLastKernel (Resample *cxt);          /* which kernel produced th
  * *pairsPerChunk (may be NULL): digit-pair products issued per 32-tap chunk, 5 .. 13 (5 where both upper digit planes of the rows are zero, + 4 for each that is not).  Synchronises. */
 int  resampleHipLastFixedPoint (Resample *cxt, double *pairsPerChunk);
 /* the form of the fixed-point kernel the last call's last launch was given to: 0 none, 1 fir_i8_stream_kernel (register-staged: 1 and 2
- * channels, ARTAMD_I8_DMA=0), 2 fir_i8_dma_kernel (LDS-DMA staging, 32-slot tiles), 3 fir_i8_slab_kernel (64 x 256 tiles, big launches).
+ * channels), 2 fir_i8_dma_kernel (LDS-DMA staging, 32-slot tiles), 3 fir_i8_slab_kernel (64 x 256 tiles, big launches).
  * All three leave the same bits. */
 int  resampleHipLastFixedPointKernel (Resample *cxt);
 unsigned int resampleHipLastHandedBack (Resample *cxt);   /* outputs the matrix-core kernels evaluated at their own exact position, off their slot's canonical pattern, so far */

@@ -1,7 +1,7 @@
 """Any-ratio streams (BASELINE.json configs[4]: stereo ASRC, nearest filter, a new ratio on every call) on the general kernel: its lean
 tap loop (several steps' loads in flight, no address arithmetic or loop control between them) takes the same taps in the same order as
-the plain loop — same bits, session by session (ARTAMD_GENERAL_LEAN=0 pins the plain loop) — and the stream is held to the oracle like
-every other path."""
+the plain loop — same bits, session by session (the plain loop is the batched entry point's: the helper makes every call twice, once
+on its own and once as a batch of one) — and the stream is held to the oracle like every other path."""
 import json, math, os, subprocess, sys
 
 import numpy as np
@@ -14,18 +14,28 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _sessions(**env):
-    r = subprocess.run([sys.executable, os.path.join(HERE, "_asrc_sessions.py")], env=dict(os.environ, **env), capture_output=True, text=True, timeout=900)
+def _sessions():
+    """(single calls, the same calls as batches of one): one record per session each"""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "_asrc_sessions.py")], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    return out["single"], out["batched"]
 
 
 def test_lean_and_plain_tap_loops_leave_the_same_bits():
-    a, b = _sessions(), _sessions(ARTAMD_GENERAL_LEAN="0")
+    a, b = _sessions()
     assert len(a) == len(b) >= 15
     for sa, sb in zip(a, b):
         assert sa["frames"] == sb["frames"] > 0
         assert sa["sha256"] == sb["sha256"], (sa, sb)
+    # every lean form (one and two channels; interpolating or not, float or double accumulators) ran tiles of more than one pass, so
+    # that a wave's later outputs were compared too, not only its first
+    lean = {}
+    for s in a:
+        if s["form"][0] <= 2:
+            key = tuple(s["form"])
+            lean[key] = lean.get(key, False) or max(s["tiles"]) > s["pass"]
+    assert len(lean) >= 5 and all(lean.values()), lean
 
 
 @pytest.mark.parametrize("interp", [False, True])

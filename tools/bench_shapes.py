@@ -24,5 +24,5 @@ n = 0; t0 = time.perf_counter()
 for _ in range(50): n += step()
 torch.cuda.synchronize(); dt = time.perf_counter() - t0
 ms, launches = rs.read_timing()
-print(f"ch {ch} T {taps} F {rs.L.resampleGetNumFilters(rs.p)} {src}->{dst} interp {interp} block {block} kernel {rs.last_kernel()} pref {kernel} "
-      f"tiles/wg {os.environ.get('ARTAMD_TILES_PER_WG', 'auto')}: {n / dt / 1e6:9.1f} Msamples/s  step {dt / 50 * 1e3:.4f} ms  fir kernel {ms / max(launches, 1):.4f} ms")
+print(f"ch {ch} T {taps} F {rs.L.resampleGetNumFilters(rs.p)} {src}->{dst} interp {interp} block {block} kernel {rs.last_kernel()} pref {kernel}: "
+      f"{n / dt / 1e6:9.1f} Msamples/s  step {dt / 50 * 1e3:.4f} ms  fir kernel {ms / max(launches, 1):.4f} ms")

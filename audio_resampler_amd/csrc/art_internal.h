@@ -71,7 +71,7 @@ typedef struct {
     int n_skip;                          /* matrix kernels on cached rows (below): the launch's tiles start at the cached period's first slot, n_skip
                                           * slots before the launch's first output — those slots of the first period are computed and not stored */
     int segs_truncated;                  /* the launch reaches beyond the segments of its table (a call of more than ART_MAX_SEGS ring epochs
-                                          * handed over whole, arthip_fir_spans_segments): only a kernel that follows the lattice from the
+                                          * handed over whole, ArtFirNeeds.one_launch): only a kernel that follows the lattice from the
                                           * launch's first period may run it — arthip_fir returns -2, nothing enqueued, otherwise */
     /* periodic-phase structure for the MFMA kernel (0 = none): out frame n+period_out sits exactly
      * period_in input frames after out frame n */
@@ -82,18 +82,18 @@ typedef struct {
     unsigned int fix_cap;
     /* device scratch for the MFMA path: per-launch effective rows + canonical slot positions */
     void *scratch; size_t scratch_bytes;
-    /* device memory for the fixed-point matrix kernel's digit planes of one launch (arthip_fir_planes_bytes; NULL: f32 kernels) */
+    /* device memory for the fixed-point matrix kernel's digit planes of one launch (ArtFirNeeds.planes_bytes; NULL: f32 kernels) */
     void *planes; size_t planes_bytes;
     /* the fixed-point kernel's filter rows ACROSS calls (digit planes, masks, the f32 tables of its stand-by): device memory of
-     * arthip_fir_rows_bytes () bytes and a zeroed host block of arthip_fir_rows_cache_bytes () bytes that describes what it holds, both owned
+     * ArtFirNeeds.rows_bytes bytes and a zeroed host block of arthip_fir_rows_cache_bytes () bytes that describes what it holds, both owned
      * by the context (NULL: the rows are rebuilt by every launch, as before round 5).  rows_masks_out (host, optional): where the used
      * set's row masks live on the device (resampleHipLastFixedPoint reads them) */
     void *rows; size_t rows_bytes; void *rows_cache; void **rows_masks_out;
-    /* device memory for the K-split streaming kernel of launches with few tiles (arthip_fir_split_bytes; NULL: unsplit): the first
+    /* device memory for the K-split streaming kernel of launches with few tiles (ArtFirNeeds.split_bytes; NULL: unsplit): the first
      * ART_SPLIT_HEAD_BYTES are arrival counters, zero whenever no launch is in flight (zeroed by the owner when allocated) */
     void *split; size_t split_bytes;
     /* device memory for launches of a channel count the matrix kernels are not compiled for (anything but 1, 2, 4, 8, 16, 32): the
-     * launch runs in groups of up to 32 channels, each copied into a buffer of the next compiled width (arthip_fir_pad_bytes; NULL: the
+     * launch runs in groups of up to 32 channels, each copied into a buffer of the next compiled width (ArtFirNeeds.pad_bytes; NULL: the
      * generic matrix kernel runs such a stream, several times slower) */
     void *pad; size_t pad_bytes;
     /* host, optional, 4 ints filled when the fixed-point kernel is enqueued: the launch's flag value (the first word of
@@ -145,28 +145,29 @@ float arthip_event_elapsed_ms (void *start, void *stop);   /* synchronises on `s
 /* ---- sinc_fir.hip ---- */
 /* returns the kernel actually used (ART_KERNEL_*), <0 on launch failure */
 int arthip_fir (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, void *stream);
-/* bytes a->planes must hold for the fixed-point matrix kernel to run a call of this shape (C, T, H, in_frames, period) making
- * `outputs` frames; 0: the call is not for it (shape, size, kernel preference) */
-size_t arthip_fir_planes_bytes (const ArtFirArgs *a, unsigned int outputs, int kernel_pref);
-/* the fixed-point kernel's rows across the calls of a context (ArtFirArgs.rows / rows_cache): device bytes a call of this shape wants (0: none),
- * size of the host block that describes the device buffer (zeroed by the owner), forgetting what the buffer held (it was replaced), releasing
- * what the host block owns */
-size_t arthip_fir_rows_bytes (const ArtFirArgs *a, unsigned int outputs, int kernel_pref);
+/* What a call's launches need, asked once per call before its buffers exist (the buffer pointers of `call` are not looked at; rows_cache is: the
+ * cut-invariant policy's launches shorter than a period are the matrix path's only with kept rows).  `call` = the call's ArtFirArgs, `first` = its
+ * first segment table (the first ART_MAX_SEGS segments of a longer call), `outputs` = its output frames. */
+typedef struct {
+    int matrix;                          /* the call's launches may take the matrix-core path: provision the buffers below (0: none, all sizes 0) */
+    int one_launch;                      /* a call of more than ART_MAX_SEGS segments may be ONE launch on its first table (segs_truncated): it runs on a
+                                          * streaming matrix-core kernel, which follows the lattice of the launch's first period, not the table */
+    size_t scratch_bytes;                /* ArtFirArgs.scratch (and the counters fix_count / fix_list) */
+    size_t planes_bytes;                 /* ArtFirArgs.planes: the fixed-point kernel's digit planes (0: the call is the f32 kernels') */
+    size_t rows_bytes;                   /* ArtFirArgs.rows: the matrix kernels' rows kept across calls (0: none) */
+    size_t split_bytes;                  /* ArtFirArgs.split: the K-split kernel's counters and partial sums (0: unsplit) */
+    size_t pad_bytes;                    /* ArtFirArgs.pad: the channel groups' padded copies (0: the stream is of a compiled width) */
+} ArtFirNeeds;
+void arthip_fir_needs (const ArtFirArgs *call, const ArtSegTable *first, unsigned int outputs, int kernel_pref, ArtFirNeeds *out);
+/* the fixed-point kernel's rows across the calls of a context (ArtFirArgs.rows / rows_cache): size of the host block that describes the device
+ * buffer (zeroed by the owner), forgetting what the buffer held (it was replaced), releasing what the host block owns */
 size_t arthip_fir_rows_cache_bytes (void);
 void   arthip_fir_rows_cache_reset (void *cache);
 void   arthip_fir_rows_cache_free (void *cache);
-/* bytes a->split must hold for a call of this shape making `outputs` frames to run on the K-split kernel; 0: the call is not for it */
-size_t arthip_fir_split_bytes (const ArtFirArgs *a, unsigned int outputs, int kernel_pref);
 /* n independent general-kernel calls (default / precise mode) in one launch per kernel variant; d_table = device scratch of
  * n * arthip_fir_batch_item_bytes () bytes (reused call after call: stream order protects it); asynchronous like arthip_fir */
 size_t arthip_fir_batch_item_bytes (void);
 int arthip_fir_batch_max_segments (void);                /* ring-epoch segments a batched call may have */
-int arthip_fir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref);   /* what arthip_fir would do */
-size_t arthip_fir_pad_bytes (const ArtFirArgs *a, unsigned int outputs);      /* bytes a->pad wants for a call of this shape making `outputs` frames (0: none) */
-/* May a call of more segments than a table holds be ONE launch (n_begin .. n_end = the whole call, segs = its first ART_MAX_SEGS
- * segments)?  Yes where the launch runs on a streaming matrix-core kernel: those take their positions from the lattice of the
- * launch's first period, not from the table (short filters: a ring epoch is a few hundred frames, a 1M-frame call eight tables) */
-int arthip_fir_spans_segments (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref);
 int arthip_fir_batch (const ArtFirArgs *a, const ArtSegTable *segs, int n, void *d_table, void *stream);
 /* new_hist[H][C] = last H frames of (hist ++ in[0..appended)); in may be NULL => zeros appended */
 int arthip_roll_history (art_s *new_hist, const art_s *hist, const art_s *in, long in_pitch, int appended, int H, int C, void *stream);

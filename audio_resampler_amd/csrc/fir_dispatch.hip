@@ -1,22 +1,12 @@
-// fir_dispatch.hip — arthip_fir: one FIR call -> the kernel that runs it (strict order, matrix cores, general).
+// fir_dispatch.hip — arthip_fir: one FIR call -> the kernel that runs it (strict order, matrix cores, general); arthip_fir_needs: what its launches need.
 #include "fir_common.hip.h"
 #include <atomic>
 #include <cstdlib>
 
 extern "C" {
 
-int arthip_fir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref) { return artfir_takes_matrix_path (a, segs, kernel_pref) ? 1 : 0; }
-
 int artamdPeriodMultiple (int outputsPerPeriod) { return outputsPerPeriod > 0 ? artfir_period_multiple (outputsPerPeriod, 32) : 0; }
 int artamdPeriodMultipleRows (int outputsPerPeriod, int rows) { return outputsPerPeriod > 0 && rows > 0 ? artfir_period_multiple (outputsPerPeriod, rows) : 0; }
-
-int arthip_fir_spans_segments (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref) { return artfir_matrix_spans_segments (a, segs, kernel_pref) ? 1 : 0; }
-
-size_t arthip_fir_split_bytes (const ArtFirArgs *a, unsigned int outputs, int kernel_pref) { return artfir_split_bytes (a, outputs, kernel_pref); }
-
-size_t arthip_fir_planes_bytes (const ArtFirArgs *a, unsigned int outputs, int kernel_pref) { return artfir_planes_bytes (a, outputs, kernel_pref); }
-
-size_t arthip_fir_rows_bytes (const ArtFirArgs *a, unsigned int outputs, int kernel_pref) { return artfir_rows_bytes (a, outputs, kernel_pref); }
 
 // ---------------------------------------------------------------------------------------------------
 // Channel counts the matrix-core kernels are not compiled for.  Their tile loops index a stream of exactly 1, 2, 4, 8, 16 or 32 channels
@@ -58,7 +48,8 @@ __global__ void group_out_kernel (art_s *out, const art_s *src, unsigned int n_b
     }
 }
 
-size_t arthip_fir_pad_bytes (const ArtFirArgs *a, unsigned int outputs)
+// bytes of ArtFirArgs.pad the groups of a launch making `outputs` frames want (0: the launch does not run in groups)
+static size_t group_pad_bytes (const ArtFirArgs *a, unsigned int outputs)
 {
     if (!channels_irregular (a->C) || a->in_pitch || a->out_pitch || (a->mode & 3) != ART_MODE_FAST) return 0;
     const size_t wp = a->C > 32 ? 32 : (size_t) padded_width (a->C);
@@ -71,7 +62,7 @@ static int fir_in_groups (const ArtFirArgs *a, const ArtSegTable *segs, int kern
     if (!a->pad || !channels_irregular (a->C) || a->in_pitch || a->out_pitch || (a->mode & 3) != ART_MODE_FAST || (!a->in && a->in_frames > 0)) return 0;
     if (!artfir_takes_matrix_path (a, segs, kernel_pref)) return 0;
     const unsigned int outs = a->n_end - a->n_begin;
-    if (arthip_fir_pad_bytes (a, outs) > a->pad_bytes) return 0;
+    if (group_pad_bytes (a, outs) > a->pad_bytes) return 0;
     const size_t wp_max = a->C > 32 ? 32 : (size_t) padded_width (a->C);
     art_s *p_hist = (art_s *) a->pad;
     art_s *p_in = (art_s *)((char *) a->pad + group_hist_bytes (a, wp_max));
@@ -104,6 +95,18 @@ static int fir_in_groups (const ArtFirArgs *a, const ArtSegTable *segs, int kern
     return (rc & ~ART_FIR_ROLLED) | (a->roll_dst ? ART_FIR_ROLLED : 0);
 }
 
+void arthip_fir_needs (const ArtFirArgs *call, const ArtSegTable *first, unsigned int outputs, int kernel_pref, ArtFirNeeds *n)
+{
+    *n = ArtFirNeeds ();
+    ArtFirArgs a = *call;
+    a.n_begin = 0; a.n_end = outputs;                        // (the call as one launch)
+    if (!artfir_takes_matrix_path (&a, first, kernel_pref, true)) return;
+    n->matrix = 1;
+    n->scratch_bytes = (size_t) 8 << 20;
+    n->pad_bytes = group_pad_bytes (&a, outputs);
+    artfir_matrix_needs (&a, first, kernel_pref, n);
+}
+
 int arthip_fir (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, void *stream)
 {
     hipStream_t st = (hipStream_t) stream;
@@ -117,7 +120,9 @@ int arthip_fir (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, v
     }
     artfir_rows_touch (a, segs);                              // (the canonical period of the rows kept across calls: every launch looks after it)
 
-    if (a->segs_truncated && ((a->mode & 3) == ART_MODE_STRICT || !artfir_matrix_spans_segments (a, segs, kernel_pref))) return -2;
+    // (a table that is only the first of the call's, arthip_fir_needs' one_launch: the streaming matrix-core kernels run such a launch, every other path
+    // declines it — here, in artfir_matrix, or below — with nothing enqueued)
+    if (a->segs_truncated && ((a->mode & 3) == ART_MODE_STRICT || channels_irregular (a->C))) return -2;
 
     if ((a->mode & 3) == ART_MODE_STRICT) {
         artfir_strict (*a, *segs, (a->mode & 4) != 0, st);

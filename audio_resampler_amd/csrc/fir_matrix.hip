@@ -882,8 +882,12 @@ static bool mfma_launch_is_regular (const ArtFirArgs *a, const ArtSegTable *segs
     return true;
 }
 
-// does this call take the matrix-core path (arthip_fir), or the general kernel?  One rule, also asked by the batched entry
-// point, which only gathers calls the general kernel would have run anyway.
+// a launch of a compiled width runs on the streaming kernels (no per-output replay of positions from the table: the lattice of its first period)
+static bool launch_streams (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref)
+{
+    return kernel_pref != 5 && (size_t) a->n_end * a->C * 4 < 0xffff0000ull && mfma_launch_is_regular (a, segs);
+}
+
 static size_t pass_fixup_min ()
 {
     static const size_t v = [] { const char *e = getenv ("ARTAMD_PASS_FIXUP_MIN"); return e && *e ? (size_t) strtoull (e, nullptr, 10) : (size_t) 0; } ();
@@ -911,7 +915,9 @@ int artfir_pass_fixup (const ArtFirArgs *a, const MfmaGeom &g, hipStream_t st)
     return 0;
 }
 
-bool artfir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref)
+// does this launch take the matrix-core path (arthip_fir), or the general kernel?  One rule, also asked for a whole call before its buffers
+// exist (sizing: arthip_fir_needs — the counters and scratch taken as given), which the host and the batched entry point both go by.
+bool artfir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, bool sizing)
 {
     if (a->n_end <= a->n_begin || (a->mode & 3) == ART_MODE_STRICT) return false;
     const unsigned int total = a->n_end - a->n_begin;
@@ -948,7 +954,7 @@ bool artfir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int
         // crossover for one group; a stream of several groups pays the matrix path's floor once per group)
         enough = (double) total * C * a->T >= 1.2e8 * ((C + 31) / 32);
     }
-    return a->mode == ART_MODE_FAST && a->period_out > 0 && a->fix_list && a->scratch && a->in_pitch == 0 && a->out_pitch == 0 &&
+    return a->mode == ART_MODE_FAST && a->period_out > 0 && (sizing || (a->fix_list && a->scratch)) && a->in_pitch == 0 && a->out_pitch == 0 &&
                          segs->lin_floor == INT_MIN && kernel_pref != ART_KERNEL_GENERAL &&
                          (enough || kernel_pref >= ART_KERNEL_MFMA) &&
                          // (a launch of less than a period is the general kernel's — unless the stream runs under the cut-invariant policy: anchored on the
@@ -993,12 +999,6 @@ static int matrix_geometry (const ArtFirArgs *a, MfmaGeom &g)
     return cgt;
 }
 
-// Parts a tile's K range is cut into for this launch (fir_mfma_split_kernel), 1: not split.  Decided from the STREAM's size (a shard
-// of a multi-device context as its whole stream would: the same parts, the same bits): tiles = slot tiles x period groups of 128
-// columns.  Measured (profiles/r3_split_k_experiment.txt): cutting K does not cut a part's sample fetch (a tile's 16 periods are
-// 147 frames apart: a quarter of the K range still spans 3/4 of the tile's input), so more than two parts lose; two parts win
-// where half the CUs would otherwise idle through a whole K walk (50-110 tiles: the 32,768-frame call of 8 ch x 988 taps,
-// 21.7 -> 16.2 us) and nowhere else.  Kernel preference 8 forces 2 / 4 / 8 parts (tests).
 // a launch of a channel count the kernels are not compiled for runs in groups of a compiled width (fir_dispatch.hip, fir_in_groups): what
 // its buffers are sized for is the widest group
 static ArtFirArgs widest_group (const ArtFirArgs *a)
@@ -1012,6 +1012,12 @@ static ArtFirArgs widest_group (const ArtFirArgs *a)
     return b;
 }
 
+// Parts a tile's K range is cut into for this launch (fir_mfma_split_kernel), 1: not split.  Decided from the STREAM's size (a shard
+// of a multi-device context as its whole stream would: the same parts, the same bits): tiles = slot tiles x period groups of 128
+// columns.  Measured (profiles/r3_split_k_experiment.txt): cutting K does not cut a part's sample fetch (a tile's 16 periods are
+// 147 frames apart: a quarter of the K range still spans 3/4 of the tile's input), so more than two parts lose; two parts win
+// where half the CUs would otherwise idle through a whole K walk (50-110 tiles: the 32,768-frame call of 8 ch x 988 taps,
+// 21.7 -> 16.2 us) and nowhere else.  Kernel preference 8 forces 2 / 4 / 8 parts (tests).
 static int matrix_split_parts (const ArtFirArgs *a, const MfmaGeom &g, unsigned int outputs, int kernel_pref)
 {
     if (kernel_pref == 5 || ART_PREF_PINS_F32 (kernel_pref) || kernel_pref == 7) return 1;
@@ -1041,33 +1047,11 @@ static int matrix_split_parts (const ArtFirArgs *a, const MfmaGeom &g, unsigned 
     return ks;
 }
 
-size_t artfir_split_bytes (const ArtFirArgs *a_, unsigned int outputs, int kernel_pref)
+// The digit planes the fixed-point kernel wants for a call of `outputs` frames (0: the call is the f32 kernels'): `a_` the stream's own call,
+// `a` and `g` its widest group and that group's geometry (of a compiled width: cgt).
+static size_t fixed_point_bytes (const ArtFirArgs *a_, const ArtFirArgs *a, const MfmaGeom &g, int cgt, unsigned int outputs, int kernel_pref)
 {
-    const ArtFirArgs wg_ = widest_group (a_), *a = &wg_;
-    if (!a->period_out || a->mode != ART_MODE_FAST) return 0;
-    ArtFirArgs b = *a;
-    b.n_begin = 0; b.n_end = outputs + (unsigned int) a->period_out * 64u;       // (any launch of the call: at most this many outputs)
-    MfmaGeom g;
-    if (!matrix_geometry (&b, g)) return 0;
-    const int ks = matrix_split_parts (a, g, outputs, kernel_pref);
-    const size_t tiles = (size_t) 8 * g.groups_per_xcd * g.slot_tiles;
-    if (ks < 2 || tiles * 16 > ART_SPLIT_HEAD_BYTES) return 0;
-    return ART_SPLIT_HEAD_BYTES + tiles * ks * 16 * MF_THREADS * sizeof (double);
-}
-
-// see arthip_fir_spans_segments (art_internal.h): the launch would run on a streaming kernel (the conditions of `regular` below)
-bool artfir_matrix_spans_segments (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref)
-{
-    if (kernel_pref == 5 || !artfir_takes_matrix_path (a, segs, kernel_pref)) return false;
-    MfmaGeom g;
-    return matrix_geometry (a, g) != 0 && (size_t) a->n_end * a->C * 4 < 0xffff0000ull && mfma_launch_is_regular (a, segs);
-}
-
-// bytes of digit planes the fixed-point kernel wants for a call of this shape (the host sizes a->planes with it before the launch)
-size_t artfir_planes_bytes (const ArtFirArgs *a_, unsigned int outputs, int kernel_pref)
-{
-    const ArtFirArgs wg_ = widest_group (a_), *a = &wg_;
-    if (!a->period_out || a->mode != ART_MODE_FAST || kernel_pref == 5 || ART_PREF_PINS_F32 (kernel_pref) || kernel_pref == 8) return 0;
+    if (kernel_pref == 5 || ART_PREF_PINS_F32 (kernel_pref) || kernel_pref == 8) return 0;
     // Where it pays (MI355X, tools/bench_shapes.py with and without ARTAMD_NO_FIXED, profiles/r2_fixed_point_shapes.txt): the
     // integer kernel gains in proportion to outputs x channels x taps, its staging pass costs in proportion to the input
     // and its extra launch ~4 us: long filters and big calls win (8 ch x 988 taps: from ~90k frames per call, +27 % at 1M;
@@ -1085,9 +1069,7 @@ size_t artfir_planes_bytes (const ArtFirArgs *a_, unsigned int outputs, int kern
     }
     static const bool off = [] { const char *e = getenv ("ARTAMD_NO_FIXED"); return e && *e && *e != '0'; } ();
     if (off) return 0;
-    MfmaGeom g;
-    const int cgt = matrix_geometry (a, g);
-    if (cgt && kernel_pref != 7) {
+    if (kernel_pref != 7) {
         // Mid-sized calls (round 5, tools/micro/fixed_crossover_r5.sh, profiles/r5_fixed_crossover.txt): the f32 streaming kernel's time is a staircase — a round of 32
         // tiles per XCD costs the same however full it is — and where its rounds are well filled it beats the fixed-point path, whose time grows smoothly with the
         // samples: 8 ch x 988 taps at 196,608 frames 41.9 against 47.7 us a call, 16 ch at 81,920 - 98,304 40.5 against 49.5, 32 ch at 49,152 44.3 against 54.3,
@@ -1105,20 +1087,29 @@ size_t artfir_planes_bytes (const ArtFirArgs *a_, unsigned int outputs, int kern
         // version without the bound sent 8 ch x 380 taps and 16 ch x 512 taps at 1M frames to the f32 kernel: 81.6 against 75.7 and 197 against 178 us)
         if (one_launch && ks <= 3000.0 && t_f32 < 0.92 * t_fixed) return 0;
     }
-    return cgt ? artfir_i8_bytes (a, g, cgt, outputs) : 0;
+    return artfir_i8_bytes (a, g, cgt, outputs);
 }
 
-// device bytes of the rows the fixed-point kernel keeps across the calls of a context (0: this call is not for that kernel)
-size_t artfir_rows_bytes (const ArtFirArgs *a_, unsigned int outputs, int kernel_pref)
+// The matrix-core buffers of a call whose launches take the path (arthip_fir_needs, fir_dispatch.hip; `a` is the call as one launch, `first` its
+// first table): one geometry — of the widest group where the stream runs in groups, for the longest launch of the call — and every size from it.
+void artfir_matrix_needs (const ArtFirArgs *a, const ArtSegTable *first, int kernel_pref, ArtFirNeeds *n)
 {
-    if (!artfir_rows_cache_enabled ()) return 0;
-    const ArtFirArgs wg_ = widest_group (a_), *a = &wg_;
-    if (!a->period_out || a->mode != ART_MODE_FAST) return 0;
+    const unsigned int outputs = a->n_end - a->n_begin;
+    ArtFirArgs w = widest_group (a);
+    w.n_begin = 0; w.n_end = outputs + (unsigned int) a->period_out * 64u;          // (any launch of the call: at most this many outputs)
     MfmaGeom g;
-    const int cgt = matrix_geometry (a, g);
-    if (!cgt) return 0;
-    // the f32 streaming kernel's set at the head, the fixed-point kernel's sets (where the call is for that kernel) behind it
-    return artfir_f32_set_bytes (g) + (artfir_planes_bytes (a_, outputs, kernel_pref) ? artfir_i8_rows_bytes (a, g, cgt, outputs) : 0);
+    const int cgt = matrix_geometry (&w, g);
+    if (!cgt) return;
+    n->planes_bytes = fixed_point_bytes (a, &w, g, cgt, outputs, kernel_pref);
+    // the rows kept across calls: the f32 streaming kernel's set at the head, the fixed-point kernel's sets (where the call is for that kernel) behind it
+    if (artfir_rows_cache_enabled ()) n->rows_bytes = artfir_f32_set_bytes (g) + (n->planes_bytes ? artfir_i8_rows_bytes (&w, g, cgt, outputs) : 0);
+    // the K-split kernel's arrival counters and partial sums (a call with digit planes is the fixed-point kernel's, which is never split)
+    const int ks = n->planes_bytes ? 1 : matrix_split_parts (&w, g, outputs, kernel_pref);
+    const size_t tiles = (size_t) 8 * g.groups_per_xcd * g.slot_tiles;
+    if (ks >= 2 && tiles * 16 <= ART_SPLIT_HEAD_BYTES) n->split_bytes = ART_SPLIT_HEAD_BYTES + tiles * ks * 16 * MF_THREADS * sizeof (double);
+    // a call of more segments than its first table holds is ONE launch where that launch runs on a streaming kernel (its own compiled width:
+    // a stream in groups is cut)
+    if (first->count >= ART_MAX_SEGS && w.C == a->C) n->one_launch = launch_streams (a, first, kernel_pref);
 }
 
 // Upkeep of the stream's canonical period (fir_matrix_i8.hip, "The rows across calls") by EVERY launch of a rational-ratio stream, whichever kernel
@@ -1176,7 +1167,7 @@ int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref
         const unsigned int roll_blocks = a->roll_dst ? (unsigned int)((a->H * a->C + wg_threads - 1) / wg_threads) : 0u;
         dim3 grid ((unsigned int)(8 * g.groups_per_xcd * g.slot_tiles) + roll_blocks, (unsigned int)((a->C + g.cg - 1) / g.cg));
 
-        const bool regular = ws && !wide && kernel_pref != 5 && (size_t) a->n_end * a->C * 4 < 0xffff0000ull && mfma_launch_is_regular (a, segs);
+        const bool regular = ws && !wide && launch_streams (a, segs, kernel_pref);
         if (a->segs_truncated && !regular) return 0;          // (the tile kernel replays positions from the table: not beyond it)
         // Fixed point on the integer matrix cores (fir_matrix_i8.hip) where the launch has its digit planes: staging pass + main
         // kernel, which carries the f32 tile loop as its own stand-by (a sample the digits cannot hold is only found on the

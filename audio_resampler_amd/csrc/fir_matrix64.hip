@@ -279,9 +279,9 @@ void fir_mfma64_kernel (ArtFirArgs a, ArtSegTable segs, WideGeom g)
 }
 } // namespace
 
-// does this call take the matrix-core path (arthip_fir), or the general kernel?  One rule, also asked by the batched entry
-// point, which only gathers calls the general kernel would have run anyway.
-bool artfir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref)
+// does this launch take the matrix-core path (arthip_fir), or the general kernel?  One rule, also asked for a whole call before its buffers
+// exist (sizing: arthip_fir_needs — the counters, scratch and group buffers taken as given), which the host and the batched entry point both go by.
+bool artfir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, bool sizing)
 {
     if (a->n_end <= a->n_begin || (a->mode & 3) == ART_MODE_STRICT) return false;
     const unsigned int total = a->n_end - a->n_begin;
@@ -293,25 +293,24 @@ bool artfir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int
                        ((uintptr_t) a->in % 16) == 0 && ((uintptr_t) a->hist % 16) == 0;
     const int cgt = (small && (a->C == 1 || a->C == 2 || a->C == 4 || a->C == 8 || a->C == 16 || a->C == 32)) ? a->C : 0;
     // (a channel count the kernel is not compiled for: in groups of a compiled width, where the launch has the buffer for them — fir_dispatch.hip)
-    const bool grouped = a->pad != nullptr && (a->C > 32 || (a->C & (a->C - 1)) != 0);
-    return a->mode == ART_MODE_FAST && a->period_out > 0 && a->fix_list && a->scratch && a->in_pitch == 0 && a->out_pitch == 0 &&
+    const bool grouped = (sizing || a->pad) && (a->C > 32 || (a->C & (a->C - 1)) != 0);
+    return a->mode == ART_MODE_FAST && a->period_out > 0 && (sizing || (a->fix_list && a->scratch)) && a->in_pitch == 0 && a->out_pitch == 0 &&
                     segs->lin_floor == INT_MIN && kernel_pref != ART_KERNEL_GENERAL && (cgt != 0 || grouped) &&
                     (enough || kernel_pref >= ART_KERNEL_MFMA) && total >= (unsigned int) a->period_out;
 }
 
-// Launch the fp64 matrix-core path for this call if it applies: ART_KERNEL_MFMA (| ART_FIR_ROLLED), -1 on a launch failure,
-// 0 when the call is for the general kernel.
-size_t artfir_planes_bytes (const ArtFirArgs *, unsigned int, int) { return 0; }
-size_t artfir_rows_bytes (const ArtFirArgs *, unsigned int, int) { return 0; }
+// beyond the counters and scratch, nothing: no fixed point, no rows kept across calls, no K split — and never one launch beyond a table (the fp64
+// kernel checks every output's position against it)
+void artfir_matrix_needs (const ArtFirArgs *, const ArtSegTable *, int, ArtFirNeeds *) { }
 void artfir_rows_touch (const ArtFirArgs *, const ArtSegTable *) { }
 extern "C" {      // (the fixed-point kernel's rows across calls: 4-byte samples only)
 size_t arthip_fir_rows_cache_bytes (void) { return 0; }
 void arthip_fir_rows_cache_reset (void *) { }
 void arthip_fir_rows_cache_free (void *) { }
 }
-size_t artfir_split_bytes (const ArtFirArgs *, unsigned int, int) { return 0; }
-bool artfir_matrix_spans_segments (const ArtFirArgs *, const ArtSegTable *, int) { return false; }    // (the fp64 kernel checks every output's position against the table)
 
+// Launch the fp64 matrix-core path for this call if it applies: ART_KERNEL_MFMA (| ART_FIR_ROLLED), -1 on a launch failure,
+// 0 when the call is for the general kernel.
 int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, void *stream)
 {
     hipStream_t st = (hipStream_t) stream;
@@ -324,7 +323,8 @@ int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref
         const bool small = (size_t) a->in_frames * a->C * 8 < 0x7fff0000ull && (size_t) a->H * a->C * 8 < 0x7fff0000ull &&
                            ((uintptr_t) a->in % 16) == 0 && ((uintptr_t) a->hist % 16) == 0;
         const int cgt = (small && (a->C == 1 || a->C == 2 || a->C == 4 || a->C == 8 || a->C == 16 || a->C == 32)) ? a->C : 0;
-        const bool ok = cgt != 0 && artfir_takes_matrix_path (a, segs, kernel_pref);     // (cgt == 0 here: the groups could not run — no buffer — and the general kernel takes the call)
+        // (cgt == 0 here: the groups could not run — no buffer — and the general kernel takes the call; a truncated table: declined, arthip_fir cuts the call)
+        const bool ok = cgt != 0 && !a->segs_truncated && artfir_takes_matrix_path (a, segs, kernel_pref);
         if (ok) {
             WideGeom g;
             {   // (short or badly fitting periods: several at a time, fir_common.hip.h)

@@ -1138,18 +1138,123 @@ static ResampleResult enqueue_call_layouts (Resample *cxt, const art_s *d_in, lo
 static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pitch, int nIn,
                                     art_s *d_out, long out_pitch, int cap, double ratio);
 
+/* where a context stands: the planner's state */
+static ArtamdPosition position_of (const Resample *cxt)
+{
+    ArtamdPosition p;
+    p.numTaps = cxt->numTaps; p.numFilters = cxt->numFilters; p.flags = cxt->flags; p.inputIndex = cxt->inputIndex;
+    p.floorActive = cxt->hip->floor_active; p.outputOffset = cxt->outputOffset; p.fixedRatio = cxt->fixedRatio;
+    return p;
+}
+
+/* plan a call from the context's position into hip->segs, grown as needed (*trial: the position after the call); returns the segment count,
+ * -1 out of memory */
+static int plan_segments (Resample *cxt, int nIn, int cap, double ratio, ArtamdPosition *trial, ResampleResult *res, int *lin_floor)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    for (;;) {
+        *trial = position_of (cxt);
+        const int nseg = artamdPlanCall (trial, nIn, cap, ratio, res, hip->segs, hip->seg_cap, lin_floor);
+        if (nseg <= hip->seg_cap) return nseg;
+        ArtamdSegment *grown = realloc (hip->segs, sizeof (ArtamdSegment) * (size_t)(nseg + 16));
+        if (!grown) return -1;
+        hip->segs = grown; hip->seg_cap = nseg + 16;
+    }
+}
+
+/* segments [s0, s1) of the planned call as a launch's table */
+static void seg_table (const struct artamd_resampler *hip, int s0, int s1, int lin_floor, ArtSegTable *tab)
+{
+    tab->count = s1 - s0; tab->lin_floor = lin_floor;
+    for (int s = s0; s < s1; ++s) {
+        tab->first [s - s0] = hip->segs [s].first_output;
+        tab->lin_base [s - s0] = hip->segs [s].lin_base;
+        tab->base [s - s0] = hip->segs [s].base_offset;
+    }
+}
+
+/* the call's FIR arguments, and the rational structure of its ratio (the launches' outputs, tables and buffers are the caller's) */
+static void fill_args (Resample *cxt, ArtFirArgs *a, double ratio, const art_s *in, long in_pitch, int in_frames, art_s *out, long out_pitch)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    const double eff_ratio = (cxt->flags & RESAMPLE_FIXED_RATIO) ? cxt->fixedRatio : ratio;
+    if (eff_ratio != hip->period_ratio) {
+        hip->period_ratio = eff_ratio;
+        find_period (eff_ratio, &hip->period_out, &hip->period_in);
+    }
+    memset (a, 0, sizeof (*a));
+    a->bank = hip->d_bank; a->hist = hip->d_hist [hip->cur];
+    a->in = in; a->in_pitch = in_pitch; a->in_frames = in_frames;
+    a->out = out; a->out_pitch = out_pitch;
+    a->C = cxt->numChannels; a->T = cxt->numTaps; a->F = cxt->numFilters; a->H = HIST_FRAMES (cxt->numTaps);
+    a->stream_C = hip->stream_channels;
+    a->lin_origin = hip->lin_origin;
+    a->interpolate = (cxt->flags & SUBSAMPLE_INTERPOLATE) != 0;
+    a->lowpass = (cxt->flags & INCLUDE_LOWPASS) != 0;
+    /* the double-precision build has one arithmetic: EXTEND_CONVOLUTION_MATH only matters for 4-byte samples
+     * (reference resampler.c:191) */
+    const int extend = !ART_WIDE && (cxt->flags & EXTEND_CONVOLUTION_MATH);
+    a->mode = (cxt->flags & RESAMPLE_STRICT_ORDER) ? ART_MODE_STRICT : extend ? ART_MODE_PRECISE : ART_MODE_FAST;
+    if ((cxt->flags & RESAMPLE_STRICT_ORDER) && extend) a->mode |= 4;
+    a->ratio = eff_ratio;
+    a->period_out = hip->period_out; a->period_in = hip->period_in;
+}
+
+/* grow a device buffer; a new one starts with its first `head` bytes zero */
+static void *grow_zeroed (void *dev, size_t *cap, size_t need, size_t head, void *stream)
+{
+    if (need <= *cap) return dev;
+    dev = grow (dev, cap, need);
+    if (dev) arthip_zero (dev, head, stream);
+    return dev;
+}
+
+/* The buffers a call's matrix-core launches need (arthip_fir_needs), handed to them in *a: allocated only once a call of this context is
+ * actually big enough for them (a service with thousands of small-block contexts never pays for them).  Returns 1 when the path has its
+ * counters and scratch; a failed allocation leaves the call on the general kernel. */
+static int provision (struct artamd_resampler *hip, const ArtFirNeeds *n, ArtFirArgs *a)
+{
+    hip->last_fixed [0] = 0;
+    if (!n->matrix) return 0;
+    /* [0] per-launch count, [1] running total of outputs the matrix kernels evaluated off their canonical pattern
+     * (diagnostics only: they are computed inside the kernel) */
+    hip->d_fix = grow_zeroed (hip->d_fix, &hip->fix_cap, 64, 2 * sizeof (unsigned int), hip->stream);
+    if (hip->d_fix) { a->fix_count = hip->d_fix; a->fix_list = hip->d_fix + 2; a->fix_cap = 0; }
+    hip->d_scratch = grow (hip->d_scratch, &hip->scratch_cap, n->scratch_bytes);
+    a->scratch = hip->d_scratch; a->scratch_bytes = hip->d_scratch ? hip->scratch_cap : 0;
+    /* digit planes for the fixed-point kernel (about the size of the call's input; without them the f32 kernels run) */
+    hip->d_planes = grow_zeroed (hip->d_planes, &hip->planes_cap, n->planes_bytes, ART_I8_HEAD_BYTES, hip->stream);
+    a->planes = n->planes_bytes ? hip->d_planes : NULL; a->planes_bytes = hip->d_planes ? hip->planes_cap : 0;
+    /* ... and the matrix kernels' filter rows, which outlive the call: built by the first launch of a stream, looked up by the others
+     * (none without their host block: resampleHipKeepRows (0), the 8-byte build) */
+    const size_t rows_want = a->rows_cache ? n->rows_bytes : 0;
+    if (rows_want > hip->rows_cap) {
+        hip->d_rows = grow (hip->d_rows, &hip->rows_cap, rows_want);
+        arthip_fir_rows_cache_reset (hip->rows_cache);
+    }
+    if (rows_want && hip->d_rows) { a->rows = hip->d_rows; a->rows_bytes = hip->rows_cap; }
+    hip->last_masks = NULL; a->rows_masks_out = &hip->last_masks;
+    /* calls of few tiles: room for the K-split kernel's partial sums (a grown buffer starts with its counters zeroed; the
+     * old one is released behind the launches that used it: stream order) */
+    hip->d_split = grow_zeroed (hip->d_split, &hip->split_cap, n->split_bytes, ART_SPLIT_HEAD_BYTES, hip->stream);
+    a->split = n->split_bytes ? hip->d_split : NULL; a->split_bytes = hip->d_split ? hip->split_cap : 0;
+    a->fixed_out = hip->last_fixed;
+    /* a channel count the matrix kernels are not compiled for: room for its groups' padded copies */
+    hip->d_pad = grow (hip->d_pad, &hip->pad_cap, n->pad_bytes);
+    a->pad = n->pad_bytes ? hip->d_pad : NULL; a->pad_bytes = hip->d_pad ? hip->pad_cap : 0;
+    return a->fix_list && a->scratch;
+}
+
 /* The first `frames` input frames of a call go into the history without any output being due (the caller established
  * that): position and ring epoch advance exactly as the reference's loop would have advanced them. */
 static int consume_silently (Resample *cxt, const art_s *d_in, long in_pitch, int frames, double ratio)
 {
     struct artamd_resampler *hip = cxt->hip;
     const int T = cxt->numTaps, C = cxt->numChannels, H = HIST_FRAMES (T);
-    ArtamdPosition pos;
+    ArtamdPosition pos = position_of (cxt);
     ResampleResult res;
     int lin_floor;
 
-    pos.numTaps = T; pos.numFilters = cxt->numFilters; pos.flags = cxt->flags; pos.inputIndex = cxt->inputIndex;
-    pos.floorActive = hip->floor_active; pos.outputOffset = cxt->outputOffset; pos.fixedRatio = cxt->fixedRatio;
     plan_call (&pos, frames, 1, ratio, &res, NULL, 0, &lin_floor, 1);
     if (res.output_generated || (int) res.input_used != frames) return -1;
 
@@ -1168,14 +1273,10 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
     struct artamd_resampler *hip = cxt->hip;
     const int T = cxt->numTaps, C = cxt->numChannels, H = HIST_FRAMES (T);
     ResampleResult res = { 0, 0 };
-    ArtamdPosition pos, trial;
-    int lin_floor, nseg;
-
-    pos.numTaps = T; pos.numFilters = cxt->numFilters; pos.flags = cxt->flags; pos.inputIndex = cxt->inputIndex;
-    pos.floorActive = hip->floor_active; pos.outputOffset = cxt->outputOffset; pos.fixedRatio = cxt->fixedRatio;
+    ArtamdPosition trial;
+    int lin_floor;
 
     const int is_flush = nIn < 0 && !(cxt->flags & RESAMPLER_FLUSHED);
-    const double eff_ratio = (cxt->flags & RESAMPLE_FIXED_RATIO) ? cxt->fixedRatio : ratio;
 
     /* EXTRAPOLATE_ENDPOINTS, first output of the stream only after the ring has rewound (the position was advanced by more
      * than 15 T): the reference extrapolates backwards from the samples that arrived SINCE the rewind, over the history
@@ -1183,7 +1284,7 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
      * consumed silently first; the rest of the call then starts inside the right ring epoch and prefills as usual. */
     if ((cxt->flags & EXTRAPOLATE_PREFILL) && !is_flush && nIn > 1 && cap > 0 && !(cxt->flags & RESAMPLER_FLUSHED)) {
         ResampleResult one;
-        trial = pos;
+        trial = position_of (cxt);
         if (plan_call (&trial, nIn, 1, ratio, &one, NULL, 0, &lin_floor, 1) >= 2 && one.output_generated == 1 && one.input_used >= 2) {
             const int lead = (int) one.input_used - 1;
             if (consume_silently (cxt, d_in, in_pitch, lead, ratio)) {
@@ -1196,19 +1297,8 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
         }
     }
 
-    for (;;) {
-        trial = pos;
-        nseg = artamdPlanCall (&trial, nIn, cap, ratio, &res, hip->segs, hip->seg_cap, &lin_floor);
-        if (nseg <= hip->seg_cap) break;
-        ArtamdSegment *grown = realloc (hip->segs, sizeof (ArtamdSegment) * (size_t)(nseg + 16));
-        if (!grown) { artamd_note_failure ("resampler: out of memory (segment table)"); res.input_used = res.output_generated = 0; return res; }
-        hip->segs = grown; hip->seg_cap = nseg + 16;
-    }
-
-    if (eff_ratio != hip->period_ratio) {
-        hip->period_ratio = eff_ratio;
-        find_period (eff_ratio, &hip->period_out, &hip->period_in);
-    }
+    const int nseg = plan_segments (cxt, nIn, cap, ratio, &trial, &res, &lin_floor);
+    if (nseg < 0) { artamd_note_failure ("resampler: out of memory (segment table)"); res.input_used = res.output_generated = 0; return res; }
 
     const int appended = is_flush ? T / 2 : (int) res.input_used;
     const art_s *flush_in = NULL;
@@ -1233,107 +1323,32 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
 
     if (res.output_generated) {
         ArtFirArgs a;
-        memset (&a, 0, sizeof (a));
-        a.bank = hip->d_bank; a.hist = hip->d_hist [hip->cur];
-        a.in = is_flush ? flush_in : d_in; a.in_pitch = is_flush ? 0 : in_pitch;
-        a.in_frames = is_flush ? (flush_in ? T / 2 : 0) : (int) res.input_used;
-        a.out = d_out; a.out_pitch = out_pitch;
-        a.C = C; a.T = T; a.F = cxt->numFilters; a.H = H;
-        a.stream_C = hip->stream_channels;
-        a.lin_origin = hip->lin_origin;
-        a.interpolate = (cxt->flags & SUBSAMPLE_INTERPOLATE) != 0;
-        a.lowpass = (cxt->flags & INCLUDE_LOWPASS) != 0;
-        /* the double-precision build has one arithmetic: EXTEND_CONVOLUTION_MATH only matters for 4-byte samples
-         * (reference resampler.c:191) */
-        const int extend = !ART_WIDE && (cxt->flags & EXTEND_CONVOLUTION_MATH);
-        a.mode = (cxt->flags & RESAMPLE_STRICT_ORDER) ? ART_MODE_STRICT : extend ? ART_MODE_PRECISE : ART_MODE_FAST;
-        if ((cxt->flags & RESAMPLE_STRICT_ORDER) && extend) a.mode |= 4;
-        a.ratio = eff_ratio;
-        a.period_out = hip->period_out; a.period_in = hip->period_in;
-        /* the matrix-core path needs its counters and 8 MB of scratch: allocated only once a call of this context is
-         * actually big enough for it (asked with stand-ins first — a service with thousands of small-block contexts never
-         * pays for them) */
-        int matrix_sized = 0;
-        hip->last_fixed [0] = 0;
+        ArtSegTable tab;
+        fill_args (cxt, &a, ratio, is_flush ? flush_in : d_in, is_flush ? 0 : in_pitch, is_flush ? (flush_in ? T / 2 : 0) : (int) res.input_used,
+                   d_out, out_pitch);
         /* the canonical period of the rows the matrix kernels keep across calls: looked after by every launch of a rational-ratio stream,
          * whichever kernel runs it (fir_matrix.hip, artfir_rows_touch) */
         if (a.period_out && a.mode == ART_MODE_FAST && !hip->rows_off && !is_flush) {
             if (!hip->rows_cache && arthip_fir_rows_cache_bytes ()) hip->rows_cache = calloc (1, arthip_fir_rows_cache_bytes ());
             a.rows_cache = hip->rows_cache;
         }
-        if (a.period_out && a.mode == ART_MODE_FAST && hip->kernel_pref != ART_KERNEL_GENERAL && !is_flush) {
-            ArtSegTable probe;
-            probe.count = 1; probe.lin_floor = lin_floor;
-            a.fix_count = a.fix_list = (unsigned int *) hip; a.scratch = hip; a.scratch_bytes = (size_t) 8 << 20; a.pad = hip;
-            a.n_begin = 0; a.n_end = res.output_generated;
-            matrix_sized = arthip_fir_takes_matrix_path (&a, &probe, hip->kernel_pref);
-            a.fix_count = a.fix_list = NULL; a.scratch = NULL; a.scratch_bytes = 0; a.n_begin = a.n_end = 0; a.pad = NULL;
-        }
-        if (matrix_sized) {
-            /* [0] per-launch count, [1] running total of outputs the matrix kernels evaluated off their canonical pattern
-             * (diagnostics only: they are computed inside the kernel) */
-            if (!hip->d_fix) {
-                hip->d_fix = grow (hip->d_fix, &hip->fix_cap, 64);
-                if (hip->d_fix) arthip_zero (hip->d_fix, 2 * sizeof (unsigned int), hip->stream);
-            }
-            if (hip->d_fix) { a.fix_count = hip->d_fix; a.fix_list = hip->d_fix + 2; a.fix_cap = 0; }
-            if (!hip->d_scratch) hip->d_scratch = grow (hip->d_scratch, &hip->scratch_cap, (size_t) 8 << 20);
-            a.scratch = hip->d_scratch; a.scratch_bytes = hip->d_scratch ? hip->scratch_cap : 0;
-            /* digit planes for the fixed-point kernel (about the size of the call's input; without them the f32 kernels run) */
-            const size_t want = arthip_fir_planes_bytes (&a, res.output_generated, hip->kernel_pref);
-            if (want > hip->planes_cap) {
-                hip->d_planes = grow (hip->d_planes, &hip->planes_cap, want);
-                if (hip->d_planes) arthip_zero (hip->d_planes, ART_I8_HEAD_BYTES, hip->stream);
-            }
-            a.planes = want ? hip->d_planes : NULL; a.planes_bytes = hip->d_planes ? hip->planes_cap : 0;
-            /* ... and the matrix kernels' filter rows, which outlive the call: built by the first launch of a stream, looked up by the others */
-            const size_t rows_want = hip->rows_off ? 0 : arthip_fir_rows_bytes (&a, res.output_generated, hip->kernel_pref);
-            if (rows_want > hip->rows_cap && hip->rows_cache) {
-                hip->d_rows = grow (hip->d_rows, &hip->rows_cap, rows_want);
-                arthip_fir_rows_cache_reset (hip->rows_cache);
-            }
-            if (rows_want && hip->d_rows && hip->rows_cache) { a.rows = hip->d_rows; a.rows_bytes = hip->rows_cap; }
-            hip->last_masks = NULL; a.rows_masks_out = &hip->last_masks;
-            /* calls of few tiles: room for the K-split kernel's partial sums (a grown buffer starts with its counters zeroed; the
-             * old one is released behind the launches that used it: stream order) */
-            const size_t split_want = want ? 0 : arthip_fir_split_bytes (&a, res.output_generated, hip->kernel_pref);
-            if (split_want > hip->split_cap) {
-                hip->d_split = grow (hip->d_split, &hip->split_cap, split_want);
-                if (hip->d_split) arthip_zero (hip->d_split, ART_SPLIT_HEAD_BYTES, hip->stream);
-            }
-            a.split = split_want ? hip->d_split : NULL; a.split_bytes = hip->d_split ? hip->split_cap : 0;
-            a.fixed_out = hip->last_fixed;
-            /* a channel count the matrix kernels are not compiled for: room for its groups' padded copies */
-            const size_t pad_want = arthip_fir_pad_bytes (&a, res.output_generated);
-            if (pad_want > hip->pad_cap) hip->d_pad = grow (hip->d_pad, &hip->pad_cap, pad_want);
-            a.pad = pad_want ? hip->d_pad : NULL; a.pad_bytes = hip->d_pad ? hip->pad_cap : 0;
-        }
+        /* what the call's launches need (a flush runs on the general kernel) */
+        ArtFirNeeds needs;
+        memset (&needs, 0, sizeof (needs));
+        seg_table (hip, 0, nseg < ART_MAX_SEGS ? nseg : ART_MAX_SEGS, lin_floor, &tab);
+        if (!is_flush) arthip_fir_needs (&a, &tab, res.output_generated, hip->kernel_pref, &needs);
+        const int matrix = provision (hip, &needs, &a);
 
         /* A call of more ring epochs than a table holds (short filters: an epoch is a few hundred frames) is cut into launches of
          * ART_MAX_SEGS segments — unless it runs on a streaming matrix-core kernel, which follows the lattice from its first period
-         * and needs the table for that period only: then the whole call is ONE launch with the first table (asked first; a launch
-         * that declines after all enqueues nothing and the cut launches follow) */
-        int whole = 0;
-        if (matrix_sized && nseg > ART_MAX_SEGS) {
-            ArtSegTable tab;
-            tab.count = ART_MAX_SEGS; tab.lin_floor = lin_floor;
-            for (int s = 0; s < ART_MAX_SEGS; ++s) {
-                tab.first [s] = hip->segs [s].first_output; tab.lin_base [s] = hip->segs [s].lin_base; tab.base [s] = hip->segs [s].base_offset;
-            }
-            a.n_begin = hip->segs [0].first_output; a.n_end = res.output_generated;
-            whole = arthip_fir_spans_segments (&a, &tab, hip->kernel_pref);
-        }
+         * and needs the table for that period only: then the whole call is ONE launch with the first table (a launch that declines
+         * after all enqueues nothing and the cut launches follow) */
+        int whole = matrix && nseg > ART_MAX_SEGS && needs.one_launch;
         for (int s0 = 0; s0 < nseg; s0 += ART_MAX_SEGS) {
             const int s_tab = s0 + ART_MAX_SEGS < nseg ? s0 + ART_MAX_SEGS : nseg;     /* segments in this launch's table ... */
             const int s1 = whole ? nseg : s_tab;                                       /* ... and those it produces */
-            ArtSegTable tab;
 
-            tab.count = s_tab - s0; tab.lin_floor = lin_floor;
-            for (int s = s0; s < s_tab; ++s) {
-                tab.first [s - s0] = hip->segs [s].first_output;
-                tab.lin_base [s - s0] = hip->segs [s].lin_base;
-                tab.base [s - s0] = hip->segs [s].base_offset;
-            }
+            seg_table (hip, s0, s_tab, lin_floor, &tab);
             a.n_begin = hip->segs [s0].first_output;
             a.n_end = s1 < nseg ? hip->segs [s1].first_output : res.output_generated;
             if (a.n_end > a.n_begin) {
@@ -1393,64 +1408,26 @@ static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, 
                        ArtFirArgs *a, ArtSegTable *tab, ResampleResult *res, ArtamdPosition *trial)
 {
     struct artamd_resampler *hip = cxt->hip;
-    const int T = cxt->numTaps, C = cxt->numChannels, H = HIST_FRAMES (T);
-    ArtamdPosition pos;
-    int lin_floor, nseg;
+    int lin_floor;
 
     if (nIn < 0 || hip->stream != lead_stream || hip->timing || hip->nshards || hip->device != arthip_current_device () ||
         (cxt->flags & (EXTRAPOLATE_ENDPOINTS | RESAMPLE_STRICT_ORDER | RESAMPLER_FLUSHED))) return 0;
 
-    pos.numTaps = T; pos.numFilters = cxt->numFilters; pos.flags = cxt->flags; pos.inputIndex = cxt->inputIndex;
-    pos.floorActive = hip->floor_active; pos.outputOffset = cxt->outputOffset; pos.fixedRatio = cxt->fixedRatio;
-    const double eff_ratio = (cxt->flags & RESAMPLE_FIXED_RATIO) ? cxt->fixedRatio : ratio;
+    const int nseg = plan_segments (cxt, nIn, cap, ratio, trial, res, &lin_floor);      /* (out of memory: the one-by-one path reports it) */
+    if (nseg < 0 || nseg > arthip_fir_batch_max_segments () || res->output_generated == 0) return 0;
 
-    for (;;) {
-        *trial = pos;
-        nseg = artamdPlanCall (trial, nIn, cap, ratio, res, hip->segs, hip->seg_cap, &lin_floor);
-        if (nseg <= hip->seg_cap) break;
-        ArtamdSegment *grown = realloc (hip->segs, sizeof (ArtamdSegment) * (size_t)(nseg + 16));
-        if (!grown) return 0;                                 /* (the one-by-one path reports it) */
-        hip->segs = grown; hip->seg_cap = nseg + 16;
-    }
-    if (nseg > arthip_fir_batch_max_segments () || res->output_generated == 0) return 0;
-
-    if (eff_ratio != hip->period_ratio) {
-        hip->period_ratio = eff_ratio;
-        find_period (eff_ratio, &hip->period_out, &hip->period_in);
-    }
-
-    memset (a, 0, sizeof (*a));
-    a->bank = hip->d_bank; a->hist = hip->d_hist [hip->cur];
-    a->in = d_in; a->in_pitch = 0; a->in_frames = (int) res->input_used;
-    a->out = d_out; a->out_pitch = 0;
-    a->C = C; a->T = T; a->F = cxt->numFilters; a->H = H;
-    a->stream_C = hip->stream_channels;
-    a->interpolate = (cxt->flags & SUBSAMPLE_INTERPOLATE) != 0;
-    a->lowpass = (cxt->flags & INCLUDE_LOWPASS) != 0;
-    a->mode = (!ART_WIDE && (cxt->flags & EXTEND_CONVOLUTION_MATH)) ? ART_MODE_PRECISE : ART_MODE_FAST;
-    a->ratio = eff_ratio;
-    a->period_out = hip->period_out; a->period_in = hip->period_in;
-    a->lin_origin = hip->lin_origin;
-
-    tab->count = nseg; tab->lin_floor = lin_floor;
-    for (int s = 0; s < nseg; ++s) {
-        tab->first [s] = hip->segs [s].first_output;
-        tab->lin_base [s] = hip->segs [s].lin_base;
-        tab->base [s] = hip->segs [s].base_offset;
-    }
+    fill_args (cxt, a, ratio, d_in, 0, (int) res->input_used, d_out, 0);
+    seg_table (hip, 0, nseg, lin_floor, tab);
     a->n_begin = hip->segs [0].first_output; a->n_end = res->output_generated;
 
     /* the cut-invariant policy: every launch of a rational-ratio stream anchored on its canonical period, or counted where it cannot be — the
      * single call decides that, with the context's kept rows (a call shorter than one period is the matrix path's only with them) */
     if (hip->kernel_pref == ART_KERNEL_INVARIANT && a->period_out && a->mode == ART_MODE_FAST) return 0;
 
-    /* would the single call take the matrix-core path?  (it has its counters and scratch whenever the ratio is
-     * rational, the mode default and the kernel not pinned: stand-ins suffice for the question) */
-    if (a->period_out && a->mode == ART_MODE_FAST && hip->kernel_pref != ART_KERNEL_GENERAL) {
-        a->fix_count = (unsigned int *) hip; a->fix_list = (unsigned int *) hip; a->scratch = hip; a->scratch_bytes = (size_t) 8 << 20;
-        if (arthip_fir_takes_matrix_path (a, tab, hip->kernel_pref)) return 0;
-        a->fix_count = a->fix_list = NULL; a->scratch = NULL; a->scratch_bytes = 0;
-    }
+    /* would the single call take the matrix-core path?  (the same question it asks) */
+    ArtFirNeeds needs;
+    arthip_fir_needs (a, tab, res->output_generated, hip->kernel_pref, &needs);
+    if (needs.matrix) return 0;
 
     const int appended = (int) res->input_used;
     a->roll_dst = appended > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;      /* the launch takes the history roll along */
@@ -1516,11 +1493,9 @@ out:
 static ResampleResult peek_call (Resample *cxt, int nIn, int cap, double ratio)
 {
     ResampleResult peek;
-    ArtamdPosition pos;
+    ArtamdPosition pos = position_of (cxt);
     int dummy_floor;
 
-    pos.numTaps = cxt->numTaps; pos.numFilters = cxt->numFilters; pos.flags = cxt->flags; pos.inputIndex = cxt->inputIndex;
-    pos.floorActive = cxt->hip->floor_active; pos.outputOffset = cxt->outputOffset; pos.fixedRatio = cxt->fixedRatio;
     artamdPlanCall (&pos, nIn, cap, ratio, &peek, NULL, 0, &dummy_floor);
     return peek;
 }

@@ -1,6 +1,6 @@
 """GPU: the library's automatic kernel choice, checked ON THE BOX THE TEST RUNS ON.
 
-The dispatch (fir_dispatch.hip, artfir_takes_matrix_path, artfir_planes_bytes, matrix_split_parts, the slab minimum) is a set of cost models
+The dispatch (fir_dispatch.hip, artfir_takes_matrix_path, arthip_fir_needs, matrix_split_parts, the slab minimum) is a set of cost models
 fitted to timings of particular boxes, and boxes differ by up to 10 %.  For three stream shapes x ten call sizes this test times a device-resident
 call with kernel preference 0 (automatic), 1 (general kernel), 6 (f32 matrix-core streaming kernel, un-split) and 7 (fixed point wherever it can run; its
 f32 stand-ins where it cannot) and fails if the automatic choice is more than 12 % slower than the best pinned kernel at any point.  The table is

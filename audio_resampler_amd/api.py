@@ -163,6 +163,7 @@ def _bind(width):
         "stretchProcessDevice": (C.c_int, [ptr, ptr, C.c_int, ptr, C.c_double]),
         "stretchFlushDevice": (C.c_int, [ptr, ptr]),
         "resampleProcessBatchInterleavedDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleProcessScheduleInterleavedDevice": (C.c_int, [RP, C.c_int, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "stretchProcessBatchDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr]),
         "stretchFlushBatchDevice": (C.c_int, [ptr, C.c_int, ptr, ptr]),
     }
@@ -337,6 +338,21 @@ def _bind(width):
             fn = self.L.resampleProcessAndFlushInterleavedDevice if and_flush else self.L.resampleProcessInterleavedDevice
             r = fn(self.p, _dev_ptr(d_in), n_in, _dev_ptr(d_out), out_cap, ratio)
             return r.input_used, r.output_generated
+
+        def process_schedule_device(self, d_in, n_ins, d_out, caps, ratios, flush_last=False):
+            """resampleProcessScheduleInterleavedDevice: blocks k = 0, 1, ... of this stream, contiguous in d_in, outputs packed in d_out
+            (which holds sum(caps) frames).  Returns (blocks_made, [(input_used, output_generated), ...]); raises if a launch failed."""
+            n = len(n_ins)
+            if len(caps) != n or len(ratios) != n:
+                raise ValueError("n_ins, caps and ratios must have one entry per block")
+            res = (ResampleResult * max(n, 1))()
+            rc = self.L.resampleProcessScheduleInterleavedDevice(
+                self.p, n, _dev_ptr(d_in), (C.c_int * max(n, 1))(*[int(v) for v in n_ins]), _dev_ptr(d_out),
+                (C.c_int * max(n, 1))(*[int(v) for v in caps]), (C.c_double * max(n, 1))(*[float(v) for v in ratios]),
+                1 if flush_last else 0, res)
+            if rc < 0:
+                raise RuntimeError("resampleProcessScheduleInterleavedDevice failed")
+            return rc, [(res[k].input_used, res[k].output_generated) for k in range(n)]
 
         def process_planar_device(self, d_in, in_pitch, n_in, d_out, out_pitch, out_cap, ratio):
             r = self.L.resampleProcessPlanarDevice(self.p, _dev_ptr(d_in), in_pitch, n_in, _dev_ptr(d_out), out_pitch, out_cap, ratio)

@@ -169,6 +169,28 @@ void   arthip_fir_rows_cache_free (void *cache);
 size_t arthip_fir_batch_item_bytes (void);
 int arthip_fir_batch_max_segments (void);                /* ring-epoch segments a batched call may have */
 int arthip_fir_batch (const ArtFirArgs *a, const ArtSegTable *segs, int n, void *d_table, void *stream);
+/* Consecutive blocks of ONE stream as one general-kernel launch (resampleProcessScheduleInterleavedDevice).  The run's linear space is
+ * (history ++ run input); a block is the single call it replaces, moved in_off frames along it. */
+typedef struct {
+    double ratio;                        /* the block's effective ratio */
+    unsigned int out_off, outputs;       /* its first output frame within the run's output, and its output frames (> 0) */
+    int in_off, in_end;                  /* its first input frame within the run's input, and the end of what it may read (in_off + input used) */
+    int lin_floor;                       /* run-linear index below which its reads are silence (>= in_off) */
+    int seg_begin, seg_end;              /* its segments in the run's segment array (first_output block-relative, lin_base the block's own) */
+    unsigned int first_tile;             /* filled by arthip_fir_schedule */
+    int pad;
+} ArtSchedBlock;
+typedef struct { unsigned int first; int lin_base; double base; } ArtSchedSeg;
+/* may this block (its planned segments, outputs) be part of a run?  (its tile's span must fit the LDS, and a tile may touch only as many
+ * segments as the kernel rebuilds) */
+int arthip_fir_schedule_accepts (const ArtFirArgs *block, const ArtamdSegment *segs, int nseg, unsigned int outputs);
+/* One launch over the run's blocks.  `run` = the run's FIR arguments (hist, in = the run's input, out = the run's output, in_frames and
+ * roll_appended = the run's input frames, roll_dst, timing events); d_table: device memory of arthip_fir_schedule_bytes bytes (reused run
+ * after run: stream order protects it).  Returns ART_KERNEL_GENERAL | ART_FIR_ROLLED, or -1 with nothing enqueued. */
+size_t arthip_fir_schedule_bytes (int nblocks, int nsegs);
+int arthip_fir_schedule (const ArtFirArgs *run, ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs, int nsegs, void *d_table, void *stream);
+/* the upkeep every launch of a rational-ratio stream does for the rows kept across calls (arthip_fir calls it itself) */
+void arthip_fir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs);
 /* new_hist[H][C] = last H frames of (hist ++ in[0..appended)); in may be NULL => zeros appended */
 int arthip_roll_history (art_s *new_hist, const art_s *hist, const art_s *in, long in_pitch, int appended, int H, int C, void *stream);
 int arthip_interleave (art_s *dst, const art_s *src_planar, long pitch, int frames, int C, void *stream);

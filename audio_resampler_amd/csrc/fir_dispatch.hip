@@ -3,6 +3,15 @@
 #include <atomic>
 #include <cstdlib>
 
+// (test hook, tests/test_gpu_failure_path.py: ARTAMD_TEST_FAIL_FIR=k makes the k-th FIR launch of the process — a call's launch, or a schedule's
+// run — fail before anything is enqueued: the only way to see the host's failure path without breaking a device)
+bool artfir_test_fail ()
+{
+    static const int fail_at = [] { const char *e = getenv ("ARTAMD_TEST_FAIL_FIR"); return e && *e ? atoi (e) : 0; } ();
+    static std::atomic<int> launches { 0 };
+    return fail_at > 0 && ++launches == fail_at;
+}
+
 extern "C" {
 
 int artamdPeriodMultiple (int outputsPerPeriod) { return outputsPerPeriod > 0 ? artfir_period_multiple (outputsPerPeriod, 32) : 0; }
@@ -95,6 +104,8 @@ static int fir_in_groups (const ArtFirArgs *a, const ArtSegTable *segs, int kern
     return (rc & ~ART_FIR_ROLLED) | (a->roll_dst ? ART_FIR_ROLLED : 0);
 }
 
+void arthip_fir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs) { artfir_rows_touch (a, segs); }
+
 void arthip_fir_needs (const ArtFirArgs *call, const ArtSegTable *first, unsigned int outputs, int kernel_pref, ArtFirNeeds *n)
 {
     *n = ArtFirNeeds ();
@@ -112,12 +123,7 @@ int arthip_fir (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, v
     hipStream_t st = (hipStream_t) stream;
 
     if (a->n_end <= a->n_begin) return ART_KERNEL_GENERAL;
-    {   // (test hook, tests/test_gpu_failure_path.py: ARTAMD_TEST_FAIL_FIR=k makes the k-th FIR launch of the process fail before anything is enqueued —
-        // the only way to see the host's failure path without breaking a device)
-        static const int fail_at = [] { const char *e = getenv ("ARTAMD_TEST_FAIL_FIR"); return e && *e ? atoi (e) : 0; } ();
-        static std::atomic<int> launches { 0 };
-        if (fail_at > 0 && ++launches == fail_at) return -1;
-    }
+    if (artfir_test_fail ()) return -1;
     artfir_rows_touch (a, segs);                              // (the canonical period of the rows kept across calls: every launch looks after it)
 
     // (a table that is only the first of the call's, arthip_fir_needs' one_launch: the streaming matrix-core kernels run such a launch, every other path

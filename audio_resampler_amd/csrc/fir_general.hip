@@ -4,6 +4,7 @@
 //
 // Reference semantics restated (not translated): reference resampler.c:1135-1181 (subsample_*), :1033-1057 (apply_filter*).
 // Compiled with -ffp-contract=off: the only fused multiply-adds are the explicit ones of the default mode.
+#include <cstring>
 #include "fir_common.hip.h"
 
 namespace {
@@ -20,8 +21,24 @@ constexpr int GEN_MAX_TILE = 48;
 // reduction and the per-output bookkeeping are then paid once per FOUR outputs, which is most of the cost when taps x
 // channels is small).  G depends on the tap count only, never on the tile, so a frame's value does not depend on how a
 // call is cut up.
+// The launch's extra workgroups (x only, y == 0) roll the history for the next call: reads hist ++ in, writes the OTHER history buffer
+// (independent of everything else in flight) — one launch less per call.  rb: the workgroup's index among them.
+__device__ __forceinline__ void general_roll (const ArtFirArgs &a, unsigned int rb, unsigned int by)
+{
+    if (by) return;
+    const int e = (int) rb * GEN_THREADS + (int) threadIdx.x;
+    if (e < a.H * a.C) {
+        const int f = e / a.C, c = e - f * a.C, lin = a.roll_appended + f;
+        art_s v = 0;
+        if (lin < a.H) v = a.hist [(size_t) lin * a.C + c];
+        else if (a.in) { const int gi = lin - a.H; v = a.in_pitch ? a.in [(size_t) c * a.in_pitch + gi] : a.in [(size_t) gi * a.C + c]; }
+        a.roll_dst [e] = v;
+    }
+}
+
+// One tile: the `cnt` consecutive outputs from n0 (call-relative), channel group `by`.
 template <int CG, bool INTERP, bool PRECISE, int G, bool PIPE = false, int LEAN = 0>
-__device__ __forceinline__ void fir_general_body (const ArtFirArgs &a, const ArtSegTable &segs, int tile, unsigned int bx, unsigned int by)
+__device__ __forceinline__ void fir_general_tile (const ArtFirArgs &a, const ArtSegTable &segs, unsigned int n0, int cnt, unsigned int by)
 {
     constexpr int SUBS = 64 / G;
     using Acc = typename std::conditional<PRECISE || ART_WIDE, double, float>::type;   // 8-byte samples accumulate in double
@@ -33,33 +50,7 @@ __device__ __forceinline__ void fir_general_body (const ArtFirArgs &a, const Art
     const int sub = lane / G, l = lane % G;       // output within the wave, lane within the output's group
     const int ch0 = by * CG;
     const int half = a.T / 2;
-    // Blocks [0, 8 * per_xcd) evaluate one tile of outputs each, XCD-aware: workgroup b is dispatched to XCD b % 8, consecutive
-    // tiles stage overlapping input spans (a tile's span is T + ~30 frames, its neighbour's starts ~30 frames later), so
-    // XCD x takes the CONTIGUOUS tiles [x * per_xcd, (x + 1) * per_xcd): its L2 then sees one eighth of the call's input
-    // instead of all of it (measured with round-robin tiles: 4.5x the algorithmic bytes from the fabric on the headline shape,
-    // 8.7x on the 65,536-frame stereo ASRC call).  Placement only affects speed.  Any
-    // further blocks (x only, y == 0) roll the history for the next call (reads hist ++ in, writes the OTHER history
-    // buffer: independent of everything else in flight) — one launch less per call.
-    const unsigned int tiles_total = (a.n_end - a.n_begin + (unsigned int) tile - 1) / (unsigned int) tile;
-    const unsigned int per_xcd = (tiles_total + 7u) / 8u, workers = 8u * per_xcd;
-    if (bx >= workers) {
-        if (by) return;
-        const int e = (int)(bx - workers) * GEN_THREADS + tid;
-        if (e < a.H * a.C) {
-            const int f = e / a.C, c = e - f * a.C, lin = a.roll_appended + f;
-            art_s v = 0;
-            if (lin < a.H) v = a.hist [(size_t) lin * a.C + c];
-            else if (a.in) { const int gi = lin - a.H; v = a.in_pitch ? a.in [(size_t) c * a.in_pitch + gi] : a.in [(size_t) gi * a.C + c]; }
-            a.roll_dst [e] = v;
-        }
-        return;
-    }
   {
-    const unsigned int tile_index = (bx & 7u) * per_xcd + (bx >> 3);
-    if (tile_index >= tiles_total) return;
-    const unsigned int n0 = a.n_begin + tile_index * (unsigned int) tile;
-    const int cnt = (int) min ((unsigned int) tile, a.n_end - n0);
-
     __syncthreads ();
     if (tid < cnt) {
         Pos p = locate<INTERP> (a, segs, n0 + tid);
@@ -331,6 +322,23 @@ __device__ __forceinline__ void fir_general_body (const ArtFirArgs &a, const Art
   }
 }
 
+// Blocks [0, 8 * per_xcd) evaluate one tile of outputs each, XCD-aware: workgroup b is dispatched to XCD b % 8, consecutive
+// tiles stage overlapping input spans (a tile's span is T + ~30 frames, its neighbour's starts ~30 frames later), so
+// XCD x takes the CONTIGUOUS tiles [x * per_xcd, (x + 1) * per_xcd): its L2 then sees one eighth of the call's input
+// instead of all of it (measured with round-robin tiles: 4.5x the algorithmic bytes from the fabric on the headline shape,
+// 8.7x on the 65,536-frame stereo ASRC call).  Placement only affects speed.  Any further blocks roll the history.
+template <int CG, bool INTERP, bool PRECISE, int G, bool PIPE = false, int LEAN = 0>
+__device__ __forceinline__ void fir_general_body (const ArtFirArgs &a, const ArtSegTable &segs, int tile, unsigned int bx, unsigned int by)
+{
+    const unsigned int tiles_total = (a.n_end - a.n_begin + (unsigned int) tile - 1) / (unsigned int) tile;
+    const unsigned int per_xcd = (tiles_total + 7u) / 8u, workers = 8u * per_xcd;
+    if (bx >= workers) { general_roll (a, bx - workers, by); return; }
+    const unsigned int tile_index = (bx & 7u) * per_xcd + (bx >> 3);
+    if (tile_index >= tiles_total) return;
+    const unsigned int n0 = a.n_begin + tile_index * (unsigned int) tile;
+    fir_general_tile<CG, INTERP, PRECISE, G, PIPE, LEAN> (a, segs, n0, (int) min ((unsigned int) tile, a.n_end - n0), by);
+}
+
 template <int CG, bool INTERP, bool PRECISE, int G, bool PIPE, int LEAN>
 __global__ __launch_bounds__ (GEN_THREADS)
 void fir_general_kernel (ArtFirArgs a, ArtSegTable segs, int tile)
@@ -364,6 +372,62 @@ void fir_general_batch_kernel (const FirBatchItem *items)
     if (threadIdx.x == 0) { s_tab.count = it.seg_count; s_tab.lin_floor = it.lin_floor; }
     __syncthreads ();
     fir_general_body<CG, INTERP, PRECISE, G> (it.a, s_tab, it.tile, blockIdx.x, blockIdx.y);
+}
+
+// Consecutive blocks of ONE stream, one launch (resampleProcessScheduleInterleavedDevice): the tiles of every block of the run, one
+// list, in the single launch's XCD-contiguous layout (the blocks' inputs follow one another: neighbouring tiles share their input in
+// the L2).  A tile never straddles a block, so it has one ratio, one floor and block-relative outputs: locate () evaluates
+// base + n / ratio with the block's own n and ratio, exactly as the block's single call does.  The block's linear space is the run's
+// moved by in_off frames (the history after k blocks is the last H frames of what came before), reads at or past its own input's end
+// are silence as in its single call (in_end).  Its segments sit in one array for the run (a 65,536-frame block of a 16-tap filter has
+// ~270 ring epochs: more than a table in kernel arguments holds); the workgroup copies the few its tile touches into the table the
+// body expects, as the batched kernel does.
+constexpr int SCHED_SEGS = 4;                       // segments a tile may touch (the host checks: arthip_fir_schedule_accepts)
+
+template <int CG, bool INTERP, bool PRECISE, int G, bool PIPE, int LEAN>
+__global__ __launch_bounds__ (GEN_THREADS)
+void fir_general_schedule_kernel (ArtFirArgs run, const ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs, unsigned int tiles_total, int tile)
+{
+    __shared__ ArtSegTable s_tab;
+    __shared__ int s_blk, s_seg0, s_seg1;
+    const unsigned int per_xcd = (tiles_total + 7u) / 8u, workers = 8u * per_xcd;
+    if (blockIdx.x >= workers) { general_roll (run, blockIdx.x - workers, blockIdx.y); return; }
+    const unsigned int g = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    if (g >= tiles_total) return;
+    const int tid = threadIdx.x;
+
+    // the tile's block: the last whose first tile is <= g (every block has a tile at least)
+    if (tid == 0) { s_blk = 0; s_seg0 = 0; s_seg1 = 0; }
+    __syncthreads ();
+    for (int b = tid; b < nblocks; b += GEN_THREADS)
+        if (blocks [b].first_tile <= g) atomicMax (&s_blk, b);
+    __syncthreads ();
+    const ArtSchedBlock &blk = blocks [s_blk];
+    const unsigned int n0 = (g - blk.first_tile) * (unsigned int) tile;
+    const int cnt = (int) min ((unsigned int) tile, blk.outputs - n0);
+
+    // the segments of its first and its last output (the block's first segment starts at output 0)
+    for (int q = blk.seg_begin + tid; q < blk.seg_end; q += GEN_THREADS) {
+        const unsigned int f = segs [q].first;
+        if (f <= n0) atomicMax (&s_seg0, q);
+        if (f <= n0 + (unsigned int)(cnt - 1)) atomicMax (&s_seg1, q);
+    }
+    __syncthreads ();
+    const int q0 = s_seg0 > blk.seg_begin ? s_seg0 : blk.seg_begin;
+    const int count = min (s_seg1 - q0 + 1, SCHED_SEGS);
+    if (tid < count) {
+        s_tab.first [tid] = segs [q0 + tid].first;
+        s_tab.lin_base [tid] = segs [q0 + tid].lin_base + blk.in_off;
+        s_tab.base [tid] = segs [q0 + tid].base;
+    }
+    if (tid == 0) { s_tab.count = count; s_tab.lin_floor = blk.lin_floor; }
+    // (the body's first barrier publishes the table)
+
+    ArtFirArgs a = run;
+    a.ratio = blk.ratio;
+    a.in_frames = blk.in_end;
+    a.out = run.out + (size_t) blk.out_off * run.C;
+    fir_general_tile<CG, INTERP, PRECISE, G, PIPE, LEAN> (a, s_tab, n0, cnt, blockIdx.y);
 }
 
 // Strict kernel: one lane per output sample, taps visited in the reference's source order
@@ -479,30 +543,43 @@ bool general_geometry (const ArtFirArgs &a, int *tile_out, size_t *lds_out, dim3
     return true;
 }
 
+// The tap loop a shape takes (every form takes the same taps in the same order: the same bits; fir_general_batch_kernel runs the plain loop).
+// Four channels and more: the pipelined loop for long filters, the plain loop below 512 taps.  One and two channels: round 5's
+// lean loop (LEAN 1), and for 4-byte STEREO streams the lean loop with its first round's coefficient loads issued before the
+// staging (LEAN 2) — config E 12.5 -> 12.0 us a call, stereo interpolating 16.6 -> 16.4; mono loses (68 -> 78 registers: 11.0
+// against 10.2 us) and keeps 1: profiles/r6_config_e.txt.  `go` receives the form as integral constants (interp, precise, group, pipe, lean).
+template <int CG, typename Go>
+void general_form (const ArtFirArgs &a, Go go)
+{
+    using std::integral_constant;
+    constexpr int LEAN = CG >= 4 ? 0 : CG == 2 && sizeof (art_s) == 4 ? 2 : 1;
+    auto loop = [&] (auto i, auto p, auto gg) {
+        if constexpr (CG >= 4) { if (a.T >= 512) go (i, p, gg, integral_constant<bool, true> (), integral_constant<int, 0> ());
+                                 else go (i, p, gg, integral_constant<bool, false> (), integral_constant<int, 0> ()); }
+        else go (i, p, gg, integral_constant<bool, false> (), integral_constant<int, LEAN> ());
+    };
+    auto group = [&] (auto i, auto p) {
+        const int gg = general_group (a.T);
+        if (gg == 16) loop (i, p, integral_constant<int, 16> ());
+        else if (gg == 32) loop (i, p, integral_constant<int, 32> ());
+        else loop (i, p, integral_constant<int, 64> ());
+    };
+    const bool precise = (a.mode & 3) == ART_MODE_PRECISE;
+    using T_ = integral_constant<bool, true>; using F_ = integral_constant<bool, false>;
+    if (a.interpolate) { if (precise) group (T_ (), T_ ()); else group (T_ (), F_ ()); }
+    else               { if (precise) group (F_ (), T_ ()); else group (F_ (), F_ ()); }
+}
+
 template <int CG>
 int launch_general (const ArtFirArgs &a, const ArtSegTable &segs, hipStream_t st)
 {
     int tile; size_t lds; dim3 grid;
     if (!general_geometry<CG> (a, &tile, &lds, &grid)) return -1;
-    const bool precise = (a.mode & 3) == ART_MODE_PRECISE;
-
-#define GO(I, P) do { const int gg = general_group (a.T); if (gg == 16) GO_ (I, P, 16); else if (gg == 32) GO_ (I, P, 32); else GO_ (I, P, 64); } while (0)
-    // The tap loop (every form takes the same taps in the same order: the same bits; fir_general_batch_kernel runs the plain loop).
-    // Four channels and more: the pipelined loop for long filters, the plain loop below 512 taps.  One and two channels: round 5's
-    // lean loop (LEAN 1), and for 4-byte STEREO streams the lean loop with its first round's coefficient loads issued before the
-    // staging (LEAN 2) — config E 12.5 -> 12.0 us a call, stereo interpolating 16.6 -> 16.4; mono loses (68 -> 78 registers: 11.0
-    // against 10.2 us) and keeps 1: profiles/r6_config_e.txt
-    constexpr int LEAN = CG >= 4 ? 0 : CG == 2 && sizeof (art_s) == 4 ? 2 : 1;
-#define GO_(I, P, GG) do { if constexpr (CG >= 4) { if (a.T >= 512) GO__ (I, P, GG, true, 0); else GO__ (I, P, GG, false, 0); } \
-        else GO__ (I, P, GG, false, LEAN); } while (0)
-#define GO__(I, P, GG, PP, LL) do { auto k = fir_general_kernel<CG, I, P, GG, PP, LL>; \
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); \
-        hipLaunchKernelGGL (k, grid, dim3 (GEN_THREADS), lds, st, a, segs, tile); } while (0)
-    if (a.interpolate) { if (precise) GO (true, true); else GO (true, false); }
-    else               { if (precise) GO (false, true); else GO (false, false); }
-#undef GO
-#undef GO_
-#undef GO__
+    general_form<CG> (a, [&] (auto i, auto p, auto gg, auto pp, auto ll) {
+        auto k = fir_general_kernel<CG, decltype (i)::value, decltype (p)::value, decltype (gg)::value, decltype (pp)::value, decltype (ll)::value>;
+        if (lds > 48 * 1024) (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+        hipLaunchKernelGGL (k, grid, dim3 (GEN_THREADS), lds, st, a, segs, tile);
+    });
     return 0;
 }
 
@@ -539,6 +616,80 @@ int batch_variant (const ArtFirArgs *a, const ArtSegTable *segs, const int *whic
 }
 
 
+// Pinned staging of the argument tables of the batched and the scheduled launches (per calling thread, kept): a table goes to the
+// device without the runtime's bounce through its own pinned buffers.  Two tables take turns, each guarded by an event recorded
+// after the copies out of it: the call returns without waiting for the stream, and the host plans the next one while this one runs.
+struct Staging { void *host; size_t cap; hipEvent_t ev; bool pending; };
+
+// the next turn's table, of `bytes` bytes at least (nullptr: out of memory)
+Staging *staging_take (size_t bytes)
+{
+    static thread_local Staging tl [2] = { { nullptr, 0, nullptr, false }, { nullptr, 0, nullptr, false } };
+    static thread_local int tl_turn = 0;
+    Staging &sg = tl [tl_turn ^= 1];
+    if (sg.pending) { (void) hipEventSynchronize (sg.ev); sg.pending = false; }
+    if (!sg.ev && hipEventCreateWithFlags (&sg.ev, hipEventDisableTiming) != hipSuccess) { sg.ev = nullptr; return nullptr; }
+    if (bytes > sg.cap) {
+        if (sg.host) (void) hipHostFree (sg.host);
+        sg.cap = bytes + bytes / 2 + 64 * sizeof (FirBatchItem);
+        if (hipHostMalloc (&sg.host, sg.cap, hipHostMallocDefault) != hipSuccess) { sg.host = nullptr; sg.cap = 0; return nullptr; }
+    }
+    return &sg;
+}
+
+// the table must outlive the asynchronous copies out of it: marked here, waited for before its next turn.  -1: neither could be made sure of
+int staging_give (Staging *sg, hipStream_t st)
+{
+    if (hipEventRecord (sg->ev, st) == hipSuccess) { sg->pending = true; return 0; }
+    return hipStreamSynchronize (st) == hipSuccess ? 0 : -1;
+}
+
+// Can a block join a run?  The run's tile is at most GEN_MAX_TILE outputs whatever the run's other blocks are: the block's span at
+// that tile must fit the LDS (otherwise its single call goes to the strict kernel), and any GEN_MAX_TILE consecutive outputs of it may
+// touch SCHED_SEGS segments at most.  (A block turned away is made as its single call: the same samples.)
+template <int CG>
+int schedule_accepts (const ArtFirArgs &a, const ArtamdSegment *segs, int nseg, unsigned int outputs)
+{
+    if (!(a.ratio > 0.0) || (double) a.T + ceil (GEN_MAX_TILE / a.ratio) + 3.0 > (double)((64 * 1024) / ((int) sizeof (art_s) * CG))) return 0;
+    // (segments q .. q + SCHED_SEGS - 1 all starting inside one window of GEN_MAX_TILE outputs, or a later one's start in the window of q: too many)
+    for (int q = 0; q + SCHED_SEGS < nseg; ++q)
+        if (segs [q + SCHED_SEGS].first_output < outputs && segs [q + SCHED_SEGS].first_output - segs [q + 1].first_output < (unsigned int) GEN_MAX_TILE) return 0;
+    return 1;
+}
+
+// One launch over the run's blocks: the tile from the run's outputs and its SMALLEST ratio (the span bound depends on the ratio; an
+// output's bits do not depend on its tile), the tap-loop form of the single launch.
+template <int CG>
+int launch_schedule (const ArtFirArgs &run, ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs, int nsegs, void *d_table, hipStream_t st)
+{
+    ArtFirArgs a = run;
+    unsigned int outputs = 0;
+    for (int b = 0; b < nblocks; ++b) { outputs += blocks [b].outputs; if (blocks [b].ratio < a.ratio || b == 0) a.ratio = blocks [b].ratio; }
+    a.n_begin = 0; a.n_end = outputs;
+    int tile; size_t lds; dim3 grid;
+    if (!general_geometry<CG> (a, &tile, &lds, &grid)) return -1;
+    unsigned int tiles = 0;
+    for (int b = 0; b < nblocks; ++b) { blocks [b].first_tile = tiles; tiles += (blocks [b].outputs + (unsigned int) tile - 1) / (unsigned int) tile; }
+    const size_t bytes_b = sizeof (ArtSchedBlock) * (size_t) nblocks, bytes = arthip_fir_schedule_bytes (nblocks, nsegs);
+    Staging *sg = staging_take (bytes);
+    if (!sg) return -1;
+    std::memcpy (sg->host, blocks, bytes_b);
+    std::memcpy ((char *) sg->host + bytes_b, segs, bytes - bytes_b);
+    if (hipMemcpyAsync (d_table, sg->host, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { (void) staging_give (sg, st); return -1; }
+    const unsigned int roll_blocks = a.roll_dst ? (unsigned int)((a.H * a.C + GEN_THREADS - 1) / GEN_THREADS) : 0u;
+    grid.x = 8u * ((tiles + 7u) / 8u) + roll_blocks;
+    if (a.ev_start) (void) hipEventRecord ((hipEvent_t) a.ev_start, st);
+    general_form<CG> (a, [&] (auto i, auto p, auto gg, auto pp, auto ll) {
+        auto k = fir_general_schedule_kernel<CG, decltype (i)::value, decltype (p)::value, decltype (gg)::value, decltype (pp)::value, decltype (ll)::value>;
+        if (lds > 48 * 1024) (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+        hipLaunchKernelGGL (k, grid, dim3 (GEN_THREADS), lds, st, run, (const ArtSchedBlock *) d_table, nblocks,
+                            (const ArtSchedSeg *)((const char *) d_table + bytes_b), tiles, tile);
+    });
+    if (a.ev_stop) (void) hipEventRecord ((hipEvent_t) a.ev_stop, st);
+    const bool ok = hipGetLastError () == hipSuccess;
+    return staging_give (sg, st) || !ok ? -1 : 0;
+}
+
 } // namespace
 
 // the general kernel on one call (default / precise mode); -1 when the tile's input span cannot fit the LDS
@@ -573,21 +724,9 @@ int arthip_fir_batch (const ArtFirArgs *a, const ArtSegTable *segs, int n, void 
 {
     hipStream_t st = (hipStream_t) stream;
     if (n <= 0) return 0;
-    // pinned staging (per calling thread, kept): the table goes to the device without the runtime's bounce through its own
-    // pinned buffers.  Two tables take turns, each guarded by an event recorded after the copies out of it: the call
-    // returns without waiting for the stream, and the host plans the next tick while this one runs.
-    struct Staging { FirBatchItem *host; size_t cap; hipEvent_t ev; bool pending; };
-    static thread_local Staging tl [2] = { { nullptr, 0, nullptr, false }, { nullptr, 0, nullptr, false } };
-    static thread_local int tl_turn = 0;
-    Staging &sg = tl [tl_turn ^= 1];
-    if (sg.pending) { (void) hipEventSynchronize (sg.ev); sg.pending = false; }
-    if (!sg.ev && hipEventCreateWithFlags (&sg.ev, hipEventDisableTiming) != hipSuccess) { sg.ev = nullptr; return -1; }
-    if ((size_t) n > sg.cap) {
-        if (sg.host) (void) hipHostFree (sg.host);
-        sg.cap = (size_t) n + (size_t) n / 2 + 64;
-        if (hipHostMalloc ((void **) &sg.host, sizeof (FirBatchItem) * sg.cap, hipHostMallocDefault) != hipSuccess) { sg.host = nullptr; sg.cap = 0; return -1; }
-    }
-    FirBatchItem *host = sg.host;
+    Staging *sg = staging_take (sizeof (FirBatchItem) * (size_t) n);
+    if (!sg) return -1;
+    FirBatchItem *host = (FirBatchItem *) sg->host;
     int *which = (int *) malloc (sizeof (int) * (size_t) n);
     if (!which) return -1;
     int rc = 0, done = 0;
@@ -614,11 +753,27 @@ int arthip_fir_batch (const ArtFirArgs *a, const ArtSegTable *segs, int n, void 
             }
             done += count;
         }
-    // the host table must outlive the asynchronous copies out of it: marked here, waited for before its next turn
-    if (hipEventRecord (sg.ev, st) == hipSuccess) sg.pending = true;
-    else if (hipStreamSynchronize (st) != hipSuccess) rc = -1;
+    if (staging_give (sg, st)) rc = -1;
     free (which);
     return rc;
+}
+
+size_t arthip_fir_schedule_bytes (int nblocks, int nsegs) { return sizeof (ArtSchedBlock) * (size_t) nblocks + sizeof (ArtSchedSeg) * (size_t) nsegs; }
+
+int arthip_fir_schedule_accepts (const ArtFirArgs *a, const ArtamdSegment *segs, int nseg, unsigned int outputs)
+{
+    return a->C > 4 ? schedule_accepts<8> (*a, segs, nseg, outputs) : a->C > 2 ? schedule_accepts<4> (*a, segs, nseg, outputs) :
+           a->C == 2 ? schedule_accepts<2> (*a, segs, nseg, outputs) : schedule_accepts<1> (*a, segs, nseg, outputs);
+}
+
+int arthip_fir_schedule (const ArtFirArgs *run, ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs, int nsegs, void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    if (nblocks <= 0 || artfir_test_fail ()) return -1;
+    const ArtFirArgs &a = *run;
+    const int rc = a.C > 4 ? launch_schedule<8> (a, blocks, nblocks, segs, nsegs, d_table, st) : a.C > 2 ? launch_schedule<4> (a, blocks, nblocks, segs, nsegs, d_table, st) :
+                   a.C == 2 ? launch_schedule<2> (a, blocks, nblocks, segs, nsegs, d_table, st) : launch_schedule<1> (a, blocks, nblocks, segs, nsegs, d_table, st);
+    return rc ? -1 : (ART_KERNEL_GENERAL | (a.roll_dst ? ART_FIR_ROLLED : 0));
 }
 
 int arthip_roll_history (art_s *new_hist, const art_s *hist, const art_s *in, long in_pitch, int appended, int H, int C, void *stream)

@@ -9,3 +9,4 @@ bool artfir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int
 int  artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, void *stream);    // fir_matrix.hip | fir_matrix64.hip
 void artfir_matrix_needs (const ArtFirArgs *a, const ArtSegTable *first, int kernel_pref, ArtFirNeeds *n);   // fir_matrix.hip | fir_matrix64.hip (nothing)
 void artfir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs);                               // fir_matrix.hip | fir_matrix64.hip (nothing)
+bool artfir_test_fail ();                                                                             // fir_dispatch.hip: the ARTAMD_TEST_FAIL_FIR hook, one count per FIR launch

@@ -76,6 +76,7 @@ struct artamd_resampler {
     int last_fixed [4];                      /* its last launch of the last call: flag value (0: none), mask words, chunks per tile, kernel form (art_hip.h) */
     unsigned int *d_fix; size_t fix_cap;    /* [0] per-launch, [1] running count of outputs the matrix kernels evaluated off-pattern */
     void *d_batch; size_t batch_cap;         /* argument table of the batched calls led by this context */
+    void *d_sched; size_t sched_cap;         /* block and segment tables of the scheduled runs (resampleProcessScheduleInterleavedDevice) */
     unsigned long batch_stamp;               /* last batched call this context took part in (duplicate check) */
 };
 
@@ -701,7 +702,7 @@ void resampleFree (Resample *cxt)
         bank_release (hip->bank); arthip_free (hip->d_hist [0]); arthip_free (hip->d_hist [1]);
         {   /* every device buffer the context may have grown (NULL where it never did) */
             void *const device_buffers [] = { hip->d_in, hip->d_out, hip->d_tmp, hip->d_fix, hip->d_scratch, hip->d_pad, hip->d_planes, hip->d_rows,
-                                              hip->d_split, hip->d_patch, hip->d_batch };
+                                              hip->d_split, hip->d_patch, hip->d_batch, hip->d_sched };
             for (size_t i = 0; i < sizeof (device_buffers) / sizeof (device_buffers [0]); ++i) arthip_free (device_buffers [i]);
         }
         if (hip->rows_cache) { arthip_fir_rows_cache_free (hip->rows_cache); free (hip->rows_cache); }
@@ -1200,6 +1201,16 @@ static void fill_args (Resample *cxt, ArtFirArgs *a, double ratio, const art_s *
     a->period_out = hip->period_out; a->period_in = hip->period_in;
 }
 
+/* the canonical period of the rows the matrix kernels keep across calls: looked after by every launch of a rational-ratio stream,
+ * whichever kernel runs it (fir_matrix.hip, artfir_rows_touch) — not by a flush's */
+static void keep_rows (struct artamd_resampler *hip, ArtFirArgs *a)
+{
+    if (a->period_out && a->mode == ART_MODE_FAST && !hip->rows_off) {
+        if (!hip->rows_cache && arthip_fir_rows_cache_bytes ()) hip->rows_cache = calloc (1, arthip_fir_rows_cache_bytes ());
+        a->rows_cache = hip->rows_cache;
+    }
+}
+
 /* grow a device buffer; a new one starts with its first `head` bytes zero */
 static void *grow_zeroed (void *dev, size_t *cap, size_t need, size_t head, void *stream)
 {
@@ -1326,12 +1337,7 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
         ArtSegTable tab;
         fill_args (cxt, &a, ratio, is_flush ? flush_in : d_in, is_flush ? 0 : in_pitch, is_flush ? (flush_in ? T / 2 : 0) : (int) res.input_used,
                    d_out, out_pitch);
-        /* the canonical period of the rows the matrix kernels keep across calls: looked after by every launch of a rational-ratio stream,
-         * whichever kernel runs it (fir_matrix.hip, artfir_rows_touch) */
-        if (a.period_out && a.mode == ART_MODE_FAST && !hip->rows_off && !is_flush) {
-            if (!hip->rows_cache && arthip_fir_rows_cache_bytes ()) hip->rows_cache = calloc (1, arthip_fir_rows_cache_bytes ());
-            a.rows_cache = hip->rows_cache;
-        }
+        if (!is_flush) keep_rows (hip, &a);
         /* what the call's launches need (a flush runs on the general kernel) */
         ArtFirNeeds needs;
         memset (&needs, 0, sizeof (needs));
@@ -1404,14 +1410,33 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
  * the remaining calls (flushes, strict mode, endpoint extrapolation, calls big enough for the matrix-core path, contexts
  * under the cut-invariant policy, other streams) one by one.  results [i] is what resampleProcessInterleavedDevice
  * (cxts [i], ...) would have returned. */
+/* A context whose ordinary calls may be gathered with others (batched streams, scheduled blocks): not sharded, and neither strict order,
+ * endpoint extrapolation nor a flushed stream (those calls are made as they stand) */
+static int gatherable_context (const Resample *cxt)
+{
+    return !cxt->hip->nshards && !(cxt->flags & (EXTRAPOLATE_ENDPOINTS | RESAMPLE_STRICT_ORDER | RESAMPLER_FLUSHED));
+}
+
+/* Does the single call give this planned call (its FIR arguments, first table, outputs) to the general kernel?  The cut-invariant policy keeps
+ * a rational-ratio stream's calls for itself (every launch anchored on the stream's canonical period, or counted where it cannot be: the
+ * single call decides that, with the context's kept rows); a call big enough for the matrix-core path is that path's (the same question the
+ * single call asks) */
+static int general_call (const Resample *cxt, const ArtFirArgs *a, const ArtSegTable *first, unsigned int outputs)
+{
+    const struct artamd_resampler *hip = cxt->hip;
+    if (hip->kernel_pref == ART_KERNEL_INVARIANT && a->period_out && a->mode == ART_MODE_FAST) return 0;
+    ArtFirNeeds needs;
+    arthip_fir_needs (a, first, outputs, hip->kernel_pref, &needs);
+    return !needs.matrix;
+}
+
 static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, int cap, double ratio, void *lead_stream,
                        ArtFirArgs *a, ArtSegTable *tab, ResampleResult *res, ArtamdPosition *trial)
 {
     struct artamd_resampler *hip = cxt->hip;
     int lin_floor;
 
-    if (nIn < 0 || hip->stream != lead_stream || hip->timing || hip->nshards || hip->device != arthip_current_device () ||
-        (cxt->flags & (EXTRAPOLATE_ENDPOINTS | RESAMPLE_STRICT_ORDER | RESAMPLER_FLUSHED))) return 0;
+    if (nIn < 0 || hip->stream != lead_stream || hip->timing || hip->device != arthip_current_device () || !gatherable_context (cxt)) return 0;
 
     const int nseg = plan_segments (cxt, nIn, cap, ratio, trial, res, &lin_floor);      /* (out of memory: the one-by-one path reports it) */
     if (nseg < 0 || nseg > arthip_fir_batch_max_segments () || res->output_generated == 0) return 0;
@@ -1419,15 +1444,7 @@ static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, 
     fill_args (cxt, a, ratio, d_in, 0, (int) res->input_used, d_out, 0);
     seg_table (hip, 0, nseg, lin_floor, tab);
     a->n_begin = hip->segs [0].first_output; a->n_end = res->output_generated;
-
-    /* the cut-invariant policy: every launch of a rational-ratio stream anchored on its canonical period, or counted where it cannot be — the
-     * single call decides that, with the context's kept rows (a call shorter than one period is the matrix path's only with them) */
-    if (hip->kernel_pref == ART_KERNEL_INVARIANT && a->period_out && a->mode == ART_MODE_FAST) return 0;
-
-    /* would the single call take the matrix-core path?  (the same question it asks) */
-    ArtFirNeeds needs;
-    arthip_fir_needs (a, tab, res->output_generated, hip->kernel_pref, &needs);
-    if (needs.matrix) return 0;
+    if (!general_call (cxt, a, tab, res->output_generated)) return 0;
 
     const int appended = (int) res->input_used;
     a->roll_dst = appended > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;      /* the launch takes the history roll along */
@@ -1487,6 +1504,181 @@ out:
     free (args); free (tabs); free (trials); free (owner);
     LEAVE_DEVICE (lead);
     return rc;
+}
+
+/* ---- consecutive blocks of one stream, one launch --------------------------------------------------------------------
+ * An ASRC loop makes a call per block with that block's ratio; each call is a launch with its own planning, staging and launch floor.
+ * Where the caller knows the next blocks' ratios, resampleProcessScheduleInterleavedDevice plans them one after the other on the context
+ * exactly as the single calls would, GATHERS those the single call would give to the general kernel into runs — one launch each
+ * (fir_general_schedule_kernel) and one history roll, riding along — and makes every other block (a flush, a block for the matrix-core
+ * path, a context the batch would not gather either) as its single call, behind the run before it.  A gathered block's position is
+ * committed as it is planned; its history only by its run's launch. */
+#define RUN_FRAMES_MAX (INT_MAX / 4)       /* input frames of one run: its linear indices (history ++ input) stay ints */
+
+typedef struct {
+    const art_s *in; art_s *out;         /* the run's first input / output frame */
+    int gathered, first;                 /* blocks in the run (outputs or not), the index of its first in `results` */
+    int frames; unsigned int outputs;    /* its input frames (appended to the history by its launch) and output frames */
+    ArtamdPosition start;                /* the context's position before the run */
+    ArtSchedBlock *blocks; int *floors; int nblocks, block_cap;     /* the blocks with outputs; their own lin_floor */
+    ArtSchedSeg *segs; int nsegs, seg_cap;
+} SchedRun;
+
+/* Plan block `k` as the single call would; gather it into the run if the general kernel is the single call's (1), else leave the context
+ * as it stands (0) */
+static int sched_gather (Resample *cxt, SchedRun *run, const art_s *in, int nIn, art_s *out, int cap, double ratio, ResampleResult *res, int k)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    ArtamdPosition trial;
+    ArtFirArgs a;
+    ArtSegTable tab;
+    int lin_floor;
+
+    if (!gatherable_context (cxt)) return 0;
+    const int nseg = plan_segments (cxt, nIn, cap, ratio, &trial, res, &lin_floor);
+    if (nseg < 0) return 0;                                              /* (out of memory: the single call reports it) */
+    if (res->output_generated) {
+        fill_args (cxt, &a, ratio, in, 0, (int) res->input_used, out, 0);
+        a.lin_origin = hip->lin_origin + run->frames;
+        keep_rows (hip, &a);
+        seg_table (hip, 0, nseg < ART_MAX_SEGS ? nseg : ART_MAX_SEGS, lin_floor, &tab);
+        if (!general_call (cxt, &a, &tab, res->output_generated) || !arthip_fir_schedule_accepts (&a, hip->segs, nseg, res->output_generated)) return 0;
+        if (run->nblocks == run->block_cap) {
+            const int want = run->block_cap ? 2 * run->block_cap : 16;
+            ArtSchedBlock *b = realloc (run->blocks, sizeof (ArtSchedBlock) * (size_t) want);
+            if (b) run->blocks = b;
+            int *f = realloc (run->floors, sizeof (int) * (size_t) want);
+            if (f) run->floors = f;
+            if (!b || !f) return 0;
+            run->block_cap = want;
+        }
+        if (run->nsegs + nseg > run->seg_cap) {
+            const int want = 2 * (run->nsegs + nseg) + 64;
+            ArtSchedSeg *g = realloc (run->segs, sizeof (ArtSchedSeg) * (size_t) want);
+            if (!g) return 0;
+            run->segs = g; run->seg_cap = want;
+        }
+        ArtSchedBlock *b = &run->blocks [run->nblocks];
+        memset (b, 0, sizeof (*b));
+        b->ratio = a.ratio;
+        b->out_off = run->outputs; b->outputs = res->output_generated;
+        b->in_off = run->frames; b->in_end = run->frames + (int) res->input_used;
+        b->lin_floor = run->frames + (lin_floor > 0 ? lin_floor : 0);      /* (load_frame: below the floor, or below 0) */
+        b->seg_begin = run->nsegs; b->seg_end = run->nsegs + nseg;
+        for (int q = 0; q < nseg; ++q) {
+            ArtSchedSeg *g = &run->segs [run->nsegs + q];
+            g->first = hip->segs [q].first_output; g->lin_base = hip->segs [q].lin_base; g->base = hip->segs [q].base_offset;
+        }
+        run->floors [run->nblocks++] = lin_floor;
+        run->nsegs += nseg;
+    }
+    if (!run->gathered++) { run->in = in; run->out = out; run->first = k; run->start = position_of (cxt); }
+    run->frames += (int) res->input_used; run->outputs += res->output_generated;
+    cxt->outputOffset = trial.outputOffset; cxt->inputIndex = trial.inputIndex;
+    cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (trial.flags & RESAMPLER_FLUSHED) |
+                 ((res->output_generated == 0) ? (cxt->flags & EXTRAPOLATE_PREFILL) : 0);
+    hip->floor_active = trial.floorActive;
+    return 1;
+}
+
+/* Launch the pending run and roll the history behind it.  -1: the launch failed — nothing of it was enqueued, the context is back where it
+ * stood before the run and the run's results are { 0, 0 } */
+static int sched_launch (Resample *cxt, SchedRun *run, ResampleResult *results)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    const int C = cxt->numChannels, H = HIST_FRAMES (cxt->numTaps);
+    int rolled = 0;
+
+    if (!run->gathered) return 0;
+    if (run->nblocks) {
+        ArtFirArgs a;
+        ArtSegTable tab;
+        /* the upkeep of the kept rows, block by block, with the arguments and tables of the single call's launches */
+        for (int i = 0; i < run->nblocks; ++i) {
+            const ArtSchedBlock *b = &run->blocks [i];
+            fill_args (cxt, &a, b->ratio, run->in + (size_t) b->in_off * C, 0, b->in_end - b->in_off, run->out + (size_t) b->out_off * C, 0);
+            a.lin_origin = hip->lin_origin + b->in_off;
+            keep_rows (hip, &a);
+            if (!a.rows_cache) continue;
+            const int nseg = b->seg_end - b->seg_begin;
+            for (int s0 = 0; s0 < nseg; s0 += ART_MAX_SEGS) {
+                const int s1 = s0 + ART_MAX_SEGS < nseg ? s0 + ART_MAX_SEGS : nseg;
+                tab.count = s1 - s0; tab.lin_floor = run->floors [i];
+                for (int q = s0; q < s1; ++q) {
+                    const ArtSchedSeg *g = &run->segs [b->seg_begin + q];
+                    tab.first [q - s0] = g->first; tab.lin_base [q - s0] = g->lin_base; tab.base [q - s0] = g->base;
+                }
+                a.n_begin = run->segs [b->seg_begin + s0].first;
+                a.n_end = s1 < nseg ? run->segs [b->seg_begin + s1].first : b->outputs;
+                if (a.n_end > a.n_begin) arthip_fir_rows_touch (&a, &tab);
+            }
+        }
+        fill_args (cxt, &a, run->blocks [0].ratio, run->in, 0, run->frames, run->out, 0);
+        a.roll_dst = run->frames > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;
+        a.roll_appended = run->frames;
+        void *ev_pre = hip->timing ? timing_event (hip) : NULL;
+        a.ev_start = hip->timing ? timing_event (hip) : NULL;
+        a.ev_stop = hip->timing ? timing_event (hip) : NULL;
+        if (ev_pre) arthip_event_record (ev_pre, hip->stream);
+        hip->d_sched = grow (hip->d_sched, &hip->sched_cap, arthip_fir_schedule_bytes (run->nblocks, run->nsegs));
+        const int k = hip->d_sched ? arthip_fir_schedule (&a, run->blocks, run->nblocks, run->segs, run->nsegs, hip->d_sched, hip->stream) : -1;
+        if (k < 0) {
+            if (hip->timing) hip->ev_count -= 3;          /* (none of the three is read) */
+            artamd_note_failure ("resampler: schedule launch failed");
+            cxt->outputOffset = run->start.outputOffset; cxt->inputIndex = run->start.inputIndex;
+            cxt->flags = run->start.flags; hip->floor_active = run->start.floorActive;
+            for (int i = run->first; i < run->first + run->gathered; ++i) results [i].input_used = results [i].output_generated = 0;
+            run->gathered = run->nblocks = run->nsegs = run->frames = 0; run->outputs = 0;
+            return -1;
+        }
+        rolled = (k & ART_FIR_ROLLED) != 0;
+        hip->last_kernel = ART_KERNEL_GENERAL;
+        hip->last_fixed [0] = 0;
+    }
+    if (run->frames > 0) {
+        if (!rolled) arthip_roll_history (hip->d_hist [hip->cur ^ 1], hip->d_hist [hip->cur], run->in, 0, run->frames, H, C, hip->stream);
+        hip->cur ^= 1; hip->lin_origin += run->frames;
+    }
+    run->gathered = run->nblocks = run->nsegs = run->frames = 0; run->outputs = 0;
+    return 0;
+}
+
+int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, const artsample_t *d_input, const int *numInputFrames,
+                                              artsample_t *d_output, const int *numOutputFrames, const double *ratios,
+                                              int flushLast, ResampleResult *results)
+{
+    if (numBlocks <= 0) return 0;
+    for (int k = 0; k < numBlocks; ++k) if (numInputFrames [k] < 0) return -1;
+    for (int k = 0; k < numBlocks; ++k) results [k].input_used = results [k].output_generated = 0;
+    struct artamd_resampler *hip = cxt->hip;
+    const int C = cxt->numChannels;
+    SchedRun run;
+    memset (&run, 0, sizeof (run));
+    size_t in_pos = 0, out_pos = 0;
+    int made = 0, failed = 0;
+
+    ENTER_DEVICE (hip);
+    for (int k = 0; k < numBlocks && !failed; ++k) {
+        const art_s *in = d_input ? d_input + in_pos * C : NULL;
+        art_s *out = d_output + out_pos * C;
+        const int flush = flushLast && k == numBlocks - 1;
+        if (run.gathered && run.frames > RUN_FRAMES_MAX - numInputFrames [k] && sched_launch (cxt, &run, results)) { failed = 1; break; }
+        if (flush || !sched_gather (cxt, &run, in, numInputFrames [k], out, numOutputFrames [k], ratios [k], &results [k], k)) {
+            /* the single call, behind the run before it (a failure of its own: { 0, 0 } and the count in artamdErrorCount) */
+            if (sched_launch (cxt, &run, results)) { failed = 1; break; }
+            const int errors = artamdErrorCount ();
+            results [k] = flush ? resampleProcessAndFlushInterleavedDevice (cxt, in, numInputFrames [k], out, numOutputFrames [k], ratios [k])
+                                : resampleProcessInterleavedDevice (cxt, in, numInputFrames [k], out, numOutputFrames [k], ratios [k]);
+            if (artamdErrorCount () != errors) { results [k].input_used = results [k].output_generated = 0; failed = 1; break; }
+        }
+        made = k + 1;
+        if ((int) results [k].input_used != numInputFrames [k]) break;          /* a cap too small: no later block is made */
+        in_pos += (size_t) numInputFrames [k]; out_pos += results [k].output_generated;
+    }
+    if (!failed && sched_launch (cxt, &run, results)) failed = 1;
+    free (run.blocks); free (run.floors); free (run.segs);
+    LEAVE_DEVICE (hip);
+    return failed ? -1 : made;
 }
 
 /* what a call would consume / produce, without touching the context */

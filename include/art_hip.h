@@ -124,6 +124,28 @@ ResampleResult resampleProcessAndFlushInterleavedDevice (Resample *cxt, const ar
 int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                                            artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
                                            ResampleResult *results);
+/* Many blocks of ONE stream, one launch.  Makes the same calls as this loop, with the same counts and the same samples bit for bit:
+ *     in = d_input; out = d_output;
+ *     for (k = 0; k < numBlocks; ++k) {
+ *         results [k] = (k == numBlocks - 1 && flushLast ? resampleProcessAndFlushInterleavedDevice : resampleProcessInterleavedDevice)
+ *                       (cxt, in, numInputFrames [k], out, numOutputFrames [k], ratios [k]);
+ *         in += numInputFrames [k] * C;                  (the blocks are contiguous in ONE device input)
+ *         out += results [k].output_generated * C;       (the outputs are packed, one block after another)
+ *         if (results [k].input_used != numInputFrames [k]) break;      (a cap too small: no later block is made)
+ *     }
+ * d_output must hold the sum of numOutputFrames [k] frames.  Returns the number of blocks made (0 .. numBlocks; blocks not made get { 0, 0 }),
+ * 0 for numBlocks <= 0, and -1 if a numInputFrames [k] is negative (nothing is enqueued) or a launch failed: the blocks of the failed launch get
+ * { 0, 0 }, the stream stands exactly where it stood before that launch, blocks made before it keep their results.  Asynchronous like the
+ * single call: the counts are known at once, the samples land on the context's stream.
+ * Blocks the single call gives to the general kernel are gathered into runs of one launch and one history roll each; every other block (a
+ * flush, a block large enough for the matrix-core path, strict order, endpoint extrapolation, the cut-invariant policy on a rational ratio,
+ * a sharded context) is made as its single call, between the runs, in stream order.  With timing on (resampleHipSetTiming) a run counts as
+ * one launch.
+ * What a caller needs: the ratios of the next numBlocks blocks, in advance — an ASRC loop that estimates the drift, or a clock-recovery loop
+ * on the host that steers by resampleGetPosition, knows them for the blocks it has buffered.  INTEGRATION.md shows such a loop. */
+int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, const artsample_t *d_input, const int *numInputFrames,
+                                              artsample_t *d_output, const int *numOutputFrames, const double *ratios,
+                                              int flushLast, ResampleResult *results);
 /* planar device buffers: channel c at d_input + c*inputPitch (in samples), likewise output; a pitch of 0 on either side means that side
  * is interleaved.  Big calls are transposed through the context's interleaved staging on the device (the matrix-core kernels read
  * interleaved frames): the same samples as the interleaved entry point's, bit for bit */

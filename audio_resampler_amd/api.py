@@ -147,6 +147,7 @@ def _bind(width):
         "decimateProcessInterleavedLEDevice": (None, [DP, ptr, C.c_int, ptr]),
         "decimateHipClipped": (C.c_long, [DP]),
         "decimateHipShardCount": (C.c_int, [DP]),
+        "decimateProcessBatchInterleavedLEDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr]),
         "artamdErrorCount": (C.c_int, []),
         "artamdPeriodMultiple": (C.c_int, [C.c_int]),
         "artamdPeriodMultipleRows": (C.c_int, [C.c_int, C.c_int]),
@@ -450,6 +451,18 @@ def _bind(width):
         if rc:
             raise RuntimeError("resampleProcessBatchInterleavedDevice failed")
         return [(r.input_used, r.output_generated) for r in res]
+
+    def decimate_batch_device(decimators, d_ins, n_ins, d_outs):
+        """decimateProcessBatchInterleavedLEDevice over a list of Decimator objects: one launch per class of work for the
+        contexts on the first one's stream.  Returns the launch count (raises if the call returned -1)."""
+        n = len(decimators)
+        ctx = (C.c_void_p * n)(*[C.cast(d.p, C.c_void_p) for d in decimators])
+        rc = lib().decimateProcessBatchInterleavedLEDevice(
+            ctx, n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), (C.c_int * n)(*[int(v) for v in n_ins]),
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]))
+        if rc < 0:
+            raise RuntimeError("decimateProcessBatchInterleavedLEDevice failed")
+        return rc
 
     return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k != "width"}, width=width)
 

@@ -214,6 +214,46 @@ typedef struct {
 /* returns 1 when the generator state was written to a->gens_next (caller swaps), 0 otherwise, <0 on error */
 int arthip_decimate (const ArtDecArgs *a, const art_s *d_in, int frames, unsigned char *d_out, void *stream);
 int arthip_decimate_planar (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream);
+/* Many contexts' calls, one launch per class (decimateProcessBatchInterleavedLEDevice).  The host builds one table per call (the
+ * classes' item arrays one after another, each 16-byte aligned), uploads it once and launches every class from its slice. */
+typedef struct {                         /* one channel of one context: a lane of the serial wave (noise shaping, or short calls) */
+    const art_s *in;                     /* the context's input + channel; frame f at in [f * stride] */
+    unsigned char *out;                  /* the context's output + channel * bytes; frame f at out [f * stride * bytes] */
+    art_s *feedback;                     /* &feedback [channel] */
+    uint32_t *gen;                       /* &gens [channel] (NULL without dither) */
+    Biquad *shaper;                      /* &shapers [channel] (NULL without noise shaping) */
+    unsigned long long *clipped;         /* the context's counter */
+    art_s scale;
+    int stride, frames, bits, bytes, dither_type;     /* frames 0: an empty lane (padding of the last workgroup) */
+} ArtDecLane;
+typedef struct {                         /* one context of a time-parallel launch (no noise shaping, >= 64 frames) */
+    const art_s *in;
+    unsigned char *out;
+    art_s *feedback;
+    uint32_t *gens, *gens_next;          /* the generator state is read from gens and left in gens_next (the host swaps them) */
+    unsigned long long *clipped;
+    long task0;                          /* first (channel, segment) task of this context in the launch's flattened task space */
+    art_s scale;
+    int C, frames, bits, bytes, dither_type;
+} ArtDecTask;
+typedef struct {
+    int serial;                          /* 1: ArtDecLane items (lanes per workgroup `lanes`), 0: ArtDecTask items */
+    int order, dither;                   /* the shaper order (0: none) and whether dither is on: every item of the class shares them */
+    int count, lanes;                    /* items; lanes per workgroup (serial; count is a multiple of it) */
+    long tasks;                          /* time-parallel: total tasks */
+    size_t offset;                       /* of the class's items in the table */
+} ArtDecClass;
+#define ART_DEC_SEG 32                   /* frames of one channel per task of the time-parallel kernels (even: generator pairs) */
+/* the lane count per workgroup the batch gives a serial class of `lanes` lanes in all */
+int arthip_decimate_batch_lanes (int lanes);
+/* copies the host table (bytes) into d_table through the shared pinned staging, on `stream`; 0 or -1 */
+int arthip_decimate_batch_upload (const void *table, size_t bytes, void *d_table, void *stream);
+/* one launch of one class from its slice of the uploaded table; 0 or -1 (nothing of it ran) */
+int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, void *stream);
+/* decimateProcessBatchInterleavedLEDevice with a fixed lane count per workgroup for every serial class (lanes > 0; 0: the rule
+ * of arthip_decimate_batch_lanes): the measurements behind that rule (tools/bench_decimate_batch.py) — pcm_host.c */
+int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
+                           unsigned char *const *d_outputs, int lanes);
 int arthip_biquad_chain (Biquad *d_sections, int C, int S, art_s *d_buf, int frames, int stride, void *stream);
 /* every section has order 2, S = 1 or 2, interleaved frames: hand-scheduled kernel */
 int arthip_biquad_order2 (Biquad *d_sections, int C, int S, art_s *d_buf, int frames, int stride, void *stream);   /* stride >= C: values between frames */

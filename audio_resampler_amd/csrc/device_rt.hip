@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstring>
 #include "art_internal.h"
+#include "staging.hip.h"
 
 static thread_local char g_err[256] = "no error";
 
@@ -207,4 +208,25 @@ float arthip_event_elapsed_ms (void *a, void *b)
     return ms;
 }
 
+}
+
+Staging *staging_take (size_t bytes)
+{
+    static thread_local Staging tl [2] = { { nullptr, 0, nullptr, false }, { nullptr, 0, nullptr, false } };
+    static thread_local int tl_turn = 0;
+    Staging &sg = tl [tl_turn ^= 1];
+    if (sg.pending) { (void) hipEventSynchronize (sg.ev); sg.pending = false; }
+    if (!sg.ev && hipEventCreateWithFlags (&sg.ev, hipEventDisableTiming) != hipSuccess) { sg.ev = nullptr; return nullptr; }
+    if (bytes > sg.cap) {
+        if (sg.host) (void) hipHostFree (sg.host);
+        sg.cap = bytes + bytes / 2 + 65536;
+        if (hipHostMalloc (&sg.host, sg.cap, hipHostMallocDefault) != hipSuccess) { sg.host = nullptr; sg.cap = 0; return nullptr; }
+    }
+    return &sg;
+}
+
+int staging_give (Staging *sg, hipStream_t st)
+{
+    if (hipEventRecord (sg->ev, st) == hipSuccess) { sg->pending = true; return 0; }
+    return hipStreamSynchronize (st) == hipSuccess ? 0 : -1;
 }

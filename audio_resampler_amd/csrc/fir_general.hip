@@ -6,6 +6,7 @@
 // Compiled with -ffp-contract=off: the only fused multiply-adds are the explicit ones of the default mode.
 #include <cstring>
 #include "fir_common.hip.h"
+#include "staging.hip.h"
 
 namespace {
 
@@ -615,34 +616,6 @@ int batch_variant (const ArtFirArgs *a, const ArtSegTable *segs, const int *whic
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-
-// Pinned staging of the argument tables of the batched and the scheduled launches (per calling thread, kept): a table goes to the
-// device without the runtime's bounce through its own pinned buffers.  Two tables take turns, each guarded by an event recorded
-// after the copies out of it: the call returns without waiting for the stream, and the host plans the next one while this one runs.
-struct Staging { void *host; size_t cap; hipEvent_t ev; bool pending; };
-
-// the next turn's table, of `bytes` bytes at least (nullptr: out of memory)
-Staging *staging_take (size_t bytes)
-{
-    static thread_local Staging tl [2] = { { nullptr, 0, nullptr, false }, { nullptr, 0, nullptr, false } };
-    static thread_local int tl_turn = 0;
-    Staging &sg = tl [tl_turn ^= 1];
-    if (sg.pending) { (void) hipEventSynchronize (sg.ev); sg.pending = false; }
-    if (!sg.ev && hipEventCreateWithFlags (&sg.ev, hipEventDisableTiming) != hipSuccess) { sg.ev = nullptr; return nullptr; }
-    if (bytes > sg.cap) {
-        if (sg.host) (void) hipHostFree (sg.host);
-        sg.cap = bytes + bytes / 2 + 64 * sizeof (FirBatchItem);
-        if (hipHostMalloc (&sg.host, sg.cap, hipHostMallocDefault) != hipSuccess) { sg.host = nullptr; sg.cap = 0; return nullptr; }
-    }
-    return &sg;
-}
-
-// the table must outlive the asynchronous copies out of it: marked here, waited for before its next turn.  -1: neither could be made sure of
-int staging_give (Staging *sg, hipStream_t st)
-{
-    if (hipEventRecord (sg->ev, st) == hipSuccess) { sg->pending = true; return 0; }
-    return hipStreamSynchronize (st) == hipSuccess ? 0 : -1;
-}
 
 // Can a block join a run?  The run's tile is at most GEN_MAX_TILE outputs whatever the run's other blocks are: the block's span at
 // that tile must fit the LDS (otherwise its single call goes to the strict kernel), and any GEN_MAX_TILE consecutive outputs of it may

@@ -527,6 +527,8 @@ struct artamd_decimator {
      * (decimator.c:92-93, 119-136) with GPUs for threads — `nshards` ordinary contexts with contiguous channel slices, each on
      * its own device and stream; this context then owns no kernel state itself, only the host mirrors of all channels */
     int nshards; Decimate **shards; int *shard_first; void **ev_shard; void *ev_parent;
+    unsigned long batch_stamp;                                     /* the last batch call that named this context */
+    void *d_batch; size_t batch_cap;                               /* a batch call's table, when this context leads it */
 };
 #define DEC_KERNEL_COPY_LIMIT ((size_t) 1 << 20)
 #define DEC_ENTER(hip) const int prev_device_ = arthip_current_device (); \
@@ -698,6 +700,7 @@ void decimateFree (Decimate *cxt)
         arthip_sync (hip->stream);
         arthip_free (hip->d_state); arthip_host_free (hip->h_state);
         arthip_free (hip->d_in); arthip_free (hip->d_out); arthip_host_free (hip->h_in); arthip_host_free (hip->h_out);
+        arthip_free (hip->d_batch);
         for (int s = 0; s < hip->nshards; ++s) {
             if (hip->shards [s]) {
                 void *st = hip->shards [s]->hip ? hip->shards [s]->hip->stream : NULL;
@@ -801,6 +804,161 @@ void decimateProcessInterleavedLEDevice (Decimate *cxt, const artsample_t *d_inp
     dec_args (cxt, &a);
     dec_swap_if (cxt, arthip_decimate (&a, d_input, numInputFrames, d_output, cxt->hip->stream));
     DEC_LEAVE (cxt->hip);
+}
+
+/* ------------------------------------------------------------------------------------------
+ * Many contexts, one launch per class of work
+ *
+ * Classes: the time-parallel form (no noise shaping, >= 64 frames: the single call's decimate_parallel_kernel), by dither on or
+ * off; everything else by (shaper order, dither on or off), one lane of the serial wave per channel.  A class's lanes are sorted
+ * by frame count (a workgroup runs until its longest lane ends) and cut into workgroups of arthip_decimate_batch_lanes () lanes.
+ * ---------------------------------------------------------------------------------------- */
+#define DEC_BATCH_CLASSES 12                       /* 2 time-parallel + 5 orders x 2 */
+
+typedef struct { int ctx, channel, frames; } DecLaneRef;
+
+static int lane_order (const void *pa, const void *pb)     /* longest first; then list order, channel order (a total order) */
+{
+    const DecLaneRef *a = pa, *b = pb;
+    if (a->frames != b->frames) return a->frames > b->frames ? -1 : 1;
+    if (a->ctx != b->ctx) return a->ctx < b->ctx ? -1 : 1;
+    return a->channel < b->channel ? -1 : a->channel > b->channel;
+}
+
+/* lanes > 0: every serial class gets that many lanes per workgroup (the measurements of the rule); 0: the rule */
+int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
+                           unsigned char *const *d_outputs, int lanes)
+{
+    if (n <= 0) return 0;
+    for (int i = 0; i < n; ++i)
+        if (!cxts [i]) { fprintf (stderr, "artamd: decimate batch: a NULL context\n"); return -1; }
+    {   /* a context may appear only once: stamp each with this call's number (one pass) */
+        static unsigned long calls;
+        const unsigned long stamp = __atomic_add_fetch (&calls, 1, __ATOMIC_RELAXED);
+        for (int i = 0; i < n; ++i) {
+            if (cxts [i]->hip->batch_stamp == stamp) { fprintf (stderr, "artamd: decimate batch: a context appears twice\n"); return -1; }
+            cxts [i]->hip->batch_stamp = stamp;
+        }
+    }
+
+    struct artamd_decimator *lead = cxts [0]->hip;
+    ArtDecArgs *args = malloc (sizeof (ArtDecArgs) * (size_t) n);
+    int *cls_of = malloc (sizeof (int) * (size_t) n);
+    ArtDecClass cls [DEC_BATCH_CLASSES];
+    DecLaneRef *refs = NULL;
+    unsigned char *table = NULL;
+    int launches = 0, rc = -1, most = 0;
+    if (!args || !cls_of) { pcm_fail ("decimate batch: out of host memory"); goto out; }
+    memset (cls, 0, sizeof (cls));
+    for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
+        cls [k].serial = k >= 2;
+        cls [k].order = k >= 2 ? (k - 2) / 2 : 0;
+        cls [k].dither = k >= 2 ? (k - 2) & 1 : k;
+    }
+
+    /* the contexts this launch cannot take are made as their single calls, in list order */
+    for (int i = 0; i < n; ++i) {
+        struct artamd_decimator *hip = cxts [i]->hip;
+        cls_of [i] = -1;
+        if (numInputFrames [i] <= 0) continue;
+        if (hip->nshards || hip->stream != lead->stream || hip->device != lead->device) {
+            decimateProcessInterleavedLEDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i]);
+            ++launches;
+            continue;
+        }
+        ArtDecArgs *a = &args [i];
+        dec_args (cxts [i], a);
+        const int k = numInputFrames [i] >= 64 && !a->shaping_on ? (a->dither_on != 0)
+                    : 2 + 2 * (a->shaping_on ? (a->shaping_order >= 1 && a->shaping_order <= 4 ? a->shaping_order : 4) : 0) + (a->dither_on != 0);
+        cls_of [i] = k;
+        if (cls [k].serial) { cls [k].count += a->C; if (a->C > most) most = a->C; }
+        else { cls [k].tasks += (long) a->C * ((numInputFrames [i] + ART_DEC_SEG - 1) / ART_DEC_SEG); cls [k].count++; }
+    }
+
+    /* the table: every present class's items, 16-byte aligned slices */
+    size_t bytes = 0;
+    int maxlanes = 0;
+    for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
+        if (!cls [k].count) continue;
+        if (cls [k].serial) {
+            cls [k].lanes = lanes > 0 ? (lanes < 64 ? lanes : 64) : arthip_decimate_batch_lanes (cls [k].count);
+            cls [k].count = (cls [k].count + cls [k].lanes - 1) / cls [k].lanes * cls [k].lanes;      /* (+ empty lanes) */
+            if (cls [k].count > maxlanes) maxlanes = cls [k].count;
+        }
+        cls [k].offset = bytes;
+        bytes += ((cls [k].serial ? sizeof (ArtDecLane) : sizeof (ArtDecTask)) * (size_t) cls [k].count + 15) & ~(size_t) 15;
+    }
+    if (!bytes) { rc = launches; goto out; }
+    table = calloc (1, bytes);
+    refs = maxlanes ? malloc (sizeof (DecLaneRef) * (size_t) maxlanes) : NULL;
+    if (!table || (maxlanes && !refs)) { pcm_fail ("decimate batch: out of host memory"); goto out; }
+    for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
+        if (!cls [k].count) continue;
+        if (!cls [k].serial) {
+            ArtDecTask *t = (ArtDecTask *)(table + cls [k].offset);
+            long task0 = 0;
+            for (int i = 0, j = 0; i < n; ++i) {
+                if (cls_of [i] != k) continue;
+                const ArtDecArgs *a = &args [i];
+                ArtDecTask *it = &t [j++];
+                it->in = d_inputs [i]; it->out = d_outputs [i];
+                it->feedback = a->feedback; it->gens = a->gens; it->gens_next = a->gens_next; it->clipped = a->clipped;
+                it->task0 = task0; it->scale = a->scale;
+                it->C = a->C; it->frames = numInputFrames [i]; it->bits = a->bits; it->bytes = a->bytes; it->dither_type = a->dither_type;
+                task0 += (long) a->C * ((numInputFrames [i] + ART_DEC_SEG - 1) / ART_DEC_SEG);
+            }
+            continue;
+        }
+        int m = 0;
+        for (int i = 0; i < n; ++i)
+            if (cls_of [i] == k)
+                for (int c = 0; c < args [i].C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numInputFrames [i]; ++m; }
+        qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
+        ArtDecLane *l = (ArtDecLane *)(table + cls [k].offset);       /* (the padding lanes stay zero: 0 frames) */
+        for (int j = 0; j < m; ++j) {
+            const int i = refs [j].ctx, c = refs [j].channel;
+            const ArtDecArgs *a = &args [i];
+            l [j].in = d_inputs [i] + c; l [j].out = d_outputs [i] + (size_t) c * a->bytes;
+            l [j].feedback = a->feedback + c;
+            l [j].gen = a->dither_on ? a->gens + c : NULL;
+            l [j].shaper = a->shaping_on ? a->shapers + c : NULL;
+            l [j].clipped = a->clipped; l [j].scale = a->scale;
+            l [j].stride = a->C; l [j].frames = numInputFrames [i]; l [j].bits = a->bits; l [j].bytes = a->bytes; l [j].dither_type = a->dither_type;
+        }
+    }
+
+    {
+        DEC_ENTER (lead);
+        if (bytes > lead->batch_cap) {
+            arthip_free (lead->d_batch);
+            lead->batch_cap = bytes * 2;
+            if (!(lead->d_batch = arthip_malloc (lead->batch_cap))) lead->batch_cap = 0;
+        }
+        if (!lead->d_batch || arthip_decimate_batch_upload (table, bytes, lead->d_batch, lead->stream))
+            pcm_fail ("decimate batch: the table could not be uploaded (nothing launched)");
+        else {
+            rc = 0;
+            for (int k = 0; k < DEC_BATCH_CLASSES && !rc; ++k) {
+                if (!cls [k].count) continue;
+                if (arthip_decimate_batch_launch (&cls [k], lead->d_batch, lead->stream)) { pcm_fail ("decimate batch: launch failed"); rc = -1; break; }
+                ++launches;
+                if (!cls [k].serial)          /* the time-parallel form left the generator state in gens_next: as dec_swap_if */
+                    for (int i = 0; i < n; ++i)
+                        if (cls_of [i] == k) dec_swap_if (cxts [i], 1);
+            }
+            if (!rc) rc = launches;
+        }
+        DEC_LEAVE (lead);
+    }
+out:
+    free (args); free (cls_of); free (refs); free (table);
+    return rc;
+}
+
+int decimateProcessBatchInterleavedLEDevice (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
+                                             unsigned char *const *d_outputs)
+{
+    return artamd_decimate_batch (cxts, n, d_inputs, numInputFrames, d_outputs, 0);
 }
 
 long decimateHipClipped (Decimate *cxt)

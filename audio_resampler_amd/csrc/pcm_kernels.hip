@@ -12,7 +12,9 @@
 #include <climits>
 #include <cstdlib>
 #include <type_traits>
+#include <cstring>
 #include "art_internal.h"
+#include "staging.hip.h"
 
 namespace {
 
@@ -779,7 +781,7 @@ __device__ __forceinline__ art_s round_half_up (art_s d)
 #endif
 }
 
-constexpr int DEC_SEG = 32;                        // consecutive samples of one channel per dither task (even)
+constexpr int DEC_SEG = ART_DEC_SEG;               // consecutive samples of one channel per dither task (even; the batch host counts tasks with it)
 
 template <int ORDER, bool DITHER>                  // ORDER 0 = no noise shaping
 __global__ __launch_bounds__ (ST_THREADS)
@@ -1072,6 +1074,206 @@ void decimate_parallel_kernel (ArtDecArgs a, const art_s *in, int frames, unsign
     if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Many contexts in one launch (decimateProcessBatchInterleavedLEDevice).  Phase B — the error-feedback recurrence — depends only
+// on the shaper order and on whether dither is on; the gain, the dither type and the output format are applied by the helper
+// waves.  So channels of different contexts share one serial wave, each lane reading its own descriptor, and the bits are those
+// of the single call: the same operations in the same order, per lane.
+// ---------------------------------------------------------------------------------------------------
+constexpr int DEC_BATCH_RUN = 60;                  // frames per chunk at most: a service tick is a few hundred frames, and the
+                                                   // pipeline's fill and drain cost two chunks of the serial lane's time
+
+// decimate_pipe_kernel over `lanes` lanes of ArtDecLane descriptors per workgroup.  LDS tiles are [lane][frame] with a pitch of
+// chunk_frames + 4 (a multiple of 4: the serial lane's 16-byte LDS accesses); the launcher sizes them by `lanes`, so small
+// workgroups are small in LDS too.  A lane whose context has fewer frames than the workgroup's longest sits the rest out.
+template <int ORDER, bool DITHER>                  // ORDER 0: no noise shaping (calls under 64 frames)
+__global__ __launch_bounds__ (ST_THREADS)
+void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_frames)
+{
+    extern __shared__ __attribute__ ((aligned (16))) unsigned char dec_lds [];
+    const int pitch = chunk_frames + 4, span = lanes * pitch;
+    art_s *const tiles = (art_s *) dec_lds;                               // [3][lanes][pitch]
+    art_s *const dths = tiles + 3 * span;                                 // [2][lanes][pitch]
+    __shared__ uint32_t s_gen [2][64];             // generator state at the start of a chunk, by chunk parity
+    __shared__ const art_s *s_in [64];
+    __shared__ unsigned char *s_out [64];
+    __shared__ art_s s_scale [64];
+    __shared__ int s_stride [64], s_frames [64], s_fmt [64];            // fmt: bits | bytes << 8 | (dither type + 1) << 16
+    __shared__ unsigned int s_clips [64];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const ArtDecLane *const mine = table + (size_t) blockIdx.x * lanes;
+
+    art_s fb = 0; SectionRegs sh; int my_frames = 0;
+    if (tid < lanes) {
+        const ArtDecLane &d = mine [tid];
+        s_in [tid] = d.in; s_out [tid] = d.out; s_scale [tid] = d.scale; s_stride [tid] = d.stride; s_frames [tid] = d.frames;
+        s_fmt [tid] = d.bits | (d.bytes << 8) | ((d.dither_type + 1) << 16);
+        s_clips [tid] = 0;
+        my_frames = d.frames;
+        if (my_frames > 0) {
+            fb = *d.feedback;
+            if (DITHER) s_gen [0][tid] = *d.gen;
+            if (ORDER) load_section (sh, *d.shaper);
+        }
+    }
+    __syncthreads ();
+    int frames = 0;
+    for (int c = 0; c < lanes; ++c) frames = max (frames, s_frames [c]);
+    const int nchunks = (frames + chunk_frames - 1) / chunk_frames;
+    constexpr int HELPERS = ST_THREADS - 64;
+
+    for (int it = -1; it <= nchunks; ++it) {
+        if (wave >= 1) {
+            const int ht = tid - 64;
+            if (it + 1 < nchunks) {                // ---- phase A of chunk it+1 (a thread walks one lane's frames: its reads are
+                const int k = it + 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);    // that context's interleave)
+                art_s *tile = tiles + (k % 3) * span, *dth = dths + (k & 1) * span;
+                for (int e = ht; e < nf * lanes; e += HELPERS) {
+                    const int c = e / nf, f = e - c * nf;
+                    if (f0 + f < s_frames [c]) tile [c * pitch + f] = s_in [c][(size_t)(f0 + f) * s_stride [c]] * s_scale [c];
+                }
+                if (DITHER) {
+                    const int segs = (nf + DEC_SEG - 1) / DEC_SEG;
+                    for (int task = ht; task < segs * lanes; task += HELPERS) {
+                        const int c = task / segs, sgm = task - c * segs, n0 = sgm * DEC_SEG;
+                        const int nfc = min (nf, s_frames [c] - f0);                 // this lane's frames in the chunk (may be <= 0)
+                        if (n0 >= nfc) continue;
+                        const int dtype = (s_fmt [c] >> 16) - 1;
+                        uint32_t g = jump_pairs (s_gen [k & 1][c], (unsigned int)(n0 / 2));
+                        const int cnt = min (DEC_SEG, nfc - n0);
+                        for (int i = 0; i < cnt; ++i) {
+                            const uint32_t start = g;
+                            uint32_t r = lcg (lcg (start));
+                            const uint32_t first = dtype < 0 ? ~start : dtype > 0 ? start : ~r;
+                            r = lcg (lcg (lcg (r)));
+                            g = r;
+                            const uint32_t u = (first >> 1) + (r >> 1);
+                            dth [c * pitch + n0 + i] = (art_s)(int)(u ^ 0x80000000u) * (art_s) 4.656612873077392578125e-10;
+                        }
+                        if (n0 + cnt == nfc) s_gen [(k & 1) ^ 1][c] = g;    // start state of the lane's chunk k+1 (or its final state)
+                    }
+                }
+            }
+            if (it >= 1) {                         // ---- phase C of chunk it-1
+                const int k = it - 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);
+                const art_s *tile = tiles + (k % 3) * span;
+                for (int e = ht; e < nf * lanes; e += HELPERS) {
+                    const int c = e / nf, f = e - c * nf;
+                    if (f0 + f >= s_frames [c]) continue;
+                    const int fmt = s_fmt [c], bits = fmt & 255, nbytes = (fmt >> 8) & 255;
+                    const int width = (bits + 7) / 8, pad = nbytes - width;
+                    const int hi = (1 << (bits - 1)) - 1, lo = ~hi;
+                    const int shift = (24 - bits) % 8;
+                    const uint32_t bias = bits <= 8 ? 128u : 0u;
+                    int q = (int) tile [c * pitch + f];
+                    if (q > hi) { q = hi; atomicAdd (&s_clips [c], 1u); }
+                    else if (q < lo) { q = lo; atomicAdd (&s_clips [c], 1u); }
+                    const uint32_t v = ((uint32_t) q << shift) + bias;
+                    unsigned char *o = s_out [c] + (size_t)(f0 + f) * s_stride [c] * nbytes;
+                    for (int j = 0; j < pad; ++j) *o++ = 0;
+                    *o++ = (unsigned char) v;
+                    if (width > 1) { *o++ = (unsigned char)(v >> 8); if (width > 2) *o++ = (unsigned char)(v >> 16); }
+                }
+            }
+        }
+        else if (tid < lanes && it >= 0 && it < nchunks && it * chunk_frames < my_frames) {     // ---- phase B of chunk it
+            const int f0 = it * chunk_frames, nf = min (chunk_frames, my_frames - f0);
+            art_s *tile = tiles + (it % 3) * span;
+            const art_s *dth = dths + (it & 1) * span;
+            auto one = [&] (art_s smp, art_s dither) -> art_s {
+                const art_s scaled = smp;                       // already times the lane's `scale` (phase A)
+                const art_s code = scaled - fb;
+                const art_s dithered = code + dither;
+                const art_s qf = round_half_up (dithered);
+                if (ORDER) { const art_s err = qf - code; fb = shaper_step<ORDER> (sh, err); }
+                return qf;
+            };
+            typedef art_s vec4 __attribute__ ((ext_vector_type (4)));
+            art_s *row = tile + tid * pitch;
+            const art_s *my_dither = dth + tid * pitch;
+            int f = 0;
+            for (; f + 8 <= nf; f += 8) {
+                vec4 xa = *reinterpret_cast<const vec4 *> (row + f), xb = *reinterpret_cast<const vec4 *> (row + f + 4), da, db;
+                if (DITHER) { da = *reinterpret_cast<const vec4 *> (my_dither + f); db = *reinterpret_cast<const vec4 *> (my_dither + f + 4); }
+                else { da = (art_s) 0; db = (art_s) 0; }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) xa [u] = one (xa [u], da [u]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) xb [u] = one (xb [u], db [u]);
+                *reinterpret_cast<vec4 *> (row + f) = xa; *reinterpret_cast<vec4 *> (row + f + 4) = xb;
+            }
+            for (; f < nf; ++f) row [f] = one (row [f], DITHER ? my_dither [f] : (art_s) 0);
+        }
+        // LDS-only barrier, as in decimate_pipe_kernel: nobody reads global memory that this launch writes
+        asm volatile ("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+    __syncthreads ();
+
+    if (tid < lanes && my_frames > 0) {
+        const ArtDecLane &d = mine [tid];
+        *d.feedback = fb;
+        if (DITHER) *d.gen = s_gen [((my_frames + chunk_frames - 1) / chunk_frames) & 1][tid];
+        if (ORDER) store_section (*d.shaper, sh, my_frames, true);
+        if (s_clips [tid]) atomicAdd (d.clipped, (unsigned long long) s_clips [tid]);
+    }
+}
+
+// decimate_parallel_kernel over a flattened task space: (context, channel, DEC_SEG-frame segment).  A thread finds its context by
+// binary search over the contexts' first tasks.
+template <bool DITHER>
+__global__ __launch_bounds__ (256)
+void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
+{
+    const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (task >= tasks) return;
+    int lo_i = 0, hi_i = n - 1;                    // the last item whose first task is <= task
+    while (lo_i < hi_i) { const int mid = (lo_i + hi_i + 1) >> 1; if (items [mid].task0 <= task) lo_i = mid; else hi_i = mid - 1; }
+    const ArtDecTask &a = items [lo_i];
+    const long t = task - a.task0;
+    const int c = (int)(t % a.C);
+    const long n0 = (t / a.C) * DEC_SEG;
+    const int frames = a.frames;
+    if (n0 >= frames) return;
+    const int cnt = (int) min ((long) DEC_SEG, frames - n0);
+
+    const int nbytes = a.bytes, width = (a.bits + 7) / 8, pad = nbytes - width;
+    const int hi = (1 << (a.bits - 1)) - 1, lo = ~hi;
+    const int shift = (24 - a.bits) % 8;
+    const uint32_t bias = a.bits <= 8 ? 128u : 0u;
+    const art_s fb = a.feedback [c];                      // constant without shaping (decimator.c:264-265)
+    const art_s scale = a.scale;
+    const int dtype = a.dither_type, C = a.C;
+    uint32_t g = DITHER ? jump_pairs (a.gens [c], (unsigned int)(n0 / 2)) : 0u;
+    unsigned int clips = 0;
+
+    for (int i = 0; i < cnt; ++i) {
+        art_s dither = 0.0f;
+        if (DITHER) {
+            const uint32_t start = g;
+            uint32_t r = lcg (lcg (start));
+            const uint32_t first = dtype < 0 ? ~start : dtype > 0 ? start : ~r;
+            r = lcg (lcg (lcg (r)));
+            g = r;
+            const uint32_t u = (first >> 1) + (r >> 1);
+            dither = (art_s)(int)(u ^ 0x80000000u) * (art_s) 4.656612873077392578125e-10;
+        }
+        const size_t e = (size_t)(n0 + i) * C + c;
+        const art_s scaled = a.in [e] * scale;
+        const art_s code = scaled - fb;
+        const art_s dithered = code + dither;
+        int q = (int) round_half_up (dithered);
+        if (q > hi) { q = hi; clips++; }
+        else if (q < lo) { q = lo; clips++; }
+        const uint32_t v = ((uint32_t) q << shift) + bias;
+        unsigned char *o = a.out + e * nbytes;
+        for (int j = 0; j < pad; ++j) *o++ = 0;
+        *o++ = (unsigned char) v;
+        if (width > 1) { *o++ = (unsigned char)(v >> 8); if (width > 2) *o++ = (unsigned char)(v >> 16); }
+    }
+    if (DITHER && n0 + cnt == frames) a.gens_next [c] = g;
+    if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
+}
+
 __global__ void ingest_kernel (const unsigned char *in, art_s g, int bits, int bytes, int stride, art_s *out, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1096,6 +1298,8 @@ static int channels_per_workgroup (int C)
     while (cpw < 64 && (C + cpw - 1) / cpw > 512) cpw += 8;
     return cpw;
 }
+static constexpr int DEC_BATCH_WORKGROUPS = 1024;  // the workgroup count a serial batch class aims at: four per CU (a small
+                                                   // workgroup's LDS lets several share a CU; their serial waves are latency-bound)
 
 extern "C" {
 
@@ -1215,6 +1419,53 @@ int arthip_decimate (const ArtDecArgs *a, const art_s *d_in, int frames, unsigne
 int arthip_decimate_planar (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream)
 {
     return decimate_launch (a, d_in, in_pitch, frames, d_out, out_pitch, stream);
+}
+
+// Lanes per workgroup of a serial batch class: enough workgroups to fill the CUs first, then more lanes per serial wave (a lane's
+// time is its chain, whatever the lane count; LDS and helper work grow with the lanes).  Measured (profiles/decimate_batch.txt):
+// the fastest L puts 512-1,024 workgroups on the chip at 2,048, 8,192 and 16,384 lanes, and L = 1-2 wins below that.
+int arthip_decimate_batch_lanes (int lanes)
+{
+    int L = 1;
+    while (L < 64 && (lanes + L - 1) / L > DEC_BATCH_WORKGROUPS) L *= 2;
+    return L;
+}
+
+int arthip_decimate_batch_upload (const void *table, size_t bytes, void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    Staging *sg = staging_take (bytes);
+    if (!sg) return -1;
+    std::memcpy (sg->host, table, bytes);
+    const bool ok = hipMemcpyAsync (d_table, sg->host, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+    return staging_give (sg, st) || !ok ? -1 : 0;
+}
+
+int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    const void *items = (const char *) d_table + cls->offset;
+    if (cls->count <= 0) return 0;
+    if (!cls->serial) {
+        const dim3 grid ((unsigned int)((cls->tasks + 255) / 256)), block (256);
+        if (cls->dither) hipLaunchKernelGGL (decimate_batch_parallel_kernel<true>, grid, block, 0, st, (const ArtDecTask *) items, cls->count, cls->tasks);
+        else hipLaunchKernelGGL (decimate_batch_parallel_kernel<false>, grid, block, 0, st, (const ArtDecTask *) items, cls->count, cls->tasks);
+        return hipGetLastError () == hipSuccess ? 0 : -1;
+    }
+    const int L = cls->lanes;
+    if (L < 1 || L > 64 || cls->count % L) return -1;
+    const int chunk_frames = min (((DEC_CHUNK / L) - 4) & ~3, DEC_BATCH_RUN);
+    const size_t lds = (size_t) 5 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 5 DEC_CHUNK samples (80 KiB)
+    const dim3 grid ((unsigned int)(cls->count / L)), block (ST_THREADS);
+#define DEC_BATCH_GO(O, D) do { auto k = decimate_batch_pipe_kernel<O, D>; static bool once = false; \
+        if (!once) { (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(5 * DEC_CHUNK * sizeof (art_s))); once = true; } \
+        hipLaunchKernelGGL (k, grid, block, lds, st, (const ArtDecLane *) items, L, chunk_frames); } while (0)
+#define DEC_BATCH_O(O) do { if (cls->dither) DEC_BATCH_GO (O, true); else DEC_BATCH_GO (O, false); } while (0)
+    switch (cls->order) { case 0: DEC_BATCH_O (0); break; case 1: DEC_BATCH_O (1); break; case 2: DEC_BATCH_O (2); break;
+                          case 3: DEC_BATCH_O (3); break; default: DEC_BATCH_O (4); }
+#undef DEC_BATCH_O
+#undef DEC_BATCH_GO
+    return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
 int arthip_ingest (const unsigned char *d_in, art_s g, int bits, int bytes, int stride, art_s *d_out, int n, void *stream)

@@ -217,6 +217,20 @@ long decimateHipClipped (Decimate *cxt);             /* synchronises; total clip
  * 119-136, with devices for threads — ordinary contexts with contiguous channel slices on the devices of artamdSetDevices ());
  * 0: an ordinary context */
 int decimateHipShardCount (Decimate *cxt);
+/* Many independent decimator contexts, one launch per kind of work: the output bytes, clip counts and state after the call are
+ * exactly those of decimateProcessInterleavedLEDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i]), i = 0..n-1.
+ * The error-feedback recurrence is serial per channel, so one stereo stream keeps two lanes of one CU busy; here the channels of
+ * many contexts share the serial waves (one launch per shaper order and dither on / off), and contexts without noise shaping of
+ * 64 frames and more are one time-parallel launch (by dither on / off).
+ * Contexts on the stream and device of cxts [0] are gathered; the launches run on that stream.  A sharded context
+ * (decimateHipShardCount > 0), or one on another stream or device, is made as its own single call, in list order.  A context with
+ * numInputFrames [i] <= 0 is skipped.  Asynchronous like the single call (clip counts: decimateHipClipped per context); the host
+ * mirrors (feedback, tpdf_generators, noise_shapers) are left as the single device call leaves them.
+ * Returns the number of kernel launches enqueued, counting each single call made on the side as one; 0 when n <= 0 or there was
+ * nothing to do; -1 with nothing enqueued if a context appears twice or a pointer in cxts is NULL; -1 if a launch failed (counted
+ * in artamdErrorCount): the contexts of a launch that failed keep their device state and generator buffers as before the call. */
+int decimateProcessBatchInterleavedLEDevice (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
+                                             unsigned char *const *d_outputs);
 void floatIntegersLEDevice (const unsigned char *d_input, double inputGain, int inputBits, int inputBytes, int inputStride,
                             artsample_t *d_output, int numSamples, void *hipStream);
 

@@ -143,6 +143,7 @@ def _bind(width):
         "biquadBankFree": (None, [ptr]),
         "biquadBankRepairs": (C.c_uint, [ptr]),
         "artamdBiquadRepairs": (C.c_uint, []),
+        "biquadBankApplyBatchInterleavedDevice": (C.c_int, [ptr, C.c_int, ptr, ptr]),
         "decimateHipSetStream": (None, [DP, ptr]),
         "decimateProcessInterleavedLEDevice": (None, [DP, ptr, C.c_int, ptr]),
         "decimateHipClipped": (C.c_long, [DP]),
@@ -462,6 +463,17 @@ def _bind(width):
             (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]))
         if rc < 0:
             raise RuntimeError("decimateProcessBatchInterleavedLEDevice failed")
+        return rc
+
+    def biquad_batch_device(banks, d_bufs, frames):
+        """biquadBankApplyBatchInterleavedDevice over a list of BiquadBank objects: one launch per section count for the banks on
+        the first one's stream.  Returns the launch count (raises if the call returned -1)."""
+        n = len(banks)
+        rc = lib().biquadBankApplyBatchInterleavedDevice(
+            (C.c_void_p * n)(*[b.p for b in banks]), n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_bufs]),
+            (C.c_int * n)(*[int(v) for v in frames]))
+        if rc < 0:
+            raise RuntimeError("biquadBankApplyBatchInterleavedDevice failed")
         return rc
 
     return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k != "width"}, width=width)

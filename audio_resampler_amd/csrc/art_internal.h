@@ -255,6 +255,27 @@ int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, v
 int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                            unsigned char *const *d_outputs, int lanes);
 int arthip_biquad_chain (Biquad *d_sections, int C, int S, art_s *d_buf, int frames, int stride, void *stream);
+/* Many banks' calls, one launch per section count (biquadBankApplyBatchInterleavedDevice).  A lane is one channel of one bank;
+ * each class's lanes are one slice of the call's table (16-byte aligned), uploaded with arthip_decimate_batch_upload. */
+typedef struct {
+    Biquad *sections;                    /* the bank's d_sections + channel * S */
+    art_s *buf;                          /* the bank's buffer + channel; frame f at buf [f * stride], in place */
+    int stride, frames;                  /* frames 0: an empty lane (padding of the last workgroup) */
+} ArtBqLane;
+typedef struct {
+    int S;                               /* sections per channel: every lane of the class has S */
+    int count, lanes;                    /* lanes in all (a multiple of `lanes`); lanes per workgroup */
+    size_t offset;                       /* of the class's lanes in the table */
+} ArtBqClass;
+/* the lane count per workgroup the batch gives a class of `lanes` lanes in all */
+int arthip_biquad_batch_lanes (int lanes);
+/* one launch of one class from its slice of the uploaded table; 0 or -1 (nothing of it ran) */
+int arthip_biquad_batch_launch (const ArtBqClass *cls, const void *d_table, void *stream);
+/* biquadBankApplyBatchInterleavedDevice with a fixed lane count per workgroup (lanes > 0; 0: arthip_biquad_batch_lanes) and a
+ * fixed bound on the frames of a gathered time-parallel call (serialMax >= 0; < 0: the library's): the measurements behind both
+ * (tools/bench_biquad_batch.py) — pcm_host.c */
+int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const int *numFrames, int lanes, int serialMax);
+int artamd_biquad_batch_serial_max (void);                              /* the library's bound (BQ_BATCH_SERIAL_MAX) */
 /* every section has order 2, S = 1 or 2, interleaved frames: hand-scheduled kernel */
 int arthip_biquad_order2 (Biquad *d_sections, int C, int S, art_s *d_buf, int frames, int stride, void *stream);   /* stride >= C: values between frames */
 /* bit-exact cascade, parallel over time (speculative chunks + exact verification, pcm_kernels.hip): d_in -> d_out, distinct

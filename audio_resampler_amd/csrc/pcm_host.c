@@ -311,6 +311,8 @@ struct artamd_biquad_bank {
      * device and stream, + the slice of the caller's buffer each works on */
     int nshards; BiquadBank **shards; int *shard_first; void **ev_shard; void *ev_parent;
     art_s *d_slice; size_t slice_cap;
+    unsigned long batch_stamp;           /* the last batch call that named this bank */
+    void *d_batch; size_t batch_cap;     /* a batch call's table, when this bank leads it */
 };
 #define BANK_ENTER(b) const int prev_device_ = arthip_current_device (); \
                       if (prev_device_ != (b)->device) arthip_set_device ((b)->device)
@@ -502,6 +504,7 @@ void biquadBankFree (BiquadBank *b)
     if (b->ev_parent) arthip_event_destroy (b->ev_parent);
     free (b->shards); free (b->shard_first); free (b->ev_shard);
     arthip_free (b->d_sections); arthip_free (b->d_tmp); arthip_free (b->d_spec); arthip_free (b->d_repairs); arthip_free (b->d_first_bad); arthip_free (b->d_slice);
+    arthip_free (b->d_batch);
     BANK_LEAVE (b);
     free (b);
 }
@@ -960,6 +963,122 @@ int decimateProcessBatchInterleavedLEDevice (Decimate *const *cxts, int n, const
 {
     return artamd_decimate_batch (cxts, n, d_inputs, numInputFrames, d_outputs, 0);
 }
+
+/* ------------------------------------------------------------------------------------------
+ * Many biquad banks, one launch per section count
+ *
+ * Every lane runs the serial form (pcm_kernels.hip, biquad_batch_pipe_kernel), whatever form the bank's single call would take:
+ * all of them give the reference's bits.  Only a call that its single call would make time-parallel AND that is longer than
+ * BQ_BATCH_SERIAL_MAX frames stays on the side: from there on one serial lane takes longer than that whole single call.  A class's
+ * lanes are sorted by frame count and cut into workgroups of arthip_biquad_batch_lanes () lanes.
+ * ---------------------------------------------------------------------------------------- */
+#define BQ_BATCH_SERIAL_MAX 512                    /* measured: profiles/biquad_batch.txt (--sweep, serial_max): one serial lane of ART's
+                                                    * pre-filter takes as long as its time-parallel single call at 510-570 frames */
+
+/* lanes > 0: every class gets that many lanes per workgroup; serialMax < 0: BQ_BATCH_SERIAL_MAX (the measurements of both rules) */
+int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const int *numFrames, int lanes, int serialMax)
+{
+    if (n <= 0) return 0;
+    for (int i = 0; i < n; ++i)
+        if (!banks [i]) { fprintf (stderr, "artamd: biquad batch: a NULL bank\n"); return -1; }
+    {   /* a bank may appear only once: stamp each with this call's number (one pass) */
+        static unsigned long calls;
+        const unsigned long stamp = __atomic_add_fetch (&calls, 1, __ATOMIC_RELAXED);
+        for (int i = 0; i < n; ++i) {
+            if (banks [i]->batch_stamp == stamp) { fprintf (stderr, "artamd: biquad batch: a bank appears twice\n"); return -1; }
+            banks [i]->batch_stamp = stamp;
+        }
+    }
+    if (serialMax < 0) serialMax = BQ_BATCH_SERIAL_MAX;
+
+    BiquadBank *lead = banks [0];
+    int *gathered = malloc (sizeof (int) * (size_t) n);
+    ArtBqClass cls [4];
+    DecLaneRef *refs = NULL;
+    unsigned char *table = NULL;
+    int launches = 0, rc = -1, maxlanes = 0;
+    if (!gathered) { pcm_fail ("biquad batch: out of host memory"); goto out; }
+    memset (cls, 0, sizeof (cls));
+
+    /* the calls this launch cannot take are made as their single calls, in list order */
+    for (int i = 0; i < n; ++i) {
+        BiquadBank *b = banks [i];
+        gathered [i] = 0;
+        if (numFrames [i] <= 0) continue;
+        const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
+        if (b->nshards || b->stream != lead->stream || b->device != lead->device || (L && numFrames [i] >= 2 * L && numFrames [i] > serialMax)) {
+            biquadBankApplyInterleavedDevice (b, d_buffers [i], numFrames [i]);
+            ++launches;
+            continue;
+        }
+        gathered [i] = 1;
+        cls [b->S - 1].count += b->C;
+    }
+
+    /* the table: every present class's lanes (+ empty lanes up to whole workgroups), 16-byte aligned slices */
+    size_t bytes = 0;
+    for (int k = 0; k < 4; ++k) {
+        if (!cls [k].count) continue;
+        cls [k].S = k + 1;
+        cls [k].lanes = lanes > 0 ? (lanes < 64 ? lanes : 64) : arthip_biquad_batch_lanes (cls [k].count);
+        cls [k].count = (cls [k].count + cls [k].lanes - 1) / cls [k].lanes * cls [k].lanes;
+        if (cls [k].count > maxlanes) maxlanes = cls [k].count;
+        cls [k].offset = bytes;
+        bytes += (sizeof (ArtBqLane) * (size_t) cls [k].count + 15) & ~(size_t) 15;
+    }
+    if (!bytes) { rc = launches; goto out; }
+    table = calloc (1, bytes);
+    refs = malloc (sizeof (DecLaneRef) * (size_t) maxlanes);
+    if (!table || !refs) { pcm_fail ("biquad batch: out of host memory"); goto out; }
+    for (int k = 0; k < 4; ++k) {
+        if (!cls [k].count) continue;
+        int m = 0;
+        for (int i = 0; i < n; ++i)
+            if (gathered [i] && banks [i]->S == k + 1)
+                for (int c = 0; c < banks [i]->C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numFrames [i]; ++m; }
+        qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
+        ArtBqLane *l = (ArtBqLane *)(table + cls [k].offset);         /* (the padding lanes stay zero: 0 frames) */
+        for (int j = 0; j < m; ++j) {
+            const BiquadBank *b = banks [refs [j].ctx];
+            const int c = refs [j].channel;
+            l [j].sections = b->d_sections + (size_t) c * b->S;
+            l [j].buf = d_buffers [refs [j].ctx] + c;
+            l [j].stride = b->C;
+            l [j].frames = refs [j].frames;
+        }
+    }
+
+    {
+        BANK_ENTER (lead);
+        if (bytes > lead->batch_cap) {
+            arthip_free (lead->d_batch);
+            lead->batch_cap = bytes * 2;
+            if (!(lead->d_batch = arthip_malloc (lead->batch_cap))) lead->batch_cap = 0;
+        }
+        if (!lead->d_batch || arthip_decimate_batch_upload (table, bytes, lead->d_batch, lead->stream))
+            pcm_fail ("biquad batch: the table could not be uploaded (nothing launched)");
+        else {
+            rc = 0;
+            for (int k = 0; k < 4; ++k) {
+                if (!cls [k].count) continue;
+                if (arthip_biquad_batch_launch (&cls [k], lead->d_batch, lead->stream)) { pcm_fail ("biquad batch: launch failed"); rc = -1; break; }
+                ++launches;
+            }
+            if (!rc) rc = launches;
+        }
+        BANK_LEAVE (lead);
+    }
+out:
+    free (gathered); free (refs); free (table);
+    return rc;
+}
+
+int biquadBankApplyBatchInterleavedDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const int *numFrames)
+{
+    return artamd_biquad_batch (banks, n, d_buffers, numFrames, 0, -1);
+}
+
+int artamd_biquad_batch_serial_max (void) { return BQ_BATCH_SERIAL_MAX; }
 
 long decimateHipClipped (Decimate *cxt)
 {

@@ -1274,6 +1274,97 @@ void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
     if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Many biquad banks in one launch (biquadBankApplyBatchInterleavedDevice): the serial cascade of biquad_chain_kernel, one lane per
+// channel of any bank, S sections per lane (each section's own order at run time), in the three-phase pipeline of
+// decimate_batch_pipe_kernel.  Waves 1-3 load chunk it+1 into LDS and store chunk it-1 back in place while lanes 0..lanes-1 of wave 0
+// run chunk it; one LDS-only barrier per step.  Every lane makes the same operations in the same order as the single call's serial
+// form (step_buffer_order, reference biquad.c:106-163), so the bits are the single call's.
+// ---------------------------------------------------------------------------------------------------
+constexpr int BQ_BATCH_RUN = 60;                   // frames per chunk at most (the decimator batch's: fill and drain cost two chunks)
+
+// LDS: three tiles [lanes][chunk_frames + 4] (the pitch is a multiple of 4: one ds_read_b128 feeds the serial lane 4 float frames),
+// sized by the launcher from `lanes`.  A lane with fewer frames than the workgroup's longest sits the rest out.
+template <int S>
+__global__ __launch_bounds__ (ST_THREADS)
+void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_frames)
+{
+    extern __shared__ __attribute__ ((aligned (16))) unsigned char bq_lds [];
+    const int pitch = chunk_frames + 4, span = lanes * pitch;
+    art_s *const tiles = (art_s *) bq_lds;                                // [3][lanes][pitch]
+    __shared__ art_s *s_buf [64];
+    __shared__ int s_stride [64], s_frames [64];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const ArtBqLane *const mine = table + (size_t) blockIdx.x * lanes;
+
+    SectionRegs r [S];
+    int my_frames = 0;
+    if (tid < lanes) {
+        const ArtBqLane &d = mine [tid];
+        s_buf [tid] = d.buf; s_stride [tid] = d.stride; s_frames [tid] = d.frames;
+        my_frames = d.frames;
+        if (my_frames > 0) {
+#pragma unroll
+            for (int s = 0; s < S; ++s) load_section (r [s], d.sections [s]);
+        }
+    }
+    __syncthreads ();
+    int frames = 0;
+    for (int c = 0; c < lanes; ++c) frames = max (frames, s_frames [c]);
+    const int nchunks = (frames + chunk_frames - 1) / chunk_frames;
+    constexpr int HELPERS = ST_THREADS - 64;
+
+    for (int it = -1; it <= nchunks; ++it) {
+        if (wave >= 1) {
+            const int ht = tid - 64;
+            if (it + 1 < nchunks) {                // ---- load chunk it+1 (a thread walks one lane's frames)
+                const int k = it + 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);
+                art_s *tile = tiles + (k % 3) * span;
+                for (int e = ht; e < nf * lanes; e += HELPERS) {
+                    const int c = e / nf, f = e - c * nf;
+                    if (f0 + f < s_frames [c]) tile [c * pitch + f] = s_buf [c][(size_t)(f0 + f) * s_stride [c]];
+                }
+            }
+            if (it >= 1) {                         // ---- store chunk it-1
+                const int k = it - 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);
+                const art_s *tile = tiles + (k % 3) * span;
+                for (int e = ht; e < nf * lanes; e += HELPERS) {
+                    const int c = e / nf, f = e - c * nf;
+                    if (f0 + f < s_frames [c]) s_buf [c][(size_t)(f0 + f) * s_stride [c]] = tile [c * pitch + f];
+                }
+            }
+        }
+        else if (tid < lanes && it >= 0 && it < nchunks && it * chunk_frames < my_frames) {     // ---- the cascade over chunk it
+            const int f0 = it * chunk_frames, nf = min (chunk_frames, my_frames - f0);
+            art_s *row = tiles + (it % 3) * span + tid * pitch;
+            typedef art_s vec4 __attribute__ ((ext_vector_type (4)));
+            int f = 0;
+            for (; f + 4 <= nf; f += 4) {
+                vec4 v = *reinterpret_cast<const vec4 *> (row + f);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int s = 0; s < S; ++s) v [u] = step_buffer_order (r [s], v [u]);
+                *reinterpret_cast<vec4 *> (row + f) = v;
+            }
+            for (; f < nf; ++f) {
+                art_s v = row [f];
+#pragma unroll
+                for (int s = 0; s < S; ++s) v = step_buffer_order (r [s], v);
+                row [f] = v;
+            }
+        }
+        // LDS-only barrier, as in decimate_pipe_kernel: nobody reads global memory that this launch writes
+        asm volatile ("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+
+    if (tid < lanes && my_frames > 0) {
+        Biquad *const sections = mine [tid].sections;
+#pragma unroll
+        for (int s = 0; s < S; ++s) store_section (sections [s], r [s], my_frames, false);
+    }
+}
+
 __global__ void ingest_kernel (const unsigned char *in, art_s g, int bits, int bytes, int stride, art_s *out, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1298,6 +1389,7 @@ static int channels_per_workgroup (int C)
     while (cpw < 64 && (C + cpw - 1) / cpw > 512) cpw += 8;
     return cpw;
 }
+static constexpr int BQ_BATCH_WORKGROUPS = 512;    // the workgroup count a biquad batch class aims at (arthip_biquad_batch_lanes)
 static constexpr int DEC_BATCH_WORKGROUPS = 1024;  // the workgroup count a serial batch class aims at: four per CU (a small
                                                    // workgroup's LDS lets several share a CU; their serial waves are latency-bound)
 
@@ -1465,6 +1557,35 @@ int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, v
                           case 3: DEC_BATCH_O (3); break; default: DEC_BATCH_O (4); }
 #undef DEC_BATCH_O
 #undef DEC_BATCH_GO
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// Lanes per workgroup of a biquad batch class: the decimator's rule with half its workgroups.  Measured (profiles/biquad_batch.txt,
+// ART's post-filter): the fastest L leaves 256-512 workgroups at 2,048, 8,192 and 16,384 lanes, where the decimator's 1,024 is 9 %
+// slower at 2,048 lanes; below 512 lanes every L is within a few microseconds of the launch.
+int arthip_biquad_batch_lanes (int lanes)
+{
+    int L = 1;
+    while (L < 64 && (lanes + L - 1) / L > BQ_BATCH_WORKGROUPS) L *= 2;
+    return L;
+}
+
+int arthip_biquad_batch_launch (const ArtBqClass *cls, const void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    const ArtBqLane *items = (const ArtBqLane *)((const char *) d_table + cls->offset);
+    const int L = cls->lanes;
+    if (cls->count <= 0) return 0;
+    if (L < 1 || L > 64 || cls->count % L || cls->S < 1 || cls->S > 4) return -1;
+    const int chunk_frames = min (((DEC_CHUNK / L) - 4) & ~3, BQ_BATCH_RUN);
+    const size_t lds = (size_t) 3 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 3 DEC_CHUNK samples (48 KiB)
+    const dim3 grid ((unsigned int)(cls->count / L)), block (ST_THREADS);
+    switch (cls->S) {
+    case 1: hipLaunchKernelGGL (biquad_batch_pipe_kernel<1>, grid, block, lds, st, items, L, chunk_frames); break;
+    case 2: hipLaunchKernelGGL (biquad_batch_pipe_kernel<2>, grid, block, lds, st, items, L, chunk_frames); break;
+    case 3: hipLaunchKernelGGL (biquad_batch_pipe_kernel<3>, grid, block, lds, st, items, L, chunk_frames); break;
+    default: hipLaunchKernelGGL (biquad_batch_pipe_kernel<4>, grid, block, lds, st, items, L, chunk_frames); break;
+    }
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 

@@ -193,6 +193,20 @@ void biquadBankFree (BiquadBank *bank);
  * (pcm_kernels.hip, biquad_spec_kernel).  These report how many chunks had to be recomputed so far (normally 0). */
 unsigned int biquadBankRepairs (BiquadBank *bank);   /* synchronises */
 unsigned int artamdBiquadRepairs (void);             /* the host-pointer calls (biquad_apply_buffer) of this process */
+/* Many independent banks, one launch per section count: the samples in d_buffers [i] and the state biquadBankRead (banks [i])
+ * returns afterwards (index included) are exactly those of biquadBankApplyInterleavedDevice (banks [i], d_buffers [i],
+ * numFrames [i]), i = 0..n-1.  The cascade is serial per channel, so a stereo stream keeps two lanes of one CU busy; here the
+ * channels of many banks share the serial waves, one lane per channel, on the serial form (every form gives the same bits).
+ * Banks on the stream and device of banks [0] are gathered; the launches run on that stream.  A sharded bank
+ * (biquadBankShardCount > 0), a bank on another stream or device, and a call whose single call would take the time-parallel form
+ * and has more than 512 frames (pcm_host.c: BQ_BATCH_SERIAL_MAX, measured) are made as their own single calls, in list order,
+ * before the gathered launches.  A bank with numFrames [i] <= 0 is skipped.  In place, interleaved [numFrames][channels]; the
+ * buffers of one call must not overlap (not checked).  Asynchronous like the single call.  A gathered call recomputes no chunks,
+ * so it adds nothing to biquadBankRepairs.
+ * Returns the number of kernel launches enqueued, counting each single call made on the side as one; 0 when n <= 0 or there was
+ * nothing to do; -1 with nothing enqueued if a bank appears twice or a pointer in banks is NULL; -1 if a launch failed (counted
+ * in artamdErrorCount): the banks of a launch that failed keep their state, and their buffers are left untouched. */
+int biquadBankApplyBatchInterleavedDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const int *numFrames);
 
 /* The reference's void entry points (biquad_apply_buffer / _sample, floatIntegersLE) cannot return an error and this library has no
  * CPU path: a failure there (no device, allocation, launch) is printed to stderr, counted, and leaves silence (floatIntegersLE) or the

@@ -154,6 +154,7 @@ def _bind(width):
         "artamdPeriodMultipleRows": (C.c_int, [C.c_int, C.c_int]),
         "artamdLastError": (C.c_char_p, []),
         "floatIntegersLEDevice": (None, [ptr, C.c_double, C.c_int, C.c_int, C.c_int, ptr, C.c_int, ptr]),
+        "floatIntegersBatchLEDevice": (C.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         # stretch.h
         "stretchInit": (ptr, [C.c_int, C.c_int, C.c_int, C.c_int]),
         "stretchGetOutputCapacity": (C.c_int, [ptr, C.c_int, C.c_double]),
@@ -474,6 +475,20 @@ def _bind(width):
             (C.c_int * n)(*[int(v) for v in frames]))
         if rc < 0:
             raise RuntimeError("biquadBankApplyBatchInterleavedDevice failed")
+        return rc
+
+    def ingest_batch_device(d_ins, gains, bits, nbytes, strides, d_outs, counts, stream=None):
+        """floatIntegersBatchLEDevice: item i as floatIntegersLEDevice (d_ins[i], gains[i], bits[i], nbytes[i], strides[i], d_outs[i],
+        counts[i]), all in one launch on `stream` (a torch stream, a raw address or None: the null stream).  Returns the launch
+        count (raises if the call returned -1)."""
+        n = len(d_ins)
+        st = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        rc = lib().floatIntegersBatchLEDevice(
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), (C.c_double * n)(*[float(v) for v in gains]),
+            (C.c_int * n)(*[int(v) for v in bits]), (C.c_int * n)(*[int(v) for v in nbytes]), (C.c_int * n)(*[int(v) for v in strides]),
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), (C.c_int * n)(*[int(v) for v in counts]), n, st)
+        if rc < 0:
+            raise RuntimeError("floatIntegersBatchLEDevice failed")
         return rc
 
     return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k != "width"}, width=width)

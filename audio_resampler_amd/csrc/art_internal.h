@@ -307,6 +307,22 @@ int arthip_stretch_batch (const ArtStretchItem *d_items, ArtStretchDone *d_done,
 void artamd_note_failure (const char *what);
 
 int arthip_ingest (const unsigned char *d_in, art_s gain_factor, int bits, int bytes, int stride, art_s *d_out, int n, void *stream);
+/* Many buffers' ingest in one launch (floatIntegersBatchLEDevice).  A task is a run of ART_INGEST_RUN consecutive samples of one
+ * item (16 bytes of output); an item's runs start `head` samples before its first sample, so that every whole run of an output
+ * aligned to its sample size is 16-byte aligned. */
+#define ART_INGEST_RUN ((int)(16 / sizeof (art_s)))
+typedef struct {
+    const unsigned char *in;
+    art_s *out;
+    long task0;                          /* first task of this item in the launch's flattened task space */
+    art_s gain_factor;                   /* ingest_gain (gain, bits): the single call's factor */
+    int bits, bytes, stride, count, head;     /* count > 0 samples; 0 <= head < ART_INGEST_RUN */
+} ArtIngestItem;
+/* uploads the n items (table of the calling thread, device memory kept across calls) through the shared pinned staging and launches
+ * ingest_batch_kernel over `tasks` tasks on `stream`; 0, or -1 (nothing launched) */
+int arthip_ingest_batch (const ArtIngestItem *items, int n, long tasks, void *stream);
+/* an item's head for this output address: (address - head * sizeof (art_s)) % 16 == 0 when the address is sample-aligned — pcm_host.c */
+int artamd_ingest_head (const void *d_output);
 
 #ifdef __cplusplus
 }

@@ -1278,6 +1278,45 @@ void floatIntegersLEDevice (const unsigned char *d_input, double inputGain, int 
     arthip_ingest (d_input, ingest_gain (inputGain, inputBits), inputBits, inputBytes, inputStride, d_output, numSamples, stream);
 }
 
+/* the samples an item's runs start before its first one: run k begins at sample k * ART_INGEST_RUN - head, i.e. at byte
+ * addr - head * sizeof (art_s) + 16 k, on a 16-byte boundary whenever the output is aligned to its sample size (else 0: scalar stores) */
+int artamd_ingest_head (const void *d_output)
+{
+    const size_t addr = (size_t) d_output;
+    return addr % sizeof (art_s) ? 0 : (int)(addr % 16 / sizeof (art_s));
+}
+
+/* many buffers, one launch: the items the single call would not skip, in list order, with their first tasks */
+int floatIntegersBatchLEDevice (const unsigned char *const *d_inputs, const double *inputGains, const int *inputBits,
+                                const int *inputBytes, const int *inputStrides, artsample_t *const *d_outputs,
+                                const int *numSamples, int n, void *hipStream)
+{
+    int live = 0;
+    for (int i = 0; i < n; ++i) {
+        if (numSamples [i] <= 0 || inputBits [i] > 24) continue;
+        if (!d_inputs [i] || !d_outputs [i]) { fprintf (stderr, "artamd: ingest batch: a NULL buffer pointer\n"); return -1; }
+        ++live;
+    }
+    if (!live) return 0;
+    ArtIngestItem *items = malloc (sizeof (ArtIngestItem) * (size_t) live);
+    if (!items) { pcm_fail ("ingest batch: out of host memory"); return -1; }
+    long tasks = 0;
+    for (int i = 0, j = 0; i < n; ++i) {
+        if (numSamples [i] <= 0 || inputBits [i] > 24) continue;
+        ArtIngestItem *it = &items [j++];
+        it->in = d_inputs [i]; it->out = d_outputs [i];
+        it->task0 = tasks;
+        it->gain_factor = ingest_gain (inputGains [i], inputBits [i]);
+        it->bits = inputBits [i]; it->bytes = inputBytes [i]; it->stride = inputStrides [i]; it->count = numSamples [i];
+        it->head = artamd_ingest_head (d_outputs [i]);
+        tasks += ((long) numSamples [i] + it->head + ART_INGEST_RUN - 1) / ART_INGEST_RUN;
+    }
+    const int rc = arthip_ingest_batch (items, live, tasks, hipStream);
+    free (items);
+    if (rc) { pcm_fail ("ingest batch: the table could not be uploaded or the launch failed"); return -1; }
+    return 1;
+}
+
 /* host-pointer form: process-wide scratch (device + page-locked), small calls by copy kernels */
 static struct { unsigned char *d_in, *h_in; art_s *d_out, *h_out; size_t in_cap, out_cap; int device; } ingest_scratch = { .device = -1 };
 static pthread_mutex_t ingest_lock = PTHREAD_MUTEX_INITIALIZER;

@@ -1378,6 +1378,46 @@ __global__ void ingest_kernel (const unsigned char *in, art_s g, int bits, int b
     out [i] = v;
 }
 
+// floatIntegersBatchLEDevice: ingest_kernel over many buffers in one launch.  A thread converts a run of ART_INGEST_RUN consecutive
+// samples of one item (16 bytes of output: one store where the address allows it) and finds its item by binary search over the
+// items' first tasks, as decimate_batch_parallel_kernel does.  Per sample: ingest_kernel's bytes, casts and one multiply.
+__global__ __launch_bounds__ (256)
+void ingest_batch_kernel (const ArtIngestItem *items, int n, long tasks)
+{
+    typedef art_s run_t __attribute__ ((ext_vector_type (ART_INGEST_RUN)));
+    const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (task >= tasks) return;
+    int lo_i = 0, hi_i = n - 1;                    // the last item whose first task is <= task
+    while (lo_i < hi_i) { const int mid = (lo_i + hi_i + 1) >> 1; if (items [mid].task0 <= task) lo_i = mid; else hi_i = mid - 1; }
+    const ArtIngestItem &a = items [lo_i];
+    const long s0 = (task - a.task0) * ART_INGEST_RUN - a.head;     // first sample of the run (the head run starts before 0)
+    const int bits = a.bits, bytes = a.bytes, stride = a.stride, count = a.count;
+    const int width = (bits + 7) / 8;
+    const unsigned char *const in = a.in + (bytes - width);
+    const art_s g = a.gain_factor;
+    art_s *const out = a.out;
+    run_t v;
+#pragma unroll
+    for (int j = 0; j < ART_INGEST_RUN; ++j) {
+        art_s x = 0;
+        if (s0 + j >= 0 && s0 + j < count) {
+            const int i = (int)(s0 + j);
+            const unsigned char *p = in + (size_t) i * stride * bytes;
+            if (bits <= 8) x = (art_s)((int) p [0] - 128) * g;
+            else if (bits <= 16) x = (art_s)(int)(short)(p [0] | (p [1] << 8)) * g;
+            else x = (art_s)(int)((uint32_t) p [0] | ((uint32_t) p [1] << 8) | ((uint32_t)(int)(signed char) p [2] << 16)) * g;
+        }
+        v [j] = x;
+    }
+    if (s0 >= 0 && s0 + ART_INGEST_RUN <= count && !((uintptr_t)(out + s0) & 15)) {
+        *(run_t *)(out + s0) = v;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < ART_INGEST_RUN; ++j)
+        if (s0 + j >= 0 && s0 + j < count) out [s0 + j] = v [j];
+}
+
 } // namespace
 
 // The serial stages are latency-bound per lane, so a workgroup gains nothing from more channels — but its LDS chunk (and
@@ -1594,6 +1634,40 @@ int arthip_ingest (const unsigned char *d_in, art_s g, int bits, int bytes, int 
     if (n <= 0) return 0;
     hipLaunchKernelGGL (ingest_kernel, dim3 ((n + 255) / 256), dim3 (256), 0, (hipStream_t) stream, d_in, g, bits, bytes, stride, d_out, n);
     return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// The ingest batch has no context to keep its table in: each calling thread keeps one in device memory.  `ev` marks the last launch
+// that read it; a call on another stream than that launch's waits for it on the device before the table is rewritten.  Like the
+// pinned staging (device_rt.hip), the table and event live as long as the process: a thread that ends leaves its table behind (one
+// allocation of at most twice its largest call's table), so a service calls from long-lived threads.
+struct IngestTable { void *d; size_t cap; int device; hipEvent_t ev; hipStream_t last; bool used; };
+
+int arthip_ingest_batch (const ArtIngestItem *items, int n, long tasks, void *stream)
+{
+    static thread_local IngestTable t = { nullptr, 0, -1, nullptr, nullptr, false };
+    hipStream_t st = (hipStream_t) stream;
+    const size_t bytes = sizeof (ArtIngestItem) * (size_t) n;
+    int device = 0;
+    if (n <= 0 || tasks <= 0) return 0;
+    if (hipGetDevice (&device) != hipSuccess) return -1;
+    if (t.device != device || bytes > t.cap) {
+        if (t.used) (void) hipEventSynchronize (t.ev);
+        if (t.d) (void) hipFree (t.d);
+        if (t.ev && t.device != device) { (void) hipEventDestroy (t.ev); t.ev = nullptr; }
+        t.d = nullptr; t.cap = 0; t.used = false; t.device = device;
+        if (!t.ev && hipEventCreateWithFlags (&t.ev, hipEventDisableTiming) != hipSuccess) { t.ev = nullptr; return -1; }
+        const size_t cap = bytes * 2 > 4096 ? bytes * 2 : 4096;
+        if (hipMalloc (&t.d, cap) != hipSuccess) { t.d = nullptr; return -1; }
+        t.cap = cap;
+    }
+    if (t.used && t.last != st && hipStreamWaitEvent (st, t.ev, 0) != hipSuccess) return -1;
+    if (arthip_decimate_batch_upload (items, bytes, t.d, st)) return -1;
+    hipLaunchKernelGGL (ingest_batch_kernel, dim3 ((unsigned int)((tasks + 255) / 256)), dim3 (256), 0, st, (const ArtIngestItem *) t.d, n, tasks);
+    if (hipGetLastError () != hipSuccess) return -1;
+    // (the table may be rewritten only after this launch: if the event cannot be recorded, wait for the stream instead)
+    if (hipEventRecord (t.ev, st) != hipSuccess) { t.used = false; return hipStreamSynchronize (st) == hipSuccess ? 0 : -1; }
+    t.last = st; t.used = true;
+    return 0;
 }
 
 }

@@ -247,6 +247,16 @@ int decimateProcessBatchInterleavedLEDevice (Decimate *const *cxts, int n, const
                                              unsigned char *const *d_outputs);
 void floatIntegersLEDevice (const unsigned char *d_input, double inputGain, int inputBits, int inputBytes, int inputStride,
                             artsample_t *d_output, int numSamples, void *hipStream);
+/* Many buffers' integer PCM to samples in ONE launch: item i leaves exactly the bits of floatIntegersLEDevice (d_inputs [i],
+ * inputGains [i], inputBits [i], inputBytes [i], inputStrides [i], d_outputs [i], numSamples [i], hipStream), in both builds.  Items
+ * the single call ignores (numSamples [i] <= 0, inputBits [i] > 24) are skipped and their outputs not touched.  Inputs may alias
+ * each other (one PCM buffer read with two gains); outputs must not overlap (not checked).  Asynchronous on hipStream (NULL: the
+ * null stream), on the current device, like the single call; the argument arrays may be reused as soon as the call returns.
+ * Returns the number of kernel launches enqueued (1); 0 when n <= 0 or every item is skipped; -1 with nothing enqueued if a live
+ * item has a NULL input or output pointer; -1 if the launch failed (counted in artamdErrorCount). */
+int floatIntegersBatchLEDevice (const unsigned char *const *d_inputs, const double *inputGains, const int *inputBits,
+                                const int *inputBytes, const int *inputStrides, artsample_t *const *d_outputs,
+                                const int *numSamples, int n, void *hipStream);
 
 /* ---- time stretcher, device pointers (stretch.h) ---- */
 void stretchHipSetStream (Stretch *cxt, void *hipStream);

@@ -122,12 +122,25 @@ int   arthip_stream_wait_event (void *stream, void *event);
 int   arthip_event_sync (void *event);
 int   arthip_enable_peer (int device, int peer);            /* 1: `device` can address `peer`'s memory (or is it); 0: no route */
 int   arthip_slice_copy_bytes (void *dst, size_t dpitch, const void *src, size_t spitch, int width, size_t rows, void *stream);   /* strided rows of bytes, by a kernel */
+/* copies a host table (bytes) into d_table through the shared pinned staging of the batch launches, on `stream`; 0 or -1 */
+int   arthip_table_upload (const void *table, size_t bytes, void *d_table, void *stream);
+/* a device buffer of `need` bytes at least: `dev` itself while *cap suffices, else a new, larger one (its content lost) and *cap
+ * updated; NULL (and *cap 0) when out of memory */
+void *arthip_grow (void *dev, size_t *cap, size_t need);
+
+/* make an object's device (its field `device`) current for the duration of a call; restored afterwards */
+#define ENTER_DEVICE(obj) const int prev_device_ = arthip_current_device (); \
+                          if (prev_device_ != (obj)->device) arthip_set_device ((obj)->device)
+#define LEAVE_DEVICE(obj) do { if (prev_device_ != (obj)->device && prev_device_ >= 0) arthip_set_device (prev_device_); } while (0)
 
 /* ---- resampler_host.c: the device list of multi-device contexts (artamdSetDevices / ARTAMD_DEVICES / ARTAMD_SHARDS) ----
  * how many shards a MULTITHREADED context of `channels` channels gets (0 or 1: an ordinary context) and on which device shard s
  * lives; devices that cannot address `home`'s memory are replaced by `home` */
 #define ART_MAX_DEVICES 64
 int   artamd_shard_plan (int channels, int home, int *devices_out);
+/* the batch calls' check of their list: no item NULL, none named twice (each item's stamp, *stamp_of (item), is set to this call's
+ * number: one pass).  0, or -1 with "artamd: <what> batch: a NULL <noun>" or "... a <noun> appears twice" printed */
+int   artamd_batch_distinct (const void *const *items, int n, unsigned long *(*stamp_of) (const void *item), const char *what, const char *noun);
 void *arthip_malloc (size_t bytes);
 void  arthip_free (void *p);
 int   arthip_h2d (void *dst, const void *src, size_t bytes, void *stream);
@@ -236,18 +249,20 @@ typedef struct {                         /* one context of a time-parallel launc
     art_s scale;
     int C, frames, bits, bytes, dither_type;
 } ArtDecTask;
-typedef struct {
-    int serial;                          /* 1: ArtDecLane items (lanes per workgroup `lanes`), 0: ArtDecTask items */
-    int order, dither;                   /* the shaper order (0: none) and whether dither is on: every item of the class shares them */
-    int count, lanes;                    /* items; lanes per workgroup (serial; count is a multiple of it) */
-    long tasks;                          /* time-parallel: total tasks */
+typedef struct {                         /* a class's slice of a batch call's table (16-byte aligned) */
+    int count;                           /* items; in a serial class, lanes (a multiple of `lanes`: empty lanes pad the last workgroup) */
+    int lanes;                           /* serial classes: lanes per workgroup */
     size_t offset;                       /* of the class's items in the table */
+} ArtBatchSlice;
+typedef struct {
+    int serial;                          /* 1: ArtDecLane items (lanes per workgroup slice.lanes), 0: ArtDecTask items */
+    int order, dither;                   /* the shaper order (0: none) and whether dither is on: every item of the class shares them */
+    long tasks;                          /* time-parallel: total tasks */
+    ArtBatchSlice slice;
 } ArtDecClass;
 #define ART_DEC_SEG 32                   /* frames of one channel per task of the time-parallel kernels (even: generator pairs) */
 /* the lane count per workgroup the batch gives a serial class of `lanes` lanes in all */
 int arthip_decimate_batch_lanes (int lanes);
-/* copies the host table (bytes) into d_table through the shared pinned staging, on `stream`; 0 or -1 */
-int arthip_decimate_batch_upload (const void *table, size_t bytes, void *d_table, void *stream);
 /* one launch of one class from its slice of the uploaded table; 0 or -1 (nothing of it ran) */
 int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, void *stream);
 /* decimateProcessBatchInterleavedLEDevice with a fixed lane count per workgroup for every serial class (lanes > 0; 0: the rule
@@ -256,7 +271,7 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
                            unsigned char *const *d_outputs, int lanes);
 int arthip_biquad_chain (Biquad *d_sections, int C, int S, art_s *d_buf, int frames, int stride, void *stream);
 /* Many banks' calls, one launch per section count (biquadBankApplyBatchInterleavedDevice).  A lane is one channel of one bank;
- * each class's lanes are one slice of the call's table (16-byte aligned), uploaded with arthip_decimate_batch_upload. */
+ * each class's lanes are one slice of the call's table (16-byte aligned), uploaded with arthip_table_upload. */
 typedef struct {
     Biquad *sections;                    /* the bank's d_sections + channel * S */
     art_s *buf;                          /* the bank's buffer + channel; frame f at buf [f * stride], in place */
@@ -264,8 +279,7 @@ typedef struct {
 } ArtBqLane;
 typedef struct {
     int S;                               /* sections per channel: every lane of the class has S */
-    int count, lanes;                    /* lanes in all (a multiple of `lanes`); lanes per workgroup */
-    size_t offset;                       /* of the class's lanes in the table */
+    ArtBatchSlice slice;
 } ArtBqClass;
 /* the lane count per workgroup the batch gives a class of `lanes` lanes in all */
 int arthip_biquad_batch_lanes (int lanes);

@@ -64,6 +64,16 @@ void *arthip_malloc (size_t bytes)
 
 void arthip_free (void *p) { if (p) (void) hipFree (p); }
 
+void *arthip_grow (void *dev, size_t *cap, size_t need)
+{
+    if (need <= *cap) return dev;
+    arthip_free (dev);
+    const size_t want = need + need / 2 + 4096;
+    dev = arthip_malloc (want);
+    *cap = dev ? want : 0;
+    return dev;
+}
+
 int arthip_h2d (void *d, const void *s, size_t n, void *st) { return n ? fail (hipMemcpyAsync (d, s, n, hipMemcpyHostToDevice, (hipStream_t) st), "H2D") : 0; }
 int arthip_d2h (void *d, const void *s, size_t n, void *st) { return n ? fail (hipMemcpyAsync (d, s, n, hipMemcpyDeviceToHost, (hipStream_t) st), "D2H") : 0; }
 int arthip_d2d (void *d, const void *s, size_t n, void *st) { return n ? fail (hipMemcpyAsync (d, s, n, hipMemcpyDeviceToDevice, (hipStream_t) st), "D2D") : 0; }
@@ -229,4 +239,14 @@ int staging_give (Staging *sg, hipStream_t st)
 {
     if (hipEventRecord (sg->ev, st) == hipSuccess) { sg->pending = true; return 0; }
     return hipStreamSynchronize (st) == hipSuccess ? 0 : -1;
+}
+
+extern "C" int arthip_table_upload (const void *table, size_t bytes, void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    Staging *sg = staging_take (bytes);
+    if (!sg) return -1;
+    std::memcpy (sg->host, table, bytes);
+    const bool ok = hipMemcpyAsync (d_table, sg->host, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+    return staging_give (sg, st) || !ok ? -1 : 0;
 }

@@ -314,9 +314,6 @@ struct artamd_biquad_bank {
     unsigned long batch_stamp;           /* the last batch call that named this bank */
     void *d_batch; size_t batch_cap;     /* a batch call's table, when this bank leads it */
 };
-#define BANK_ENTER(b) const int prev_device_ = arthip_current_device (); \
-                      if (prev_device_ != (b)->device) arthip_set_device ((b)->device)
-#define BANK_LEAVE(b) do { if (prev_device_ != (b)->device && prev_device_ >= 0) arthip_set_device (prev_device_); } while (0)
 
 BiquadBank *biquadBankCreate (const Biquad *sections, int numChannels, int numSections)
 {
@@ -388,9 +385,9 @@ int biquadBankShardCount (BiquadBank *b) { return b->nshards; }
 void biquadBankSetStream (BiquadBank *b, void *stream)
 {
     if (b->stream == stream) return;
-    BANK_ENTER (b);
+    ENTER_DEVICE (b);
     arthip_sync (b->stream);
-    BANK_LEAVE (b);
+    LEAVE_DEVICE (b);
     b->stream = stream;
 }
 
@@ -430,7 +427,7 @@ void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int
         if (prev >= 0) arthip_set_device (prev);
         return;
     }
-    BANK_ENTER (b);
+    ENTER_DEVICE (b);
     const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
 
     if (L && numFrames >= 2 * L) {
@@ -448,7 +445,7 @@ void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int
         if (b->d_tmp && b->d_spec) {
             arthip_d2d (b->d_tmp, d_buffer, samples * sizeof (art_s), b->stream);
             if (!arthip_biquad_spec (b->d_sections, b->C, b->S, b->d_tmp, b->C, d_buffer, b->C, numFrames, L, b->warmup, b->d_spec, b->d_first_bad, b->d_repairs, b->stream)) {
-                BANK_LEAVE (b);
+                LEAVE_DEVICE (b);
                 return;
             }
         }
@@ -458,12 +455,12 @@ void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int
         arthip_biquad_order2 (b->d_sections, b->C, b->S, d_buffer, numFrames, b->C, b->stream);
     else
         arthip_biquad_chain (b->d_sections, b->C, b->S, d_buffer, numFrames, b->C, b->stream);
-    BANK_LEAVE (b);
+    LEAVE_DEVICE (b);
 }
 
 void biquadBankRead (BiquadBank *b, Biquad *sections)
 {
-    BANK_ENTER (b);
+    ENTER_DEVICE (b);
     if (b->nshards) {
         arthip_sync (b->stream);
         for (int k = 0; k < b->nshards; ++k) biquadBankRead (b->shards [k], sections + (size_t) b->shard_first [k] * b->S);
@@ -472,14 +469,14 @@ void biquadBankRead (BiquadBank *b, Biquad *sections)
         arthip_d2h (sections, b->d_sections, sizeof (Biquad) * (size_t) b->C * b->S, b->stream);
         arthip_sync (b->stream);
     }
-    BANK_LEAVE (b);
+    LEAVE_DEVICE (b);
 }
 
 /* chunks the time-parallel form had to recompute for this bank so far (synchronises; diagnostics) */
 unsigned int biquadBankRepairs (BiquadBank *b)
 {
     unsigned int n = 0;
-    BANK_ENTER (b);
+    ENTER_DEVICE (b);
     if (b->nshards) {
         arthip_sync (b->stream);
         for (int k = 0; k < b->nshards; ++k) n += biquadBankRepairs (b->shards [k]);
@@ -488,14 +485,14 @@ unsigned int biquadBankRepairs (BiquadBank *b)
         arthip_d2h (&n, b->d_repairs, sizeof (n), b->stream);
         arthip_sync (b->stream);
     }
-    BANK_LEAVE (b);
+    LEAVE_DEVICE (b);
     return n;
 }
 
 void biquadBankFree (BiquadBank *b)
 {
     if (!b) return;
-    BANK_ENTER (b);
+    ENTER_DEVICE (b);
     arthip_sync (b->stream);
     for (int k = 0; k < b->nshards; ++k) {
         if (b->shards [k]) { void *st = b->shards [k]->stream; biquadBankFree (b->shards [k]); arthip_stream_destroy (st); }
@@ -505,7 +502,7 @@ void biquadBankFree (BiquadBank *b)
     free (b->shards); free (b->shard_first); free (b->ev_shard);
     arthip_free (b->d_sections); arthip_free (b->d_tmp); arthip_free (b->d_spec); arthip_free (b->d_repairs); arthip_free (b->d_first_bad); arthip_free (b->d_slice);
     arthip_free (b->d_batch);
-    BANK_LEAVE (b);
+    LEAVE_DEVICE (b);
     free (b);
 }
 
@@ -534,9 +531,6 @@ struct artamd_decimator {
     void *d_batch; size_t batch_cap;                               /* a batch call's table, when this context leads it */
 };
 #define DEC_KERNEL_COPY_LIMIT ((size_t) 1 << 20)
-#define DEC_ENTER(hip) const int prev_device_ = arthip_current_device (); \
-                       if (prev_device_ != (hip)->device) arthip_set_device ((hip)->device)
-#define DEC_LEAVE(hip) do { if (prev_device_ != (hip)->device && prev_device_ >= 0) arthip_set_device (prev_device_); } while (0)
 
 /* noise-shaping transfer function N(z) (a0 == 1) -> error-feedback filter H(z), reference decimator.c:389-409 */
 static void shaper_design (Biquad *f, double a1, double a2, double a3, double a4, double b1, double b2, double b3, double b4)
@@ -699,7 +693,7 @@ void decimateFree (Decimate *cxt)
     if (!cxt) return;
     struct artamd_decimator *hip = cxt->hip;
     if (hip) {
-        DEC_ENTER (hip);
+        ENTER_DEVICE (hip);
         arthip_sync (hip->stream);
         arthip_free (hip->d_state); arthip_host_free (hip->h_state);
         arthip_free (hip->d_in); arthip_free (hip->d_out); arthip_host_free (hip->h_in); arthip_host_free (hip->h_out);
@@ -714,7 +708,7 @@ void decimateFree (Decimate *cxt)
         }
         if (hip->ev_parent) arthip_event_destroy (hip->ev_parent);
         free (hip->shards); free (hip->shard_first); free (hip->ev_shard);
-        DEC_LEAVE (hip);
+        LEAVE_DEVICE (hip);
         free (hip);
     }
     free (cxt->feedback); free (cxt->tpdf_generators); free (cxt->noise_shapers);
@@ -737,9 +731,9 @@ static void dec_args (Decimate *cxt, ArtDecArgs *a)
 void decimateHipSetStream (Decimate *cxt, void *stream)
 {
     if (cxt->hip->stream == stream) return;
-    DEC_ENTER (cxt->hip);
+    ENTER_DEVICE (cxt->hip);
     arthip_sync (cxt->hip->stream);
-    DEC_LEAVE (cxt->hip);
+    LEAVE_DEVICE (cxt->hip);
     cxt->hip->stream = stream;
 }
 
@@ -803,10 +797,10 @@ void decimateProcessInterleavedLEDevice (Decimate *cxt, const artsample_t *d_inp
     if (numInputFrames <= 0) return;
     if (cxt->hip->nshards) { dec_sharded_device_call (cxt, d_input, numInputFrames, d_output); return; }
     ArtDecArgs a;
-    DEC_ENTER (cxt->hip);
+    ENTER_DEVICE (cxt->hip);
     dec_args (cxt, &a);
     dec_swap_if (cxt, arthip_decimate (&a, d_input, numInputFrames, d_output, cxt->hip->stream));
-    DEC_LEAVE (cxt->hip);
+    LEAVE_DEVICE (cxt->hip);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -828,21 +822,14 @@ static int lane_order (const void *pa, const void *pb)     /* longest first; the
     return a->channel < b->channel ? -1 : a->channel > b->channel;
 }
 
+static unsigned long *dec_stamp (const void *cxt) { return &((const Decimate *) cxt)->hip->batch_stamp; }
+
 /* lanes > 0: every serial class gets that many lanes per workgroup (the measurements of the rule); 0: the rule */
 int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                            unsigned char *const *d_outputs, int lanes)
 {
     if (n <= 0) return 0;
-    for (int i = 0; i < n; ++i)
-        if (!cxts [i]) { fprintf (stderr, "artamd: decimate batch: a NULL context\n"); return -1; }
-    {   /* a context may appear only once: stamp each with this call's number (one pass) */
-        static unsigned long calls;
-        const unsigned long stamp = __atomic_add_fetch (&calls, 1, __ATOMIC_RELAXED);
-        for (int i = 0; i < n; ++i) {
-            if (cxts [i]->hip->batch_stamp == stamp) { fprintf (stderr, "artamd: decimate batch: a context appears twice\n"); return -1; }
-            cxts [i]->hip->batch_stamp = stamp;
-        }
-    }
+    if (artamd_batch_distinct ((const void *const *) cxts, n, dec_stamp, "decimate", "context")) return -1;
 
     struct artamd_decimator *lead = cxts [0]->hip;
     ArtDecArgs *args = malloc (sizeof (ArtDecArgs) * (size_t) n);
@@ -874,31 +861,31 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
         const int k = numInputFrames [i] >= 64 && !a->shaping_on ? (a->dither_on != 0)
                     : 2 + 2 * (a->shaping_on ? (a->shaping_order >= 1 && a->shaping_order <= 4 ? a->shaping_order : 4) : 0) + (a->dither_on != 0);
         cls_of [i] = k;
-        if (cls [k].serial) { cls [k].count += a->C; if (a->C > most) most = a->C; }
-        else { cls [k].tasks += (long) a->C * ((numInputFrames [i] + ART_DEC_SEG - 1) / ART_DEC_SEG); cls [k].count++; }
+        if (cls [k].serial) { cls [k].slice.count += a->C; if (a->C > most) most = a->C; }
+        else { cls [k].tasks += (long) a->C * ((numInputFrames [i] + ART_DEC_SEG - 1) / ART_DEC_SEG); cls [k].slice.count++; }
     }
 
     /* the table: every present class's items, 16-byte aligned slices */
     size_t bytes = 0;
     int maxlanes = 0;
     for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
-        if (!cls [k].count) continue;
+        if (!cls [k].slice.count) continue;
         if (cls [k].serial) {
-            cls [k].lanes = lanes > 0 ? (lanes < 64 ? lanes : 64) : arthip_decimate_batch_lanes (cls [k].count);
-            cls [k].count = (cls [k].count + cls [k].lanes - 1) / cls [k].lanes * cls [k].lanes;      /* (+ empty lanes) */
-            if (cls [k].count > maxlanes) maxlanes = cls [k].count;
+            cls [k].slice.lanes = lanes > 0 ? (lanes < 64 ? lanes : 64) : arthip_decimate_batch_lanes (cls [k].slice.count);
+            cls [k].slice.count = (cls [k].slice.count + cls [k].slice.lanes - 1) / cls [k].slice.lanes * cls [k].slice.lanes;      /* (+ empty lanes) */
+            if (cls [k].slice.count > maxlanes) maxlanes = cls [k].slice.count;
         }
-        cls [k].offset = bytes;
-        bytes += ((cls [k].serial ? sizeof (ArtDecLane) : sizeof (ArtDecTask)) * (size_t) cls [k].count + 15) & ~(size_t) 15;
+        cls [k].slice.offset = bytes;
+        bytes += ((cls [k].serial ? sizeof (ArtDecLane) : sizeof (ArtDecTask)) * (size_t) cls [k].slice.count + 15) & ~(size_t) 15;
     }
     if (!bytes) { rc = launches; goto out; }
     table = calloc (1, bytes);
     refs = maxlanes ? malloc (sizeof (DecLaneRef) * (size_t) maxlanes) : NULL;
     if (!table || (maxlanes && !refs)) { pcm_fail ("decimate batch: out of host memory"); goto out; }
     for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
-        if (!cls [k].count) continue;
+        if (!cls [k].slice.count) continue;
         if (!cls [k].serial) {
-            ArtDecTask *t = (ArtDecTask *)(table + cls [k].offset);
+            ArtDecTask *t = (ArtDecTask *)(table + cls [k].slice.offset);
             long task0 = 0;
             for (int i = 0, j = 0; i < n; ++i) {
                 if (cls_of [i] != k) continue;
@@ -917,7 +904,7 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
             if (cls_of [i] == k)
                 for (int c = 0; c < args [i].C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numInputFrames [i]; ++m; }
         qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
-        ArtDecLane *l = (ArtDecLane *)(table + cls [k].offset);       /* (the padding lanes stay zero: 0 frames) */
+        ArtDecLane *l = (ArtDecLane *)(table + cls [k].slice.offset);       /* (the padding lanes stay zero: 0 frames) */
         for (int j = 0; j < m; ++j) {
             const int i = refs [j].ctx, c = refs [j].channel;
             const ArtDecArgs *a = &args [i];
@@ -931,18 +918,14 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
     }
 
     {
-        DEC_ENTER (lead);
-        if (bytes > lead->batch_cap) {
-            arthip_free (lead->d_batch);
-            lead->batch_cap = bytes * 2;
-            if (!(lead->d_batch = arthip_malloc (lead->batch_cap))) lead->batch_cap = 0;
-        }
-        if (!lead->d_batch || arthip_decimate_batch_upload (table, bytes, lead->d_batch, lead->stream))
+        ENTER_DEVICE (lead);
+        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, bytes);
+        if (!lead->d_batch || arthip_table_upload (table, bytes, lead->d_batch, lead->stream))
             pcm_fail ("decimate batch: the table could not be uploaded (nothing launched)");
         else {
             rc = 0;
             for (int k = 0; k < DEC_BATCH_CLASSES && !rc; ++k) {
-                if (!cls [k].count) continue;
+                if (!cls [k].slice.count) continue;
                 if (arthip_decimate_batch_launch (&cls [k], lead->d_batch, lead->stream)) { pcm_fail ("decimate batch: launch failed"); rc = -1; break; }
                 ++launches;
                 if (!cls [k].serial)          /* the time-parallel form left the generator state in gens_next: as dec_swap_if */
@@ -951,7 +934,7 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
             }
             if (!rc) rc = launches;
         }
-        DEC_LEAVE (lead);
+        LEAVE_DEVICE (lead);
     }
 out:
     free (args); free (cls_of); free (refs); free (table);
@@ -975,20 +958,13 @@ int decimateProcessBatchInterleavedLEDevice (Decimate *const *cxts, int n, const
 #define BQ_BATCH_SERIAL_MAX 512                    /* measured: profiles/biquad_batch.txt (--sweep, serial_max): one serial lane of ART's
                                                     * pre-filter takes as long as its time-parallel single call at 510-570 frames */
 
+static unsigned long *bank_stamp (const void *b) { return &((BiquadBank *) b)->batch_stamp; }
+
 /* lanes > 0: every class gets that many lanes per workgroup; serialMax < 0: BQ_BATCH_SERIAL_MAX (the measurements of both rules) */
 int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const int *numFrames, int lanes, int serialMax)
 {
     if (n <= 0) return 0;
-    for (int i = 0; i < n; ++i)
-        if (!banks [i]) { fprintf (stderr, "artamd: biquad batch: a NULL bank\n"); return -1; }
-    {   /* a bank may appear only once: stamp each with this call's number (one pass) */
-        static unsigned long calls;
-        const unsigned long stamp = __atomic_add_fetch (&calls, 1, __ATOMIC_RELAXED);
-        for (int i = 0; i < n; ++i) {
-            if (banks [i]->batch_stamp == stamp) { fprintf (stderr, "artamd: biquad batch: a bank appears twice\n"); return -1; }
-            banks [i]->batch_stamp = stamp;
-        }
-    }
+    if (artamd_batch_distinct ((const void *const *) banks, n, bank_stamp, "biquad", "bank")) return -1;
     if (serialMax < 0) serialMax = BQ_BATCH_SERIAL_MAX;
 
     BiquadBank *lead = banks [0];
@@ -1012,32 +988,32 @@ int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_
             continue;
         }
         gathered [i] = 1;
-        cls [b->S - 1].count += b->C;
+        cls [b->S - 1].slice.count += b->C;
     }
 
     /* the table: every present class's lanes (+ empty lanes up to whole workgroups), 16-byte aligned slices */
     size_t bytes = 0;
     for (int k = 0; k < 4; ++k) {
-        if (!cls [k].count) continue;
+        if (!cls [k].slice.count) continue;
         cls [k].S = k + 1;
-        cls [k].lanes = lanes > 0 ? (lanes < 64 ? lanes : 64) : arthip_biquad_batch_lanes (cls [k].count);
-        cls [k].count = (cls [k].count + cls [k].lanes - 1) / cls [k].lanes * cls [k].lanes;
-        if (cls [k].count > maxlanes) maxlanes = cls [k].count;
-        cls [k].offset = bytes;
-        bytes += (sizeof (ArtBqLane) * (size_t) cls [k].count + 15) & ~(size_t) 15;
+        cls [k].slice.lanes = lanes > 0 ? (lanes < 64 ? lanes : 64) : arthip_biquad_batch_lanes (cls [k].slice.count);
+        cls [k].slice.count = (cls [k].slice.count + cls [k].slice.lanes - 1) / cls [k].slice.lanes * cls [k].slice.lanes;
+        if (cls [k].slice.count > maxlanes) maxlanes = cls [k].slice.count;
+        cls [k].slice.offset = bytes;
+        bytes += (sizeof (ArtBqLane) * (size_t) cls [k].slice.count + 15) & ~(size_t) 15;
     }
     if (!bytes) { rc = launches; goto out; }
     table = calloc (1, bytes);
     refs = malloc (sizeof (DecLaneRef) * (size_t) maxlanes);
     if (!table || !refs) { pcm_fail ("biquad batch: out of host memory"); goto out; }
     for (int k = 0; k < 4; ++k) {
-        if (!cls [k].count) continue;
+        if (!cls [k].slice.count) continue;
         int m = 0;
         for (int i = 0; i < n; ++i)
             if (gathered [i] && banks [i]->S == k + 1)
                 for (int c = 0; c < banks [i]->C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numFrames [i]; ++m; }
         qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
-        ArtBqLane *l = (ArtBqLane *)(table + cls [k].offset);         /* (the padding lanes stay zero: 0 frames) */
+        ArtBqLane *l = (ArtBqLane *)(table + cls [k].slice.offset);         /* (the padding lanes stay zero: 0 frames) */
         for (int j = 0; j < m; ++j) {
             const BiquadBank *b = banks [refs [j].ctx];
             const int c = refs [j].channel;
@@ -1049,24 +1025,20 @@ int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_
     }
 
     {
-        BANK_ENTER (lead);
-        if (bytes > lead->batch_cap) {
-            arthip_free (lead->d_batch);
-            lead->batch_cap = bytes * 2;
-            if (!(lead->d_batch = arthip_malloc (lead->batch_cap))) lead->batch_cap = 0;
-        }
-        if (!lead->d_batch || arthip_decimate_batch_upload (table, bytes, lead->d_batch, lead->stream))
+        ENTER_DEVICE (lead);
+        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, bytes);
+        if (!lead->d_batch || arthip_table_upload (table, bytes, lead->d_batch, lead->stream))
             pcm_fail ("biquad batch: the table could not be uploaded (nothing launched)");
         else {
             rc = 0;
             for (int k = 0; k < 4; ++k) {
-                if (!cls [k].count) continue;
+                if (!cls [k].slice.count) continue;
                 if (arthip_biquad_batch_launch (&cls [k], lead->d_batch, lead->stream)) { pcm_fail ("biquad batch: launch failed"); rc = -1; break; }
                 ++launches;
             }
             if (!rc) rc = launches;
         }
-        BANK_LEAVE (lead);
+        LEAVE_DEVICE (lead);
     }
 out:
     free (gathered); free (refs); free (table);
@@ -1086,17 +1058,17 @@ long decimateHipClipped (Decimate *cxt)
     if (cxt->hip->nshards) {
         long sum = 0;
         {
-            DEC_ENTER (cxt->hip);
+            ENTER_DEVICE (cxt->hip);
             arthip_sync (cxt->hip->stream);
-            DEC_LEAVE (cxt->hip);
+            LEAVE_DEVICE (cxt->hip);
         }
         for (int k = 0; k < cxt->hip->nshards; ++k) sum += decimateHipClipped (cxt->hip->shards [k]);
         return sum;
     }
-    DEC_ENTER (cxt->hip);
+    ENTER_DEVICE (cxt->hip);
     arthip_d2h (&total, cxt->hip->d_clipped, sizeof (total), cxt->hip->stream);
     arthip_sync (cxt->hip->stream);
-    DEC_LEAVE (cxt->hip);
+    LEAVE_DEVICE (cxt->hip);
     return (long) total;
 }
 
@@ -1181,11 +1153,11 @@ int decimateProcessInterleavedLE (Decimate *cxt, const artsample_t *input, int n
     if (numInputFrames <= 0) return 0;
     const size_t samples = (size_t) numInputFrames * cxt->numChannels, in_bytes = samples * sizeof (art_s);
     ArtDecArgs a;
-    DEC_ENTER (hip);
+    ENTER_DEVICE (hip);
 
     if (dec_reserve (cxt, in_bytes, samples * cxt->outputBytes)) {
         fprintf (stderr, "artamd: decimator device allocation failed: %s\n", arthip_last_error ());
-        DEC_LEAVE (hip);
+        LEAVE_DEVICE (hip);
         return 0;
     }
     if (in_bytes + 16 <= DEC_KERNEL_COPY_LIMIT) {
@@ -1211,7 +1183,7 @@ int decimateProcessInterleavedLE (Decimate *cxt, const artsample_t *input, int n
         dec_swap_if (cxt, arthip_decimate (&a, hip->d_in, numInputFrames, hip->d_out, hip->stream));
         clipped = dec_finish (cxt, output, samples * cxt->outputBytes);
     }
-    DEC_LEAVE (hip);
+    LEAVE_DEVICE (hip);
     return clipped;
 }
 
@@ -1256,9 +1228,9 @@ int decimateProcessLE (Decimate *cxt, const artsample_t *const *input, int numIn
         if (prev >= 0) arthip_set_device (prev);
         return dec_finish_shards (cxt);
     }
-    DEC_ENTER (hip);
+    ENTER_DEVICE (hip);
     const int clipped = dec_planar_begin (cxt, input, numInputFrames, output) ? 0 : dec_finish (cxt, NULL, 0);
-    DEC_LEAVE (hip);
+    LEAVE_DEVICE (hip);
     return clipped;
 }
 

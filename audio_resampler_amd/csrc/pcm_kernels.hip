@@ -12,9 +12,7 @@
 #include <climits>
 #include <cstdlib>
 #include <type_traits>
-#include <cstring>
 #include "art_internal.h"
-#include "staging.hip.h"
 
 namespace {
 
@@ -322,6 +320,21 @@ void biquad_commit_kernel (Biquad *sections, int C, int K, int L, const art_s *i
 
 __device__ __forceinline__ uint32_t lcg (uint32_t r) { return ((r << 4) - r) ^ 1u; }
 
+// One draw of the TPDF dither (reference decimator.c:370-382): five generator steps, and u = (first >> 1) + (r >> 1); the dither
+// is u / 2^31 - 1.0.
+__device__ __forceinline__ uint32_t tpdf_step (uint32_t &g, int dither_type)
+{
+    const uint32_t start = g;
+    uint32_t r = lcg (lcg (start));
+    const uint32_t first = dither_type < 0 ? ~start : dither_type > 0 ? start : ~r;
+    r = lcg (lcg (lcg (r)));
+    g = r;
+    return (first >> 1) + (r >> 1);
+}
+
+// u / 2^31 - 1.0, converted to the sample type, is exactly this (power-of-two scale)
+__device__ __forceinline__ art_s tpdf_value (uint32_t u) { return (art_s)(int)(u ^ 0x80000000u) * (art_s) 4.656612873077392578125e-10; }
+
 __global__ void decimate_kernel (ArtDecArgs a, const art_s *in, long in_pitch, int frames, unsigned char *out, long out_pitch)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -343,12 +356,7 @@ __global__ void decimate_kernel (ArtDecArgs a, const art_s *in, long in_pitch, i
         art_s dither = 0.0f;
 
         if (a.dither_on) {
-            const uint32_t start = gen;
-            uint32_t r = lcg (lcg (start));
-            const uint32_t first = a.dither_type < 0 ? ~start : a.dither_type > 0 ? start : ~r;
-            r = lcg (lcg (lcg (r)));
-            gen = r;
-            const double tri = ((double)((first >> 1) + (r >> 1)) / 2147483648.0) - 1.0;
+            const double tri = ((double) tpdf_step (gen, a.dither_type) / 2147483648.0) - 1.0;     // the reference's order
             dither = (art_s) tri;
         }
 
@@ -822,16 +830,7 @@ void decimate_lds_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned ch
                 const int c = task % Cg, k = task / Cg, n0 = k * DEC_SEG;
                 uint32_t g = jump_pairs (s_gen [c], (unsigned int)(n0 / 2));
                 const int cnt = min (DEC_SEG, nf - n0);
-                for (int i = 0; i < cnt; ++i) {
-                    const uint32_t start = g;
-                    uint32_t r = lcg (lcg (start));
-                    const uint32_t first = dtype < 0 ? ~start : dtype > 0 ? start : ~r;
-                    r = lcg (lcg (lcg (r)));
-                    g = r;
-                    // ((first>>1)+(r>>1))/2^31 - 1.0, converted to the sample type, is exactly this (power-of-two scale)
-                    const uint32_t u = (first >> 1) + (r >> 1);
-                    dth [(n0 + i) * Cg + c] = (art_s)(int)(u ^ 0x80000000u) * (art_s) 4.656612873077392578125e-10;
-                }
+                for (int i = 0; i < cnt; ++i) dth [(n0 + i) * Cg + c] = tpdf_value (tpdf_step (g, dtype));
                 if (n0 + cnt == nf) s_next [c] = g;          // the channel's last task publishes the next chunk's state
             }
         }
@@ -951,15 +950,7 @@ void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned c
                         const int c = task % Cg, sgm = task / Cg, n0 = sgm * DEC_SEG;
                         uint32_t g = jump_pairs (s_gen [k & 1][c], (unsigned int)(n0 / 2));
                         const int cnt = min (DEC_SEG, nf - n0);
-                        for (int i = 0; i < cnt; ++i) {
-                            const uint32_t start = g;
-                            uint32_t r = lcg (lcg (start));
-                            const uint32_t first = dtype < 0 ? ~start : dtype > 0 ? start : ~r;
-                            r = lcg (lcg (lcg (r)));
-                            g = r;
-                            const uint32_t u = (first >> 1) + (r >> 1);
-                            dth [c * pitch + n0 + i] = (art_s)(int)(u ^ 0x80000000u) * (art_s) 4.656612873077392578125e-10;
-                        }
+                        for (int i = 0; i < cnt; ++i) dth [c * pitch + n0 + i] = tpdf_value (tpdf_step (g, dtype));
                         if (n0 + cnt == nf) s_gen [(k & 1) ^ 1][c] = g;      // start state of chunk k+1
                     }
                 }
@@ -1047,16 +1038,7 @@ void decimate_parallel_kernel (ArtDecArgs a, const art_s *in, int frames, unsign
     unsigned int clips = 0;
 
     for (int i = 0; i < cnt; ++i) {
-        art_s dither = 0.0f;
-        if (DITHER) {
-            const uint32_t start = g;
-            uint32_t r = lcg (lcg (start));
-            const uint32_t first = a.dither_type < 0 ? ~start : a.dither_type > 0 ? start : ~r;
-            r = lcg (lcg (lcg (r)));
-            g = r;
-            const uint32_t u = (first >> 1) + (r >> 1);
-            dither = (art_s)(int)(u ^ 0x80000000u) * (art_s) 4.656612873077392578125e-10;
-        }
+        const art_s dither = DITHER ? tpdf_value (tpdf_step (g, a.dither_type)) : 0.0f;
         const size_t e = (size_t)(n0 + i) * a.C + c;
         const art_s scaled = in [e] * a.scale;
         const art_s code = scaled - fb;
@@ -1141,15 +1123,7 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
                         const int dtype = (s_fmt [c] >> 16) - 1;
                         uint32_t g = jump_pairs (s_gen [k & 1][c], (unsigned int)(n0 / 2));
                         const int cnt = min (DEC_SEG, nfc - n0);
-                        for (int i = 0; i < cnt; ++i) {
-                            const uint32_t start = g;
-                            uint32_t r = lcg (lcg (start));
-                            const uint32_t first = dtype < 0 ? ~start : dtype > 0 ? start : ~r;
-                            r = lcg (lcg (lcg (r)));
-                            g = r;
-                            const uint32_t u = (first >> 1) + (r >> 1);
-                            dth [c * pitch + n0 + i] = (art_s)(int)(u ^ 0x80000000u) * (art_s) 4.656612873077392578125e-10;
-                        }
+                        for (int i = 0; i < cnt; ++i) dth [c * pitch + n0 + i] = tpdf_value (tpdf_step (g, dtype));
                         if (n0 + cnt == nfc) s_gen [(k & 1) ^ 1][c] = g;    // start state of the lane's chunk k+1 (or its final state)
                     }
                 }
@@ -1218,17 +1192,24 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
     }
 }
 
+// the item a task of a flattened task space belongs to: the last whose first task is <= task (items [0].task0 == 0, ascending)
+template <typename Item>
+__device__ __forceinline__ const Item &item_of (const Item *items, int n, long task)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (items [mid].task0 <= task) lo = mid; else hi = mid - 1; }
+    return items [lo];
+}
+
 // decimate_parallel_kernel over a flattened task space: (context, channel, DEC_SEG-frame segment).  A thread finds its context by
-// binary search over the contexts' first tasks.
+// binary search over the contexts' first tasks (item_of).
 template <bool DITHER>
 __global__ __launch_bounds__ (256)
 void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
 {
     const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
     if (task >= tasks) return;
-    int lo_i = 0, hi_i = n - 1;                    // the last item whose first task is <= task
-    while (lo_i < hi_i) { const int mid = (lo_i + hi_i + 1) >> 1; if (items [mid].task0 <= task) lo_i = mid; else hi_i = mid - 1; }
-    const ArtDecTask &a = items [lo_i];
+    const ArtDecTask &a = item_of (items, n, task);
     const long t = task - a.task0;
     const int c = (int)(t % a.C);
     const long n0 = (t / a.C) * DEC_SEG;
@@ -1247,16 +1228,7 @@ void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
     unsigned int clips = 0;
 
     for (int i = 0; i < cnt; ++i) {
-        art_s dither = 0.0f;
-        if (DITHER) {
-            const uint32_t start = g;
-            uint32_t r = lcg (lcg (start));
-            const uint32_t first = dtype < 0 ? ~start : dtype > 0 ? start : ~r;
-            r = lcg (lcg (lcg (r)));
-            g = r;
-            const uint32_t u = (first >> 1) + (r >> 1);
-            dither = (art_s)(int)(u ^ 0x80000000u) * (art_s) 4.656612873077392578125e-10;
-        }
+        const art_s dither = DITHER ? tpdf_value (tpdf_step (g, dtype)) : 0.0f;
         const size_t e = (size_t)(n0 + i) * C + c;
         const art_s scaled = a.in [e] * scale;
         const art_s code = scaled - fb;
@@ -1365,17 +1337,20 @@ void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_fram
     }
 }
 
+// one little-endian integer sample (p: its first value byte) times g (reference decimator.c:416-450)
+__device__ __forceinline__ art_s decode_pcm (const unsigned char *p, int bits, art_s g)
+{
+    if (bits <= 8) return (art_s)((int) p [0] - 128) * g;
+    if (bits <= 16) return (art_s)(int)(short)(p [0] | (p [1] << 8)) * g;
+    return (art_s)(int)((uint32_t) p [0] | ((uint32_t) p [1] << 8) | ((uint32_t)(int)(signed char) p [2] << 16)) * g;
+}
+
 __global__ void ingest_kernel (const unsigned char *in, art_s g, int bits, int bytes, int stride, art_s *out, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int width = (bits + 7) / 8;
-    const unsigned char *p = in + (size_t) i * stride * bytes + (bytes - width);
-    art_s v;
-    if (bits <= 8) v = (art_s)((int) p [0] - 128) * g;
-    else if (bits <= 16) v = (art_s)(int)(short)(p [0] | (p [1] << 8)) * g;
-    else v = (art_s)(int)((uint32_t) p [0] | ((uint32_t) p [1] << 8) | ((uint32_t)(int)(signed char) p [2] << 16)) * g;
-    out [i] = v;
+    out [i] = decode_pcm (in + (size_t) i * stride * bytes + (bytes - width), bits, g);
 }
 
 // floatIntegersBatchLEDevice: ingest_kernel over many buffers in one launch.  A thread converts a run of ART_INGEST_RUN consecutive
@@ -1387,9 +1362,7 @@ void ingest_batch_kernel (const ArtIngestItem *items, int n, long tasks)
     typedef art_s run_t __attribute__ ((ext_vector_type (ART_INGEST_RUN)));
     const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
     if (task >= tasks) return;
-    int lo_i = 0, hi_i = n - 1;                    // the last item whose first task is <= task
-    while (lo_i < hi_i) { const int mid = (lo_i + hi_i + 1) >> 1; if (items [mid].task0 <= task) lo_i = mid; else hi_i = mid - 1; }
-    const ArtIngestItem &a = items [lo_i];
+    const ArtIngestItem &a = item_of (items, n, task);
     const long s0 = (task - a.task0) * ART_INGEST_RUN - a.head;     // first sample of the run (the head run starts before 0)
     const int bits = a.bits, bytes = a.bytes, stride = a.stride, count = a.count;
     const int width = (bits + 7) / 8;
@@ -1400,13 +1373,7 @@ void ingest_batch_kernel (const ArtIngestItem *items, int n, long tasks)
 #pragma unroll
     for (int j = 0; j < ART_INGEST_RUN; ++j) {
         art_s x = 0;
-        if (s0 + j >= 0 && s0 + j < count) {
-            const int i = (int)(s0 + j);
-            const unsigned char *p = in + (size_t) i * stride * bytes;
-            if (bits <= 8) x = (art_s)((int) p [0] - 128) * g;
-            else if (bits <= 16) x = (art_s)(int)(short)(p [0] | (p [1] << 8)) * g;
-            else x = (art_s)(int)((uint32_t) p [0] | ((uint32_t) p [1] << 8) | ((uint32_t)(int)(signed char) p [2] << 16)) * g;
-        }
+        if (s0 + j >= 0 && s0 + j < count) x = decode_pcm (in + (size_t)(int)(s0 + j) * stride * bytes, bits, g);
         v [j] = x;
     }
     if (s0 >= 0 && s0 + ART_INGEST_RUN <= count && !((uintptr_t)(out + s0) & 15)) {
@@ -1429,9 +1396,26 @@ static int channels_per_workgroup (int C)
     while (cpw < 64 && (C + cpw - 1) / cpw > 512) cpw += 8;
     return cpw;
 }
-static constexpr int BQ_BATCH_WORKGROUPS = 512;    // the workgroup count a biquad batch class aims at (arthip_biquad_batch_lanes)
-static constexpr int DEC_BATCH_WORKGROUPS = 1024;  // the workgroup count a serial batch class aims at: four per CU (a small
-                                                   // workgroup's LDS lets several share a CU; their serial waves are latency-bound)
+
+// Lanes per workgroup of a serial batch class of `lanes` lanes in all: enough workgroups to fill the CUs first, then more lanes per
+// serial wave (a lane's time is its chain, whatever the lane count; LDS and helper work grow with the lanes), until the class is
+// `workgroups` workgroups.
+static int batch_lanes (int lanes, int workgroups)
+{
+    int L = 1;
+    while (L < 64 && (lanes + L - 1) / L > workgroups) L *= 2;
+    return L;
+}
+// Measured (profiles/decimate_batch.txt): the fastest L puts 512-1,024 workgroups on the chip at 2,048, 8,192 and 16,384 lanes,
+// and L = 1-2 wins below that.  1,024 is four per CU (a small workgroup's LDS lets several share a CU; their serial waves are
+// latency-bound).
+static constexpr int DEC_BATCH_WORKGROUPS = 1024;
+// Measured (profiles/biquad_batch.txt, ART's post-filter): the fastest L leaves 256-512 workgroups at 2,048, 8,192 and 16,384 lanes,
+// where the decimator's 1,024 is 9 % slower at 2,048 lanes; below 512 lanes every L is within a few microseconds of the launch.
+static constexpr int BQ_BATCH_WORKGROUPS = 512;
+
+// frames per chunk of a serial batch workgroup of L lanes: the LDS tile's row (a multiple of 4) or `run`, whichever is less
+static int batch_chunk_frames (int L, int run) { return min (((DEC_CHUNK / L) - 4) & ~3, run); }
 
 extern "C" {
 
@@ -1553,42 +1537,24 @@ int arthip_decimate_planar (const ArtDecArgs *a, const art_s *d_in, long in_pitc
     return decimate_launch (a, d_in, in_pitch, frames, d_out, out_pitch, stream);
 }
 
-// Lanes per workgroup of a serial batch class: enough workgroups to fill the CUs first, then more lanes per serial wave (a lane's
-// time is its chain, whatever the lane count; LDS and helper work grow with the lanes).  Measured (profiles/decimate_batch.txt):
-// the fastest L puts 512-1,024 workgroups on the chip at 2,048, 8,192 and 16,384 lanes, and L = 1-2 wins below that.
-int arthip_decimate_batch_lanes (int lanes)
-{
-    int L = 1;
-    while (L < 64 && (lanes + L - 1) / L > DEC_BATCH_WORKGROUPS) L *= 2;
-    return L;
-}
-
-int arthip_decimate_batch_upload (const void *table, size_t bytes, void *d_table, void *stream)
-{
-    hipStream_t st = (hipStream_t) stream;
-    Staging *sg = staging_take (bytes);
-    if (!sg) return -1;
-    std::memcpy (sg->host, table, bytes);
-    const bool ok = hipMemcpyAsync (d_table, sg->host, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
-    return staging_give (sg, st) || !ok ? -1 : 0;
-}
+int arthip_decimate_batch_lanes (int lanes) { return batch_lanes (lanes, DEC_BATCH_WORKGROUPS); }
 
 int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, void *stream)
 {
     hipStream_t st = (hipStream_t) stream;
-    const void *items = (const char *) d_table + cls->offset;
-    if (cls->count <= 0) return 0;
+    const void *items = (const char *) d_table + cls->slice.offset;
+    if (cls->slice.count <= 0) return 0;
     if (!cls->serial) {
         const dim3 grid ((unsigned int)((cls->tasks + 255) / 256)), block (256);
-        if (cls->dither) hipLaunchKernelGGL (decimate_batch_parallel_kernel<true>, grid, block, 0, st, (const ArtDecTask *) items, cls->count, cls->tasks);
-        else hipLaunchKernelGGL (decimate_batch_parallel_kernel<false>, grid, block, 0, st, (const ArtDecTask *) items, cls->count, cls->tasks);
+        if (cls->dither) hipLaunchKernelGGL (decimate_batch_parallel_kernel<true>, grid, block, 0, st, (const ArtDecTask *) items, cls->slice.count, cls->tasks);
+        else hipLaunchKernelGGL (decimate_batch_parallel_kernel<false>, grid, block, 0, st, (const ArtDecTask *) items, cls->slice.count, cls->tasks);
         return hipGetLastError () == hipSuccess ? 0 : -1;
     }
-    const int L = cls->lanes;
-    if (L < 1 || L > 64 || cls->count % L) return -1;
-    const int chunk_frames = min (((DEC_CHUNK / L) - 4) & ~3, DEC_BATCH_RUN);
+    const int L = cls->slice.lanes;
+    if (L < 1 || L > 64 || cls->slice.count % L) return -1;
+    const int chunk_frames = batch_chunk_frames (L, DEC_BATCH_RUN);
     const size_t lds = (size_t) 5 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 5 DEC_CHUNK samples (80 KiB)
-    const dim3 grid ((unsigned int)(cls->count / L)), block (ST_THREADS);
+    const dim3 grid ((unsigned int)(cls->slice.count / L)), block (ST_THREADS);
 #define DEC_BATCH_GO(O, D) do { auto k = decimate_batch_pipe_kernel<O, D>; static bool once = false; \
         if (!once) { (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(5 * DEC_CHUNK * sizeof (art_s))); once = true; } \
         hipLaunchKernelGGL (k, grid, block, lds, st, (const ArtDecLane *) items, L, chunk_frames); } while (0)
@@ -1600,26 +1566,18 @@ int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, v
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-// Lanes per workgroup of a biquad batch class: the decimator's rule with half its workgroups.  Measured (profiles/biquad_batch.txt,
-// ART's post-filter): the fastest L leaves 256-512 workgroups at 2,048, 8,192 and 16,384 lanes, where the decimator's 1,024 is 9 %
-// slower at 2,048 lanes; below 512 lanes every L is within a few microseconds of the launch.
-int arthip_biquad_batch_lanes (int lanes)
-{
-    int L = 1;
-    while (L < 64 && (lanes + L - 1) / L > BQ_BATCH_WORKGROUPS) L *= 2;
-    return L;
-}
+int arthip_biquad_batch_lanes (int lanes) { return batch_lanes (lanes, BQ_BATCH_WORKGROUPS); }
 
 int arthip_biquad_batch_launch (const ArtBqClass *cls, const void *d_table, void *stream)
 {
     hipStream_t st = (hipStream_t) stream;
-    const ArtBqLane *items = (const ArtBqLane *)((const char *) d_table + cls->offset);
-    const int L = cls->lanes;
-    if (cls->count <= 0) return 0;
-    if (L < 1 || L > 64 || cls->count % L || cls->S < 1 || cls->S > 4) return -1;
-    const int chunk_frames = min (((DEC_CHUNK / L) - 4) & ~3, BQ_BATCH_RUN);
+    const ArtBqLane *items = (const ArtBqLane *)((const char *) d_table + cls->slice.offset);
+    const int L = cls->slice.lanes;
+    if (cls->slice.count <= 0) return 0;
+    if (L < 1 || L > 64 || cls->slice.count % L || cls->S < 1 || cls->S > 4) return -1;
+    const int chunk_frames = batch_chunk_frames (L, BQ_BATCH_RUN);
     const size_t lds = (size_t) 3 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 3 DEC_CHUNK samples (48 KiB)
-    const dim3 grid ((unsigned int)(cls->count / L)), block (ST_THREADS);
+    const dim3 grid ((unsigned int)(cls->slice.count / L)), block (ST_THREADS);
     switch (cls->S) {
     case 1: hipLaunchKernelGGL (biquad_batch_pipe_kernel<1>, grid, block, lds, st, items, L, chunk_frames); break;
     case 2: hipLaunchKernelGGL (biquad_batch_pipe_kernel<2>, grid, block, lds, st, items, L, chunk_frames); break;
@@ -1661,7 +1619,7 @@ int arthip_ingest_batch (const ArtIngestItem *items, int n, long tasks, void *st
         t.cap = cap;
     }
     if (t.used && t.last != st && hipStreamWaitEvent (st, t.ev, 0) != hipSuccess) return -1;
-    if (arthip_decimate_batch_upload (items, bytes, t.d, st)) return -1;
+    if (arthip_table_upload (items, bytes, t.d, st)) return -1;
     hipLaunchKernelGGL (ingest_batch_kernel, dim3 ((unsigned int)((tasks + 255) / 256)), dim3 (256), 0, st, (const ArtIngestItem *) t.d, n, tasks);
     if (hipGetLastError () != hipSuccess) return -1;
     // (the table may be rewritten only after this launch: if the event cannot be recorded, wait for the stream instead)

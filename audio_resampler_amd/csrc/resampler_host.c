@@ -277,16 +277,6 @@ static void find_period (double ratio, int *p_out, int *q_out)
  * Contexts
  * ---------------------------------------------------------------------------------------- */
 
-static void *grow (void *dev, size_t *cap, size_t need)
-{
-    if (need <= *cap) return dev;
-    arthip_free (dev);
-    size_t want = need + need / 2 + 4096;
-    dev = arthip_malloc (want);
-    *cap = dev ? want : 0;
-    return dev;
-}
-
 static void *grow_pinned (void *host, size_t *cap, size_t need)
 {
     if (need <= *cap) return host;
@@ -353,6 +343,19 @@ int artamdSetDevices (const int *devices, int count)
  * stream is not worth two devices' launches: ARTAMD_MIN_SHARD_CHANNELS); ARTAMD_SHARDS forces the count.  The slice kernels
  * of a shard read and write the caller's buffers on `home` in place: a device with no peer route to `home` (IOMMU,
  * containers, mixed topology — a page fault, not an error code, if it were used) is replaced by `home` itself. */
+int artamd_batch_distinct (const void *const *items, int n, unsigned long *(*stamp_of) (const void *item), const char *what, const char *noun)
+{
+    static unsigned long calls;
+    const unsigned long stamp = __atomic_add_fetch (&calls, 1, __ATOMIC_RELAXED);
+    for (int i = 0; i < n; ++i) {
+        if (!items [i]) { fprintf (stderr, "artamd: %s batch: a NULL %s\n", what, noun); return -1; }
+        unsigned long *seen = stamp_of (items [i]);
+        if (*seen == stamp) { fprintf (stderr, "artamd: %s batch: a %s appears twice\n", what, noun); return -1; }
+        *seen = stamp;
+    }
+    return 0;
+}
+
 int artamd_shard_plan (int channels, int home, int *devices_out)
 {
     pthread_mutex_lock (&dev_lock);
@@ -377,11 +380,6 @@ int artamd_shard_plan (int channels, int home, int *devices_out)
             }
     return n;
 }
-
-/* make a context's device current for the duration of a call; restored afterwards */
-#define ENTER_DEVICE(hip) const int prev_device_ = arthip_current_device (); \
-                          if (prev_device_ != (hip)->device) arthip_set_device ((hip)->device)
-#define LEAVE_DEVICE(hip) do { if (prev_device_ != (hip)->device && prev_device_ >= 0) arthip_set_device (prev_device_); } while (0)
 
 /* ------------------------------------------------------------------------------------------
  * Filter banks are shared: a service opens thousands of contexts with a handful of presets, a bank is up to 4 MB of HBM
@@ -1088,7 +1086,7 @@ static const art_s *flush_tail (Resample *cxt, art_s **tail_out)
         if (tail) memcpy (tail + (size_t) c * half, work + half, sizeof (art_s) * (size_t) half);
     }
 
-    hip->d_patch = grow (hip->d_patch, &hip->patch_cap, sizeof (art_s) * (size_t) half * C);
+    hip->d_patch = arthip_grow (hip->d_patch, &hip->patch_cap, sizeof (art_s) * (size_t) half * C);
     if (hip->d_patch) {
         arthip_h2d (hip->d_patch, patch, sizeof (art_s) * (size_t) half * C, hip->stream);
         arthip_sync (hip->stream);
@@ -1215,7 +1213,7 @@ static void keep_rows (struct artamd_resampler *hip, ArtFirArgs *a)
 static void *grow_zeroed (void *dev, size_t *cap, size_t need, size_t head, void *stream)
 {
     if (need <= *cap) return dev;
-    dev = grow (dev, cap, need);
+    dev = arthip_grow (dev, cap, need);
     if (dev) arthip_zero (dev, head, stream);
     return dev;
 }
@@ -1231,7 +1229,7 @@ static int provision (struct artamd_resampler *hip, const ArtFirNeeds *n, ArtFir
      * (diagnostics only: they are computed inside the kernel) */
     hip->d_fix = grow_zeroed (hip->d_fix, &hip->fix_cap, 64, 2 * sizeof (unsigned int), hip->stream);
     if (hip->d_fix) { a->fix_count = hip->d_fix; a->fix_list = hip->d_fix + 2; a->fix_cap = 0; }
-    hip->d_scratch = grow (hip->d_scratch, &hip->scratch_cap, n->scratch_bytes);
+    hip->d_scratch = arthip_grow (hip->d_scratch, &hip->scratch_cap, n->scratch_bytes);
     a->scratch = hip->d_scratch; a->scratch_bytes = hip->d_scratch ? hip->scratch_cap : 0;
     /* digit planes for the fixed-point kernel (about the size of the call's input; without them the f32 kernels run) */
     hip->d_planes = grow_zeroed (hip->d_planes, &hip->planes_cap, n->planes_bytes, ART_I8_HEAD_BYTES, hip->stream);
@@ -1240,7 +1238,7 @@ static int provision (struct artamd_resampler *hip, const ArtFirNeeds *n, ArtFir
      * (none without their host block: resampleHipKeepRows (0), the 8-byte build) */
     const size_t rows_want = a->rows_cache ? n->rows_bytes : 0;
     if (rows_want > hip->rows_cap) {
-        hip->d_rows = grow (hip->d_rows, &hip->rows_cap, rows_want);
+        hip->d_rows = arthip_grow (hip->d_rows, &hip->rows_cap, rows_want);
         arthip_fir_rows_cache_reset (hip->rows_cache);
     }
     if (rows_want && hip->d_rows) { a->rows = hip->d_rows; a->rows_bytes = hip->rows_cap; }
@@ -1251,7 +1249,7 @@ static int provision (struct artamd_resampler *hip, const ArtFirNeeds *n, ArtFir
     a->split = n->split_bytes ? hip->d_split : NULL; a->split_bytes = hip->d_split ? hip->split_cap : 0;
     a->fixed_out = hip->last_fixed;
     /* a channel count the matrix kernels are not compiled for: room for its groups' padded copies */
-    hip->d_pad = grow (hip->d_pad, &hip->pad_cap, n->pad_bytes);
+    hip->d_pad = arthip_grow (hip->d_pad, &hip->pad_cap, n->pad_bytes);
     a->pad = n->pad_bytes ? hip->d_pad : NULL; a->pad_bytes = hip->d_pad ? hip->pad_cap : 0;
     return a->fix_list && a->scratch;
 }
@@ -1452,6 +1450,8 @@ static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, 
     return 1;
 }
 
+static unsigned long *stamp_of (const void *cxt) { return &((const Resample *) cxt)->hip->batch_stamp; }
+
 int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                                            artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
                                            ResampleResult *results)
@@ -1465,15 +1465,7 @@ int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const a
     int *owner = malloc (sizeof (int) * (size_t) n);
     int gathered = 0, rc = -1;
 
-    if (!args || !tabs || !trials || !owner) goto out;
-    {   /* a context may appear only once: stamp each with this call's number (one pass) */
-        static unsigned long calls;
-        const unsigned long stamp = __atomic_add_fetch (&calls, 1, __ATOMIC_RELAXED);
-        for (int i = 0; i < n; ++i) {
-            if (cxts [i]->hip->batch_stamp == stamp) { fprintf (stderr, "artamd: resample batch: a context appears twice\n"); goto out; }
-            cxts [i]->hip->batch_stamp = stamp;
-        }
-    }
+    if (!args || !tabs || !trials || !owner || artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample", "context")) goto out;
 
     for (int i = 0; i < n; ++i) {
         if (batch_plan (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i], lead->stream,
@@ -1484,7 +1476,7 @@ int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const a
     }
 
     if (gathered) {
-        lead->d_batch = grow (lead->d_batch, &lead->batch_cap, arthip_fir_batch_item_bytes () * (size_t) gathered);
+        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_batch_item_bytes () * (size_t) gathered);
         if (!lead->d_batch || arthip_fir_batch (args, tabs, gathered, lead->d_batch, lead->stream)) {
             fprintf (stderr, "artamd: resample batch launch failed: %s\n", arthip_last_error ());
             for (int k = 0; k < gathered; ++k) results [owner [k]].input_used = results [owner [k]].output_generated = 0;
@@ -1620,7 +1612,7 @@ static int sched_launch (Resample *cxt, SchedRun *run, ResampleResult *results)
         a.ev_start = hip->timing ? timing_event (hip) : NULL;
         a.ev_stop = hip->timing ? timing_event (hip) : NULL;
         if (ev_pre) arthip_event_record (ev_pre, hip->stream);
-        hip->d_sched = grow (hip->d_sched, &hip->sched_cap, arthip_fir_schedule_bytes (run->nblocks, run->nsegs));
+        hip->d_sched = arthip_grow (hip->d_sched, &hip->sched_cap, arthip_fir_schedule_bytes (run->nblocks, run->nsegs));
         const int k = hip->d_sched ? arthip_fir_schedule (&a, run->blocks, run->nblocks, run->segs, run->nsegs, hip->d_sched, hip->stream) : -1;
         if (k < 0) {
             if (hip->timing) hip->ev_count -= 3;          /* (none of the three is read) */
@@ -1743,14 +1735,14 @@ static ResampleResult shard_part (Resample *cxt, int k, const struct shard_job *
          * is a strided slice of the caller's stream-wide frames and goes through the shard's slice staging, as in the branch below */
         const int wpw = (int)(sizeof (art_s) / 4);
         if (j->out_pitch) {                                     /* interleaved in, planar out */
-            sp->d_in = grow (sp->d_in, &sp->in_cap, sizeof (art_s) * (size_t) j->peek.input_used * width);
+            sp->d_in = arthip_grow (sp->d_in, &sp->in_cap, sizeof (art_s) * (size_t) j->peek.input_used * width);
             if (j->peek.input_used && !sp->d_in) { *failed = 1; arthip_event_record (hip->ev_shard [k], sp->stream); return res; }
             if (j->peek.input_used && j->d_in)
                 arthip_slice_copy (sp->d_in, (size_t) width * wpw, j->d_in + first, (size_t) C * wpw, width * wpw, j->peek.input_used, sp->stream);
             res = enqueue_call_layouts (sh, j->d_in ? sp->d_in : NULL, 0, j->nIn, j->d_out + (size_t) first * j->out_pitch, j->out_pitch, j->cap, j->ratio);
         }
         else {                                                  /* planar in, interleaved out */
-            sp->d_out = grow (sp->d_out, &sp->out_cap, sizeof (art_s) * ((size_t) j->peek.output_generated + 16) * width);
+            sp->d_out = arthip_grow (sp->d_out, &sp->out_cap, sizeof (art_s) * ((size_t) j->peek.output_generated + 16) * width);
             if (j->peek.output_generated && !sp->d_out) { *failed = 1; arthip_event_record (hip->ev_shard [k], sp->stream); return res; }
             res = enqueue_call_layouts (sh, j->d_in ? j->d_in + (size_t) first * j->in_pitch : NULL, j->in_pitch, j->nIn, sp->d_out, 0, j->cap, j->ratio);
             if (res.output_generated)
@@ -1758,8 +1750,8 @@ static ResampleResult shard_part (Resample *cxt, int k, const struct shard_job *
         }
     }
     else {
-        sp->d_in = grow (sp->d_in, &sp->in_cap, sizeof (art_s) * (size_t) j->peek.input_used * width);
-        sp->d_out = grow (sp->d_out, &sp->out_cap, sizeof (art_s) * (size_t) j->peek.output_generated * width);
+        sp->d_in = arthip_grow (sp->d_in, &sp->in_cap, sizeof (art_s) * (size_t) j->peek.input_used * width);
+        sp->d_out = arthip_grow (sp->d_out, &sp->out_cap, sizeof (art_s) * (size_t) j->peek.output_generated * width);
         if ((j->peek.input_used && !sp->d_in) || (j->peek.output_generated && !sp->d_out)) { *failed = 1; arthip_event_record (hip->ev_shard [k], sp->stream); return res; }
         const int wpw = (int)(sizeof (art_s) / 4);              /* 4-byte words per sample */
         if (j->peek.input_used && j->d_in)
@@ -1906,14 +1898,14 @@ static ResampleResult enqueue_call_layouts (Resample *cxt, const art_s *d_in, lo
         const art_s *in_i = d_in; art_s *out_i = d_out;
         int ok = 1;
         if (in_pitch) {
-            hip->d_in = grow (hip->d_in, &hip->in_cap, sizeof (art_s) * (size_t) nIn * C);
+            hip->d_in = arthip_grow (hip->d_in, &hip->in_cap, sizeof (art_s) * (size_t) nIn * C);
             ok = hip->d_in && !arthip_interleave (hip->d_in, d_in, in_pitch, nIn, C, hip->stream);
             in_i = hip->d_in;
         }
         if (ok && out_pitch) {
             /* (room for the frames the call will make, not for the caller's whole capacity) */
             const ResampleResult pk = peek_call (cxt, nIn, cap, ratio);
-            hip->d_out = grow (hip->d_out, &hip->out_cap, sizeof (art_s) * ((size_t) pk.output_generated + 16) * C);
+            hip->d_out = arthip_grow (hip->d_out, &hip->out_cap, sizeof (art_s) * ((size_t) pk.output_generated + 16) * C);
             ok = hip->d_out != NULL;
             out_i = hip->d_out;
         }
@@ -2001,15 +1993,15 @@ static void host_begin (Resample *cxt, const art_s *input, int in_stride, const 
     double trace_t_ = trace_on > 0 ? trace_now () : 0.0;
     trace_calls += trace_on > 0;
 
-    hip->d_in = grow (hip->d_in, &hip->in_cap, sizeof (art_s) * in_samples);
-    hip->d_out = grow (hip->d_out, &hip->out_cap, sizeof (art_s) * out_samples);
+    hip->d_in = arthip_grow (hip->d_in, &hip->in_cap, sizeof (art_s) * in_samples);
+    hip->d_out = arthip_grow (hip->d_out, &hip->out_cap, sizeof (art_s) * out_samples);
     if (staged) {
         hip->h_in = grow_pinned (hip->h_in, &hip->h_in_cap, sizeof (art_s) * in_samples);
         hip->h_out = grow_pinned (hip->h_out, &hip->h_out_cap, sizeof (art_s) * out_samples);
     }
     else if (planes || out_planes) {
         const size_t big = in_samples > out_samples ? in_samples : out_samples;
-        hip->d_tmp = grow (hip->d_tmp, &hip->tmp_cap, sizeof (art_s) * big);
+        hip->d_tmp = arthip_grow (hip->d_tmp, &hip->tmp_cap, sizeof (art_s) * big);
     }
     if ((in_samples && !hip->d_in) || (out_samples && !hip->d_out) || (staged && ((in_samples && !hip->h_in) || (out_samples && !hip->h_out))) ||
         (!staged && (planes || out_planes) && !hip->d_tmp)) {

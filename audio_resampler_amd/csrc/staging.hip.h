@@ -1,4 +1,4 @@
-// staging.hip.h — pinned staging of the argument tables of the multi-item launches (FIR batch and schedule, decimator batch).
+// staging.hip.h — pinned staging of the argument tables of the multi-item launches (FIR batch and schedule; arthip_table_upload for the rest).
 // C++ linkage, library-private; defined in device_rt.hip.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -21,15 +21,6 @@ struct artamd_stretch {
     unsigned long batch_stamp;                         /* last batched call this context took part in (duplicate check) */
 };
 
-static void *regrow (void *dev, size_t *cap, size_t need)
-{
-    if (need <= *cap) return dev;
-    arthip_free (dev);
-    dev = arthip_malloc (need + need / 2 + 4096);
-    *cap = dev ? need + need / 2 + 4096 : 0;
-    return dev;
-}
-
 static int push_state (Stretch *cxt)                   /* host mirrors -> device state (init / reset) */
 {
     DevState st [2];
@@ -193,6 +184,8 @@ int stretchFlushDevice (Stretch *cxt, artsample_t *d_output)
 /* n independent streams, one launch: item i is exactly the call stretchProcessDevice (cxts [i], ...) / stretchFlushDevice
  * would make — same device code, one workgroup per stream — so results are identical to n separate calls.  The launch
  * goes to the stream of cxts [0], whose scratch also carries the item table. */
+static unsigned long *stamp_of (const void *cxt) { return &((const Stretch *) cxt)->hip->batch_stamp; }
+
 static int batch_call (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const int *num_samples,
                        artsample_t *const *d_outputs, const double *ratios, int flush, int *produced)
 {
@@ -203,14 +196,10 @@ static int batch_call (Stretch *const *cxts, int n, const artsample_t *const *d_
     ArtStretchDone *done = malloc (done_bytes);
     int rc = -1;
 
-    lead->d_batch = regrow (lead->d_batch, &lead->batch_cap, items_bytes + done_bytes);
-    if (!items || !done || !lead->d_batch) goto out;
+    lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, items_bytes + done_bytes);
+    if (!items || !done || !lead->d_batch || artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "stretch", "context")) goto out;
 
-    static unsigned long calls;
-    const unsigned long stamp = __atomic_add_fetch (&calls, 1, __ATOMIC_RELAXED);
     for (int i = 0; i < n; ++i) {
-        if (cxts [i]->hip->batch_stamp == stamp) { fprintf (stderr, "artamd: stretch batch: a context appears twice\n"); goto out; }
-        cxts [i]->hip->batch_stamp = stamp;
         items [i].args = cxts [i]->hip->args;
         items [i].in = flush ? NULL : d_samples [i];
         items [i].out = d_outputs [i];
@@ -266,8 +255,8 @@ int stretchProcess (Stretch *cxt, const artsample_t *samples, int num_samples, a
     const int C = cxt->num_chans;
 
     if (num_samples <= 0) return 0;
-    hip->d_in = regrow (hip->d_in, &hip->in_cap, sizeof (art_s) * (size_t) num_samples * C);
-    hip->d_out = regrow (hip->d_out, &hip->out_cap, sizeof (art_s) * worst_case_frames (cxt, num_samples) * C);
+    hip->d_in = arthip_grow (hip->d_in, &hip->in_cap, sizeof (art_s) * (size_t) num_samples * C);
+    hip->d_out = arthip_grow (hip->d_out, &hip->out_cap, sizeof (art_s) * worst_case_frames (cxt, num_samples) * C);
     if (!hip->d_in || !hip->d_out || arthip_h2d (hip->d_in, samples, sizeof (art_s) * (size_t) num_samples * C, hip->stream)) {
         fprintf (stderr, "artamd: stretchProcess: %s\n", arthip_last_error ());
         return 0;
@@ -283,7 +272,7 @@ int stretchFlush (Stretch *cxt, artsample_t *output)
     struct artamd_stretch *hip = cxt->hip;
     const int C = cxt->num_chans;
 
-    hip->d_out = regrow (hip->d_out, &hip->out_cap, sizeof (art_s) * worst_case_frames (cxt, 0) * C);
+    hip->d_out = arthip_grow (hip->d_out, &hip->out_cap, sizeof (art_s) * worst_case_frames (cxt, 0) * C);
     if (!hip->d_out) return 0;
     const int made = device_call (cxt, NULL, 0, hip->d_out, 1.0, 1);
     if (made > 0) { arthip_d2h (output, hip->d_out, sizeof (art_s) * (size_t) made * C, hip->stream); arthip_sync (hip->stream); }

@@ -122,6 +122,7 @@ def _bind(width):
         "resampleHipSetCutInvariant": (None, [RP, C.c_int]),
         "resampleHipCutInvariantFallbacks": (C.c_uint, [RP]),
         "resampleHipLastKernel": (C.c_int, [RP]),
+        "resampleHipLastGathered": (C.c_int, [RP]),
         "resampleHipLastHandedBack": (C.c_uint, [RP]),
         "resampleHipLastFixedPoint": (C.c_int, [RP, C.POINTER(C.c_double)]),
         "resampleHipLastFixedPointKernel": (C.c_int, [RP]),
@@ -155,6 +156,7 @@ def _bind(width):
         "artamdLastError": (C.c_char_p, []),
         "floatIntegersLEDevice": (None, [ptr, C.c_double, C.c_int, C.c_int, C.c_int, ptr, C.c_int, ptr]),
         "floatIntegersBatchLEDevice": (C.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
+        "artamdExtrapolateBatchDevice": (C.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         # stretch.h
         "stretchInit": (ptr, [C.c_int, C.c_int, C.c_int, C.c_int]),
         "stretchGetOutputCapacity": (C.c_int, [ptr, C.c_int, C.c_double]),
@@ -279,6 +281,9 @@ def _bind(width):
 
         def last_kernel(self):
             return self.L.resampleHipLastKernel(self.p)
+
+        def last_gathered(self):
+            return self.L.resampleHipLastGathered(self.p)
 
         def synchronize(self):
             self.L.resampleHipSynchronize(self.p)
@@ -489,6 +494,20 @@ def _bind(width):
             (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), (C.c_int * n)(*[int(v) for v in counts]), n, st)
         if rc < 0:
             raise RuntimeError("floatIntegersBatchLEDevice failed")
+        return rc
+
+    def extrapolate_batch_device(d_known, counts, strides, backward, d_outs, extras, stream=None):
+        """artamdExtrapolateBatchDevice: run i fits counts[i] known samples at d_known[i] (stride strides[i], oldest first) and writes
+        extras[i] samples to d_outs[i] (same stride): past the newest, or before the oldest (nearest first) where backward[i], all in
+        one launch on `stream` (a torch stream, a raw address or None: the null stream).  Raises if the call returned -1."""
+        n = len(d_known)
+        st = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        rc = lib().artamdExtrapolateBatchDevice(
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_known]), (C.c_int * n)(*[int(v) for v in counts]),
+            (C.c_int * n)(*[int(v) for v in strides]), (C.c_int * n)(*[int(bool(v)) for v in backward]),
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), (C.c_int * n)(*[int(v) for v in extras]), n, st)
+        if rc < 0:
+            raise RuntimeError("artamdExtrapolateBatchDevice failed")
         return rc
 
     return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k != "width"}, width=width)

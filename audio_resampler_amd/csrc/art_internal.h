@@ -209,9 +209,21 @@ int arthip_roll_history (art_s *new_hist, const art_s *hist, const art_s *in, lo
 int arthip_interleave (art_s *dst, const art_s *src_planar, long pitch, int frames, int C, void *stream);
 int arthip_deinterleave (art_s *dst_planar, long pitch, const art_s *src, int frames, int C, void *stream);
 
-/* ---- extrapolate_host.c (host, scalar) ---- */
-void art_extrapolate_forward (art_s *x, int count, int extra);
-void art_extrapolate_backward (const art_s *known_newest_last, int count, art_s *older_nearest_first, int extra);
+/* ---- extrapolate_kernels.hip: LPC end-point extrapolation, one workgroup per run ----
+ * A run's known samples, oldest first, are n[0] samples at src[0] + j * stride[0] followed by n[1] at src[1] + j * stride[1]
+ * (n[0] + n[1] in 8 .. ARTAMD_EXTRAPOLATE_MAX_KNOWN).  backward == 0: the `extras` samples that continue past the newest
+ * (reference extrapolate_forward); != 0: the `extras` samples that precede the oldest, nearest first (extrapolate_reverse).
+ * Sample i goes to out + i * out_stride (a negative stride walks back through an interleaved history). */
+typedef struct {
+    const art_s *src [2];
+    long stride [2];
+    int n [2];
+    art_s *out;
+    long out_stride;
+    int extras, backward;
+} ArtExtrapRun;
+/* uploads the n runs (table of the calling thread, device memory kept across calls) and launches them on `stream`; 0, or -1 */
+int arthip_extrapolate (const ArtExtrapRun *runs, int n, void *stream);
 
 /* ---- pcm_kernels.hip ---- */
 typedef struct {

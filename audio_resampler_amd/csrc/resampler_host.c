@@ -78,6 +78,7 @@ struct artamd_resampler {
     void *d_batch; size_t batch_cap;         /* argument table of the batched calls led by this context */
     void *d_sched; size_t sched_cap;         /* block and segment tables of the scheduled runs (resampleProcessScheduleInterleavedDevice) */
     unsigned long batch_stamp;               /* last batched call this context took part in (duplicate check) */
+    int last_gathered;                       /* the last call or block ran in a launch shared by the batch or schedule entry (resampleHipLastGathered) */
 };
 
 static struct shard_pool *shard_pool_create (Resample *cxt, int n);
@@ -861,6 +862,7 @@ void resampleHipKeepRows (Resample *cxt, int on)
 
 int resampleHipGetDevice (Resample *cxt) { return cxt->hip->device; }
 int resampleHipNumShards (Resample *cxt) { return cxt->hip->nshards; }
+int resampleHipLastGathered (Resample *cxt) { return cxt->hip->last_gathered; }
 
 int resampleHipShardInfo (Resample *cxt, int shard, int *device, int *firstChannel, int *numChannels)
 {
@@ -997,143 +999,107 @@ unsigned int resampleHipLastHandedBack (Resample *cxt)
 
 /* ------------------------------------------------------------------------------------------
  * End-point extrapolation (EXTRAPOLATE_ENDPOINTS; reference resampler.c:677-680, :691-698, :812-819).
- * The LPC fit is scalar host work on a few hundred samples, at most twice per stream; the samples it
- * produces are written into HBM and consumed by the kernels like ordinary history / input.
+ * The LPC fits run on the device (extrapolate_kernels.hip), one run per channel, in stream order in front of the call's FIR
+ * launches: they read the history ring and the call's input where they lie and write their samples into the ring or d_patch.
  * ---------------------------------------------------------------------------------------- */
 
-/* fetch `count` frames starting at linear index `lin` of (history ++ input) into planes[c][0..count) */
-static void gather_linear (Resample *cxt, const art_s *d_in, long in_pitch, int lin, int count, art_s *planes)
+/* channel c's `count` frames from linear index `lin` of (history ++ input), as the known samples of a run: the history's frames,
+ * then the input's (interleaved, or planar with in_pitch) */
+static void linear_run (const Resample *cxt, const art_s *d_in, long in_pitch, int lin, int count, int c, ArtExtrapRun *r)
 {
-    struct artamd_resampler *hip = cxt->hip;
+    const struct artamd_resampler *hip = cxt->hip;
     const int C = cxt->numChannels, H = HIST_FRAMES (cxt->numTaps);
-    art_s *tmp = malloc (sizeof (art_s) * (size_t) count * C);
-    const int from_hist = lin < H ? (H - lin < count ? H - lin : count) : 0;
+    const int from_hist = lin < H ? (H - lin < count ? H - lin : count) : 0, first = lin + from_hist - H;
 
-    if (from_hist)
-        arthip_d2h (tmp, hip->d_hist [hip->cur] + (size_t) lin * C, sizeof (art_s) * (size_t) from_hist * C, hip->stream);
-    if (count > from_hist) {
-        const int first = lin + from_hist - H, n = count - from_hist;
-        if (in_pitch)
-            for (int c = 0; c < C; ++c)      /* planar: land directly in the plane */
-                arthip_d2h (planes + (size_t) c * count + from_hist, d_in + (size_t) c * in_pitch + first, sizeof (art_s) * (size_t) n, hip->stream);
-        else
-            arthip_d2h (tmp + (size_t) from_hist * C, d_in + (size_t) first * C, sizeof (art_s) * (size_t) n * C, hip->stream);
-    }
-    arthip_sync (hip->stream);
-
-    const int inter = in_pitch ? from_hist : count;     /* frames that arrived interleaved in tmp */
-    for (int f = 0; f < inter; ++f)
-        for (int c = 0; c < C; ++c)
-            planes [(size_t) c * count + f] = tmp [(size_t) f * C + c];
-    free (tmp);
+    r->src [0] = from_hist ? hip->d_hist [hip->cur] + (size_t) lin * C + c : NULL;
+    r->stride [0] = C; r->n [0] = from_hist;
+    r->src [1] = count > from_hist ? (in_pitch ? d_in + (size_t) c * in_pitch + first : d_in + (size_t) first * C + c) : NULL;
+    r->stride [1] = in_pitch ? 1 : C; r->n [1] = count - from_hist;
 }
 
-/* Backward extrapolation into the silent pre-history, just before the first output of a stream. */
-static void prefill_history (Resample *cxt, const art_s *d_in, long in_pitch)
+/* Backward extrapolation into the silent pre-history, just before the first output of a stream: the runs of one context
+ * (C of them, or 0 when there is nothing to extrapolate from) appended at `runs` */
+static int prefill_history_runs (const Resample *cxt, const art_s *d_in, long in_pitch, ArtExtrapRun *runs)
 {
-    struct artamd_resampler *hip = cxt->hip;
+    const struct artamd_resampler *hip = cxt->hip;
     const int T = cxt->numTaps, C = cxt->numChannels, H = HIST_FRAMES (T), half = T / 2;
     long first_emit = (long) floor (cxt->outputOffset) + half + 1;     /* inputIndex when output 0 becomes possible */
     if (first_emit < cxt->inputIndex) first_emit = cxt->inputIndex;
     const int known = (int)(first_emit - T), extra = T - known;
 
-    if (known < 8 || extra <= 0) return;                                /* reference resampler.c:695 / :815 */
+    if (known < 8 || extra <= 0) return 0;                              /* reference resampler.c:695 / :815 */
 
     const int lin_known = T + H - cxt->inputIndex;                      /* ring index T in linear terms */
-    art_s *planes = malloc (sizeof (art_s) * (size_t) known * C);
-    art_s *older = malloc (sizeof (art_s) * (size_t) extra);
-    art_s *patch = malloc (sizeof (art_s) * (size_t) extra * C);
-
-    gather_linear (cxt, d_in, in_pitch, lin_known, known, planes);
-
     for (int c = 0; c < C; ++c) {
-        art_extrapolate_backward (planes + (size_t) c * known, known, older, extra);
-        for (int e = 0; e < extra; ++e)                                 /* older[e] is ring index T-1-e */
-            patch [(size_t)(extra - 1 - e) * C + c] = older [e];
+        linear_run (cxt, d_in, in_pitch, lin_known, known, c, &runs [c]);
+        /* older sample e is ring index T-1-e = linear lin_known-1-e: inside the history buffer by construction */
+        runs [c].out = hip->d_hist [hip->cur] + (size_t)(lin_known - 1) * C + c;
+        runs [c].out_stride = -C;
+        runs [c].extras = extra; runs [c].backward = 1;
     }
-
-    /* ring [known, T) = linear [lin_known - extra, lin_known): inside the history buffer by construction */
-    arthip_h2d (hip->d_hist [hip->cur] + (size_t)(lin_known - extra) * C, patch, sizeof (art_s) * (size_t) extra * C, hip->stream);
-    arthip_sync (hip->stream);
-    free (planes); free (older); free (patch);
+    return C;
 }
 
-/* Forward extrapolation of half a window at flush time; returns a device buffer of T/2 frames x C.  *tail_out (optional)
- * receives the same samples on the host, planar [c][T/2] (caller frees). */
-static const art_s *flush_tail (Resample *cxt, art_s **tail_out)
+static int prefill_history (Resample *cxt, const art_s *d_in, long in_pitch)
+{
+    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) cxt->numChannels);
+    if (!runs) return -1;
+    const int n = prefill_history_runs (cxt, d_in, in_pitch, runs);
+    const int rc = n ? arthip_extrapolate (runs, n, cxt->hip->stream) : 0;
+    free (runs);
+    return rc;
+}
+
+/* Forward extrapolation of half a window at flush time into d_patch (T/2 frames x C); NULL on failure */
+static const art_s *flush_tail (Resample *cxt)
 {
     struct artamd_resampler *hip = cxt->hip;
     const int T = cxt->numTaps, C = cxt->numChannels, H = HIST_FRAMES (T), half = T / 2;
-    art_s *planes = malloc (sizeof (art_s) * (size_t) half * C);
-    art_s *work = malloc (sizeof (art_s) * (size_t) T);
-    art_s *patch = malloc (sizeof (art_s) * (size_t) half * C);
-    art_s *tail = tail_out ? malloc (sizeof (art_s) * (size_t) half * C) : NULL;
-
-    if (tail_out) *tail_out = NULL;
-    if (!planes || !work || !patch || (tail_out && !tail)) {
-        fprintf (stderr, "artamd: out of memory (end-point extrapolation)\n");
-        free (planes); free (work); free (patch); free (tail);
-        return NULL;
-    }
-
-    gather_linear (cxt, NULL, 0, H - half, half, planes);
-
-    for (int c = 0; c < C; ++c) {
-        memcpy (work, planes + (size_t) c * half, sizeof (art_s) * (size_t) half);
-        art_extrapolate_forward (work, half, half);
-        for (int f = 0; f < half; ++f)
-            patch [(size_t) f * C + c] = work [half + f];
-        if (tail) memcpy (tail + (size_t) c * half, work + half, sizeof (art_s) * (size_t) half);
-    }
+    /* (the reference fits the last T/2 samples and predicts from the last 4: with T = 4 that is 4 samples and no fit, the same) */
+    const int known = half < 4 ? 4 : half;
 
     hip->d_patch = arthip_grow (hip->d_patch, &hip->patch_cap, sizeof (art_s) * (size_t) half * C);
-    if (hip->d_patch) {
-        arthip_h2d (hip->d_patch, patch, sizeof (art_s) * (size_t) half * C, hip->stream);
-        arthip_sync (hip->stream);
+    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) C);
+    if (!hip->d_patch || !runs) { free (runs); return NULL; }
+    for (int c = 0; c < C; ++c) {
+        linear_run (cxt, NULL, 0, H - known, known, c, &runs [c]);
+        runs [c].out = hip->d_patch + c; runs [c].out_stride = C;
+        runs [c].extras = half; runs [c].backward = 0;
     }
-    free (planes); free (work); free (patch);
-    if (tail_out) *tail_out = tail;
-    return hip->d_patch;
+    const int rc = arthip_extrapolate (runs, C, hip->stream);
+    free (runs);
+    return rc ? NULL : hip->d_patch;
 }
 
 /* The stream's FIRST output is produced by the flush call itself (fewer than T/2 frames ever arrived): the reference's
  * prefill then runs after the postfill (resampler.c:775-791 then :812-819) over the real samples ++ the flush tail.
- * inputIndex is the value BEFORE the flush; `tail` = flush_tail's host copy, planar [c][T/2]. */
-static void prefill_at_flush (Resample *cxt, const art_s *tail)
+ * inputIndex is the value BEFORE the flush; the tail is in d_patch (flush_tail, earlier on the stream). */
+static int prefill_at_flush (Resample *cxt)
 {
     struct artamd_resampler *hip = cxt->hip;
     const int T = cxt->numTaps, C = cxt->numChannels, H = HIST_FRAMES (T), half = T / 2;
     const int real = cxt->inputIndex - T, known = real + half, extra = T - known;
 
-    if (real < 0 || known < 8 || extra <= 0) return;                     /* reference resampler.c:695 / :815 */
+    if (real < 0 || known < 8 || extra <= 0) return 0;                   /* reference resampler.c:695 / :815 */
 
-    art_s *samples = malloc (sizeof (art_s) * (size_t) known * C);       /* planar [c][known], oldest first */
-    art_s *recent = malloc (sizeof (art_s) * (size_t)(real ? real : 1) * C);
-    art_s *older = malloc (sizeof (art_s) * (size_t) extra);
-    art_s *patch = malloc (sizeof (art_s) * (size_t) extra * C);
-    if (!samples || !recent || !older || !patch) {
-        fprintf (stderr, "artamd: out of memory (end-point extrapolation)\n");
-        free (samples); free (recent); free (older); free (patch);
-        return;
-    }
-
-    if (real) gather_linear (cxt, NULL, 0, H - real, real, recent);      /* ring [T, inputIndex) = the newest `real` history frames */
-
+    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) C);
+    if (!runs) return -1;
     for (int c = 0; c < C; ++c) {
-        memcpy (samples + (size_t) c * known, recent + (size_t) c * real, sizeof (art_s) * (size_t) real);
-        memcpy (samples + (size_t) c * known + real, tail + (size_t) c * half, sizeof (art_s) * (size_t) half);
-        art_extrapolate_backward (samples + (size_t) c * known, known, older, extra);
-        for (int e = 0; e < extra; ++e)                                  /* older[e] is ring index T-1-e */
-            patch [(size_t)(extra - 1 - e) * C + c] = older [e];
+        /* ring [T, inputIndex) = the newest `real` history frames, then the tail */
+        linear_run (cxt, NULL, 0, H - real, real, c, &runs [c]);
+        runs [c].src [1] = hip->d_patch + c; runs [c].stride [1] = C; runs [c].n [1] = half;
+        /* older sample e is ring index T-1-e = linear H - inputIndex + T-1-e = H - real - 1 - e: inside the history */
+        runs [c].out = hip->d_hist [hip->cur] + (size_t)(H - real - 1) * C + c;
+        runs [c].out_stride = -C;
+        runs [c].extras = extra; runs [c].backward = 1;
     }
-
-    /* ring [known, T) = linear [H - inputIndex + known, H - inputIndex + T) = [T, H - real): inside the history */
-    arthip_h2d (hip->d_hist [hip->cur] + (size_t)(H - cxt->inputIndex + known) * C, patch, sizeof (art_s) * (size_t) extra * C, hip->stream);
-    arthip_sync (hip->stream);
-    free (samples); free (recent); free (older); free (patch);
+    const int rc = arthip_extrapolate (runs, C, hip->stream);
+    free (runs);
+    return rc;
 }
 
 static ResampleResult enqueue_call_layouts (Resample *cxt, const art_s *d_in, long in_pitch, int nIn, art_s *d_out, long out_pitch, int cap, double ratio);
+static int rewind_lead (Resample *cxt, int nIn, int cap, double ratio);
 static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pitch, int nIn,
                                     art_s *d_out, long out_pitch, int cap, double ratio);
 
@@ -1254,6 +1220,22 @@ static int provision (struct artamd_resampler *hip, const ArtFirNeeds *n, ArtFir
     return a->fix_list && a->scratch;
 }
 
+/* EXTRAPOLATE_ENDPOINTS, first output of the stream only after the ring has rewound (the position was advanced by more than 15 T):
+ * the reference extrapolates backwards from the samples that arrived SINCE the rewind, over the history (resampler.c:812-819 with
+ * the ring's inputIndex).  The single call then consumes the frames before the one that makes output 0 possible silently first
+ * (consume_silently); the rest of the call starts inside the right ring epoch and prefills as usual.  Returns how many frames
+ * that is, or 0 where an ordinary (non-flush) call of nIn frames takes no such route. */
+static int rewind_lead (Resample *cxt, int nIn, int cap, double ratio)
+{
+    ResampleResult one;
+    int lin_floor;
+    if (!(cxt->flags & EXTRAPOLATE_PREFILL) || nIn <= 1 || cap <= 0 || (cxt->flags & RESAMPLER_FLUSHED)) return 0;
+    ArtamdPosition trial = position_of (cxt);
+    if (plan_call (&trial, nIn, 1, ratio, &one, NULL, 0, &lin_floor, 1) >= 2 && one.output_generated == 1 && one.input_used >= 2)
+        return (int) one.input_used - 1;
+    return 0;
+}
+
 /* The first `frames` input frames of a call go into the history without any output being due (the caller established
  * that): position and ring epoch advance exactly as the reference's loop would have advanced them. */
 static int consume_silently (Resample *cxt, const art_s *d_in, long in_pitch, int frames, double ratio)
@@ -1286,24 +1268,18 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
     int lin_floor;
 
     const int is_flush = nIn < 0 && !(cxt->flags & RESAMPLER_FLUSHED);
+    int lead;
 
-    /* EXTRAPOLATE_ENDPOINTS, first output of the stream only after the ring has rewound (the position was advanced by more
-     * than 15 T): the reference extrapolates backwards from the samples that arrived SINCE the rewind, over the history
-     * (resampler.c:812-819 with the ring's inputIndex).  Everything before the frame that makes output 0 possible is
-     * consumed silently first; the rest of the call then starts inside the right ring epoch and prefills as usual. */
-    if ((cxt->flags & EXTRAPOLATE_PREFILL) && !is_flush && nIn > 1 && cap > 0 && !(cxt->flags & RESAMPLER_FLUSHED)) {
-        ResampleResult one;
-        trial = position_of (cxt);
-        if (plan_call (&trial, nIn, 1, ratio, &one, NULL, 0, &lin_floor, 1) >= 2 && one.output_generated == 1 && one.input_used >= 2) {
-            const int lead = (int) one.input_used - 1;
-            if (consume_silently (cxt, d_in, in_pitch, lead, ratio)) {
-                fprintf (stderr, "artamd: end-point extrapolation: could not advance to the first output: %s\n", arthip_last_error ());
-                return res;
-            }
-            res = enqueue_call (cxt, in_pitch ? d_in + lead : d_in + (size_t) lead * C, in_pitch, nIn - lead, d_out, out_pitch, cap, ratio);
-            res.input_used += (unsigned int) lead;
+    hip->last_gathered = 0;
+    /* EXTRAPOLATE_ENDPOINTS, first output of the stream only after the ring has rewound: consumed silently up to it (rewind_lead) */
+    if (!is_flush && (lead = rewind_lead (cxt, nIn, cap, ratio)) > 0) {
+        if (consume_silently (cxt, d_in, in_pitch, lead, ratio)) {
+            fprintf (stderr, "artamd: end-point extrapolation: could not advance to the first output: %s\n", arthip_last_error ());
             return res;
         }
+        res = enqueue_call (cxt, in_pitch ? d_in + lead : d_in + (size_t) lead * C, in_pitch, nIn - lead, d_out, out_pitch, cap, ratio);
+        res.input_used += (unsigned int) lead;
+        return res;
     }
 
     const int nseg = plan_segments (cxt, nIn, cap, ratio, &trial, &res, &lin_floor);
@@ -1318,15 +1294,20 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
          * ordinary call (a rewind right in front of output 0 leaves one known sample: nothing to extrapolate from), a
          * flush continued after it was cut short, or — below — the flush call itself */
         const int first_now = (cxt->flags & EXTRAPOLATE_PREFILL) && res.output_generated;
+        int failed = 0;
         if (first_now && !is_flush && (nseg == 1 || hip->segs [1].first_output > 0))
-            prefill_history (cxt, nIn > 0 ? d_in : NULL, in_pitch);
+            failed = prefill_history (cxt, nIn > 0 ? d_in : NULL, in_pitch) != 0;
         if (is_flush) {
-            art_s *tail = NULL;
-            flush_in = flush_tail (cxt, first_now ? &tail : NULL);
+            flush_in = flush_tail (cxt);
+            failed = !flush_in;
             /* (a flush that had to rewind the ring first leaves more than T known samples: nothing to prefill) */
-            if (first_now && tail && trial.inputIndex == cxt->inputIndex + T / 2)
-                prefill_at_flush (cxt, tail);
-            free (tail);
+            if (!failed && first_now && trial.inputIndex == cxt->inputIndex + T / 2)
+                failed = prefill_at_flush (cxt) != 0;
+        }
+        if (failed) {
+            /* nothing of the stream has moved (as after a failed FIR launch): { 0, 0 } and the count in artamdErrorCount */
+            artamd_note_failure ("resampler: end-point extrapolation launch failed");
+            res.input_used = res.output_generated = 0; return res;
         }
     }
 
@@ -1405,14 +1386,16 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
  * plans every context's call on the host exactly as the single call does, gathers those the general kernel would run
  * (any ratio per stream, default or EXTEND mode, ordinary call, on the stream of cxts [0]) into one launch per kernel
  * variant — each stream cut into the tiles its own launch would use, so the samples are identical — and simply makes
- * the remaining calls (flushes, strict mode, endpoint extrapolation, calls big enough for the matrix-core path, contexts
- * under the cut-invariant policy, other streams) one by one.  results [i] is what resampleProcessInterleavedDevice
- * (cxts [i], ...) would have returned. */
+ * the remaining calls (flushes, strict mode, calls big enough for the matrix-core path, contexts under the cut-invariant
+ * policy, other streams, a first output after a rewind) one by one.  The first output of an extrapolating stream is gathered
+ * too: its backward fits, for all such streams, are one launch in front of the FIR launches.  results [i] is what
+ * resampleProcessInterleavedDevice (cxts [i], ...) would have returned. */
 /* A context whose ordinary calls may be gathered with others (batched streams, scheduled blocks): not sharded, and neither strict order,
- * endpoint extrapolation nor a flushed stream (those calls are made as they stand) */
+ * a flushed stream nor an extrapolating stream before its first output (those calls are made as they stand; after its first output an
+ * extrapolating stream's ordinary calls are a plain stream's) */
 static int gatherable_context (const Resample *cxt)
 {
-    return !cxt->hip->nshards && !(cxt->flags & (EXTRAPOLATE_ENDPOINTS | RESAMPLE_STRICT_ORDER | RESAMPLER_FLUSHED));
+    return !cxt->hip->nshards && !(cxt->flags & (EXTRAPOLATE_PREFILL | RESAMPLE_STRICT_ORDER | RESAMPLER_FLUSHED));
 }
 
 /* Does the single call give this planned call (its FIR arguments, first table, outputs) to the general kernel?  The cut-invariant policy keeps
@@ -1428,13 +1411,17 @@ static int general_call (const Resample *cxt, const ArtFirArgs *a, const ArtSegT
     return !needs.matrix;
 }
 
+/* (an extrapolating stream's first output, *nruns != NULL: its prefill runs, as the single call would make them, are appended at
+ * runs + *nruns) */
 static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, int cap, double ratio, void *lead_stream,
-                       ArtFirArgs *a, ArtSegTable *tab, ResampleResult *res, ArtamdPosition *trial)
+                       ArtFirArgs *a, ArtSegTable *tab, ResampleResult *res, ArtamdPosition *trial, ArtExtrapRun *runs, int *nruns)
 {
     struct artamd_resampler *hip = cxt->hip;
     int lin_floor;
+    const int first = (cxt->flags & (EXTRAPOLATE_PREFILL | RESAMPLER_FLUSHED)) == EXTRAPOLATE_PREFILL;
 
-    if (nIn < 0 || hip->stream != lead_stream || hip->timing || hip->device != arthip_current_device () || !gatherable_context (cxt)) return 0;
+    if (nIn < 0 || hip->stream != lead_stream || hip->timing || hip->device != arthip_current_device ()) return 0;
+    if (first ? (hip->nshards || (cxt->flags & RESAMPLE_STRICT_ORDER) || !runs || rewind_lead (cxt, nIn, cap, ratio)) : !gatherable_context (cxt)) return 0;
 
     const int nseg = plan_segments (cxt, nIn, cap, ratio, trial, res, &lin_floor);      /* (out of memory: the one-by-one path reports it) */
     if (nseg < 0 || nseg > arthip_fir_batch_max_segments () || res->output_generated == 0) return 0;
@@ -1447,6 +1434,8 @@ static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, 
     const int appended = (int) res->input_used;
     a->roll_dst = appended > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;      /* the launch takes the history roll along */
     a->roll_appended = appended;
+    if (first && (nseg == 1 || hip->segs [1].first_output > 0))           /* (enqueue_call's condition for the prefill) */
+        *nruns += prefill_history_runs (cxt, nIn > 0 ? d_in : NULL, 0, runs + *nruns);
     return 1;
 }
 
@@ -1463,13 +1452,18 @@ int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const a
     ArtSegTable *tabs = malloc (sizeof (ArtSegTable) * (size_t) n);
     ArtamdPosition *trials = malloc (sizeof (ArtamdPosition) * (size_t) n);
     int *owner = malloc (sizeof (int) * (size_t) n);
-    int gathered = 0, rc = -1;
+    ArtExtrapRun *runs = NULL;
+    int gathered = 0, nruns = 0, rc = -1;
 
     if (!args || !tabs || !trials || !owner || artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample", "context")) goto out;
+    size_t channels = 0;                 /* (room for the prefill runs of every extrapolating stream's first output: one per channel) */
+    for (int i = 0; i < n; ++i)
+        if ((cxts [i]->flags & EXTRAPOLATE_PREFILL) && !cxts [i]->hip->nshards) channels += (size_t) cxts [i]->numChannels;
+    if (channels) runs = malloc (sizeof (ArtExtrapRun) * channels);     /* (none: those calls are made one by one) */
 
     for (int i = 0; i < n; ++i) {
         if (batch_plan (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i], lead->stream,
-                        &args [gathered], &tabs [gathered], &results [i], &trials [gathered]))
+                        &args [gathered], &tabs [gathered], &results [i], &trials [gathered], runs, &nruns))
             owner [gathered++] = i;
         else
             results [i] = resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]);
@@ -1477,13 +1471,16 @@ int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const a
 
     if (gathered) {
         lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_batch_item_bytes () * (size_t) gathered);
-        if (!lead->d_batch || arthip_fir_batch (args, tabs, gathered, lead->d_batch, lead->stream)) {
+        /* the prefill fits of the first outputs, one launch in front of the FIR launches that read what they write */
+        if (!lead->d_batch || (nruns && arthip_extrapolate (runs, nruns, lead->stream)) ||
+            arthip_fir_batch (args, tabs, gathered, lead->d_batch, lead->stream)) {
             fprintf (stderr, "artamd: resample batch launch failed: %s\n", arthip_last_error ());
             for (int k = 0; k < gathered; ++k) results [owner [k]].input_used = results [owner [k]].output_generated = 0;
             goto out;
         }
         for (int k = 0; k < gathered; ++k) {
             Resample *cxt = cxts [owner [k]];
+            cxt->hip->last_gathered = 1;
             if (args [k].roll_dst) { cxt->hip->cur ^= 1; cxt->hip->lin_origin += args [k].roll_appended; }
             cxt->outputOffset = trials [k].outputOffset; cxt->inputIndex = trials [k].inputIndex;
             cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (trials [k].flags & RESAMPLER_FLUSHED);
@@ -1493,7 +1490,7 @@ int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const a
     }
     rc = 0;
 out:
-    free (args); free (tabs); free (trials); free (owner);
+    free (args); free (tabs); free (trials); free (owner); free (runs);
     LEAVE_DEVICE (lead);
     return rc;
 }
@@ -1565,6 +1562,7 @@ static int sched_gather (Resample *cxt, SchedRun *run, const art_s *in, int nIn,
         run->nsegs += nseg;
     }
     if (!run->gathered++) { run->in = in; run->out = out; run->first = k; run->start = position_of (cxt); }
+    hip->last_gathered = 1;
     run->frames += (int) res->input_used; run->outputs += res->output_generated;
     cxt->outputOffset = trial.outputOffset; cxt->inputIndex = trial.inputIndex;
     cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (trial.flags & RESAMPLER_FLUSHED) |

@@ -90,6 +90,9 @@ unsigned int resampleHipCutInvariantFallbacks (Resample *cxt);
  * Either way a sample is within the parity bar; the two differ in the last place of a few per cent of the samples. */
 void resampleHipKeepRows (Resample *cxt, int on);
 int  resampleHipLastKernel (Resample *cxt);          /* which kernel produced the bulk of the last call */
+/* 1 when the context's last call or block ran inside a launch shared by resampleProcessBatchInterleavedDevice or
+ * resampleProcessScheduleInterleavedDevice, 0 when it ran as a single call (which streams of a service batch) */
+int  resampleHipLastGathered (Resample *cxt);
 /* the matrix-core path's fixed-point kernel (regular launches, 4-byte samples): 0 = the last call did not use it, 1 = it ran,
  * 2 = it was enqueued and stood down for the f32 kernel's tile loop (an infinity or a NaN among the frames the launch reads: any finite
  * amplitude is held, the block exponents follow the channel's peak).
@@ -117,7 +120,9 @@ ResampleResult resampleProcessAndFlushInterleavedDevice (Resample *cxt, const ar
  * resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i])
  * would have produced.  Contexts whose call the general kernel runs (any ratio per context, default or EXTEND mode, an
  * ordinary call, on the stream of cxts [0]) share launches — a service with hundreds of small-block streams is
- * launch-bound one call at a time; all other calls (strict mode, endpoint extrapolation, calls large enough for the
+ * launch-bound one call at a time.  EXTRAPOLATE_ENDPOINTS streams share them too: an ordinary call after the first output is a
+ * plain stream's, and the calls that make a first output put their backward LPC fits, all in one launch, in front of the FIR
+ * launches.  All other calls (strict mode, flushes, a first output after a rewind of the position, calls large enough for the
  * matrix-core path, contexts under the cut-invariant policy, contexts on other streams) are simply made one by one —
  * a policy context's call, of any size, is the single call, anchored or counted as there.  A context may appear only once.  Asynchronous
  * like the single call: counts are returned at once, the samples land on the stream.  Returns 0, or -1 if a launch failed. */
@@ -138,8 +143,9 @@ int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const a
  * { 0, 0 }, the stream stands exactly where it stood before that launch, blocks made before it keep their results.  Asynchronous like the
  * single call: the counts are known at once, the samples land on the context's stream.
  * Blocks the single call gives to the general kernel are gathered into runs of one launch and one history roll each; every other block (a
- * flush, a block large enough for the matrix-core path, strict order, endpoint extrapolation, the cut-invariant policy on a rational ratio,
- * a sharded context) is made as its single call, between the runs, in stream order.  With timing on (resampleHipSetTiming) a run counts as
+ * flush, a block large enough for the matrix-core path, strict order, an EXTRAPOLATE_ENDPOINTS stream's blocks up to and including its
+ * first output — its later blocks are gathered —, the cut-invariant policy on a rational ratio, a sharded context) is made as its single
+ * call, between the runs, in stream order.  With timing on (resampleHipSetTiming) a run counts as
  * one launch.
  * What a caller needs: the ratios of the next numBlocks blocks, in advance — an ASRC loop that estimates the drift, or a clock-recovery loop
  * on the host that steers by resampleGetPosition, knows them for the blocks it has buffered.  INTEGRATION.md shows such a loop. */
@@ -257,6 +263,20 @@ void floatIntegersLEDevice (const unsigned char *d_input, double inputGain, int 
 int floatIntegersBatchLEDevice (const unsigned char *const *d_inputs, const double *inputGains, const int *inputBits,
                                 const int *inputBytes, const int *inputStrides, artsample_t *const *d_outputs,
                                 const int *numSamples, int n, void *hipStream);
+
+/* ---- end-point extrapolation, device pointers ---- */
+/* the most known samples one run may have: the resampler extrapolates from at most numTaps - 1 (LDS holds the run) */
+#define ARTAMD_EXTRAPOLATE_MAX_KNOWN 1023
+/* LPC extrapolation (the fit EXTRAPOLATE_ENDPOINTS uses), n independent runs in one launch on hipStream.  Run i: counts [i] known
+ * samples, oldest first, at d_known [i] + j * strides [i]; backward [i] == 0 writes extras [i] samples that continue past the newest
+ * (reference extrapolate_forward), != 0 the extras [i] samples that precede the oldest, nearest first (extrapolate_reverse), to
+ * d_out [i] + j * strides [i].  Bit-identical to the reference.  Returns 0, or -1 (nothing enqueued) on a bad argument.
+ * Bad: counts [i] < 8 or > ARTAMD_EXTRAPOLATE_MAX_KNOWN, extras [i] < 0, strides [i] < 1, a NULL pointer of a run with extras [i] > 0.
+ * n <= 0 does nothing and returns 0; runs with extras [i] == 0 write nothing.  One workgroup per run, on the current device,
+ * asynchronous; the argument arrays may be reused as soon as the call returns.  A failed launch returns -1 and is counted in
+ * artamdErrorCount.  The known samples of a run must not overlap its own or another run's output (not checked). */
+int artamdExtrapolateBatchDevice (const artsample_t *const *d_known, const int *counts, const int *strides, const int *backward,
+                                  artsample_t *const *d_out, const int *extras, int n, void *hipStream);
 
 /* ---- time stretcher, device pointers (stretch.h) ---- */
 void stretchHipSetStream (Stretch *cxt, void *hipStream);

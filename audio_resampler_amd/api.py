@@ -168,6 +168,7 @@ def _bind(width):
         "stretchProcessDevice": (C.c_int, [ptr, ptr, C.c_int, ptr, C.c_double]),
         "stretchFlushDevice": (C.c_int, [ptr, ptr]),
         "resampleProcessBatchInterleavedDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleProcessAndFlushBatchInterleavedDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleProcessScheduleInterleavedDevice": (C.c_int, [RP, C.c_int, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "stretchProcessBatchDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr]),
         "stretchFlushBatchDevice": (C.c_int, [ptr, C.c_int, ptr, ptr]),
@@ -457,6 +458,21 @@ def _bind(width):
             (C.c_double * n)(*[float(v) for v in ratios]), res)
         if rc:
             raise RuntimeError("resampleProcessBatchInterleavedDevice failed")
+        return [(r.input_used, r.output_generated) for r in res]
+
+    def process_and_flush_batch_device(resamplers, d_ins, n_ins, d_outs, out_caps, ratios):
+        """resampleProcessAndFlushBatchInterleavedDevice over a list of Resampler objects: every context's
+        resampleProcessAndFlushInterleavedDevice call, the process calls and then the flushes gathered into shared launches (a
+        d_ins entry may be None with n_ins 0: a pure flush).  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
+        n = len(resamplers)
+        ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])
+        res = (ResampleResult * n)()
+        rc = lib().resampleProcessAndFlushBatchInterleavedDevice(
+            ctx, n, (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_ins]), (C.c_int * n)(*[int(v) for v in n_ins]),
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), (C.c_int * n)(*[int(v) for v in out_caps]),
+            (C.c_double * n)(*[float(v) for v in ratios]), res)
+        if rc:
+            raise RuntimeError("resampleProcessAndFlushBatchInterleavedDevice failed")
         return [(r.input_used, r.output_generated) for r in res]
 
     def decimate_batch_device(decimators, d_ins, n_ins, d_outs):

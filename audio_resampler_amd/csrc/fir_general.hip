@@ -713,7 +713,7 @@ int arthip_fir_batch (const ArtFirArgs *a, const ArtSegTable *segs, int n, void 
             for (int i = 0; i < n; ++i) {
                 const int cls = a [i].C > 4 ? 3 : a [i].C > 2 ? 2 : a [i].C == 2 ? 1 : 0;
                 if (cls == cgi && (a [i].interpolate != 0) == interp && (((a [i].mode & 3) == ART_MODE_PRECISE) == precise) &&
-                    general_group (a [i].T) == group && a [i].n_end > a [i].n_begin)
+                    general_group (a [i].T) == group && (a [i].n_end > a [i].n_begin || a [i].roll_dst))     // (no outputs but a roll: an item of roll workgroups only)
                     which [count++] = i;
             }
             if (!count) continue;

@@ -76,6 +76,7 @@ struct artamd_resampler {
     int last_fixed [4];                      /* its last launch of the last call: flag value (0: none), mask words, chunks per tile, kernel form (art_hip.h) */
     unsigned int *d_fix; size_t fix_cap;    /* [0] per-launch, [1] running count of outputs the matrix kernels evaluated off-pattern */
     void *d_batch; size_t batch_cap;         /* argument table of the batched calls led by this context */
+    art_s *d_tails; size_t tails_cap;        /* ... and the flush tails of every extrapolating context of such a call (resampleProcessAndFlushBatchInterleavedDevice) */
     void *d_sched; size_t sched_cap;         /* block and segment tables of the scheduled runs (resampleProcessScheduleInterleavedDevice) */
     unsigned long batch_stamp;               /* last batched call this context took part in (duplicate check) */
     int last_gathered;                       /* the last call or block ran in a launch shared by the batch or schedule entry (resampleHipLastGathered) */
@@ -701,7 +702,7 @@ void resampleFree (Resample *cxt)
         bank_release (hip->bank); arthip_free (hip->d_hist [0]); arthip_free (hip->d_hist [1]);
         {   /* every device buffer the context may have grown (NULL where it never did) */
             void *const device_buffers [] = { hip->d_in, hip->d_out, hip->d_tmp, hip->d_fix, hip->d_scratch, hip->d_pad, hip->d_planes, hip->d_rows,
-                                              hip->d_split, hip->d_patch, hip->d_batch, hip->d_sched };
+                                              hip->d_split, hip->d_patch, hip->d_batch, hip->d_tails, hip->d_sched };
             for (size_t i = 0; i < sizeof (device_buffers) / sizeof (device_buffers [0]); ++i) arthip_free (device_buffers [i]);
         }
         if (hip->rows_cache) { arthip_fir_rows_cache_free (hip->rows_cache); free (hip->rows_cache); }
@@ -1050,50 +1051,65 @@ static int prefill_history (Resample *cxt, const art_s *d_in, long in_pitch)
     return rc;
 }
 
-/* Forward extrapolation of half a window at flush time into d_patch (T/2 frames x C); NULL on failure */
-static const art_s *flush_tail (Resample *cxt)
+/* Forward extrapolation of half a window at flush time into `tail` (T/2 frames x C): the runs of one context, C of them, at `runs` */
+static int flush_tail_runs (const Resample *cxt, art_s *tail, ArtExtrapRun *runs)
 {
-    struct artamd_resampler *hip = cxt->hip;
     const int T = cxt->numTaps, C = cxt->numChannels, H = HIST_FRAMES (T), half = T / 2;
     /* (the reference fits the last T/2 samples and predicts from the last 4: with T = 4 that is 4 samples and no fit, the same) */
     const int known = half < 4 ? 4 : half;
 
-    hip->d_patch = arthip_grow (hip->d_patch, &hip->patch_cap, sizeof (art_s) * (size_t) half * C);
-    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) C);
-    if (!hip->d_patch || !runs) { free (runs); return NULL; }
     for (int c = 0; c < C; ++c) {
         linear_run (cxt, NULL, 0, H - known, known, c, &runs [c]);
-        runs [c].out = hip->d_patch + c; runs [c].out_stride = C;
+        runs [c].out = tail + c; runs [c].out_stride = C;
         runs [c].extras = half; runs [c].backward = 0;
     }
-    const int rc = arthip_extrapolate (runs, C, hip->stream);
+    return C;
+}
+
+/* ... into d_patch, launched; NULL on failure */
+static const art_s *flush_tail (Resample *cxt)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    const int C = cxt->numChannels;
+
+    hip->d_patch = arthip_grow (hip->d_patch, &hip->patch_cap, sizeof (art_s) * (size_t)(cxt->numTaps / 2) * C);
+    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) C);
+    if (!hip->d_patch || !runs) { free (runs); return NULL; }
+    const int rc = arthip_extrapolate (runs, flush_tail_runs (cxt, hip->d_patch, runs), hip->stream);
     free (runs);
     return rc ? NULL : hip->d_patch;
 }
 
 /* The stream's FIRST output is produced by the flush call itself (fewer than T/2 frames ever arrived): the reference's
  * prefill then runs after the postfill (resampler.c:775-791 then :812-819) over the real samples ++ the flush tail.
- * inputIndex is the value BEFORE the flush; the tail is in d_patch (flush_tail, earlier on the stream). */
-static int prefill_at_flush (Resample *cxt)
+ * inputIndex is the value BEFORE the flush; the tail (flush_tail_runs, earlier on the stream) is at `tail`.  The runs of one
+ * context (C of them, or 0 when there is nothing to extrapolate from) at `runs`. */
+static int prefill_at_flush_runs (const Resample *cxt, const art_s *tail, ArtExtrapRun *runs)
 {
-    struct artamd_resampler *hip = cxt->hip;
+    const struct artamd_resampler *hip = cxt->hip;
     const int T = cxt->numTaps, C = cxt->numChannels, H = HIST_FRAMES (T), half = T / 2;
     const int real = cxt->inputIndex - T, known = real + half, extra = T - known;
 
     if (real < 0 || known < 8 || extra <= 0) return 0;                   /* reference resampler.c:695 / :815 */
 
-    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) C);
-    if (!runs) return -1;
     for (int c = 0; c < C; ++c) {
         /* ring [T, inputIndex) = the newest `real` history frames, then the tail */
         linear_run (cxt, NULL, 0, H - real, real, c, &runs [c]);
-        runs [c].src [1] = hip->d_patch + c; runs [c].stride [1] = C; runs [c].n [1] = half;
+        runs [c].src [1] = tail + c; runs [c].stride [1] = C; runs [c].n [1] = half;
         /* older sample e is ring index T-1-e = linear H - inputIndex + T-1-e = H - real - 1 - e: inside the history */
         runs [c].out = hip->d_hist [hip->cur] + (size_t)(H - real - 1) * C + c;
         runs [c].out_stride = -C;
         runs [c].extras = extra; runs [c].backward = 1;
     }
-    const int rc = arthip_extrapolate (runs, C, hip->stream);
+    return C;
+}
+
+static int prefill_at_flush (Resample *cxt)
+{
+    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) cxt->numChannels);
+    if (!runs) return -1;
+    const int n = prefill_at_flush_runs (cxt, cxt->hip->d_patch, runs);
+    const int rc = n ? arthip_extrapolate (runs, n, cxt->hip->stream) : 0;
     free (runs);
     return rc;
 }
@@ -1411,86 +1427,226 @@ static int general_call (const Resample *cxt, const ArtFirArgs *a, const ArtSegT
     return !needs.matrix;
 }
 
-/* (an extrapolating stream's first output, *nruns != NULL: its prefill runs, as the single call would make them, are appended at
- * runs + *nruns) */
-static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, int cap, double ratio, void *lead_stream,
-                       ArtFirArgs *a, ArtSegTable *tab, ResampleResult *res, ArtamdPosition *trial, ArtExtrapRun *runs, int *nruns)
+/* What a batch call has gathered: the FIR arguments, table and planned position of each gathered call (`owner`: its index in the
+ * caller's list), and the extrapolation runs in front of the FIR launch — `runs`, and `late`, which read what `runs` write (a flush:
+ * the prefill of a stream whose first output the flush makes reads the tails) and so are a second launch. */
+typedef struct {
+    ArtFirArgs *args; ArtSegTable *tabs; ArtamdPosition *trials; ResampleResult *res; int *owner;
+    ArtExtrapRun *runs, *late;
+    int gathered, nruns, nlate;
+} BatchWork;
+
+/* room for n calls and run_cap runs of either kind (0: none — extrapolating calls are then made one by one); 0 or -1 */
+static int batch_work_init (BatchWork *w, int n, size_t run_cap)
+{
+    memset (w, 0, sizeof (*w));
+    w->args = malloc (sizeof (ArtFirArgs) * (size_t) n); w->tabs = malloc (sizeof (ArtSegTable) * (size_t) n);
+    w->trials = malloc (sizeof (ArtamdPosition) * (size_t) n); w->res = malloc (sizeof (ResampleResult) * (size_t) n);
+    w->owner = malloc (sizeof (int) * (size_t) n);
+    if (run_cap && (w->runs = malloc (sizeof (ArtExtrapRun) * 2 * run_cap)) != NULL) w->late = w->runs + run_cap;
+    return w->args && w->tabs && w->trials && w->res && w->owner ? 0 : -1;
+}
+
+static void batch_work_free (BatchWork *w)
+{
+    free (w->args); free (w->tabs); free (w->trials); free (w->res); free (w->owner); free (w->runs);
+}
+
+/* Plan one context's call as the single call would; gather it at w's next place (1) if the general kernel is the single call's and the
+ * context may share a launch, else leave the context as it stands (0: the caller makes the single call).  *res: the planned counts.
+ * nIn >= 0, an ordinary call: an extrapolating stream's first output brings its prefill runs, as the single call would make them.
+ * nIn < 0, a flush: gathered only with `tail` — room for the context's T/2 x C tail frames when it extrapolates, any non-NULL pointer
+ * otherwise (the existing batch entry passes NULL: its flushes are single calls).  The flush proper runs on the general kernel whatever
+ * the context's other calls run on; it brings its forward tail fits (w->runs) and, when it makes the stream's first output, the prefill
+ * over the samples ++ the tail (w->late).  (The flush call of an already flushed stream is the single call: behind the process phase it
+ * has no output left to make.) */
+static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, int cap, double ratio, void *lead_stream, art_s *tail,
+                       BatchWork *w, ResampleResult *res)
 {
     struct artamd_resampler *hip = cxt->hip;
-    int lin_floor;
+    ArtFirArgs *a = &w->args [w->gathered];
+    ArtSegTable *tab = &w->tabs [w->gathered];
+    ArtamdPosition *trial = &w->trials [w->gathered];
+    const int T = cxt->numTaps, is_flush = nIn < 0;
     const int first = (cxt->flags & (EXTRAPOLATE_PREFILL | RESAMPLER_FLUSHED)) == EXTRAPOLATE_PREFILL;
+    int lin_floor;
 
-    if (nIn < 0 || hip->stream != lead_stream || hip->timing || hip->device != arthip_current_device ()) return 0;
-    if (first ? (hip->nshards || (cxt->flags & RESAMPLE_STRICT_ORDER) || !runs || rewind_lead (cxt, nIn, cap, ratio)) : !gatherable_context (cxt)) return 0;
+    if ((is_flush && !tail) || hip->stream != lead_stream || hip->timing || hip->device != arthip_current_device ()) return 0;
+    if (is_flush) {
+        if (hip->nshards || (cxt->flags & (RESAMPLE_STRICT_ORDER | RESAMPLER_FLUSHED)) || ((cxt->flags & EXTRAPOLATE_ENDPOINTS) && !w->runs)) return 0;
+    }
+    else if (first ? (hip->nshards || (cxt->flags & RESAMPLE_STRICT_ORDER) || !w->runs || rewind_lead (cxt, nIn, cap, ratio)) : !gatherable_context (cxt)) return 0;
 
     const int nseg = plan_segments (cxt, nIn, cap, ratio, trial, res, &lin_floor);      /* (out of memory: the one-by-one path reports it) */
-    if (nseg < 0 || nseg > arthip_fir_batch_max_segments () || res->output_generated == 0) return 0;
+    /* (a flush without an output still appends its half window to the history: an item of roll workgroups only) */
+    if (nseg < 0 || nseg > arthip_fir_batch_max_segments () || (res->output_generated == 0 && !is_flush)) return 0;
 
-    fill_args (cxt, a, ratio, d_in, 0, (int) res->input_used, d_out, 0);
+    const int extrapolated = is_flush && (cxt->flags & EXTRAPOLATE_ENDPOINTS);
+    const int appended = is_flush ? T / 2 : (int) res->input_used;
+    /* (enqueue_call's arguments: a flush reads its tail, T/2 frames, or no input frames at all) */
+    fill_args (cxt, a, ratio, is_flush ? (extrapolated ? tail : NULL) : d_in, 0, is_flush ? (extrapolated ? T / 2 : 0) : (int) res->input_used, d_out, 0);
     seg_table (hip, 0, nseg, lin_floor, tab);
     a->n_begin = hip->segs [0].first_output; a->n_end = res->output_generated;
-    if (!general_call (cxt, a, tab, res->output_generated)) return 0;
+    if (!is_flush && !general_call (cxt, a, tab, res->output_generated)) return 0;
 
-    const int appended = (int) res->input_used;
     a->roll_dst = appended > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;      /* the launch takes the history roll along */
     a->roll_appended = appended;
-    if (first && (nseg == 1 || hip->segs [1].first_output > 0))           /* (enqueue_call's condition for the prefill) */
-        *nruns += prefill_history_runs (cxt, nIn > 0 ? d_in : NULL, 0, runs + *nruns);
+    /* (enqueue_call's conditions for the fits) */
+    if (first && !is_flush && (nseg == 1 || hip->segs [1].first_output > 0))
+        w->nruns += prefill_history_runs (cxt, nIn > 0 ? d_in : NULL, 0, w->runs + w->nruns);
+    if (extrapolated) {
+        w->nruns += flush_tail_runs (cxt, tail, w->runs + w->nruns);
+        /* (a flush that had to rewind the ring first leaves more than T known samples: nothing to prefill) */
+        if (first && res->output_generated && trial->inputIndex == cxt->inputIndex + T / 2)
+            w->nlate += prefill_at_flush_runs (cxt, tail, w->late + w->nlate);
+    }
     return 1;
 }
 
+/* the gathered calls' launches on the lead's stream: the fits, those that read them, then every FIR (the history rolls ride along); 0 or -1 */
+static int batch_launch (struct artamd_resampler *lead, const BatchWork *w)
+{
+    lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_batch_item_bytes () * (size_t) w->gathered);
+    if (lead->d_batch && !(w->nruns && arthip_extrapolate (w->runs, w->nruns, lead->stream)) &&
+        !(w->nlate && arthip_extrapolate (w->late, w->nlate, lead->stream)) &&
+        !arthip_fir_batch (w->args, w->tabs, w->gathered, lead->d_batch, lead->stream))
+        return 0;
+    fprintf (stderr, "artamd: resample batch launch failed: %s\n", arthip_last_error ());
+    return -1;
+}
+
+/* ... and the contexts' positions, behind them (enqueue_call's commit) */
+static void batch_commit (Resample *const *cxts, const BatchWork *w)
+{
+    for (int k = 0; k < w->gathered; ++k) {
+        Resample *cxt = cxts [w->owner [k]];
+        const int outputs = w->args [k].n_end > w->args [k].n_begin;
+        cxt->hip->last_gathered = 1;
+        if (w->args [k].roll_dst) { cxt->hip->cur ^= 1; cxt->hip->lin_origin += w->args [k].roll_appended; }
+        cxt->outputOffset = w->trials [k].outputOffset; cxt->inputIndex = w->trials [k].inputIndex;
+        cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (w->trials [k].flags & RESAMPLER_FLUSHED) |
+                     (outputs ? 0 : (cxt->flags & EXTRAPOLATE_PREFILL));
+        cxt->hip->floor_active = w->trials [k].floorActive;
+        if (outputs) cxt->hip->last_kernel = ART_KERNEL_GENERAL;
+    }
+}
+
 static unsigned long *stamp_of (const void *cxt) { return &((const Resample *) cxt)->hip->batch_stamp; }
+
+/* the batch entries' process phase, on the lead's device: every context's ordinary call, gathered or single */
+static int batch_process (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
+                          artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios, ResampleResult *results)
+{
+    struct artamd_resampler *lead = cxts [0]->hip;
+    BatchWork w;
+    int rc = -1;
+
+    size_t channels = 0;                 /* (room for the prefill runs of every extrapolating stream's first output: one per channel) */
+    for (int i = 0; i < n; ++i)
+        if ((cxts [i]->flags & EXTRAPOLATE_PREFILL) && !cxts [i]->hip->nshards) channels += (size_t) cxts [i]->numChannels;
+    if (batch_work_init (&w, n, channels)) goto out;
+
+    for (int i = 0; i < n; ++i) {
+        if (batch_plan (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i], lead->stream, NULL, &w, &results [i]))
+            w.owner [w.gathered++] = i;
+        else
+            results [i] = resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]);
+    }
+
+    if (w.gathered) {
+        /* the prefill fits of the first outputs, one launch in front of the FIR launches that read what they write */
+        if (batch_launch (lead, &w)) {
+            for (int k = 0; k < w.gathered; ++k) results [w.owner [k]].input_used = results [w.owner [k]].output_generated = 0;
+            goto out;
+        }
+        batch_commit (cxts, &w);
+    }
+    rc = 0;
+out:
+    batch_work_free (&w);
+    return rc;
+}
 
 int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                                            artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
                                            ResampleResult *results)
 {
     if (n <= 0) return 0;
+    if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample", "context")) return -1;
     struct artamd_resampler *lead = cxts [0]->hip;
     ENTER_DEVICE (lead);
-    ArtFirArgs *args = malloc (sizeof (ArtFirArgs) * (size_t) n);
-    ArtSegTable *tabs = malloc (sizeof (ArtSegTable) * (size_t) n);
-    ArtamdPosition *trials = malloc (sizeof (ArtamdPosition) * (size_t) n);
-    int *owner = malloc (sizeof (int) * (size_t) n);
-    ArtExtrapRun *runs = NULL;
-    int gathered = 0, nruns = 0, rc = -1;
+    const int rc = batch_process (cxts, n, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results);
+    LEAVE_DEVICE (lead);
+    return rc;
+}
 
-    if (!args || !tabs || !trials || !owner || artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample", "context")) goto out;
-    size_t channels = 0;                 /* (room for the prefill runs of every extrapolating stream's first output: one per channel) */
+/* ---- many whole clips, one launch per stage ------------------------------------------------------------------------
+ * A clip is init / reset -> process -> flush, and the flush is the dear call of an EXTRAPOLATE_ENDPOINTS stream: one forward fit per
+ * channel, each a one-wave workgroup that runs for milliseconds.  resampleProcessAndFlushBatchInterleavedDevice makes the batch's process
+ * phase (above), then plans the flush of every context whose single resampleProcessAndFlushInterleavedDevice would go on to it, and
+ * gathers them: all tail fits one launch (into one buffer of the lead's, a slice per context), the prefills of the streams whose first
+ * output the flush makes a second, the flushes' FIR one more with their rolls.  Flushes that cannot be gathered are the single call. */
+static int flush_due (const int *numInputFrames, const int *numOutputFrames, const ResampleResult *results, int i)
+{
+    /* (resampleProcessAndFlushInterleavedDevice's early return: input not all used, or no room left) */
+    return numInputFrames [i] - (int) results [i].input_used == 0 && numOutputFrames [i] - (int) results [i].output_generated != 0;
+}
+
+static int batch_flush (Resample *const *cxts, int n, const int *numInputFrames, artsample_t *const *d_outputs, const int *numOutputFrames,
+                        const double *ratios, ResampleResult *results)
+{
+    struct artamd_resampler *lead = cxts [0]->hip;
+    BatchWork w;
+    int rc = -1;
+
+    size_t channels = 0, tail_samples = 0;
     for (int i = 0; i < n; ++i)
-        if ((cxts [i]->flags & EXTRAPOLATE_PREFILL) && !cxts [i]->hip->nshards) channels += (size_t) cxts [i]->numChannels;
-    if (channels) runs = malloc (sizeof (ArtExtrapRun) * channels);     /* (none: those calls are made one by one) */
+        if (flush_due (numInputFrames, numOutputFrames, results, i) && (cxts [i]->flags & EXTRAPOLATE_ENDPOINTS) && !cxts [i]->hip->nshards) {
+            channels += (size_t) cxts [i]->numChannels;
+            tail_samples += (size_t)(cxts [i]->numTaps / 2) * cxts [i]->numChannels;
+        }
+    if (batch_work_init (&w, n, channels)) goto out;
+    /* (no tails: the extrapolating contexts' flushes are made one by one) */
+    if (tail_samples) lead->d_tails = arthip_grow (lead->d_tails, &lead->tails_cap, sizeof (art_s) * tail_samples);
 
+    art_s *tail = lead->d_tails;
     for (int i = 0; i < n; ++i) {
-        if (batch_plan (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i], lead->stream,
-                        &args [gathered], &tabs [gathered], &results [i], &trials [gathered], runs, &nruns))
-            owner [gathered++] = i;
+        if (!flush_due (numInputFrames, numOutputFrames, results, i)) continue;
+        Resample *cxt = cxts [i];
+        const int cap = numOutputFrames [i] - (int) results [i].output_generated;
+        art_s *out = d_outputs [i] + (size_t) results [i].output_generated * cxt->numChannels;
+        const int extrapolates = (cxt->flags & EXTRAPOLATE_ENDPOINTS) && !cxt->hip->nshards;
+
+        if (batch_plan (cxt, NULL, -1, out, cap, ratios [i], lead->stream, extrapolates ? tail : out, &w, &w.res [w.gathered]))
+            w.owner [w.gathered++] = i;
         else
-            results [i] = resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]);
+            results [i].output_generated += resampleProcessInterleavedDevice (cxt, NULL, -1, out, cap, ratios [i]).output_generated;
+        if (extrapolates && tail) tail += (size_t)(cxt->numTaps / 2) * cxt->numChannels;
     }
 
-    if (gathered) {
-        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_batch_item_bytes () * (size_t) gathered);
-        /* the prefill fits of the first outputs, one launch in front of the FIR launches that read what they write */
-        if (!lead->d_batch || (nruns && arthip_extrapolate (runs, nruns, lead->stream)) ||
-            arthip_fir_batch (args, tabs, gathered, lead->d_batch, lead->stream)) {
-            fprintf (stderr, "artamd: resample batch launch failed: %s\n", arthip_last_error ());
-            for (int k = 0; k < gathered; ++k) results [owner [k]].input_used = results [owner [k]].output_generated = 0;
-            goto out;
-        }
-        for (int k = 0; k < gathered; ++k) {
-            Resample *cxt = cxts [owner [k]];
-            cxt->hip->last_gathered = 1;
-            if (args [k].roll_dst) { cxt->hip->cur ^= 1; cxt->hip->lin_origin += args [k].roll_appended; }
-            cxt->outputOffset = trials [k].outputOffset; cxt->inputIndex = trials [k].inputIndex;
-            cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (trials [k].flags & RESAMPLER_FLUSHED);
-            cxt->hip->floor_active = trials [k].floorActive;
-            cxt->hip->last_kernel = ART_KERNEL_GENERAL;
-        }
+    if (w.gathered) {
+        /* (a failed launch: the flushes of its contexts were not made — their results are the process phase's, as after a failed single flush) */
+        if (batch_launch (lead, &w)) goto out;
+        batch_commit (cxts, &w);
+        for (int k = 0; k < w.gathered; ++k) results [w.owner [k]].output_generated += w.res [k].output_generated;
     }
     rc = 0;
 out:
-    free (args); free (tabs); free (trials); free (owner); free (runs);
+    batch_work_free (&w);
+    return rc;
+}
+
+int resampleProcessAndFlushBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
+                                                   artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
+                                                   ResampleResult *results)
+{
+    if (n <= 0) return 0;
+    if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample", "context")) return -1;
+    struct artamd_resampler *lead = cxts [0]->hip;
+    ENTER_DEVICE (lead);
+    int rc = batch_process (cxts, n, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results);
+    if (!rc) rc = batch_flush (cxts, n, numInputFrames, d_outputs, numOutputFrames, ratios, results);
+    if (rc) artamd_note_failure ("resampler: a launch of the batched process-and-flush failed");
     LEAVE_DEVICE (lead);
     return rc;
 }

@@ -90,8 +90,8 @@ unsigned int resampleHipCutInvariantFallbacks (Resample *cxt);
  * Either way a sample is within the parity bar; the two differ in the last place of a few per cent of the samples. */
 void resampleHipKeepRows (Resample *cxt, int on);
 int  resampleHipLastKernel (Resample *cxt);          /* which kernel produced the bulk of the last call */
-/* 1 when the context's last call or block ran inside a launch shared by resampleProcessBatchInterleavedDevice or
- * resampleProcessScheduleInterleavedDevice, 0 when it ran as a single call (which streams of a service batch) */
+/* 1 when the context's last call or block ran inside a launch shared by resampleProcessBatchInterleavedDevice,
+ * resampleProcessAndFlushBatchInterleavedDevice or resampleProcessScheduleInterleavedDevice, 0 when it ran as a single call (which streams of a service batch) */
 int  resampleHipLastGathered (Resample *cxt);
 /* the matrix-core path's fixed-point kernel (regular launches, 4-byte samples): 0 = the last call did not use it, 1 = it ran,
  * 2 = it was enqueued and stood down for the f32 kernel's tile loop (an infinity or a NaN among the frames the launch reads: any finite
@@ -129,6 +129,24 @@ ResampleResult resampleProcessAndFlushInterleavedDevice (Resample *cxt, const ar
 int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                                            artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
                                            ResampleResult *results);
+/* Many whole clips (or streams that end), one launch per stage: results [i], the samples in d_outputs [i] and the context's state afterwards
+ * (position, flags, history, resampleHipLastKernel) are exactly those of resampleProcessAndFlushInterleavedDevice (cxts [i], d_inputs [i],
+ * numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]) — including its early return: a context whose input was not all used, or
+ * whose output has no room left, is not flushed.  numInputFrames [i] == 0 with a NULL input is a pure flush.
+ * First the ordinary calls, as resampleProcessBatchInterleavedDevice makes them (gathered or one by one).  Then the flushes: those of the
+ * contexts that may share a launch (on the stream and device of cxts [0], not sharded, not strict order, timing off; the flush proper always
+ * runs on the general kernel, so a clip long enough for the matrix-core path is processed singly and flushed with the others) are gathered —
+ * the forward tail fits of ALL EXTRAPOLATE_ENDPOINTS contexts one launch, the prefills of the streams whose first output the flush makes a
+ * second, the flushes' FIR with their history rolls a third — and the others (also the flush call of a stream that was flushed before) are
+ * made as the single call.  Five launches for any number of gathered contexts of one shape (a FIR launch per kernel variant: channel
+ * group, interpolation, accumulator, taps class), and no allocation once warm (the tails live in one buffer of cxts [0]).
+ * resampleHipLastGathered is 1 for a context whose flush (or, where none was due, whose ordinary call) ran in a shared launch.  A context may appear only once.  Asynchronous like
+ * the single call.  Returns 0 (also for n <= 0); -1 with nothing enqueued and nothing counted if a context is NULL or appears twice; -1 if a
+ * launch failed (counted in artamdErrorCount): the contexts of the failed launch stand where they stood before it — a failed process launch
+ * leaves them { 0, 0 } and no flush is made for anyone, a failed flush launch leaves them the results of their process call. */
+int resampleProcessAndFlushBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
+                                                   artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
+                                                   ResampleResult *results);
 /* Many blocks of ONE stream, one launch.  Makes the same calls as this loop, with the same counts and the same samples bit for bit:
  *     in = d_input; out = d_output;
  *     for (k = 0; k < numBlocks; ++k) {

@@ -448,7 +448,9 @@ def _bind(width):
 
     def process_batch_device(resamplers, d_ins, n_ins, d_outs, out_caps, ratios):
         """resampleProcessBatchInterleavedDevice over a list of Resampler objects: one call per context, one launch for those
-        the general kernel runs.  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
+        the general kernel runs and one grouped launch per shape for those the f32 streaming matrix kernel runs un-split on kept rows
+        (matrix-size calls under preference 6, anchored calls under the cut-invariant policy; a stream's first matrix call, which
+        builds its rows, and everything else is made one by one).  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
         n = len(resamplers)
         ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])
         res = (ResampleResult * n)()
@@ -462,7 +464,8 @@ def _bind(width):
 
     def process_and_flush_batch_device(resamplers, d_ins, n_ins, d_outs, out_caps, ratios):
         """resampleProcessAndFlushBatchInterleavedDevice over a list of Resampler objects: every context's
-        resampleProcessAndFlushInterleavedDevice call, the process calls and then the flushes gathered into shared launches (a
+        resampleProcessAndFlushInterleavedDevice call, the process calls (general-kernel and matrix-core calls alike, as
+        process_batch_device gathers them) and then the flushes gathered into shared launches (a
         d_ins entry may be None with n_ins 0: a pure flush).  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
         n = len(resamplers)
         ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])

@@ -182,6 +182,23 @@ void   arthip_fir_rows_cache_free (void *cache);
 size_t arthip_fir_batch_item_bytes (void);
 int arthip_fir_batch_max_segments (void);                /* ring-epoch segments a batched call may have */
 int arthip_fir_batch (const ArtFirArgs *a, const ArtSegTable *segs, int n, void *d_table, void *stream);
+/* n independent calls of the f32 streaming matrix-core kernel in one launch per shape (4-byte build; the 8-byte build plans none).
+ * arthip_fir_group_plan: `a` / `segs` as arthip_fir would get them (buffers provisioned, roll_dst set, no timing events) — would that call be ONE
+ * regular, un-split launch of that kernel on rows kept across calls whose set is built?  1: *out is that launch, nothing enqueued, and the
+ * context's host-side rows cache is as the single launch's own look-ups leave it; 0: the call is made as it stands (arthip_fir), as if never asked.
+ * Calls of one shape (arthip_fir_group_same_class) may share a launch: the caller numbers the classes it wants launched 0 .. in `cls` and hands
+ * them to arthip_fir_group with device memory of arthip_fir_group_table_bytes (n) bytes (reused call after call: stream order protects it).
+ * Returns 0, or -1 with nothing enqueued; the history rolls ride along (every call as ART_KERNEL_MFMA | ART_FIR_ROLLED where roll_dst is set). */
+typedef struct {
+    ArtFirArgs a;                        /* the launch, anchored on the stream's canonical period */
+    int cls;                             /* the caller's: the launch class of this call */
+    int fixup;                           /* the nearest-filter pass-through pass follows the launch */
+    union { char bytes [160]; double align; } geom;     /* the launch's tile geometry (fir_matrix.hip) */
+} ArtFirGroupCall;
+int arthip_fir_group_plan (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, ArtFirGroupCall *out);
+int arthip_fir_group_same_class (const ArtFirGroupCall *x, const ArtFirGroupCall *y);
+size_t arthip_fir_group_table_bytes (int n);
+int arthip_fir_group (const ArtFirGroupCall *calls, int n, void *d_table, void *stream);
 /* Consecutive blocks of ONE stream as one general-kernel launch (resampleProcessScheduleInterleavedDevice).  The run's linear space is
  * (history ++ run input); a block is the single call it replaces, moved in_off frames along it. */
 typedef struct {

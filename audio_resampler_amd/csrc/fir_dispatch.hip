@@ -106,6 +106,11 @@ static int fir_in_groups (const ArtFirArgs *a, const ArtSegTable *segs, int kern
 
 void arthip_fir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs) { artfir_rows_touch (a, segs); }
 
+int arthip_fir_group_plan (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, ArtFirGroupCall *out) { return artfir_group_plan (a, segs, kernel_pref, out); }
+int arthip_fir_group_same_class (const ArtFirGroupCall *x, const ArtFirGroupCall *y) { return artfir_group_same_class (x, y); }
+size_t arthip_fir_group_table_bytes (int n) { return artfir_group_table_bytes (n); }
+int arthip_fir_group (const ArtFirGroupCall *calls, int n, void *d_table, void *stream) { return artfir_group (calls, n, d_table, stream); }
+
 void arthip_fir_needs (const ArtFirArgs *call, const ArtSegTable *first, unsigned int outputs, int kernel_pref, ArtFirNeeds *n)
 {
     *n = ArtFirNeeds ();

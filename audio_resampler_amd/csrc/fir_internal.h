@@ -10,3 +10,8 @@ int  artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pre
 void artfir_matrix_needs (const ArtFirArgs *a, const ArtSegTable *first, int kernel_pref, ArtFirNeeds *n);   // fir_matrix.hip | fir_matrix64.hip (nothing)
 void artfir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs);                               // fir_matrix.hip | fir_matrix64.hip (nothing)
 bool artfir_test_fail ();                                                                             // fir_dispatch.hip: the ARTAMD_TEST_FAIL_FIR hook, one count per FIR launch
+// many calls of one shape as one launch of the f32 streaming matrix kernel (fir_matrix.hip; the 8-byte build has no such kernel: never planned)
+int    artfir_group_plan (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, ArtFirGroupCall *out);   // fir_matrix.hip | fir_matrix64.hip (0)
+int    artfir_group_same_class (const ArtFirGroupCall *x, const ArtFirGroupCall *y);
+size_t artfir_group_table_bytes (int n);
+int    artfir_group (const ArtFirGroupCall *calls, int n, void *d_table, void *stream);

@@ -3,6 +3,7 @@
 // regular launches: the headline path), fir_mfma_kernel (one tile per workgroup with per-output position replay: every other
 // launch), their shared K walk, and the host-side rules that pick between them and the general kernel.
 #include "fir_matrix_stream.hip.h"
+#include <cstring>
 
 #if !ART_WIDE          // the 8-byte sample build has its own matrix-core kernel (fir_matrix64.hip)
 
@@ -620,6 +621,118 @@ void fir_mfma_stream_kernel (ArtFirArgs a, MfmaGeom g, int wgs_per_xcd)
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The streaming kernel over MANY launches of one shape (arthip_fir_group: the batch entry's calls that would each be one un-split
+// fir_mfma_stream_kernel launch on kept rows).  A matrix launch has a floor that does not shrink with the call, and a call of a few
+// tiles leaves most of the chip idle under it: N streams of one shape are N x the columns of one GEMM.  A tile never mixes launches,
+// so each tile is the tile its own launch would have run — same staging, same K walk and flush schedule, same epilogue (the text of
+// fir_matrix_stream_body.inc): what differs is where a tile's constants come from.  The shape (MfmaGroupClass) is a kernel argument,
+// uniform for the launch, so the per-thread offsets stay loop-invariant; what belongs to one launch (MfmaGroupItem; its first flat tile in first [])  is read per tile
+// from a table in device memory, uniformly for the workgroup (scalar loads).
+// Flat tile list = the items' tiles one after another, each item's in its own launch's order (period group major, slot tile minor;
+// only the tiles that hold an output: `tiles` of the item); cut into 8 contiguous ranges, one per XCD, each strided by that XCD's
+// persistent workgroups.  Flat tile -> item: binary search over the items' first tiles.  Which workgroup runs a tile never enters
+// its arithmetic.  The items' history rolls ride along as extra workgroups, `roll_blocks` per item.
+// ---------------------------------------------------------------------------------------------------
+struct MfmaGroupItem {
+    const float *in, *hist, *eff, *head;
+    float *out, *roll_dst;
+    const int *tile_w0;
+    unsigned int n_begin, n_end;
+    int n_skip, in_frames, w_shift, head_frames, head_pad, roll_appended;
+};
+struct MfmaGroupClass {
+    int P, Q, ktot, slot_tiles, band_lo, band_hi, H;
+    int items, tiles, tiles_per_xcd, wgs_per_xcd, roll_blocks;
+};
+
+// the item of flat tile `tile`: the last one whose first tile is not behind it (first [0] == 0)
+__device__ __forceinline__ int group_item_of (const unsigned int *__restrict__ first, int items, unsigned int tile)
+{
+    int lo = 0, hi = items - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (first [mid] <= tile) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// every item's head (head_pad zero frames ++ history ++ first input frames: what mfma_head_kernel writes per call); `blocks` workgroups per item
+__global__ __launch_bounds__ (256)
+void mfma_head_group_kernel (const MfmaGroupItem *__restrict__ items, int H, int C, int blocks)
+{
+    const MfmaGroupItem &it = items [blockIdx.x / (unsigned int) blocks];
+    const unsigned int total = (unsigned int) it.head_frames * (unsigned int) C, e = (blockIdx.x % (unsigned int) blocks) * 256u + threadIdx.x;
+    if (e >= total) return;
+    const unsigned int pad = (unsigned int) it.head_pad * (unsigned int) C, hist = (unsigned int) H * (unsigned int) C;
+    float v = 0.0f;
+    if (e >= pad) {
+        unsigned int k = e - pad;
+        if (k < hist) v = it.hist [k];
+        else { k -= hist; if (k < (unsigned int) it.in_frames * (unsigned int) C) v = it.in [k]; }
+    }
+    const_cast<float *> (it.head) [e] = v;
+}
+
+template <bool INTERP, int CG>
+__global__ __launch_bounds__ (2 * MF_THREADS) __attribute__ ((amdgpu_waves_per_eu (6)))
+void fir_mfma_group_kernel (MfmaGroupClass cls, const unsigned int *__restrict__ first, const MfmaGroupItem *__restrict__ items)
+{
+    constexpr int THREADS = 2 * MF_THREADS;
+    constexpr int PPW = MF_COLS / CG > MF_MAX_PPW ? MF_MAX_PPW : MF_COLS / CG;
+    constexpr int NCOLS = PPW * CG;
+    constexpr bool PASS = false;                              // (nearest-filter streams without a low-pass: pass_fixup behind the launch)
+    __shared__ __attribute__ ((aligned (16))) float As_ [2] [32 * MF_LD];
+    __shared__ __attribute__ ((aligned (16))) float Bs_ [2] [MF_COLS * MF_LD];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool loader = wave >= 4;
+    const int pt = tid & (MF_THREADS - 1);
+    const int wgs_per_xcd = cls.wgs_per_xcd;
+
+    const unsigned int stream_blocks = 8u * (unsigned int) wgs_per_xcd;
+    if (blockIdx.x >= stream_blocks) {                        // extra workgroups: the items' history rolls (as in fir_mfma_stream_kernel)
+        const unsigned int rb = blockIdx.x - stream_blocks;
+        const MfmaGroupItem &it = items [rb / (unsigned int) cls.roll_blocks];
+        if (it.roll_dst) {
+            const int e = (int)(rb % (unsigned int) cls.roll_blocks) * THREADS + tid;
+            if (e < cls.H * CG) {
+                const int f = e / CG, c = e - f * CG, lin = it.roll_appended + f;
+                float v = 0.0f;
+                if (lin < cls.H) v = it.hist [(size_t) lin * CG + c];
+                else if (it.in && lin - cls.H < it.in_frames) v = it.in [(size_t)(lin - cls.H) * CG + c];
+                it.roll_dst [e] = v;
+            }
+        }
+        return;
+    }
+
+    // the tile's launch, as the single kernel's arguments: the class's part once, the item's by tile_at
+    ArtFirArgs a;
+    MfmaGeom g;
+    a.C = CG; a.H = cls.H;
+    g.P = cls.P; g.Q = cls.Q; g.ktot = cls.ktot; g.slot_tiles = cls.slot_tiles; g.band_lo = cls.band_lo; g.band_hi = cls.band_hi;
+    const int xcd = blockIdx.x & 7;
+    const int xcd_end = min ((xcd + 1) * cls.tiles_per_xcd, cls.tiles);
+    const int rank = xcd * cls.tiles_per_xcd + (int)(blockIdx.x >> 3);
+    auto tile_at = [&] (int within, int &st, int &jg) -> bool {
+        if (within >= xcd_end) return false;
+        const int idx = group_item_of (first, cls.items, (unsigned int) within);
+        const MfmaGroupItem &it = items [idx];
+        a.in = it.in; a.in_frames = it.in_frames; a.out = it.out; a.n_begin = it.n_begin; a.n_end = it.n_end; a.n_skip = it.n_skip;
+        g.eff = const_cast<float *> (it.eff); g.tile_w0 = const_cast<int *> (it.tile_w0); g.w_shift = it.w_shift;
+        g.head = const_cast<float *> (it.head); g.head_frames = it.head_frames; g.head_pad = it.head_pad;
+        const int t = within - (int) first [idx];
+        jg = t / g.slot_tiles; st = t - jg * g.slot_tiles;
+        return true;
+    };
+#define MF_TILE_LIST
+#define MF_COUNT_TILES(n) { const int left = xcd_end - rank; if (left > 0) n = (left + wgs_per_xcd - 1) / wgs_per_xcd; }
+#include "fir_matrix_stream_body.inc"
+#undef MF_COUNT_TILES
+#undef MF_TILE_LIST
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The streaming kernel for launches of FEW tiles (calls of some ten thousand frames: fewer tiles than the chip has CUs).  One
 // workgroup per tile walks the whole K range at the pace ONE CU draws rows and samples through a cold L2 (~20 us for 32 chunks
 // whatever the call's size: profiles/r3_small_launch_experiment.txt).  Here a tile's K range is cut into KS parts, each a work item
@@ -1124,11 +1237,19 @@ void artfir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs)
     (void) artfir_rows_canonical (a, segs, mu * a->period_out, mu * a->period_in, (ArtRowsCache *) a->rows_cache, &pos0, &slot0, &w, false);
 }
 
-// Launch the matrix-core path for this call if it applies: returns ART_KERNEL_MFMA (| ART_FIR_ROLLED), -1 on a launch failure,
-// 0 when the call is for the general kernel.
-int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, void *stream)
+// What artfir_matrix decides about a call before it enqueues anything, in two steps (the fixed-point kernel's own launch sits between them):
+// the tiles — geometry, tables carved out of the scratch buffer, grid, whether the launch is regular — and the rows: whether the launch runs
+// anchored on the stream's canonical period on rows kept across calls, and whether that set is already built.  arthip_fir_group_plan asks
+// the same two steps for a call the batch entry would like to run with others in one launch.
+struct MatrixPlan {
+    MfmaGeom g; int cgt; bool ws, regular; unsigned int roll_blocks; dim3 grid;
+    ArtFirArgs a_v; ArtRowsTable tb; bool rows_ready, on_kept_rows;
+    ArtRowsCache *rc_build; int w_build;                      // the f32 set this launch is to build (nullptr: none): described in the cache once the launch is certain
+};
+
+// false: the call is for the general kernel
+static bool matrix_plan_tiles (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, MatrixPlan &p)
 {
-    hipStream_t st = (hipStream_t) stream;
     // MFMA path: exact rational ratio, default numeric mode, interleaved buffers, no history floor — and enough work
     // to beat the general kernel.  Cost models fitted to MI355X measurements (tools/bench_small_taps.py,
     // profiles/r1_small_calls.txt), n = output frames of the launch:
@@ -1137,38 +1258,106 @@ int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref
     //                                             also those at the history seam, stages through the same loop (was 14 + 1.4)
     // The MFMA path is taken when the general kernel would take longer than the floor.  For channel counts without a
     // compiled column group the older rule stays: outputs x channels x taps of at least 1.2e8.
-    const bool mfma_ok = artfir_takes_matrix_path (a, segs, kernel_pref);
+    if (!artfir_takes_matrix_path (a, segs, kernel_pref)) return false;
+    MfmaGeom &g = p.g;
+    const int cgt = p.cgt = matrix_geometry (a, g);
+    const bool ws = p.ws = cgt != 0;                          // (generic channel counts: the non-specialised instantiation on the same tiles)
+    const bool wide = false;                                  // (64-slot tiles, two m-tiles per X tile, lost: 156 VGPRs => one workgroup per CU, 29 vs 36 Gsamples/s in round 1; the template keeps the parameter, nothing instantiates it)
+    {   // carve the per-launch tables out of the scratch buffer
+        const size_t rows = (size_t) g.slot_tiles * g.tile_rows, eff_bytes = rows * g.ktot * sizeof (float);
+        char *base = (char *) a->scratch;
+        g.eff = (float *) base;
+        g.canon_frac = (double *)(base + ((eff_bytes + 15) & ~(size_t) 15));
+        g.canon_ip = (int *)(g.canon_frac + rows);
+        g.canon_fi = g.canon_ip + rows;
+        g.tile_w0 = g.canon_fi + rows;
+        if (!base || (size_t)((char *)(g.tile_w0 + 3 * g.slot_tiles) - base) > a->scratch_bytes) return false;
+        g.head = nullptr; g.head_frames = 0;
+        if (ws && !wide) {
+            // the call's head as one contiguous array: everything a tile whose window starts inside the history can read
+            // (+ the two chunks the staging runs ahead)
+            const size_t used = (((size_t)((char *)(g.tile_w0 + 3 * g.slot_tiles) - base)) + 255) & ~(size_t) 255;
+            g.head_frames = g.head_pad + a->H + (g.ppw - 1) * g.Q + g.ktot + 3 * MF_KC;
+            if (used + (size_t) g.head_frames * a->C * sizeof (float) > a->scratch_bytes) return false;
+            g.head = (float *)(base + used);
+        }
+    }
+    const unsigned int wg_threads = ws ? 2 * MF_THREADS : MF_THREADS;
+    p.roll_blocks = a->roll_dst ? (unsigned int)((a->H * a->C + wg_threads - 1) / wg_threads) : 0u;
+    p.grid = dim3 ((unsigned int)(8 * g.groups_per_xcd * g.slot_tiles) + p.roll_blocks, (unsigned int)((a->C + g.cg - 1) / g.cg));
+
+    p.regular = ws && !wide && launch_streams (a, segs, kernel_pref);
+    if (a->segs_truncated && !p.regular) return false;        // (the tile kernel replays positions from the table: not beyond it)
+    return true;
+}
+
+// The f32 streaming kernel on rows kept across calls (fir_matrix_i8.hip, "The rows across calls": the same canonical period, one set of
+// eff / canon_* / tile_w0 at the head of a->rows — no block alignment to honour): the launch is anchored on the canonical period
+// (n_skip slots of its first period computed and not stored), the set's linear indices carried w_shift frames on, and all the call
+// still prepares is its head (mfma_head_kernel) — or, once per stream, the set itself, from the canonical period's constants.
+// (Both forms of the streaming kernel, K split or not; the one-tile-per-workgroup kernel keeps building its rows from its own positions.)
+static void matrix_plan_rows (const ArtFirArgs *a, const ArtSegTable *segs, MatrixPlan &p)
+{
+    MfmaGeom &g = p.g;
+    const int cgt = p.cgt;
+    p.a_v = *a;
+    ArtRowsTable &tb = p.tb; tb.on = 0; tb.lin = tb.w = 0; tb.n0 = 0u; tb.base = 0.0;
+    p.rows_ready = p.on_kept_rows = false; p.rc_build = nullptr; p.w_build = 0;
+    ArtRowsCache *rc = p.regular && g.head && artfir_rows_cache_enabled () && a->rows && artfir_f32_set_bytes (g) <= a->rows_bytes ? (ArtRowsCache *) a->rows_cache : nullptr;
+    HostPos pos0; int slot0 = 0, w = 0;
+    // (the virtual start's window inside the head's zero frames — head_pad covers a whole period's input: every tile of the launch's first period
+    // group is based on the virtual period's start, so it is slot 0's window that must lie inside, not only the first stored slot's)
+    if (rc && artfir_rows_canonical (a, segs, g.P, g.Q, rc, &pos0, &slot0, &w) &&
+        rc->c_ip [0] + w - a->T / 2 + 1 >= -g.head_pad) {
+        ArtFirArgs t = *a;
+        t.n_begin = a->n_begin + (unsigned int)(g.P - slot0); t.n_end = a->n_end + (unsigned int) g.P;
+        t.out = a->out - (size_t) g.P * a->C; t.n_skip = slot0;
+        MfmaGeom g2;
+        if (matrix_geometry (&t, g2) == cgt && g2.slot_tiles == g.slot_tiles && g2.ktot == g.ktot && (size_t) t.n_end * t.C * 4 < 0xffff0000ull) {
+            // (the tables in the set; the head stays in the call's scratch)
+            const size_t rows = (size_t) g.slot_tiles * 32, eff_bytes = rows * g.ktot * sizeof (float);
+            char *base = (char *) a->rows;
+            g2.eff = (float *) base;
+            g2.canon_frac = (double *)(base + ((eff_bytes + 15) & ~(size_t) 15));
+            g2.canon_ip = (int *)(g2.canon_frac + rows); g2.canon_fi = g2.canon_ip + rows; g2.tile_w0 = g2.canon_fi + rows;
+            g2.head = g.head; g2.head_frames = g.head_frames;
+            const bool same = rc->f_valid && rc->f_lowpass == a->lowpass && rc->f_slot_tiles == g.slot_tiles && rc->f_ktot == g.ktot;
+            if (same) { g2.w_shift = w - rc->f_w_build; p.rows_ready = true; }
+            else {
+                p.rc_build = rc; p.w_build = w;
+                g2.w_shift = 0;
+                tb.on = 1; tb.base = rc->c_base; tb.lin = rc->c_lin; tb.n0 = rc->c_n0; tb.w = w;
+            }
+            p.a_v = t; g = g2; p.on_kept_rows = true;
+        }
+    }
+}
+
+// the parts a regular launch's tiles are cut into (fir_mfma_split_kernel; 1: the un-split streaming kernel), the buffer for them looked at
+static int launch_split_parts (const ArtFirArgs *a, const MfmaGeom &g, int kernel_pref)
+{
+    const int tiles_per_xcd = g.groups_per_xcd * g.slot_tiles;
+    // (the rule looks at the launch's own outputs: the slots a launch on kept rows computes in front of its first do not count)
+    const int ks = a->split ? matrix_split_parts (a, g, a->n_end - a->n_begin - (unsigned int) a->n_skip, kernel_pref) : 1;
+    if (ks > 1 && (size_t) 8 * tiles_per_xcd * 16 <= ART_SPLIT_HEAD_BYTES &&
+        ART_SPLIT_HEAD_BYTES + (size_t) 8 * tiles_per_xcd * ks * 16 * MF_THREADS * sizeof (double) <= a->split_bytes) return ks;
+    return 1;
+}
+
+// Launch the matrix-core path for this call if it applies: returns ART_KERNEL_MFMA (| ART_FIR_ROLLED), -1 on a launch failure,
+// 0 when the call is for the general kernel.
+int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    MatrixPlan p;
+    const bool mfma_ok = matrix_plan_tiles (a, segs, kernel_pref, p);
 
     if (mfma_ok) {
-        MfmaGeom g;
-        const int cgt = matrix_geometry (a, g);
-        const bool ws = cgt != 0;                             // (generic channel counts: the non-specialised instantiation on the same tiles)
-        const bool wide = false;                              // (64-slot tiles, two m-tiles per X tile, lost: 156 VGPRs => one workgroup per CU, 29 vs 36 Gsamples/s in round 1; the template keeps the parameter, nothing instantiates it)
-        {   // carve the per-launch tables out of the scratch buffer
-            const size_t rows = (size_t) g.slot_tiles * g.tile_rows, eff_bytes = rows * g.ktot * sizeof (float);
-            char *base = (char *) a->scratch;
-            g.eff = (float *) base;
-            g.canon_frac = (double *)(base + ((eff_bytes + 15) & ~(size_t) 15));
-            g.canon_ip = (int *)(g.canon_frac + rows);
-            g.canon_fi = g.canon_ip + rows;
-            g.tile_w0 = g.canon_fi + rows;
-            if (!base || (size_t)((char *)(g.tile_w0 + 3 * g.slot_tiles) - base) > a->scratch_bytes) return 0;
-            g.head = nullptr; g.head_frames = 0;
-            if (ws && !wide) {
-                // the call's head as one contiguous array: everything a tile whose window starts inside the history can read
-                // (+ the two chunks the staging runs ahead)
-                const size_t used = (((size_t)((char *)(g.tile_w0 + 3 * g.slot_tiles) - base)) + 255) & ~(size_t) 255;
-                g.head_frames = g.head_pad + a->H + (g.ppw - 1) * g.Q + g.ktot + 3 * MF_KC;
-                if (used + (size_t) g.head_frames * a->C * sizeof (float) > a->scratch_bytes) return 0;
-                g.head = (float *)(base + used);
-            }
-        }
-        const unsigned int wg_threads = ws ? 2 * MF_THREADS : MF_THREADS;
-        const unsigned int roll_blocks = a->roll_dst ? (unsigned int)((a->H * a->C + wg_threads - 1) / wg_threads) : 0u;
-        dim3 grid ((unsigned int)(8 * g.groups_per_xcd * g.slot_tiles) + roll_blocks, (unsigned int)((a->C + g.cg - 1) / g.cg));
-
-        const bool regular = ws && !wide && launch_streams (a, segs, kernel_pref);
-        if (a->segs_truncated && !regular) return 0;          // (the tile kernel replays positions from the table: not beyond it)
+        MfmaGeom &g = p.g;
+        const int cgt = p.cgt;
+        const bool ws = p.ws, regular = p.regular;
+        const unsigned int roll_blocks = p.roll_blocks;
+        const dim3 grid = p.grid;
         // Fixed point on the integer matrix cores (fir_matrix_i8.hip) where the launch has its digit planes: staging pass + main
         // kernel, which carries the f32 tile loop as its own stand-by (a sample the digits cannot hold is only found on the
         // device) and takes the history roll along.  kernel_pref 6 pins the f32 kernel.
@@ -1176,44 +1365,14 @@ int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref
             const int i8 = artfir_i8_launch (a, segs, g, cgt, roll_blocks, st);       // 1: enqueued, 0: not for this launch, -1: failed part-way
             if (i8) return i8 > 0 && hipGetLastError () == hipSuccess ? (ART_KERNEL_MFMA | (a->roll_dst ? ART_FIR_ROLLED : 0)) : -1;
         }
-        // The f32 streaming kernel on rows kept across calls (fir_matrix_i8.hip, "The rows across calls": the same canonical period, one set of
-        // eff / canon_* / tile_w0 at the head of a->rows — no block alignment to honour): the launch is anchored on the canonical period
-        // (n_skip slots of its first period computed and not stored), the set's linear indices carried w_shift frames on, and all the call
-        // still prepares is its head (mfma_head_kernel) — or, once per stream, the set itself, from the canonical period's constants.
-        // (Both forms of the streaming kernel, K split or not; the one-tile-per-workgroup kernel keeps building its rows from its own positions.)
-        ArtFirArgs a_v = *a;
-        ArtRowsTable tb; tb.on = 0; tb.lin = tb.w = 0; tb.n0 = 0u; tb.base = 0.0;
-        bool rows_ready = false, on_kept_rows = false;
-        {
-            ArtRowsCache *rc = regular && g.head && artfir_rows_cache_enabled () && a->rows && artfir_f32_set_bytes (g) <= a->rows_bytes ? (ArtRowsCache *) a->rows_cache : nullptr;
-            HostPos pos0; int slot0 = 0, w = 0;
-            // (the virtual start's window inside the head's zero frames — head_pad covers a whole period's input: every tile of the launch's first period
-            // group is based on the virtual period's start, so it is slot 0's window that must lie inside, not only the first stored slot's)
-            if (rc && artfir_rows_canonical (a, segs, g.P, g.Q, rc, &pos0, &slot0, &w) &&
-                rc->c_ip [0] + w - a->T / 2 + 1 >= -g.head_pad) {
-                ArtFirArgs t = *a;
-                t.n_begin = a->n_begin + (unsigned int)(g.P - slot0); t.n_end = a->n_end + (unsigned int) g.P;
-                t.out = a->out - (size_t) g.P * a->C; t.n_skip = slot0;
-                MfmaGeom g2;
-                if (matrix_geometry (&t, g2) == cgt && g2.slot_tiles == g.slot_tiles && g2.ktot == g.ktot && (size_t) t.n_end * t.C * 4 < 0xffff0000ull) {
-                    // (the tables in the set; the head stays in the call's scratch)
-                    const size_t rows = (size_t) g.slot_tiles * 32, eff_bytes = rows * g.ktot * sizeof (float);
-                    char *base = (char *) a->rows;
-                    g2.eff = (float *) base;
-                    g2.canon_frac = (double *)(base + ((eff_bytes + 15) & ~(size_t) 15));
-                    g2.canon_ip = (int *)(g2.canon_frac + rows); g2.canon_fi = g2.canon_ip + rows; g2.tile_w0 = g2.canon_fi + rows;
-                    g2.head = g.head; g2.head_frames = g.head_frames;
-                    const bool same = rc->f_valid && rc->f_lowpass == a->lowpass && rc->f_slot_tiles == g.slot_tiles && rc->f_ktot == g.ktot;
-                    if (same) { g2.w_shift = w - rc->f_w_build; rows_ready = true; }
-                    else {
-                        rc->f_valid = 1; rc->f_w_build = w; rc->f_lowpass = a->lowpass; rc->f_slot_tiles = g.slot_tiles; rc->f_ktot = g.ktot;
-                        g2.w_shift = 0;
-                        tb.on = 1; tb.base = rc->c_base; tb.lin = rc->c_lin; tb.n0 = rc->c_n0; tb.w = w;
-                    }
-                    a_v = t; g = g2; on_kept_rows = true;
-                }
-            }
+        matrix_plan_rows (a, segs, p);
+        if (p.rc_build) {
+            ArtRowsCache *rc = p.rc_build;
+            rc->f_valid = 1; rc->f_w_build = p.w_build; rc->f_lowpass = a->lowpass; rc->f_slot_tiles = g.slot_tiles; rc->f_ktot = g.ktot;
         }
+        const ArtRowsTable &tb = p.tb;
+        const bool rows_ready = p.rows_ready, on_kept_rows = p.on_kept_rows;
+        const ArtFirArgs &a_v = p.a_v;
         // the cut-invariant policy runs anchored launches only: anything else is handed to the general kernel (0; the host counts it: resampleHipCutInvariantFallbacks)
         if (kernel_pref == ART_KERNEL_INVARIANT && !on_kept_rows) return 0;
         a = &a_v;
@@ -1241,10 +1400,8 @@ int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref
             const int wgs_per_xcd = tiles_per_xcd < resident ? tiles_per_xcd : resident;
             // launches of few tiles: a tile's K range as several work items (fir_mfma_split_kernel)
             const bool fixup = artfir_pass_fixup_wanted (a);
-            // (the rule looks at the launch's own outputs: the slots a launch on kept rows computes in front of its first do not count)
-            const int ks = a->split ? matrix_split_parts (a, g, a->n_end - a->n_begin - (unsigned int) a->n_skip, kernel_pref) : 1;
-            if (ks > 1 && (size_t) 8 * tiles_per_xcd * 16 <= ART_SPLIT_HEAD_BYTES &&
-                ART_SPLIT_HEAD_BYTES + (size_t) 8 * tiles_per_xcd * ks * 16 * MF_THREADS * sizeof (double) <= a->split_bytes) {
+            const int ks = launch_split_parts (a, g, kernel_pref);
+            if (ks > 1) {
                 const int items = tiles_per_xcd * ks;
                 const int wgs = items < resident ? items : resident;
                 const dim3 kgrid ((unsigned int)(8 * wgs) + roll_blocks);
@@ -1288,6 +1445,135 @@ int artfir_matrix (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref
         return hipGetLastError () == hipSuccess ? (ART_KERNEL_MFMA | (a->roll_dst ? ART_FIR_ROLLED : 0)) : -1;
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Many calls of one shape in one launch (the batch entries; art_internal.h: arthip_fir_group_plan / arthip_fir_group).
+// ---------------------------------------------------------------------------------------------------
+static_assert (sizeof (MfmaGeom) <= sizeof (((ArtFirGroupCall *) nullptr)->geom), "ArtFirGroupCall.geom holds the launch's MfmaGeom");
+static_assert (sizeof (MfmaGroupItem) % 8 == 0, "the items' pointers stay aligned in the table");
+
+static bool group_enabled ()
+{
+    static const bool on = [] { const char *e = getenv ("ARTAMD_BATCH_MATRIX"); return !(e && *e == '0'); } ();
+    return on;
+}
+static inline const MfmaGeom &geom_of (const ArtFirGroupCall *c) { return *reinterpret_cast<const MfmaGeom *> (c->geom.bytes); }
+
+// Would the single call make this one as ONE regular, un-split fir_mfma_stream_kernel launch on kept rows whose set is built — the plain
+// instantiation, the pass-through pass behind it where the stream wants one?  Then (1) *out is that launch: its arguments anchored on the
+// canonical period, its geometry.  Nothing is enqueued.  What the question does to the context's host-side cache is what the single
+// launch's own look-ups do (artfir_rows_touch, artfir_rows_canonical: the same answers however often they are asked), so a call that is
+// declined here (0) goes on to its single launch as if it had not been asked.
+int artfir_group_plan (const ArtFirArgs *a, const ArtSegTable *segs, int kernel_pref, ArtFirGroupCall *out)
+{
+    if (!group_enabled () || a->n_end <= a->n_begin || a->ev_start || a->ev_stop || a->pad) return 0;
+    artfir_rows_touch (a, segs);
+    MatrixPlan p;
+    if (!matrix_plan_tiles (a, segs, kernel_pref, p) || !p.regular || p.cgt != a->C) return 0;
+    if (!ART_PREF_PINS_F32 (kernel_pref) && a->planes) return 0;             // (the fixed-point kernel's call)
+    matrix_plan_rows (a, segs, p);
+    if (!p.on_kept_rows || !p.rows_ready) return 0;                           // (a stream's first matrix launch builds the set: a single call)
+    if (launch_split_parts (&p.a_v, p.g, kernel_pref) != 1) return 0;
+    const int fixup = artfir_pass_fixup_wanted (&p.a_v) ? 1 : 0;
+    if (!a->interpolate && !a->lowpass && !fixup) return 0;                   // (the PASS instantiation's launch)
+    out->a = p.a_v;
+    out->cls = -1; out->fixup = fixup;
+    std::memcpy (out->geom.bytes, &p.g, sizeof (MfmaGeom));
+    return 1;
+}
+
+int artfir_group_same_class (const ArtFirGroupCall *x, const ArtFirGroupCall *y)
+{
+    const MfmaGeom &g = geom_of (x), &h = geom_of (y);
+    return x->a.interpolate == y->a.interpolate && x->a.C == y->a.C && x->a.T == y->a.T && g.P == h.P && g.Q == h.Q && g.ktot == h.ktot &&
+           g.slot_tiles == h.slot_tiles && g.band_lo == h.band_lo && g.band_hi == h.band_hi && x->fixup == y->fixup &&
+           g.head_frames == h.head_frames && g.head_pad == h.head_pad;
+}
+
+size_t artfir_group_table_bytes (int n) { return (size_t)(n > 0 ? n : 0) * (sizeof (MfmaGroupItem) + sizeof (unsigned int) + 32); }
+
+template <int CG>
+static void group_launch_class (const MfmaGroupClass &cls, int interpolate, unsigned int head_blocks, const unsigned int *d_first, const MfmaGroupItem *d_items, hipStream_t st)
+{
+    hipLaunchKernelGGL (mfma_head_group_kernel, dim3 (head_blocks * (unsigned int) cls.items), dim3 (256), 0, st, d_items, cls.H, CG, (int) head_blocks);
+    const dim3 grid ((unsigned int)(8 * cls.wgs_per_xcd) + (unsigned int) cls.items * (unsigned int) cls.roll_blocks);
+    if (interpolate) hipLaunchKernelGGL ((fir_mfma_group_kernel<true, CG>), grid, dim3 (2 * MF_THREADS), 0, st, cls, d_first, d_items);
+    else hipLaunchKernelGGL ((fir_mfma_group_kernel<false, CG>), grid, dim3 (2 * MF_THREADS), 0, st, cls, d_first, d_items);
+}
+
+// The planned calls, class by class (ArtFirGroupCall.cls: 0 .. classes - 1, every class's calls of one shape): one table for all of them, uploaded
+// once; per class one head launch, one main launch with the history rolls, and the pass-through pass of each of its calls where the class wants it
+// (one small launch per call: ~2 us of launch overhead each on the stream, no dependence between them).  0, or -1: before the upload, nothing was enqueued; where a later class's launch
+// fails, the earlier classes' launches are on the stream — they wrote outputs and the history sides no context has switched to, and the caller commits nobody.
+int artfir_group (const ArtFirGroupCall *calls, int n, void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    if (n <= 0) return 0;
+    if (!d_table || artfir_test_fail ()) return -1;
+    int classes = 0;
+    for (int i = 0; i < n; ++i) { if (calls [i].cls < 0) return -1; if (calls [i].cls >= classes) classes = calls [i].cls + 1; }
+    char *table = (char *) malloc (artfir_group_table_bytes (n));
+    MfmaGroupClass *cl = (MfmaGroupClass *) calloc ((size_t) classes, sizeof (MfmaGroupClass));
+    size_t *off_first = (size_t *) malloc (sizeof (size_t) * 2 * (size_t) classes), *off_items = off_first ? off_first + classes : nullptr;
+    if (!table || !cl || !off_first) { free (table); free (cl); free (off_first); return -1; }
+    size_t bytes = 0;
+    for (int c = 0; c < classes; ++c) {
+        int m = 0;
+        for (int i = 0; i < n; ++i) m += calls [i].cls == c;
+        off_first [c] = bytes; bytes += (((size_t) m + 1) * sizeof (unsigned int) + 15) & ~(size_t) 15;
+        off_items [c] = bytes; bytes += (size_t) m * sizeof (MfmaGroupItem);
+        unsigned int *first = (unsigned int *)(table + off_first [c]);
+        MfmaGroupItem *items = (MfmaGroupItem *)(table + off_items [c]);
+        unsigned int tiles = 0; int k = 0;
+        for (int i = 0; i < n; ++i) {
+            if (calls [i].cls != c) continue;
+            const ArtFirArgs &a = calls [i].a;
+            const MfmaGeom &g = geom_of (&calls [i]);
+            if (k == 0) {
+                cl [c].P = g.P; cl [c].Q = g.Q; cl [c].ktot = g.ktot; cl [c].slot_tiles = g.slot_tiles; cl [c].band_lo = g.band_lo; cl [c].band_hi = g.band_hi;
+                cl [c].H = a.H; cl [c].roll_blocks = (a.H * a.C + 2 * MF_THREADS - 1) / (2 * MF_THREADS);
+                if (cl [c].roll_blocks < 1) cl [c].roll_blocks = 1;
+            }
+            MfmaGroupItem &it = items [k];
+            it.in = a.in; it.hist = a.hist; it.eff = g.eff; it.head = g.head; it.out = a.out; it.roll_dst = a.roll_dst; it.tile_w0 = g.tile_w0;
+            it.n_begin = a.n_begin; it.n_end = a.n_end;
+            it.n_skip = a.n_skip; it.in_frames = a.in_frames; it.w_shift = g.w_shift; it.head_frames = g.head_frames; it.head_pad = g.head_pad;
+            it.roll_appended = a.roll_appended;
+            first [k++] = tiles;
+            // the item's tiles that hold an output: every slot tile of all period groups but the last, the last one's up to the launch's end
+            const unsigned int total = a.n_end - a.n_begin, rest = total - (unsigned int)(g.period_groups - 1) * (unsigned int) g.ppw * (unsigned int) g.P;
+            const unsigned int last = (rest + 31u) / 32u < (unsigned int) g.slot_tiles ? (rest + 31u) / 32u : (unsigned int) g.slot_tiles;
+            tiles += (unsigned int)(g.period_groups - 1) * (unsigned int) g.slot_tiles + last;
+        }
+        first [k] = tiles;
+        cl [c].items = m; cl [c].tiles = (int) tiles; cl [c].tiles_per_xcd = (int)((tiles + 7u) / 8u);
+        // (as many workgroups as stay resident, as the single launch: artfir_matrix)
+        cl [c].wgs_per_xcd = cl [c].tiles_per_xcd < 94 ? cl [c].tiles_per_xcd : 94;
+        if (tiles == 0u || tiles > 0x3fffffffu) { free (table); free (cl); free (off_first); return -1; }
+    }
+    int rc = arthip_table_upload (table, bytes, d_table, stream);
+    for (int c = 0; c < classes && !rc; ++c) {
+        const ArtFirGroupCall *lead = nullptr;
+        for (int i = 0; i < n && !lead; ++i) if (calls [i].cls == c) lead = &calls [i];
+        const unsigned int *d_first = (const unsigned int *)((char *) d_table + off_first [c]);
+        const MfmaGroupItem *d_items = (const MfmaGroupItem *)((char *) d_table + off_items [c]);
+        const unsigned int hb = (unsigned int)(((size_t) geom_of (lead).head_frames * lead->a.C + 255) / 256);
+        switch (lead->a.C) {
+            case 32: group_launch_class<32> (cl [c], lead->a.interpolate, hb, d_first, d_items, st); break;
+            case 16: group_launch_class<16> (cl [c], lead->a.interpolate, hb, d_first, d_items, st); break;
+            case 8:  group_launch_class<8>  (cl [c], lead->a.interpolate, hb, d_first, d_items, st); break;
+            case 4:  group_launch_class<4>  (cl [c], lead->a.interpolate, hb, d_first, d_items, st); break;
+            case 2:  group_launch_class<2>  (cl [c], lead->a.interpolate, hb, d_first, d_items, st); break;
+            default: group_launch_class<1>  (cl [c], lead->a.interpolate, hb, d_first, d_items, st);
+        }
+        if (lead->fixup)
+            for (int i = 0; i < n && !rc; ++i)
+                if (calls [i].cls == c && artfir_pass_fixup (&calls [i].a, geom_of (&calls [i]), st)) rc = -1;
+        if (hipGetLastError () != hipSuccess) rc = -1;
+    }
+    free (table); free (cl); free (off_first);
+    return rc;
 }
 
 #endif  // !ART_WIDE

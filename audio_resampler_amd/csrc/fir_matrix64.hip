@@ -303,6 +303,11 @@ bool artfir_takes_matrix_path (const ArtFirArgs *a, const ArtSegTable *segs, int
 // kernel checks every output's position against it)
 void artfir_matrix_needs (const ArtFirArgs *, const ArtSegTable *, int, ArtFirNeeds *) { }
 void artfir_rows_touch (const ArtFirArgs *, const ArtSegTable *) { }
+// (no streaming kernel and no kept rows in this build: the batch entries keep making matrix-size calls one by one)
+int artfir_group_plan (const ArtFirArgs *, const ArtSegTable *, int, ArtFirGroupCall *) { return 0; }
+int artfir_group_same_class (const ArtFirGroupCall *, const ArtFirGroupCall *) { return 0; }
+size_t artfir_group_table_bytes (int) { return 0; }
+int artfir_group (const ArtFirGroupCall *, int n, void *, void *) { return n > 0 ? -1 : 0; }
 extern "C" {      // (the fixed-point kernel's rows across calls: 4-byte samples only)
 size_t arthip_fir_rows_cache_bytes (void) { return 0; }
 void arthip_fir_rows_cache_reset (void *) { }

@@ -3,9 +3,12 @@
 // code spilt ~500 registers in the f32 kernel — 0.022 -> 0.061 ms per 65,536-frame call; as text it compiles as it always did.)
 // Expects in scope: ArtFirArgs a; MfmaGeom g; int wgs_per_xcd; float As_ [2] [32 * MF_LD], Bs_ [2] [MF_COLS * MF_LD] (LDS);
 // template parameters / constants CG, PASS, THREADS, PPW, NCOLS; tid, lane, wave, loader, pt of an 8-wave workgroup.
+// MF_TILE_LIST defined: the includer brings the tile list itself (fir_mfma_group_kernel: the tiles of many launches of one shape, a and g
+// re-read from its item table by tile_at) — `rank`, the first tile of this workgroup, tile_at (within, st, jg), which also makes
+// a / g those of the tile's launch, and MF_COUNT_TILES (n), the tiles this workgroup walks; the tiles are `wgs_per_xcd` apart.
+#ifndef MF_TILE_LIST
     const int xcd = blockIdx.x & 7, rank = blockIdx.x >> 3;
     const int tiles_per_xcd = g.groups_per_xcd * g.slot_tiles;
-    const int nchunks = g.ktot / MF_KC;
 
     // tile `within` of this XCD's list -> (slot tile, period group); false past the last valid tile (validity is monotone)
     auto tile_at = [&] (int within, int &st, int &jg) -> bool {
@@ -14,6 +17,10 @@
         if (jg >= g.period_groups) return false;
         return a.n_begin + (unsigned int)(jg * PPW) * g.P + (unsigned int)(st * 32) < a.n_end;
     };
+#define MF_COUNT_TILES(n) { int st, jg; for (int w = rank; tile_at (w, st, jg); w += wgs_per_xcd) ++n; }
+#define MF_COUNT_TILES_OWN
+#endif
+    const int nchunks = g.ktot / MF_KC;
 
     if (NCOLS < MF_COLS)                                      // unused columns stay zero for the whole kernel
         for (int e = tid; e < (MF_COLS - NCOLS) * MF_LD; e += THREADS)
@@ -78,7 +85,7 @@
 
         // chunks this workgroup will consume in total (the matrix waves count the same way)
         int my_tiles = 0;
-        { int st, jg; for (int w = rank; tile_at (w, st, jg); w += wgs_per_xcd) ++my_tiles; }
+        MF_COUNT_TILES (my_tiles)
         const int total = my_tiles * nchunks;
         if (total == 0) return;
 
@@ -98,7 +105,7 @@
 
     // ---- matrix waves ----
     int my_tiles = 0;
-    { int st, jg; for (int w = rank; tile_at (w, st, jg); w += wgs_per_xcd) ++my_tiles; }
+    MF_COUNT_TILES (my_tiles)
     if (my_tiles == 0) return;
 
     const int arow = (lane & 31) * MF_LD + 4 * (lane >> 5);
@@ -145,3 +152,7 @@
                 __builtin_amdgcn_raw_buffer_store_b32 (__float_as_uint (y), rs_out, (int)(out_off + (unsigned int)(i_const * CG) * 4u), 0, 0);
         }
     }
+#ifdef MF_COUNT_TILES_OWN
+#undef MF_COUNT_TILES
+#undef MF_COUNT_TILES_OWN
+#endif

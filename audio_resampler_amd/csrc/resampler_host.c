@@ -76,6 +76,7 @@ struct artamd_resampler {
     int last_fixed [4];                      /* its last launch of the last call: flag value (0: none), mask words, chunks per tile, kernel form (art_hip.h) */
     unsigned int *d_fix; size_t fix_cap;    /* [0] per-launch, [1] running count of outputs the matrix kernels evaluated off-pattern */
     void *d_batch; size_t batch_cap;         /* argument table of the batched calls led by this context */
+    void *d_group; size_t group_cap;         /* ... and of their grouped matrix-core launches (both tables are in flight in one batch call) */
     art_s *d_tails; size_t tails_cap;        /* ... and the flush tails of every extrapolating context of such a call (resampleProcessAndFlushBatchInterleavedDevice) */
     void *d_sched; size_t sched_cap;         /* block and segment tables of the scheduled runs (resampleProcessScheduleInterleavedDevice) */
     unsigned long batch_stamp;               /* last batched call this context took part in (duplicate check) */
@@ -702,7 +703,7 @@ void resampleFree (Resample *cxt)
         bank_release (hip->bank); arthip_free (hip->d_hist [0]); arthip_free (hip->d_hist [1]);
         {   /* every device buffer the context may have grown (NULL where it never did) */
             void *const device_buffers [] = { hip->d_in, hip->d_out, hip->d_tmp, hip->d_fix, hip->d_scratch, hip->d_pad, hip->d_planes, hip->d_rows,
-                                              hip->d_split, hip->d_patch, hip->d_batch, hip->d_tails, hip->d_sched };
+                                              hip->d_split, hip->d_patch, hip->d_batch, hip->d_group, hip->d_tails, hip->d_sched };
             for (size_t i = 0; i < sizeof (device_buffers) / sizeof (device_buffers [0]); ++i) arthip_free (device_buffers [i]);
         }
         if (hip->rows_cache) { arthip_fir_rows_cache_free (hip->rows_cache); free (hip->rows_cache); }
@@ -1401,9 +1402,12 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
  * A service that resamples hundreds of streams in small blocks is launch-bound one call at a time.  This entry point
  * plans every context's call on the host exactly as the single call does, gathers those the general kernel would run
  * (any ratio per stream, default or EXTEND mode, ordinary call, on the stream of cxts [0]) into one launch per kernel
- * variant — each stream cut into the tiles its own launch would use, so the samples are identical — and simply makes
- * the remaining calls (flushes, strict mode, calls big enough for the matrix-core path, contexts under the cut-invariant
- * policy, other streams, a first output after a rewind) one by one.  The first output of an extrapolating stream is gathered
+ * variant — each stream cut into the tiles its own launch would use, so the samples are identical — gathers those the single call
+ * would make as one un-split launch of the f32 streaming matrix-core kernel on rows kept across calls (calls big enough for that path,
+ * every anchored call of a context under the cut-invariant policy) into one launch per shape (arthip_fir_group: the tiles of every
+ * such launch, unchanged, on one grid), and simply makes the remaining calls (flushes, strict mode, matrix-core calls of any other
+ * kind — a stream's first, which builds its rows, the fixed-point and K-split kernels', channel counts without a compiled width —,
+ * other streams, a first output after a rewind) one by one.  The first output of an extrapolating stream is gathered
  * too: its backward fits, for all such streams, are one launch in front of the FIR launches.  results [i] is what
  * resampleProcessInterleavedDevice (cxts [i], ...) would have returned. */
 /* A context whose ordinary calls may be gathered with others (batched streams, scheduled blocks): not sharded, and neither strict order,
@@ -1436,6 +1440,16 @@ typedef struct {
     int gathered, nruns, nlate;
 } BatchWork;
 
+/* ... and the calls it may run in grouped matrix-core launches: the planned launch (arthip_fir_group_plan), position and owner of each */
+typedef struct {
+    ArtFirGroupCall *calls; ArtamdPosition *trials; int *owner;
+    int gathered;
+} MatrixWork;
+
+/* A grouped matrix-core launch has at least this many calls; the calls of a smaller class are made one by one (a class of one: no table
+ * upload for nothing) */
+#define MATRIX_GROUP_MIN 2
+
 /* room for n calls and run_cap runs of either kind (0: none — extrapolating calls are then made one by one); 0 or -1 */
 static int batch_work_init (BatchWork *w, int n, size_t run_cap)
 {
@@ -1460,8 +1474,28 @@ static void batch_work_free (BatchWork *w)
  * the context's other calls run on; it brings its forward tail fits (w->runs) and, when it makes the stream's first output, the prefill
  * over the samples ++ the tail (w->late).  (The flush call of an already flushed stream is the single call: behind the process phase it
  * has no output left to make.) */
+/* The planned call is not the general kernel's: may it run in a grouped matrix-core launch?  As the single call goes about it — the context's
+ * kept rows, what the launch needs, its buffers — up to the launch itself, which is only planned (1: at m's next place); 0: the single call's */
+static int batch_plan_matrix (Resample *cxt, ArtFirArgs *a, const ArtSegTable *tab, int nseg, const ResampleResult *res, const ArtamdPosition *trial, MatrixWork *m)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    ArtFirNeeds needs;
+    if (ART_WIDE || !m || !m->calls) return 0;
+    keep_rows (hip, a);
+    arthip_fir_needs (a, tab, res->output_generated, hip->kernel_pref, &needs);
+    /* (a call of more segments than its table holds: one launch only where the single call would try that first) */
+    if (!needs.matrix || (nseg > ART_MAX_SEGS && !needs.one_launch) || !provision (hip, &needs, a)) return 0;
+    a->roll_dst = res->input_used > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;
+    a->roll_appended = (int) res->input_used;
+    a->segs_truncated = nseg > ART_MAX_SEGS;
+    if (!arthip_fir_group_plan (a, tab, hip->kernel_pref, &m->calls [m->gathered])) return 0;
+    m->trials [m->gathered] = *trial;
+    return 1;
+}
+
+/* (returns 2 where the call was gathered for a grouped matrix-core launch instead: at m's next place; m NULL: never) */
 static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, int cap, double ratio, void *lead_stream, art_s *tail,
-                       BatchWork *w, ResampleResult *res)
+                       BatchWork *w, MatrixWork *m, ResampleResult *res)
 {
     struct artamd_resampler *hip = cxt->hip;
     ArtFirArgs *a = &w->args [w->gathered];
@@ -1479,15 +1513,19 @@ static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, 
 
     const int nseg = plan_segments (cxt, nIn, cap, ratio, trial, res, &lin_floor);      /* (out of memory: the one-by-one path reports it) */
     /* (a flush without an output still appends its half window to the history: an item of roll workgroups only) */
-    if (nseg < 0 || nseg > arthip_fir_batch_max_segments () || (res->output_generated == 0 && !is_flush)) return 0;
+    if (nseg < 0 || (res->output_generated == 0 && !is_flush)) return 0;
+    /* (the general kernel's gathered launch takes calls of a few segments; the matrix-core path's follows the lattice from the first table) */
+    if (nseg > arthip_fir_batch_max_segments () && (is_flush || !m)) return 0;
 
     const int extrapolated = is_flush && (cxt->flags & EXTRAPOLATE_ENDPOINTS);
     const int appended = is_flush ? T / 2 : (int) res->input_used;
     /* (enqueue_call's arguments: a flush reads its tail, T/2 frames, or no input frames at all) */
     fill_args (cxt, a, ratio, is_flush ? (extrapolated ? tail : NULL) : d_in, 0, is_flush ? (extrapolated ? T / 2 : 0) : (int) res->input_used, d_out, 0);
-    seg_table (hip, 0, nseg, lin_floor, tab);
+    seg_table (hip, 0, nseg < ART_MAX_SEGS ? nseg : ART_MAX_SEGS, lin_floor, tab);
     a->n_begin = hip->segs [0].first_output; a->n_end = res->output_generated;
-    if (!is_flush && !general_call (cxt, a, tab, res->output_generated)) return 0;
+    if (!is_flush && !general_call (cxt, a, tab, res->output_generated))
+        return !first && batch_plan_matrix (cxt, a, tab, nseg, res, trial, m) ? 2 : 0;
+    if (nseg > arthip_fir_batch_max_segments ()) return 0;
 
     a->roll_dst = appended > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;      /* the launch takes the history roll along */
     a->roll_appended = appended;
@@ -1516,19 +1554,64 @@ static int batch_launch (struct artamd_resampler *lead, const BatchWork *w)
 }
 
 /* ... and the contexts' positions, behind them (enqueue_call's commit) */
+static void commit_one (Resample *cxt, const ArtFirArgs *a, const ArtamdPosition *trial, int kernel)
+{
+    const int outputs = a->n_end > a->n_begin;
+    cxt->hip->last_gathered = 1;
+    if (a->roll_dst) { cxt->hip->cur ^= 1; cxt->hip->lin_origin += a->roll_appended; }
+    cxt->outputOffset = trial->outputOffset; cxt->inputIndex = trial->inputIndex;
+    cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (trial->flags & RESAMPLER_FLUSHED) |
+                 (outputs ? 0 : (cxt->flags & EXTRAPOLATE_PREFILL));
+    cxt->hip->floor_active = trial->floorActive;
+    if (outputs) cxt->hip->last_kernel = kernel;
+}
+
 static void batch_commit (Resample *const *cxts, const BatchWork *w)
 {
-    for (int k = 0; k < w->gathered; ++k) {
-        Resample *cxt = cxts [w->owner [k]];
-        const int outputs = w->args [k].n_end > w->args [k].n_begin;
-        cxt->hip->last_gathered = 1;
-        if (w->args [k].roll_dst) { cxt->hip->cur ^= 1; cxt->hip->lin_origin += w->args [k].roll_appended; }
-        cxt->outputOffset = w->trials [k].outputOffset; cxt->inputIndex = w->trials [k].inputIndex;
-        cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (w->trials [k].flags & RESAMPLER_FLUSHED) |
-                     (outputs ? 0 : (cxt->flags & EXTRAPOLATE_PREFILL));
-        cxt->hip->floor_active = w->trials [k].floorActive;
-        if (outputs) cxt->hip->last_kernel = ART_KERNEL_GENERAL;
+    for (int k = 0; k < w->gathered; ++k) commit_one (cxts [w->owner [k]], &w->args [k], &w->trials [k], ART_KERNEL_GENERAL);
+}
+
+/* The calls planned for grouped matrix-core launches: classes by shape; the calls of a class too small for a launch of its own are made one by
+ * one (the contexts stand where they stood), the others launched — one launch per class — and committed.  0, or -1: the grouped launches failed
+ * (nothing of them enqueued: their contexts' results { 0, 0 }, positions and histories untouched; counted, artamdErrorCount: -2). */
+static int batch_matrix (Resample *const *cxts, MatrixWork *m, const artsample_t *const *d_inputs, const int *numInputFrames,
+                         artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios, ResampleResult *results)
+{
+    struct artamd_resampler *lead = cxts [0]->hip;
+    const int n = m->gathered;
+    int *rep = malloc (sizeof (int) * 2 * (size_t) n), *count = rep ? rep + n : NULL;      /* a class's first call, its size */
+    int classes = 0, kept = 0, rc = 0;
+    if (!rep) {
+        for (int k = 0; k < n; ++k) m->calls [k].cls = -1;
     }
+    else for (int k = 0; k < n; ++k) {
+        int c = 0;
+        while (c < classes && !arthip_fir_group_same_class (&m->calls [rep [c]], &m->calls [k])) ++c;
+        if (c == classes) { rep [classes] = k; count [classes++] = 0; }
+        m->calls [k].cls = c; ++count [c];
+    }
+    /* the classes that are launched, renumbered 0 ..; their calls moved to the front */
+    for (int c = 0, next = 0; c < classes; ++c) rep [c] = count [c] >= MATRIX_GROUP_MIN ? next++ : -1;
+    for (int k = 0; k < n; ++k) {
+        const int i = m->owner [k], c = m->calls [k].cls < 0 ? -1 : rep [m->calls [k].cls];
+        if (c < 0) { results [i] = resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]); continue; }
+        m->calls [kept] = m->calls [k]; m->calls [kept].cls = c; m->trials [kept] = m->trials [k]; m->owner [kept++] = i;
+    }
+    free (rep);
+    if (kept) {
+        lead->d_group = arthip_grow (lead->d_group, &lead->group_cap, arthip_fir_group_table_bytes (kept));
+        if (!lead->d_group || arthip_fir_group (m->calls, kept, lead->d_group, lead->stream)) {
+            fprintf (stderr, "artamd: resample batch: grouped matrix-core launch failed: %s\n", arthip_last_error ());
+            artamd_note_failure ("resampler: grouped FIR launch failed");
+            for (int k = 0; k < kept; ++k) results [m->owner [k]].input_used = results [m->owner [k]].output_generated = 0;
+            rc = -2;                     /* (counted) */
+        }
+        else for (int k = 0; k < kept; ++k) {
+            /* (roll_dst and roll_appended of the anchored launch are the call's own) */
+            commit_one (cxts [m->owner [k]], &m->calls [k].a, &m->trials [k], ART_KERNEL_MFMA);
+        }
+    }
+    return rc;
 }
 
 static unsigned long *stamp_of (const void *cxt) { return &((const Resample *) cxt)->hip->batch_stamp; }
@@ -1539,16 +1622,22 @@ static int batch_process (Resample *const *cxts, int n, const artsample_t *const
 {
     struct artamd_resampler *lead = cxts [0]->hip;
     BatchWork w;
-    int rc = -1;
+    MatrixWork m;
+    int rc = -1, failed = 0;
 
     size_t channels = 0;                 /* (room for the prefill runs of every extrapolating stream's first output: one per channel) */
     for (int i = 0; i < n; ++i)
         if ((cxts [i]->flags & EXTRAPOLATE_PREFILL) && !cxts [i]->hip->nshards) channels += (size_t) cxts [i]->numChannels;
+    memset (&m, 0, sizeof (m));
     if (batch_work_init (&w, n, channels)) goto out;
+    /* (without room for them the matrix-core calls are made one by one) */
+    m.calls = malloc (sizeof (ArtFirGroupCall) * (size_t) n); m.trials = malloc (sizeof (ArtamdPosition) * (size_t) n); m.owner = malloc (sizeof (int) * (size_t) n);
+    if (!m.calls || !m.trials || !m.owner) { free (m.calls); m.calls = NULL; }
 
     for (int i = 0; i < n; ++i) {
-        if (batch_plan (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i], lead->stream, NULL, &w, &results [i]))
-            w.owner [w.gathered++] = i;
+        const int how = batch_plan (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i], lead->stream, NULL, &w, &m, &results [i]);
+        if (how == 1) w.owner [w.gathered++] = i;
+        else if (how == 2) m.owner [m.gathered++] = i;
         else
             results [i] = resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]);
     }
@@ -1557,13 +1646,16 @@ static int batch_process (Resample *const *cxts, int n, const artsample_t *const
         /* the prefill fits of the first outputs, one launch in front of the FIR launches that read what they write */
         if (batch_launch (lead, &w)) {
             for (int k = 0; k < w.gathered; ++k) results [w.owner [k]].input_used = results [w.owner [k]].output_generated = 0;
-            goto out;
+            failed = -1;
         }
-        batch_commit (cxts, &w);
+        else batch_commit (cxts, &w);
     }
-    rc = 0;
+    /* (the matrix-core calls are made whatever became of the general kernel's launch: other contexts) */
+    rc = m.gathered ? batch_matrix (cxts, &m, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results) : 0;
+    if (failed) rc = failed;
 out:
     batch_work_free (&w);
+    free (m.calls); free (m.trials); free (m.owner);
     return rc;
 }
 
@@ -1577,7 +1669,7 @@ int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const a
     ENTER_DEVICE (lead);
     const int rc = batch_process (cxts, n, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results);
     LEAVE_DEVICE (lead);
-    return rc;
+    return rc ? -1 : 0;
 }
 
 /* ---- many whole clips, one launch per stage ------------------------------------------------------------------------
@@ -1617,7 +1709,7 @@ static int batch_flush (Resample *const *cxts, int n, const int *numInputFrames,
         art_s *out = d_outputs [i] + (size_t) results [i].output_generated * cxt->numChannels;
         const int extrapolates = (cxt->flags & EXTRAPOLATE_ENDPOINTS) && !cxt->hip->nshards;
 
-        if (batch_plan (cxt, NULL, -1, out, cap, ratios [i], lead->stream, extrapolates ? tail : out, &w, &w.res [w.gathered]))
+        if (batch_plan (cxt, NULL, -1, out, cap, ratios [i], lead->stream, extrapolates ? tail : out, &w, NULL, &w.res [w.gathered]))
             w.owner [w.gathered++] = i;
         else
             results [i].output_generated += resampleProcessInterleavedDevice (cxt, NULL, -1, out, cap, ratios [i]).output_generated;
@@ -1646,9 +1738,9 @@ int resampleProcessAndFlushBatchInterleavedDevice (Resample *const *cxts, int n,
     ENTER_DEVICE (lead);
     int rc = batch_process (cxts, n, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results);
     if (!rc) rc = batch_flush (cxts, n, numInputFrames, d_outputs, numOutputFrames, ratios, results);
-    if (rc) artamd_note_failure ("resampler: a launch of the batched process-and-flush failed");
+    if (rc == -1) artamd_note_failure ("resampler: a launch of the batched process-and-flush failed");      /* (-2: counted where it failed) */
     LEAVE_DEVICE (lead);
-    return rc;
+    return rc ? -1 : 0;
 }
 
 /* ---- consecutive blocks of one stream, one launch --------------------------------------------------------------------

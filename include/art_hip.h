@@ -122,10 +122,25 @@ ResampleResult resampleProcessAndFlushInterleavedDevice (Resample *cxt, const ar
  * ordinary call, on the stream of cxts [0]) share launches — a service with hundreds of small-block streams is
  * launch-bound one call at a time.  EXTRAPOLATE_ENDPOINTS streams share them too: an ordinary call after the first output is a
  * plain stream's, and the calls that make a first output put their backward LPC fits, all in one launch, in front of the FIR
- * launches.  All other calls (strict mode, flushes, a first output after a rewind of the position, calls large enough for the
- * matrix-core path, contexts under the cut-invariant policy, contexts on other streams) are simply made one by one —
- * a policy context's call, of any size, is the single call, anchored or counted as there.  A context may appear only once.  Asynchronous
- * like the single call: counts are returned at once, the samples land on the stream.  Returns 0, or -1 if a launch failed. */
+ * launches.  Matrix-core calls share launches too (4-byte build): a call that the single call would make as ONE un-split launch of the f32
+ * streaming kernel on the context's kept rows — a call large enough for the matrix-core path under kernel preference 6, or under 0 / 2 where
+ * that kernel is the library's own choice; every anchored call of a context under the cut-invariant policy, a 441-frame tick or a call
+ * shorter than one period included — runs with the other such calls of its shape in one grouped launch: the tiles its own launch would
+ * have run, on one grid.  (The intent: N streams pay one launch floor instead of N.  Not measured yet — DESIGN.md 4.6.)  Calls share a launch
+ * when they agree in interpolation, channels, taps, the period taken at a time (outputs and inputs), the tiles' K length, slot tiles and centre
+ * band, the head's length and zero pad, and whether the pass-through pass follows; the count is taken per such class after every call has been
+ * decided, and a class of fewer than two calls is made one by one.  resampleHipLastKernel then reads the matrix-core path's value and
+ * resampleHipLastGathered 1.
+ * All other calls are simply made one by one: strict mode, flushes, a first output after a rewind of the position, contexts on other
+ * streams or devices, sharded contexts, timing on — and the matrix-core calls of any other kind: a stream's first matrix launch (it builds
+ * the kept rows), calls for the fixed-point or the K-split kernel, launches that are not regular (the one-tile-per-workgroup kernel's), a
+ * nearest-filter stream without a low-pass whose launch substitutes its pass-through samples in the kernel's own epilogue (ARTAMD_PASS_FIXUP_MIN,
+ * periods of more than 8192 slots) instead of in the pass behind it, channel counts without a compiled width, device input not aligned to
+ * 16 bytes / one frame, resampleHipKeepRows (0), the 8-byte build.  A policy context's call that cannot run anchored is the single call,
+ * counted as there (resampleHipCutInvariantFallbacks): the policy's guarantee holds through this entry as through the single call.
+ * ARTAMD_BATCH_MATRIX=0 (read once) makes every matrix-core call one by one, as before.  A context may appear only once.  Asynchronous
+ * like the single call: counts are returned at once, the samples land on the stream.  Returns 0, or -1 if a launch failed (a failed grouped
+ * launch is counted in artamdErrorCount and leaves its contexts { 0, 0 }, positions and histories untouched). */
 int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                                            artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
                                            ResampleResult *results);
@@ -135,7 +150,8 @@ int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const a
  * whose output has no room left, is not flushed.  numInputFrames [i] == 0 with a NULL input is a pure flush.
  * First the ordinary calls, as resampleProcessBatchInterleavedDevice makes them (gathered or one by one).  Then the flushes: those of the
  * contexts that may share a launch (on the stream and device of cxts [0], not sharded, not strict order, timing off; the flush proper always
- * runs on the general kernel, so a clip long enough for the matrix-core path is processed singly and flushed with the others) are gathered —
+ * runs on the general kernel, so a clip long enough for the matrix-core path is processed there — in a grouped launch where the process
+ * phase gathers it, singly otherwise — and flushed with the others) are gathered —
  * the forward tail fits of ALL EXTRAPOLATE_ENDPOINTS contexts one launch, the prefills of the streams whose first output the flush makes a
  * second, the flushes' FIR with their history rolls a third — and the others (also the flush call of a stream that was flushed before) are
  * made as the single call.  Five launches for any number of gathered contexts of one shape (a FIR launch per kernel variant: channel

@@ -939,6 +939,21 @@ static void *timing_event (struct artamd_resampler *hip)
     return hip->ev [hip->ev_count++];
 }
 
+/* a launch's three timing events (before its first kernel — recorded here —, before its dominant kernel, after it: none without timing),
+ * and the three given back where the launch enqueued nothing (none of them is read) */
+static void take_events (struct artamd_resampler *hip, ArtFirArgs *a)
+{
+    void *ev_pre = hip->timing ? timing_event (hip) : NULL;
+    a->ev_start = hip->timing ? timing_event (hip) : NULL;
+    a->ev_stop = hip->timing ? timing_event (hip) : NULL;
+    if (ev_pre) arthip_event_record (ev_pre, hip->stream);
+}
+
+static void return_events (struct artamd_resampler *hip)
+{
+    if (hip->timing) hip->ev_count -= 3;
+}
+
 /* Did the last call's FIR run on the fixed-point matrix kernel?  0: no; 1: yes; 2: it was enqueued and stood down (a sample
  * outside (-1.98, 1.98) or not finite: the f32 kernel behind it produced the call).  *pairsPerChunk (optional): digit-pair
  * products issued per 32-tap chunk and 32 x 32 outputs, averaged over the tile families (5 .. 13: the products with a digit plane of
@@ -1042,16 +1057,6 @@ static int prefill_history_runs (const Resample *cxt, const art_s *d_in, long in
     return C;
 }
 
-static int prefill_history (Resample *cxt, const art_s *d_in, long in_pitch)
-{
-    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) cxt->numChannels);
-    if (!runs) return -1;
-    const int n = prefill_history_runs (cxt, d_in, in_pitch, runs);
-    const int rc = n ? arthip_extrapolate (runs, n, cxt->hip->stream) : 0;
-    free (runs);
-    return rc;
-}
-
 /* Forward extrapolation of half a window at flush time into `tail` (T/2 frames x C): the runs of one context, C of them, at `runs` */
 static int flush_tail_runs (const Resample *cxt, art_s *tail, ArtExtrapRun *runs)
 {
@@ -1065,20 +1070,6 @@ static int flush_tail_runs (const Resample *cxt, art_s *tail, ArtExtrapRun *runs
         runs [c].extras = half; runs [c].backward = 0;
     }
     return C;
-}
-
-/* ... into d_patch, launched; NULL on failure */
-static const art_s *flush_tail (Resample *cxt)
-{
-    struct artamd_resampler *hip = cxt->hip;
-    const int C = cxt->numChannels;
-
-    hip->d_patch = arthip_grow (hip->d_patch, &hip->patch_cap, sizeof (art_s) * (size_t)(cxt->numTaps / 2) * C);
-    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) C);
-    if (!hip->d_patch || !runs) { free (runs); return NULL; }
-    const int rc = arthip_extrapolate (runs, flush_tail_runs (cxt, hip->d_patch, runs), hip->stream);
-    free (runs);
-    return rc ? NULL : hip->d_patch;
 }
 
 /* The stream's FIRST output is produced by the flush call itself (fewer than T/2 frames ever arrived): the reference's
@@ -1103,16 +1094,6 @@ static int prefill_at_flush_runs (const Resample *cxt, const art_s *tail, ArtExt
         runs [c].extras = extra; runs [c].backward = 1;
     }
     return C;
-}
-
-static int prefill_at_flush (Resample *cxt)
-{
-    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * (size_t) cxt->numChannels);
-    if (!runs) return -1;
-    const int n = prefill_at_flush_runs (cxt, cxt->hip->d_patch, runs);
-    const int rc = n ? arthip_extrapolate (runs, n, cxt->hip->stream) : 0;
-    free (runs);
-    return rc;
 }
 
 static ResampleResult enqueue_call_layouts (Resample *cxt, const art_s *d_in, long in_pitch, int nIn, art_s *d_out, long out_pitch, int cap, double ratio);
@@ -1142,6 +1123,37 @@ static int plan_segments (Resample *cxt, int nIn, int cap, double ratio, ArtamdP
         if (!grown) return -1;
         hip->segs = grown; hip->seg_cap = nseg + 16;
     }
+}
+
+/* One context's call, planned: what the single call, the batch entries and the schedule all derive from the context and the call's
+ * arguments before anything is enqueued.  The segments themselves are in hip->segs until the context's next plan. */
+typedef struct {
+    ArtamdPosition trial;                    /* the position after the call */
+    ResampleResult res;                      /* the call's counts */
+    int nseg, lin_floor;
+    int is_flush, appended;                  /* a flush appends half a window (its tail, or silence) to the history, any other call the input it used */
+    /* the EXTRAPOLATE_ENDPOINTS fits due in front of the FIR launches */
+    int fit_prefill;                         /* backwards from (history ++ input), just before the stream's first output */
+    int fit_tail;                            /* forwards, the flush's half window */
+    int fit_late;                            /* backwards from the samples ++ that tail: the flush itself makes the first output */
+} CallPlan;
+
+/* returns the segment count, -1 out of memory */
+static int plan_one_call (Resample *cxt, int nIn, int cap, double ratio, CallPlan *p)
+{
+    const int T = cxt->numTaps;
+    p->is_flush = nIn < 0 && !(cxt->flags & RESAMPLER_FLUSHED);
+    p->nseg = plan_segments (cxt, nIn, cap, ratio, &p->trial, &p->res, &p->lin_floor);
+    if (p->nseg < 0) return -1;
+    p->appended = p->is_flush ? T / 2 : (int) p->res.input_used;
+    /* the prefill comes just before the first output of the stream (resampler.c:812-819), whichever call produces it: an ordinary call (a
+     * rewind right in front of output 0 leaves one known sample: nothing to extrapolate from), a flush continued after it was cut short, or
+     * the flush call itself (one that had to rewind the ring first leaves more than T known samples: nothing to prefill) */
+    const int first = (cxt->flags & EXTRAPOLATE_PREFILL) && p->res.output_generated;
+    p->fit_prefill = first && !p->is_flush && (p->nseg == 1 || cxt->hip->segs [1].first_output > 0);
+    p->fit_tail = p->is_flush && (cxt->flags & EXTRAPOLATE_ENDPOINTS);
+    p->fit_late = p->fit_tail && first && p->trial.inputIndex == cxt->inputIndex + T / 2;
+    return p->nseg;
 }
 
 /* segments [s0, s1) of the planned call as a launch's table */
@@ -1180,6 +1192,47 @@ static void fill_args (Resample *cxt, ArtFirArgs *a, double ratio, const art_s *
     if ((cxt->flags & RESAMPLE_STRICT_ORDER) && extend) a->mode |= 4;
     a->ratio = eff_ratio;
     a->period_out = hip->period_out; a->period_in = hip->period_in;
+}
+
+/* A planned call as ONE launch with its first table: every output, the history roll riding along.  A flush reads its extrapolated `tail`
+ * (T/2 frames) or, without one (NULL), no input frames at all: silence. */
+static void plan_args (Resample *cxt, const CallPlan *p, double ratio, const art_s *in, long in_pitch, art_s *out, long out_pitch, const art_s *tail,
+                       ArtFirArgs *a, ArtSegTable *tab)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    if (p->is_flush) fill_args (cxt, a, ratio, tail, 0, tail ? cxt->numTaps / 2 : 0, out, out_pitch);
+    else fill_args (cxt, a, ratio, in, in_pitch, (int) p->res.input_used, out, out_pitch);
+    seg_table (hip, 0, p->nseg < ART_MAX_SEGS ? p->nseg : ART_MAX_SEGS, p->lin_floor, tab);
+    a->n_begin = hip->segs [0].first_output; a->n_end = p->res.output_generated;
+    a->roll_dst = p->appended > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;
+    a->roll_appended = p->appended;
+}
+
+/* The fits due for a planned call, appended to the caller's lists: `late` reads what `early` writes (the flush's tail, T/2 x C frames at
+ * `tail`) and so is a second launch */
+static void plan_fits (const Resample *cxt, const CallPlan *p, const art_s *in, long in_pitch, art_s *tail,
+                       ArtExtrapRun *early, int *nearly, ArtExtrapRun *late, int *nlate)
+{
+    if (p->fit_prefill) *nearly += prefill_history_runs (cxt, in, in_pitch, early + *nearly);
+    if (p->fit_tail) *nearly += flush_tail_runs (cxt, tail, early + *nearly);
+    if (p->fit_late) *nlate += prefill_at_flush_runs (cxt, tail, late + *nlate);
+}
+
+/* ... of the single call, launched on its stream (the tail in d_patch); 0 or -1 */
+static int launch_fits (Resample *cxt, const CallPlan *p, const art_s *in, long in_pitch)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    const int C = cxt->numChannels;
+    ArtExtrapRun *runs = malloc (sizeof (ArtExtrapRun) * 2 * (size_t) C);      /* (C early, C late at most) */
+    int nearly = 0, nlate = 0, rc = -1;
+
+    if (p->fit_tail) hip->d_patch = arthip_grow (hip->d_patch, &hip->patch_cap, sizeof (art_s) * (size_t)(cxt->numTaps / 2) * C);
+    if (runs && (hip->d_patch || !p->fit_tail)) {
+        plan_fits (cxt, p, in, in_pitch, hip->d_patch, runs, &nearly, runs + C, &nlate);
+        rc = (nearly && arthip_extrapolate (runs, nearly, hip->stream)) || (nlate && arthip_extrapolate (runs + C, nlate, hip->stream)) ? -1 : 0;
+    }
+    free (runs);
+    return rc;
 }
 
 /* the canonical period of the rows the matrix kernels keep across calls: looked after by every launch of a rational-ratio stream,
@@ -1253,6 +1306,30 @@ static int rewind_lead (Resample *cxt, int nIn, int cap, double ratio)
     return 0;
 }
 
+/* A call's launches are enqueued: the context moves to the planned position (the prefill stays due until a call has made output), and
+ * the history ring to the buffer the roll wrote */
+static void commit_position (Resample *cxt, const ArtamdPosition *trial, int made_output)
+{
+    cxt->outputOffset = trial->outputOffset; cxt->inputIndex = trial->inputIndex;
+    cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (trial->flags & RESAMPLER_FLUSHED) |
+                 (made_output ? 0 : (cxt->flags & EXTRAPOLATE_PREFILL));
+    cxt->hip->floor_active = trial->floorActive;
+}
+
+static void commit_history (struct artamd_resampler *hip, int appended)
+{
+    if (appended > 0) { hip->cur ^= 1; hip->lin_origin += appended; }
+}
+
+/* nothing consumed, nothing made: results [k], or with `owner` results [owner [k]], k < n */
+static void zero_results (ResampleResult *results, const int *owner, int n)
+{
+    for (int k = 0; k < n; ++k) {
+        ResampleResult *r = &results [owner ? owner [k] : k];
+        r->input_used = r->output_generated = 0;
+    }
+}
+
 /* The first `frames` input frames of a call go into the history without any output being due (the caller established
  * that): position and ring epoch advance exactly as the reference's loop would have advanced them. */
 static int consume_silently (Resample *cxt, const art_s *d_in, long in_pitch, int frames, double ratio)
@@ -1267,9 +1344,8 @@ static int consume_silently (Resample *cxt, const art_s *d_in, long in_pitch, in
     if (res.output_generated || (int) res.input_used != frames) return -1;
 
     if (arthip_roll_history (hip->d_hist [hip->cur ^ 1], hip->d_hist [hip->cur], d_in, in_pitch, frames, H, C, hip->stream)) return -1;
-    hip->cur ^= 1; hip->lin_origin += frames;
-    cxt->outputOffset = pos.outputOffset; cxt->inputIndex = pos.inputIndex;
-    hip->floor_active = pos.floorActive;
+    commit_history (hip, frames);
+    commit_position (cxt, &pos, 0);
     return 0;
 }
 
@@ -1279,17 +1355,16 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
                                     art_s *d_out, long out_pitch, int cap, double ratio)
 {
     struct artamd_resampler *hip = cxt->hip;
-    const int T = cxt->numTaps, C = cxt->numChannels, H = HIST_FRAMES (T);
-    ResampleResult res = { 0, 0 };
-    ArtamdPosition trial;
-    int lin_floor;
-
-    const int is_flush = nIn < 0 && !(cxt->flags & RESAMPLER_FLUSHED);
-    int lead;
+    const int C = cxt->numChannels, H = HIST_FRAMES (cxt->numTaps);
+    CallPlan p;
+    ArtFirArgs a;
+    ArtSegTable tab;
+    int lead, rolled = 0;
 
     hip->last_gathered = 0;
     /* EXTRAPOLATE_ENDPOINTS, first output of the stream only after the ring has rewound: consumed silently up to it (rewind_lead) */
-    if (!is_flush && (lead = rewind_lead (cxt, nIn, cap, ratio)) > 0) {
+    if ((lead = rewind_lead (cxt, nIn, cap, ratio)) > 0) {
+        ResampleResult res = { 0, 0 };
         if (consume_silently (cxt, d_in, in_pitch, lead, ratio)) {
             fprintf (stderr, "artamd: end-point extrapolation: could not advance to the first output: %s\n", arthip_last_error ());
             return res;
@@ -1299,46 +1374,21 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
         return res;
     }
 
-    const int nseg = plan_segments (cxt, nIn, cap, ratio, &trial, &res, &lin_floor);
-    if (nseg < 0) { artamd_note_failure ("resampler: out of memory (segment table)"); res.input_used = res.output_generated = 0; return res; }
+    const int nseg = plan_one_call (cxt, nIn, cap, ratio, &p);
+    /* (a failure from here on: nothing of the stream has moved — the position and the history ring are committed below, behind the call's
+     * last launch —, a caller sees { 0, 0 }, the count in artamdErrorCount, and with ARTAMD_ABORT_ON_ERROR=1 the process stops there) */
+    const char *failure = nseg < 0 ? "resampler: out of memory (segment table)" : NULL;
+    if (!failure && (p.fit_prefill || p.fit_tail) && launch_fits (cxt, &p, d_in, in_pitch))
+        failure = "resampler: end-point extrapolation launch failed";
+    if (failure) goto failed;
 
-    const int appended = is_flush ? T / 2 : (int) res.input_used;
-    const art_s *flush_in = NULL;
-    int rolled = 0;
-
-    if (cxt->flags & EXTRAPOLATE_ENDPOINTS) {
-        /* prefill just before the first output of the stream (resampler.c:812-819), whichever call produces it: an
-         * ordinary call (a rewind right in front of output 0 leaves one known sample: nothing to extrapolate from), a
-         * flush continued after it was cut short, or — below — the flush call itself */
-        const int first_now = (cxt->flags & EXTRAPOLATE_PREFILL) && res.output_generated;
-        int failed = 0;
-        if (first_now && !is_flush && (nseg == 1 || hip->segs [1].first_output > 0))
-            failed = prefill_history (cxt, nIn > 0 ? d_in : NULL, in_pitch) != 0;
-        if (is_flush) {
-            flush_in = flush_tail (cxt);
-            failed = !flush_in;
-            /* (a flush that had to rewind the ring first leaves more than T known samples: nothing to prefill) */
-            if (!failed && first_now && trial.inputIndex == cxt->inputIndex + T / 2)
-                failed = prefill_at_flush (cxt) != 0;
-        }
-        if (failed) {
-            /* nothing of the stream has moved (as after a failed FIR launch): { 0, 0 } and the count in artamdErrorCount */
-            artamd_note_failure ("resampler: end-point extrapolation launch failed");
-            res.input_used = res.output_generated = 0; return res;
-        }
-    }
-
-    if (res.output_generated) {
-        ArtFirArgs a;
-        ArtSegTable tab;
-        fill_args (cxt, &a, ratio, is_flush ? flush_in : d_in, is_flush ? 0 : in_pitch, is_flush ? (flush_in ? T / 2 : 0) : (int) res.input_used,
-                   d_out, out_pitch);
-        if (!is_flush) keep_rows (hip, &a);
+    plan_args (cxt, &p, ratio, d_in, in_pitch, d_out, out_pitch, p.fit_tail ? hip->d_patch : NULL, &a, &tab);
+    if (p.res.output_generated) {
+        if (!p.is_flush) keep_rows (hip, &a);
         /* what the call's launches need (a flush runs on the general kernel) */
         ArtFirNeeds needs;
         memset (&needs, 0, sizeof (needs));
-        seg_table (hip, 0, nseg < ART_MAX_SEGS ? nseg : ART_MAX_SEGS, lin_floor, &tab);
-        if (!is_flush) arthip_fir_needs (&a, &tab, res.output_generated, hip->kernel_pref, &needs);
+        if (!p.is_flush) arthip_fir_needs (&a, &tab, p.res.output_generated, hip->kernel_pref, &needs);
         const int matrix = provision (hip, &needs, &a);
 
         /* A call of more ring epochs than a table holds (short filters: an epoch is a few hundred frames) is cut into launches of
@@ -1350,52 +1400,42 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
             const int s_tab = s0 + ART_MAX_SEGS < nseg ? s0 + ART_MAX_SEGS : nseg;     /* segments in this launch's table ... */
             const int s1 = whole ? nseg : s_tab;                                       /* ... and those it produces */
 
-            seg_table (hip, s0, s_tab, lin_floor, &tab);
+            if (s0) seg_table (hip, s0, s_tab, p.lin_floor, &tab);                     /* (the first is the plan's) */
             a.n_begin = hip->segs [s0].first_output;
-            a.n_end = s1 < nseg ? hip->segs [s1].first_output : res.output_generated;
+            a.n_end = s1 < nseg ? hip->segs [s1].first_output : p.res.output_generated;
             if (a.n_end > a.n_begin) {
-                void *ev_pre = hip->timing ? timing_event (hip) : NULL;
-                a.ev_start = hip->timing ? timing_event (hip) : NULL;
-                a.ev_stop = hip->timing ? timing_event (hip) : NULL;
-                if (ev_pre) arthip_event_record (ev_pre, hip->stream);
+                take_events (hip, &a);
                 /* the last FIR launch of the call may take the history roll along (one launch less on the stream) */
-                a.roll_dst = (s1 == nseg && appended > 0) ? hip->d_hist [hip->cur ^ 1] : NULL;
-                a.roll_appended = appended;
+                a.roll_dst = (s1 == nseg && p.appended > 0) ? hip->d_hist [hip->cur ^ 1] : NULL;
                 a.segs_truncated = whole;
                 int k = arthip_fir (&a, &tab, hip->kernel_pref, hip->stream);
                 a.segs_truncated = 0;
                 if (k == -2 && whole) {                /* (declined: nothing enqueued — again, cut) */
-                    if (hip->timing) hip->ev_count -= 3;        /* (the three events go back: only ev_pre was recorded, none is read) */
+                    return_events (hip);
                     whole = 0; s0 = -ART_MAX_SEGS; continue;
                 }
                 if (k >= 0 && (k & ART_FIR_ROLLED)) { rolled = 1; k &= ~ART_FIR_ROLLED; }
-                if (k < 0) {
-                    /* nothing of the stream has moved: the position and the history ring are committed below, behind the call's last
-                     * launch — a caller sees { 0, 0 }, the count in artamdErrorCount, and with ARTAMD_ABORT_ON_ERROR=1 the process stops here */
-                    artamd_note_failure ("resampler: FIR launch failed");
-                    res.input_used = res.output_generated = 0; return res;
-                }
+                if (k < 0) { failure = "resampler: FIR launch failed"; goto failed; }
                 hip->last_kernel = k;
                 /* the cut-invariant policy: a launch of a rational-ratio stream that could not run anchored on the matrix cores went to the general
                  * kernel — still independent of the cut by itself, but another arithmetic than the stream's other outputs: counted (art_hip.h) */
-                if (hip->kernel_pref == ART_KERNEL_INVARIANT && k == ART_KERNEL_GENERAL && a.period_out && a.mode == ART_MODE_FAST && !is_flush)
+                if (hip->kernel_pref == ART_KERNEL_INVARIANT && k == ART_KERNEL_GENERAL && a.period_out && a.mode == ART_MODE_FAST && !p.is_flush)
                     hip->invariant_fallbacks++;
             }
             if (whole) break;
         }
     }
 
-    if (appended > 0) {
-        if (!rolled)
-            arthip_roll_history (hip->d_hist [hip->cur ^ 1], hip->d_hist [hip->cur], is_flush ? flush_in : d_in, is_flush ? 0 : in_pitch, appended, H, C, hip->stream);
-        hip->cur ^= 1; hip->lin_origin += appended;
-    }
+    if (p.appended > 0 && !rolled)
+        arthip_roll_history (hip->d_hist [hip->cur ^ 1], hip->d_hist [hip->cur], a.in, a.in_pitch, p.appended, H, C, hip->stream);
+    commit_history (hip, p.appended);
+    commit_position (cxt, &p.trial, p.res.output_generated != 0);
+    return p.res;
 
-    cxt->outputOffset = trial.outputOffset; cxt->inputIndex = trial.inputIndex;
-    cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (trial.flags & RESAMPLER_FLUSHED) |
-                 ((res.output_generated == 0) ? (cxt->flags & EXTRAPOLATE_PREFILL) : 0);
-    hip->floor_active = trial.floorActive;
-    return res;
+failed:
+    artamd_note_failure (failure);
+    zero_results (&p.res, NULL, 1);
+    return p.res;
 }
 
 /* ---- many independent streams, one launch -------------------------------------------------------------------------
@@ -1410,12 +1450,13 @@ static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pi
  * other streams, a first output after a rewind) one by one.  The first output of an extrapolating stream is gathered
  * too: its backward fits, for all such streams, are one launch in front of the FIR launches.  results [i] is what
  * resampleProcessInterleavedDevice (cxts [i], ...) would have returned. */
-/* A context whose ordinary calls may be gathered with others (batched streams, scheduled blocks): not sharded, and neither strict order,
- * a flushed stream nor an extrapolating stream before its first output (those calls are made as they stand; after its first output an
- * extrapolating stream's ordinary calls are a plain stream's) */
-static int gatherable_context (const Resample *cxt)
+/* May a context's call be gathered with others (batched streams, scheduled blocks)?  Not a sharded context's, and neither in strict order
+ * nor on a flushed stream (those calls are made as they stand); a call that may bring fits — the flush of an extrapolating stream, an ordinary
+ * call before such a stream's first output (after it, its ordinary calls are a plain stream's) — only where there is room for their runs */
+static int gatherable (const Resample *cxt, int is_flush, int have_runs)
 {
-    return !cxt->hip->nshards && !(cxt->flags & (EXTRAPOLATE_PREFILL | RESAMPLE_STRICT_ORDER | RESAMPLER_FLUSHED));
+    if (cxt->hip->nshards || (cxt->flags & (RESAMPLE_STRICT_ORDER | RESAMPLER_FLUSHED))) return 0;
+    return have_runs || !(cxt->flags & (is_flush ? EXTRAPOLATE_ENDPOINTS : EXTRAPOLATE_PREFILL));
 }
 
 /* Does the single call give this planned call (its FIR arguments, first table, outputs) to the general kernel?  The cut-invariant policy keeps
@@ -1431,113 +1472,85 @@ static int general_call (const Resample *cxt, const ArtFirArgs *a, const ArtSegT
     return !needs.matrix;
 }
 
-/* What a batch call has gathered: the FIR arguments, table and planned position of each gathered call (`owner`: its index in the
- * caller's list), and the extrapolation runs in front of the FIR launch — `runs`, and `late`, which read what `runs` write (a flush:
- * the prefill of a stream whose first output the flush makes reads the tails) and so are a second launch. */
+/* What a batch call has gathered.  For the general kernel's launch: the FIR arguments, first table and plan of each gathered call (`owner`: its
+ * index in the caller's list), and the extrapolation runs in front of it — `runs`, and `late`, which read what `runs` write (a flush: the
+ * prefill of a stream whose first output the flush makes reads the tails) and so are a second launch.  For the grouped matrix-core launches: the
+ * planned launch (arthip_fir_group_plan), plan and owner of each call (`calls` NULL: no room, such calls are made one by one). */
 typedef struct {
-    ArtFirArgs *args; ArtSegTable *tabs; ArtamdPosition *trials; ResampleResult *res; int *owner;
-    ArtExtrapRun *runs, *late;
-    int gathered, nruns, nlate;
+    ArtFirArgs *args; ArtSegTable *tabs; CallPlan *plans; int *owner; int gathered;
+    ArtFirGroupCall *calls; CallPlan *matrix_plans; int *matrix_owner; int matrix_gathered;
+    ArtExtrapRun *runs, *late; int nruns, nlate;
 } BatchWork;
-
-/* ... and the calls it may run in grouped matrix-core launches: the planned launch (arthip_fir_group_plan), position and owner of each */
-typedef struct {
-    ArtFirGroupCall *calls; ArtamdPosition *trials; int *owner;
-    int gathered;
-} MatrixWork;
 
 /* A grouped matrix-core launch has at least this many calls; the calls of a smaller class are made one by one (a class of one: no table
  * upload for nothing) */
 #define MATRIX_GROUP_MIN 2
 
-/* room for n calls and run_cap runs of either kind (0: none — extrapolating calls are then made one by one); 0 or -1 */
-static int batch_work_init (BatchWork *w, int n, size_t run_cap)
+/* room for n calls on either list (`matrix` 0: none on the second) and run_cap runs of either kind (0: none — extrapolating calls are then made
+ * one by one); 0 or -1 */
+static int batch_work_init (BatchWork *w, int n, size_t run_cap, int matrix)
 {
     memset (w, 0, sizeof (*w));
     w->args = malloc (sizeof (ArtFirArgs) * (size_t) n); w->tabs = malloc (sizeof (ArtSegTable) * (size_t) n);
-    w->trials = malloc (sizeof (ArtamdPosition) * (size_t) n); w->res = malloc (sizeof (ResampleResult) * (size_t) n);
-    w->owner = malloc (sizeof (int) * (size_t) n);
+    w->plans = malloc (sizeof (CallPlan) * 2 * (size_t) n); w->owner = malloc (sizeof (int) * 2 * (size_t) n);
+    if (!w->args || !w->tabs || !w->plans || !w->owner) return -1;
+    w->matrix_plans = w->plans + n; w->matrix_owner = w->owner + n;
+    if (matrix) w->calls = malloc (sizeof (ArtFirGroupCall) * (size_t) n);
     if (run_cap && (w->runs = malloc (sizeof (ArtExtrapRun) * 2 * run_cap)) != NULL) w->late = w->runs + run_cap;
-    return w->args && w->tabs && w->trials && w->res && w->owner ? 0 : -1;
+    return 0;
 }
 
 static void batch_work_free (BatchWork *w)
 {
-    free (w->args); free (w->tabs); free (w->trials); free (w->res); free (w->owner); free (w->runs);
+    free (w->args); free (w->tabs); free (w->plans); free (w->owner); free (w->calls); free (w->runs);
 }
 
-/* Plan one context's call as the single call would; gather it at w's next place (1) if the general kernel is the single call's and the
- * context may share a launch, else leave the context as it stands (0: the caller makes the single call).  *res: the planned counts.
- * nIn >= 0, an ordinary call: an extrapolating stream's first output brings its prefill runs, as the single call would make them.
- * nIn < 0, a flush: gathered only with `tail` — room for the context's T/2 x C tail frames when it extrapolates, any non-NULL pointer
- * otherwise (the existing batch entry passes NULL: its flushes are single calls).  The flush proper runs on the general kernel whatever
- * the context's other calls run on; it brings its forward tail fits (w->runs) and, when it makes the stream's first output, the prefill
- * over the samples ++ the tail (w->late).  (The flush call of an already flushed stream is the single call: behind the process phase it
- * has no output left to make.) */
 /* The planned call is not the general kernel's: may it run in a grouped matrix-core launch?  As the single call goes about it — the context's
- * kept rows, what the launch needs, its buffers — up to the launch itself, which is only planned (1: at m's next place); 0: the single call's */
-static int batch_plan_matrix (Resample *cxt, ArtFirArgs *a, const ArtSegTable *tab, int nseg, const ResampleResult *res, const ArtamdPosition *trial, MatrixWork *m)
+ * kept rows, what the launch needs, its buffers — up to the launch itself, which is only planned (1: at w's next matrix place); 0: the single call's */
+static int batch_plan_matrix (Resample *cxt, ArtFirArgs *a, const ArtSegTable *tab, const CallPlan *p, BatchWork *w)
 {
     struct artamd_resampler *hip = cxt->hip;
     ArtFirNeeds needs;
-    if (ART_WIDE || !m || !m->calls) return 0;
+    if (ART_WIDE || !w->calls) return 0;
     keep_rows (hip, a);
-    arthip_fir_needs (a, tab, res->output_generated, hip->kernel_pref, &needs);
+    arthip_fir_needs (a, tab, p->res.output_generated, hip->kernel_pref, &needs);
     /* (a call of more segments than its table holds: one launch only where the single call would try that first) */
-    if (!needs.matrix || (nseg > ART_MAX_SEGS && !needs.one_launch) || !provision (hip, &needs, a)) return 0;
-    a->roll_dst = res->input_used > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;
-    a->roll_appended = (int) res->input_used;
-    a->segs_truncated = nseg > ART_MAX_SEGS;
-    if (!arthip_fir_group_plan (a, tab, hip->kernel_pref, &m->calls [m->gathered])) return 0;
-    m->trials [m->gathered] = *trial;
+    if (!needs.matrix || (p->nseg > ART_MAX_SEGS && !needs.one_launch) || !provision (hip, &needs, a)) return 0;
+    a->segs_truncated = p->nseg > ART_MAX_SEGS;
+    if (!arthip_fir_group_plan (a, tab, hip->kernel_pref, &w->calls [w->matrix_gathered])) return 0;
+    w->matrix_plans [w->matrix_gathered] = *p;
     return 1;
 }
 
-/* (returns 2 where the call was gathered for a grouped matrix-core launch instead: at m's next place; m NULL: never) */
-static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, int cap, double ratio, void *lead_stream, art_s *tail,
-                       BatchWork *w, MatrixWork *m, ResampleResult *res)
+/* Plan one context's call as the single call would; gather it at w's next place (1) if the general kernel is the single call's and the
+ * context may share a launch, at w's next matrix place (2) if a grouped matrix-core launch may run it, else leave the context as it stands
+ * (0: the caller makes the single call).
+ * nIn >= 0, an ordinary call: an extrapolating stream's first output brings its prefill runs, as the single call would make them.
+ * nIn < 0, a flush: `tail` is room for the context's T/2 x C tail frames when it extrapolates (NULL: none, the flush is the single call).
+ * The flush proper runs on the general kernel whatever the context's other calls run on; it brings its forward tail fits (w->runs) and,
+ * when it makes the stream's first output, the prefill over the samples ++ the tail (w->late).  (The flush call of an already flushed
+ * stream is the single call: behind the process phase it has no output left to make.) */
+static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, int cap, double ratio, void *lead_stream, art_s *tail, BatchWork *w)
 {
     struct artamd_resampler *hip = cxt->hip;
     ArtFirArgs *a = &w->args [w->gathered];
     ArtSegTable *tab = &w->tabs [w->gathered];
-    ArtamdPosition *trial = &w->trials [w->gathered];
-    const int T = cxt->numTaps, is_flush = nIn < 0;
-    const int first = (cxt->flags & (EXTRAPOLATE_PREFILL | RESAMPLER_FLUSHED)) == EXTRAPOLATE_PREFILL;
-    int lin_floor;
+    CallPlan *p = &w->plans [w->gathered];
+    const int is_flush = nIn < 0;
 
-    if ((is_flush && !tail) || hip->stream != lead_stream || hip->timing || hip->device != arthip_current_device ()) return 0;
-    if (is_flush) {
-        if (hip->nshards || (cxt->flags & (RESAMPLE_STRICT_ORDER | RESAMPLER_FLUSHED)) || ((cxt->flags & EXTRAPOLATE_ENDPOINTS) && !w->runs)) return 0;
-    }
-    else if (first ? (hip->nshards || (cxt->flags & RESAMPLE_STRICT_ORDER) || !w->runs || rewind_lead (cxt, nIn, cap, ratio)) : !gatherable_context (cxt)) return 0;
+    if (hip->stream != lead_stream || hip->timing || hip->device != arthip_current_device ()) return 0;
+    /* (a first output after a rewind is the single call's, which consumes the frames in front of it silently) */
+    if (!gatherable (cxt, is_flush, w->runs && (tail || !is_flush)) || rewind_lead (cxt, nIn, cap, ratio)) return 0;
 
-    const int nseg = plan_segments (cxt, nIn, cap, ratio, trial, res, &lin_floor);      /* (out of memory: the one-by-one path reports it) */
-    /* (a flush without an output still appends its half window to the history: an item of roll workgroups only) */
-    if (nseg < 0 || (res->output_generated == 0 && !is_flush)) return 0;
+    /* (out of memory: the one-by-one path reports it; a flush without an output still appends its half window to the history: an item of
+     * roll workgroups only) */
+    if (plan_one_call (cxt, nIn, cap, ratio, p) < 0 || (p->res.output_generated == 0 && !is_flush)) return 0;
+    plan_args (cxt, p, ratio, d_in, 0, d_out, 0, p->fit_tail ? tail : NULL, a, tab);
+    if (!is_flush && !general_call (cxt, a, tab, p->res.output_generated))
+        return !(cxt->flags & EXTRAPOLATE_PREFILL) && batch_plan_matrix (cxt, a, tab, p, w) ? 2 : 0;
     /* (the general kernel's gathered launch takes calls of a few segments; the matrix-core path's follows the lattice from the first table) */
-    if (nseg > arthip_fir_batch_max_segments () && (is_flush || !m)) return 0;
-
-    const int extrapolated = is_flush && (cxt->flags & EXTRAPOLATE_ENDPOINTS);
-    const int appended = is_flush ? T / 2 : (int) res->input_used;
-    /* (enqueue_call's arguments: a flush reads its tail, T/2 frames, or no input frames at all) */
-    fill_args (cxt, a, ratio, is_flush ? (extrapolated ? tail : NULL) : d_in, 0, is_flush ? (extrapolated ? T / 2 : 0) : (int) res->input_used, d_out, 0);
-    seg_table (hip, 0, nseg < ART_MAX_SEGS ? nseg : ART_MAX_SEGS, lin_floor, tab);
-    a->n_begin = hip->segs [0].first_output; a->n_end = res->output_generated;
-    if (!is_flush && !general_call (cxt, a, tab, res->output_generated))
-        return !first && batch_plan_matrix (cxt, a, tab, nseg, res, trial, m) ? 2 : 0;
-    if (nseg > arthip_fir_batch_max_segments ()) return 0;
-
-    a->roll_dst = appended > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;      /* the launch takes the history roll along */
-    a->roll_appended = appended;
-    /* (enqueue_call's conditions for the fits) */
-    if (first && !is_flush && (nseg == 1 || hip->segs [1].first_output > 0))
-        w->nruns += prefill_history_runs (cxt, nIn > 0 ? d_in : NULL, 0, w->runs + w->nruns);
-    if (extrapolated) {
-        w->nruns += flush_tail_runs (cxt, tail, w->runs + w->nruns);
-        /* (a flush that had to rewind the ring first leaves more than T known samples: nothing to prefill) */
-        if (first && res->output_generated && trial->inputIndex == cxt->inputIndex + T / 2)
-            w->nlate += prefill_at_flush_runs (cxt, tail, w->late + w->nlate);
-    }
+    if (p->nseg > arthip_fir_batch_max_segments ()) return 0;
+    plan_fits (cxt, p, d_in, 0, tail, w->runs, &w->nruns, w->late, &w->nlate);
     return 1;
 }
 
@@ -1553,63 +1566,56 @@ static int batch_launch (struct artamd_resampler *lead, const BatchWork *w)
     return -1;
 }
 
-/* ... and the contexts' positions, behind them (enqueue_call's commit) */
-static void commit_one (Resample *cxt, const ArtFirArgs *a, const ArtamdPosition *trial, int kernel)
+/* ... and the contexts' positions and histories, behind them */
+static void batch_commit (Resample *const *cxts, const CallPlan *plans, const int *owner, int n, int kernel)
 {
-    const int outputs = a->n_end > a->n_begin;
-    cxt->hip->last_gathered = 1;
-    if (a->roll_dst) { cxt->hip->cur ^= 1; cxt->hip->lin_origin += a->roll_appended; }
-    cxt->outputOffset = trial->outputOffset; cxt->inputIndex = trial->inputIndex;
-    cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (trial->flags & RESAMPLER_FLUSHED) |
-                 (outputs ? 0 : (cxt->flags & EXTRAPOLATE_PREFILL));
-    cxt->hip->floor_active = trial->floorActive;
-    if (outputs) cxt->hip->last_kernel = kernel;
-}
-
-static void batch_commit (Resample *const *cxts, const BatchWork *w)
-{
-    for (int k = 0; k < w->gathered; ++k) commit_one (cxts [w->owner [k]], &w->args [k], &w->trials [k], ART_KERNEL_GENERAL);
+    for (int k = 0; k < n; ++k) {
+        Resample *cxt = cxts [owner [k]];
+        const int made_output = plans [k].res.output_generated != 0;
+        cxt->hip->last_gathered = 1;
+        commit_history (cxt->hip, plans [k].appended);
+        commit_position (cxt, &plans [k].trial, made_output);
+        if (made_output) cxt->hip->last_kernel = kernel;
+    }
 }
 
 /* The calls planned for grouped matrix-core launches: classes by shape; the calls of a class too small for a launch of its own are made one by
  * one (the contexts stand where they stood), the others launched — one launch per class — and committed.  0, or -1: the grouped launches failed
  * (nothing of them enqueued: their contexts' results { 0, 0 }, positions and histories untouched; counted, artamdErrorCount: -2). */
-static int batch_matrix (Resample *const *cxts, MatrixWork *m, const artsample_t *const *d_inputs, const int *numInputFrames,
+static int batch_matrix (Resample *const *cxts, BatchWork *w, const artsample_t *const *d_inputs, const int *numInputFrames,
                          artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios, ResampleResult *results)
 {
     struct artamd_resampler *lead = cxts [0]->hip;
-    const int n = m->gathered;
+    ArtFirGroupCall *calls = w->calls;
+    const int n = w->matrix_gathered;
     int *rep = malloc (sizeof (int) * 2 * (size_t) n), *count = rep ? rep + n : NULL;      /* a class's first call, its size */
     int classes = 0, kept = 0, rc = 0;
     if (!rep) {
-        for (int k = 0; k < n; ++k) m->calls [k].cls = -1;
+        for (int k = 0; k < n; ++k) calls [k].cls = -1;
     }
     else for (int k = 0; k < n; ++k) {
         int c = 0;
-        while (c < classes && !arthip_fir_group_same_class (&m->calls [rep [c]], &m->calls [k])) ++c;
+        while (c < classes && !arthip_fir_group_same_class (&calls [rep [c]], &calls [k])) ++c;
         if (c == classes) { rep [classes] = k; count [classes++] = 0; }
-        m->calls [k].cls = c; ++count [c];
+        calls [k].cls = c; ++count [c];
     }
     /* the classes that are launched, renumbered 0 ..; their calls moved to the front */
     for (int c = 0, next = 0; c < classes; ++c) rep [c] = count [c] >= MATRIX_GROUP_MIN ? next++ : -1;
     for (int k = 0; k < n; ++k) {
-        const int i = m->owner [k], c = m->calls [k].cls < 0 ? -1 : rep [m->calls [k].cls];
+        const int i = w->matrix_owner [k], c = calls [k].cls < 0 ? -1 : rep [calls [k].cls];
         if (c < 0) { results [i] = resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]); continue; }
-        m->calls [kept] = m->calls [k]; m->calls [kept].cls = c; m->trials [kept] = m->trials [k]; m->owner [kept++] = i;
+        calls [kept] = calls [k]; calls [kept].cls = c; w->matrix_plans [kept] = w->matrix_plans [k]; w->matrix_owner [kept++] = i;
     }
     free (rep);
     if (kept) {
         lead->d_group = arthip_grow (lead->d_group, &lead->group_cap, arthip_fir_group_table_bytes (kept));
-        if (!lead->d_group || arthip_fir_group (m->calls, kept, lead->d_group, lead->stream)) {
+        if (!lead->d_group || arthip_fir_group (calls, kept, lead->d_group, lead->stream)) {
             fprintf (stderr, "artamd: resample batch: grouped matrix-core launch failed: %s\n", arthip_last_error ());
             artamd_note_failure ("resampler: grouped FIR launch failed");
-            for (int k = 0; k < kept; ++k) results [m->owner [k]].input_used = results [m->owner [k]].output_generated = 0;
+            zero_results (results, w->matrix_owner, kept);
             rc = -2;                     /* (counted) */
         }
-        else for (int k = 0; k < kept; ++k) {
-            /* (roll_dst and roll_appended of the anchored launch are the call's own) */
-            commit_one (cxts [m->owner [k]], &m->calls [k].a, &m->trials [k], ART_KERNEL_MFMA);
-        }
+        else batch_commit (cxts, w->matrix_plans, w->matrix_owner, kept, ART_KERNEL_MFMA);
     }
     return rc;
 }
@@ -1622,22 +1628,18 @@ static int batch_process (Resample *const *cxts, int n, const artsample_t *const
 {
     struct artamd_resampler *lead = cxts [0]->hip;
     BatchWork w;
-    MatrixWork m;
     int rc = -1, failed = 0;
 
     size_t channels = 0;                 /* (room for the prefill runs of every extrapolating stream's first output: one per channel) */
     for (int i = 0; i < n; ++i)
         if ((cxts [i]->flags & EXTRAPOLATE_PREFILL) && !cxts [i]->hip->nshards) channels += (size_t) cxts [i]->numChannels;
-    memset (&m, 0, sizeof (m));
-    if (batch_work_init (&w, n, channels)) goto out;
-    /* (without room for them the matrix-core calls are made one by one) */
-    m.calls = malloc (sizeof (ArtFirGroupCall) * (size_t) n); m.trials = malloc (sizeof (ArtamdPosition) * (size_t) n); m.owner = malloc (sizeof (int) * (size_t) n);
-    if (!m.calls || !m.trials || !m.owner) { free (m.calls); m.calls = NULL; }
+    if (batch_work_init (&w, n, channels, 1)) goto out;
 
     for (int i = 0; i < n; ++i) {
-        const int how = batch_plan (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i], lead->stream, NULL, &w, &m, &results [i]);
-        if (how == 1) w.owner [w.gathered++] = i;
-        else if (how == 2) m.owner [m.gathered++] = i;
+        /* (a flush handed to this phase is the single call) */
+        const int how = numInputFrames [i] < 0 ? 0 : batch_plan (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i], lead->stream, NULL, &w);
+        if (how == 1) { results [i] = w.plans [w.gathered].res; w.owner [w.gathered++] = i; }
+        else if (how == 2) { results [i] = w.matrix_plans [w.matrix_gathered].res; w.matrix_owner [w.matrix_gathered++] = i; }
         else
             results [i] = resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]);
     }
@@ -1645,17 +1647,16 @@ static int batch_process (Resample *const *cxts, int n, const artsample_t *const
     if (w.gathered) {
         /* the prefill fits of the first outputs, one launch in front of the FIR launches that read what they write */
         if (batch_launch (lead, &w)) {
-            for (int k = 0; k < w.gathered; ++k) results [w.owner [k]].input_used = results [w.owner [k]].output_generated = 0;
+            zero_results (results, w.owner, w.gathered);
             failed = -1;
         }
-        else batch_commit (cxts, &w);
+        else batch_commit (cxts, w.plans, w.owner, w.gathered, ART_KERNEL_GENERAL);
     }
     /* (the matrix-core calls are made whatever became of the general kernel's launch: other contexts) */
-    rc = m.gathered ? batch_matrix (cxts, &m, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results) : 0;
+    rc = w.matrix_gathered ? batch_matrix (cxts, &w, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results) : 0;
     if (failed) rc = failed;
 out:
     batch_work_free (&w);
-    free (m.calls); free (m.trials); free (m.owner);
     return rc;
 }
 
@@ -1697,7 +1698,7 @@ static int batch_flush (Resample *const *cxts, int n, const int *numInputFrames,
             channels += (size_t) cxts [i]->numChannels;
             tail_samples += (size_t)(cxts [i]->numTaps / 2) * cxts [i]->numChannels;
         }
-    if (batch_work_init (&w, n, channels)) goto out;
+    if (batch_work_init (&w, n, channels, 0)) goto out;
     /* (no tails: the extrapolating contexts' flushes are made one by one) */
     if (tail_samples) lead->d_tails = arthip_grow (lead->d_tails, &lead->tails_cap, sizeof (art_s) * tail_samples);
 
@@ -1709,7 +1710,7 @@ static int batch_flush (Resample *const *cxts, int n, const int *numInputFrames,
         art_s *out = d_outputs [i] + (size_t) results [i].output_generated * cxt->numChannels;
         const int extrapolates = (cxt->flags & EXTRAPOLATE_ENDPOINTS) && !cxt->hip->nshards;
 
-        if (batch_plan (cxt, NULL, -1, out, cap, ratios [i], lead->stream, extrapolates ? tail : out, &w, NULL, &w.res [w.gathered]))
+        if (batch_plan (cxt, NULL, -1, out, cap, ratios [i], lead->stream, extrapolates ? tail : NULL, &w))
             w.owner [w.gathered++] = i;
         else
             results [i].output_generated += resampleProcessInterleavedDevice (cxt, NULL, -1, out, cap, ratios [i]).output_generated;
@@ -1719,8 +1720,8 @@ static int batch_flush (Resample *const *cxts, int n, const int *numInputFrames,
     if (w.gathered) {
         /* (a failed launch: the flushes of its contexts were not made — their results are the process phase's, as after a failed single flush) */
         if (batch_launch (lead, &w)) goto out;
-        batch_commit (cxts, &w);
-        for (int k = 0; k < w.gathered; ++k) results [w.owner [k]].output_generated += w.res [k].output_generated;
+        batch_commit (cxts, w.plans, w.owner, w.gathered, ART_KERNEL_GENERAL);
+        for (int k = 0; k < w.gathered; ++k) results [w.owner [k]].output_generated += w.plans [k].res.output_generated;
     }
     rc = 0;
 out:
@@ -1766,19 +1767,19 @@ typedef struct {
 static int sched_gather (Resample *cxt, SchedRun *run, const art_s *in, int nIn, art_s *out, int cap, double ratio, ResampleResult *res, int k)
 {
     struct artamd_resampler *hip = cxt->hip;
-    ArtamdPosition trial;
+    CallPlan p;
     ArtFirArgs a;
     ArtSegTable tab;
-    int lin_floor;
 
-    if (!gatherable_context (cxt)) return 0;
-    const int nseg = plan_segments (cxt, nIn, cap, ratio, &trial, res, &lin_floor);
+    if (!gatherable (cxt, 0, 0)) return 0;
+    const int nseg = plan_one_call (cxt, nIn, cap, ratio, &p);
+    const int lin_floor = p.lin_floor;
     if (nseg < 0) return 0;                                              /* (out of memory: the single call reports it) */
+    *res = p.res;
     if (res->output_generated) {
-        fill_args (cxt, &a, ratio, in, 0, (int) res->input_used, out, 0);
-        a.lin_origin = hip->lin_origin + run->frames;
+        plan_args (cxt, &p, ratio, in, 0, out, 0, NULL, &a, &tab);
+        a.lin_origin = hip->lin_origin + run->frames;                    /* (the run's earlier blocks are not in the history yet) */
         keep_rows (hip, &a);
-        seg_table (hip, 0, nseg < ART_MAX_SEGS ? nseg : ART_MAX_SEGS, lin_floor, &tab);
         if (!general_call (cxt, &a, &tab, res->output_generated) || !arthip_fir_schedule_accepts (&a, hip->segs, nseg, res->output_generated)) return 0;
         if (run->nblocks == run->block_cap) {
             const int want = run->block_cap ? 2 * run->block_cap : 16;
@@ -1812,10 +1813,7 @@ static int sched_gather (Resample *cxt, SchedRun *run, const art_s *in, int nIn,
     if (!run->gathered++) { run->in = in; run->out = out; run->first = k; run->start = position_of (cxt); }
     hip->last_gathered = 1;
     run->frames += (int) res->input_used; run->outputs += res->output_generated;
-    cxt->outputOffset = trial.outputOffset; cxt->inputIndex = trial.inputIndex;
-    cxt->flags = (cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL)) | (trial.flags & RESAMPLER_FLUSHED) |
-                 ((res->output_generated == 0) ? (cxt->flags & EXTRAPOLATE_PREFILL) : 0);
-    hip->floor_active = trial.floorActive;
+    commit_position (cxt, &p.trial, res->output_generated != 0);
     return 1;
 }
 
@@ -1854,18 +1852,15 @@ static int sched_launch (Resample *cxt, SchedRun *run, ResampleResult *results)
         fill_args (cxt, &a, run->blocks [0].ratio, run->in, 0, run->frames, run->out, 0);
         a.roll_dst = run->frames > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;
         a.roll_appended = run->frames;
-        void *ev_pre = hip->timing ? timing_event (hip) : NULL;
-        a.ev_start = hip->timing ? timing_event (hip) : NULL;
-        a.ev_stop = hip->timing ? timing_event (hip) : NULL;
-        if (ev_pre) arthip_event_record (ev_pre, hip->stream);
+        take_events (hip, &a);
         hip->d_sched = arthip_grow (hip->d_sched, &hip->sched_cap, arthip_fir_schedule_bytes (run->nblocks, run->nsegs));
         const int k = hip->d_sched ? arthip_fir_schedule (&a, run->blocks, run->nblocks, run->segs, run->nsegs, hip->d_sched, hip->stream) : -1;
         if (k < 0) {
-            if (hip->timing) hip->ev_count -= 3;          /* (none of the three is read) */
+            return_events (hip);
             artamd_note_failure ("resampler: schedule launch failed");
             cxt->outputOffset = run->start.outputOffset; cxt->inputIndex = run->start.inputIndex;
             cxt->flags = run->start.flags; hip->floor_active = run->start.floorActive;
-            for (int i = run->first; i < run->first + run->gathered; ++i) results [i].input_used = results [i].output_generated = 0;
+            zero_results (results + run->first, NULL, run->gathered);
             run->gathered = run->nblocks = run->nsegs = run->frames = 0; run->outputs = 0;
             return -1;
         }
@@ -1873,10 +1868,8 @@ static int sched_launch (Resample *cxt, SchedRun *run, ResampleResult *results)
         hip->last_kernel = ART_KERNEL_GENERAL;
         hip->last_fixed [0] = 0;
     }
-    if (run->frames > 0) {
-        if (!rolled) arthip_roll_history (hip->d_hist [hip->cur ^ 1], hip->d_hist [hip->cur], run->in, 0, run->frames, H, C, hip->stream);
-        hip->cur ^= 1; hip->lin_origin += run->frames;
-    }
+    if (run->frames > 0 && !rolled) arthip_roll_history (hip->d_hist [hip->cur ^ 1], hip->d_hist [hip->cur], run->in, 0, run->frames, H, C, hip->stream);
+    commit_history (hip, run->frames);
     run->gathered = run->nblocks = run->nsegs = run->frames = 0; run->outputs = 0;
     return 0;
 }
@@ -1887,7 +1880,7 @@ int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, cons
 {
     if (numBlocks <= 0) return 0;
     for (int k = 0; k < numBlocks; ++k) if (numInputFrames [k] < 0) return -1;
-    for (int k = 0; k < numBlocks; ++k) results [k].input_used = results [k].output_generated = 0;
+    zero_results (results, NULL, numBlocks);
     struct artamd_resampler *hip = cxt->hip;
     const int C = cxt->numChannels;
     SchedRun run;
@@ -1907,7 +1900,7 @@ int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, cons
             const int errors = artamdErrorCount ();
             results [k] = flush ? resampleProcessAndFlushInterleavedDevice (cxt, in, numInputFrames [k], out, numOutputFrames [k], ratios [k])
                                 : resampleProcessInterleavedDevice (cxt, in, numInputFrames [k], out, numOutputFrames [k], ratios [k]);
-            if (artamdErrorCount () != errors) { results [k].input_used = results [k].output_generated = 0; failed = 1; break; }
+            if (artamdErrorCount () != errors) { zero_results (&results [k], NULL, 1); failed = 1; break; }
         }
         made = k + 1;
         if ((int) results [k].input_used != numInputFrames [k]) break;          /* a cap too small: no later block is made */
@@ -1941,7 +1934,7 @@ static ResampleResult shards_agree (Resample *cxt, const ResampleResult *per_sha
         if (per_shard [k].input_used != res.input_used || per_shard [k].output_generated != res.output_generated ||
             hip->shards [k]->inputIndex != first->inputIndex || hip->shards [k]->outputOffset != first->outputOffset) {
             fprintf (stderr, "artamd: sharded context: shard %d disagrees with shard 0 (a launch failed?)\n", k);
-            res.input_used = res.output_generated = 0;
+            zero_results (&res, NULL, 1);
         }
     cxt->outputOffset = first->outputOffset; cxt->inputIndex = first->inputIndex;
     cxt->flags = first->flags | RESAMPLE_MULTITHREADED;
@@ -2125,7 +2118,7 @@ static ResampleResult sharded_device_call (Resample *cxt, const art_s *d_in, lon
     if (prev >= 0) arthip_set_device (prev);
 
     res = shards_agree (cxt, per_shard);
-    if (failed) { artamd_note_failure ("resampler: sharded context: device allocation failed"); res.input_used = res.output_generated = 0; }
+    if (failed) { artamd_note_failure ("resampler: sharded context: device allocation failed"); zero_results (&res, NULL, 1); }
     return res;
 }
 
@@ -2234,7 +2227,7 @@ static void host_begin (Resample *cxt, const art_s *input, int in_stride, const 
     const char *limit_env = getenv ("ARTAMD_STAGE_LIMIT");
     const int staged = sizeof (art_s) * (in_samples + out_samples) <= (limit_env && *limit_env ? (size_t) strtoull (limit_env, NULL, 10) : STAGE_LIMIT);
 
-    pend->res.input_used = pend->res.output_generated = 0; pend->staged_out = 0; pend->failed = 1;
+    zero_results (&pend->res, NULL, 1); pend->staged_out = 0; pend->failed = 1;
     if (trace_on < 0) { const char *e = getenv ("ARTAMD_HOST_TRACE"); trace_on = e && *e && *e != '0'; if (trace_on) atexit (trace_report); }
     double trace_t_ = trace_on > 0 ? trace_now () : 0.0;
     trace_calls += trace_on > 0;

@@ -13,4 +13,5 @@ from .api import (  # noqa: F401
     RESAMPLE_STRICT_ORDER, DITHER_HIGHPASS, DITHER_FLAT, DITHER_LOWPASS, SHAPING_1ST_ORDER, SHAPING_2ND_ORDER,
     SHAPING_3RD_ORDER, SHAPING_ATH_CURVE, DECIMATE_MULTITHREADED, EXPORTED_SYMBOLS, wide, binding, decimate_batch_device,
     biquad_batch_device, ingest_batch_device, extrapolate_batch_device, process_and_flush_batch_device,
+    process_batch_device, process_batch_planar_device, process_and_flush_batch_planar_device, ClipResampler,
 )

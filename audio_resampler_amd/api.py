@@ -172,6 +172,9 @@ def _bind(width):
         "resampleProcessScheduleInterleavedDevice": (C.c_int, [RP, C.c_int, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "stretchProcessBatchDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr]),
         "stretchFlushBatchDevice": (C.c_int, [ptr, C.c_int, ptr, ptr]),
+        "resampleProcessAndFlushPlanarDevice": (ResampleResult, [RP, ptr, C.c_long, C.c_int, ptr, C.c_long, C.c_int, C.c_double]),
+        "resampleProcessBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
     }
 
     _state = {"lib": None}
@@ -367,6 +370,12 @@ def _bind(width):
             r = self.L.resampleProcessPlanarDevice(self.p, _dev_ptr(d_in), in_pitch, n_in, _dev_ptr(d_out), out_pitch, out_cap, ratio)
             return r.input_used, r.output_generated
 
+        def process_and_flush_planar_device(self, d_in, in_pitch, n_in, d_out, out_pitch, out_cap, ratio):
+            """resampleProcessAndFlushPlanarDevice: a whole clip in planes (pitches in samples, 0: that side interleaved); the flush writes
+            behind the process call's frames in every plane"""
+            r = self.L.resampleProcessAndFlushPlanarDevice(self.p, _dev_ptr(d_in), in_pitch, n_in, _dev_ptr(d_out), out_pitch, out_cap, ratio)
+            return r.input_used, r.output_generated
+
 
     class Decimator:
         def __init__(self, channels, bits, nbytes, gain, rate, flags):
@@ -477,6 +486,96 @@ def _bind(width):
         if rc:
             raise RuntimeError("resampleProcessAndFlushBatchInterleavedDevice failed")
         return [(r.input_used, r.output_generated) for r in res]
+
+    def _batch_planar(name, resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios):
+        n = len(resamplers)
+        ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])
+        res = (ResampleResult * n)()
+        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
+        rc = getattr(lib(), name)(
+            ctx, n, (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_ins]), pitches(in_pitches), (C.c_int * n)(*[int(v) for v in n_ins]),
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches), (C.c_int * n)(*[int(v) for v in out_caps]),
+            (C.c_double * n)(*[float(v) for v in ratios]), res)
+        if rc:
+            raise RuntimeError(name + " failed")
+        return [(r.input_used, r.output_generated) for r in res]
+
+    def process_batch_planar_device(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios):
+        """resampleProcessBatchPlanarDevice: process_batch_device with a pitch per buffer, in samples (channel c of item i at
+        d_ins[i] + c * in_pitches[i]; 0: that side of that item interleaved; None for a pitch list: every item's is).  Calls the single
+        planar call would stage are transposed by one launch in front of the FIR launches and one behind.
+        Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
+        return _batch_planar("resampleProcessBatchPlanarDevice", resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios)
+
+    def process_and_flush_batch_planar_device(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios):
+        """resampleProcessAndFlushBatchPlanarDevice: process_and_flush_batch_device on channels-first buffers (pitches as in
+        process_batch_planar_device; a d_ins entry may be None with n_ins 0: a pure flush).  The flushes write behind the process
+        calls' frames in every plane.  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
+        return _batch_planar("resampleProcessAndFlushBatchPlanarDevice", resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios)
+
+    class ClipResampler:
+        """Whole clips, channels-first, from one fixed rate to another: x [B, C, T] (or [C, T]) on the GPU in, (y [B, C, Tout_max],
+        out_lengths) out — one resampleProcessAndFlushBatchPlanarDevice call on the tensor's own rows, no copy of the samples on the way.
+        Clip i is what a fresh fixed-ratio context makes of x[i, :, :lengths[i]] with resampleProcessAndFlushPlanarDevice (its lead-in
+        of half a filter length included); y[i, :, out_lengths[i]:] is zero.  Holds a pool of up to max_batch contexts, reset for every
+        call; a larger batch is made max_batch clips at a time."""
+
+        def __init__(self, channels, src_rate, dst_rate, taps=380, filters=380, flags=BLACKMAN_HARRIS | SUBSAMPLE_INTERPOLATE | INCLUDE_LOWPASS,
+                     max_batch=1024):
+            self.channels, self.taps, self.max_batch = channels, taps, max(1, int(max_batch))
+            self._init = (channels, taps, filters, 0.0, flags, (float(src_rate), float(dst_rate), 0))
+            self.ratio = float(dst_rate) / float(src_rate)
+            self.pool = []
+            self._expected = {}                                  # clip length -> the process call's output frames (a dry run on a reset context)
+
+        def close(self):
+            for r in self.pool:
+                r.close()
+            self.pool = []
+
+        def _room(self, frames):
+            """output frames a clip of `frames` frames can make: the process call's (resampleGetExpectedOutput, the context just reset)
+            plus the flush's share — half a window of appended silence at the stream's ratio, rounded up, with a few frames to spare (the dry run steps the position by addition, the call by division)"""
+            if frames not in self._expected:
+                self._expected[frames] = lib().resampleGetExpectedOutput(self.pool[0].p, frames, self.ratio)
+            return self._expected[frames] + int(self.taps / 2 * self.ratio) + 4
+
+        def __call__(self, x, lengths=None):
+            import torch
+            if x.dim() == 2:
+                x = x.unsqueeze(0)
+            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
+                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
+            if x.shape[2] and x.stride(2) != 1:
+                x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
+            B, Cn, T = x.shape
+            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
+                raise ValueError("lengths: one entry per clip, 0 .. T")
+            while len(self.pool) < min(B, self.max_batch):
+                self.pool.append(Resampler(*self._init[:5], fixed=self._init[5]))
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            for r in self.pool[:min(B, self.max_batch)]:
+                r.set_stream(stream)
+                r.reset()
+            rooms = [self._room(v) for v in lengths]
+            y = torch.zeros(B, Cn, max(rooms, default=0), dtype=x.dtype, device=x.device)
+            size = x.element_size()
+            xp, yp = x.data_ptr(), y.data_ptr()
+            in_pitch, out_pitch = (x.stride(1), y.stride(1)) if Cn > 1 else (0, 0)      # (one channel: the same call in either layout)
+            made = []
+            for b0 in range(0, B, self.max_batch):
+                idx = range(b0, min(B, b0 + self.max_batch))
+                if b0:
+                    for r in self.pool[:len(idx)]:
+                        r.reset()
+                got = process_and_flush_batch_planar_device(
+                    self.pool[:len(idx)], [xp + i * x.stride(0) * size for i in idx], [in_pitch] * len(idx), [lengths[i] for i in idx],
+                    [yp + i * y.stride(0) * size for i in idx], [out_pitch] * len(idx), [rooms[i] for i in idx],
+                    [self.ratio] * len(idx))
+                made += [g for _, g in got]
+            out_lengths = torch.tensor(made, dtype=torch.int64)
+            return y[:, :, :max(made, default=0)], out_lengths
 
     def decimate_batch_device(decimators, d_ins, n_ins, d_outs):
         """decimateProcessBatchInterleavedLEDevice over a list of Decimator objects: one launch per class of work for the

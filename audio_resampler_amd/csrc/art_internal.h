@@ -226,6 +226,19 @@ int arthip_roll_history (art_s *new_hist, const art_s *hist, const art_s *in, lo
 int arthip_interleave (art_s *dst, const art_s *src_planar, long pitch, int frames, int C, void *stream);
 int arthip_deinterleave (art_s *dst_planar, long pitch, const art_s *src, int frames, int C, void *stream);
 
+/* ---- layout_kernels.hip: the same two copies for many buffers in one launch (transpose_group_kernel) ---- */
+typedef struct {
+    art_s *planes;                       /* the planar side: channel c at planes + c * pitch */
+    art_s *frames;                       /* the interleaved side: [frame][C] */
+    long pitch;                          /* samples between planes (>= count; any alignment) */
+    long task0;                          /* first task of this item in the launch's flattened task space (filled by the launch) */
+    int count, C;                        /* frames to move (> 0), channels */
+    int tile, pad;                       /* frames per task (filled by the launch) */
+} ArtLayoutItem;
+/* uploads the n items through the shared pinned staging into d_table (device memory of n items, reused call after call: stream order protects
+ * it) and moves every item in one launch on `stream`: planes -> frames, or (to_planar) frames -> planes; 0, or -1 (nothing launched) */
+int arthip_transpose_group (ArtLayoutItem *items, int n, int to_planar, void *d_table, void *stream);
+
 /* ---- extrapolate_kernels.hip: LPC end-point extrapolation, one workgroup per run ----
  * A run's known samples, oldest first, are n[0] samples at src[0] + j * stride[0] followed by n[1] at src[1] + j * stride[1]
  * (n[0] + n[1] in 8 .. ARTAMD_EXTRAPOLATE_MAX_KNOWN).  backward == 0: the `extras` samples that continue past the newest

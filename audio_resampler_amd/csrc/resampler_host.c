@@ -77,6 +77,7 @@ struct artamd_resampler {
     unsigned int *d_fix; size_t fix_cap;    /* [0] per-launch, [1] running count of outputs the matrix kernels evaluated off-pattern */
     void *d_batch; size_t batch_cap;         /* argument table of the batched calls led by this context */
     void *d_group; size_t group_cap;         /* ... and of their grouped matrix-core launches (both tables are in flight in one batch call) */
+    void *d_layout; size_t layout_cap;       /* ... and of the two transposing launches round the staged calls of a planar batch (resampleProcessBatchPlanarDevice) */
     art_s *d_tails; size_t tails_cap;        /* ... and the flush tails of every extrapolating context of such a call (resampleProcessAndFlushBatchInterleavedDevice) */
     void *d_sched; size_t sched_cap;         /* block and segment tables of the scheduled runs (resampleProcessScheduleInterleavedDevice) */
     unsigned long batch_stamp;               /* last batched call this context took part in (duplicate check) */
@@ -703,7 +704,7 @@ void resampleFree (Resample *cxt)
         bank_release (hip->bank); arthip_free (hip->d_hist [0]); arthip_free (hip->d_hist [1]);
         {   /* every device buffer the context may have grown (NULL where it never did) */
             void *const device_buffers [] = { hip->d_in, hip->d_out, hip->d_tmp, hip->d_fix, hip->d_scratch, hip->d_pad, hip->d_planes, hip->d_rows,
-                                              hip->d_split, hip->d_patch, hip->d_batch, hip->d_group, hip->d_tails, hip->d_sched };
+                                              hip->d_split, hip->d_patch, hip->d_batch, hip->d_group, hip->d_layout, hip->d_tails, hip->d_sched };
             for (size_t i = 0; i < sizeof (device_buffers) / sizeof (device_buffers [0]); ++i) arthip_free (device_buffers [i]);
         }
         if (hip->rows_cache) { arthip_fir_rows_cache_free (hip->rows_cache); free (hip->rows_cache); }
@@ -1097,6 +1098,9 @@ static int prefill_at_flush_runs (const Resample *cxt, const art_s *tail, ArtExt
 }
 
 static ResampleResult enqueue_call_layouts (Resample *cxt, const art_s *d_in, long in_pitch, int nIn, art_s *d_out, long out_pitch, int cap, double ratio);
+static ResampleResult device_call (Resample *cxt, const art_s *d_in, long in_pitch, int nIn, art_s *d_out, long out_pitch, int cap, double ratio);
+static ResampleResult peek_call (Resample *cxt, int nIn, int cap, double ratio);
+static int staged_layouts (const Resample *cxt, const art_s *d_in, long in_pitch, int nIn, const art_s *d_out, long out_pitch, int cap);
 static int rewind_lead (Resample *cxt, int nIn, int cap, double ratio);
 static ResampleResult enqueue_call (Resample *cxt, const art_s *d_in, long in_pitch, int nIn,
                                     art_s *d_out, long out_pitch, int cap, double ratio);
@@ -1472,6 +1476,11 @@ static int general_call (const Resample *cxt, const ArtFirArgs *a, const ArtSegT
     return !needs.matrix;
 }
 
+/* Where a batch call's context reads and writes: the caller's buffers with their pitches (0: interleaved), or — a planar call the single call
+ * would stage (staged_layouts) — the context's own interleaved staging, filled and emptied by the batch's two transposing launches.
+ * staged < 0: the transposing launch in front could not be made, the call is the single planar call on the caller's buffers. */
+typedef struct { const art_s *in; art_s *out; long in_pitch, out_pitch; int staged; } BatchIo;
+
 /* What a batch call has gathered.  For the general kernel's launch: the FIR arguments, first table and plan of each gathered call (`owner`: its
  * index in the caller's list), and the extrapolation runs in front of it — `runs`, and `late`, which read what `runs` write (a flush: the
  * prefill of a stream whose first output the flush makes reads the tails) and so are a second launch.  For the grouped matrix-core launches: the
@@ -1525,12 +1534,15 @@ static int batch_plan_matrix (Resample *cxt, ArtFirArgs *a, const ArtSegTable *t
 /* Plan one context's call as the single call would; gather it at w's next place (1) if the general kernel is the single call's and the
  * context may share a launch, at w's next matrix place (2) if a grouped matrix-core launch may run it, else leave the context as it stands
  * (0: the caller makes the single call).
+ * The buffers are interleaved, or planar where a pitch is given (the general kernel, the history rolls and the fits read and write planes as they
+ * come).
  * nIn >= 0, an ordinary call: an extrapolating stream's first output brings its prefill runs, as the single call would make them.
  * nIn < 0, a flush: `tail` is room for the context's T/2 x C tail frames when it extrapolates (NULL: none, the flush is the single call).
  * The flush proper runs on the general kernel whatever the context's other calls run on; it brings its forward tail fits (w->runs) and,
  * when it makes the stream's first output, the prefill over the samples ++ the tail (w->late).  (The flush call of an already flushed
  * stream is the single call: behind the process phase it has no output left to make.) */
-static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, int cap, double ratio, void *lead_stream, art_s *tail, BatchWork *w)
+static int batch_plan (Resample *cxt, const art_s *d_in, long in_pitch, int nIn, art_s *d_out, long out_pitch, int cap, double ratio, void *lead_stream,
+                       art_s *tail, BatchWork *w)
 {
     struct artamd_resampler *hip = cxt->hip;
     ArtFirArgs *a = &w->args [w->gathered];
@@ -1545,12 +1557,13 @@ static int batch_plan (Resample *cxt, const art_s *d_in, int nIn, art_s *d_out, 
     /* (out of memory: the one-by-one path reports it; a flush without an output still appends its half window to the history: an item of
      * roll workgroups only) */
     if (plan_one_call (cxt, nIn, cap, ratio, p) < 0 || (p->res.output_generated == 0 && !is_flush)) return 0;
-    plan_args (cxt, p, ratio, d_in, 0, d_out, 0, p->fit_tail ? tail : NULL, a, tab);
+    plan_args (cxt, p, ratio, d_in, in_pitch, d_out, out_pitch, p->fit_tail ? tail : NULL, a, tab);
+    /* (the matrix-core path takes interleaved frames only: a planar call that is not the general kernel's is the single call's to decide) */
     if (!is_flush && !general_call (cxt, a, tab, p->res.output_generated))
-        return !(cxt->flags & EXTRAPOLATE_PREFILL) && batch_plan_matrix (cxt, a, tab, p, w) ? 2 : 0;
+        return !in_pitch && !out_pitch && !(cxt->flags & EXTRAPOLATE_PREFILL) && batch_plan_matrix (cxt, a, tab, p, w) ? 2 : 0;
     /* (the general kernel's gathered launch takes calls of a few segments; the matrix-core path's follows the lattice from the first table) */
     if (p->nseg > arthip_fir_batch_max_segments ()) return 0;
-    plan_fits (cxt, p, d_in, 0, tail, w->runs, &w->nruns, w->late, &w->nlate);
+    plan_fits (cxt, p, d_in, in_pitch, tail, w->runs, &w->nruns, w->late, &w->nlate);
     return 1;
 }
 
@@ -1582,8 +1595,8 @@ static void batch_commit (Resample *const *cxts, const CallPlan *plans, const in
 /* The calls planned for grouped matrix-core launches: classes by shape; the calls of a class too small for a launch of its own are made one by
  * one (the contexts stand where they stood), the others launched — one launch per class — and committed.  0, or -1: the grouped launches failed
  * (nothing of them enqueued: their contexts' results { 0, 0 }, positions and histories untouched; counted, artamdErrorCount: -2). */
-static int batch_matrix (Resample *const *cxts, BatchWork *w, const artsample_t *const *d_inputs, const int *numInputFrames,
-                         artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios, ResampleResult *results)
+static int batch_matrix (Resample *const *cxts, BatchWork *w, const BatchIo *io, const int *numInputFrames, const int *numOutputFrames,
+                         const double *ratios, ResampleResult *results)
 {
     struct artamd_resampler *lead = cxts [0]->hip;
     ArtFirGroupCall *calls = w->calls;
@@ -1603,7 +1616,7 @@ static int batch_matrix (Resample *const *cxts, BatchWork *w, const artsample_t 
     for (int c = 0, next = 0; c < classes; ++c) rep [c] = count [c] >= MATRIX_GROUP_MIN ? next++ : -1;
     for (int k = 0; k < n; ++k) {
         const int i = w->matrix_owner [k], c = calls [k].cls < 0 ? -1 : rep [calls [k].cls];
-        if (c < 0) { results [i] = resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]); continue; }
+        if (c < 0) { results [i] = device_call (cxts [i], io [i].in, 0, numInputFrames [i], io [i].out, 0, numOutputFrames [i], ratios [i]); continue; }
         calls [kept] = calls [k]; calls [kept].cls = c; w->matrix_plans [kept] = w->matrix_plans [k]; w->matrix_owner [kept++] = i;
     }
     free (rep);
@@ -1622,13 +1635,36 @@ static int batch_matrix (Resample *const *cxts, BatchWork *w, const artsample_t 
 
 static unsigned long *stamp_of (const void *cxt) { return &((const Resample *) cxt)->hip->batch_stamp; }
 
-/* the batch entries' process phase, on the lead's device: every context's ordinary call, gathered or single */
-static int batch_process (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
-                          artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios, ResampleResult *results)
+/* May a context's planar call be staged by the batch's own transposing launches?  They run on the lead's stream: a context the batch makes one by
+ * one anyway (sharded, another stream or device, timing on) stages its call itself, as the single planar call does */
+static int shares_lead (const Resample *cxt, const struct artamd_resampler *lead)
+{
+    const struct artamd_resampler *hip = cxt->hip;
+    return !hip->nshards && hip->stream == lead->stream && !hip->timing && hip->device == lead->device;
+}
+
+/* one transposing launch over the staged calls of a batch (the table in the lead's d_layout: `slot` 0 in front of the FIR launches, 1 behind) */
+static int batch_transpose (struct artamd_resampler *lead, ArtLayoutItem *items, int count, int n, int to_planar)
+{
+    if (!count) return 0;
+    lead->d_layout = arthip_grow (lead->d_layout, &lead->layout_cap, sizeof (ArtLayoutItem) * 2 * (size_t) n);
+    if (lead->d_layout && !arthip_transpose_group (items, count, to_planar, (ArtLayoutItem *) lead->d_layout + (to_planar ? n : 0), lead->stream)) return 0;
+    fprintf (stderr, "artamd: resample batch: transposing launch failed: %s\n", arthip_last_error ());
+    return -1;
+}
+
+/* the batch entries' process phase, on the lead's device: every context's ordinary call, gathered or single.  Pitches as in
+ * resampleProcessPlanarDevice (NULL: every buffer of that side interleaved).  A planar call decides as the single planar call does
+ * (staged_layouts): left as it is, it is the general kernel's with its pitches; staged, it is the interleaved call on the context's own
+ * staging — all such calls' inputs transposed by one launch in front of everything else, their outputs by one launch behind. */
+static int batch_process (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *in_pitches, const int *numInputFrames,
+                          artsample_t *const *d_outputs, const long *out_pitches, const int *numOutputFrames, const double *ratios,
+                          ResampleResult *results, BatchIo *io)
 {
     struct artamd_resampler *lead = cxts [0]->hip;
     BatchWork w;
-    int rc = -1, failed = 0;
+    ArtLayoutItem *items = NULL;
+    int rc = -1, failed = 0, staged = 0, moved = 0;
 
     size_t channels = 0;                 /* (room for the prefill runs of every extrapolating stream's first output: one per channel) */
     for (int i = 0; i < n; ++i)
@@ -1636,12 +1672,44 @@ static int batch_process (Resample *const *cxts, int n, const artsample_t *const
     if (batch_work_init (&w, n, channels, 1)) goto out;
 
     for (int i = 0; i < n; ++i) {
+        Resample *cxt = cxts [i];
+        struct artamd_resampler *hip = cxt->hip;
+        BatchIo *b = &io [i];
+        b->in = d_inputs [i]; b->out = d_outputs [i]; b->staged = 0;
+        b->in_pitch = in_pitches ? in_pitches [i] : 0; b->out_pitch = out_pitches ? out_pitches [i] : 0;
+        if (!shares_lead (cxt, lead) || !staged_layouts (cxt, b->in, b->in_pitch, numInputFrames [i], b->out, b->out_pitch, numOutputFrames [i])) continue;
+        if (!items && !(items = malloc (sizeof (ArtLayoutItem) * (size_t) n))) continue;       /* (no table: the single planar call stages itself) */
+        const int C = cxt->numChannels;
+        if (b->in_pitch) hip->d_in = arthip_grow (hip->d_in, &hip->in_cap, sizeof (art_s) * (size_t) numInputFrames [i] * C);
+        if (b->out_pitch)                /* (room for the frames the call will make, not for the caller's whole capacity) */
+            hip->d_out = arthip_grow (hip->d_out, &hip->out_cap,
+                                      sizeof (art_s) * ((size_t) peek_call (cxt, numInputFrames [i], numOutputFrames [i], ratios [i]).output_generated + 16) * C);
+        if ((b->in_pitch && !hip->d_in) || (b->out_pitch && !hip->d_out)) continue;            /* (... which then falls back as it always did) */
+        b->staged = 1; ++staged;
+        if (b->in_pitch) {
+            ArtLayoutItem *it = &items [moved++];
+            memset (it, 0, sizeof (*it));
+            it->planes = (art_s *) b->in; it->frames = hip->d_in; it->pitch = b->in_pitch; it->count = numInputFrames [i]; it->C = C;
+            b->in = hip->d_in; b->in_pitch = 0;
+        }
+        if (b->out_pitch) { b->out = hip->d_out; b->out_pitch = 0; }
+    }
+    if (batch_transpose (lead, items, moved, n, 0))
+        for (int i = 0; i < n; ++i)
+            if (io [i].staged) {
+                io [i].in = d_inputs [i]; io [i].out = d_outputs [i]; io [i].staged = -1;
+                io [i].in_pitch = in_pitches ? in_pitches [i] : 0; io [i].out_pitch = out_pitches ? out_pitches [i] : 0;
+            }
+
+    for (int i = 0; i < n; ++i) {
+        const BatchIo *b = &io [i];
         /* (a flush handed to this phase is the single call) */
-        const int how = numInputFrames [i] < 0 ? 0 : batch_plan (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i], lead->stream, NULL, &w);
+        const int how = numInputFrames [i] < 0 || b->staged < 0 ? 0 :
+                        batch_plan (cxts [i], b->in, b->in_pitch, numInputFrames [i], b->out, b->out_pitch, numOutputFrames [i], ratios [i], lead->stream, NULL, &w);
         if (how == 1) { results [i] = w.plans [w.gathered].res; w.owner [w.gathered++] = i; }
         else if (how == 2) { results [i] = w.matrix_plans [w.matrix_gathered].res; w.matrix_owner [w.matrix_gathered++] = i; }
         else
-            results [i] = resampleProcessInterleavedDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i], numOutputFrames [i], ratios [i]);
+            results [i] = device_call (cxts [i], b->in, b->in_pitch, numInputFrames [i], b->out, b->out_pitch, numOutputFrames [i], ratios [i]);
     }
 
     if (w.gathered) {
@@ -1653,24 +1721,42 @@ static int batch_process (Resample *const *cxts, int n, const artsample_t *const
         else batch_commit (cxts, w.plans, w.owner, w.gathered, ART_KERNEL_GENERAL);
     }
     /* (the matrix-core calls are made whatever became of the general kernel's launch: other contexts) */
-    rc = w.matrix_gathered ? batch_matrix (cxts, &w, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results) : 0;
+    rc = w.matrix_gathered ? batch_matrix (cxts, &w, io, numInputFrames, numOutputFrames, ratios, results) : 0;
     if (failed) rc = failed;
+
+    /* the staged calls' outputs, back into the callers' planes */
+    moved = 0;
+    for (int i = 0; i < n && staged; ++i)
+        if (io [i].staged > 0 && out_pitches && out_pitches [i] && results [i].output_generated) {
+            ArtLayoutItem *it = &items [moved++];
+            memset (it, 0, sizeof (*it));
+            it->planes = d_outputs [i]; it->frames = cxts [i]->hip->d_out; it->pitch = out_pitches [i];
+            it->count = (int) results [i].output_generated; it->C = cxts [i]->numChannels;
+        }
+    if (batch_transpose (lead, items, moved, n, 1)) rc = -1;
 out:
+    free (items);
     batch_work_free (&w);
     return rc;
 }
+
+/* both batch entries: the process phase, then (and_flush) the flushes */
+static int batch_entry (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *in_pitches, const int *numInputFrames,
+                        artsample_t *const *d_outputs, const long *out_pitches, const int *numOutputFrames, const double *ratios,
+                        ResampleResult *results, int and_flush);
 
 int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                                            artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
                                            ResampleResult *results)
 {
-    if (n <= 0) return 0;
-    if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample", "context")) return -1;
-    struct artamd_resampler *lead = cxts [0]->hip;
-    ENTER_DEVICE (lead);
-    const int rc = batch_process (cxts, n, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results);
-    LEAVE_DEVICE (lead);
-    return rc ? -1 : 0;
+    return batch_entry (cxts, n, d_inputs, NULL, numInputFrames, d_outputs, NULL, numOutputFrames, ratios, results, 0);
+}
+
+int resampleProcessBatchPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                      const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
+                                      const int *numOutputFrames, const double *ratios, ResampleResult *results)
+{
+    return batch_entry (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, results, 0);
 }
 
 /* ---- many whole clips, one launch per stage ------------------------------------------------------------------------
@@ -1685,8 +1771,8 @@ static int flush_due (const int *numInputFrames, const int *numOutputFrames, con
     return numInputFrames [i] - (int) results [i].input_used == 0 && numOutputFrames [i] - (int) results [i].output_generated != 0;
 }
 
-static int batch_flush (Resample *const *cxts, int n, const int *numInputFrames, artsample_t *const *d_outputs, const int *numOutputFrames,
-                        const double *ratios, ResampleResult *results)
+static int batch_flush (Resample *const *cxts, int n, const long *in_pitches, const int *numInputFrames, artsample_t *const *d_outputs,
+                        const long *out_pitches, const int *numOutputFrames, const double *ratios, ResampleResult *results)
 {
     struct artamd_resampler *lead = cxts [0]->hip;
     BatchWork w;
@@ -1707,13 +1793,15 @@ static int batch_flush (Resample *const *cxts, int n, const int *numInputFrames,
         if (!flush_due (numInputFrames, numOutputFrames, results, i)) continue;
         Resample *cxt = cxts [i];
         const int cap = numOutputFrames [i] - (int) results [i].output_generated;
-        art_s *out = d_outputs [i] + (size_t) results [i].output_generated * cxt->numChannels;
+        /* (behind the process call's frames: in every plane, or in the interleaved buffer) */
+        const long in_pitch = in_pitches ? in_pitches [i] : 0, out_pitch = out_pitches ? out_pitches [i] : 0;
+        art_s *out = d_outputs [i] + (size_t) results [i].output_generated * (out_pitch ? 1 : cxt->numChannels);
         const int extrapolates = (cxt->flags & EXTRAPOLATE_ENDPOINTS) && !cxt->hip->nshards;
 
-        if (batch_plan (cxt, NULL, -1, out, cap, ratios [i], lead->stream, extrapolates ? tail : NULL, &w))
+        if (batch_plan (cxt, NULL, 0, -1, out, out_pitch, cap, ratios [i], lead->stream, extrapolates ? tail : NULL, &w))
             w.owner [w.gathered++] = i;
         else
-            results [i].output_generated += resampleProcessInterleavedDevice (cxt, NULL, -1, out, cap, ratios [i]).output_generated;
+            results [i].output_generated += device_call (cxt, NULL, in_pitch, -1, out, out_pitch, cap, ratios [i]).output_generated;
         if (extrapolates && tail) tail += (size_t)(cxt->numTaps / 2) * cxt->numChannels;
     }
 
@@ -1729,19 +1817,37 @@ out:
     return rc;
 }
 
-int resampleProcessAndFlushBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
-                                                   artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
-                                                   ResampleResult *results)
+static int batch_entry (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *in_pitches, const int *numInputFrames,
+                        artsample_t *const *d_outputs, const long *out_pitches, const int *numOutputFrames, const double *ratios,
+                        ResampleResult *results, int and_flush)
 {
     if (n <= 0) return 0;
     if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample", "context")) return -1;
     struct artamd_resampler *lead = cxts [0]->hip;
+    BatchIo *io = malloc (sizeof (BatchIo) * (size_t) n);
     ENTER_DEVICE (lead);
-    int rc = batch_process (cxts, n, d_inputs, numInputFrames, d_outputs, numOutputFrames, ratios, results);
-    if (!rc) rc = batch_flush (cxts, n, numInputFrames, d_outputs, numOutputFrames, ratios, results);
-    if (rc == -1) artamd_note_failure ("resampler: a launch of the batched process-and-flush failed");      /* (-2: counted where it failed) */
+    int rc = io ? batch_process (cxts, n, d_inputs, in_pitches, numInputFrames, d_outputs, out_pitches, numOutputFrames, ratios, results, io) : -1;
+    if (and_flush) {
+        if (!rc) rc = batch_flush (cxts, n, in_pitches, numInputFrames, d_outputs, out_pitches, numOutputFrames, ratios, results);
+        if (rc == -1) artamd_note_failure ("resampler: a launch of the batched process-and-flush failed");      /* (-2: counted where it failed) */
+    }
     LEAVE_DEVICE (lead);
+    free (io);
     return rc ? -1 : 0;
+}
+
+int resampleProcessAndFlushBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
+                                                   artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
+                                                   ResampleResult *results)
+{
+    return batch_entry (cxts, n, d_inputs, NULL, numInputFrames, d_outputs, NULL, numOutputFrames, ratios, results, 1);
+}
+
+int resampleProcessAndFlushBatchPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                              const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
+                                              const int *numOutputFrames, const double *ratios, ResampleResult *results)
+{
+    return batch_entry (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, results, 1);
 }
 
 /* ---- consecutive blocks of one stream, one launch --------------------------------------------------------------------
@@ -2122,6 +2228,16 @@ static ResampleResult sharded_device_call (Resample *cxt, const art_s *d_in, lon
     return res;
 }
 
+/* Does a device-pointer call of these layouts go through the context's interleaved staging buffers (enqueue_call_layouts, and the planar batch
+ * entries, which decide for every context as its single call would)? */
+static int staged_layouts (const Resample *cxt, const art_s *d_in, long in_pitch, int nIn, const art_s *d_out, long out_pitch, int cap)
+{
+    const struct artamd_resampler *hip = cxt->hip;
+    return (in_pitch || out_pitch) && nIn > 0 && cap > 0 && d_in && d_out &&
+           ((double) nIn * (hip->stream_channels > cxt->numChannels ? hip->stream_channels : cxt->numChannels) * cxt->numTaps >= 2.0e8 ||       /* (a shard: its whole stream's size) */
+            hip->kernel_pref == ART_KERNEL_INVARIANT);           /* (the cut-invariant policy: every call, whatever its size, on the same kernel) */
+}
+
 /* enqueue_call for device buffers of either layout (the context's device is current) */
 static ResampleResult enqueue_call_layouts (Resample *cxt, const art_s *d_in, long in_pitch, int nIn, art_s *d_out, long out_pitch, int cap, double ratio)
 {
@@ -2130,9 +2246,7 @@ static ResampleResult enqueue_call_layouts (Resample *cxt, const art_s *d_in, lo
      * kernel is 4-7 x slower than the same call interleaved (8 ch x 988 taps, 1M frames: 960 against 140 us).  Such a call goes
      * through the context's interleaved staging buffers — two transposing copies on the device, ~4 % of the call — and so does a
      * call with only one planar side.  (Small calls stay as they are: the general kernel takes planes as they come.) */
-    if ((in_pitch || out_pitch) && nIn > 0 && cap > 0 && d_in && d_out &&
-        ((double) nIn * (hip->stream_channels > cxt->numChannels ? hip->stream_channels : cxt->numChannels) * cxt->numTaps >= 2.0e8 ||       /* (a shard: its whole stream's size) */
-         hip->kernel_pref == ART_KERNEL_INVARIANT)) {            /* (the cut-invariant policy: every call, whatever its size, on the same kernel) */
+    if (staged_layouts (cxt, d_in, in_pitch, nIn, d_out, out_pitch, cap)) {
         const int C = cxt->numChannels;
         const art_s *in_i = d_in; art_s *out_i = d_out;
         int ok = 1;
@@ -2189,6 +2303,21 @@ ResampleResult resampleProcessAndFlushInterleavedDevice (Resample *cxt, const ar
 
     ResampleResult tail = resampleProcessInterleavedDevice (cxt, NULL, -1, d_output + (size_t) res.output_generated * cxt->numChannels,
                                                             numOutputFrames, ratio);
+    res.output_generated += tail.output_generated;
+    return res;
+}
+
+/* (the flush writes behind the process call's frames: in every plane of a planar output) */
+ResampleResult resampleProcessAndFlushPlanarDevice (Resample *cxt, const artsample_t *d_input, long inputPitch, int numInputFrames,
+                                                    artsample_t *d_output, long outputPitch, int numOutputFrames, double ratio)
+{
+    ResampleResult res = resampleProcessPlanarDevice (cxt, d_input, inputPitch, numInputFrames, d_output, outputPitch, numOutputFrames, ratio);
+
+    if ((numInputFrames -= res.input_used) != 0 || (numOutputFrames -= res.output_generated) == 0)
+        return res;
+
+    ResampleResult tail = resampleProcessPlanarDevice (cxt, NULL, inputPitch, -1, d_output + (size_t) res.output_generated * (outputPitch ? 1 : cxt->numChannels),
+                                                       outputPitch, numOutputFrames, ratio);
     res.output_generated += tail.output_generated;
     return res;
 }

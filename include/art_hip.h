@@ -191,6 +191,35 @@ int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, cons
  * interleaved frames): the same samples as the interleaved entry point's, bit for bit */
 ResampleResult resampleProcessPlanarDevice (Resample *cxt, const artsample_t *d_input, long inputPitch, int numInputFrames,
                                             artsample_t *d_output, long outputPitch, int numOutputFrames, double ratio);
+/* ... and a whole clip: resampleProcessPlanarDevice, then — unless the input was not all used or the output has no room left, as in
+ * resampleProcessAndFlushInterleavedDevice — the flush, which writes behind the process call's frames in every plane (at frame
+ * output_generated of the planes; behind the interleaved frames where outputPitch is 0).  The same counts and samples as the interleaved
+ * entry point's, bit for bit */
+ResampleResult resampleProcessAndFlushPlanarDevice (Resample *cxt, const artsample_t *d_input, long inputPitch, int numInputFrames,
+                                                    artsample_t *d_output, long outputPitch, int numOutputFrames, double ratio);
+/* Many streams, channels-first buffers (a torch waveform is [C, T], a batch of clips [B, C, Tmax] plus lengths).  The two interleaved batch
+ * entries above with a pitch per buffer, in samples, as in resampleProcessPlanarDevice: channel c of item i is at
+ * d_inputs [i] + c * inputPitches [i], likewise the output; a pitch of 0 means that side of that item is interleaved, a NULL pitch array that
+ * every item's is (both NULL: the interleaved entry itself).  A pitch may exceed the frame count (rows of a padded tensor: what lies between
+ * the frames written and the pitch is not touched) and need not be a multiple of 4 samples.  A one-channel context is the same call in either layout.
+ * results [i], the samples and the context's state afterwards (position, flags, history), resampleHipLastKernel and
+ * resampleHipCutInvariantFallbacks are exactly those of the loop of resampleProcessPlanarDevice (resampleProcessAndFlushPlanarDevice) calls
+ * — and so, that call being bit-identical to the interleaved one, those of the interleaved batch entry on transposed copies.
+ * Every context decides as its single planar call does.  A call that stays planar (below frames x stream channels x taps = 2e8, no
+ * cut-invariant policy) is gathered on the batched general kernel, which reads and writes the planes as they come, its history roll and the
+ * EXTRAPOLATE_ENDPOINTS fits likewise.  A call the single call would stage is the interleaved call on the context's own staging, gathered or made
+ * singly as the interleaved batch entry would (a grouped matrix-core launch from a stream's second such call on); the inputs of ALL staged calls
+ * are transposed by one launch (transpose_group_kernel) in front of the FIR launches, their outputs by one launch behind them: two launches for
+ * any number of contexts where the loop of single calls makes two per call.  The flushes always run on the general kernel and write their
+ * planes directly.  Contexts that are made one by one (sharded, another stream or device, strict order, timing on) are the single planar call,
+ * which stages for itself.  Return values, the failure contract, "a context may appear only once" and asynchronous operation as in the
+ * interleaved entries. */
+int resampleProcessBatchPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                      const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
+                                      const int *numOutputFrames, const double *ratios, ResampleResult *results);
+int resampleProcessAndFlushBatchPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                              const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
+                                              const int *numOutputFrames, const double *ratios, ResampleResult *results);
 
 /* ---- host-only building blocks (no GPU needed; used by the CPU test-suite) ---- */
 /* (numFilters+1) x numTaps bank exactly as resampleInit builds it (reference resampler.c:149-168, 1090-1133) */

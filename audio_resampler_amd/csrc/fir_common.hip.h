@@ -216,4 +216,17 @@ static inline int artfir_period_multiple (int P, int rows)
 // a 4,096-frame stereo call 5.3 | 5.6)
 __host__ __device__ constexpr int general_group (int taps) { return taps <= 512 ? 16 : 32; }
 
+// The history roll that rides along with a matrix launch (both sample widths), element e < H * C of it: frame `appended` + e / C of hist ++ in
+// (interleaved; zeros past the call's input) -> dst [e].  Reads hist ++ in, writes the OTHER history buffer: independent of everything else in flight.
+// (fir_general.hip's general_roll reads planar input too and is its own.)
+template <typename S>
+__device__ __forceinline__ void matrix_roll (S *dst, const S *hist, const S *in, int in_frames, int H, int C, int appended, int e)
+{
+    const int f = e / C, c = e - f * C, lin = appended + f;
+    S v = (S) 0;
+    if (lin < H) v = hist [(size_t) lin * C + c];
+    else if (in && lin - H < in_frames) v = in [(size_t)(lin - H) * C + c];
+    dst [e] = v;
+}
+
 } // namespace

@@ -237,13 +237,7 @@ void fir_mfma_kernel (ArtFirArgs a, ArtSegTable segs, MfmaGeom g)
     if (blockIdx.x >= tile_blocks) {
         if (blockIdx.y == 0 && a.roll_dst) {
             const int e = (int)(blockIdx.x - tile_blocks) * THREADS + tid;
-            if (e < a.H * a.C) {
-                const int f = e / a.C, c = e - f * a.C, lin = a.roll_appended + f;
-                float v = 0.0f;
-                if (lin < a.H) v = a.hist [(size_t) lin * a.C + c];
-                else if (a.in && lin - a.H < a.in_frames) v = a.in [(size_t)(lin - a.H) * a.C + c];
-                a.roll_dst [e] = v;
-            }
+            if (e < a.H * a.C) matrix_roll (a.roll_dst, a.hist, a.in, a.in_frames, a.H, a.C, a.roll_appended, e);
         }
         return;
     }
@@ -605,13 +599,7 @@ void fir_mfma_stream_kernel (ArtFirArgs a, MfmaGeom g, int wgs_per_xcd)
     if (blockIdx.x >= stream_blocks) {                        // extra workgroups: the history roll (as in fir_mfma_kernel)
         if (a.roll_dst) {
             const int e = (int)(blockIdx.x - stream_blocks) * THREADS + tid;
-            if (e < a.H * a.C) {
-                const int f = e / a.C, c = e - f * a.C, lin = a.roll_appended + f;
-                float v = 0.0f;
-                if (lin < a.H) v = a.hist [(size_t) lin * a.C + c];
-                else if (a.in && lin - a.H < a.in_frames) v = a.in [(size_t)(lin - a.H) * a.C + c];
-                a.roll_dst [e] = v;
-            }
+            if (e < a.H * a.C) matrix_roll (a.roll_dst, a.hist, a.in, a.in_frames, a.H, a.C, a.roll_appended, e);
         }
         return;
     }
@@ -695,13 +683,7 @@ void fir_mfma_group_kernel (MfmaGroupClass cls, const unsigned int *__restrict__
         const MfmaGroupItem &it = items [rb / (unsigned int) cls.roll_blocks];
         if (it.roll_dst) {
             const int e = (int)(rb % (unsigned int) cls.roll_blocks) * THREADS + tid;
-            if (e < cls.H * CG) {
-                const int f = e / CG, c = e - f * CG, lin = it.roll_appended + f;
-                float v = 0.0f;
-                if (lin < cls.H) v = it.hist [(size_t) lin * CG + c];
-                else if (it.in && lin - cls.H < it.in_frames) v = it.in [(size_t)(lin - cls.H) * CG + c];
-                it.roll_dst [e] = v;
-            }
+            if (e < cls.H * CG) matrix_roll (it.roll_dst, it.hist, it.in, it.in_frames, cls.H, CG, it.roll_appended, e);
         }
         return;
     }
@@ -764,13 +746,7 @@ void fir_mfma_split_kernel (ArtFirArgs a, MfmaGeom g, int wgs_per_xcd, int KS, d
     if (blockIdx.x >= stream_blocks) {                        // extra workgroups: the history roll (as in fir_mfma_kernel)
         if (a.roll_dst) {
             const int e = (int)(blockIdx.x - stream_blocks) * THREADS + tid;
-            if (e < a.H * a.C) {
-                const int f = e / a.C, c = e - f * a.C, lin = a.roll_appended + f;
-                float v = 0.0f;
-                if (lin < a.H) v = a.hist [(size_t) lin * a.C + c];
-                else if (a.in && lin - a.H < a.in_frames) v = a.in [(size_t)(lin - a.H) * a.C + c];
-                a.roll_dst [e] = v;
-            }
+            if (e < a.H * a.C) matrix_roll (a.roll_dst, a.hist, a.in, a.in_frames, a.H, a.C, a.roll_appended, e);
         }
         return;
     }

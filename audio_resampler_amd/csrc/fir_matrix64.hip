@@ -110,13 +110,7 @@ void fir_mfma64_kernel (ArtFirArgs a, ArtSegTable segs, WideGeom g)
     if (blockIdx.x >= tile_blocks) {
         if (a.roll_dst) {
             const int e = (int)(blockIdx.x - tile_blocks) * MW_THREADS + (int) threadIdx.x;
-            if (e < a.H * a.C) {
-                const int f = e / a.C, c = e - f * a.C, lin = a.roll_appended + f;
-                double v = 0.0;
-                if (lin < a.H) v = a.hist [(size_t) lin * a.C + c];
-                else if (a.in && lin - a.H < a.in_frames) v = a.in [(size_t)(lin - a.H) * a.C + c];
-                a.roll_dst [e] = v;
-            }
+            if (e < a.H * a.C) matrix_roll (a.roll_dst, a.hist, a.in, a.in_frames, a.H, a.C, a.roll_appended, e);
         }
         return;
     }

@@ -84,7 +84,6 @@ template <> struct VecLoad<4> { static __device__ __forceinline__ void load (flo
     u32x4 v = __builtin_amdgcn_raw_buffer_load_b128 (r, (int) off, 0, 0);
     dst [0] = __uint_as_float (v.x); dst [1] = __uint_as_float (v.y); dst [2] = __uint_as_float (v.z); dst [3] = __uint_as_float (v.w); } };
 
-
 } // namespace
 
 // ---------------------------------------------------------------------------------------------------

@@ -50,6 +50,7 @@ constexpr int I8_KC = 32;                 // taps per staged chunk = K of one in
 constexpr int I8_PITCH = 48;              // LDS bytes per (row or column, plane) of a chunk: 32 + 16 pad, conflict-free b128 reads
 constexpr int I8_COLS = 128;              // columns per workgroup
 constexpr int I8_MAX_PPW = 64;
+constexpr int i8_ppw (int cols, int cg) { return cols / cg > I8_MAX_PPW ? I8_MAX_PPW : cols / cg; }        // periods per tile of `cols` columns
 constexpr float I8_SCALE = 1073741824.0f; // 2^30: the filter rows' fixed point
 constexpr float I8_LIMIT = 1.98f;         // |row value| the digits can hold: 0x7f7f7f7f / 2^30 = 1.98437..., rounded down
 
@@ -415,12 +416,18 @@ __device__ __forceinline__ void stand_by_tiles (const ArtFirArgs &a, const MfmaG
 #include "fir_matrix_stream_body.inc"
 }
 
+// an entry of the tile table, uniform.  Through a plain pointer: a vector load and readfirstlane (the entry arrives in a vector register, and a resource
+// built from it would make every load a waterfall loop; the value is the same in all lanes).  Through a constant-address-space pointer: the scalar cache
+// (the DMA kernels: a vector load would sit on the VM counter among the DMAs)
+__device__ __forceinline__ int i8_table_entry (const int *table, int i) { return __builtin_amdgcn_readfirstlane (table [i]); }
+__device__ __forceinline__ int i8_table_entry (const __attribute__ ((address_space (4))) int *table, int i) { return table [i]; }
+
 template <int CG, bool PASS>
 __global__ __launch_bounds__ (2 * MF_THREADS) __attribute__ ((amdgpu_waves_per_eu (4, 4)))
 void fir_i8_stream_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
 {
     constexpr int THREADS = 2 * MF_THREADS;
-    constexpr int PPW = I8_COLS / CG > I8_MAX_PPW ? I8_MAX_PPW : I8_COLS / CG;
+    constexpr int PPW = i8_ppw (I8_COLS, CG);
     constexpr int NCOLS = PPW * CG;
     __shared__ __attribute__ ((aligned (16))) unsigned char As_ [2] [4] [32 * I8_PITCH];
     __shared__ __attribute__ ((aligned (16))) unsigned char Bs_ [2] [4] [I8_COLS * I8_PITCH];
@@ -429,44 +436,8 @@ void fir_i8_stream_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
     const bool loader = wave >= 4;
     const int pt = tid & (MF_THREADS - 1);
 
-    const unsigned int stream_blocks = 8u * (unsigned int) wgs_per_xcd;
-    if (blockIdx.x >= stream_blocks) {                        // extra workgroups: the history roll (as in fir_mfma_kernel)
-        if (a.roll_dst) {
-            const int e = (int)(blockIdx.x - stream_blocks) * THREADS + tid;
-            if (e < a.H * a.C) {
-                const int f = e / a.C, c = e - f * a.C, lin = a.roll_appended + f;
-                float v = 0.0f;
-                if (lin < a.H) v = a.hist [(size_t) lin * a.C + c];
-                else if (a.in && lin - a.H < a.in_frames) v = a.in [(size_t)(lin - a.H) * a.C + c];
-                a.roll_dst [e] = v;
-            }
-        }
-        return;
-    }
-    // Samples the digits cannot hold (flag raised by the staging pass; uniform): the launch is produced in f32 by the streaming
-    // kernel's own tile loop on this kernel's workgroups and LDS (its 2 x 32 rows and 2 x 128 columns of 36 floats fit the
-    // digit buffers), from the tables the staging pass has left for it — the bits of fir_mfma_stream_kernel.
-    if (*q.flag == q.epoch) {
-        static_assert (sizeof (As_) >= 2 * 32 * MF_LD * sizeof (float) && sizeof (Bs_) >= 2 * MF_COLS * MF_LD * sizeof (float), "the f32 tiles live in the digit buffers");
-        stand_by_tiles<CG, PASS> (a, g, wgs_per_xcd, *reinterpret_cast<float (*) [2] [32 * MF_LD]> (&As_ [0] [0] [0]), *reinterpret_cast<float (*) [2] [MF_COLS * MF_LD]> (&Bs_ [0] [0] [0]));
-        return;
-    }
-
-    const int xcd = blockIdx.x & 7, rank = blockIdx.x >> 3;
-    const int tiles_per_xcd = q.sg_per_xcd * q.g * q.tiles;
-    const int nchunks = q.ktot / I8_KC;
-
-    // tile `within` of this XCD's list -> (slot tile, first period); false if the tile holds no output of the launch
-    auto tile_at = [&] (int within, int &st, int &j0) -> bool {
-        st = within % q.tiles;
-        const int t2 = within / q.tiles, jr = t2 % q.g, sg = xcd * q.sg_per_xcd + t2 / q.g;
-        if (sg >= q.super_groups) return false;
-        j0 = sg * q.g * PPW + jr;
-        return a.n_begin + (unsigned int) j0 * g.P + (unsigned int)(st * 32) < a.n_end;
-    };
-    int my_tiles = 0;
-    { int st, j0; for (int w = rank; w < tiles_per_xcd; w += wgs_per_xcd) my_tiles += tile_at (w, st, j0) ? 1 : 0; }
-    if (my_tiles == 0) return;
+#define I8_PART 1     // roll workgroups, stand-by, this workgroup's tile list (tile_at, my_tiles)
+#include "fir_i8_tile32.inc"
 
     if (NCOLS < I8_COLS)                                      // unused columns stay zero for the whole kernel
         for (int e = tid; e < 2 * 4 * (I8_COLS - NCOLS) * I8_PITCH / 4; e += THREADS) {
@@ -493,38 +464,13 @@ void fir_i8_stream_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
             bper [u] = m * q.g;                                                   // the unit's column: this many periods behind the tile's first
             bdel [u] = 0u;
         }
-        // a column whose period lies d exponent blocks behind the tile's first column stages from that block's own planes: d regions
-        // further on, where the same 4-frame block sits d * eb_step blocks earlier
-        const unsigned int x_total = 4u * q.eb_plane_bytes;
-        const unsigned int eb_hop = x_total - (unsigned int) q.eb_step * (unsigned int)(CG * 4);
         // two register stages: the loads of chunk c + 3 are issued while those of c + 2 are still in flight (a chunk is ~0.5 us
         // of matrix work, less than a loaded L2 round trip: with one stage the kernel ran at the memory latency, 139 us)
         unsigned int ra0 [2] [4], rb0 [2] [4] [NB * VEC];
+        const int *tile_w0 = g.tile_w0;                       // (read with a vector load and readfirstlane: i8_table_entry)
 
-        int f_within = rank - wgs_per_xcd, f_chunk = 0;
-        bool f_live = false;
-        const unsigned char *fa_base = nullptr, *fb_base = nullptr;
-        unsigned int fa_bytes = 0, fb_bytes = 0;
-        auto open_tile = [&] () {                             // next tile of this workgroup's list that holds outputs
-            int st = 0, j0 = 0;
-            f_live = false;
-            for (f_within += wgs_per_xcd; f_within < tiles_per_xcd; f_within += wgs_per_xcd)
-                if (tile_at (f_within, st, j0)) { f_live = true; break; }
-            if (!f_live) return;
-            // (readfirstlane: the table entry arrives in a vector register, and a resource built from it would make every load a
-            // waterfall loop; the value is the same in all lanes)
-            const int la = max (__builtin_amdgcn_readfirstlane (g.tile_w0 [3 * st]) + g.w_shift + j0 * g.Q + g.head_pad, 0);
-            // the tile's exponent block and its first 4-frame block inside that block's own planes
-            const int eb = j0 / q.eb_periods;
-            unsigned int skip = (unsigned int) max ((la >> 2) - q.b0 - eb * q.eb_step, 0) * (unsigned int)(CG * 4);
-            if (skip > q.eb_plane_bytes) skip = q.eb_plane_bytes;
-            const size_t from = (size_t) eb * x_total + skip;
-            fb_base = q.x_planes + from; fb_bytes = (unsigned int) min (q.x_bytes - from, (size_t) 0xfffffff0u);
-#pragma unroll
-            for (int u = 0; u < NB; ++u) bdel [u] = (unsigned int)((j0 + bper [u]) / q.eb_periods - eb) * eb_hop;
-            fa_bytes = (unsigned int) nchunks * 4096u;
-            fa_base = q.a_planes + (size_t)(st * q.g + (j0 + q.jr_rot) % q.g) * fa_bytes;
-        };
+#define I8_PART 2     // the tile stream: open_tile and what it leaves (fa_*, fb_*, bdel)
+#include "fir_i8_tile32.inc"
         auto fetch_next = [&] (auto set_tag) {
             constexpr int SET = decltype (set_tag)::value;
             if (f_live) {
@@ -594,22 +540,8 @@ void fir_i8_stream_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
     for (int within = rank; within < tiles_per_xcd; within += wgs_per_xcd) {
         int st, j0;
         if (!tile_at (within, st, j0)) continue;
-        // rows carry 30 fraction bits, this lane's channel 2^shift in its period's exponent block; the class sums are combined at
-        // weight 256^(4 - s) in units of 2^16: the result is scaled by 2^(-14 - shift) (loaded now, used after the K loop)
-        const int out_exp = -14 - q.shifts [((j0 + jl * q.g) / q.eb_periods) * CG + c];
-        i32x16 acc [5];
-#pragma unroll
-        for (int s = 0; s < 5; ++s)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc [s] [r] = 0;
-        // chunks in which some row of this tile has a non-zero most significant digit (the few around the rows' centres: taps
-        // fall off as 1 / distance): everywhere else the four products with that digit plane are exactly zero and not issued
-        // (and likewise the second digit plane — zero in the window's tails, where the taps are below 2^-15: its four products too)
-        unsigned long long top = q.a_masks [(st * q.g + (j0 + q.jr_rot) % q.g) * 32 + (lane & 31)], sec = q.a_masks [q.mask_words + (st * q.g + (j0 + q.jr_rot) % q.g) * 32 + (lane & 31)];
-#pragma unroll
-        for (int off = 1; off < 32; off <<= 1) { top |= __shfl_xor (top, off); sec |= __shfl_xor (sec, off); }
-        const unsigned int top_lo = __builtin_amdgcn_readfirstlane ((unsigned int) top), top_hi = __builtin_amdgcn_readfirstlane ((unsigned int)(top >> 32));
-        const unsigned int sec_lo = __builtin_amdgcn_readfirstlane ((unsigned int) sec), sec_hi = __builtin_amdgcn_readfirstlane ((unsigned int)(sec >> 32));
+#define I8_PART 3     // out_exp, acc, the row masks
+#include "fir_i8_tile32.inc"
 
         for (int ch = 0; ch < nchunks; ++ch, ++qn) {
             // (one loop body, the LDS buffer chosen by address: two bodies made the compiler keep two copies of the accumulators)
@@ -625,49 +557,11 @@ void fir_i8_stream_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
             // LDS round trip per plane), and the buffer is handed back as soon as they have landed
             __builtin_amdgcn_sched_group_barrier (0x100, 8, 0);
             __syncthreads ();
-#pragma unroll
-            for (int i = 2; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (i + j <= 4) acc [i + j] = __builtin_amdgcn_mfma_i32_32x32x32_i8 (av [i], bv [j], acc [i + j], 0, 0, 0);
-            if (((ch < 32 ? sec_lo >> ch : sec_hi >> (ch - 32)) & 1u) != 0u) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc [1 + j] = __builtin_amdgcn_mfma_i32_32x32x32_i8 (av [1], bv [j], acc [1 + j], 0, 0, 0);
-            }
-            if (((ch < 32 ? top_lo >> ch : top_hi >> (ch - 32)) & 1u) != 0u) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc [j] = __builtin_amdgcn_mfma_i32_32x32x32_i8 (av [0], bv [j], acc [j], 0, 0, 0);
-            }
+#define I8_PART 4     // the 13-product ladder on acc
+#include "fir_i8_tile32.inc"
         }
-
-        // ---- the tile's outputs: C/D layout of 32x32: row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), col = lane & 31
-        const unsigned int n_tile = a.n_begin + (unsigned int) j0 * g.P + (unsigned int)(st * 32);
-        const int rows_valid = min (32, g.P - st * 32);
-        const size_t left = (size_t)(a.n_end - n_tile) * CG * 4;
-        const __amdgpu_buffer_rsrc_t rs_out = make_rsrc (a.out + (size_t) n_tile * CG, left > 0xffffff00ull ? 0xffffff00u : (unsigned int) left);
-        const unsigned int pass_rows = PASS ? (unsigned int) g.tile_w0 [3 * st + 1] : 0u;
-        // (a launch on rows kept across calls starts mid-period: the slots of its first period in front of its first output are not stored.
-        // They sit in the first CG columns of the first matrix wave of the launch's first period group: a scalar bound — 0 everywhere else —
-        // and a test on the lane's own number, nothing kept live through the tile loop)
-        const int lo = a.n_skip != 0 && j0 == 0 && wave == 0 ? a.n_skip - st * 32 : 0;
-        // (the lane's half, opaque and per tile: as loop invariants the slot numbers below were computed in front of the tile loop, spilled and read back per tile)
-        int half = lane >> 5;
-        asm volatile ("" : "+v" (half));
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int i_const = (r & 3) + 8 * (r >> 2);      // compile-time part of the slot
-            // class sums, weights 256^(4 - s), as one exact 64-bit integer, scaled back by the rows' and the channel's exponents (a
-            // power of two: exact) and rounded ONCE to float — the same arithmetic in every fixed-point kernel: the same bits
-            float y = i8_round (i8_total (acc [0] [r], acc [1] [r], acc [2] [r], acc [3] [r], acc [4] [r]), out_exp);
-            const int i = i_const + 4 * half;
-            if constexpr (PASS) {
-                // nearest-filter mode, the position falls exactly on an input sample: the reference copies it (resampler.c:1141-1142)
-                if ((pass_rows >> i) & 1u)
-                    y = load_frame (a, INT_MIN, g.canon_ip [st * 32 + i] + g.w_shift + g.canon_fi [st * 32 + i] / a.F + (j0 + jl * q.g) * g.Q, c);
-            }
-            if (col_live && i < rows_valid && (i >= lo || (lane & 31) >= CG))      // (frames at or past n_end: out of the resource's range, dropped)
-                __builtin_amdgcn_raw_buffer_store_b32 (__float_as_uint (y), rs_out, (int)(out_off + (unsigned int)(i_const * CG) * 4u), 0, 0);
-        }
+#define I8_PART 5     // the tile's outputs
+#include "fir_i8_tile32.inc"
     }
 }
 
@@ -701,42 +595,8 @@ void fir_i8_dma_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool loader = wave >= 4;
 
-    const unsigned int stream_blocks = 8u * (unsigned int) wgs_per_xcd;
-    if (blockIdx.x >= stream_blocks) {                        // extra workgroups: the history roll (as in fir_mfma_kernel)
-        if (a.roll_dst) {
-            const int e = (int)(blockIdx.x - stream_blocks) * THREADS + tid;
-            if (e < a.H * a.C) {
-                const int f = e / a.C, c = e - f * a.C, lin = a.roll_appended + f;
-                float v = 0.0f;
-                if (lin < a.H) v = a.hist [(size_t) lin * a.C + c];
-                else if (a.in && lin - a.H < a.in_frames) v = a.in [(size_t)(lin - a.H) * a.C + c];
-                a.roll_dst [e] = v;
-            }
-        }
-        return;
-    }
-    // (stand-by: as fir_i8_stream_kernel)
-    if (*q.flag == q.epoch) {
-        static_assert (sizeof (As_) >= 2 * 32 * MF_LD * sizeof (float) && sizeof (Bs_) >= 2 * MF_COLS * MF_LD * sizeof (float), "the f32 tiles live in the digit buffers");
-        stand_by_tiles<CG, PASS> (a, g, wgs_per_xcd, *reinterpret_cast<float (*) [2] [32 * MF_LD]> (&As_ [0]), *reinterpret_cast<float (*) [2] [MF_COLS * MF_LD]> (&Bs_ [0]));
-        return;
-    }
-
-    const int xcd = blockIdx.x & 7, rank = blockIdx.x >> 3;
-    const int tiles_per_xcd = q.sg_per_xcd * q.g * q.tiles;
-    const int nchunks = q.ktot / I8_KC;
-
-    // tile `within` of this XCD's list -> (slot tile, first period); false if the tile holds no output of the launch
-    auto tile_at = [&] (int within, int &st, int &j0) -> bool {
-        st = within % q.tiles;
-        const int t2 = within / q.tiles, jr = t2 % q.g, sg = xcd * q.sg_per_xcd + t2 / q.g;
-        if (sg >= q.super_groups) return false;
-        j0 = sg * q.g * PPW + jr;
-        return a.n_begin + (unsigned int) j0 * g.P + (unsigned int)(st * 32) < a.n_end;
-    };
-    int my_tiles = 0;
-    { int st, j0; for (int w = rank; w < tiles_per_xcd; w += wgs_per_xcd) my_tiles += tile_at (w, st, j0) ? 1 : 0; }
-    if (my_tiles == 0) return;
+#define I8_PART 1     // roll workgroups, stand-by, this workgroup's tile list (tile_at, my_tiles)
+#include "fir_i8_tile32.inc"
     const int total = my_tiles * nchunks;
 
     if (loader) {
@@ -746,34 +606,14 @@ void fir_i8_dma_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
         const int kb = 2 * lw + (lane >> 5), colquad = lane & 31, m = colquad / VPF, cv = colquad - m * VPF;
         const unsigned int boff = (unsigned int)((m * q.gq4 + kb) * CG + cv * 4) * 4u;       // (the tile's first block sits in the resource base)
         const unsigned int a_off = (unsigned int)(lw * 1024 + lane * 16);
-        // a column whose period lies d exponent blocks behind the tile's first column stages from that block's own planes: d regions
-        // further on, where the same 4-frame block sits d * eb_step blocks earlier
-        const unsigned int x_total = 4u * q.eb_plane_bytes;
-        const unsigned int eb_hop = x_total - (unsigned int) q.eb_step * (unsigned int)(CG * 4);
-        unsigned int bdel = 0u;
+        constexpr int NB = 1;                                 // one staged unit per thread
+        const int bper [NB] = { m * q.g };
+        unsigned int bdel [NB] = { 0u };
         // (the tile table through the scalar cache: a vector load here would sit on the VM counter among the DMAs)
         const __attribute__ ((address_space (4))) int *tile_w0 = (const __attribute__ ((address_space (4))) int *) g.tile_w0;
 
-        int f_within = rank - wgs_per_xcd, f_chunk = 0;
-        bool f_live = false;
-        const unsigned char *fa_base = nullptr, *fb_base = nullptr;
-        unsigned int fa_bytes = 0, fb_bytes = 0;
-        auto open_tile = [&] () {                             // next tile of this workgroup's list that holds outputs
-            int st = 0, j0 = 0;
-            f_live = false;
-            for (f_within += wgs_per_xcd; f_within < tiles_per_xcd; f_within += wgs_per_xcd)
-                if (tile_at (f_within, st, j0)) { f_live = true; break; }
-            if (!f_live) return;
-            const int la = max (tile_w0 [3 * st] + g.w_shift + j0 * g.Q + g.head_pad, 0);
-            const int eb = j0 / q.eb_periods;
-            unsigned int skip = (unsigned int) max ((la >> 2) - q.b0 - eb * q.eb_step, 0) * (unsigned int)(CG * 4);
-            if (skip > q.eb_plane_bytes) skip = q.eb_plane_bytes;
-            const size_t from = (size_t) eb * x_total + skip;
-            fb_base = q.x_planes + from; fb_bytes = (unsigned int) min (q.x_bytes - from, (size_t) 0xfffffff0u);
-            bdel = (unsigned int)((j0 + m * q.g) / q.eb_periods - eb) * eb_hop;
-            fa_bytes = (unsigned int) nchunks * 4096u;
-            fa_base = q.a_planes + (size_t)(st * q.g + (j0 + q.jr_rot) % q.g) * fa_bytes;
-        };
+#define I8_PART 2     // the tile stream: open_tile and what it leaves (fa_*, fb_*, bdel)
+#include "fir_i8_tile32.inc"
         // the next chunk of the workgroup's stream -> LDS buffer `buf`: 5 DMA instructions of this wave, or none past the end
         auto issue = [&] (int buf) -> bool {
             if (!f_live) return false;
@@ -782,7 +622,7 @@ void fir_i8_dma_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
             __builtin_amdgcn_raw_ptr_buffer_load_lds (ra_, (lds_ptr_t)(As_ + buf * A_BUF + lw * 1024), 16, (int) a_off, 0, 0, 0);
 #pragma unroll
             for (int pn = 0; pn < 4; ++pn)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds (rb_, (lds_ptr_t)(Bs_ + buf * B_BUF + pn * 4096 + lw * 1024), 16, (int)(boff + bdel), (int)((unsigned int) pn * q.eb_plane_bytes), 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds (rb_, (lds_ptr_t)(Bs_ + buf * B_BUF + pn * 4096 + lw * 1024), 16, (int)(boff + bdel [0]), (int)((unsigned int) pn * q.eb_plane_bytes), 0, 0);
             if (++f_chunk == nchunks) { f_chunk = 0; open_tile (); }
             return true;
         };
@@ -814,6 +654,7 @@ void fir_i8_dma_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
         if (hw_id & 1u) __builtin_amdgcn_s_setprio (3); else __builtin_amdgcn_s_setprio (0);
     }
     const int col = wave * 32 + (lane & 31);
+    constexpr bool col_live = true;                           // (whole 16-byte vectors of 4 channels: every column exists)
     const int jl = col / CG, c = col - jl * CG;
     const unsigned char *Ab0 = As_ + (lane & 31) * 16 + (lane >> 5) * 512;
     const unsigned char *Bb0 = Bs_ + (lane >> 5) * 2048 + col * 4;
@@ -827,22 +668,8 @@ void fir_i8_dma_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
     for (int within = rank; within < tiles_per_xcd; within += wgs_per_xcd) {
         int st, j0;
         if (!tile_at (within, st, j0)) continue;
-        // rows carry 30 fraction bits, this lane's channel 2^shift in its period's exponent block; the class sums are combined at
-        // weight 256^(4 - s) in units of 2^16: the result is scaled by 2^(-14 - shift) (loaded now, used after the K loop)
-        const int out_exp = -14 - q.shifts [((j0 + jl * q.g) / q.eb_periods) * CG + c];
-        i32x16 acc [5];
-#pragma unroll
-        for (int s = 0; s < 5; ++s)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc [s] [r] = 0;
-        // chunks in which some row of this tile has a non-zero most significant digit (the few around the rows' centres: taps
-        // fall off as 1 / distance): everywhere else the four products with that digit plane are exactly zero and not issued
-        // (and likewise the second digit plane — zero in the window's tails, where the taps are below 2^-15: its four products too)
-        unsigned long long top = q.a_masks [(st * q.g + (j0 + q.jr_rot) % q.g) * 32 + (lane & 31)], sec = q.a_masks [q.mask_words + (st * q.g + (j0 + q.jr_rot) % q.g) * 32 + (lane & 31)];
-#pragma unroll
-        for (int off = 1; off < 32; off <<= 1) { top |= __shfl_xor (top, off); sec |= __shfl_xor (sec, off); }
-        const unsigned int top_lo = __builtin_amdgcn_readfirstlane ((unsigned int) top), top_hi = __builtin_amdgcn_readfirstlane ((unsigned int)(top >> 32));
-        const unsigned int sec_lo = __builtin_amdgcn_readfirstlane ((unsigned int) sec), sec_hi = __builtin_amdgcn_readfirstlane ((unsigned int)(sec >> 32));
+#define I8_PART 3     // out_exp, acc, the row masks
+#include "fir_i8_tile32.inc"
 
         for (int ch = 0; ch < nchunks; ++ch) {
             const unsigned char *Ab = Ab0 + qb * A_BUF, *Bb = Bb0 + qb * B_BUF;
@@ -860,46 +687,11 @@ void fir_i8_dma_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, int wgs_per_xcd)
             asm volatile ("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier ();
             asm volatile ("" ::: "memory");
-#pragma unroll
-            for (int i = 2; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (i + j <= 4) acc [i + j] = __builtin_amdgcn_mfma_i32_32x32x32_i8 (av [i], bv [j], acc [i + j], 0, 0, 0);
-            if (((ch < 32 ? sec_lo >> ch : sec_hi >> (ch - 32)) & 1u) != 0u) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc [1 + j] = __builtin_amdgcn_mfma_i32_32x32x32_i8 (av [1], bv [j], acc [1 + j], 0, 0, 0);
-            }
-            if (((ch < 32 ? top_lo >> ch : top_hi >> (ch - 32)) & 1u) != 0u) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc [j] = __builtin_amdgcn_mfma_i32_32x32x32_i8 (av [0], bv [j], acc [j], 0, 0, 0);
-            }
+#define I8_PART 4     // the 13-product ladder on acc
+#include "fir_i8_tile32.inc"
         }
-
-        // ---- the tile's outputs: C/D layout of 32x32: row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), col = lane & 31
-        const unsigned int n_tile = a.n_begin + (unsigned int) j0 * g.P + (unsigned int)(st * 32);
-        const int rows_valid = min (32, g.P - st * 32);
-        const size_t left = (size_t)(a.n_end - n_tile) * CG * 4;
-        const __amdgpu_buffer_rsrc_t rs_out = make_rsrc (a.out + (size_t) n_tile * CG, left > 0xffffff00ull ? 0xffffff00u : (unsigned int) left);
-        const unsigned int pass_rows = PASS ? (unsigned int) g.tile_w0 [3 * st + 1] : 0u;
-        // (a launch on rows kept across calls starts mid-period: the slots of its first period in front of its first output are not stored.
-        // They sit in the first CG columns of the first matrix wave of the launch's first period group: a scalar bound — 0 everywhere else —
-        // and a test on the lane's own number, nothing kept live through the tile loop)
-        const int lo = a.n_skip != 0 && j0 == 0 && wave == 0 ? a.n_skip - st * 32 : 0;
-        // (the lane's half, opaque and per tile: as loop invariants the slot numbers below were computed in front of the tile loop, spilled and read back per tile)
-        int half = lane >> 5;
-        asm volatile ("" : "+v" (half));
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int i_const = (r & 3) + 8 * (r >> 2);      // compile-time part of the slot
-            float y = i8_round (i8_total (acc [0] [r], acc [1] [r], acc [2] [r], acc [3] [r], acc [4] [r]), out_exp);
-            const int i = i_const + 4 * half;
-            if constexpr (PASS) {
-                if ((pass_rows >> i) & 1u)
-                    y = load_frame (a, INT_MIN, g.canon_ip [st * 32 + i] + g.w_shift + g.canon_fi [st * 32 + i] / a.F + (j0 + jl * q.g) * g.Q, c);
-            }
-            if (i < rows_valid && (i >= lo || (lane & 31) >= CG))                  // (frames at or past n_end: out of the resource's range, dropped)
-                __builtin_amdgcn_raw_buffer_store_b32 (__float_as_uint (y), rs_out, (int)(out_off + (unsigned int)(i_const * CG) * 4u), 0, 0);
-        }
+#define I8_PART 5     // the tile's outputs
+#include "fir_i8_tile32.inc"
     }
 }
 
@@ -954,13 +746,8 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
 
     // the history roll: every workgroup its share
     if (a.roll_dst) {
-        for (int e = (int) blockIdx.x * THREADS + tid; e < a.H * a.C; e += (int) gridDim.x * THREADS) {
-            const int f = e / a.C, c = e - f * a.C, lin = a.roll_appended + f;
-            float v = 0.0f;
-            if (lin < a.H) v = a.hist [(size_t) lin * a.C + c];
-            else if (a.in && lin - a.H < a.in_frames) v = a.in [(size_t)(lin - a.H) * a.C + c];
-            a.roll_dst [e] = v;
-        }
+        for (int e = (int) blockIdx.x * THREADS + tid; e < a.H * a.C; e += (int) gridDim.x * THREADS)
+            matrix_roll (a.roll_dst, a.hist, a.in, a.in_frames, a.H, a.C, a.roll_appended, e);
     }
     const int W = sl.wgs_per_xcd;
     // (stand-by: as fir_i8_stream_kernel — the f32 streaming kernel's tile loop on this kernel's workgroups and LDS)
@@ -1384,14 +1171,14 @@ static size_t i8_layout (const ArtFirArgs *a, const MfmaGeom &g, int cgt, I8Geom
     if (!cgt || g.tile_rows != 32 || (g.ktot % I8_KC)) return 0;
     // (outputs != 0: sizing a call's buffer before its launches are cut — any launch of the call has at most this many periods)
     const unsigned int total = outputs ? outputs + (unsigned int) g.P : a->n_end - a->n_begin, periods = (total + g.P - 1) / g.P;
-    const int gg = (g.Q % 4 == 0) ? 1 : (g.Q % 2 == 0) ? 2 : 4;
+    q.g = (g.Q % 4 == 0) ? 1 : (g.Q % 2 == 0) ? 2 : 4;
     q.tr = 32; q.cols = I8_COLS; q.rows_cached = 0; q.jr_rot = 0; q.rows_table = 0; q.tb_base = 0.0; q.tb_lin = q.tb_w = 0; q.tb_n0 = 0u;
     if (artfir_i8_slab_enabled () && cgt >= 4) {
         // slabs where the launch has enough of them (decided from this context's own columns: every fixed-point kernel leaves the
         // same bits, so a shard need not decide as its stream would)
-        const int ppw64 = SL_COLS / cgt;
-        const int sgs = (int)((periods + (unsigned int)(gg * ppw64) - 1) / (unsigned int)(gg * ppw64));
-        const int per_xcd = ((sgs + 7) / 8) * gg * ((g.P + 63) / 64);
+        const int ppw64 = i8_ppw (SL_COLS, cgt);
+        const int sgs = (int)((periods + (unsigned int)(q.g * ppw64) - 1) / (unsigned int)(q.g * ppw64));
+        const int per_xcd = ((sgs + 7) / 8) * q.g * ((g.P + 63) / 64);
         if (per_xcd >= i8_slab_min_tiles ()) { q.tr = 64; q.cols = SL_COLS; }
     }
     for (;;) {  // (as matrix_geometry's ktot, for tiles of tr rows; + 3: a tile's K columns start on a 4-frame block, up to 3 frames early)
@@ -1402,8 +1189,7 @@ static size_t i8_layout (const ArtFirArgs *a, const MfmaGeom &g, int cgt, I8Geom
         break;
     }
     q.tiles = (g.P + q.tr - 1) / q.tr;
-    const int ppw = q.cols / cgt > I8_MAX_PPW ? I8_MAX_PPW : q.cols / cgt;
-    q.g = (g.Q % 4 == 0) ? 1 : (g.Q % 2 == 0) ? 2 : 4;
+    const int ppw = i8_ppw (q.cols, cgt);
     q.gq4 = q.g * g.Q / 4;
     q.super_groups = (int)((periods + (unsigned int)(q.g * ppw) - 1) / (unsigned int)(q.g * ppw));
     q.sg_per_xcd = (q.super_groups + 7) / 8;
@@ -1528,6 +1314,37 @@ size_t artfir_i8_rows_bytes (const ArtFirArgs *a, const MfmaGeom &g, int cgt, un
     return (size_t)(4 / q.g) * (rows_set_layout (g, q, nullptr, nullptr) + 4096);      // (behind the f32 kernel's set: artfir_rows_bytes adds it)
 }
 
+namespace {
+
+// The kernel of a launch from its channels per column group and whether its epilogue substitutes the pass-through slots: the one place that
+// picks an instantiation.  32-slot tiles: the register-staged kernel for 1 and 2 channels per column group — the DMA kernel's 16-byte pieces hold 4
+typedef void (*I8TileKernel) (ArtFirArgs, MfmaGeom, I8Geom, int);
+typedef void (*I8SlabKernel) (ArtFirArgs, MfmaGeom, I8Geom, I8Slab);
+#define I8_PICK(KERNEL, CGT) (pass ? KERNEL<CGT, true> : KERNEL<CGT, false>)
+I8TileKernel i8_tile_kernel (int cgt, bool pass)
+{
+    switch (cgt) {
+        case 32: return I8_PICK (fir_i8_dma_kernel, 32);
+        case 16: return I8_PICK (fir_i8_dma_kernel, 16);
+        case 8: return I8_PICK (fir_i8_dma_kernel, 8);
+        case 4: return I8_PICK (fir_i8_dma_kernel, 4);
+        case 2: return I8_PICK (fir_i8_stream_kernel, 2);
+        default: return I8_PICK (fir_i8_stream_kernel, 1);
+    }
+}
+I8SlabKernel i8_slab_kernel (int cgt, bool pass)              // (cgt >= 4: i8_layout gives no other launch 64-slot tiles)
+{
+    switch (cgt) {
+        case 32: return I8_PICK (fir_i8_slab_kernel, 32);
+        case 16: return I8_PICK (fir_i8_slab_kernel, 16);
+        case 8: return I8_PICK (fir_i8_slab_kernel, 8);
+        default: return I8_PICK (fir_i8_slab_kernel, 4);
+    }
+}
+#undef I8_PICK
+
+} // namespace
+
 int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const MfmaGeom &g_in, int cgt, unsigned int roll_blocks, hipStream_t st)
 {
     static std::atomic<int> launches {0};
@@ -1549,10 +1366,9 @@ int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const Mfm
         a_v.out = a_in->out - (size_t) g.P * a_in->C; a_v.n_skip = slot0;
     }
     size_t need = i8_layout (a, g, cgt, q, (char *) a_in->planes);
-    if (rc && (!need || need > a_in->planes_bytes)) {         // (the partial period in front does not fit: as before)
-        rc = nullptr; a_v = *a_in;
-        need = i8_layout (a, g, cgt, q, (char *) a_in->planes);
-    }
+    // give up the kept rows: this launch alone, in its own buffers, from its own positions
+    auto without_rows = [&] () { rc = nullptr; a_v = *a_in; need = i8_layout (a, g, cgt, q, (char *) a_in->planes); };
+    if (rc && (!need || need > a_in->planes_bytes)) without_rows ();       // (the partial period in front does not fit: as before)
     if (!need || need > a_in->planes_bytes) return 0;
 
     // ---- the set of rows that serves it, or that it builds
@@ -1563,9 +1379,8 @@ int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const Mfm
         const int nsets = 4 / q.g;
         const bool same = rc->lowpass == a_in->lowpass && rc->tr == q.tr && rc->ktot == q.ktot && rc->tiles == q.tiles && rc->g == q.g && rc->slot_tiles == g.slot_tiles &&
                           rc->ktot32 == g.ktot && rc->set_bytes == set_bytes && rc->nsets == nsets;
-        if (artfir_f32_set_bytes (g) + (size_t) nsets * (set_bytes + 4096) > a_in->rows_bytes) {          // (no room: this launch alone, in its own buffers, from its own positions)
-            rc = nullptr; a_v = *a_in;
-            need = i8_layout (a, g, cgt, q, (char *) a_in->planes);
+        if (artfir_f32_set_bytes (g) + (size_t) nsets * (set_bytes + 4096) > a_in->rows_bytes) {          // (no room for the sets)
+            without_rows ();
             if (!need || need > a_in->planes_bytes) return 0;
         }
         else {
@@ -1642,7 +1457,7 @@ int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const Mfm
         sl.parts = q.parts;
         sl.arrivals = (unsigned int *)((char *) a->planes + ART_I8_FLAG_BYTES);
         {   // tiles of each XCD's list that hold outputs: a prefix of the list (a tile holds outputs iff its first column's period does)
-            const int ppw = q.cols / cgt > I8_MAX_PPW ? I8_MAX_PPW : q.cols / cgt;
+            const int ppw = i8_ppw (q.cols, cgt);
             const unsigned int n_out = a->n_end - a->n_begin;
             for (int x = 0; x < 8; ++x) {
                 int live = 0; bool prefix = true;
@@ -1656,25 +1471,13 @@ int artfir_i8_launch (const ArtFirArgs *a_in, const ArtSegTable *segs, const Mfm
             }
         }
         const dim3 wgrid ((unsigned int)(8 * SL_WGS));
-#define I8_SLAB(CGT) do { if (pass) hipLaunchKernelGGL ((fir_i8_slab_kernel<CGT, true>), wgrid, dim3 (SL_THREADS), 0, st, *a, g, q, sl); \
-                          else hipLaunchKernelGGL ((fir_i8_slab_kernel<CGT, false>), wgrid, dim3 (SL_THREADS), 0, st, *a, g, q, sl); } while (0)
-        switch (cgt) { case 32: I8_SLAB (32); break; case 16: I8_SLAB (16); break; case 8: I8_SLAB (8); break; default: I8_SLAB (4); }
-#undef I8_SLAB
+        hipLaunchKernelGGL (i8_slab_kernel (cgt, pass), wgrid, dim3 (SL_THREADS), 0, st, *a, g, q, sl);
         if (a->ev_stop) arthip_event_record (a->ev_stop, (void *) st);
         if (fixup && artfir_pass_fixup (a, g, st)) return -1;
         return 1;
     }
     const dim3 sgrid ((unsigned int)(8 * wgs_per_xcd) + roll_blocks);
-#define I8_GO(CGT) do { if (pass) hipLaunchKernelGGL ((fir_i8_stream_kernel<CGT, true>), sgrid, dim3 (2 * MF_THREADS), 0, st, *a, g, q, wgs_per_xcd); \
-                        else hipLaunchKernelGGL ((fir_i8_stream_kernel<CGT, false>), sgrid, dim3 (2 * MF_THREADS), 0, st, *a, g, q, wgs_per_xcd); } while (0)
-#define I8_DMA(CGT) do { if (pass) hipLaunchKernelGGL ((fir_i8_dma_kernel<CGT, true>), sgrid, dim3 (2 * MF_THREADS), 0, st, *a, g, q, wgs_per_xcd); \
-                         else hipLaunchKernelGGL ((fir_i8_dma_kernel<CGT, false>), sgrid, dim3 (2 * MF_THREADS), 0, st, *a, g, q, wgs_per_xcd); } while (0)
-    // (the register-staged kernel for 1 and 2 channels per column group: the DMA kernel's 16-byte pieces hold 4)
-    if (cgt >= 4) switch (cgt) { case 32: I8_DMA (32); break; case 16: I8_DMA (16); break; case 8: I8_DMA (8); break; default: I8_DMA (4); }
-    else if (cgt == 2) I8_GO (2);
-    else I8_GO (1);
-#undef I8_DMA
-#undef I8_GO
+    hipLaunchKernelGGL (i8_tile_kernel (cgt, pass), sgrid, dim3 (2 * MF_THREADS), 0, st, *a, g, q, wgs_per_xcd);
     if (a->ev_stop) arthip_event_record (a->ev_stop, (void *) st);
     if (fixup && artfir_pass_fixup (a, g, st)) return -1;
     return 1;

@@ -7,10 +7,14 @@ The switches are read once per process, so each variant runs in a process of its
   ARTAMD_I8_SLAB=0        no slabs, periods taken to fill 32-slot tiles (other rows: the parity bar, not the same bits)."""
 import json, os, subprocess, sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+from _hip import HipResampler
+from _oracle import noise, BH, INTERP
 
 
 def _sessions(**env):
@@ -43,3 +47,26 @@ def test_fixed_point_files_under_the_switch(env):
                         os.path.join(HERE, "test_gpu_fixed_point.py"), os.path.join(HERE, "test_gpu_short_periods.py"),
                         "-k", "not the_rule"], env=dict(os.environ, **env), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+def test_register_staged_and_dma_forms_leave_the_same_bits():
+    """Exponent blocks depend on the ratio and the filter only, and a channel's exponent on its own samples: two channels played alone
+    (2 per column group: fir_i8_stream_kernel, registers) and as channels 0-1 of a 4-channel stream (fir_i8_dma_kernel) are the same bytes."""
+    blocks, ratio = (24000, 20001), 48000 / 44100
+    x2, _ = noise(sum(blocks) * 2, state=20001)
+    other, _ = noise(sum(blocks) * 2, state=4441)
+    x2 = x2.reshape(-1, 2)
+    x4 = np.ascontiguousarray(np.concatenate([x2, other.reshape(-1, 2)], axis=1))
+    outs = {}
+    for ch, x, form in ((2, x2, "fir_i8_stream_kernel"), (4, x4, "fir_i8_dma_kernel")):
+        r = HipResampler(ch, 156, 156, 0.0, BH | INTERP, kernel=7)
+        r.advance(156 / 2)
+        pos, ys = 0, []
+        for n in blocks:
+            u, g, y = r.process(x[pos:pos + n], int(n * ratio) + 4000, ratio)
+            assert u == n
+            assert r.fixed_point()[0] == 1 and r.fixed_point_kernel() == form, (ch, n, r.fixed_point(), r.fixed_point_kernel())
+            ys.append(np.array(y[:g], copy=True)); pos += n
+        outs[ch] = np.concatenate(ys)
+    assert outs[2].shape[0] == outs[4].shape[0]
+    assert np.ascontiguousarray(outs[4][:, :2]).tobytes() == outs[2].tobytes()

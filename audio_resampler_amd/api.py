@@ -150,6 +150,9 @@ def _bind(width):
         "decimateHipClipped": (C.c_long, [DP]),
         "decimateHipShardCount": (C.c_int, [DP]),
         "decimateProcessBatchInterleavedLEDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr]),
+        "decimateProcessPlanarLEDevice": (None, [DP, ptr, C.c_long, C.c_int, ptr, C.c_long]),
+        "decimateProcessBatchPlanarLEDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr]),
+        "decimateHipReset": (None, [DP]),
         "artamdErrorCount": (C.c_int, []),
         "artamdPeriodMultiple": (C.c_int, [C.c_int]),
         "artamdPeriodMultipleRows": (C.c_int, [C.c_int, C.c_int]),
@@ -412,6 +415,15 @@ def _bind(width):
         def process_device(self, d_in, frames, d_out):
             self.L.decimateProcessInterleavedLEDevice(self.p, _dev_ptr(d_in), frames, _dev_ptr(d_out))
 
+        def process_planar_device(self, d_in, in_pitch, frames, d_out, out_pitch):
+            """decimateProcessPlanarLEDevice: channel c of the input at d_in + c * in_pitch (samples), of the output at d_out + c * out_pitch
+            (bytes); a pitch of 0: that side is interleaved.  The bytes of process_device on the transposed input, transposed back"""
+            self.L.decimateProcessPlanarLEDevice(self.p, _dev_ptr(d_in), in_pitch, frames, _dev_ptr(d_out), out_pitch)
+
+        def reset(self):
+            """decimateHipReset: back to what the constructor left (the clip counter keeps its total), on the context's stream"""
+            self.L.decimateHipReset(self.p)
+
         def clipped(self):
             return self.L.decimateHipClipped(self.p)
 
@@ -588,6 +600,82 @@ def _bind(width):
         if rc < 0:
             raise RuntimeError("decimateProcessBatchInterleavedLEDevice failed")
         return rc
+
+    def decimate_batch_planar_device(decimators, d_ins, in_pitches, n_ins, d_outs, out_pitches):
+        """decimateProcessBatchPlanarLEDevice: decimate_batch_device with a pitch per buffer (channel c of item i's input at
+        d_ins[i] + c * in_pitches[i] samples, of its output at d_outs[i] + c * out_pitches[i] bytes; 0: that side of that item is
+        interleaved; None for a pitch list: every item's is).  Returns the launch count (raises if the call returned -1)."""
+        n = len(decimators)
+        ctx = (C.c_void_p * n)(*[C.cast(d.p, C.c_void_p) for d in decimators])
+        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
+        rc = lib().decimateProcessBatchPlanarLEDevice(
+            ctx, n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), pitches(in_pitches), (C.c_int * n)(*[int(v) for v in n_ins]),
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches))
+        if rc < 0:
+            raise RuntimeError("decimateProcessBatchPlanarLEDevice failed")
+        return rc
+
+    class ClipDecimator:
+        """Whole clips, channels-first, to integer PCM: x [B, C, T] (or [C, T]) on the GPU in, (pcm uint8 [B, C, T * nbytes], clipped)
+        out — one decimateProcessBatchPlanarLEDevice call on the tensor's own rows, no copy of the samples on the way.  Clip i is what
+        a fresh Decimator makes of x[i, :, :lengths[i]]; pcm[i, :, lengths[i] * nbytes:] is zero; clipped[i] is clip i's count of
+        clipped samples (reading it waits for the call).  Holds a pool of up to max_batch contexts, reset for every call, on the
+        caller's current torch stream; a larger batch is made max_batch clips at a time.  Takes ClipResampler's (y, out_lengths) as
+        they come."""
+
+        def __init__(self, channels, bits, nbytes, gain, rate, flags, max_batch=1024):
+            self.channels, self.bits, self.nbytes, self.max_batch = channels, bits, nbytes, max(1, int(max_batch))
+            self._init = (channels, bits, nbytes, gain, rate, flags)
+            self.pool, self._seen = [], []                       # the contexts and their clip counters' totals after the last call
+
+        def close(self):
+            for d in self.pool:
+                d.close()
+            self.pool, self._seen = [], []
+
+        def as_int(self, pcm):
+            """pcm of 2 or 4 bytes per sample as int16 / int32 [B, C, T] (a view: little-endian samples on a little-endian host)"""
+            import torch
+            if self.nbytes not in (2, 4):
+                raise ValueError("as_int: 2 or 4 bytes per sample")
+            return pcm.view(torch.int16 if self.nbytes == 2 else torch.int32)
+
+        def __call__(self, x, lengths=None):
+            import torch
+            if x.dim() == 2:
+                x = x.unsqueeze(0)
+            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
+                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
+            if x.shape[2] and x.stride(2) != 1:
+                x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
+            B, Cn, T = x.shape
+            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
+                raise ValueError("lengths: one entry per clip, 0 .. T")
+            while len(self.pool) < min(B, self.max_batch):
+                self.pool.append(Decimator(*self._init))
+                self._seen.append(0)
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            for d in self.pool[:min(B, self.max_batch)]:
+                d.set_stream(stream)
+            pcm = torch.zeros(B, Cn, T * self.nbytes, dtype=torch.uint8, device=x.device)
+            size = x.element_size()
+            xp, pp = x.data_ptr(), pcm.data_ptr()
+            in_pitch, out_pitch = (x.stride(1), pcm.stride(1)) if Cn > 1 else (0, 0)     # (one channel: the same call in either layout)
+            clipped = []
+            for b0 in range(0, B, self.max_batch):
+                idx = range(b0, min(B, b0 + self.max_batch))
+                pool = self.pool[:len(idx)]
+                for d in pool:
+                    d.reset()
+                before = self._seen[:len(pool)]                     # (only this object's calls move the pool's counters)
+                decimate_batch_planar_device(
+                    pool, [xp + i * x.stride(0) * size for i in idx], [in_pitch] * len(idx), [lengths[i] for i in idx],
+                    [pp + i * pcm.stride(0) for i in idx], [out_pitch] * len(idx))
+                after = [d.clipped() for d in pool]
+                self._seen[:len(pool)] = after
+                clipped += [a - b for a, b in zip(after, before)]
+            return pcm, torch.tensor(clipped, dtype=torch.int64)
 
     def biquad_batch_device(banks, d_bufs, frames):
         """biquadBankApplyBatchInterleavedDevice over a list of BiquadBank objects: one launch per section count for the banks on

@@ -269,17 +269,22 @@ typedef struct {
 /* returns 1 when the generator state was written to a->gens_next (caller swaps), 0 otherwise, <0 on error */
 int arthip_decimate (const ArtDecArgs *a, const art_s *d_in, int frames, unsigned char *d_out, void *stream);
 int arthip_decimate_planar (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream);
+/* arthip_decimate on planes: channel c of the input at d_in + c * in_pitch (samples), of the output at d_out + c * out_pitch (bytes); a
+ * pitch of 0: that side is interleaved.  The same kernel as the interleaved call would run, and the same return values
+ * (arthip_decimate_planar above is the host-pointer planar call's: always the one-lane kernel) */
+int arthip_decimate_pitched (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream);
 /* Many contexts' calls, one launch per class (decimateProcessBatchInterleavedLEDevice).  The host builds one table per call (the
  * classes' item arrays one after another, each 16-byte aligned), uploads it once and launches every class from its slice. */
 typedef struct {                         /* one channel of one context: a lane of the serial wave (noise shaping, or short calls) */
-    const art_s *in;                     /* the context's input + channel; frame f at in [f * stride] */
-    unsigned char *out;                  /* the context's output + channel * bytes; frame f at out [f * stride * bytes] */
+    const art_s *in;                     /* the lane's first input sample (interleaved: input + channel, planar: its plane); frame f at in [f * stride] */
+    unsigned char *out;                  /* the lane's first output byte (interleaved: output + channel * bytes, planar: its plane); frame f at out [f * out_stride * bytes] */
     art_s *feedback;                     /* &feedback [channel] */
     uint32_t *gen;                       /* &gens [channel] (NULL without dither) */
     Biquad *shaper;                      /* &shapers [channel] (NULL without noise shaping) */
     unsigned long long *clipped;         /* the context's counter */
     art_s scale;
     int stride, frames, bits, bytes, dither_type;     /* frames 0: an empty lane (padding of the last workgroup) */
+    int out_stride;                      /* stride / out_stride: frames between the lane's samples on either side — the channel count, or 1 on a planar side */
 } ArtDecLane;
 typedef struct {                         /* one context of a time-parallel launch (no noise shaping, >= 64 frames) */
     const art_s *in;
@@ -290,6 +295,7 @@ typedef struct {                         /* one context of a time-parallel launc
     long task0;                          /* first (channel, segment) task of this context in the launch's flattened task space */
     art_s scale;
     int C, frames, bits, bytes, dither_type;
+    long in_pitch, out_pitch;            /* samples / bytes between the planes of that side; 0: that side is interleaved */
 } ArtDecTask;
 typedef struct {                         /* a class's slice of a batch call's table (16-byte aligned) */
     int count;                           /* items; in a serial class, lanes (a multiple of `lanes`: empty lanes pad the last workgroup) */
@@ -300,6 +306,7 @@ typedef struct {
     int serial;                          /* 1: ArtDecLane items (lanes per workgroup slice.lanes), 0: ArtDecTask items */
     int order, dither;                   /* the shaper order (0: none) and whether dither is on: every item of the class shares them */
     long tasks;                          /* time-parallel: total tasks */
+    int pitched;                         /* an item of the class has a planar side: the kernel's PITCHED instantiation */
     ArtBatchSlice slice;
 } ArtDecClass;
 #define ART_DEC_SEG 32                   /* frames of one channel per task of the time-parallel kernels (even: generator pairs) */
@@ -311,6 +318,9 @@ int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, v
  * of arthip_decimate_batch_lanes): the measurements behind that rule (tools/bench_decimate_batch.py) — pcm_host.c */
 int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                            unsigned char *const *d_outputs, int lanes);
+/* ... and decimateProcessBatchPlanarLEDevice likewise: the one body of both layouts (NULL pitch arrays: artamd_decimate_batch) */
+int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                  const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches, int lanes);
 int arthip_biquad_chain (Biquad *d_sections, int C, int S, art_s *d_buf, int frames, int stride, void *stream);
 /* Many banks' calls, one launch per section count (biquadBankApplyBatchInterleavedDevice).  A lane is one channel of one bank;
  * each class's lanes are one slice of the call's table (16-byte aligned), uploaded with arthip_table_upload. */

@@ -529,6 +529,8 @@ struct artamd_decimator {
     int nshards; Decimate **shards; int *shard_first; void **ev_shard; void *ev_parent;
     unsigned long batch_stamp;                                     /* the last batch call that named this context */
     void *d_batch; size_t batch_cap;                               /* a batch call's table, when this context leads it */
+    unsigned char *d_state0;                                       /* the state block as decimateInit left it (decimateHipReset copies it back) */
+    int rate, first_channel;                                       /* what the host mirrors were made from */
 };
 #define DEC_KERNEL_COPY_LIMIT ((size_t) 1 << 20)
 
@@ -561,6 +563,26 @@ static void shaper_for (Biquad *f, int flags, int rate)
 
 static uint32_t lcg_step (uint32_t r) { return ((r << 4) - r) ^ 1; }
 
+/* the host-visible state of a fresh leaf context: feedback zero, the generators' seeds, the shapers' empty histories */
+static void dec_fresh_mirrors (Decimate *cxt)
+{
+    const int C = cxt->numChannels;
+    memset (cxt->feedback, 0, sizeof (art_s) * (size_t) C);
+    if (cxt->tpdf_generators) {
+        /* per-channel seeds: little-endian words cut from the byte stream (state >> 24), three steps per byte */
+        uint32_t s = 0x31415926;
+        memset (cxt->tpdf_generators, 0, sizeof (uint32_t) * (size_t) C);
+        for (int c = -cxt->hip->first_channel; c < C; ++c)
+            for (int b = 0; b < 4; ++b) {
+                if (c >= 0) cxt->tpdf_generators [c] |= (uint32_t)(s >> 24) << (8 * b);
+                s = lcg_step (lcg_step (lcg_step (s)));
+            }
+    }
+    if (cxt->noise_shapers)
+        for (int c = 0; c < C; ++c)
+            shaper_for (cxt->noise_shapers + c, cxt->flags, cxt->hip->rate);
+}
+
 /* an ordinary context on the current device; `firstChannel`: its channels are channels firstChannel.. of a wider stream (the
  * dither generators of a stream are seeded channel after channel from one byte stream, decimator.c:40-52) */
 static Decimate *dec_init_leaf (int numChannels, int outputBits, int outputBytes, double outputGain, int sampleRate, int flags, int firstChannel)
@@ -572,6 +594,7 @@ static Decimate *dec_init_leaf (int numChannels, int outputBits, int outputBytes
     if (!cxt || !hip) { free (cxt); free (hip); return NULL; }
     cxt->hip = hip;
     hip->device = arthip_current_device ();
+    hip->rate = sampleRate; hip->first_channel = firstChannel;
     cxt->numChannels = C; cxt->outputBits = outputBits; cxt->outputBytes = outputBytes;
     cxt->outputGain = outputGain; cxt->flags = flags;
     cxt->feedback = calloc (C, sizeof (art_s));
@@ -583,8 +606,9 @@ static Decimate *dec_init_leaf (int numChannels, int outputBits, int outputBytes
         const size_t o_sh = off;     off += (sizeof (Biquad) * C + 15) & ~(size_t) 15;
         hip->state_bytes = off;
         hip->d_state = arthip_malloc (off);
+        hip->d_state0 = arthip_malloc (off);
         hip->h_state = arthip_host_alloc (off);
-        if (hip->d_state && hip->h_state) {
+        if (hip->d_state && hip->d_state0 && hip->h_state) {
             arthip_zero (hip->d_state, off, NULL);
             hip->d_clipped = (unsigned long long *) hip->d_state;
             hip->d_feedback = (art_s *)(hip->d_state + o_fb);
@@ -593,25 +617,15 @@ static Decimate *dec_init_leaf (int numChannels, int outputBits, int outputBytes
         }
     }
 
-    if ((flags & DITHER_ENABLED) && hip->d_state) {
-        /* per-channel seeds: little-endian words cut from the byte stream (state >> 24), three steps per byte */
-        uint32_t s = 0x31415926;
+    if ((flags & DITHER_ENABLED) && hip->d_gens) {
         cxt->tpdf_generators = calloc (C, sizeof (uint32_t));
-        for (int c = -firstChannel; c < C; ++c)
-            for (int b = 0; b < 4; ++b) {
-                if (c >= 0) cxt->tpdf_generators [c] |= (uint32_t)(s >> 24) << (8 * b);
-                s = lcg_step (lcg_step (lcg_step (s)));
-            }
         cxt->dither_type = (flags & DITHER_HIGHPASS) ? -1 : (flags & DITHER_LOWPASS) ? 1 : 0;
-        arthip_h2d (hip->d_gens, cxt->tpdf_generators, sizeof (uint32_t) * C, NULL);
     }
-
-    if ((flags & SHAPING_ENABLED) && hip->d_state) {
-        cxt->noise_shapers = calloc (C, sizeof (Biquad));
-        for (int c = 0; c < C; ++c)
-            shaper_for (cxt->noise_shapers + c, flags, sampleRate);
-        arthip_h2d (hip->d_shapers, cxt->noise_shapers, sizeof (Biquad) * C, NULL);
-    }
+    if ((flags & SHAPING_ENABLED) && hip->d_shapers) cxt->noise_shapers = calloc (C, sizeof (Biquad));
+    if (cxt->feedback) dec_fresh_mirrors (cxt);
+    if (cxt->tpdf_generators) arthip_h2d (hip->d_gens, cxt->tpdf_generators, sizeof (uint32_t) * C, NULL);
+    if (cxt->noise_shapers) arthip_h2d (hip->d_shapers, cxt->noise_shapers, sizeof (Biquad) * C, NULL);
+    if (hip->d_feedback) arthip_d2d (hip->d_state0, hip->d_state, hip->state_bytes, NULL);       /* what decimateHipReset restores */
 
     if (arthip_sync (NULL) || !hip->d_feedback || !hip->d_clipped) {
         fprintf (stderr, "artamd: decimateInit: device setup failed: %s\n", arthip_last_error ());
@@ -695,7 +709,7 @@ void decimateFree (Decimate *cxt)
     if (hip) {
         ENTER_DEVICE (hip);
         arthip_sync (hip->stream);
-        arthip_free (hip->d_state); arthip_host_free (hip->h_state);
+        arthip_free (hip->d_state); arthip_free (hip->d_state0); arthip_host_free (hip->h_state);
         arthip_free (hip->d_in); arthip_free (hip->d_out); arthip_host_free (hip->h_in); arthip_host_free (hip->h_out);
         arthip_free (hip->d_batch);
         for (int s = 0; s < hip->nshards; ++s) {
@@ -803,6 +817,93 @@ void decimateProcessInterleavedLEDevice (Decimate *cxt, const artsample_t *d_inp
     LEAVE_DEVICE (cxt->hip);
 }
 
+/* a leaf context's call with a pitch on either side (0: interleaved); a one-channel context is the same call in either layout */
+static void dec_leaf_pitched (Decimate *cxt, const art_s *d_input, long in_pitch, int frames, unsigned char *d_output, long out_pitch)
+{
+    ArtDecArgs a;
+    if (cxt->numChannels == 1) in_pitch = out_pitch = 0;
+    dec_args (cxt, &a);
+    dec_swap_if (cxt, arthip_decimate_pitched (&a, d_input, in_pitch, frames, d_output, out_pitch, cxt->hip->stream));
+}
+
+/* dec_sharded_device_call with planes on either side: a shard's channels are a run of the caller's planes, which the shard reads
+ * or writes where they lie; an interleaved side (pitch 0) goes through the shard's staging as there */
+static void dec_sharded_planar_call (Decimate *cxt, const art_s *d_input, long in_pitch, int frames, unsigned char *d_output, long out_pitch)
+{
+    struct artamd_decimator *hip = cxt->hip;
+    const int C = cxt->numChannels, B = cxt->outputBytes, prev = arthip_current_device ();
+    const int wps = (int)(sizeof (art_s) / 4);
+
+    for (int k = 0; k < hip->nshards; ++k) {
+        Decimate *leaf = hip->shards [k];
+        const int width = hip->shard_first [k + 1] - hip->shard_first [k];
+        arthip_set_device (leaf->hip->device);
+        if (dec_reserve (leaf, in_pitch ? 0 : (size_t) frames * width * sizeof (art_s), out_pitch ? 0 : (size_t) frames * width * B)) {
+            pcm_fail ("sharded decimator: device allocation failed (output zeroed)");
+            arthip_set_device (hip->device);
+            if (!out_pitch) arthip_zero (d_output, (size_t) frames * C * B, hip->stream);
+            else for (int c = 0; c < C; ++c) arthip_zero (d_output + (size_t) c * out_pitch, (size_t) frames * B, hip->stream);
+            if (prev >= 0) arthip_set_device (prev);
+            return;
+        }
+    }
+    arthip_set_device (hip->device);
+    arthip_event_record (hip->ev_parent, hip->stream);
+    for (int k = 0; k < hip->nshards; ++k) {
+        Decimate *leaf = hip->shards [k];
+        struct artamd_decimator *sp = leaf->hip;
+        const int first = hip->shard_first [k], width = hip->shard_first [k + 1] - first;
+        arthip_set_device (sp->device);
+        arthip_stream_wait_event (sp->stream, hip->ev_parent);
+        if (!in_pitch) arthip_slice_copy (sp->d_in, (size_t) width * wps, d_input + first, (size_t) C * wps, width * wps, (size_t) frames, sp->stream);
+        dec_leaf_pitched (leaf, in_pitch ? d_input + (size_t) first * in_pitch : sp->d_in, in_pitch, frames,
+                          out_pitch ? d_output + (size_t) first * out_pitch : sp->d_out, out_pitch);
+        if (!out_pitch) arthip_slice_copy_bytes (d_output + (size_t) first * B, (size_t) C * B, sp->d_out, (size_t) width * B, width * B, (size_t) frames, sp->stream);
+        arthip_event_record (hip->ev_shard [k], sp->stream);
+    }
+    arthip_set_device (hip->device);
+    for (int k = 0; k < hip->nshards; ++k)
+        arthip_stream_wait_event (hip->stream, hip->ev_shard [k]);
+    if (prev >= 0) arthip_set_device (prev);
+}
+
+void decimateProcessPlanarLEDevice (Decimate *cxt, const artsample_t *d_input, long inputPitch, int numInputFrames,
+                                    unsigned char *d_output, long outputPitch)
+{
+    if (numInputFrames <= 0) return;
+    if (cxt->numChannels == 1) inputPitch = outputPitch = 0;
+    if (!inputPitch && !outputPitch) { decimateProcessInterleavedLEDevice (cxt, d_input, numInputFrames, d_output); return; }
+    if (cxt->hip->nshards) { dec_sharded_planar_call (cxt, d_input, inputPitch, numInputFrames, d_output, outputPitch); return; }
+    ENTER_DEVICE (cxt->hip);
+    dec_leaf_pitched (cxt, d_input, inputPitch, numInputFrames, d_output, outputPitch);
+    LEAVE_DEVICE (cxt->hip);
+}
+
+/* back to what decimateInit left, on the context's stream: the device state block from its image (all but the clip counter, which
+ * counts since init), the host mirrors recomputed */
+void decimateHipReset (Decimate *cxt)
+{
+    struct artamd_decimator *hip = cxt->hip;
+    if (hip->nshards) {
+        const int prev = arthip_current_device ();
+        for (int k = 0; k < hip->nshards; ++k) {
+            Decimate *leaf = hip->shards [k];
+            const int first = hip->shard_first [k], width = hip->shard_first [k + 1] - first;
+            decimateHipReset (leaf);            /* (on the shard's own stream, behind the shard's part of every earlier call) */
+            if (cxt->tpdf_generators && leaf->tpdf_generators) memcpy (cxt->tpdf_generators + first, leaf->tpdf_generators, sizeof (uint32_t) * width);
+            if (cxt->noise_shapers && leaf->noise_shapers) memcpy (cxt->noise_shapers + first, leaf->noise_shapers, sizeof (Biquad) * width);
+        }
+        memset (cxt->feedback, 0, sizeof (art_s) * (size_t) cxt->numChannels);
+        if (prev >= 0) arthip_set_device (prev);
+        return;
+    }
+    ENTER_DEVICE (hip);
+    if (arthip_d2d (hip->d_state + 16, hip->d_state0 + 16, hip->state_bytes - 16, hip->stream)) pcm_fail ("decimateHipReset: the state could not be restored");
+    if (hip->d_gens > hip->d_gens_alt) dec_swap_if (cxt, 1);          /* the image holds the generators in the first of the two arrays */
+    LEAVE_DEVICE (hip);
+    dec_fresh_mirrors (cxt);
+}
+
 /* ------------------------------------------------------------------------------------------
  * Many contexts, one launch per class of work
  *
@@ -825,8 +926,8 @@ static int lane_order (const void *pa, const void *pb)     /* longest first; the
 static unsigned long *dec_stamp (const void *cxt) { return &((const Decimate *) cxt)->hip->batch_stamp; }
 
 /* lanes > 0: every serial class gets that many lanes per workgroup (the measurements of the rule); 0: the rule */
-int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
-                           unsigned char *const *d_outputs, int lanes)
+int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                  const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches, int lanes)
 {
     if (n <= 0) return 0;
     if (artamd_batch_distinct ((const void *const *) cxts, n, dec_stamp, "decimate", "context")) return -1;
@@ -834,11 +935,12 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
     struct artamd_decimator *lead = cxts [0]->hip;
     ArtDecArgs *args = malloc (sizeof (ArtDecArgs) * (size_t) n);
     int *cls_of = malloc (sizeof (int) * (size_t) n);
+    long *pitch = malloc (sizeof (long) * 2 * (size_t) n);         /* [2 i]: item i's input pitch, [2 i + 1]: its output pitch (0: interleaved) */
     ArtDecClass cls [DEC_BATCH_CLASSES];
     DecLaneRef *refs = NULL;
     unsigned char *table = NULL;
     int launches = 0, rc = -1, most = 0;
-    if (!args || !cls_of) { pcm_fail ("decimate batch: out of host memory"); goto out; }
+    if (!args || !cls_of || !pitch) { pcm_fail ("decimate batch: out of host memory"); goto out; }
     memset (cls, 0, sizeof (cls));
     for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
         cls [k].serial = k >= 2;
@@ -851,8 +953,11 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
         struct artamd_decimator *hip = cxts [i]->hip;
         cls_of [i] = -1;
         if (numInputFrames [i] <= 0) continue;
+        const int planes = cxts [i]->numChannels > 1;              /* (one channel: the same call in either layout) */
+        const long ip = pitch [2 * i] = planes && inputPitches ? inputPitches [i] : 0;
+        const long op = pitch [2 * i + 1] = planes && outputPitches ? outputPitches [i] : 0;
         if (hip->nshards || hip->stream != lead->stream || hip->device != lead->device) {
-            decimateProcessInterleavedLEDevice (cxts [i], d_inputs [i], numInputFrames [i], d_outputs [i]);
+            decimateProcessPlanarLEDevice (cxts [i], d_inputs [i], ip, numInputFrames [i], d_outputs [i], op);
             ++launches;
             continue;
         }
@@ -861,6 +966,7 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
         const int k = numInputFrames [i] >= 64 && !a->shaping_on ? (a->dither_on != 0)
                     : 2 + 2 * (a->shaping_on ? (a->shaping_order >= 1 && a->shaping_order <= 4 ? a->shaping_order : 4) : 0) + (a->dither_on != 0);
         cls_of [i] = k;
+        if (ip || op) cls [k].pitched = 1;
         if (cls [k].serial) { cls [k].slice.count += a->C; if (a->C > most) most = a->C; }
         else { cls [k].tasks += (long) a->C * ((numInputFrames [i] + ART_DEC_SEG - 1) / ART_DEC_SEG); cls [k].slice.count++; }
     }
@@ -895,6 +1001,7 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
                 it->feedback = a->feedback; it->gens = a->gens; it->gens_next = a->gens_next; it->clipped = a->clipped;
                 it->task0 = task0; it->scale = a->scale;
                 it->C = a->C; it->frames = numInputFrames [i]; it->bits = a->bits; it->bytes = a->bytes; it->dither_type = a->dither_type;
+                it->in_pitch = pitch [2 * i]; it->out_pitch = pitch [2 * i + 1];
                 task0 += (long) a->C * ((numInputFrames [i] + ART_DEC_SEG - 1) / ART_DEC_SEG);
             }
             continue;
@@ -908,12 +1015,13 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
         for (int j = 0; j < m; ++j) {
             const int i = refs [j].ctx, c = refs [j].channel;
             const ArtDecArgs *a = &args [i];
-            l [j].in = d_inputs [i] + c; l [j].out = d_outputs [i] + (size_t) c * a->bytes;
+            const long ip = pitch [2 * i], op = pitch [2 * i + 1];
+            l [j].in = d_inputs [i] + (ip ? c * ip : c); l [j].out = d_outputs [i] + (op ? c * op : (long) c * a->bytes);
             l [j].feedback = a->feedback + c;
             l [j].gen = a->dither_on ? a->gens + c : NULL;
             l [j].shaper = a->shaping_on ? a->shapers + c : NULL;
             l [j].clipped = a->clipped; l [j].scale = a->scale;
-            l [j].stride = a->C; l [j].frames = numInputFrames [i]; l [j].bits = a->bits; l [j].bytes = a->bytes; l [j].dither_type = a->dither_type;
+            l [j].stride = ip ? 1 : a->C; l [j].out_stride = op ? 1 : a->C; l [j].frames = numInputFrames [i]; l [j].bits = a->bits; l [j].bytes = a->bytes; l [j].dither_type = a->dither_type;
         }
     }
 
@@ -937,8 +1045,20 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
         LEAVE_DEVICE (lead);
     }
 out:
-    free (args); free (cls_of); free (refs); free (table);
+    free (args); free (cls_of); free (pitch); free (refs); free (table);
     return rc;
+}
+
+int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
+                           unsigned char *const *d_outputs, int lanes)
+{
+    return artamd_decimate_batch_planar (cxts, n, d_inputs, NULL, numInputFrames, d_outputs, NULL, lanes);
+}
+
+int decimateProcessBatchPlanarLEDevice (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                        const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches)
+{
+    return artamd_decimate_batch_planar (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, 0);
 }
 
 int decimateProcessBatchInterleavedLEDevice (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,

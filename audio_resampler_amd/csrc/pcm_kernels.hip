@@ -791,9 +791,191 @@ __device__ __forceinline__ art_s round_half_up (art_s d)
 
 constexpr int DEC_SEG = ART_DEC_SEG;               // consecutive samples of one channel per dither task (even; the batch host counts tasks with it)
 
-template <int ORDER, bool DITHER>                  // ORDER 0 = no noise shaping
+// ---------------------------------------------------------------------------------------------------
+// Channels-first (planar) sides: channel c of a buffer is a plane, c * pitch away from the first.  The arithmetic of every kernel
+// below is untouched; a planar side only changes where a lane's or a task's samples are fetched and where its bytes land.  A
+// plane's frames are consecutive, so a run of them is moved in whole aligned units cut at the boundaries of the run's OWN address
+// (layout_kernels.hip does the same for samples): element by element before the first boundary and after the last, one access per
+// unit between — 16-byte loads, 16-byte stores in the time-parallel kernels, 4-byte stores in the serial kernels' helper waves
+// (dec_store_unit_of says why).  A pitch or a base of any alignment costs a run a head and a tail and nothing else.
+// The kernels take a template parameter PITCHED: false is the interleaved kernel as it always was, true takes a pitch per side
+// (0: that side interleaved).  The single-call kernels branch on it uniformly; in the batch kernels a side belongs to a lane
+// (serial class) or an item (time-parallel class), which share workgroups whatever their layout, so there the branch is per lane
+// or per task and a wave that holds both layouts pays for both.
+// ---------------------------------------------------------------------------------------------------
+constexpr int DEC_VEC = 16 / (int) sizeof (art_s);
+typedef art_s dec_vec_t __attribute__ ((ext_vector_type (DEC_VEC)));
+
+struct DecFmt { int nbytes, width, pad, hi, lo, shift; uint32_t bias; };
+__device__ __forceinline__ DecFmt dec_fmt (int bits, int bytes)
+{
+    DecFmt f;
+    f.nbytes = bytes; f.width = (bits + 7) / 8; f.pad = bytes - f.width;
+    f.hi = (1 << (bits - 1)) - 1; f.lo = ~f.hi;
+    f.shift = (24 - bits) % 8;
+    f.bias = bits <= 8 ? 128u : 0u;
+    return f;
+}
+// the nbytes little-endian output bytes of a clipped code value, as one word (the kernels' byte stores: pad zero bytes, then
+// the value's `width` bytes)
+__device__ __forceinline__ uint32_t dec_word (const DecFmt &f, int q)
+{
+    const uint32_t v = ((uint32_t) q << f.shift) + f.bias;
+    return (v & (0xffffffffu >> (32 - 8 * f.width))) << (8 * f.pad);
+}
+
+// w's bytes at byte `pos` (0..15) of the 16-byte image hi:lo; bytes past the image are dropped
+__device__ __forceinline__ void dec_place (uint64_t &lo, uint64_t &hi, uint32_t w, int pos)
+{
+    const int sh = pos * 8;
+    if (sh < 64) { lo |= (uint64_t) w << sh; if (sh > 32) hi |= (uint64_t) w >> (64 - sh); }
+    else hi |= (uint64_t) w << (sh - 64);
+}
+__device__ __forceinline__ void dec_put_bytes (unsigned char *unit, uint64_t lo, uint64_t hi, int from, int to)     // bytes [from, to) of the image
+{
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (j >= from && j < to) unit [j] = (unsigned char)(j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8)));
+}
+__device__ __forceinline__ void dec_put_unit (unsigned char *unit, uint64_t lo, uint64_t hi)                        // unit: 16-byte aligned
+{
+    *reinterpret_cast<uint4 *> (unit) = make_uint4 ((uint32_t) lo, (uint32_t)(lo >> 32), (uint32_t) hi, (uint32_t)(hi >> 32));
+}
+
+// f (i, x) for the cnt consecutive samples at p, in order
+template <typename F>
+__device__ __forceinline__ void dec_for_run (const art_s *p, int cnt, F f)
+{
+    const int head = min (cnt, (int)(((16u - (unsigned int)((uintptr_t) p & 15u)) & 15u) / sizeof (art_s)));
+    int i = 0;
+    for (; i < head; ++i) f (i, p [i]);
+    for (; i + DEC_VEC <= cnt; i += DEC_VEC) {
+        const dec_vec_t v = *reinterpret_cast<const dec_vec_t *> (p + i);
+#pragma unroll
+        for (int j = 0; j < DEC_VEC; ++j) f (i + j, v [j]);
+    }
+    for (; i < cnt; ++i) f (i, p [i]);
+}
+
+// A thread's consecutive output bytes, in order: whole 16-byte units are one store each, the run's first and last unit go byte by byte
+struct DecPacker {
+    unsigned char *unit; uint64_t lo, hi; int pos, first;        // the unit being filled, its image, the next byte and the first valid one
+    __device__ __forceinline__ void begin (unsigned char *p)
+    {
+        const int a = (int)((uintptr_t) p & 15u);
+        unit = p - a; pos = first = a; lo = hi = 0;
+    }
+    __device__ __forceinline__ void put (uint32_t w, int nb)      // w: nb bytes (1..4), the rest zero
+    {
+        dec_place (lo, hi, w, pos);
+        const int np = pos + nb;
+        if (np < 16) { pos = np; return; }
+        if (first == 0) dec_put_unit (unit, lo, hi); else dec_put_bytes (unit, lo, hi, first, 16);
+        const int over = np - 16;                                 // bytes of w that belong to the next unit (0..3)
+        lo = over ? (uint64_t)(w >> (8 * (nb - over))) : 0; hi = 0;
+        unit += 16; first = 0; pos = over;
+    }
+    __device__ __forceinline__ void end () { if (pos > first) dec_put_bytes (unit, lo, hi, first, pos); }
+};
+
+// Unit u of a run of n consecutive samples at p (units are the 16-byte lines of the run's own address; at most
+// dec_load_units (n) of them): store (i, x) for its samples
+__device__ __forceinline__ int dec_load_units (int n) { return (n + 2 * DEC_VEC - 2) / DEC_VEC; }
+template <typename F>
+__device__ __forceinline__ void dec_load_unit (const art_s *p, int n, int u, F store)
+{
+    const int a = (int)(((uintptr_t) p & 15u) / sizeof (art_s));
+    const int b = u * DEC_VEC - a, e = b + DEC_VEC;
+    if (b >= 0 && e <= n) {
+        const dec_vec_t v = *reinterpret_cast<const dec_vec_t *> (p + b);
+#pragma unroll
+        for (int j = 0; j < DEC_VEC; ++j) store (b + j, v [j]);
+    }
+    else
+        for (int i = max (b, 0); i < min (e, n); ++i) store (i, p [i]);
+}
+
+// Unit u of the n * NB consecutive output bytes at p, a unit being UB = 4 aligned bytes of the run's own address (at most
+// dec_store_units (n * NB) of them): word (f, counted) is frame f's bytes (dec_word); `counted` is true in exactly one unit per
+// frame — the one that holds the frame's first byte — for the clip count.  Every frame that touches the unit is fetched (their number
+// is bounded by NB and UB alone, so the fetches are independent of each other and of the unit's offset), laid out from the first
+// one's first byte, and the image is then moved down by the bytes that lie before the unit.  A whole unit is one store, the run's
+// first and last go byte by byte.
+// UB: the serial kernels' helper waves have a few hundred bytes per lane and chunk to store and a chunk's step waits for the longest
+// THREAD among them, so they take 4-byte units, not 16-byte ones (a quarter of the code per thread, four times the threads; a
+// wave's stores still cover consecutive addresses); the 16-byte form's measurement is in profiles/decimate_planar.txt.
+constexpr int DEC_STORE_UNIT = 4;
+__device__ __forceinline__ int dec_store_units (int bytes) { return (bytes + 2 * DEC_STORE_UNIT - 2) / DEC_STORE_UNIT; }
+template <int NB, typename F>
+__device__ __forceinline__ void dec_store_unit_of (unsigned char *p, int n, int u, F word)
+{
+    constexpr int UB = DEC_STORE_UNIT;
+    constexpr int MAXF = (UB + 2 * (NB - 1)) / NB;                 // frames a unit can touch (4, 3, 2, 2)
+    constexpr int WORDS = (MAXF * NB + 7) / 8 + 1;
+    const int a = (int)((uintptr_t) p & (UB - 1));
+    const int b = max (u * UB - a, 0), e = min (u * UB - a + UB, n * NB);
+    if (b >= e) return;
+    const int f0 = b / NB, skip = b - f0 * NB;
+    uint64_t im [WORDS] = {};
+#pragma unroll
+    for (int k = 0; k < MAXF; ++k) {
+        const int f = f0 + k, at = k * NB;                         // (frames past the run or the unit: their bytes are never stored)
+        const uint64_t w = word (min (f, n - 1), f < n && f * NB >= b && f * NB < e);
+        im [at / 8] |= w << (8 * (at % 8));
+        if (at % 8 + NB > 8) im [at / 8 + 1] |= w >> (64 - 8 * (at % 8));
+    }
+    const int sh = 8 * skip;
+    const uint64_t lo = sh ? (im [0] >> sh) | (im [1] << (64 - sh)) : im [0];
+    if (e - b == 4) *reinterpret_cast<uint32_t *> (p + b) = (uint32_t) lo;
+    else
+#pragma unroll
+        for (int j = 0; j < 3; ++j) if (j < e - b) p [b + j] = (unsigned char)(lo >> (8 * j));
+}
+template <typename F>
+__device__ __forceinline__ void dec_store_unit (unsigned char *p, int n, int nbytes, int u, F word)
+{
+    switch (nbytes) {
+    case 1: dec_store_unit_of<1> (p, n, u, word); break;
+    case 2: dec_store_unit_of<2> (p, n, u, word); break;
+    case 3: dec_store_unit_of<3> (p, n, u, word); break;
+    default: dec_store_unit_of<4> (p, n, u, word); break;
+    }
+}
+
+// One task of the time-parallel kernels with a pitch on either side: frames [n0, n0 + cnt) of channel c through the kernels' own
+// per-sample expressions.  A planar input is read as one run, a planar output packed into 16-byte stores; returns the clip count.
+template <bool DITHER>
+__device__ __forceinline__ unsigned int dec_segment_pitched (const art_s *in, long in_pitch, unsigned char *out, long out_pitch, int C, int c, long n0, int cnt,
+                                                             const DecFmt &fm, art_s scale, art_s fb, int dtype, uint32_t &g)
+{
+    unsigned int clips = 0;
+    DecPacker pk;
+    unsigned char *const rows = out + ((size_t) n0 * C + c) * fm.nbytes;        // interleaved output: frame i at rows + i * C * nbytes
+    if (out_pitch) pk.begin (out + (long) c * out_pitch + n0 * fm.nbytes);
+    auto one = [&] (int i, art_s smp) {
+        const art_s dither = DITHER ? tpdf_value (tpdf_step (g, dtype)) : 0.0f;
+        const art_s scaled = smp * scale;
+        const art_s code = scaled - fb;
+        const art_s dithered = code + dither;
+        int q = (int) round_half_up (dithered);
+        if (q > fm.hi) { q = fm.hi; clips++; }
+        else if (q < fm.lo) { q = fm.lo; clips++; }
+        const uint32_t w = dec_word (fm, q);
+        if (out_pitch) pk.put (w, fm.nbytes);
+        else {
+            unsigned char *o = rows + (size_t) i * C * fm.nbytes;
+            for (int j = 0; j < fm.nbytes; ++j) o [j] = (unsigned char)(w >> (8 * j));
+        }
+    };
+    if (in_pitch) dec_for_run (in + (long) c * in_pitch + n0, cnt, one);
+    else for (int i = 0; i < cnt; ++i) one (i, in [(size_t)(n0 + i) * C + c]);
+    if (out_pitch) pk.end ();
+    return clips;
+}
+
+template <int ORDER, bool DITHER, bool PITCHED = false>                  // ORDER 0 = no noise shaping
 __global__ __launch_bounds__ (ST_THREADS)
-void decimate_lds_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned char *out, int cpw)     // cpw: channels per workgroup (<= 64)
+void decimate_lds_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned char *out, int cpw, long in_pitch, long out_pitch)     // cpw: channels per workgroup (<= 64)
 {
     __shared__ __attribute__ ((aligned (16))) art_s tile [DEC_CHUNK];          // input, then the rounded code values
     __shared__ __attribute__ ((aligned (16))) art_s dth [DITHER ? DEC_CHUNK : 1];
@@ -820,6 +1002,14 @@ void decimate_lds_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned ch
         const int nf = min (chunk_frames, frames - f0);
 
         // ---- phase A (all threads): load the chunk; produce its dither by jump-ahead
+        if (PITCHED && in_pitch) {                 // a channel's frames are one run of its plane
+            const int units = dec_load_units (nf);
+            for (int e = tid; e < units * Cg; e += ST_THREADS) {
+                const int c = e / units, u = e - c * units;
+                dec_load_unit (in + (long)(c0 + c) * in_pitch + f0, nf, u, [&] (int f, art_s x) { tile [f * Cg + c] = x; });
+            }
+        }
+        else
         for (int e = tid; e < nf * Cg; e += ST_THREADS) {
             const int f = e / Cg, c = e - f * Cg;
             tile [e] = in [(size_t)(f0 + f) * a.C + c0 + c];
@@ -874,6 +1064,20 @@ void decimate_lds_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned ch
         __syncthreads ();
 
         // ---- phase C (all threads): clip, pack little-endian, store
+        if (PITCHED && out_pitch) {                // a channel's bytes are one run of its plane
+            const DecFmt fm = dec_fmt (a.bits, nbytes);
+            const int units = dec_store_units (nf * nbytes);
+            for (int e = tid; e < units * Cg; e += ST_THREADS) {
+                const int c = e / units, u = e - c * units;
+                dec_store_unit (out + (long)(c0 + c) * out_pitch + (long) f0 * nbytes, nf, nbytes, u, [&] (int f, bool counted) {
+                    int q = (int) tile [f * Cg + c];
+                    if (q > hi) { q = hi; if (counted) clips++; }
+                    else if (q < lo) { q = lo; if (counted) clips++; }
+                    return dec_word (fm, q);
+                });
+            }
+        }
+        else
         for (int e = tid; e < nf * Cg; e += ST_THREADS) {
             const int f = e / Cg, c = e - f * Cg;
             int q = (int) tile [e];
@@ -902,9 +1106,9 @@ void decimate_lds_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned ch
 //     waves 1-3   phase A of chunk it+1 (load, dither by jump-ahead)   |   phase C of chunk it-1 (clip, pack, store)
 //     wave 0      phase B of chunk it: one lane per channel through the error-feedback recurrence
 // one LDS-only barrier per step; three sample tiles (by chunk % 3), two dither tiles and two generator-state rows.
-template <int ORDER, bool DITHER>                  // ORDER >= 1
+template <int ORDER, bool DITHER, bool PITCHED = false>                  // ORDER >= 1
 __global__ __launch_bounds__ (ST_THREADS)
-void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned char *out, int cpw)
+void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned char *out, int cpw, long in_pitch, long out_pitch)
 {
     extern __shared__ __attribute__ ((aligned (16))) unsigned char dec_lds [];
     art_s *const tiles = (art_s *) dec_lds;                               // [3][DEC_CHUNK]
@@ -940,6 +1144,14 @@ void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned c
             if (it + 1 < nchunks) {                // ---- phase A of chunk it+1
                 const int k = it + 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);
                 art_s *tile = tiles + (k % 3) * DEC_CHUNK, *dth = dths + (k & 1) * DEC_CHUNK;
+                if (PITCHED && in_pitch) {         // a channel's frames are one run of its plane
+                    const int units = dec_load_units (nf);
+                    for (int e = ht; e < units * Cg; e += HELPERS) {
+                        const int c = e / units, u = e - c * units;
+                        dec_load_unit (in + (long)(c0 + c) * in_pitch + f0, nf, u, [&] (int f, art_s x) { tile [c * pitch + f] = x * scale; });
+                    }
+                }
+                else
                 for (int e = ht; e < nf * Cg; e += HELPERS) {
                     const int f = e / Cg, c = e - f * Cg;
                     tile [c * pitch + f] = in [(size_t)(f0 + f) * a.C + c0 + c] * scale;     // (the serial wave's first operation, done here: same product)
@@ -958,6 +1170,20 @@ void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned c
             if (it >= 1) {                         // ---- phase C of chunk it-1
                 const int k = it - 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);
                 const art_s *tile = tiles + (k % 3) * DEC_CHUNK;
+                if (PITCHED && out_pitch) {        // a channel's bytes are one run of its plane
+                    const DecFmt fm = dec_fmt (a.bits, nbytes);
+                    const int units = dec_store_units (nf * nbytes);
+                    for (int e = ht; e < units * Cg; e += HELPERS) {
+                        const int c = e / units, u = e - c * units;
+                        dec_store_unit (out + (long)(c0 + c) * out_pitch + (long) f0 * nbytes, nf, nbytes, u, [&] (int f, bool counted) {
+                            int q = (int) tile [c * pitch + f];
+                            if (q > hi) { q = hi; if (counted) clips++; }
+                            else if (q < lo) { q = lo; if (counted) clips++; }
+                            return dec_word (fm, q);
+                        });
+                    }
+                }
+                else
                 for (int e = ht; e < nf * Cg; e += HELPERS) {
                     const int f = e / Cg, c = e - f * Cg;
                     int q = (int) tile [c * pitch + f];
@@ -1018,11 +1244,24 @@ void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned c
 // jumps its channel's dither generator to its segment and converts it.  Adjacent threads are adjacent
 // channels of the same frames.  The generator state after the call is written to a second array (the first
 // is still being read by other threads); the host swaps them.
-template <bool DITHER>
+template <bool DITHER, bool PITCHED = false>
 __global__ __launch_bounds__ (256)
-void decimate_parallel_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned char *out, uint32_t *gens_out)
+void decimate_parallel_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned char *out, uint32_t *gens_out, long in_pitch, long out_pitch)
 {
     const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (PITCHED) {                                 // neighbouring threads are neighbouring segments of one plane
+        const long segs = (frames + DEC_SEG - 1) / DEC_SEG;
+        if (task >= segs * a.C) return;
+        const int c = (int)(task / segs);
+        const long n0 = (task - c * segs) * DEC_SEG;
+        const int cnt = (int) min ((long) DEC_SEG, frames - n0);
+        uint32_t g = DITHER ? jump_pairs (a.gens [c], (unsigned int)(n0 / 2)) : 0u;
+        const unsigned int clips = dec_segment_pitched<DITHER> (in, in_pitch, out, out_pitch, a.C, c, n0, cnt, dec_fmt (a.bits, a.bytes), a.scale,
+                                                                a.feedback [c], a.dither_type, g);
+        if (DITHER && n0 + cnt == frames) gens_out [c] = g;
+        if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
+        return;
+    }
     const int c = (int)(task % a.C);
     const long seg = task / a.C;
     const long n0 = seg * DEC_SEG;
@@ -1068,7 +1307,10 @@ constexpr int DEC_BATCH_RUN = 60;                  // frames per chunk at most: 
 // decimate_pipe_kernel over `lanes` lanes of ArtDecLane descriptors per workgroup.  LDS tiles are [lane][frame] with a pitch of
 // chunk_frames + 4 (a multiple of 4: the serial lane's 16-byte LDS accesses); the launcher sizes them by `lanes`, so small
 // workgroups are small in LDS too.  A lane whose context has fewer frames than the workgroup's longest sits the rest out.
-template <int ORDER, bool DITHER>                  // ORDER 0: no noise shaping (calls under 64 frames)
+// PITCHED: a class with a planar side among its lanes.  A lane's side is a run of consecutive frames exactly when its stride there is 1
+// (a plane, or a one-channel stream): the helper waves then move that lane's side of a chunk unit by unit, and every other lane's
+// element by element as before.
+template <int ORDER, bool DITHER, bool PITCHED = false>                  // ORDER 0: no noise shaping (calls under 64 frames)
 __global__ __launch_bounds__ (ST_THREADS)
 void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_frames)
 {
@@ -1081,6 +1323,7 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
     __shared__ unsigned char *s_out [64];
     __shared__ art_s s_scale [64];
     __shared__ int s_stride [64], s_frames [64], s_fmt [64];            // fmt: bits | bytes << 8 | (dither type + 1) << 16
+    __shared__ int s_ostride [PITCHED ? 64 : 1];                        // PITCHED: the output's stride in frames (s_stride: the input's)
     __shared__ unsigned int s_clips [64];
     const int tid = threadIdx.x, wave = tid >> 6;
     const ArtDecLane *const mine = table + (size_t) blockIdx.x * lanes;
@@ -1091,6 +1334,7 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
         s_in [tid] = d.in; s_out [tid] = d.out; s_scale [tid] = d.scale; s_stride [tid] = d.stride; s_frames [tid] = d.frames;
         s_fmt [tid] = d.bits | (d.bytes << 8) | ((d.dither_type + 1) << 16);
         s_clips [tid] = 0;
+        if (PITCHED) s_ostride [tid] = d.out_stride;
         my_frames = d.frames;
         if (my_frames > 0) {
             fb = *d.feedback;
@@ -1112,6 +1356,13 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
                 art_s *tile = tiles + (k % 3) * span, *dth = dths + (k & 1) * span;
                 for (int e = ht; e < nf * lanes; e += HELPERS) {
                     const int c = e / nf, f = e - c * nf;
+                    if (PITCHED && s_stride [c] == 1) {      // task f of the lane is unit f of its run (a run has at most nf units)
+                        const int nfc = min (nf, s_frames [c] - f0);
+                        const art_s sc = s_scale [c];
+                        if (nfc > 0 && f < dec_load_units (nfc))
+                            dec_load_unit (s_in [c] + f0, nfc, f, [&] (int i, art_s x) { tile [c * pitch + i] = x * sc; });
+                        continue;
+                    }
                     if (f0 + f < s_frames [c]) tile [c * pitch + f] = s_in [c][(size_t)(f0 + f) * s_stride [c]] * s_scale [c];
                 }
                 if (DITHER) {
@@ -1131,9 +1382,22 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
             if (it >= 1) {                         // ---- phase C of chunk it-1
                 const int k = it - 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);
                 const art_s *tile = tiles + (k % 3) * span;
-                for (int e = ht; e < nf * lanes; e += HELPERS) {
-                    const int c = e / nf, f = e - c * nf;
-                    if (f0 + f >= s_frames [c]) continue;
+                const int per = PITCHED ? max (nf, dec_store_units (nf * 4)) : nf;     // tasks per lane: its frames, or the units of a 4-byte format's run
+                for (int e = ht; e < per * lanes; e += HELPERS) {
+                    const int c = e / per, f = e - c * per;
+                    if (PITCHED && s_ostride [c] == 1) {     // task f of the lane is unit f of its run of bytes
+                        const int nfc = min (nf, s_frames [c] - f0);
+                        const DecFmt fm = dec_fmt (s_fmt [c] & 255, (s_fmt [c] >> 8) & 255);
+                        if (nfc > 0 && f < dec_store_units (nfc * fm.nbytes))
+                            dec_store_unit (s_out [c] + (size_t) f0 * fm.nbytes, nfc, fm.nbytes, f, [&] (int i, bool counted) {
+                                int q = (int) tile [c * pitch + i];
+                                if (q > fm.hi) { q = fm.hi; if (counted) atomicAdd (&s_clips [c], 1u); }
+                                else if (q < fm.lo) { q = fm.lo; if (counted) atomicAdd (&s_clips [c], 1u); }
+                                return dec_word (fm, q);
+                            });
+                        continue;
+                    }
+                    if ((PITCHED && f >= nf) || f0 + f >= s_frames [c]) continue;
                     const int fmt = s_fmt [c], bits = fmt & 255, nbytes = (fmt >> 8) & 255;
                     const int width = (bits + 7) / 8, pad = nbytes - width;
                     const int hi = (1 << (bits - 1)) - 1, lo = ~hi;
@@ -1143,7 +1407,7 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
                     if (q > hi) { q = hi; atomicAdd (&s_clips [c], 1u); }
                     else if (q < lo) { q = lo; atomicAdd (&s_clips [c], 1u); }
                     const uint32_t v = ((uint32_t) q << shift) + bias;
-                    unsigned char *o = s_out [c] + (size_t)(f0 + f) * s_stride [c] * nbytes;
+                    unsigned char *o = s_out [c] + (size_t)(f0 + f) * (PITCHED ? s_ostride [c] : s_stride [c]) * nbytes;
                     for (int j = 0; j < pad; ++j) *o++ = 0;
                     *o++ = (unsigned char) v;
                     if (width > 1) { *o++ = (unsigned char)(v >> 8); if (width > 2) *o++ = (unsigned char)(v >> 16); }
@@ -1203,7 +1467,7 @@ __device__ __forceinline__ const Item &item_of (const Item *items, int n, long t
 
 // decimate_parallel_kernel over a flattened task space: (context, channel, DEC_SEG-frame segment).  A thread finds its context by
 // binary search over the contexts' first tasks (item_of).
-template <bool DITHER>
+template <bool DITHER, bool PITCHED = false>      // PITCHED: a class with a planar side among its items
 __global__ __launch_bounds__ (256)
 void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
 {
@@ -1211,6 +1475,18 @@ void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
     if (task >= tasks) return;
     const ArtDecTask &a = item_of (items, n, task);
     const long t = task - a.task0;
+    if (PITCHED && (a.in_pitch || a.out_pitch)) {  // (an interleaved item of the class takes the code below)
+        const long segs = (a.frames + DEC_SEG - 1) / DEC_SEG;
+        const int c = (int)(t / segs);
+        const long n0 = (t - c * segs) * DEC_SEG;
+        const int cnt = (int) min ((long) DEC_SEG, a.frames - n0);
+        uint32_t g = DITHER ? jump_pairs (a.gens [c], (unsigned int)(n0 / 2)) : 0u;
+        const unsigned int clips = dec_segment_pitched<DITHER> (a.in, a.in_pitch, a.out, a.out_pitch, a.C, c, n0, cnt, dec_fmt (a.bits, a.bytes), a.scale,
+                                                                a.feedback [c], a.dither_type, g);
+        if (DITHER && n0 + cnt == a.frames) a.gens_next [c] = g;
+        if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
+        return;
+    }
     const int c = (int)(t % a.C);
     const long n0 = (t / a.C) * DEC_SEG;
     const int frames = a.frames;
@@ -1495,13 +1771,18 @@ static int decimate_launch (const ArtDecArgs *a, const art_s *d_in, long in_pitc
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
-int arthip_decimate (const ArtDecArgs *a, const art_s *d_in, int frames, unsigned char *d_out, void *stream)
+// in_pitch / out_pitch: samples / bytes between the planes of that side, 0: that side is interleaved.  The kernel is chosen as for
+// the interleaved call; with a pitch on either side it is that kernel's PITCHED instantiation.
+int arthip_decimate_pitched (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream)
 {
+    const bool pitched = in_pitch || out_pitch;
     if (frames >= 64 && !a->shaping_on && (!a->dither_on || a->gens_next) && (DEC_SEG % 2) == 0) {
         const long tasks = (long) a->C * ((frames + DEC_SEG - 1) / DEC_SEG);
         const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256);
-        if (a->dither_on) hipLaunchKernelGGL (decimate_parallel_kernel<true>, grid, block, 0, (hipStream_t) stream, *a, d_in, frames, d_out, a->gens_next);
-        else hipLaunchKernelGGL (decimate_parallel_kernel<false>, grid, block, 0, (hipStream_t) stream, *a, d_in, frames, d_out, a->gens_next);
+#define DEC_PAR(P) do { if (a->dither_on) hipLaunchKernelGGL ((decimate_parallel_kernel<true, P>), grid, block, 0, (hipStream_t) stream, *a, d_in, frames, d_out, a->gens_next, in_pitch, out_pitch); \
+                        else hipLaunchKernelGGL ((decimate_parallel_kernel<false, P>), grid, block, 0, (hipStream_t) stream, *a, d_in, frames, d_out, a->gens_next, in_pitch, out_pitch); } while (0)
+        if (pitched) DEC_PAR (true); else DEC_PAR (false);
+#undef DEC_PAR
         return hipGetLastError () == hipSuccess ? 1 : -1;      // 1: generator state now lives in gens_next
     }
     if (frames >= 64) {
@@ -1509,14 +1790,16 @@ int arthip_decimate (const ArtDecArgs *a, const art_s *d_in, int frames, unsigne
         const dim3 grid ((a->C + cpw - 1) / cpw), block (ST_THREADS);
         hipStream_t st = (hipStream_t) stream;
         const int order = a->shaping_on ? a->shaping_order : 0;
-#define DEC_GO(O) do { if (a->dither_on) hipLaunchKernelGGL ((decimate_lds_kernel<O, true>), grid, block, 0, st, *a, d_in, frames, d_out, cpw); \
-                       else hipLaunchKernelGGL ((decimate_lds_kernel<O, false>), grid, block, 0, st, *a, d_in, frames, d_out, cpw); } while (0)
-#define DEC_PIPE(O) do { auto kd = decimate_pipe_kernel<O, true>; auto kn = decimate_pipe_kernel<O, false>; \
+#define DEC_GO_P(O, P) do { if (a->dither_on) hipLaunchKernelGGL ((decimate_lds_kernel<O, true, P>), grid, block, 0, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch); \
+                            else hipLaunchKernelGGL ((decimate_lds_kernel<O, false, P>), grid, block, 0, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch); } while (0)
+#define DEC_GO(O) do { if (pitched) DEC_GO_P (O, true); else DEC_GO_P (O, false); } while (0)
+#define DEC_PIPE_P(O, P) do { auto kd = decimate_pipe_kernel<O, true, P>; auto kn = decimate_pipe_kernel<O, false, P>; \
                          static bool once = false; \
                          if (!once) { (void) hipFuncSetAttribute ((const void *) kd, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pipe_lds); \
                                       (void) hipFuncSetAttribute ((const void *) kn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pipe_lds); once = true; } \
-                         if (a->dither_on) hipLaunchKernelGGL (kd, grid, block, pipe_lds, st, *a, d_in, frames, d_out, cpw); \
-                         else hipLaunchKernelGGL (kn, grid, block, pipe_lds, st, *a, d_in, frames, d_out, cpw); } while (0)
+                         if (a->dither_on) hipLaunchKernelGGL (kd, grid, block, pipe_lds, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch); \
+                         else hipLaunchKernelGGL (kn, grid, block, pipe_lds, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch); } while (0)
+#define DEC_PIPE(O) do { if (pitched) DEC_PIPE_P (O, true); else DEC_PIPE_P (O, false); } while (0)
         const size_t pipe_lds = (size_t) 5 * DEC_CHUNK * sizeof (art_s);
         // with more workgroups than CUs the chip is busy anyway and the smaller LDS footprint of the unpipelined form
         // (more workgroups per CU) wins: 4,096 channels 49 vs 36 Gsamples/s
@@ -1526,10 +1809,17 @@ int arthip_decimate (const ArtDecArgs *a, const art_s *d_in, int frames, unsigne
         }
         switch (order) { case 0: DEC_GO (0); break; case 1: DEC_GO (1); break; case 2: DEC_GO (2); break; case 3: DEC_GO (3); break; default: DEC_GO (4); }
 #undef DEC_PIPE
+#undef DEC_PIPE_P
 #undef DEC_GO
+#undef DEC_GO_P
         return hipGetLastError () == hipSuccess ? 0 : -1;
     }
-    return decimate_launch (a, d_in, 0, frames, d_out, 0, stream);
+    return decimate_launch (a, d_in, in_pitch, frames, d_out, out_pitch, stream);
+}
+
+int arthip_decimate (const ArtDecArgs *a, const art_s *d_in, int frames, unsigned char *d_out, void *stream)
+{
+    return arthip_decimate_pitched (a, d_in, 0, frames, d_out, 0, stream);
 }
 
 int arthip_decimate_planar (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream)
@@ -1546,8 +1836,10 @@ int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, v
     if (cls->slice.count <= 0) return 0;
     if (!cls->serial) {
         const dim3 grid ((unsigned int)((cls->tasks + 255) / 256)), block (256);
-        if (cls->dither) hipLaunchKernelGGL (decimate_batch_parallel_kernel<true>, grid, block, 0, st, (const ArtDecTask *) items, cls->slice.count, cls->tasks);
-        else hipLaunchKernelGGL (decimate_batch_parallel_kernel<false>, grid, block, 0, st, (const ArtDecTask *) items, cls->slice.count, cls->tasks);
+#define DEC_BATCH_PAR(D) do { if (cls->pitched) hipLaunchKernelGGL ((decimate_batch_parallel_kernel<D, true>), grid, block, 0, st, (const ArtDecTask *) items, cls->slice.count, cls->tasks); \
+                              else hipLaunchKernelGGL ((decimate_batch_parallel_kernel<D, false>), grid, block, 0, st, (const ArtDecTask *) items, cls->slice.count, cls->tasks); } while (0)
+        if (cls->dither) DEC_BATCH_PAR (true); else DEC_BATCH_PAR (false);
+#undef DEC_BATCH_PAR
         return hipGetLastError () == hipSuccess ? 0 : -1;
     }
     const int L = cls->slice.lanes;
@@ -1555,13 +1847,15 @@ int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, v
     const int chunk_frames = batch_chunk_frames (L, DEC_BATCH_RUN);
     const size_t lds = (size_t) 5 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 5 DEC_CHUNK samples (80 KiB)
     const dim3 grid ((unsigned int)(cls->slice.count / L)), block (ST_THREADS);
-#define DEC_BATCH_GO(O, D) do { auto k = decimate_batch_pipe_kernel<O, D>; static bool once = false; \
+#define DEC_BATCH_GO(O, D, P) do { auto k = decimate_batch_pipe_kernel<O, D, P>; static bool once = false; \
         if (!once) { (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(5 * DEC_CHUNK * sizeof (art_s))); once = true; } \
         hipLaunchKernelGGL (k, grid, block, lds, st, (const ArtDecLane *) items, L, chunk_frames); } while (0)
-#define DEC_BATCH_O(O) do { if (cls->dither) DEC_BATCH_GO (O, true); else DEC_BATCH_GO (O, false); } while (0)
+#define DEC_BATCH_D(O, D) do { if (cls->pitched) DEC_BATCH_GO (O, D, true); else DEC_BATCH_GO (O, D, false); } while (0)
+#define DEC_BATCH_O(O) do { if (cls->dither) DEC_BATCH_D (O, true); else DEC_BATCH_D (O, false); } while (0)
     switch (cls->order) { case 0: DEC_BATCH_O (0); break; case 1: DEC_BATCH_O (1); break; case 2: DEC_BATCH_O (2); break;
                           case 3: DEC_BATCH_O (3); break; default: DEC_BATCH_O (4); }
 #undef DEC_BATCH_O
+#undef DEC_BATCH_D
 #undef DEC_BATCH_GO
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }

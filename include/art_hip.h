@@ -314,6 +314,33 @@ int decimateHipShardCount (Decimate *cxt);
  * in artamdErrorCount): the contexts of a launch that failed keep their device state and generator buffers as before the call. */
 int decimateProcessBatchInterleavedLEDevice (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                                              unsigned char *const *d_outputs);
+/* planar device buffers (a torch waveform is [C, T]): channel c of the input at d_input + c*inputPitch (in samples), channel c of the
+ * output at d_output + c*outputPitch (in BYTES), frame f of an output plane at f*outputBytes; a pitch of 0 on either side means that
+ * side is interleaved, as in resampleProcessPlanarDevice.  A pitch may exceed the plane's length (rows of a padded tensor: nothing
+ * between a plane's last byte and the next plane is touched) and need not be a multiple of anything; the input needs the sample's own
+ * alignment, the output none.  A one-channel context is the same call in either layout.  The output bytes, the clip count and the
+ * context's state afterwards are exactly those of decimateProcessInterleavedLEDevice on the transposed input, transposed back, and a
+ * stream may mix the two calls freely.  The call runs on the kernel its interleaved twin would (time-parallel without noise shaping
+ * from 64 frames on, the LDS-staged serial forms with it): a plane's run of frames is fetched with 16-byte loads and its bytes are
+ * stored with whole aligned stores (16 bytes in the time-parallel form, 4 in the serial forms' helper waves), cut at the boundaries
+ * of the run's own address, so an odd pitch or base costs a run a head and a tail of single accesses and nothing else.  A sharded
+ * context's shards take their run of planes where they lie.  Asynchronous like the interleaved call. */
+void decimateProcessPlanarLEDevice (Decimate *cxt, const artsample_t *d_input, long inputPitch, int numInputFrames,
+                                    unsigned char *d_output, long outputPitch);
+/* decimateProcessBatchInterleavedLEDevice with a pitch per buffer, as in decimateProcessPlanarLEDevice: the input pitches in samples,
+ * the output pitches in bytes, 0 for an interleaved side of an item, a NULL pitch array for "every item's is" (both NULL: the
+ * interleaved entry itself).  The output bytes, clip counts and state after the call are exactly those of
+ * decimateProcessPlanarLEDevice (cxts [i], d_inputs [i], inputPitches [i], numInputFrames [i], d_outputs [i], outputPitches [i]).
+ * Planar and interleaved items share the launches of their class (the class count does not grow); sharded contexts and contexts on
+ * another stream or device are made as their own single planar calls, in list order.  Return values, the failure contract, "a
+ * context may appear only once", skipping numInputFrames [i] <= 0 and asynchronous operation as in the interleaved entry. */
+int decimateProcessBatchPlanarLEDevice (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                        const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches);
+/* Puts the context back to what decimateInit left — error feedback zero, dither generators re-seeded, shaper histories empty, on
+ * the device and in the host mirrors (feedback, tpdf_generators, noise_shapers) — so that a pool of contexts serves clip after clip
+ * without decimateFree / decimateInit.  The clip counter is NOT reset (decimateHipClipped: total since init).  Asynchronous on the
+ * context's stream, behind every earlier call; no allocation; sharded contexts too. */
+void decimateHipReset (Decimate *cxt);
 void floatIntegersLEDevice (const unsigned char *d_input, double inputGain, int inputBits, int inputBytes, int inputStride,
                             artsample_t *d_output, int numSamples, void *hipStream);
 /* Many buffers' integer PCM to samples in ONE launch: item i leaves exactly the bits of floatIntegersLEDevice (d_inputs [i],

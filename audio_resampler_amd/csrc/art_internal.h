@@ -182,6 +182,9 @@ void   arthip_fir_rows_cache_free (void *cache);
 size_t arthip_fir_batch_item_bytes (void);
 int arthip_fir_batch_max_segments (void);                /* ring-epoch segments a batched call may have */
 int arthip_fir_batch (const ArtFirArgs *a, const ArtSegTable *segs, int n, void *d_table, void *stream);
+/* may this general-kernel call be an item of arthip_fir_batch?  (its one-output tile's span must fit the launches' shared LDS budget: a ratio
+ * below that is the single call's — more LDS for itself, or the strict kernel) */
+int arthip_fir_batch_accepts (const ArtFirArgs *call);
 /* n independent calls of the f32 streaming matrix-core kernel in one launch per shape (4-byte build; the 8-byte build plans none).
  * arthip_fir_group_plan: `a` / `segs` as arthip_fir would get them (buffers provisioned, roll_dst set, no timing events) — would that call be ONE
  * regular, un-split launch of that kernel on rows kept across calls whose set is built?  1: *out is that launch, nothing enqueued, and the

@@ -509,13 +509,32 @@ __global__ void deinterleave_kernel (art_s *dst, long pitch, const art_s *src, i
     dst [(size_t) c * pitch + f] = src [e];
 }
 
+// The span rule, stated once.  A tile of `tile` consecutive outputs stages T + ceil (tile / ratio) + 3 frames of CG channels in the LDS.
+// GEN_LDS_BUDGET is what a launch asks for as long as a tile of one output at least fits it; below that ratio the tile is one output and the
+// launch asks for its span, up to GEN_LDS_LIMIT (the CU's 160 KiB less the kernels' own tables); beyond that the call is not the general
+// kernel's (arthip_fir: the strict kernel).  Three regimes by ratio, and what the gathering entries do with them:
+//   span (1) <= budget             the ordinary launch (tile 1 .. GEN_MAX_TILE): single, batched or scheduled (a block: span (GEN_MAX_TILE) <= budget)
+//   budget < span (1) <= limit     tile 1, more than 64 KiB of LDS: the single call only
+//   limit < span (1)               the strict kernel: the single call only
+constexpr size_t GEN_LDS_BUDGET = 64 * 1024, GEN_LDS_LIMIT = 160 * 1024 - 1024;
+
+template <int CG>
+constexpr int general_max_span (size_t lds_bytes) { return (int)(lds_bytes / (sizeof (art_s) * CG)); }
+
+__host__ inline long general_span (int T, double ratio, int tile) { return T + (long) ceil (tile / ratio) + 3; }
+
+template <int CG>
+bool general_span_fits (int T, double ratio, int tile, size_t lds_bytes)
+{
+    return ratio > 0.0 && (double) T + ceil (tile / ratio) + 3.0 <= (double) general_max_span<CG> (lds_bytes);
+}
+
 // tile size, LDS bytes and grid of one general-kernel launch (shared by the single and the batched launch)
 template <int CG>
 bool general_geometry (const ArtFirArgs &a, int *tile_out, size_t *lds_out, dim3 *grid_out, unsigned int crowd = 1)
 {
     // tile size: as many consecutive outputs as keep the staged span within the LDS budget
-    const int lds_budget = 64 * 1024;
-    const int max_span = lds_budget / ((int) sizeof (art_s) * CG);
+    const int max_span = general_max_span<CG> (GEN_LDS_BUDGET);
     int tile = (int) floor ((max_span - a.T - 3) * a.ratio);
     if (tile > GEN_MAX_TILE) tile = GEN_MAX_TILE;
     // small calls: prefer many small tiles (each wave walks its tile's outputs serially, so latency ~ tile/4
@@ -534,9 +553,8 @@ bool general_geometry (const ArtFirArgs &a, int *tile_out, size_t *lds_out, dim3
         tile = k * pass;
     }
     if (tile < 1) tile = 1;
-    long span = a.T + (long) ceil (tile / a.ratio) + 3;
-    size_t lds = (size_t) span * CG * sizeof (art_s);
-    if (lds > 160 * 1024 - 1024) return false;              // absurd ratio/taps combination
+    if (!general_span_fits<CG> (a.T, a.ratio, tile, GEN_LDS_LIMIT)) return false;      // absurd ratio/taps combination
+    const size_t lds = (size_t) general_span (a.T, a.ratio, tile) * CG * sizeof (art_s);
     const unsigned int total = a.n_end - a.n_begin;
     const unsigned int roll_blocks = a.roll_dst ? (unsigned int)((a.H * a.C + GEN_THREADS - 1) / GEN_THREADS) : 0u;
     *tile_out = tile; *lds_out = lds;
@@ -617,13 +635,22 @@ int batch_variant (const ArtFirArgs *a, const ArtSegTable *segs, const int *whic
 }
 
 
+// Can a call join a gathered launch?  Every item of the launch asks for the LDS of the largest: a call whose one-output tile does not fit the
+// budget (more than 64 KiB for itself, one workgroup per CU for everybody, and past the CU's LDS with the batched kernel's own table — or
+// not the general kernel's at all) is made as its single call: the same samples.
+template <int CG>
+int batch_accepts (const ArtFirArgs &a)
+{
+    return general_span_fits<CG> (a.T, a.ratio, 1, GEN_LDS_BUDGET);
+}
+
 // Can a block join a run?  The run's tile is at most GEN_MAX_TILE outputs whatever the run's other blocks are: the block's span at
-// that tile must fit the LDS (otherwise its single call goes to the strict kernel), and any GEN_MAX_TILE consecutive outputs of it may
-// touch SCHED_SEGS segments at most.  (A block turned away is made as its single call: the same samples.)
+// that tile must fit the LDS budget (otherwise its single call chooses its own, smaller tile, or goes to the strict kernel), and any
+// GEN_MAX_TILE consecutive outputs of it may touch SCHED_SEGS segments at most.  (A block turned away is made as its single call: the same samples.)
 template <int CG>
 int schedule_accepts (const ArtFirArgs &a, const ArtamdSegment *segs, int nseg, unsigned int outputs)
 {
-    if (!(a.ratio > 0.0) || (double) a.T + ceil (GEN_MAX_TILE / a.ratio) + 3.0 > (double)((64 * 1024) / ((int) sizeof (art_s) * CG))) return 0;
+    if (!general_span_fits<CG> (a.T, a.ratio, GEN_MAX_TILE, GEN_LDS_BUDGET)) return 0;
     // (segments q .. q + SCHED_SEGS - 1 all starting inside one window of GEN_MAX_TILE outputs, or a later one's start in the window of q: too many)
     for (int q = 0; q + SCHED_SEGS < nseg; ++q)
         if (segs [q + SCHED_SEGS].first_output < outputs && segs [q + SCHED_SEGS].first_output - segs [q + 1].first_output < (unsigned int) GEN_MAX_TILE) return 0;
@@ -732,6 +759,11 @@ int arthip_fir_batch (const ArtFirArgs *a, const ArtSegTable *segs, int n, void 
 }
 
 size_t arthip_fir_schedule_bytes (int nblocks, int nsegs) { return sizeof (ArtSchedBlock) * (size_t) nblocks + sizeof (ArtSchedSeg) * (size_t) nsegs; }
+
+int arthip_fir_batch_accepts (const ArtFirArgs *a)
+{
+    return a->C > 4 ? batch_accepts<8> (*a) : a->C > 2 ? batch_accepts<4> (*a) : a->C == 2 ? batch_accepts<2> (*a) : batch_accepts<1> (*a);
+}
 
 int arthip_fir_schedule_accepts (const ArtFirArgs *a, const ArtamdSegment *segs, int nseg, unsigned int outputs)
 {

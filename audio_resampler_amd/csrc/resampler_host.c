@@ -1563,6 +1563,8 @@ static int batch_plan (Resample *cxt, const art_s *d_in, long in_pitch, int nIn,
         return !in_pitch && !out_pitch && !(cxt->flags & EXTRAPOLATE_PREFILL) && batch_plan_matrix (cxt, a, tab, p, w) ? 2 : 0;
     /* (the general kernel's gathered launch takes calls of a few segments; the matrix-core path's follows the lattice from the first table) */
     if (p->nseg > arthip_fir_batch_max_segments ()) return 0;
+    /* (... and calls whose span fits the launch's LDS budget: a ratio below that is the single call's, as a schedule's block of that kind is) */
+    if (!arthip_fir_batch_accepts (a)) return 0;
     plan_fits (cxt, p, d_in, in_pitch, tail, w->runs, &w->nruns, w->late, &w->nlate);
     return 1;
 }

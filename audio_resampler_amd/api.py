@@ -145,6 +145,9 @@ def _bind(width):
         "biquadBankRepairs": (C.c_uint, [ptr]),
         "artamdBiquadRepairs": (C.c_uint, []),
         "biquadBankApplyBatchInterleavedDevice": (C.c_int, [ptr, C.c_int, ptr, ptr]),
+        "biquadBankApplyPlanarDevice": (None, [ptr, ptr, C.c_long, C.c_int]),
+        "biquadBankApplyBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr]),
+        "biquadBankReset": (None, [ptr]),
         "decimateHipSetStream": (None, [DP, ptr]),
         "decimateProcessInterleavedLEDevice": (None, [DP, ptr, C.c_int, ptr]),
         "decimateHipClipped": (C.c_long, [DP]),
@@ -453,6 +456,14 @@ def _bind(width):
         def apply_device(self, d_buf, frames):
             self.L.biquadBankApplyInterleavedDevice(self.p, _dev_ptr(d_buf), frames)
 
+        def apply_planar_device(self, d_buf, pitch, frames):
+            """in place over planes: channel c at d_buf + c * pitch samples (0: interleaved, the call above)"""
+            self.L.biquadBankApplyPlanarDevice(self.p, _dev_ptr(d_buf), int(pitch), frames)
+
+        def reset(self):
+            """every section back to what the bank was created from, in stream order (biquadBankReset)"""
+            self.L.biquadBankReset(self.p)
+
         def set_stream(self, s):
             self.L.biquadBankSetStream(self.p, s)
 
@@ -687,6 +698,74 @@ def _bind(width):
         if rc < 0:
             raise RuntimeError("biquadBankApplyBatchInterleavedDevice failed")
         return rc
+
+    def biquad_batch_planar_device(banks, d_bufs, pitches, frames):
+        """biquadBankApplyBatchPlanarDevice: biquad_batch_device with a pitch per buffer (channel c of item i at d_bufs[i] + c * pitches[i]
+        samples; 0: that item is interleaved; None for the list: every item is).  Returns the launch count (raises if the call
+        returned -1)."""
+        n = len(banks)
+        rc = lib().biquadBankApplyBatchPlanarDevice(
+            (C.c_void_p * n)(*[b.p for b in banks]), n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_bufs]),
+            None if pitches is None else (C.c_long * n)(*[int(q) for q in pitches]), (C.c_int * n)(*[int(v) for v in frames]))
+        if rc < 0:
+            raise RuntimeError("biquadBankApplyBatchPlanarDevice failed")
+        return rc
+
+    class ClipFilter:
+        """Whole clips, channels-first, through a cascade of one to four second-order sections, IN PLACE: x [B, C, T] (or [C, T]) on the
+        GPU in, the same tensor out — one biquadBankApplyBatchPlanarDevice call on the tensor's own rows, no copy of the samples on the
+        way.  sections: [("lowpass" | "highpass", frequency), ...] (frequency as biquad_lowpass / biquad_highpass take it: a fraction
+        of the sample rate; gain 1.0); ART's -p is two low-passes at one frequency.  Clip i is what a fresh bank makes of
+        x[i, :, :lengths[i]]; x[i, :, lengths[i]:] is not touched.  Holds a pool of up to max_batch banks, reset for every call, on the
+        caller's current torch stream; a larger batch is made max_batch clips at a time.  Takes and gives what ClipResampler and
+        ClipDecimator take."""
+
+        def __init__(self, channels, sections, max_batch=1024):
+            sections = list(sections)
+            if not 1 <= len(sections) <= 4 or any(kind not in ("lowpass", "highpass") for kind, _ in sections):
+                raise ValueError('sections: one to four of ("lowpass" | "highpass", frequency)')
+            self.channels, self.nsections, self.max_batch = channels, len(sections), max(1, int(max_batch))
+            L = lib()
+            self._sections = (Biquad * (channels * self.nsections))()
+            for s, (kind, freq) in enumerate(sections):
+                co = BiquadCoefficients()
+                (L.biquad_lowpass if kind == "lowpass" else L.biquad_highpass)(C.byref(co), float(freq))
+                for c in range(channels):
+                    L.biquad_init(C.byref(self._sections[c * self.nsections + s]), C.byref(co), 1.0)
+            self.pool = []
+
+        def close(self):
+            for b in self.pool:
+                b.close()
+            self.pool = []
+
+        def __call__(self, x, lengths=None):
+            import torch
+            whole = x
+            if x.dim() == 2:
+                x = x.unsqueeze(0)
+            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
+                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
+            if x.shape[2] and x.stride(2) != 1:
+                raise ValueError("in place: the frames of a channel must be consecutive (stride 1 along T)")
+            B, Cn, T = x.shape
+            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
+                raise ValueError("lengths: one entry per clip, 0 .. T")
+            while len(self.pool) < min(B, self.max_batch):
+                self.pool.append(BiquadBank(self._sections, Cn, self.nsections))
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            for b in self.pool[:min(B, self.max_batch)]:
+                b.set_stream(stream)
+            size, xp = x.element_size(), x.data_ptr()
+            pitch = x.stride(1) if Cn > 1 else 0                  # (one channel: the same call in either layout)
+            for b0 in range(0, B, self.max_batch):
+                idx = range(b0, min(B, b0 + self.max_batch))
+                pool = self.pool[:len(idx)]
+                for b in pool:
+                    b.reset()
+                biquad_batch_planar_device(pool, [xp + i * x.stride(0) * size for i in idx], [pitch] * len(idx), [lengths[i] for i in idx])
+            return whole
 
     def ingest_batch_device(d_ins, gains, bits, nbytes, strides, d_outs, counts, stream=None):
         """floatIntegersBatchLEDevice: item i as floatIntegersLEDevice (d_ins[i], gains[i], bits[i], nbytes[i], strides[i], d_outs[i],

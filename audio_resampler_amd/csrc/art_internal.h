@@ -344,6 +344,10 @@ int arthip_biquad_batch_launch (const ArtBqClass *cls, const void *d_table, void
  * fixed bound on the frames of a gathered time-parallel call (serialMax >= 0; < 0: the library's): the measurements behind both
  * (tools/bench_biquad_batch.py) — pcm_host.c */
 int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const int *numFrames, int lanes, int serialMax);
+/* ... and biquadBankApplyBatchPlanarDevice likewise: the one body of both layouts (NULL pitches: artamd_biquad_batch).  A planar
+ * item's lane is a plane: buf = the item's buffer + channel * pitch, stride 1 */
+int artamd_biquad_batch_planar (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches, const int *numFrames,
+                                int lanes, int serialMax);
 int artamd_biquad_batch_serial_max (void);                              /* the library's bound (BQ_BATCH_SERIAL_MAX) */
 /* every section has order 2, S = 1 or 2, interleaved frames: hand-scheduled kernel */
 int arthip_biquad_order2 (Biquad *d_sections, int C, int S, art_s *d_buf, int frames, int stride, void *stream);   /* stride >= C: values between frames */
@@ -353,6 +357,11 @@ size_t arthip_biquad_spec_scratch (int C, int S, int frames, int L);
 int arthip_biquad_spec_arm (int *d_first_bad, int C, void *stream);      /* once per scratch: C ints the calls keep at "no mismatch" */
 int arthip_biquad_spec (Biquad *d_sections, int C, int S, const art_s *d_in, int in_stride, art_s *d_out, int out_stride, int frames,
                         int L, int W, void *d_states, int *d_first_bad, unsigned int *d_repairs, void *stream);
+/* the same over planes: channel c's frames are consecutive from d_in + c * in_pitch and go to d_out + c * out_pitch (pitches in
+ * samples; distinct buffers).  A lane moves its run 16 bytes at a time, cut at the 16-byte boundaries of the run's own address;
+ * its stores are whole too where the two planes' addresses agree modulo 16 */
+int arthip_biquad_spec_planar (Biquad *d_sections, int C, int S, const art_s *d_in, long in_pitch, art_s *d_out, long out_pitch, int frames,
+                               int L, int W, void *d_states, int *d_first_bad, unsigned int *d_repairs, void *stream);
 /* ---- time stretcher (stretch_kernels.hip) ---- */
 typedef struct {
     art_s *ring [2][2];                  /* [stage][ping-pong] input rings, `room` values each */

@@ -4,8 +4,10 @@
  * caller buffers to/from HBM.  Every sample is processed by the kernels in pcm_kernels.hip.
  */
 #define _USE_MATH_DEFINES
+#include <limits.h>
 #include <math.h>
 #include <pthread.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -298,6 +300,7 @@ unsigned int artamdBiquadRepairs (void)
 
 struct artamd_biquad_bank {
     Biquad *d_sections;
+    Biquad *d_sections0;                 /* the sections the bank was created from (biquadBankReset) */
     int C, S;
     int all_order2;                      /* every section is second order: hand-scheduled serial kernel */
     int warmup;                          /* time-parallel form: warm-up frames per section (0: serial kernels only) */
@@ -338,10 +341,11 @@ BiquadBank *biquadBankCreate (const Biquad *sections, int numChannels, int numSe
         }
     }
     b->d_sections = arthip_malloc (bytes);
+    b->d_sections0 = arthip_malloc (bytes);
     b->d_repairs = arthip_malloc (sizeof (unsigned int));
     b->d_first_bad = arthip_malloc (sizeof (int) * (size_t) numChannels);
-    if (!b->d_sections || !b->d_repairs || !b->d_first_bad || arthip_h2d (b->d_sections, sections, bytes, NULL) ||
-        arthip_zero (b->d_repairs, sizeof (unsigned int), NULL) || arthip_biquad_spec_arm (b->d_first_bad, numChannels, NULL) ||
+    if (!b->d_sections || !b->d_sections0 || !b->d_repairs || !b->d_first_bad || arthip_h2d (b->d_sections, sections, bytes, NULL) ||
+        arthip_h2d (b->d_sections0, sections, bytes, NULL) || arthip_zero (b->d_repairs, sizeof (unsigned int), NULL) || arthip_biquad_spec_arm (b->d_first_bad, numChannels, NULL) ||
         arthip_sync (NULL)) { biquadBankFree (b); return NULL; }
     return b;
 }
@@ -391,10 +395,11 @@ void biquadBankSetStream (BiquadBank *b, void *stream)
     b->stream = stream;
 }
 
-void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int numFrames)
+/* a sharded bank's call in either layout (pitch 0: interleaved; else the planes of biquadBankApplyPlanarDevice, of which a shard
+ * takes its run as the rows of its slice) */
+static void bank_sharded_call (BiquadBank *b, artsample_t *d_buffer, long pitch, int numFrames)
 {
-    if (numFrames <= 0) return;
-    if (b->nshards) {
+    {
         /* every shard waits for the bank's stream, pulls its channel slice of the caller's buffer (peer-to-peer when it sits on
          * another device), filters it in its own HBM and pushes it back; the bank's stream then waits for all of them */
         const int prev = arthip_current_device (), wps = (int)(sizeof (art_s) / 4);
@@ -417,6 +422,14 @@ void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int
                     continue;
                 }
             }
+            if (pitch) {
+                artsample_t *planes = d_buffer + (size_t) first * pitch;
+                arthip_slice_copy (sh->d_slice, (size_t) numFrames * wps, planes, (size_t) pitch * wps, numFrames * wps, (size_t) width, sh->stream);
+                biquadBankApplyPlanarDevice (sh, sh->d_slice, numFrames, numFrames);
+                arthip_slice_copy (planes, (size_t) pitch * wps, sh->d_slice, (size_t) numFrames * wps, numFrames * wps, (size_t) width, sh->stream);
+                arthip_event_record (b->ev_shard [k], sh->stream);
+                continue;
+            }
             arthip_slice_copy (sh->d_slice, (size_t) width * wps, d_buffer + first, (size_t) b->C * wps, width * wps, (size_t) numFrames, sh->stream);
             biquadBankApplyInterleavedDevice (sh, sh->d_slice, numFrames);
             arthip_slice_copy (d_buffer + first, (size_t) b->C * wps, sh->d_slice, (size_t) width * wps, width * wps, (size_t) numFrames, sh->stream);
@@ -425,8 +438,13 @@ void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int
         arthip_set_device (b->device);
         for (int k = 0; k < b->nshards; ++k) arthip_stream_wait_event (b->stream, b->ev_shard [k]);
         if (prev >= 0) arthip_set_device (prev);
-        return;
     }
+}
+
+void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int numFrames)
+{
+    if (numFrames <= 0) return;
+    if (b->nshards) { bank_sharded_call (b, d_buffer, 0, numFrames); return; }
     ENTER_DEVICE (b);
     const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
 
@@ -455,6 +473,60 @@ void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int
         arthip_biquad_order2 (b->d_sections, b->C, b->S, d_buffer, numFrames, b->C, b->stream);
     else
         arthip_biquad_chain (b->d_sections, b->C, b->S, d_buffer, numFrames, b->C, b->stream);
+    LEAVE_DEVICE (b);
+}
+
+/* Channels-first buffers.  The time-parallel form reads one buffer and writes another: the planes go aside into d_tmp by ONE 2-D
+ * copy, dense but for up to 3 samples per plane — d_tmp's plane c starts at the caller's plane c's address modulo 16, so that the
+ * kernel's 16-byte fetches (cut on d_tmp's boundaries) and its 16-byte stores (on the caller's) are the same cuts.  The serial form
+ * is the batch kernel with this bank's planes as its lanes (a one-bank class). */
+void biquadBankApplyPlanarDevice (BiquadBank *b, artsample_t *d_buffer, long pitch, int numFrames)
+{
+    if (numFrames <= 0) return;
+    if (b->C == 1) pitch = 0;
+    if (!pitch) { biquadBankApplyInterleavedDevice (b, d_buffer, numFrames); return; }
+    if (b->nshards) { bank_sharded_call (b, d_buffer, pitch, numFrames); return; }
+    const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
+
+    if (L && numFrames >= 2 * L) {
+        ENTER_DEVICE (b);
+        const long q = 16 / (long) sizeof (art_s);
+        const long dense = numFrames + (((pitch - numFrames) % q) + q) % q;                /* = pitch modulo q, >= numFrames */
+        const size_t lead = (size_t)((uintptr_t) d_buffer & 15) / sizeof (art_s);
+        const size_t samples = (size_t) dense * b->C + lead, need = arthip_biquad_spec_scratch (b->C, b->S, numFrames, L);
+        if (samples * sizeof (art_s) > b->tmp_cap) {
+            arthip_free (b->d_tmp);
+            b->tmp_cap = (samples + samples / 2) * sizeof (art_s);
+            if (!(b->d_tmp = arthip_malloc (b->tmp_cap))) b->tmp_cap = 0;
+        }
+        if (need > b->spec_cap) {
+            arthip_free (b->d_spec);
+            b->spec_cap = need + need / 2;
+            if (!(b->d_spec = arthip_malloc (b->spec_cap))) b->spec_cap = 0;
+        }
+        if (b->d_tmp && b->d_spec &&
+            !arthip_copy2d (b->d_tmp + lead, (size_t) dense * sizeof (art_s), d_buffer, (size_t) pitch * sizeof (art_s),
+                            (size_t) numFrames * sizeof (art_s), (size_t) b->C, b->stream) &&
+            !arthip_biquad_spec_planar (b->d_sections, b->C, b->S, b->d_tmp + lead, dense, d_buffer, pitch, numFrames, L, b->warmup, b->d_spec,
+                                        b->d_first_bad, b->d_repairs, b->stream)) {
+            LEAVE_DEVICE (b);
+            return;
+        }
+        LEAVE_DEVICE (b);
+        fprintf (stderr, "artamd: time-parallel biquad unavailable (%s): serial kernel\n", arthip_last_error ());
+    }
+    artamd_biquad_batch_planar (&b, 1, &d_buffer, &pitch, &numFrames, 0, INT_MAX);       /* (INT_MAX: never handed back to this call) */
+}
+
+/* every section as biquadBankCreate was given it: a copy on the device, in stream order */
+void biquadBankReset (BiquadBank *b)
+{
+    if (b->nshards) {
+        for (int k = 0; k < b->nshards; ++k) biquadBankReset (b->shards [k]);
+        return;
+    }
+    ENTER_DEVICE (b);
+    if (arthip_d2d (b->d_sections, b->d_sections0, sizeof (Biquad) * (size_t) b->C * b->S, b->stream)) pcm_fail ("biquadBankReset: the copy failed (state kept)");
     LEAVE_DEVICE (b);
 }
 
@@ -500,7 +572,7 @@ void biquadBankFree (BiquadBank *b)
     }
     if (b->ev_parent) arthip_event_destroy (b->ev_parent);
     free (b->shards); free (b->shard_first); free (b->ev_shard);
-    arthip_free (b->d_sections); arthip_free (b->d_tmp); arthip_free (b->d_spec); arthip_free (b->d_repairs); arthip_free (b->d_first_bad); arthip_free (b->d_slice);
+    arthip_free (b->d_sections); arthip_free (b->d_sections0); arthip_free (b->d_tmp); arthip_free (b->d_spec); arthip_free (b->d_repairs); arthip_free (b->d_first_bad); arthip_free (b->d_slice);
     arthip_free (b->d_batch);
     LEAVE_DEVICE (b);
     free (b);
@@ -1083,6 +1155,13 @@ static unsigned long *bank_stamp (const void *b) { return &((BiquadBank *) b)->b
 /* lanes > 0: every class gets that many lanes per workgroup; serialMax < 0: BQ_BATCH_SERIAL_MAX (the measurements of both rules) */
 int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const int *numFrames, int lanes, int serialMax)
 {
+    return artamd_biquad_batch_planar (banks, n, d_buffers, NULL, numFrames, lanes, serialMax);
+}
+
+/* pitches: NULL (every item interleaved) or a pitch per item, 0 for an interleaved one (biquadBankApplyPlanarDevice's) */
+int artamd_biquad_batch_planar (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches, const int *numFrames,
+                                int lanes, int serialMax)
+{
     if (n <= 0) return 0;
     if (artamd_batch_distinct ((const void *const *) banks, n, bank_stamp, "biquad", "bank")) return -1;
     if (serialMax < 0) serialMax = BQ_BATCH_SERIAL_MAX;
@@ -1103,7 +1182,7 @@ int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_
         if (numFrames [i] <= 0) continue;
         const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
         if (b->nshards || b->stream != lead->stream || b->device != lead->device || (L && numFrames [i] >= 2 * L && numFrames [i] > serialMax)) {
-            biquadBankApplyInterleavedDevice (b, d_buffers [i], numFrames [i]);
+            biquadBankApplyPlanarDevice (b, d_buffers [i], pitches ? pitches [i] : 0, numFrames [i]);       /* (pitch 0: the interleaved call) */
             ++launches;
             continue;
         }
@@ -1138,8 +1217,9 @@ int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_
             const BiquadBank *b = banks [refs [j].ctx];
             const int c = refs [j].channel;
             l [j].sections = b->d_sections + (size_t) c * b->S;
-            l [j].buf = d_buffers [refs [j].ctx] + c;
-            l [j].stride = b->C;
+            const long pitch = pitches && b->C > 1 ? pitches [refs [j].ctx] : 0;
+            l [j].buf = d_buffers [refs [j].ctx] + (pitch ? (size_t) c * pitch : (size_t) c);
+            l [j].stride = pitch ? 1 : b->C;
             l [j].frames = refs [j].frames;
         }
     }
@@ -1168,6 +1248,11 @@ out:
 int biquadBankApplyBatchInterleavedDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const int *numFrames)
 {
     return artamd_biquad_batch (banks, n, d_buffers, numFrames, 0, -1);
+}
+
+int biquadBankApplyBatchPlanarDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches, const int *numFrames)
+{
+    return artamd_biquad_batch_planar (banks, n, d_buffers, pitches, numFrames, 0, -1);
 }
 
 int artamd_biquad_batch_serial_max (void) { return BQ_BATCH_SERIAL_MAX; }

@@ -160,12 +160,88 @@ __device__ __forceinline__ void put_state (SectionRegs *r, const SpecState *src)
         for (int k = 0; k < 4; ++k) { r [s].x [k] = src [s].x [k]; r [s].y [k] = src [s].y [k]; }
 }
 
+// PLANAR instantiations take pitches (samples between planes) where the interleaved ones take strides
+template <bool PLANAR> using spec_stride = typename std::conditional<PLANAR, long, int>::type;
+
+// spec_run over a plane: frames [from, to) are consecutive at in + from (and out + from).  The run is cut at the 16-byte boundaries
+// of its own address: single frames up to the first boundary, batches of U frames by 16-byte loads from there (two batches in
+// flight, as below), single frames behind the last whole batch.  Stores are 16 bytes too where `out` is aligned as `in` is.  The
+// arithmetic is the interleaved form's, frame by frame in the same order.
+template <int ACTIVE, bool STORE>
+__device__ __forceinline__ void spec_run_plane (SectionRegs *r, const art_s *in, art_s *out, int from, int to)
+{
+    constexpr int U = 8, Q = 16 / (int) sizeof (art_s);                   // Q frames to 16 bytes
+    typedef art_s vecq __attribute__ ((ext_vector_type (Q)));
+    auto one = [&] (int n) {
+        art_s v = in [n];
+#pragma unroll
+        for (int s = 0; s < ACTIVE; ++s) v = step_buffer_order (r [s], v);
+        if constexpr (STORE) out [n] = v;
+    };
+    int n = from;
+    const int head = min (to - from, (int)((Q - (int)(((uintptr_t)(in + from) / sizeof (art_s)) & (Q - 1))) & (Q - 1)));
+    for (const int e = from + head; n < e; ++n) one (n);
+    bool whole = false;                                                   // (in + n is on a boundary now, or n == to)
+    if constexpr (STORE) whole = !((uintptr_t)(out + n) & 15);
+    auto fetch = [&] (art_s (&v) [U], int at) {
+#pragma unroll
+        for (int q = 0; q < U / Q; ++q) {
+            const vecq t = *reinterpret_cast<const vecq *> (in + at + q * Q);
+#pragma unroll
+            for (int j = 0; j < Q; ++j) v [q * Q + j] = t [j];
+        }
+    };
+    auto work = [&] (art_s (&v) [U], int at) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int s = 0; s < ACTIVE; ++s) v [u] = step_buffer_order (r [s], v [u]);
+        }
+        if constexpr (STORE) {
+            if (whole) {
+#pragma unroll
+                for (int q = 0; q < U / Q; ++q) {
+                    vecq t;
+#pragma unroll
+                    for (int j = 0; j < Q; ++j) t [j] = v [q * Q + j];
+                    *reinterpret_cast<vecq *> (out + at + q * Q) = t;
+                }
+            }
+            else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) out [at + u] = v [u];
+            }
+        }
+    };
+    const int batches = (to - n) / U;
+    if (batches > 0) {
+        art_s cur [U], nxt [U];
+        fetch (cur, n);
+        for (int b = 0; b < batches; ++b, n += U) {
+            const bool more = b + 1 < batches;
+            if (more) fetch (nxt, n + U);                  // in flight while this batch's dependent chain runs
+            work (cur, n);
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) cur [u] = nxt [u];
+            }
+        }
+    }
+    for (; n < to; ++n) one (n);
+}
+
 // frames [from, to) of channel c through sections 0 .. ACTIVE-1, exact order; STORE: the results go to `out`.
 // The recurrence is latency-bound and a lane's loads are independent of it: two batches of U frames are kept in flight
 // (the next batch's loads are issued before the current batch's dependent chain starts).
-template <int S, int ACTIVE, bool STORE>
-__device__ __forceinline__ void spec_run (SectionRegs *r, const art_s *in, int stride, art_s *out, int out_stride, int c, int from, int to)
+template <int S, int ACTIVE, bool STORE, bool PLANAR = false>
+__device__ __forceinline__ void spec_run (SectionRegs *r, const art_s *in, spec_stride<PLANAR> stride, art_s *out, spec_stride<PLANAR> out_stride,
+                                          int c, int from, int to)
 {
+    if constexpr (PLANAR) {
+        spec_run_plane<ACTIVE, STORE> (r, in + (size_t) c * stride, STORE ? out + (size_t) c * out_stride : nullptr, from, to);
+        return;
+    }
+    else {
     constexpr int U = 8;
     auto fetch = [&] (art_s (&v) [U], int n) {
 #pragma unroll
@@ -203,28 +279,30 @@ __device__ __forceinline__ void spec_run (SectionRegs *r, const art_s *in, int s
         for (int s = 0; s < ACTIVE; ++s) v = step_buffer_order (r [s], v);
         if (STORE) out [(size_t) n * out_stride + c] = v;
     }
+    }
 }
 
 // the warm-up of a speculative chunk: W frames with section 0 alone, W more with sections 0-1, ... (section s joins (S - s) W
 // frames before the chunk's first frame, fed by sections that have already converged)
-template <int S, int J = 0>
-__device__ __forceinline__ void spec_warm_up (SectionRegs *r, const art_s *in, int stride, int c, int begin, int W)
+template <int S, bool PLANAR, int J = 0>
+__device__ __forceinline__ void spec_warm_up (SectionRegs *r, const art_s *in, spec_stride<PLANAR> stride, int c, int begin, int W)
 {
     if constexpr (J < S) {
-        spec_run<S, J + 1, false> (r, in, stride, nullptr, 0, c, begin + J * W, begin + (J + 1) * W);
-        spec_warm_up<S, J + 1> (r, in, stride, c, begin, W);
+        spec_run<S, J + 1, false, PLANAR> (r, in, stride, nullptr, 0, c, begin + J * W, begin + (J + 1) * W);
+        spec_warm_up<S, PLANAR, J + 1> (r, in, stride, c, begin, W);
     }
 }
 
-// task = (chunk k, channel c), c fastest: the lanes of a wave read neighbouring channels of a few chunks
-template <int S>
+// task = (chunk k, channel c), c fastest: the lanes of a wave read neighbouring channels of a few chunks.  PLANAR: k fastest —
+// consecutive lanes walk consecutive chunks of ONE plane, so a wave touches one contiguous stretch of it.
+template <int S, bool PLANAR = false>
 __global__ __launch_bounds__ (256)
-void biquad_spec_kernel (const Biquad *sections, int C, int K, int L, int W, const art_s *in, int stride, art_s *out, int out_stride,
-                         int frames, SpecState *starts, SpecState *ends)
+void biquad_spec_kernel (const Biquad *sections, int C, int K, int L, int W, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
+                         spec_stride<PLANAR> out_stride, int frames, SpecState *starts, SpecState *ends)
 {
     const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
     if (task >= (long) C * K) return;
-    const int c = (int)(task % C), k = (int)(task / C);
+    const int c = PLANAR ? (int)(task / K) : (int)(task % C), k = PLANAR ? (int)(task % K) : (int)(task / C);
     const int first = k * L, last = min (first + L, frames);
 
     SectionRegs r [S];
@@ -238,18 +316,18 @@ void biquad_spec_kernel (const Biquad *sections, int C, int K, int L, int W, con
         for (int s = 0; s < S; ++s)
 #pragma unroll
             for (int q = 0; q < 4; ++q) { r [s].x [q] = 0; r [s].y [q] = 0; }
-        spec_warm_up<S> (r, in, stride, c, begin, W);
+        spec_warm_up<S, PLANAR> (r, in, stride, c, begin, W);
     }
     else if (first > 0)
         // close to the start of the call: from the carried-in state through frames [0, first) — exact, nothing stored
-        spec_run<S, S, false> (r, in, stride, nullptr, 0, c, 0, first);
+        spec_run<S, S, false, PLANAR> (r, in, stride, nullptr, 0, c, 0, first);
 
     SpecState st [S];
     get_state<S> (st, r);
 #pragma unroll
     for (int s = 0; s < S; ++s) starts [((size_t) c * K + k) * S + s] = st [s];
 
-    spec_run<S, S, true> (r, in, stride, out, out_stride, c, first, last);
+    spec_run<S, S, true, PLANAR> (r, in, stride, out, out_stride, c, first, last);
 
     get_state<S> (st, r);
 #pragma unroll
@@ -274,9 +352,10 @@ void biquad_check_kernel (int C, int K, const SpecState *starts, const SpecState
 // One thread per channel: repairs from the first mismatch (rare: recomputes from the exact state until it rejoins a
 // speculative trajectory — in the worst case everything, serially), then the channel's final state goes back into
 // `sections`.  repairs: running count of chunks recomputed (diagnostics).  first_bad is re-armed for the next call.
-template <int S>
+template <int S, bool PLANAR = false>
 __global__ __launch_bounds__ (64)
-void biquad_commit_kernel (Biquad *sections, int C, int K, int L, const art_s *in, int stride, art_s *out, int out_stride, int frames,
+void biquad_commit_kernel (Biquad *sections, int C, int K, int L, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
+                           spec_stride<PLANAR> out_stride, int frames,
                            const SpecState *starts, SpecState *ends, const unsigned char *bad, int *first_bad, unsigned int *repairs)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -296,7 +375,7 @@ void biquad_commit_kernel (Biquad *sections, int C, int K, int L, const art_s *i
         // chunk k again, from the exact state its predecessor left
         put_state<S> (r, en + (size_t)(k - 1) * S);
         const int first = k * L, last = min (first + L, frames);
-        spec_run<S, S, true> (r, in, stride, out, out_stride, c, first, last);
+        spec_run<S, S, true, PLANAR> (r, in, stride, out, out_stride, c, first, last);
         SpecState now [S];
         get_state<S> (now, r);
 #pragma unroll
@@ -471,6 +550,7 @@ void biquad_chain_lds_kernel (Biquad *sections, int C, int S, art_s *buf, int fr
 constexpr int FF_CAP = ART_WIDE ? 1536 : 3072;      // samples per LDS array (12 KiB); 9 arrays
 constexpr int FF_HELPERS = 64;                     // threads per helper role (one wave each)
 constexpr int FF_RUN = 48;                         // frames per helper lane and chunk (upper bound)
+constexpr int FF_GROUP = 16;                       // frames wave 3 holds in registers at a time (divides FF_RUN)
 
 // Raw buffer accesses with hardware bounds checking (word 3 = 0x00020000: raw, 32-bit): an out-of-range load
 // returns 0 and an out-of-range store is dropped, so the helper loops carry no per-element predicates.
@@ -610,10 +690,9 @@ void biquad_order2_ff_kernel (Biquad *sections, int C, int stride, art_s *buf, i
         // the two frames before the chunk (f0 == 0: patched from xtail later) are forced out of range by a select — a
         // negative offset is not left to wrap, the hardware's range check does not wrap register + immediate to 32 bits
 #pragma unroll
-        for (int j = 0; j < FF_RUN + 2; ++j) {
-            if (j >= run + 2) break;
+        for (int j = 0; j < FF_RUN + 2; ++j) {     // (guards, not a break: constant trip counts keep the arrays in registers; run is a multiple of 4)
             const int f = f0 + j - 2;
-            xr [j] = ff_load (rs, f >= 0 ? (f * stride + hc) * esz : (int) 0xfffffff0u, art_s ());
+            if (j < 2 || ((j - 2) & ~3) < run) xr [j] = ff_load (rs, f >= 0 ? (f * stride + hc) * esz : (int) 0xfffffff0u, art_s ());
         }
         xl0 = ff_load (rs, ((L - 1) * stride + hc) * esz, art_s ());
         xl1 = ff_load (rs, L >= 2 ? ((L - 2) * stride + hc) * esz : (int) 0xfffffff0u, art_s ());
@@ -637,10 +716,11 @@ void biquad_order2_ff_kernel (Biquad *sections, int C, int stride, art_s *buf, i
                     const art_s a0 = ffc [0][hc][0], a1 = ffc [0][hc][1], a2 = ffc [0][hc][2];
 #pragma unroll
                     for (int j = 0; j < FF_RUN; ++j) {     // frames past a short first chunk land in row slack
-                        if (j >= run) break;
-                        const art_s p0 = xr [j + 2] * a0, p1 = xr [j + 1] * a1;
-                        ud [j] = p0 + p1;
-                        pd [j] = xr [j] * a2;
+                        if ((j & ~3) < run) {
+                            const art_s p0 = xr [j + 2] * a0, p1 = xr [j + 1] * a1;
+                            ud [j] = p0 + p1;
+                            pd [j] = xr [j] * a2;
+                        }
                     }
                 }
                 fetch (it + 2);                            // in flight across the barrier
@@ -655,31 +735,37 @@ void biquad_order2_ff_kernel (Biquad *sections, int C, int stride, art_s *buf, i
                         const art_s *src = (S == 2 ? A2 + (k & 1) * FF_CAP : A1 + (k % 3) * FF_CAP) + hc * pitch + f0;
                         const __amdgpu_buffer_rsrc_t rs = ff_rsrc (buf + (size_t) chunk_start (k) * stride + c0, ((size_t) L * stride - c0) * esz);
                         const int base = (f0 * stride + hc) * esz;
-                        art_s v [FF_RUN];
 #pragma unroll
-                        for (int j = 0; j < FF_RUN; ++j) { if (j >= run) break; v [j] = src [j]; }
+                        for (int g = 0; g < FF_RUN; g += FF_GROUP) {       // FF_GROUP frames at a time: reads first, then stores
+                            art_s v [FF_GROUP];
 #pragma unroll
-                        for (int j = 0; j < FF_RUN; ++j) { if (j >= run) break; ff_store (rs, base + j * stride * esz, v [j]); }
+                            for (int j = 0; j < FF_GROUP; ++j) { if (g + (j & ~3) < run) v [j] = src [g + j]; }
+#pragma unroll
+                            for (int j = 0; j < FF_GROUP; ++j) { if (g + (j & ~3) < run) ff_store (rs, base + (g + j) * stride * esz, v [j]); }
+                        }
                     }
                 }
                 if (S == 2 && it >= 1 && it <= nchunks) {  // section 2's feed-forward part from section 1's outputs
                     const int k = it - 1;
                     const art_s *row = A1 + (k % 3) * FF_CAP + hc * pitch + f0;
                     art_s *ud = A2 + (k & 1) * FF_CAP + hc * pitch + f0, *pd = B2 + (k & 1) * FF_CAP + hc * pitch + f0;
-                    art_s x [FF_RUN + 2];
-#pragma unroll
-                    for (int j = 0; j < FF_RUN + 2; ++j) {
-                        if (j >= run + 2) break;
-                        x [j] = row [hr == 0 && j < 2 ? 0 : j - 2];
-                    }
-                    if (hr == 0) { x [0] = mtail [k % 3][hc][1]; x [1] = mtail [k % 3][hc][0]; }
                     const art_s a0 = ffc [1][hc][0], a1 = ffc [1][hc][1], a2 = ffc [1][hc][2];
 #pragma unroll
-                    for (int j = 0; j < FF_RUN; ++j) {
-                        if (j >= run) break;
-                        const art_s p0 = x [j + 2] * a0, p1 = x [j + 1] * a1;
-                        ud [j] = p0 + p1;
-                        pd [j] = x [j] * a2;
+                    for (int g = 0; g < FF_RUN; g += FF_GROUP) {           // FF_GROUP frames at a time (+ the two before them)
+                        art_s x [FF_GROUP + 2];
+#pragma unroll
+                        for (int j = 0; j < FF_GROUP + 2; ++j) {
+                            if (g + (j < 2 ? 0 : (j - 2) & ~3) < run) x [j] = row [hr == 0 && g + j < 2 ? 0 : g + j - 2];
+                        }
+                        if (g == 0 && hr == 0) { x [0] = mtail [k % 3][hc][1]; x [1] = mtail [k % 3][hc][0]; }
+#pragma unroll
+                        for (int j = 0; j < FF_GROUP; ++j) {
+                            if (g + (j & ~3) < run) {
+                                const art_s p0 = x [j + 2] * a0, p1 = x [j + 1] * a1;
+                                ud [g + j] = p0 + p1;
+                                pd [g + j] = x [j] * a2;
+                            }
+                        }
                     }
                 }
             }
@@ -1529,6 +1615,11 @@ void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
 // run chunk it; one LDS-only barrier per step.  Every lane makes the same operations in the same order as the single call's serial
 // form (step_buffer_order, reference biquad.c:106-163), so the bits are the single call's.
 // ---------------------------------------------------------------------------------------------------
+constexpr int BQ_Q = 16 / (int) sizeof (art_s);    // frames to 16 bytes
+typedef art_s bq_vecq __attribute__ ((ext_vector_type (BQ_Q)));
+// a lane whose frames are consecutive (a plane, or a one-channel bank) from a 16-byte boundary: the helper waves move it 16 bytes at a time
+__device__ __forceinline__ bool bq_plane_aligned (const art_s *buf, int stride) { return stride == 1 && !((uintptr_t) buf & 15); }
+
 constexpr int BQ_BATCH_RUN = 60;                   // frames per chunk at most (the decimator batch's: fill and drain cost two chunks)
 
 // LDS: three tiles [lanes][chunk_frames + 4] (the pitch is a multiple of 4: one ds_read_b128 feeds the serial lane 4 float frames),
@@ -1570,7 +1661,17 @@ void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_fram
                 art_s *tile = tiles + (k % 3) * span;
                 for (int e = ht; e < nf * lanes; e += HELPERS) {
                     const int c = e / nf, f = e - c * nf;
-                    if (f0 + f < s_frames [c]) tile [c * pitch + f] = s_buf [c][(size_t)(f0 + f) * s_stride [c]];
+                    const int left = s_frames [c] - (f0 + f);
+                    if (left <= 0) continue;
+                    const art_s *g = s_buf [c] + (size_t)(f0 + f) * s_stride [c];
+                    if (bq_plane_aligned (s_buf [c], s_stride [c])) {
+                        // a plane on a 16-byte boundary (f0 is a multiple of 4): the first thread of every whole group of BQ_Q frames moves it
+                        if (left >= BQ_Q - (f & (BQ_Q - 1))) {
+                            if (!(f & (BQ_Q - 1))) *reinterpret_cast<bq_vecq *> (tile + c * pitch + f) = *reinterpret_cast<const bq_vecq *> (g);
+                            continue;
+                        }
+                    }
+                    tile [c * pitch + f] = *g;
                 }
             }
             if (it >= 1) {                         // ---- store chunk it-1
@@ -1578,7 +1679,16 @@ void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_fram
                 const art_s *tile = tiles + (k % 3) * span;
                 for (int e = ht; e < nf * lanes; e += HELPERS) {
                     const int c = e / nf, f = e - c * nf;
-                    if (f0 + f < s_frames [c]) s_buf [c][(size_t)(f0 + f) * s_stride [c]] = tile [c * pitch + f];
+                    const int left = s_frames [c] - (f0 + f);
+                    if (left <= 0) continue;
+                    art_s *g = s_buf [c] + (size_t)(f0 + f) * s_stride [c];
+                    if (bq_plane_aligned (s_buf [c], s_stride [c])) {
+                        if (left >= BQ_Q - (f & (BQ_Q - 1))) {
+                            if (!(f & (BQ_Q - 1))) *reinterpret_cast<bq_vecq *> (g) = *reinterpret_cast<const bq_vecq *> (tile + c * pitch + f);
+                            continue;
+                        }
+                    }
+                    *g = tile [c * pitch + f];
                 }
             }
         }
@@ -1725,6 +1835,27 @@ int arthip_biquad_spec (Biquad *d_sections, int C, int S, const art_s *d_in, int
         hipLaunchKernelGGL (biquad_spec_kernel<SS>, grid, block, 0, st, (const Biquad *) d_sections, C, K, L, W, d_in, in_stride, d_out, out_stride, frames, starts, ends); \
         hipLaunchKernelGGL (biquad_check_kernel<SS>, grid, block, 0, st, C, K, (const SpecState *) starts, (const SpecState *) ends, bad, d_first_bad); \
         hipLaunchKernelGGL (biquad_commit_kernel<SS>, dim3 ((C + 63) / 64), dim3 (64), 0, st, d_sections, C, K, L, d_in, in_stride, d_out, out_stride, frames, \
+                            (const SpecState *) starts, ends, (const unsigned char *) bad, d_first_bad, d_repairs); } while (0)
+    switch (S) { case 1: SPEC_GO (1); break; case 2: SPEC_GO (2); break; case 3: SPEC_GO (3); break; default: SPEC_GO (4); }
+#undef SPEC_GO
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+int arthip_biquad_spec_planar (Biquad *d_sections, int C, int S, const art_s *d_in, long in_pitch, art_s *d_out, long out_pitch, int frames,
+                               int L, int W, void *d_states, int *d_first_bad, unsigned int *d_repairs, void *stream)
+{
+    if (frames <= 0) return 0;
+    if (S < 1 || S > MAX_CHAIN || L < 1) return -1;
+    const int K = (frames + L - 1) / L;
+    SpecState *starts = (SpecState *) d_states, *ends = starts + (size_t) C * K * S;
+    unsigned char *bad = (unsigned char *)(ends + (size_t) C * K * S);
+    const long tasks = (long) C * K;
+    const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256);
+    hipStream_t st = (hipStream_t) stream;
+#define SPEC_GO(SS) do { \
+        hipLaunchKernelGGL ((biquad_spec_kernel<SS, true>), grid, block, 0, st, (const Biquad *) d_sections, C, K, L, W, d_in, in_pitch, d_out, out_pitch, frames, starts, ends); \
+        hipLaunchKernelGGL (biquad_check_kernel<SS>, grid, block, 0, st, C, K, (const SpecState *) starts, (const SpecState *) ends, bad, d_first_bad); \
+        hipLaunchKernelGGL ((biquad_commit_kernel<SS, true>), dim3 ((C + 63) / 64), dim3 (64), 0, st, d_sections, C, K, L, d_in, in_pitch, d_out, out_pitch, frames, \
                             (const SpecState *) starts, ends, (const unsigned char *) bad, d_first_bad, d_repairs); } while (0)
     switch (S) { case 1: SPEC_GO (1); break; case 2: SPEC_GO (2); break; case 3: SPEC_GO (3); break; default: SPEC_GO (4); }
 #undef SPEC_GO

@@ -276,6 +276,31 @@ unsigned int artamdBiquadRepairs (void);             /* the host-pointer calls (
  * nothing to do; -1 with nothing enqueued if a bank appears twice or a pointer in banks is NULL; -1 if a launch failed (counted
  * in artamdErrorCount): the banks of a launch that failed keep their state, and their buffers are left untouched. */
 int biquadBankApplyBatchInterleavedDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const int *numFrames);
+/* planar device buffers (a torch waveform is [C, T]), in place: channel c at d_buffer + c*pitch (in samples), frame f of a plane at
+ * + f; a pitch of 0 means interleaved — the call then IS biquadBankApplyInterleavedDevice — as in decimateProcessPlanarLEDevice.  A
+ * pitch may exceed numFrames (rows of a padded tensor: nothing between a plane's last frame and the next plane is read for a result
+ * or written) and need not be a multiple of anything; the base needs the sample's own alignment.  A one-channel bank is the same
+ * call in either layout.  The samples and the state biquadBankRead returns afterwards (index included) are exactly those of
+ * biquadBankApplyInterleavedDevice on the transposed buffer, and a stream may mix the two calls freely.  The call takes the form
+ * its interleaved twin would: time-parallel (the planes are first copied aside by one 2-D copy; a lane then fetches and stores its
+ * run of a plane 16 bytes at a time, cut at the 16-byte boundaries of the run's own address, so an odd pitch, base or chunk start
+ * costs a run a head and a tail of single accesses and nothing else), or serial, on the batch entry's kernel with one lane per
+ * plane.  A sharded bank's shards take their run of planes through their slices.  Asynchronous on the bank's stream; numFrames <= 0
+ * does nothing. */
+void biquadBankApplyPlanarDevice (BiquadBank *bank, artsample_t *d_buffer, long pitch, int numFrames);
+/* biquadBankApplyBatchInterleavedDevice with a pitch per item, as in biquadBankApplyPlanarDevice: 0 for an interleaved item, a NULL
+ * array for "every item is" (the interleaved entry itself).  Samples and state after the call are exactly those of
+ * biquadBankApplyPlanarDevice (banks [i], d_buffers [i], pitches [i], numFrames [i]).  Planar and interleaved items of one section
+ * count share the launch of their class (a plane is a lane whose frames are consecutive); sharded banks, banks on another stream or
+ * device and calls of more than 512 frames that their single call makes time-parallel are made as their own single planar calls, in
+ * list order, before the gathered launches, one launch each in the return value.  Return values, the failure contract, "a bank may
+ * appear only once", skipping numFrames [i] <= 0 and asynchronous operation as in the interleaved entry. */
+int biquadBankApplyBatchPlanarDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches,
+                                      const int *numFrames);
+/* Puts every section's delay lines and index back to what biquadBankCreate was given (the bank keeps a copy on the device), so that
+ * a pool of banks serves clip after clip without biquadBankFree / biquadBankCreate, as decimateHipReset does for decimators.
+ * biquadBankRepairs is NOT reset.  Asynchronous on the bank's stream, behind every earlier call; no allocation; sharded banks too. */
+void biquadBankReset (BiquadBank *bank);
 
 /* The reference's void entry points (biquad_apply_buffer / _sample, floatIntegersLE) cannot return an error and this library has no
  * CPU path: a failure there (no device, allocation, launch) is printed to stderr, counted, and leaves silence (floatIntegersLE) or the

@@ -271,11 +271,13 @@ typedef struct {
 } ArtDecArgs;
 /* returns 1 when the generator state was written to a->gens_next (caller swaps), 0 otherwise, <0 on error */
 int arthip_decimate (const ArtDecArgs *a, const art_s *d_in, int frames, unsigned char *d_out, void *stream);
-int arthip_decimate_planar (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream);
-/* arthip_decimate on planes: channel c of the input at d_in + c * in_pitch (samples), of the output at d_out + c * out_pitch (bytes); a
- * pitch of 0: that side is interleaved.  The same kernel as the interleaved call would run, and the same return values
- * (arthip_decimate_planar above is the host-pointer planar call's: always the one-lane kernel) */
+/* THE planar call: arthip_decimate on planes, channel c of the input at d_in + c * in_pitch (samples), of the output at
+ * d_out + c * out_pitch (bytes); a pitch of 0: that side is interleaved (both 0: arthip_decimate).  The same kernel as the
+ * interleaved call would run, and the same return values */
 int arthip_decimate_pitched (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream);
+/* NOT the planar call, whatever its name says: always the one-lane kernel (decimate_kernel), whatever the frame count — the
+ * host-pointer planar entry's (decimateProcessLE), whose generator state must stay where it is.  Returns 0, or <0 on error */
+int arthip_decimate_planar (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream);
 /* Many contexts' calls, one launch per class (decimateProcessBatchInterleavedLEDevice).  The host builds one table per call (the
  * classes' item arrays one after another, each 16-byte aligned), uploads it once and launches every class from its slice. */
 typedef struct {                         /* one channel of one context: a lane of the serial wave (noise shaping, or short calls) */

@@ -441,6 +441,25 @@ static void bank_sharded_call (BiquadBank *b, artsample_t *d_buffer, long pitch,
     }
 }
 
+/* the time-parallel form's buffers, each grown by half as much again when a call needs more: d_tmp for `samples` samples (the
+ * input set aside), d_spec for `need` bytes of chunk states.  0: one of them could not be had */
+static int bank_spec_reserve (BiquadBank *b, size_t samples, size_t need)
+{
+    if (samples * sizeof (art_s) > b->tmp_cap) {
+        arthip_free (b->d_tmp);
+        b->tmp_cap = (samples + samples / 2) * sizeof (art_s);
+        if (!(b->d_tmp = arthip_malloc (b->tmp_cap))) b->tmp_cap = 0;
+    }
+    if (need > b->spec_cap) {
+        arthip_free (b->d_spec);
+        b->spec_cap = need + need / 2;
+        if (!(b->d_spec = arthip_malloc (b->spec_cap))) b->spec_cap = 0;
+    }
+    return b->d_tmp && b->d_spec;
+}
+/* ... and what a call says when it falls back to the serial kernels (no room, or a launch failed) */
+static void bank_spec_unavailable (void) { fprintf (stderr, "artamd: time-parallel biquad unavailable (%s): serial kernel\n", arthip_last_error ()); }
+
 void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int numFrames)
 {
     if (numFrames <= 0) return;
@@ -450,24 +469,14 @@ void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int
 
     if (L && numFrames >= 2 * L) {
         const size_t samples = (size_t) numFrames * b->C, need = arthip_biquad_spec_scratch (b->C, b->S, numFrames, L);
-        if (samples * sizeof (art_s) > b->tmp_cap) {
-            arthip_free (b->d_tmp);
-            b->tmp_cap = (samples + samples / 2) * sizeof (art_s);
-            if (!(b->d_tmp = arthip_malloc (b->tmp_cap))) b->tmp_cap = 0;
-        }
-        if (need > b->spec_cap) {
-            arthip_free (b->d_spec);
-            b->spec_cap = need + need / 2;
-            if (!(b->d_spec = arthip_malloc (b->spec_cap))) b->spec_cap = 0;
-        }
-        if (b->d_tmp && b->d_spec) {
+        if (bank_spec_reserve (b, samples, need)) {
             arthip_d2d (b->d_tmp, d_buffer, samples * sizeof (art_s), b->stream);
             if (!arthip_biquad_spec (b->d_sections, b->C, b->S, b->d_tmp, b->C, d_buffer, b->C, numFrames, L, b->warmup, b->d_spec, b->d_first_bad, b->d_repairs, b->stream)) {
                 LEAVE_DEVICE (b);
                 return;
             }
         }
-        fprintf (stderr, "artamd: time-parallel biquad unavailable (%s): serial kernel\n", arthip_last_error ());
+        bank_spec_unavailable ();
     }
     if (b->all_order2 && numFrames >= 64)
         arthip_biquad_order2 (b->d_sections, b->C, b->S, d_buffer, numFrames, b->C, b->stream);
@@ -494,17 +503,7 @@ void biquadBankApplyPlanarDevice (BiquadBank *b, artsample_t *d_buffer, long pit
         const long dense = numFrames + (((pitch - numFrames) % q) + q) % q;                /* = pitch modulo q, >= numFrames */
         const size_t lead = (size_t)((uintptr_t) d_buffer & 15) / sizeof (art_s);
         const size_t samples = (size_t) dense * b->C + lead, need = arthip_biquad_spec_scratch (b->C, b->S, numFrames, L);
-        if (samples * sizeof (art_s) > b->tmp_cap) {
-            arthip_free (b->d_tmp);
-            b->tmp_cap = (samples + samples / 2) * sizeof (art_s);
-            if (!(b->d_tmp = arthip_malloc (b->tmp_cap))) b->tmp_cap = 0;
-        }
-        if (need > b->spec_cap) {
-            arthip_free (b->d_spec);
-            b->spec_cap = need + need / 2;
-            if (!(b->d_spec = arthip_malloc (b->spec_cap))) b->spec_cap = 0;
-        }
-        if (b->d_tmp && b->d_spec &&
+        if (bank_spec_reserve (b, samples, need) &&
             !arthip_copy2d (b->d_tmp + lead, (size_t) dense * sizeof (art_s), d_buffer, (size_t) pitch * sizeof (art_s),
                             (size_t) numFrames * sizeof (art_s), (size_t) b->C, b->stream) &&
             !arthip_biquad_spec_planar (b->d_sections, b->C, b->S, b->d_tmp + lead, dense, d_buffer, pitch, numFrames, L, b->warmup, b->d_spec,
@@ -513,7 +512,7 @@ void biquadBankApplyPlanarDevice (BiquadBank *b, artsample_t *d_buffer, long pit
             return;
         }
         LEAVE_DEVICE (b);
-        fprintf (stderr, "artamd: time-parallel biquad unavailable (%s): serial kernel\n", arthip_last_error ());
+        bank_spec_unavailable ();
     }
     artamd_biquad_batch_planar (&b, 1, &d_buffer, &pitch, &numFrames, 0, INT_MAX);       /* (INT_MAX: never handed back to this call) */
 }
@@ -833,62 +832,6 @@ static void dec_swap_if (Decimate *cxt, int rc)
 
 static int dec_reserve (Decimate *cxt, size_t in_bytes, size_t out_bytes);
 
-/* a sharded context's call on device buffers (the caller's, or this context's own staging of a host-pointer call): every shard
- * waits for the context's stream, pulls its channel slice with a slice kernel (peer-to-peer when it sits on another device),
- * decimates it with its own state and pushes its packed bytes into the interleaved output; the context's stream then waits for
- * all of them */
-static void dec_sharded_device_call (Decimate *cxt, const art_s *d_input, int frames, unsigned char *d_output)
-{
-    struct artamd_decimator *hip = cxt->hip;
-    const int C = cxt->numChannels, B = cxt->outputBytes, prev = arthip_current_device ();
-    const int wps = (int)(sizeof (art_s) / 4);
-
-    /* every shard's buffers first: a shard that cannot get them would leave its channels of the interleaved output unwritten, so
-     * the whole call then leaves silence behind, and the failure is counted (art_hip.h: the error contract) */
-    for (int k = 0; k < hip->nshards; ++k) {
-        Decimate *leaf = hip->shards [k];
-        const int width = hip->shard_first [k + 1] - hip->shard_first [k];
-        arthip_set_device (leaf->hip->device);
-        if (dec_reserve (leaf, (size_t) frames * width * sizeof (art_s), (size_t) frames * width * B)) {
-            pcm_fail ("sharded decimator: device allocation failed (output zeroed)");
-            arthip_set_device (hip->device);
-            arthip_zero (d_output, (size_t) frames * C * B, hip->stream);
-            if (prev >= 0) arthip_set_device (prev);
-            return;
-        }
-    }
-    arthip_set_device (hip->device);
-    arthip_event_record (hip->ev_parent, hip->stream);
-    for (int k = 0; k < hip->nshards; ++k) {
-        Decimate *leaf = hip->shards [k];
-        struct artamd_decimator *sp = leaf->hip;
-        const int first = hip->shard_first [k], width = hip->shard_first [k + 1] - first;
-        ArtDecArgs a;
-        arthip_set_device (sp->device);
-        arthip_stream_wait_event (sp->stream, hip->ev_parent);
-        arthip_slice_copy (sp->d_in, (size_t) width * wps, d_input + first, (size_t) C * wps, width * wps, (size_t) frames, sp->stream);
-        dec_args (leaf, &a);
-        dec_swap_if (leaf, arthip_decimate (&a, sp->d_in, frames, sp->d_out, sp->stream));
-        arthip_slice_copy_bytes (d_output + (size_t) first * B, (size_t) C * B, sp->d_out, (size_t) width * B, width * B, (size_t) frames, sp->stream);
-        arthip_event_record (hip->ev_shard [k], sp->stream);
-    }
-    arthip_set_device (hip->device);
-    for (int k = 0; k < hip->nshards; ++k)
-        arthip_stream_wait_event (hip->stream, hip->ev_shard [k]);
-    if (prev >= 0) arthip_set_device (prev);
-}
-
-void decimateProcessInterleavedLEDevice (Decimate *cxt, const artsample_t *d_input, int numInputFrames, unsigned char *d_output)
-{
-    if (numInputFrames <= 0) return;
-    if (cxt->hip->nshards) { dec_sharded_device_call (cxt, d_input, numInputFrames, d_output); return; }
-    ArtDecArgs a;
-    ENTER_DEVICE (cxt->hip);
-    dec_args (cxt, &a);
-    dec_swap_if (cxt, arthip_decimate (&a, d_input, numInputFrames, d_output, cxt->hip->stream));
-    LEAVE_DEVICE (cxt->hip);
-}
-
 /* a leaf context's call with a pitch on either side (0: interleaved); a one-channel context is the same call in either layout */
 static void dec_leaf_pitched (Decimate *cxt, const art_s *d_input, long in_pitch, int frames, unsigned char *d_output, long out_pitch)
 {
@@ -898,14 +841,19 @@ static void dec_leaf_pitched (Decimate *cxt, const art_s *d_input, long in_pitch
     dec_swap_if (cxt, arthip_decimate_pitched (&a, d_input, in_pitch, frames, d_output, out_pitch, cxt->hip->stream));
 }
 
-/* dec_sharded_device_call with planes on either side: a shard's channels are a run of the caller's planes, which the shard reads
- * or writes where they lie; an interleaved side (pitch 0) goes through the shard's staging as there */
-static void dec_sharded_planar_call (Decimate *cxt, const art_s *d_input, long in_pitch, int frames, unsigned char *d_output, long out_pitch)
+/* a sharded context's call on device buffers (the caller's, or this context's own staging of a host-pointer call), either side
+ * interleaved (pitch 0) or planar: every shard waits for the context's stream, decimates its channels with its own state, and the
+ * context's stream then waits for all of them.  An interleaved side goes through the shard's staging: the shard pulls its channel
+ * slice with a slice kernel (peer-to-peer when it sits on another device) and pushes its packed bytes into the interleaved output.
+ * On a planar side a shard's channels are a run of the caller's planes, which it reads or writes where they lie. */
+static void dec_sharded_call (Decimate *cxt, const art_s *d_input, long in_pitch, int frames, unsigned char *d_output, long out_pitch)
 {
     struct artamd_decimator *hip = cxt->hip;
     const int C = cxt->numChannels, B = cxt->outputBytes, prev = arthip_current_device ();
     const int wps = (int)(sizeof (art_s) / 4);
 
+    /* every shard's buffers first: a shard that cannot get them would leave its channels of the output unwritten, so the whole
+     * call then leaves silence behind, and the failure is counted (art_hip.h: the error contract) */
     for (int k = 0; k < hip->nshards; ++k) {
         Decimate *leaf = hip->shards [k];
         const int width = hip->shard_first [k + 1] - hip->shard_first [k];
@@ -939,13 +887,24 @@ static void dec_sharded_planar_call (Decimate *cxt, const art_s *d_input, long i
     if (prev >= 0) arthip_set_device (prev);
 }
 
+void decimateProcessInterleavedLEDevice (Decimate *cxt, const artsample_t *d_input, int numInputFrames, unsigned char *d_output)
+{
+    if (numInputFrames <= 0) return;
+    if (cxt->hip->nshards) { dec_sharded_call (cxt, d_input, 0, numInputFrames, d_output, 0); return; }
+    ArtDecArgs a;
+    ENTER_DEVICE (cxt->hip);
+    dec_args (cxt, &a);
+    dec_swap_if (cxt, arthip_decimate (&a, d_input, numInputFrames, d_output, cxt->hip->stream));
+    LEAVE_DEVICE (cxt->hip);
+}
+
 void decimateProcessPlanarLEDevice (Decimate *cxt, const artsample_t *d_input, long inputPitch, int numInputFrames,
                                     unsigned char *d_output, long outputPitch)
 {
     if (numInputFrames <= 0) return;
     if (cxt->numChannels == 1) inputPitch = outputPitch = 0;
     if (!inputPitch && !outputPitch) { decimateProcessInterleavedLEDevice (cxt, d_input, numInputFrames, d_output); return; }
-    if (cxt->hip->nshards) { dec_sharded_planar_call (cxt, d_input, inputPitch, numInputFrames, d_output, outputPitch); return; }
+    if (cxt->hip->nshards) { dec_sharded_call (cxt, d_input, inputPitch, numInputFrames, d_output, outputPitch); return; }
     ENTER_DEVICE (cxt->hip);
     dec_leaf_pitched (cxt, d_input, inputPitch, numInputFrames, d_output, outputPitch);
     LEAVE_DEVICE (cxt->hip);
@@ -1374,7 +1333,7 @@ int decimateProcessInterleavedLE (Decimate *cxt, const artsample_t *input, int n
     if (hip->nshards) {
         /* the whole interleaved buffer is staged on this context's device (one dense transfer each way), the shards work on it */
         const size_t out_bytes = samples * cxt->outputBytes;
-        dec_sharded_device_call (cxt, hip->d_in, numInputFrames, hip->d_out);
+        dec_sharded_call (cxt, hip->d_in, 0, numInputFrames, hip->d_out, 0);
         if (out_bytes + 16 <= DEC_KERNEL_COPY_LIMIT) {
             arthip_copy_by_kernel (hip->h_out, hip->d_out, (out_bytes + 3) & ~(size_t) 3, hip->stream);
             arthip_sync (hip->stream);

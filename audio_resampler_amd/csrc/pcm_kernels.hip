@@ -414,6 +414,37 @@ __device__ __forceinline__ uint32_t tpdf_step (uint32_t &g, int dither_type)
 // u / 2^31 - 1.0, converted to the sample type, is exactly this (power-of-two scale)
 __device__ __forceinline__ art_s tpdf_value (uint32_t u) { return (art_s)(int)(u ^ 0x80000000u) * (art_s) 4.656612873077392578125e-10; }
 
+// ---------------------------------------------------------------------------------------------------
+// The output format, once for every decimator kernel (reference decimator.c:266-283): a code value is clipped to the format's range,
+// shifted up to whole bytes (8-bit codes are offset binary: + 128), and leaves as `pad` zero bytes and then its `width` value bytes,
+// least significant first.  Every kernel but decimate_kernel builds a DecFmt once, clips with DEC_CLIP and stores with DEC_STORE_BYTES (interleaved
+// bytes, one at a time) or packs dec_word (planar bytes, in whole units).
+// DEC_FMT, DEC_CLIP and DEC_STORE_BYTES are TEXT, not functions: as __forceinline__ functions (the clip returning bool, or taking the
+// count as a callable; the format returned by value) each moved the register rows of the interleaved serial kernels, which must
+// stay the parent's (profiles/pcm_shared_parts.txt has the table of every form tried).
+// ---------------------------------------------------------------------------------------------------
+struct DecFmt { int nbytes, width, pad, hi, lo, shift; uint32_t bias; };
+// the fields of a DecFmt in order: nbytes, width, pad, hi, lo, shift, bias
+#define DEC_FMT(bits, bytes) { (bytes), ((bits) + 7) / 8, (bytes) - ((bits) + 7) / 8, (1 << ((bits) - 1)) - 1, ~((1 << ((bits) - 1)) - 1), (24 - (bits)) % 8, (bits) <= 8 ? 128u : 0u }
+__device__ __forceinline__ DecFmt dec_fmt (int bits, int bytes) { const DecFmt f = DEC_FMT (bits, bytes); return f; }
+// q into the format's range; COUNT is the statement that counts a clip (a register, or the batch's LDS counter per lane)
+#define DEC_CLIP(fm, q, COUNT) do { if ((q) > (fm).hi) { (q) = (fm).hi; COUNT; } else if ((q) < (fm).lo) { (q) = (fm).lo; COUNT; } } while (0)
+__device__ __forceinline__ uint32_t dec_value (const DecFmt &f, int q) { return ((uint32_t) q << f.shift) + f.bias; }
+// a clipped code value's nbytes output bytes at `at`, byte by byte (an interleaved sample has no alignment to speak of)
+#define DEC_STORE_BYTES(at, fm, q) do { const uint32_t v_ = ((uint32_t)(q) << (fm).shift) + (fm).bias; unsigned char *o_ = (at); \
+        for (int j_ = 0; j_ < (fm).pad; ++j_) *o_++ = 0; \
+        *o_++ = (unsigned char) v_; \
+        if ((fm).width > 1) { *o_++ = (unsigned char)(v_ >> 8); if ((fm).width > 2) *o_++ = (unsigned char)(v_ >> 16); } } while (0)
+// ... and the same bytes as one little-endian word (the planar sides' packers)
+__device__ __forceinline__ uint32_t dec_word (const DecFmt &f, int q)
+{
+    return (dec_value (f, q) & (0xffffffffu >> (32 - 8 * f.width))) << (8 * f.pad);
+}
+
+// the one-lane form: calls under 64 frames, and the host-pointer planar call.  Its dither and rounding are written as the reference
+// writes them (through double), where the chunked kernels below use tpdf_value and round_half_up.  Its clip and store are written out
+// too, NOT through DEC_CLIP / DEC_STORE_BYTES: with them its registers were the same and its code two scalar instructions other, and
+// 63-frame calls measured 2-4 % slower in two alternating runs (profiles/pcm_shared_parts.txt), so by the rule of that change it stays.
 __global__ void decimate_kernel (ArtDecArgs a, const art_s *in, long in_pitch, int frames, unsigned char *out, long out_pitch)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -892,24 +923,6 @@ constexpr int DEC_SEG = ART_DEC_SEG;               // consecutive samples of one
 constexpr int DEC_VEC = 16 / (int) sizeof (art_s);
 typedef art_s dec_vec_t __attribute__ ((ext_vector_type (DEC_VEC)));
 
-struct DecFmt { int nbytes, width, pad, hi, lo, shift; uint32_t bias; };
-__device__ __forceinline__ DecFmt dec_fmt (int bits, int bytes)
-{
-    DecFmt f;
-    f.nbytes = bytes; f.width = (bits + 7) / 8; f.pad = bytes - f.width;
-    f.hi = (1 << (bits - 1)) - 1; f.lo = ~f.hi;
-    f.shift = (24 - bits) % 8;
-    f.bias = bits <= 8 ? 128u : 0u;
-    return f;
-}
-// the nbytes little-endian output bytes of a clipped code value, as one word (the kernels' byte stores: pad zero bytes, then
-// the value's `width` bytes)
-__device__ __forceinline__ uint32_t dec_word (const DecFmt &f, int q)
-{
-    const uint32_t v = ((uint32_t) q << f.shift) + f.bias;
-    return (v & (0xffffffffu >> (32 - 8 * f.width))) << (8 * f.pad);
-}
-
 // w's bytes at byte `pos` (0..15) of the 16-byte image hi:lo; bytes past the image are dropped
 __device__ __forceinline__ void dec_place (uint64_t &lo, uint64_t &hi, uint32_t w, int pos)
 {
@@ -1028,12 +1041,20 @@ __device__ __forceinline__ void dec_store_unit (unsigned char *p, int n, int nby
     }
 }
 
-// One task of the time-parallel kernels with a pitch on either side: frames [n0, n0 + cnt) of channel c through the kernels' own
-// per-sample expressions.  A planar input is read as one run, a planar output packed into 16-byte stores; returns the clip count.
-template <bool DITHER>
-__device__ __forceinline__ unsigned int dec_segment_pitched (const art_s *in, long in_pitch, unsigned char *out, long out_pitch, int C, int c, long n0, int cnt,
-                                                             const DecFmt &fm, art_s scale, art_s fb, int dtype, uint32_t &g)
+// One task of the time-parallel kernels (no noise shaping, so no recurrence: the feedback term is a constant, decimator.c:264-265):
+// frames [n0, n0 + DEC_SEG) of channel c of item `a`, the generator jumped to n0.  PITCHED: either side may be planar — a planar
+// input is read as one run, a planar output packed into 16-byte stores; without it both sides are interleaved and the pitches are
+// not looked at.  The channel's last task leaves the generator state in gens_next (the rest still read gens; the host swaps them).
+template <bool DITHER, bool PITCHED>
+__device__ __forceinline__ void dec_parallel_task (const ArtDecTask &a, int c, long n0)
 {
+    const art_s *const in = a.in;
+    unsigned char *const out = a.out;
+    const long in_pitch = PITCHED ? a.in_pitch : 0, out_pitch = PITCHED ? a.out_pitch : 0;
+    const int C = a.C, dtype = a.dither_type, cnt = (int) min ((long) DEC_SEG, a.frames - n0);
+    const DecFmt fm = dec_fmt (a.bits, a.bytes);
+    const art_s scale = a.scale, fb = a.feedback [c];
+    uint32_t g = DITHER ? jump_pairs (a.gens [c], (unsigned int)(n0 / 2)) : 0u;
     unsigned int clips = 0;
     DecPacker pk;
     unsigned char *const rows = out + ((size_t) n0 * C + c) * fm.nbytes;        // interleaved output: frame i at rows + i * C * nbytes
@@ -1044,19 +1065,15 @@ __device__ __forceinline__ unsigned int dec_segment_pitched (const art_s *in, lo
         const art_s code = scaled - fb;
         const art_s dithered = code + dither;
         int q = (int) round_half_up (dithered);
-        if (q > fm.hi) { q = fm.hi; clips++; }
-        else if (q < fm.lo) { q = fm.lo; clips++; }
-        const uint32_t w = dec_word (fm, q);
-        if (out_pitch) pk.put (w, fm.nbytes);
-        else {
-            unsigned char *o = rows + (size_t) i * C * fm.nbytes;
-            for (int j = 0; j < fm.nbytes; ++j) o [j] = (unsigned char)(w >> (8 * j));
-        }
+        DEC_CLIP (fm, q, clips++);
+        if (out_pitch) pk.put (dec_word (fm, q), fm.nbytes);
+        else DEC_STORE_BYTES (rows + (size_t) i * C * fm.nbytes, fm, q);
     };
     if (in_pitch) dec_for_run (in + (long) c * in_pitch + n0, cnt, one);
     else for (int i = 0; i < cnt; ++i) one (i, in [(size_t)(n0 + i) * C + c]);
     if (out_pitch) pk.end ();
-    return clips;
+    if (DITHER && n0 + cnt == a.frames) a.gens_next [c] = g;
+    if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
 }
 
 template <int ORDER, bool DITHER, bool PITCHED = false>                  // ORDER 0 = no noise shaping
@@ -1076,11 +1093,8 @@ void decimate_lds_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned ch
         if (DITHER) s_gen [tid] = a.gens [c0 + tid];
         if (ORDER) load_section (sh, a.shapers [c0 + tid]);
     }
-    const int nbytes = a.bytes, width = (a.bits + 7) / 8, pad = nbytes - width;
-    const int hi = (1 << (a.bits - 1)) - 1, lo = ~hi;
-    const int shift = (24 - a.bits) % 8;
-    const uint32_t bias = a.bits <= 8 ? 128u : 0u;
-    const int dtype = a.dither_type;
+    const DecFmt fm = dec_fmt (a.bits, a.bytes);
+    const int nbytes = fm.nbytes, dtype = a.dither_type;
     const art_s scale = a.scale;
     __syncthreads ();
 
@@ -1151,14 +1165,12 @@ void decimate_lds_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned ch
 
         // ---- phase C (all threads): clip, pack little-endian, store
         if (PITCHED && out_pitch) {                // a channel's bytes are one run of its plane
-            const DecFmt fm = dec_fmt (a.bits, nbytes);
             const int units = dec_store_units (nf * nbytes);
             for (int e = tid; e < units * Cg; e += ST_THREADS) {
                 const int c = e / units, u = e - c * units;
                 dec_store_unit (out + (long)(c0 + c) * out_pitch + (long) f0 * nbytes, nf, nbytes, u, [&] (int f, bool counted) {
                     int q = (int) tile [f * Cg + c];
-                    if (q > hi) { q = hi; if (counted) clips++; }
-                    else if (q < lo) { q = lo; if (counted) clips++; }
+                    DEC_CLIP (fm, q, if (counted) clips++);
                     return dec_word (fm, q);
                 });
             }
@@ -1167,13 +1179,8 @@ void decimate_lds_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned ch
         for (int e = tid; e < nf * Cg; e += ST_THREADS) {
             const int f = e / Cg, c = e - f * Cg;
             int q = (int) tile [e];
-            if (q > hi) { q = hi; clips++; }
-            else if (q < lo) { q = lo; clips++; }
-            const uint32_t v = ((uint32_t) q << shift) + bias;
-            unsigned char *o = out + ((size_t)(f0 + f) * a.C + c0 + c) * nbytes;
-            for (int j = 0; j < pad; ++j) *o++ = 0;
-            *o++ = (unsigned char) v;
-            if (width > 1) { *o++ = (unsigned char)(v >> 8); if (width > 2) *o++ = (unsigned char)(v >> 16); }
+            DEC_CLIP (fm, q, clips++);
+            DEC_STORE_BYTES (out + ((size_t)(f0 + f) * a.C + c0 + c) * nbytes, fm, q);
         }
         __syncthreads ();
     }
@@ -1215,11 +1222,8 @@ void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned c
         if (DITHER) s_gen [0][tid] = a.gens [c0 + tid];
         load_section (sh, a.shapers [c0 + tid]);
     }
-    const int nbytes = a.bytes, width = (a.bits + 7) / 8, pad = nbytes - width;
-    const int hi = (1 << (a.bits - 1)) - 1, lo = ~hi;
-    const int shift = (24 - a.bits) % 8;
-    const uint32_t bias = a.bits <= 8 ? 128u : 0u;
-    const int dtype = a.dither_type;
+    const DecFmt fm = dec_fmt (a.bits, a.bytes);
+    const int nbytes = fm.nbytes, dtype = a.dither_type;
     const art_s scale = a.scale;
     constexpr int HELPERS = ST_THREADS - 64;
     __syncthreads ();
@@ -1257,14 +1261,12 @@ void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned c
                 const int k = it - 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);
                 const art_s *tile = tiles + (k % 3) * DEC_CHUNK;
                 if (PITCHED && out_pitch) {        // a channel's bytes are one run of its plane
-                    const DecFmt fm = dec_fmt (a.bits, nbytes);
                     const int units = dec_store_units (nf * nbytes);
                     for (int e = ht; e < units * Cg; e += HELPERS) {
                         const int c = e / units, u = e - c * units;
                         dec_store_unit (out + (long)(c0 + c) * out_pitch + (long) f0 * nbytes, nf, nbytes, u, [&] (int f, bool counted) {
                             int q = (int) tile [c * pitch + f];
-                            if (q > hi) { q = hi; if (counted) clips++; }
-                            else if (q < lo) { q = lo; if (counted) clips++; }
+                            DEC_CLIP (fm, q, if (counted) clips++);
                             return dec_word (fm, q);
                         });
                     }
@@ -1273,13 +1275,8 @@ void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned c
                 for (int e = ht; e < nf * Cg; e += HELPERS) {
                     const int f = e / Cg, c = e - f * Cg;
                     int q = (int) tile [c * pitch + f];
-                    if (q > hi) { q = hi; clips++; }
-                    else if (q < lo) { q = lo; clips++; }
-                    const uint32_t v = ((uint32_t) q << shift) + bias;
-                    unsigned char *o = out + ((size_t)(f0 + f) * a.C + c0 + c) * nbytes;
-                    for (int j = 0; j < pad; ++j) *o++ = 0;
-                    *o++ = (unsigned char) v;
-                    if (width > 1) { *o++ = (unsigned char)(v >> 8); if (width > 2) *o++ = (unsigned char)(v >> 16); }
+                    DEC_CLIP (fm, q, clips++);
+                    DEC_STORE_BYTES (out + ((size_t)(f0 + f) * a.C + c0 + c) * nbytes, fm, q);
                 }
             }
         }
@@ -1287,30 +1284,7 @@ void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned c
             const int f0 = it * chunk_frames, nf = min (chunk_frames, frames - f0);
             art_s *tile = tiles + (it % 3) * DEC_CHUNK;
             const art_s *dth = dths + (it & 1) * DEC_CHUNK;
-            auto one = [&] (art_s smp, art_s dither) -> art_s {
-                const art_s scaled = smp;                       // already times `scale` (phase A)
-                const art_s code = scaled - fb;
-                const art_s dithered = code + dither;
-                const art_s qf = round_half_up (dithered);
-                const art_s err = qf - code;
-                fb = shaper_step<ORDER> (sh, err);
-                return qf;
-            };
-            typedef art_s vec4 __attribute__ ((ext_vector_type (4)));
-            art_s *mine = tile + tid * pitch;
-            const art_s *my_dither = dth + tid * pitch;
-            int f = 0;
-            for (; f + 8 <= nf; f += 8) {
-                vec4 xa = *reinterpret_cast<const vec4 *> (mine + f), xb = *reinterpret_cast<const vec4 *> (mine + f + 4), da, db;
-                if (DITHER) { da = *reinterpret_cast<const vec4 *> (my_dither + f); db = *reinterpret_cast<const vec4 *> (my_dither + f + 4); }
-                else { da = (art_s) 0; db = (art_s) 0; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) xa [u] = one (xa [u], da [u]);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) xb [u] = one (xb [u], db [u]);
-                *reinterpret_cast<vec4 *> (mine + f) = xa; *reinterpret_cast<vec4 *> (mine + f + 4) = xb;
-            }
-            for (; f < nf; ++f) mine [f] = one (mine [f], DITHER ? my_dither [f] : (art_s) 0);
+#include "pcm_dec_serial_row.inc"
         }
         // LDS-only barrier: the helpers' stores (and loads already consumed) stay in flight; nobody reads global memory
         // that this launch writes
@@ -1332,53 +1306,18 @@ void decimate_pipe_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned c
 // is still being read by other threads); the host swaps them.
 template <bool DITHER, bool PITCHED = false>
 __global__ __launch_bounds__ (256)
-void decimate_parallel_kernel (ArtDecArgs a, const art_s *in, int frames, unsigned char *out, uint32_t *gens_out, long in_pitch, long out_pitch)
+void decimate_parallel_kernel (ArtDecTask a)       // one item, by value (task0 = 0)
 {
     const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
     if (PITCHED) {                                 // neighbouring threads are neighbouring segments of one plane
-        const long segs = (frames + DEC_SEG - 1) / DEC_SEG;
+        const long segs = (a.frames + DEC_SEG - 1) / DEC_SEG;
         if (task >= segs * a.C) return;
         const int c = (int)(task / segs);
-        const long n0 = (task - c * segs) * DEC_SEG;
-        const int cnt = (int) min ((long) DEC_SEG, frames - n0);
-        uint32_t g = DITHER ? jump_pairs (a.gens [c], (unsigned int)(n0 / 2)) : 0u;
-        const unsigned int clips = dec_segment_pitched<DITHER> (in, in_pitch, out, out_pitch, a.C, c, n0, cnt, dec_fmt (a.bits, a.bytes), a.scale,
-                                                                a.feedback [c], a.dither_type, g);
-        if (DITHER && n0 + cnt == frames) gens_out [c] = g;
-        if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
+        dec_parallel_task<DITHER, true> (a, c, (task - c * segs) * DEC_SEG);
         return;
     }
-    const int c = (int)(task % a.C);
-    const long seg = task / a.C;
-    const long n0 = seg * DEC_SEG;
-    if (n0 >= frames) return;
-    const int cnt = (int) min ((long) DEC_SEG, frames - n0);
-
-    const int nbytes = a.bytes, width = (a.bits + 7) / 8, pad = nbytes - width;
-    const int hi = (1 << (a.bits - 1)) - 1, lo = ~hi;
-    const int shift = (24 - a.bits) % 8;
-    const uint32_t bias = a.bits <= 8 ? 128u : 0u;
-    const art_s fb = a.feedback [c];                      // constant without shaping (decimator.c:264-265)
-    uint32_t g = DITHER ? jump_pairs (a.gens [c], (unsigned int)(n0 / 2)) : 0u;
-    unsigned int clips = 0;
-
-    for (int i = 0; i < cnt; ++i) {
-        const art_s dither = DITHER ? tpdf_value (tpdf_step (g, a.dither_type)) : 0.0f;
-        const size_t e = (size_t)(n0 + i) * a.C + c;
-        const art_s scaled = in [e] * a.scale;
-        const art_s code = scaled - fb;
-        const art_s dithered = code + dither;
-        int q = (int) round_half_up (dithered);
-        if (q > hi) { q = hi; clips++; }
-        else if (q < lo) { q = lo; clips++; }
-        const uint32_t v = ((uint32_t) q << shift) + bias;
-        unsigned char *o = out + e * nbytes;
-        for (int j = 0; j < pad; ++j) *o++ = 0;
-        *o++ = (unsigned char) v;
-        if (width > 1) { *o++ = (unsigned char)(v >> 8); if (width > 2) *o++ = (unsigned char)(v >> 16); }
-    }
-    if (DITHER && n0 + cnt == frames) gens_out [c] = g;
-    if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
+    const long n0 = (task / a.C) * DEC_SEG;        // neighbouring threads are neighbouring channels of the same frames
+    if (n0 < a.frames) dec_parallel_task<DITHER, false> (a, (int)(task % a.C), n0);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1477,26 +1416,17 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
                         if (nfc > 0 && f < dec_store_units (nfc * fm.nbytes))
                             dec_store_unit (s_out [c] + (size_t) f0 * fm.nbytes, nfc, fm.nbytes, f, [&] (int i, bool counted) {
                                 int q = (int) tile [c * pitch + i];
-                                if (q > fm.hi) { q = fm.hi; if (counted) atomicAdd (&s_clips [c], 1u); }
-                                else if (q < fm.lo) { q = fm.lo; if (counted) atomicAdd (&s_clips [c], 1u); }
+                                DEC_CLIP (fm, q, if (counted) atomicAdd (&s_clips [c], 1u));
                                 return dec_word (fm, q);
                             });
                         continue;
                     }
                     if ((PITCHED && f >= nf) || f0 + f >= s_frames [c]) continue;
                     const int fmt = s_fmt [c], bits = fmt & 255, nbytes = (fmt >> 8) & 255;
-                    const int width = (bits + 7) / 8, pad = nbytes - width;
-                    const int hi = (1 << (bits - 1)) - 1, lo = ~hi;
-                    const int shift = (24 - bits) % 8;
-                    const uint32_t bias = bits <= 8 ? 128u : 0u;
+                    const DecFmt fm = DEC_FMT (bits, nbytes);
                     int q = (int) tile [c * pitch + f];
-                    if (q > hi) { q = hi; atomicAdd (&s_clips [c], 1u); }
-                    else if (q < lo) { q = lo; atomicAdd (&s_clips [c], 1u); }
-                    const uint32_t v = ((uint32_t) q << shift) + bias;
-                    unsigned char *o = s_out [c] + (size_t)(f0 + f) * (PITCHED ? s_ostride [c] : s_stride [c]) * nbytes;
-                    for (int j = 0; j < pad; ++j) *o++ = 0;
-                    *o++ = (unsigned char) v;
-                    if (width > 1) { *o++ = (unsigned char)(v >> 8); if (width > 2) *o++ = (unsigned char)(v >> 16); }
+                    DEC_CLIP (fm, q, atomicAdd (&s_clips [c], 1u));
+                    DEC_STORE_BYTES (s_out [c] + (size_t)(f0 + f) * (PITCHED ? s_ostride [c] : s_stride [c]) * fm.nbytes, fm, q);
                 }
             }
         }
@@ -1504,29 +1434,7 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
             const int f0 = it * chunk_frames, nf = min (chunk_frames, my_frames - f0);
             art_s *tile = tiles + (it % 3) * span;
             const art_s *dth = dths + (it & 1) * span;
-            auto one = [&] (art_s smp, art_s dither) -> art_s {
-                const art_s scaled = smp;                       // already times the lane's `scale` (phase A)
-                const art_s code = scaled - fb;
-                const art_s dithered = code + dither;
-                const art_s qf = round_half_up (dithered);
-                if (ORDER) { const art_s err = qf - code; fb = shaper_step<ORDER> (sh, err); }
-                return qf;
-            };
-            typedef art_s vec4 __attribute__ ((ext_vector_type (4)));
-            art_s *row = tile + tid * pitch;
-            const art_s *my_dither = dth + tid * pitch;
-            int f = 0;
-            for (; f + 8 <= nf; f += 8) {
-                vec4 xa = *reinterpret_cast<const vec4 *> (row + f), xb = *reinterpret_cast<const vec4 *> (row + f + 4), da, db;
-                if (DITHER) { da = *reinterpret_cast<const vec4 *> (my_dither + f); db = *reinterpret_cast<const vec4 *> (my_dither + f + 4); }
-                else { da = (art_s) 0; db = (art_s) 0; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) xa [u] = one (xa [u], da [u]);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) xb [u] = one (xb [u], db [u]);
-                *reinterpret_cast<vec4 *> (row + f) = xa; *reinterpret_cast<vec4 *> (row + f + 4) = xb;
-            }
-            for (; f < nf; ++f) row [f] = one (row [f], DITHER ? my_dither [f] : (art_s) 0);
+#include "pcm_dec_serial_row.inc"
         }
         // LDS-only barrier, as in decimate_pipe_kernel: nobody reads global memory that this launch writes
         asm volatile ("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1561,51 +1469,14 @@ void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
     if (task >= tasks) return;
     const ArtDecTask &a = item_of (items, n, task);
     const long t = task - a.task0;
-    if (PITCHED && (a.in_pitch || a.out_pitch)) {  // (an interleaved item of the class takes the code below)
+    if (PITCHED && (a.in_pitch || a.out_pitch)) {  // neighbouring threads are neighbouring segments of one plane
         const long segs = (a.frames + DEC_SEG - 1) / DEC_SEG;
         const int c = (int)(t / segs);
-        const long n0 = (t - c * segs) * DEC_SEG;
-        const int cnt = (int) min ((long) DEC_SEG, a.frames - n0);
-        uint32_t g = DITHER ? jump_pairs (a.gens [c], (unsigned int)(n0 / 2)) : 0u;
-        const unsigned int clips = dec_segment_pitched<DITHER> (a.in, a.in_pitch, a.out, a.out_pitch, a.C, c, n0, cnt, dec_fmt (a.bits, a.bytes), a.scale,
-                                                                a.feedback [c], a.dither_type, g);
-        if (DITHER && n0 + cnt == a.frames) a.gens_next [c] = g;
-        if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
+        dec_parallel_task<DITHER, true> (a, c, (t - c * segs) * DEC_SEG);
         return;
     }
-    const int c = (int)(t % a.C);
-    const long n0 = (t / a.C) * DEC_SEG;
-    const int frames = a.frames;
-    if (n0 >= frames) return;
-    const int cnt = (int) min ((long) DEC_SEG, frames - n0);
-
-    const int nbytes = a.bytes, width = (a.bits + 7) / 8, pad = nbytes - width;
-    const int hi = (1 << (a.bits - 1)) - 1, lo = ~hi;
-    const int shift = (24 - a.bits) % 8;
-    const uint32_t bias = a.bits <= 8 ? 128u : 0u;
-    const art_s fb = a.feedback [c];                      // constant without shaping (decimator.c:264-265)
-    const art_s scale = a.scale;
-    const int dtype = a.dither_type, C = a.C;
-    uint32_t g = DITHER ? jump_pairs (a.gens [c], (unsigned int)(n0 / 2)) : 0u;
-    unsigned int clips = 0;
-
-    for (int i = 0; i < cnt; ++i) {
-        const art_s dither = DITHER ? tpdf_value (tpdf_step (g, dtype)) : 0.0f;
-        const size_t e = (size_t)(n0 + i) * C + c;
-        const art_s scaled = a.in [e] * scale;
-        const art_s code = scaled - fb;
-        const art_s dithered = code + dither;
-        int q = (int) round_half_up (dithered);
-        if (q > hi) { q = hi; clips++; }
-        else if (q < lo) { q = lo; clips++; }
-        const uint32_t v = ((uint32_t) q << shift) + bias;
-        unsigned char *o = a.out + e * nbytes;
-        for (int j = 0; j < pad; ++j) *o++ = 0;
-        *o++ = (unsigned char) v;
-        if (width > 1) { *o++ = (unsigned char)(v >> 8); if (width > 2) *o++ = (unsigned char)(v >> 16); }
-    }
-    if (DITHER && n0 + cnt == frames) a.gens_next [c] = g;
-    if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
+    const long n0 = (t / a.C) * DEC_SEG;           // (an interleaved item of a PITCHED class as well) neighbouring threads are
+    if (n0 < a.frames) dec_parallel_task<DITHER, false> (a, (int)(t % a.C), n0);       // neighbouring channels of the same frames
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1619,6 +1490,31 @@ constexpr int BQ_Q = 16 / (int) sizeof (art_s);    // frames to 16 bytes
 typedef art_s bq_vecq __attribute__ ((ext_vector_type (BQ_Q)));
 // a lane whose frames are consecutive (a plane, or a one-channel bank) from a 16-byte boundary: the helper waves move it 16 bytes at a time
 __device__ __forceinline__ bool bq_plane_aligned (const art_s *buf, int stride) { return stride == 1 && !((uintptr_t) buf & 15); }
+
+// The helper waves' move of one chunk (frames [f0, f0 + nf) of every lane) between the lanes' buffers and an LDS tile, LOAD: into
+// the tile.  Task e = (lane c, frame f), a thread walks one lane's frames.  A plane on a 16-byte boundary (f0 is a multiple of 4)
+// goes 16 bytes at a time: the first thread of every whole group of BQ_Q frames moves the group.
+template <bool LOAD>
+__device__ __forceinline__ void bq_move_chunk (art_s *tile, int pitch, int lanes, int f0, int nf, int first, int step,
+                                               art_s *const *bufs, const int *strides, const int *counts)
+{
+    for (int e = first; e < nf * lanes; e += step) {
+        const int c = e / nf, f = e - c * nf;
+        const int left = counts [c] - (f0 + f);
+        if (left <= 0) continue;
+        art_s *const g = bufs [c] + (size_t)(f0 + f) * strides [c], *const t = tile + c * pitch + f;
+        if (bq_plane_aligned (bufs [c], strides [c])) {
+            if (left >= BQ_Q - (f & (BQ_Q - 1))) {
+                if (!(f & (BQ_Q - 1))) {
+                    if (LOAD) *reinterpret_cast<bq_vecq *> (t) = *reinterpret_cast<const bq_vecq *> (g);
+                    else *reinterpret_cast<bq_vecq *> (g) = *reinterpret_cast<const bq_vecq *> (t);
+                }
+                continue;
+            }
+        }
+        if (LOAD) *t = *g; else *g = *t;
+    }
+}
 
 constexpr int BQ_BATCH_RUN = 60;                   // frames per chunk at most (the decimator batch's: fill and drain cost two chunks)
 
@@ -1656,40 +1552,13 @@ void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_fram
     for (int it = -1; it <= nchunks; ++it) {
         if (wave >= 1) {
             const int ht = tid - 64;
-            if (it + 1 < nchunks) {                // ---- load chunk it+1 (a thread walks one lane's frames)
-                const int k = it + 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);
-                art_s *tile = tiles + (k % 3) * span;
-                for (int e = ht; e < nf * lanes; e += HELPERS) {
-                    const int c = e / nf, f = e - c * nf;
-                    const int left = s_frames [c] - (f0 + f);
-                    if (left <= 0) continue;
-                    const art_s *g = s_buf [c] + (size_t)(f0 + f) * s_stride [c];
-                    if (bq_plane_aligned (s_buf [c], s_stride [c])) {
-                        // a plane on a 16-byte boundary (f0 is a multiple of 4): the first thread of every whole group of BQ_Q frames moves it
-                        if (left >= BQ_Q - (f & (BQ_Q - 1))) {
-                            if (!(f & (BQ_Q - 1))) *reinterpret_cast<bq_vecq *> (tile + c * pitch + f) = *reinterpret_cast<const bq_vecq *> (g);
-                            continue;
-                        }
-                    }
-                    tile [c * pitch + f] = *g;
-                }
+            if (it + 1 < nchunks) {                // ---- load chunk it+1
+                const int k = it + 1, f0 = k * chunk_frames;
+                bq_move_chunk<true> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS, s_buf, s_stride, s_frames);
             }
             if (it >= 1) {                         // ---- store chunk it-1
-                const int k = it - 1, f0 = k * chunk_frames, nf = min (chunk_frames, frames - f0);
-                const art_s *tile = tiles + (k % 3) * span;
-                for (int e = ht; e < nf * lanes; e += HELPERS) {
-                    const int c = e / nf, f = e - c * nf;
-                    const int left = s_frames [c] - (f0 + f);
-                    if (left <= 0) continue;
-                    art_s *g = s_buf [c] + (size_t)(f0 + f) * s_stride [c];
-                    if (bq_plane_aligned (s_buf [c], s_stride [c])) {
-                        if (left >= BQ_Q - (f & (BQ_Q - 1))) {
-                            if (!(f & (BQ_Q - 1))) *reinterpret_cast<bq_vecq *> (g) = *reinterpret_cast<const bq_vecq *> (tile + c * pitch + f);
-                            continue;
-                        }
-                    }
-                    *g = tile [c * pitch + f];
-                }
+                const int k = it - 1, f0 = k * chunk_frames;
+                bq_move_chunk<false> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS, s_buf, s_stride, s_frames);
             }
         }
         else if (tid < lanes && it >= 0 && it < nchunks && it * chunk_frames < my_frames) {     // ---- the cascade over chunk it
@@ -1803,6 +1672,88 @@ static constexpr int BQ_BATCH_WORKGROUPS = 512;
 // frames per chunk of a serial batch workgroup of L lanes: the LDS tile's row (a multiple of 4) or `run`, whichever is less
 static int batch_chunk_frames (int L, int run) { return min (((DEC_CHUNK / L) - 4) & ~3, run); }
 
+// The decimator kernel of a launch from its shaper order (0: none; above 4 as 4), whether dither is on and whether a side is planar:
+// one function per kernel family, the only places that name an instantiation.  The pipelined families' dynamic LDS goes up to
+// DEC_PIPE_LDS, past the default limit: that is set the first time an instantiation is handed out.
+typedef void (*DecCallKernel) (ArtDecArgs, const art_s *, int, unsigned char *, int, long, long);
+typedef void (*DecParallelKernel) (ArtDecTask);
+typedef void (*DecBatchPipeKernel) (const ArtDecLane *, int, int);
+typedef void (*DecBatchParallelKernel) (const ArtDecTask *, int, long);
+static constexpr size_t DEC_PIPE_LDS = (size_t) 5 * DEC_CHUNK * sizeof (art_s);          // three sample tiles, two dither tiles
+
+#define DEC_PICK2(KERNEL) (pitched ? (dither ? KERNEL<true, true> : KERNEL<false, true>) : (dither ? KERNEL<true, false> : KERNEL<false, false>))
+#define DEC_PICK3(KERNEL, O) (pitched ? (dither ? KERNEL<O, true, true> : KERNEL<O, false, true>) : (dither ? KERNEL<O, true, false> : KERNEL<O, false, false>))
+static DecParallelKernel dec_parallel_kernel (bool dither, bool pitched) { return DEC_PICK2 (decimate_parallel_kernel); }
+static DecBatchParallelKernel dec_batch_parallel_kernel (bool dither, bool pitched) { return DEC_PICK2 (decimate_batch_parallel_kernel); }
+static DecCallKernel dec_lds_kernel (int order, bool dither, bool pitched)
+{
+    switch (order) {
+        case 0: return DEC_PICK3 (decimate_lds_kernel, 0);
+        case 1: return DEC_PICK3 (decimate_lds_kernel, 1);
+        case 2: return DEC_PICK3 (decimate_lds_kernel, 2);
+        case 3: return DEC_PICK3 (decimate_lds_kernel, 3);
+        default: return DEC_PICK3 (decimate_lds_kernel, 4);
+    }
+}
+template <typename Kernel>
+static Kernel dec_pipe_lds_allowed (Kernel k, int order, bool dither, bool pitched, bool (&done) [5][2][2])
+{
+    bool &once = done [order < 0 || order > 4 ? 4 : order][dither][pitched];      // (as the pickers' switches: anything else is 4)
+    if (!once) { (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) DEC_PIPE_LDS); once = true; }
+    return k;
+}
+static DecCallKernel dec_pipe_kernel (int order, bool dither, bool pitched)               // order >= 1
+{
+    static bool done [5][2][2];
+    DecCallKernel k;
+    switch (order) {
+        case 1: k = DEC_PICK3 (decimate_pipe_kernel, 1); break;
+        case 2: k = DEC_PICK3 (decimate_pipe_kernel, 2); break;
+        case 3: k = DEC_PICK3 (decimate_pipe_kernel, 3); break;
+        default: k = DEC_PICK3 (decimate_pipe_kernel, 4); break;
+    }
+    return dec_pipe_lds_allowed (k, order, dither, pitched, done);
+}
+static DecBatchPipeKernel dec_batch_pipe_kernel (int order, bool dither, bool pitched)
+{
+    static bool done [5][2][2];
+    DecBatchPipeKernel k;
+    switch (order) {
+        case 0: k = DEC_PICK3 (decimate_batch_pipe_kernel, 0); break;
+        case 1: k = DEC_PICK3 (decimate_batch_pipe_kernel, 1); break;
+        case 2: k = DEC_PICK3 (decimate_batch_pipe_kernel, 2); break;
+        case 3: k = DEC_PICK3 (decimate_batch_pipe_kernel, 3); break;
+        default: k = DEC_PICK3 (decimate_batch_pipe_kernel, 4); break;
+    }
+    return dec_pipe_lds_allowed (k, order, dither, pitched, done);
+}
+#undef DEC_PICK3
+#undef DEC_PICK2
+
+// The time-parallel bit-exact cascade (biquad_spec_kernel), the one body of arthip_biquad_spec (strides) and arthip_biquad_spec_planar
+// (pitches)
+template <bool PLANAR>
+static int biquad_spec_launch (Biquad *d_sections, int C, int S, const art_s *d_in, spec_stride<PLANAR> in_stride, art_s *d_out, spec_stride<PLANAR> out_stride,
+                               int frames, int L, int W, void *d_states, int *d_first_bad, unsigned int *d_repairs, void *stream)
+{
+    if (frames <= 0) return 0;
+    if (S < 1 || S > MAX_CHAIN || L < 1) return -1;
+    const int K = (frames + L - 1) / L;
+    SpecState *starts = (SpecState *) d_states, *ends = starts + (size_t) C * K * S;
+    unsigned char *bad = (unsigned char *)(ends + (size_t) C * K * S);
+    const long tasks = (long) C * K;
+    const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256);
+    hipStream_t st = (hipStream_t) stream;
+#define SPEC_GO(SS) do { \
+        hipLaunchKernelGGL ((biquad_spec_kernel<SS, PLANAR>), grid, block, 0, st, (const Biquad *) d_sections, C, K, L, W, d_in, in_stride, d_out, out_stride, frames, starts, ends); \
+        hipLaunchKernelGGL (biquad_check_kernel<SS>, grid, block, 0, st, C, K, (const SpecState *) starts, (const SpecState *) ends, bad, d_first_bad); \
+        hipLaunchKernelGGL ((biquad_commit_kernel<SS, PLANAR>), dim3 ((C + 63) / 64), dim3 (64), 0, st, d_sections, C, K, L, d_in, in_stride, d_out, out_stride, frames, \
+                            (const SpecState *) starts, ends, (const unsigned char *) bad, d_first_bad, d_repairs); } while (0)
+    switch (S) { case 1: SPEC_GO (1); break; case 2: SPEC_GO (2); break; case 3: SPEC_GO (3); break; default: SPEC_GO (4); }
+#undef SPEC_GO
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
 extern "C" {
 
 // The time-parallel bit-exact cascade (biquad_spec_kernel): `d_in` -> `d_out` (distinct buffers), frames x C with the given
@@ -1823,43 +1774,13 @@ int arthip_biquad_spec_arm (int *d_first_bad, int C, void *stream)
 int arthip_biquad_spec (Biquad *d_sections, int C, int S, const art_s *d_in, int in_stride, art_s *d_out, int out_stride, int frames,
                         int L, int W, void *d_states, int *d_first_bad, unsigned int *d_repairs, void *stream)
 {
-    if (frames <= 0) return 0;
-    if (S < 1 || S > MAX_CHAIN || L < 1) return -1;
-    const int K = (frames + L - 1) / L;
-    SpecState *starts = (SpecState *) d_states, *ends = starts + (size_t) C * K * S;
-    unsigned char *bad = (unsigned char *)(ends + (size_t) C * K * S);
-    const long tasks = (long) C * K;
-    const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256);
-    hipStream_t st = (hipStream_t) stream;
-#define SPEC_GO(SS) do { \
-        hipLaunchKernelGGL (biquad_spec_kernel<SS>, grid, block, 0, st, (const Biquad *) d_sections, C, K, L, W, d_in, in_stride, d_out, out_stride, frames, starts, ends); \
-        hipLaunchKernelGGL (biquad_check_kernel<SS>, grid, block, 0, st, C, K, (const SpecState *) starts, (const SpecState *) ends, bad, d_first_bad); \
-        hipLaunchKernelGGL (biquad_commit_kernel<SS>, dim3 ((C + 63) / 64), dim3 (64), 0, st, d_sections, C, K, L, d_in, in_stride, d_out, out_stride, frames, \
-                            (const SpecState *) starts, ends, (const unsigned char *) bad, d_first_bad, d_repairs); } while (0)
-    switch (S) { case 1: SPEC_GO (1); break; case 2: SPEC_GO (2); break; case 3: SPEC_GO (3); break; default: SPEC_GO (4); }
-#undef SPEC_GO
-    return hipGetLastError () == hipSuccess ? 0 : -1;
+    return biquad_spec_launch<false> (d_sections, C, S, d_in, in_stride, d_out, out_stride, frames, L, W, d_states, d_first_bad, d_repairs, stream);
 }
 
 int arthip_biquad_spec_planar (Biquad *d_sections, int C, int S, const art_s *d_in, long in_pitch, art_s *d_out, long out_pitch, int frames,
                                int L, int W, void *d_states, int *d_first_bad, unsigned int *d_repairs, void *stream)
 {
-    if (frames <= 0) return 0;
-    if (S < 1 || S > MAX_CHAIN || L < 1) return -1;
-    const int K = (frames + L - 1) / L;
-    SpecState *starts = (SpecState *) d_states, *ends = starts + (size_t) C * K * S;
-    unsigned char *bad = (unsigned char *)(ends + (size_t) C * K * S);
-    const long tasks = (long) C * K;
-    const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256);
-    hipStream_t st = (hipStream_t) stream;
-#define SPEC_GO(SS) do { \
-        hipLaunchKernelGGL ((biquad_spec_kernel<SS, true>), grid, block, 0, st, (const Biquad *) d_sections, C, K, L, W, d_in, in_pitch, d_out, out_pitch, frames, starts, ends); \
-        hipLaunchKernelGGL (biquad_check_kernel<SS>, grid, block, 0, st, C, K, (const SpecState *) starts, (const SpecState *) ends, bad, d_first_bad); \
-        hipLaunchKernelGGL ((biquad_commit_kernel<SS, true>), dim3 ((C + 63) / 64), dim3 (64), 0, st, d_sections, C, K, L, d_in, in_pitch, d_out, out_pitch, frames, \
-                            (const SpecState *) starts, ends, (const unsigned char *) bad, d_first_bad, d_repairs); } while (0)
-    switch (S) { case 1: SPEC_GO (1); break; case 2: SPEC_GO (2); break; case 3: SPEC_GO (3); break; default: SPEC_GO (4); }
-#undef SPEC_GO
-    return hipGetLastError () == hipSuccess ? 0 : -1;
+    return biquad_spec_launch<true> (d_sections, C, S, d_in, in_pitch, d_out, out_pitch, frames, L, W, d_states, d_first_bad, d_repairs, stream);
 }
 
 int arthip_biquad_order2 (Biquad *d_sections, int C, int S, art_s *d_buf, int frames, int stride, void *stream)
@@ -1906,43 +1827,27 @@ static int decimate_launch (const ArtDecArgs *a, const art_s *d_in, long in_pitc
 // the interleaved call; with a pitch on either side it is that kernel's PITCHED instantiation.
 int arthip_decimate_pitched (const ArtDecArgs *a, const art_s *d_in, long in_pitch, int frames, unsigned char *d_out, long out_pitch, void *stream)
 {
-    const bool pitched = in_pitch || out_pitch;
-    if (frames >= 64 && !a->shaping_on && (!a->dither_on || a->gens_next) && (DEC_SEG % 2) == 0) {
+    const bool pitched = in_pitch || out_pitch, dither = a->dither_on != 0;
+    hipStream_t st = (hipStream_t) stream;
+    if (frames >= 64 && !a->shaping_on && (!dither || a->gens_next) && (DEC_SEG % 2) == 0) {
         const long tasks = (long) a->C * ((frames + DEC_SEG - 1) / DEC_SEG);
-        const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256);
-#define DEC_PAR(P) do { if (a->dither_on) hipLaunchKernelGGL ((decimate_parallel_kernel<true, P>), grid, block, 0, (hipStream_t) stream, *a, d_in, frames, d_out, a->gens_next, in_pitch, out_pitch); \
-                        else hipLaunchKernelGGL ((decimate_parallel_kernel<false, P>), grid, block, 0, (hipStream_t) stream, *a, d_in, frames, d_out, a->gens_next, in_pitch, out_pitch); } while (0)
-        if (pitched) DEC_PAR (true); else DEC_PAR (false);
-#undef DEC_PAR
+        ArtDecTask item;                                       // the call as the batch's table would hold it: one item, first task 0
+        item.in = d_in; item.out = d_out; item.in_pitch = in_pitch; item.out_pitch = out_pitch; item.frames = frames; item.task0 = 0;
+        item.feedback = a->feedback; item.gens = a->gens; item.gens_next = a->gens_next; item.clipped = a->clipped;
+        item.scale = a->scale; item.C = a->C; item.bits = a->bits; item.bytes = a->bytes; item.dither_type = a->dither_type;
+        hipLaunchKernelGGL (dec_parallel_kernel (dither, pitched), dim3 ((unsigned int)((tasks + 255) / 256)), dim3 (256), 0, st, item);
         return hipGetLastError () == hipSuccess ? 1 : -1;      // 1: generator state now lives in gens_next
     }
     if (frames >= 64) {
         const int cpw = channels_per_workgroup (a->C);
         const dim3 grid ((a->C + cpw - 1) / cpw), block (ST_THREADS);
-        hipStream_t st = (hipStream_t) stream;
         const int order = a->shaping_on ? a->shaping_order : 0;
-#define DEC_GO_P(O, P) do { if (a->dither_on) hipLaunchKernelGGL ((decimate_lds_kernel<O, true, P>), grid, block, 0, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch); \
-                            else hipLaunchKernelGGL ((decimate_lds_kernel<O, false, P>), grid, block, 0, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch); } while (0)
-#define DEC_GO(O) do { if (pitched) DEC_GO_P (O, true); else DEC_GO_P (O, false); } while (0)
-#define DEC_PIPE_P(O, P) do { auto kd = decimate_pipe_kernel<O, true, P>; auto kn = decimate_pipe_kernel<O, false, P>; \
-                         static bool once = false; \
-                         if (!once) { (void) hipFuncSetAttribute ((const void *) kd, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pipe_lds); \
-                                      (void) hipFuncSetAttribute ((const void *) kn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pipe_lds); once = true; } \
-                         if (a->dither_on) hipLaunchKernelGGL (kd, grid, block, pipe_lds, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch); \
-                         else hipLaunchKernelGGL (kn, grid, block, pipe_lds, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch); } while (0)
-#define DEC_PIPE(O) do { if (pitched) DEC_PIPE_P (O, true); else DEC_PIPE_P (O, false); } while (0)
-        const size_t pipe_lds = (size_t) 5 * DEC_CHUNK * sizeof (art_s);
         // with more workgroups than CUs the chip is busy anyway and the smaller LDS footprint of the unpipelined form
         // (more workgroups per CU) wins: 4,096 channels 49 vs 36 Gsamples/s
-        if (order >= 1 && grid.x <= 256) {
-            switch (order) { case 1: DEC_PIPE (1); break; case 2: DEC_PIPE (2); break; case 3: DEC_PIPE (3); break; default: DEC_PIPE (4); }
-            return hipGetLastError () == hipSuccess ? 0 : -1;
-        }
-        switch (order) { case 0: DEC_GO (0); break; case 1: DEC_GO (1); break; case 2: DEC_GO (2); break; case 3: DEC_GO (3); break; default: DEC_GO (4); }
-#undef DEC_PIPE
-#undef DEC_PIPE_P
-#undef DEC_GO
-#undef DEC_GO_P
+        if (order >= 1 && grid.x <= 256)
+            hipLaunchKernelGGL (dec_pipe_kernel (order, dither, pitched), grid, block, DEC_PIPE_LDS, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch);
+        else
+            hipLaunchKernelGGL (dec_lds_kernel (order, dither, pitched), grid, block, 0, st, *a, d_in, frames, d_out, cpw, in_pitch, out_pitch);
         return hipGetLastError () == hipSuccess ? 0 : -1;
     }
     return decimate_launch (a, d_in, in_pitch, frames, d_out, out_pitch, stream);
@@ -1966,28 +1871,16 @@ int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, v
     const void *items = (const char *) d_table + cls->slice.offset;
     if (cls->slice.count <= 0) return 0;
     if (!cls->serial) {
-        const dim3 grid ((unsigned int)((cls->tasks + 255) / 256)), block (256);
-#define DEC_BATCH_PAR(D) do { if (cls->pitched) hipLaunchKernelGGL ((decimate_batch_parallel_kernel<D, true>), grid, block, 0, st, (const ArtDecTask *) items, cls->slice.count, cls->tasks); \
-                              else hipLaunchKernelGGL ((decimate_batch_parallel_kernel<D, false>), grid, block, 0, st, (const ArtDecTask *) items, cls->slice.count, cls->tasks); } while (0)
-        if (cls->dither) DEC_BATCH_PAR (true); else DEC_BATCH_PAR (false);
-#undef DEC_BATCH_PAR
+        hipLaunchKernelGGL (dec_batch_parallel_kernel (cls->dither != 0, cls->pitched != 0), dim3 ((unsigned int)((cls->tasks + 255) / 256)), dim3 (256), 0, st,
+                            (const ArtDecTask *) items, cls->slice.count, cls->tasks);
         return hipGetLastError () == hipSuccess ? 0 : -1;
     }
     const int L = cls->slice.lanes;
     if (L < 1 || L > 64 || cls->slice.count % L) return -1;
     const int chunk_frames = batch_chunk_frames (L, DEC_BATCH_RUN);
-    const size_t lds = (size_t) 5 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 5 DEC_CHUNK samples (80 KiB)
-    const dim3 grid ((unsigned int)(cls->slice.count / L)), block (ST_THREADS);
-#define DEC_BATCH_GO(O, D, P) do { auto k = decimate_batch_pipe_kernel<O, D, P>; static bool once = false; \
-        if (!once) { (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(5 * DEC_CHUNK * sizeof (art_s))); once = true; } \
-        hipLaunchKernelGGL (k, grid, block, lds, st, (const ArtDecLane *) items, L, chunk_frames); } while (0)
-#define DEC_BATCH_D(O, D) do { if (cls->pitched) DEC_BATCH_GO (O, D, true); else DEC_BATCH_GO (O, D, false); } while (0)
-#define DEC_BATCH_O(O) do { if (cls->dither) DEC_BATCH_D (O, true); else DEC_BATCH_D (O, false); } while (0)
-    switch (cls->order) { case 0: DEC_BATCH_O (0); break; case 1: DEC_BATCH_O (1); break; case 2: DEC_BATCH_O (2); break;
-                          case 3: DEC_BATCH_O (3); break; default: DEC_BATCH_O (4); }
-#undef DEC_BATCH_O
-#undef DEC_BATCH_D
-#undef DEC_BATCH_GO
+    const size_t lds = (size_t) 5 * L * (chunk_frames + 4) * sizeof (art_s);          // <= DEC_PIPE_LDS (80 KiB)
+    hipLaunchKernelGGL (dec_batch_pipe_kernel (cls->order, cls->dither != 0, cls->pitched != 0), dim3 ((unsigned int)(cls->slice.count / L)), dim3 (ST_THREADS), lds, st,
+                        (const ArtDecLane *) items, L, chunk_frames);
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 

@@ -21,6 +21,8 @@ RESAMPLER_FLUSHED, RESAMPLER_SNAP_OFFSET, RESAMPLE_STRICT_ORDER = 0x200, 0x400, 
 DITHER_HIGHPASS, DITHER_FLAT, DITHER_LOWPASS = 0x1, 0x2, 0x4
 SHAPING_1ST_ORDER, SHAPING_2ND_ORDER, SHAPING_3RD_ORDER, SHAPING_ATH_CURVE = 0x100, 0x200, 0x400, 0x800
 DECIMATE_MULTITHREADED = 0x1000
+# stretch.h flags
+STRETCH_FAST_FLAG, STRETCH_DUAL_FLAG = 0x1, 0x2
 
 def _bind(width):
     """everything below exists once per sample width: 32 (libartamd.so, float) and 64 (libartamd64.so, double —
@@ -181,6 +183,8 @@ def _bind(width):
         "resampleProcessAndFlushPlanarDevice": (ResampleResult, [RP, ptr, C.c_long, C.c_int, ptr, C.c_long, C.c_int, C.c_double]),
         "resampleProcessBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "stretchProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
+        "artamdStretchClipCapacity": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double]),
     }
 
     _state = {"lib": None}
@@ -766,6 +770,129 @@ def _bind(width):
                     b.reset()
                 biquad_batch_planar_device(pool, [xp + i * x.stride(0) * size for i in idx], [pitch] * len(idx), [lengths[i] for i in idx])
             return whole
+
+    class Stretcher:
+        """Owner of a Stretch * (stretch.h): periods in frames, one or two channels, flags STRETCH_FAST_FLAG | STRETCH_DUAL_FLAG"""
+
+        def __init__(self, shortest, longest, channels, flags=0):
+            self.L = lib()
+            self.p = self.L.stretchInit(shortest, longest, channels, flags)
+            if not self.p:
+                raise RuntimeError("stretchInit failed (bad periods or channels, or no MI355X visible — there is no CPU path)")
+            self.channels, self.longest, self.flags = channels, longest, flags
+
+        def close(self):
+            if getattr(self, "p", None):
+                self.L.stretchFree(self.p)
+                self.p = None
+
+        __del__ = close
+
+        def set_stream(self, s):
+            self.L.stretchHipSetStream(self.p, s)
+
+    def stretch_clips_batch_planar_device(ctxs, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios, from_start=True):
+        """stretchProcessAndFlushBatchPlanarDevice over a list of Stretcher objects: every clip's process call and all its flushes in one
+        launch, one workgroup per clip (channel c of item i's input at d_ins[i] + c * in_pitches[i] samples, of its output at
+        d_outs[i] + c * out_pitches[i]; 0: that side of that item is interleaved; None for a pitch list: every item's is; a d_ins entry
+        may be None with n_ins 0).  out_caps in frames, at least artamdStretchClipCapacity each.  from_start: every context first put
+        where stretchInit left it.  Returns the frames made per clip (raises if the call returned -1)."""
+        n = len(ctxs)
+        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
+        produced = (C.c_int * max(n, 1))()
+        rc = lib().stretchProcessAndFlushBatchPlanarDevice(
+            (C.c_void_p * n)(*[c.p for c in ctxs]), n, (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_ins]), pitches(in_pitches),
+            (C.c_int * n)(*[int(v) for v in n_ins]), (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches),
+            (C.c_int * n)(*[int(v) for v in out_caps]), (C.c_double * n)(*[float(v) for v in ratios]), 1 if from_start else 0, produced)
+        if rc < 0:
+            raise RuntimeError("stretchProcessAndFlushBatchPlanarDevice failed")
+        return list(produced[:n])
+
+    class ClipStretcher:
+        """Whole clips, channels-first, stretched in time without a change of pitch: x [B, C, T] (or [C, T]) on the GPU and a ratio
+        (output length over input length, as stretchProcess takes it; a float, or one value per clip) in, (y [B, C, Tout_max],
+        out_lengths) out — one stretchProcessAndFlushBatchPlanarDevice call per pool on the tensor's own rows, no copy of the samples on
+        the way.  Clip i is what a fresh context with periods rate // 350 and rate // 50 (ART's choice) makes of x[i, :, :lengths[i]],
+        process call and flushes together; y[i, :, out_lengths[i]:] is zero.  flags=None keeps two pools of up to max_batch contexts, a
+        single stage for ratios in 0.5 .. 2 and a STRETCH_DUAL_FLAG pair outside, and sends each clip to the one its ratio needs; given
+        flags make one pool.  Ratios outside 0.25 .. 4 (0.5 .. 2 for given flags without STRETCH_DUAL_FLAG) and more than two channels
+        raise.  Runs on the caller's current torch stream; a larger batch is made max_batch clips at a time.  Its output feeds
+        ClipResampler as it comes: a pitch shift by `pitch` at a tempo change `tempo` is ClipStretcher at the ratio pitch / tempo
+        followed by ClipResampler from rate * pitch to rate."""
+
+        def __init__(self, channels, rate, flags=None, max_batch=1024):
+            if channels not in (1, 2):
+                raise ValueError("mono or stereo only")
+            self.channels, self.rate, self.flags, self.max_batch = channels, int(rate), flags, max(1, int(max_batch))
+            self.shortest, self.longest = self.rate // 350, self.rate // 50
+            self.pools = {}                                      # flags -> contexts
+
+        def close(self):
+            for pool in self.pools.values():
+                for s in pool:
+                    s.close()
+            self.pools = {}
+
+        def _flags_for(self, ratio):
+            if not 0.25 <= ratio <= 4.0:                         # (also refuses a ratio that is not a number)
+                raise ValueError("ratio: 0.25 .. 4")
+            if self.flags is None:
+                return 0 if 0.5 <= ratio <= 2.0 else STRETCH_DUAL_FLAG
+            if not self.flags & STRETCH_DUAL_FLAG and not 0.5 <= ratio <= 2.0:
+                raise ValueError("ratio: 0.5 .. 2 without STRETCH_DUAL_FLAG")
+            return self.flags
+
+        def __call__(self, x, ratio, lengths=None):
+            import torch
+            if x.dim() == 2:
+                x = x.unsqueeze(0)
+            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
+                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
+            if x.shape[2] and x.stride(2) != 1:
+                x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
+            B, Cn, T = x.shape
+            if Cn > 1 and x.stride(1) < T:
+                x = x.contiguous()                                # (a broadcast channel dimension: a pitch of 0 would mean interleaved)
+            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
+                raise ValueError("lengths: one entry per clip, 0 .. T")
+            if hasattr(ratio, "tolist"):
+                ratio = ratio.tolist()
+            ratios = [float(v) for v in ratio] if isinstance(ratio, (list, tuple)) else [float(ratio)] * B
+            if len(ratios) != B:
+                raise ValueError("ratio: a float, or one value per clip")
+            groups = {}                                          # flags -> the clips of that pool
+            for i, r in enumerate(ratios):
+                groups.setdefault(self._flags_for(r), []).append(i)
+            L = lib()
+            rooms = [0] * B
+            for flags, idx in groups.items():
+                for i in idx:
+                    rooms[i] = L.artamdStretchClipCapacity(self.longest, flags, lengths[i], ratios[i])
+                    if rooms[i] < 0:
+                        raise ValueError("clip too long")
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            y = torch.zeros(B, Cn, max(rooms, default=0), dtype=x.dtype, device=x.device)
+            size = x.element_size()
+            xp, yp = x.data_ptr(), y.data_ptr()
+            in_pitch, out_pitch = (x.stride(1), y.stride(1)) if Cn > 1 else (0, 0)      # (one channel: the same call in either layout)
+            made = [0] * B
+            for flags, idx in groups.items():
+                pool = self.pools.setdefault(flags, [])
+                while len(pool) < min(len(idx), self.max_batch):
+                    pool.append(Stretcher(self.shortest, self.longest, Cn, flags))
+                for s in pool[:min(len(idx), self.max_batch)]:
+                    s.set_stream(stream)
+                for b0 in range(0, len(idx), self.max_batch):
+                    part = idx[b0:b0 + self.max_batch]
+                    got = stretch_clips_batch_planar_device(
+                        pool[:len(part)], [xp + i * x.stride(0) * size for i in part], [in_pitch] * len(part), [lengths[i] for i in part],
+                        [yp + i * y.stride(0) * size for i in part], [out_pitch] * len(part), [rooms[i] for i in part],
+                        [ratios[i] for i in part], from_start=True)
+                    for i, g in zip(part, got):
+                        made[i] = g
+            out_lengths = torch.tensor(made, dtype=torch.int64)
+            return y[:, :, :max(made, default=0)], out_lengths
 
     def ingest_batch_device(d_ins, gains, bits, nbytes, strides, d_outs, counts, stream=None):
         """floatIntegersBatchLEDevice: item i as floatIntegersLEDevice (d_ins[i], gains[i], bits[i], nbytes[i], strides[i], d_outs[i],

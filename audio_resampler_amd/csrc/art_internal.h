@@ -381,6 +381,11 @@ typedef struct { int mark, fill, cur, pad; double drift; } ArtStretchState;     
 typedef struct { ArtStretchArgs args; const art_s *in; art_s *out; double ratio; int frames, flush; } ArtStretchItem;
 typedef struct { int made, pad; ArtStretchState state [2]; } ArtStretchDone;
 int arthip_stretch_batch (const ArtStretchItem *d_items, ArtStretchDone *d_done, int n, void *stream);
+/* whole clips, one workgroup each in ONE launch: from the state stretchInit leaves where from_start, the process call (frames > 0),
+ * then the flushes until one gives nothing, written behind one another.  Channel c of the input is at in + c * in_pitch samples, of
+ * the output at out + c * out_pitch (0: that side interleaved).  No bounds checks: the caller has made sure `out` holds it all */
+typedef struct { ArtStretchArgs args; const art_s *in; art_s *out; long in_pitch, out_pitch; double ratio; int frames, from_start; } ArtStretchClip;
+int arthip_stretch_clips (const ArtStretchClip *d_items, ArtStretchDone *d_done, int n, void *stream);
 
 /* a failure of an entry point that cannot return one (the reference's ABI has no error codes): printed, counted (artamdErrorCount /
  * artamdLastError), fatal under ARTAMD_ABORT_ON_ERROR=1 — pcm_host.c */

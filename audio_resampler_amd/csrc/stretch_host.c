@@ -186,6 +186,14 @@ int stretchFlushDevice (Stretch *cxt, artsample_t *d_output)
  * goes to the stream of cxts [0], whose scratch also carries the item table. */
 static unsigned long *stamp_of (const void *cxt) { return &((const Stretch *) cxt)->hip->batch_stamp; }
 
+/* what a batched launch reports for one context: the frame count, and the host mirrors of the state it left */
+static void mirror_state (Stretch *c, const ArtStretchDone *done, int *produced)
+{
+    *produced = done->made;
+    c->tail = done->state [0].mark; c->head = done->state [0].fill; c->outsamples_error = done->state [0].drift;
+    if (c->next) { c->next->tail = done->state [1].mark; c->next->head = done->state [1].fill; c->next->outsamples_error = done->state [1].drift; }
+}
+
 static int batch_call (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const int *num_samples,
                        artsample_t *const *d_outputs, const double *ratios, int flush, int *produced)
 {
@@ -217,12 +225,7 @@ static int batch_call (Stretch *const *cxts, int n, const artsample_t *const *d_
         goto out;
     }
 
-    for (int i = 0; i < n; ++i) {
-        Stretch *c = cxts [i];
-        produced [i] = done [i].made;
-        c->tail = done [i].state [0].mark; c->head = done [i].state [0].fill; c->outsamples_error = done [i].state [0].drift;
-        if (c->next) { c->next->tail = done [i].state [1].mark; c->next->head = done [i].state [1].fill; c->next->outsamples_error = done [i].state [1].drift; }
-    }
+    for (int i = 0; i < n; ++i) mirror_state (cxts [i], &done [i], &produced [i]);
     rc = 0;
 out:
     free (items); free (done);
@@ -238,6 +241,89 @@ int stretchProcessBatchDevice (Stretch *const *cxts, int n, const artsample_t *c
 int stretchFlushBatchDevice (Stretch *const *cxts, int n, artsample_t *const *d_outputs, int *produced)
 {
     return batch_call (cxts, n, NULL, NULL, d_outputs, NULL, 1, produced);
+}
+
+/* Frames a whole clip can emit, process call and every flush together, from ANY state of the context: a stage holds at most its
+ * ring of values beside what comes in, each of them is consumed by one step or flushed once, a flush emits at 1, and a step emits
+ * at most ceil (2 r) / 2 values per value it consumes (r: the stage's clipped ratio; 0.5: p for 2p, 1: 2p for 2p, 1.5: 3p for 2p,
+ * 2: 2p for p, and the drift only chooses between floor and ceil of 2 r).  A ratio that is not a number takes the 2:1 step. */
+static long long stage_bound (long long frames, int longest, int fast, double ratio)
+{
+    const double r = ratio < 0.5 ? 0.5 : ratio;
+    const double gain = !(r <= 2.0) ? 2.0 : fmax (1.0, ceil (r * 2.0) / 2.0);
+    return (long long) ceil ((double)(frames + (long long) longest * (fast ? 4 : 3)) * gain);
+}
+
+int artamdStretchClipCapacity (int longest_period, int flags, int num_samples, double ratio)
+{
+    const int fast = (flags & STRETCH_FAST_FLAG) != 0, dual = (flags & STRETCH_DUAL_FLAG) != 0;
+    double here = ratio, rest = 1.0;
+
+    if (fast) longest_period = (longest_period + 1) & ~1;
+    if (longest_period < 1 || longest_period > MAX_PERIOD) return -1;
+    if (num_samples < 0) num_samples = 0;
+    if (dual) {                                         /* as stretchGetOutputCapacity splits the ratio */
+        if (here < 0.5) { rest = here / 0.5; here = 0.5; }
+        else if (here > 2.0) { rest = here / 2.0; here = 2.0; }
+    }
+    long long frames = stage_bound (num_samples, longest_period, fast, here);
+    if (dual) frames = stage_bound (frames, longest_period, fast, rest);
+    return frames > 0x7fffffff ? -1 : (int) frames;     /* (-1: more than an int holds) */
+}
+
+/* Whole clips in ONE launch and one synchronisation: art_hip.h.  Everything is checked before anything is enqueued. */
+int stretchProcessAndFlushBatchPlanarDevice (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const long *inputPitches,
+                                             const int *num_samples, artsample_t *const *d_outputs, const long *outputPitches,
+                                             const int *outputCaps, const double *ratios, int fromStart, int *produced)
+{
+    if (n <= 0) return 0;
+    if (!cxts || !num_samples || !d_outputs || !outputCaps || !ratios || !produced) return -1;
+    for (int i = 0; i < n; ++i) {
+        const Stretch *c = cxts [i];
+        if (!c || !c->hip) return -1;
+        const int need = artamdStretchClipCapacity (c->longest / c->num_chans, (c->fast_mode ? STRETCH_FAST_FLAG : 0) | (c->next ? STRETCH_DUAL_FLAG : 0),
+                                                    num_samples [i], ratios [i]);
+        if (!d_outputs [i] || (num_samples [i] > 0 && (!d_samples || !d_samples [i])) || need < 0 || outputCaps [i] < need) return -1;
+        /* planes must not run into one another: a pitch holds the clip, the output's everything the clip can emit */
+        const long in_pitch = inputPitches ? inputPitches [i] : 0, out_pitch = outputPitches ? outputPitches [i] : 0;
+        if (c->num_chans > 1 && ((in_pitch && in_pitch < num_samples [i]) || (out_pitch && out_pitch < need))) return -1;
+    }
+    if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "stretch", "context")) return -1;
+
+    struct artamd_stretch *lead = cxts [0]->hip;
+    const size_t items_bytes = ((size_t) n * sizeof (ArtStretchClip) + 63) & ~(size_t) 63, done_bytes = (size_t) n * sizeof (ArtStretchDone);
+    ArtStretchClip *items = malloc (items_bytes);
+    ArtStretchDone *done = malloc (done_bytes);
+    int rc = -1;
+
+    lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, items_bytes + done_bytes);
+    if (!items || !done || !lead->d_batch) goto out;
+
+    for (int i = 0; i < n; ++i) {
+        items [i].args = cxts [i]->hip->args;
+        items [i].in = num_samples [i] > 0 ? d_samples [i] : NULL;
+        items [i].out = d_outputs [i];
+        items [i].in_pitch = inputPitches ? inputPitches [i] : 0;
+        items [i].out_pitch = outputPitches ? outputPitches [i] : 0;
+        items [i].ratio = ratios [i];
+        items [i].frames = num_samples [i] > 0 ? num_samples [i] : 0;
+        items [i].from_start = fromStart != 0;
+    }
+
+    ArtStretchDone *d_done = (ArtStretchDone *)((char *) lead->d_batch + items_bytes);
+    if (arthip_h2d (lead->d_batch, items, (size_t) n * sizeof (ArtStretchClip), lead->stream) ||
+        arthip_stretch_clips ((const ArtStretchClip *) lead->d_batch, d_done, n, lead->stream) ||
+        arthip_d2h (done, d_done, done_bytes, lead->stream) || arthip_sync (lead->stream)) {
+        fprintf (stderr, "artamd: stretch clip launch failed: %s\n", arthip_last_error ());
+        artamd_note_failure ("stretch: the whole-clip launch failed");
+        goto out;
+    }
+
+    for (int i = 0; i < n; ++i) mirror_state (cxts [i], &done [i], &produced [i]);
+    rc = 0;
+out:
+    free (items); free (done);
+    return rc;
 }
 
 /* frames a call can emit at most: what is buffered plus what comes in, at the largest stage ratios, plus slack */

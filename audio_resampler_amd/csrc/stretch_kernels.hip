@@ -168,7 +168,24 @@ __device__ int pick_period (const StretchStage &S, Scratch &L, const art_s *x)
     return L.pick;
 }
 
-__device__ __forceinline__ void crossfade (art_s *out, const art_s *from, const art_s *to, int n)
+// Where a stage's input comes from and where the last stage's output goes is a template parameter of feed / drain: a plain
+// pointer (consecutive interleaved values: every buffer of the call and batch kernels, the rings, `between`), or Rows, a whole
+// clip's buffer in either layout.  Both are indexed by VALUE (frame * channels + channel) and advanced by whole frames' values.
+struct RowsLayout {                                // value v of a clip: channel v % C of frame v / C (C is 1 or 2: mask and shift)
+    long across, along; int shift;                 // samples from a channel to the next / from a frame to the next; C - 1
+    // pitch in samples between a clip's channels, 0: interleaved.  (One channel: `across` is never used, frames are consecutive.)
+    __device__ void set (long pitch, int C) { across = pitch ? pitch : 1; along = pitch ? 1 : (long) C; shift = C - 1; }
+};
+
+template <class T>
+struct Rows {                                      // (the layout stays in LDS: only the pointer is carried through the period search)
+    T *p; const RowsLayout *lay;
+    __device__ __forceinline__ T &operator[] (int v) const { return p [(long)(v & lay->shift) * lay->across + (long)(v >> lay->shift) * lay->along]; }
+    __device__ __forceinline__ Rows operator+ (int values) const { return Rows { p + (long)(values >> lay->shift) * lay->along, lay }; }
+};
+
+template <class D>
+__device__ __forceinline__ void crossfade (D out, const art_s *from, const art_s *to, int n)
 {
     for (int i = threadIdx.x; i < n; i += ST_WG) {
         const art_s a = from [i] * (art_s)(n - i);
@@ -178,9 +195,25 @@ __device__ __forceinline__ void crossfade (art_s *out, const art_s *from, const 
     }
 }
 
-__device__ __forceinline__ void copy_values (art_s *dst, const art_s *src, int n)
+template <class D>
+__device__ __forceinline__ void copy_values (D dst, const art_s *src, int n)
 {
     for (int i = threadIdx.x; i < n; i += ST_WG) dst [i] = src [i];
+}
+
+// n new input values into the (interleaved) ring
+__device__ __forceinline__ void take_values (art_s *ring, const art_s *in, int n, int) { copy_values (ring, in, n); }
+
+// ... from a clip's rows, interleaving on the fly: one pass per channel with the lanes along time, so that a wave's loads are
+// consecutive samples of one plane.  n is whole frames (see feed).
+__device__ __forceinline__ void take_values (art_s *ring, const Rows<const art_s> &in, int n, int C)
+{
+    const int frames = n >> in.lay->shift;
+    const long along = in.lay->along;
+    for (int c = 0; c < C; ++c) {
+        const art_s *from = in.p + (long) c * in.lay->across;
+        for (int f = threadIdx.x; f < frames; f += ST_WG) ring [f * C + c] = from [(long) f * along];
+    }
 }
 
 __device__ __forceinline__ void split_ratio (bool paired, double &ratio, double &rest)
@@ -193,13 +226,19 @@ __device__ __forceinline__ void split_ratio (bool paired, double &ratio, double 
 
 // One stage consuming `values` input values.  PAIRED: this is stage 1 of a cascade and hands every step's output to
 // stage 2 (the same function, unpaired).  Returns FRAMES written to `out` (by the last stage).
-template <bool PAIRED>
-__device__ int feed (const StretchStage *stages, StretchState *states, Scratch &L, const art_s *in, int values,
-                     art_s *out, double ratio)
+template <bool PAIRED, class OUT>
+__device__ __forceinline__ auto step_output (art_s *between, OUT out)
+{
+    if constexpr (PAIRED) return between; else return out;
+}
+
+template <bool PAIRED, class IN, class OUT>
+__device__ int feed (const StretchStage *stages, StretchState *states, Scratch &L, IN in, int values,
+                     OUT out, double ratio)
 {
     const StretchStage &S = stages [0];
     StretchState st = states [0];                  // every thread reads the same words; thread 0 writes them back
-    art_s *dst = PAIRED ? S.between : out;
+    auto dst = step_output<PAIRED> (S.between, out);
     int made = 0, made_next = 0;
     double rest;
 
@@ -214,8 +253,10 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
         // loop (stretch.c:195-212: nothing copied, nothing processed, num_samples unchanged) never ends.  A spinning workgroup would take the device with it: stop, keep
         // what the call has produced, drop the rest of its input.
         if (take == 0 && !(st.mark >= S.hi && st.fill - st.mark >= S.hi * (S.quick ? 3 : 2))) break;
-        copy_values (S.ring [st.cur] + st.fill, in, take);
-        left -= take; in += take; st.fill += take;
+        // room, hi and every period are whole frames' values, so fill, mark and take are whole frames whenever `values` is:
+        // take_values and Rows' "+" rely on it
+        take_values (S.ring [st.cur] + st.fill, in, take, S.channels);
+        left -= take; in = in + take; st.fill += take;
         __syncthreads ();
 
         while (st.mark >= S.hi && st.fill - st.mark >= S.hi * (S.quick ? 3 : 2)) {
@@ -256,8 +297,8 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
             }
             __syncthreads ();                      // step output complete (stage 2 / compaction read it)
 
-            if (PAIRED) {
-                made_next += feed<false> (stages + 1, states + 1, L, dst, made, out + made_next * S.channels, rest);
+            if constexpr (PAIRED) {
+                made_next += feed<false> (stages + 1, states + 1, L, (const art_s *) dst, made, out + made_next * S.channels, rest);
                 made = 0;
             }
 
@@ -274,8 +315,8 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
     if (ratio == 1.0 && st.drift == 0.0 && st.fill != st.mark) {        // nothing to stretch: pass the pending values on
         art_s *ring = S.ring [st.cur];
         const int pending = st.fill - st.mark;
-        if (PAIRED)
-            made_next += feed<false> (stages + 1, states + 1, L, ring + st.mark, pending, out + made_next * S.channels, rest);
+        if constexpr (PAIRED)
+            made_next += feed<false> (stages + 1, states + 1, L, (const art_s *)(ring + st.mark), pending, out + made_next * S.channels, rest);
         else {
             copy_values (dst + made, ring + st.mark, pending);
             made += pending;
@@ -293,16 +334,16 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
 }
 
 // everything still buffered, at normal speed (stretch.c:335-356)
-template <bool PAIRED>
-__device__ int drain (const StretchStage *stages, StretchState *states, Scratch &L, art_s *out)
+template <bool PAIRED, class OUT>
+__device__ int drain (const StretchStage *stages, StretchState *states, Scratch &L, OUT out)
 {
     const StretchStage &S = stages [0];
     StretchState st = states [0];
     __syncthreads ();
     const int pending = st.fill - st.mark;
     int frames = 0;
-    if (PAIRED) {
-        if (pending) frames = feed<false> (stages + 1, states + 1, L, S.ring [st.cur] + st.mark, pending, out, 1.0);
+    if constexpr (PAIRED) {
+        if (pending) frames = feed<false> (stages + 1, states + 1, L, (const art_s *)(S.ring [st.cur] + st.mark), pending, out, 1.0);
         if (!frames) frames = drain<false> (stages + 1, states + 1, L, out);
     }
     else {
@@ -334,6 +375,28 @@ void stretch_call_kernel (StretchLaunch a, const art_s *in, int frames, art_s *o
     if (threadIdx.x == 0) *result = made;
 }
 
+// (thread 0) a batch item's context into LDS
+__device__ __forceinline__ void unpack (const ArtStretchArgs &args, StretchStage *stage, Scratch &L)
+{
+    for (int s = 0; s < 2; ++s) {
+        stage [s].ring [0] = (art_s *) args.ring [s][0]; stage [s].ring [1] = (art_s *) args.ring [s][1];
+        stage [s].between = (art_s *) args.between;
+        stage [s].channels = args.channels; stage [s].room = args.room; stage [s].lo = args.lo; stage [s].hi = args.hi;
+        stage [s].quick = args.quick;
+    }
+    L.total = (art_s *) args.total; L.score = (art_s *) args.score;
+}
+
+// (thread 0) a batch item's frame count and the state it leaves
+__device__ __forceinline__ void report (ArtStretchDone &d, int made, const StretchState *state)
+{
+    d.made = made; d.pad = 0;
+    for (int s = 0; s < 2; ++s) {
+        d.state [s].mark = state [s].mark; d.state [s].fill = state [s].fill; d.state [s].cur = state [s].cur;
+        d.state [s].pad = 0; d.state [s].drift = state [s].drift;
+    }
+}
+
 // one workgroup per stream: the single-stream kernel's body on item blockIdx.x; the stream's state after the call is
 // copied beside the frame count so that the host reads everything back in one transfer
 __global__ __launch_bounds__ (ST_WG)
@@ -342,15 +405,7 @@ void stretch_batch_kernel (const ArtStretchItem *items, ArtStretchDone *done)
     __shared__ Scratch L;
     __shared__ StretchStage stage [2];
     const ArtStretchItem &it = items [blockIdx.x];
-    if (threadIdx.x == 0) {
-        for (int s = 0; s < 2; ++s) {
-            stage [s].ring [0] = (art_s *) it.args.ring [s][0]; stage [s].ring [1] = (art_s *) it.args.ring [s][1];
-            stage [s].between = (art_s *) it.args.between;
-            stage [s].channels = it.args.channels; stage [s].room = it.args.room; stage [s].lo = it.args.lo; stage [s].hi = it.args.hi;
-            stage [s].quick = it.args.quick;
-        }
-        L.total = (art_s *) it.args.total; L.score = (art_s *) it.args.score;
-    }
+    if (threadIdx.x == 0) unpack (it.args, stage, L);
     StretchState *state = (StretchState *) it.args.state;
     __syncthreads ();
     int made;
@@ -361,17 +416,52 @@ void stretch_batch_kernel (const ArtStretchItem *items, ArtStretchDone *done)
         made = it.args.paired ? feed<true> (stage, state, L, it.in, values, it.out, it.ratio) : feed<false> (stage, state, L, it.in, values, it.out, it.ratio);
     }
     __syncthreads ();
-    if (threadIdx.x == 0) {
-        ArtStretchDone &d = done [blockIdx.x];
-        d.made = made; d.pad = 0;
-        for (int s = 0; s < 2; ++s) {
-            d.state [s].mark = state [s].mark; d.state [s].fill = state [s].fill; d.state [s].cur = state [s].cur;
-            d.state [s].pad = 0; d.state [s].drift = state [s].drift;
+    if (threadIdx.x == 0) report (done [blockIdx.x], made, state);
+}
+
+// Whole clips, one workgroup each: optionally from the state stretchInit leaves, the process call, then the flushes, behind
+// one another in the clip's own rows (either layout on either side).
+__global__ __launch_bounds__ (ST_WG)
+void stretch_clip_kernel (const ArtStretchClip *items, ArtStretchDone *done)
+{
+    __shared__ Scratch L;
+    __shared__ StretchStage stage [2];
+    __shared__ RowsLayout layout [2];
+    const ArtStretchClip &it = items [blockIdx.x];
+    if (threadIdx.x == 0) { unpack (it.args, stage, L); layout [0].set (it.in_pitch, it.args.channels); layout [1].set (it.out_pitch, it.args.channels); }
+    StretchState *state = (StretchState *) it.args.state;
+    const int C = it.args.channels, paired = it.args.paired;
+    if (it.from_start)                             // what stretchInit left: one longest period of silence in front of the mark, no error
+        for (int s = 0; s < (paired ? 2 : 1); ++s) {
+            art_s *ring = (art_s *) it.args.ring [s][0];
+            for (int i = threadIdx.x; i < it.args.hi; i += ST_WG) ring [i] = 0;
+            if (threadIdx.x == 0) { StretchState st; st.mark = st.fill = it.args.hi; st.cur = 0; st.pad = 0; st.drift = 0.0; state [s] = st; }
         }
+    __syncthreads ();
+    const Rows<const art_s> in { it.in, &layout [0] };
+    const Rows<art_s> out { it.out, &layout [1] };
+    int made = 0;
+    if (it.frames > 0)
+        made = paired ? feed<true> (stage, state, L, in, it.frames * C, out, it.ratio) : feed<false> (stage, state, L, in, it.frames * C, out, it.ratio);
+    // stretchFlush "until it returns 0": a cascaded pair needs three rounds that give something, so four always end it, in
+    // whatever state the context arrived.  Every thread sees the same counts: the loop is workgroup-uniform.
+    for (int round = 0; round < 4; ++round) {
+        const int more = paired ? drain<true> (stage, state, L, out + made * C) : drain<false> (stage, state, L, out + made * C);
+        if (!more) break;
+        made += more;
     }
+    __syncthreads ();
+    if (threadIdx.x == 0) report (done [blockIdx.x], made, state);
 }
 
 } // namespace
+
+extern "C" int arthip_stretch_clips (const ArtStretchClip *d_items, ArtStretchDone *d_done, int n, void *stream)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL (stretch_clip_kernel, dim3 (n), dim3 (ST_WG), 0, (hipStream_t) stream, d_items, d_done);
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
 
 extern "C" int arthip_stretch_batch (const ArtStretchItem *d_items, ArtStretchDone *d_done, int n, void *stream)
 {

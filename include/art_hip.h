@@ -406,6 +406,32 @@ int stretchFlushDevice (Stretch *cxt, artsample_t *d_output);
 int stretchProcessBatchDevice (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const int *num_samples,
                                artsample_t *const *d_outputs, const double *ratios, int *produced);
 int stretchFlushBatchDevice (Stretch *const *cxts, int n, artsample_t *const *d_outputs, int *produced);
+/* Whole clips, channels-first or interleaved, in ONE launch and ONE synchronisation for any number of clips: for item i exactly
+ * stretchProcessDevice (cxts[i], ..., num_samples[i], ..., ratios[i]) (skipped when num_samples[i] <= 0) followed by
+ * stretchFlushDevice calls until one returns 0 (four at the most), made on interleaved copies with the outputs behind one
+ * another: the same samples, produced[i] = their total in frames, the same context state afterwards.  So it also finishes a stream that
+ * earlier single or batched calls began.  fromStart != 0: the same on a context as stretchInit left it, the accumulated length error
+ * (outsamples_error) at zero too — stretchReset does NOT zero that, as the reference's does not; so a pool of contexts serves clip
+ * after clip and gives what fresh contexts give, with no reset call in between.  Afterwards the context is flushed: terminal, as in the
+ * reference, until stretchReset or another fromStart call.
+ * Channel c of item i's input is at d_samples[i] + c * inputPitches[i] samples, of its output at d_outputs[i] + c * outputPitches[i];
+ * a pitch of 0: that side of that item is interleaved; a NULL pitch array: every item's is.  One channel is the same call in either
+ * layout.  A pitch need not be a multiple of anything, and nothing between a plane's last written frame and the next plane is touched;
+ * with two channels a non-zero input pitch must be at least num_samples[i] and a non-zero output pitch at least the capacity below;
+ * with one channel a pitch is ignored.
+ * The launch runs on the stream of cxts[0]; the call waits for it (the counts come from the device).
+ * Returns 0 (also for n <= 0).  Returns -1 with nothing enqueued and no state changed for a NULL context, a context listed twice, an
+ * item with a NULL output, or a NULL input and num_samples[i] > 0, a pitch too short (or negative), or outputCaps[i] (frames) below artamdStretchClipCapacity for that
+ * context's longest period, flags, num_samples[i] and ratios[i]: the device code does not check bounds.  Returns -1 if the launch
+ * failed (counted in artamdErrorCount; nothing is then known about the contexts' state). */
+int stretchProcessAndFlushBatchPlanarDevice (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const long *inputPitches,
+                                             const int *num_samples, artsample_t *const *d_outputs, const long *outputPitches,
+                                             const int *outputCaps, const double *ratios, int fromStart, int *produced);
+/* frames a whole clip (the process call plus every flush) can emit at most, for a context made with this longest period (frames, as
+ * given to stretchInit) and these flags, from any state it can be in: per stage ceil ((in + ring) * max (1, ceil (2 r) / 2)), r the
+ * stage's clipped ratio, ring = longest period * 3 (4 with STRETCH_FAST_FLAG), the two stages of a STRETCH_DUAL_FLAG pair chained.
+ * Host arithmetic only: no context, no device.  -1: a longest period out of range, or more frames than an int holds. */
+int artamdStretchClipCapacity (int longest_period, int flags, int num_samples, double ratio);
 
 #ifdef __cplusplus
 }

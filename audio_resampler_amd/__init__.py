@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     SHAPING_3RD_ORDER, SHAPING_ATH_CURVE, DECIMATE_MULTITHREADED, EXPORTED_SYMBOLS, wide, binding, decimate_batch_device,
     biquad_batch_device, ingest_batch_device, extrapolate_batch_device, process_and_flush_batch_device,
     process_batch_device, process_batch_planar_device, process_and_flush_batch_planar_device, ClipResampler,
+    process_schedule_batch_device, process_schedule_batch_planar_device,
     decimate_batch_planar_device, ClipDecimator, biquad_batch_planar_device, ClipFilter,
     STRETCH_FAST_FLAG, STRETCH_DUAL_FLAG, Stretcher, stretch_clips_batch_planar_device, ClipStretcher,
 )

@@ -185,6 +185,9 @@ def _bind(width):
         "resampleProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "stretchProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "artamdStretchClipCapacity": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double]),
+        "resampleProcessSchedulePlanarDevice": (C.c_int, [RP, C.c_int, ptr, C.c_long, ptr, ptr, C.c_long, ptr, ptr, C.c_int, ptr]),
+        "resampleProcessScheduleBatchInterleavedDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleProcessScheduleBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
     }
 
     _state = {"lib": None}
@@ -376,6 +379,22 @@ def _bind(width):
                 raise RuntimeError("resampleProcessScheduleInterleavedDevice failed")
             return rc, [(res[k].input_used, res[k].output_generated) for k in range(n)]
 
+        def process_schedule_planar_device(self, d_in, in_pitch, n_ins, d_out, out_pitch, caps, ratios, flush_last=False):
+            """resampleProcessSchedulePlanarDevice: process_schedule_device on channels-first buffers (pitches in samples, 0: that side
+            interleaved): the blocks follow one another along every input plane, the outputs are packed along every output plane.
+            Returns (blocks_made, [(input_used, output_generated), ...]); raises if a launch failed."""
+            n = len(n_ins)
+            if len(caps) != n or len(ratios) != n:
+                raise ValueError("n_ins, caps and ratios must have one entry per block")
+            res = (ResampleResult * max(n, 1))()
+            rc = self.L.resampleProcessSchedulePlanarDevice(
+                self.p, n, _dev_ptr(d_in), int(in_pitch), (C.c_int * max(n, 1))(*[int(v) for v in n_ins]), _dev_ptr(d_out), int(out_pitch),
+                (C.c_int * max(n, 1))(*[int(v) for v in caps]), (C.c_double * max(n, 1))(*[float(v) for v in ratios]),
+                1 if flush_last else 0, res)
+            if rc < 0:
+                raise RuntimeError("resampleProcessSchedulePlanarDevice failed")
+            return rc, [(res[k].input_used, res[k].output_generated) for k in range(n)]
+
         def process_planar_device(self, d_in, in_pitch, n_in, d_out, out_pitch, out_cap, ratio):
             r = self.L.resampleProcessPlanarDevice(self.p, _dev_ptr(d_in), in_pitch, n_in, _dev_ptr(d_out), out_pitch, out_cap, ratio)
             return r.input_used, r.output_generated
@@ -539,6 +558,50 @@ def _bind(width):
         process_batch_planar_device; a d_ins entry may be None with n_ins 0: a pure flush).  The flushes write behind the process
         calls' frames in every plane.  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
         return _batch_planar("resampleProcessAndFlushBatchPlanarDevice", resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios)
+
+    def _schedule_batch(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last):
+        n = len(resamplers)
+        if not (len(d_ins) == len(n_ins) == len(d_outs) == len(caps) == len(ratios) == n):
+            raise ValueError("one entry per stream in every list")
+        m = max(n, 1)
+        counts = [len(v) for v in n_ins]
+        if any(len(caps[i]) != counts[i] or len(ratios[i]) != counts[i] for i in range(n)):
+            raise ValueError("n_ins[i], caps[i] and ratios[i] must have one entry per block")
+        rows = lambda ctype, lists: [(ctype * max(len(v), 1))(*v) for v in lists]
+        table = lambda arrays: (C.c_void_p * m)(*[C.cast(a, C.c_void_p) for a in arrays])
+        frames = rows(C.c_int, [[int(v) for v in row] for row in n_ins])
+        room = rows(C.c_int, [[int(v) for v in row] for row in caps])
+        rates = rows(C.c_double, [[float(v) for v in row] for row in ratios])
+        res = [(ResampleResult * max(k, 1))() for k in counts]
+        made = (C.c_int * m)()
+        pitches = lambda v: None if v is None else (C.c_long * m)(*[int(q) for q in v])
+        head = [(C.c_void_p * m)(*[C.cast(r.p, C.c_void_p) for r in resamplers]), n, (C.c_int * m)(*counts),
+                (C.c_void_p * m)(*[None if d is None else _dev_ptr(d) for d in d_ins])]
+        outs = (C.c_void_p * m)(*[_dev_ptr(d) for d in d_outs])
+        tail = [table(rates), None if flush_last is None else (C.c_int * m)(*[1 if f else 0 for f in flush_last]), table(res), made]
+        if in_pitches is None and out_pitches is None:
+            name = "resampleProcessScheduleBatchInterleavedDevice"
+            rc = lib().resampleProcessScheduleBatchInterleavedDevice(*head, table(frames), outs, table(room), *tail)
+        else:
+            name = "resampleProcessScheduleBatchPlanarDevice"
+            rc = lib().resampleProcessScheduleBatchPlanarDevice(*head, pitches(in_pitches), table(frames), outs, pitches(out_pitches), table(room), *tail)
+        if rc < 0:
+            raise RuntimeError(name + " failed")
+        return rc, [(made[i], [(res[i][k].input_used, res[i][k].output_generated) for k in range(counts[i])]) for i in range(n)]
+
+    def process_schedule_batch_device(resamplers, d_ins, n_ins, d_outs, caps, ratios, flush_last=None):
+        """resampleProcessScheduleBatchInterleavedDevice: Resampler.process_schedule_device for every stream of a list in one call —
+        n_ins[i], caps[i] and ratios[i] are stream i's blocks, contiguous in d_ins[i], the outputs packed in d_outs[i]; flush_last: a flag
+        per stream, or None.  The gatherable blocks of all streams share one launch per kernel variant.
+        Returns (launches, [(blocks_made_i, [(input_used, output_generated), ...]), ...]); raises if a launch failed."""
+        return _schedule_batch(resamplers, d_ins, None, n_ins, d_outs, None, caps, ratios, flush_last)
+
+    def process_schedule_batch_planar_device(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last=None):
+        """resampleProcessScheduleBatchPlanarDevice: process_schedule_batch_device with a pitch per buffer, in samples (channel c of
+        stream i at d_ins[i] + c * in_pitches[i]; 0: that side of that stream interleaved; None for a pitch list: every stream's is)."""
+        if in_pitches is None and out_pitches is None:
+            in_pitches = [0] * len(resamplers)
+        return _schedule_batch(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last)
 
     class ClipResampler:
         """Whole clips, channels-first, from one fixed rate to another: x [B, C, T] (or [C, T]) on the GPU in, (y [B, C, Tout_max],

@@ -222,6 +222,20 @@ int arthip_fir_schedule_accepts (const ArtFirArgs *block, const ArtamdSegment *s
  * after run: stream order protects it).  Returns ART_KERNEL_GENERAL | ART_FIR_ROLLED, or -1 with nothing enqueued. */
 size_t arthip_fir_schedule_bytes (int nblocks, int nsegs);
 int arthip_fir_schedule (const ArtFirArgs *run, ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs, int nsegs, void *d_table, void *stream);
+/* The runs of MANY streams as one launch per kernel variant (resampleProcessScheduleBatch*Device; fir_general_schedule_batch_kernel).  An item is
+ * what arthip_fir_schedule would get for its stream (nblocks > 0; no timing events), each keeps the tile of its own launch; the history rolls
+ * ride along.  One upload carries every item, block and segment: d_table is device memory of arthip_fir_schedule_batch_bytes bytes (reused call
+ * after call: stream order protects it).  Returns the number of launches enqueued, every item's `launched` 1 — or -1: a launch failed (or the
+ * ARTAMD_TEST_FAIL_FIR hook, which counts one per call of this function, before anything is enqueued) and `launched` says whose run is on the
+ * stream all the same (all 0 where nothing was enqueued). */
+typedef struct {
+    ArtFirArgs run;
+    const ArtSchedBlock *blocks; int nblocks;
+    const ArtSchedSeg *segs; int nsegs;
+    int launched;
+} ArtSchedItem;
+size_t arthip_fir_schedule_batch_bytes (int nitems, int nblocks, int nsegs);
+int arthip_fir_schedule_batch (ArtSchedItem *items, int n, void *d_table, void *stream);
 /* the upkeep every launch of a rational-ratio stream does for the rows kept across calls (arthip_fir calls it itself) */
 void arthip_fir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs);
 /* new_hist[H][C] = last H frames of (hist ++ in[0..appended)); in may be NULL => zeros appended */

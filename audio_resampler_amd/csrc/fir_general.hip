@@ -385,15 +385,17 @@ void fir_general_batch_kernel (const FirBatchItem *items)
 // body expects, as the batched kernel does.
 constexpr int SCHED_SEGS = 4;                       // segments a tile may touch (the host checks: arthip_fir_schedule_accepts)
 
+// (bx, by: the workgroup's place in the run's own grid — the launch's, or an item's of the many-stream launch below.  The run's buffers are
+// interleaved, or planes where a pitch is set: the block's outputs start at frame out_off of every plane.)
 template <int CG, bool INTERP, bool PRECISE, int G, bool PIPE, int LEAN>
-__global__ __launch_bounds__ (GEN_THREADS)
-void fir_general_schedule_kernel (ArtFirArgs run, const ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs, unsigned int tiles_total, int tile)
+__device__ __forceinline__ void fir_general_schedule_body (const ArtFirArgs &run, const ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs,
+                                                           unsigned int tiles_total, int tile, unsigned int bx, unsigned int by)
 {
     __shared__ ArtSegTable s_tab;
     __shared__ int s_blk, s_seg0, s_seg1;
     const unsigned int per_xcd = (tiles_total + 7u) / 8u, workers = 8u * per_xcd;
-    if (blockIdx.x >= workers) { general_roll (run, blockIdx.x - workers, blockIdx.y); return; }
-    const unsigned int g = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    if (bx >= workers) { general_roll (run, bx - workers, by); return; }
+    const unsigned int g = (bx & 7u) * per_xcd + (bx >> 3);
     if (g >= tiles_total) return;
     const int tid = threadIdx.x;
 
@@ -427,8 +429,36 @@ void fir_general_schedule_kernel (ArtFirArgs run, const ArtSchedBlock *blocks, i
     ArtFirArgs a = run;
     a.ratio = blk.ratio;
     a.in_frames = blk.in_end;
-    a.out = run.out + (size_t) blk.out_off * run.C;
-    fir_general_tile<CG, INTERP, PRECISE, G, PIPE, LEAN> (a, s_tab, n0, cnt, blockIdx.y);
+    a.out = run.out_pitch ? run.out + (size_t) blk.out_off : run.out + (size_t) blk.out_off * run.C;
+    fir_general_tile<CG, INTERP, PRECISE, G, PIPE, LEAN> (a, s_tab, n0, cnt, by);
+}
+
+template <int CG, bool INTERP, bool PRECISE, int G, bool PIPE, int LEAN>
+__global__ __launch_bounds__ (GEN_THREADS)
+void fir_general_schedule_kernel (ArtFirArgs run, const ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs, unsigned int tiles_total, int tile)
+{
+    fir_general_schedule_body<CG, INTERP, PRECISE, G, PIPE, LEAN> (run, blocks, nblocks, segs, tiles_total, tile, blockIdx.x, blockIdx.y);
+}
+
+// The runs of MANY streams, one launch (resampleProcessScheduleBatch*Device): blockIdx.z picks a stream's run — an item of a table in device
+// memory: the arguments its own launch above would have passed by value, its blocks and segments at their offsets into the launch's two
+// arrays —, x / y are that run's own grid, roll workgroups included.  Same body, the run's own tile => the samples are those of n separate
+// launches.  The plain tap loop, as the batched kernel: every form gives the same bits.
+struct FirSchedItem {
+    ArtFirArgs run;
+    unsigned int block_off, seg_off;                // the run's blocks and segments in the launch's arrays
+    int nblocks; unsigned int tiles_total;
+    int tile; unsigned int blocks_x, blocks_y; int pad;
+};
+
+template <int CG, bool INTERP, bool PRECISE, int G>
+__global__ __launch_bounds__ (GEN_THREADS)
+void fir_general_schedule_batch_kernel (const FirSchedItem *items, const ArtSchedBlock *blocks, const ArtSchedSeg *segs)
+{
+    const FirSchedItem &it = items [blockIdx.z];
+    if (blockIdx.x >= it.blocks_x || blockIdx.y >= it.blocks_y) return;
+    fir_general_schedule_body<CG, INTERP, PRECISE, G, false, 0> (it.run, blocks + it.block_off, it.nblocks, segs + it.seg_off, it.tiles_total, it.tile,
+                                                                 blockIdx.x, blockIdx.y);
 }
 
 // Strict kernel: one lane per output sample, taps visited in the reference's source order
@@ -657,27 +687,39 @@ int schedule_accepts (const ArtFirArgs &a, const ArtamdSegment *segs, int nseg, 
     return 1;
 }
 
-// One launch over the run's blocks: the tile from the run's outputs and its SMALLEST ratio (the span bound depends on the ratio; an
-// output's bits do not depend on its tile), the tap-loop form of the single launch.
+// The geometry of a run's launch: the tile from the run's outputs and its SMALLEST ratio (the span bound depends on the ratio; an output's
+// bits do not depend on its tile), every block's first tile, the grid with the roll's workgroups.  `a`: the run's arguments with that ratio.
 template <int CG>
-int launch_schedule (const ArtFirArgs &run, ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs, int nsegs, void *d_table, hipStream_t st)
+bool schedule_geometry (const ArtFirArgs &run, ArtSchedBlock *blocks, int nblocks, ArtFirArgs *a_out, int *tile_out, size_t *lds_out, dim3 *grid_out,
+                        unsigned int *tiles_out)
 {
     ArtFirArgs a = run;
     unsigned int outputs = 0;
     for (int b = 0; b < nblocks; ++b) { outputs += blocks [b].outputs; if (blocks [b].ratio < a.ratio || b == 0) a.ratio = blocks [b].ratio; }
     a.n_begin = 0; a.n_end = outputs;
     int tile; size_t lds; dim3 grid;
-    if (!general_geometry<CG> (a, &tile, &lds, &grid)) return -1;
+    if (!general_geometry<CG> (a, &tile, &lds, &grid)) return false;
     unsigned int tiles = 0;
     for (int b = 0; b < nblocks; ++b) { blocks [b].first_tile = tiles; tiles += (blocks [b].outputs + (unsigned int) tile - 1) / (unsigned int) tile; }
+    const unsigned int roll_blocks = a.roll_dst ? (unsigned int)((a.H * a.C + GEN_THREADS - 1) / GEN_THREADS) : 0u;
+    grid.x = 8u * ((tiles + 7u) / 8u) + roll_blocks;
+    *a_out = a; *tile_out = tile; *lds_out = lds; *grid_out = grid; *tiles_out = tiles;
+    return true;
+}
+
+// One launch over the run's blocks, the tap-loop form of the single launch.
+template <int CG>
+int launch_schedule (const ArtFirArgs &run, ArtSchedBlock *blocks, int nblocks, const ArtSchedSeg *segs, int nsegs, void *d_table, hipStream_t st)
+{
+    ArtFirArgs a;
+    int tile; size_t lds; dim3 grid; unsigned int tiles;
+    if (!schedule_geometry<CG> (run, blocks, nblocks, &a, &tile, &lds, &grid, &tiles)) return -1;
     const size_t bytes_b = sizeof (ArtSchedBlock) * (size_t) nblocks, bytes = arthip_fir_schedule_bytes (nblocks, nsegs);
     Staging *sg = staging_take (bytes);
     if (!sg) return -1;
     std::memcpy (sg->host, blocks, bytes_b);
     std::memcpy ((char *) sg->host + bytes_b, segs, bytes - bytes_b);
     if (hipMemcpyAsync (d_table, sg->host, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { (void) staging_give (sg, st); return -1; }
-    const unsigned int roll_blocks = a.roll_dst ? (unsigned int)((a.H * a.C + GEN_THREADS - 1) / GEN_THREADS) : 0u;
-    grid.x = 8u * ((tiles + 7u) / 8u) + roll_blocks;
     if (a.ev_start) (void) hipEventRecord ((hipEvent_t) a.ev_start, st);
     general_form<CG> (a, [&] (auto i, auto p, auto gg, auto pp, auto ll) {
         auto k = fir_general_schedule_kernel<CG, decltype (i)::value, decltype (p)::value, decltype (gg)::value, decltype (pp)::value, decltype (ll)::value>;
@@ -688,6 +730,44 @@ int launch_schedule (const ArtFirArgs &run, ArtSchedBlock *blocks, int nblocks, 
     if (a.ev_stop) (void) hipEventRecord ((hipEvent_t) a.ev_stop, st);
     const bool ok = hipGetLastError () == hipSuccess;
     return staging_give (sg, st) || !ok ? -1 : 0;
+}
+
+// The kernel variant of a run (as arthip_fir_batch classes calls): channel group x interpolation x accumulator x lane group
+inline int schedule_variant (const ArtFirArgs &a)
+{
+    const int cgi = a.C > 4 ? 3 : a.C > 2 ? 2 : a.C == 2 ? 1 : 0;
+    const int lanes = general_group (a.T) == 16 ? 0 : general_group (a.T) == 32 ? 1 : 2;
+    return cgi * 12 + lanes * 4 + ((a.mode & 3) == ART_MODE_PRECISE ? 2 : 0) + (a.interpolate ? 1 : 0);
+}
+
+// An item of the many-stream launch: the run's own geometry (its blocks' first tiles go into the table's copy `hblocks`); false: not a launch's
+template <int CG>
+bool schedule_item (const ArtSchedItem &src, FirSchedItem *it, ArtSchedBlock *hblocks, size_t *lds_out)
+{
+    ArtFirArgs a;
+    int tile; size_t lds; dim3 grid; unsigned int tiles;
+    if (!schedule_geometry<CG> (src.run, hblocks, src.nblocks, &a, &tile, &lds, &grid, &tiles) || lds > GEN_LDS_BUDGET) return false;
+    it->run = src.run; it->nblocks = src.nblocks; it->tiles_total = tiles; it->tile = tile;
+    it->blocks_x = grid.x; it->blocks_y = grid.y; it->pad = 0;
+    *lds_out = lds;
+    return true;
+}
+
+template <int CG>
+int launch_schedule_batch (int form, const FirSchedItem *d_items, unsigned int count, dim3 grid, size_t lds, const ArtSchedBlock *d_blocks,
+                           const ArtSchedSeg *d_segs, hipStream_t st)
+{
+    const bool interp = (form & 1) != 0, precise = (form & 2) != 0;
+    const int lanes = form >> 2;
+#define GOS(I, P) do { if (lanes == 0) GOS_ (I, P, 16); else if (lanes == 1) GOS_ (I, P, 32); else GOS_ (I, P, 64); } while (0)
+#define GOS_(I, P, GG) do { auto k = fir_general_schedule_batch_kernel<CG, I, P, GG>; \
+        if (lds > 48 * 1024) (void) hipFuncSetAttribute ((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); \
+        hipLaunchKernelGGL (k, dim3 (grid.x, grid.y, count), dim3 (GEN_THREADS), lds, st, d_items, d_blocks, d_segs); } while (0)
+    if (interp) { if (precise) GOS (true, true); else GOS (true, false); }
+    else        { if (precise) GOS (false, true); else GOS (false, false); }
+#undef GOS
+#undef GOS_
+    return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
 } // namespace
@@ -779,6 +859,79 @@ int arthip_fir_schedule (const ArtFirArgs *run, ArtSchedBlock *blocks, int nbloc
     const int rc = a.C > 4 ? launch_schedule<8> (a, blocks, nblocks, segs, nsegs, d_table, st) : a.C > 2 ? launch_schedule<4> (a, blocks, nblocks, segs, nsegs, d_table, st) :
                    a.C == 2 ? launch_schedule<2> (a, blocks, nblocks, segs, nsegs, d_table, st) : launch_schedule<1> (a, blocks, nblocks, segs, nsegs, d_table, st);
     return rc ? -1 : (ART_KERNEL_GENERAL | (a.roll_dst ? ART_FIR_ROLLED : 0));
+}
+
+size_t arthip_fir_schedule_batch_bytes (int nitems, int nblocks, int nsegs)
+{
+    return sizeof (FirSchedItem) * (size_t) nitems + sizeof (ArtSchedBlock) * (size_t) nblocks + sizeof (ArtSchedSeg) * (size_t) nsegs;
+}
+
+int arthip_fir_schedule_batch (ArtSchedItem *items, int n, void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    constexpr int VARIANTS = 48;
+    constexpr unsigned int GRID_Z = 65535u;
+    for (int i = 0; i < n; ++i) items [i].launched = 0;
+    if (n <= 0) return 0;
+    if (artfir_test_fail ()) return -1;
+    int nblocks = 0, nsegs = 0;
+    for (int i = 0; i < n; ++i) {
+        if (items [i].nblocks <= 0 || items [i].run.ev_start) return -1;
+        nblocks += items [i].nblocks; nsegs += items [i].nsegs;
+    }
+    const size_t bytes = arthip_fir_schedule_batch_bytes (n, nblocks, nsegs);
+    Staging *sg = staging_take (bytes);
+    int *order = (int *) malloc (sizeof (int) * (size_t) n);
+    if (!sg || !order) { free (order); return -1; }
+    // the table: the items variant by variant (a launch takes a slice of them), every run's blocks, every run's segments
+    FirSchedItem *hitems = (FirSchedItem *) sg->host;
+    ArtSchedBlock *hblocks = (ArtSchedBlock *)(hitems + n);
+    ArtSchedSeg *hsegs = (ArtSchedSeg *)(hblocks + nblocks);
+    const FirSchedItem *ditems = (const FirSchedItem *) d_table;
+    const ArtSchedBlock *dblocks = (const ArtSchedBlock *)(ditems + n);
+    const ArtSchedSeg *dsegs = (const ArtSchedSeg *)(dblocks + nblocks);
+    struct { int first, count; size_t lds; dim3 grid; } slice [VARIANTS];
+    int done = 0, rc = 0, launches = 0;
+    unsigned int block_off = 0, seg_off = 0;
+    for (int v = 0; v < VARIANTS && !rc; ++v) {
+        slice [v].first = done; slice [v].count = 0; slice [v].lds = 0; slice [v].grid = dim3 (0, 0, 1);
+        for (int i = 0; i < n && !rc; ++i) {
+            const ArtSchedItem &src = items [i];
+            if (schedule_variant (src.run) != v) continue;
+            FirSchedItem *it = &hitems [done];
+            std::memcpy (hblocks + block_off, src.blocks, sizeof (ArtSchedBlock) * (size_t) src.nblocks);
+            std::memcpy (hsegs + seg_off, src.segs, sizeof (ArtSchedSeg) * (size_t) src.nsegs);
+            size_t lds = 0;
+            const int cgi = v / 12;
+            const bool ok = cgi == 3 ? schedule_item<8> (src, it, hblocks + block_off, &lds) : cgi == 2 ? schedule_item<4> (src, it, hblocks + block_off, &lds) :
+                            cgi == 1 ? schedule_item<2> (src, it, hblocks + block_off, &lds) : schedule_item<1> (src, it, hblocks + block_off, &lds);
+            if (!ok) { rc = -1; break; }
+            it->block_off = block_off; it->seg_off = seg_off;
+            block_off += (unsigned int) src.nblocks; seg_off += (unsigned int) src.nsegs;
+            if (lds > slice [v].lds) slice [v].lds = lds;
+            if (it->blocks_x > slice [v].grid.x) slice [v].grid.x = it->blocks_x;
+            if (it->blocks_y > slice [v].grid.y) slice [v].grid.y = it->blocks_y;
+            order [done++] = i; ++slice [v].count;
+        }
+    }
+    if (!rc && hipMemcpyAsync (d_table, sg->host, bytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = -1;
+    for (int v = 0; v < VARIANTS && !rc; ++v)
+        for (int at = 0; at < slice [v].count && !rc; at += (int) GRID_Z) {         // (a grid's z holds 65,535 items)
+            const unsigned int count = slice [v].count - at < (int) GRID_Z ? (unsigned int)(slice [v].count - at) : GRID_Z;
+            const FirSchedItem *d = ditems + slice [v].first + at;
+            switch (v / 12) {
+                case 3: rc = launch_schedule_batch<8> (v % 12, d, count, slice [v].grid, slice [v].lds, dblocks, dsegs, st); break;
+                case 2: rc = launch_schedule_batch<4> (v % 12, d, count, slice [v].grid, slice [v].lds, dblocks, dsegs, st); break;
+                case 1: rc = launch_schedule_batch<2> (v % 12, d, count, slice [v].grid, slice [v].lds, dblocks, dsegs, st); break;
+                default: rc = launch_schedule_batch<1> (v % 12, d, count, slice [v].grid, slice [v].lds, dblocks, dsegs, st); break;
+            }
+            if (rc) break;
+            for (unsigned int k = 0; k < count; ++k) items [order [slice [v].first + at + (int) k]].launched = 1;
+            ++launches;
+        }
+    if (staging_give (sg, st)) rc = -1;
+    free (order);
+    return rc ? -1 : launches;
 }
 
 int arthip_roll_history (art_s *new_hist, const art_s *hist, const art_s *in, long in_pitch, int appended, int H, int C, void *stream)

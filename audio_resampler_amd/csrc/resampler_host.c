@@ -80,6 +80,7 @@ struct artamd_resampler {
     void *d_layout; size_t layout_cap;       /* ... and of the two transposing launches round the staged calls of a planar batch (resampleProcessBatchPlanarDevice) */
     art_s *d_tails; size_t tails_cap;        /* ... and the flush tails of every extrapolating context of such a call (resampleProcessAndFlushBatchInterleavedDevice) */
     void *d_sched; size_t sched_cap;         /* block and segment tables of the scheduled runs (resampleProcessScheduleInterleavedDevice) */
+    void *d_sched_batch; size_t sched_batch_cap;     /* item, block and segment table of the many-stream schedules led by this context */
     unsigned long batch_stamp;               /* last batched call this context took part in (duplicate check) */
     int last_gathered;                       /* the last call or block ran in a launch shared by the batch or schedule entry (resampleHipLastGathered) */
 };
@@ -704,7 +705,7 @@ void resampleFree (Resample *cxt)
         bank_release (hip->bank); arthip_free (hip->d_hist [0]); arthip_free (hip->d_hist [1]);
         {   /* every device buffer the context may have grown (NULL where it never did) */
             void *const device_buffers [] = { hip->d_in, hip->d_out, hip->d_tmp, hip->d_fix, hip->d_scratch, hip->d_pad, hip->d_planes, hip->d_rows,
-                                              hip->d_split, hip->d_patch, hip->d_batch, hip->d_group, hip->d_layout, hip->d_tails, hip->d_sched };
+                                              hip->d_split, hip->d_patch, hip->d_batch, hip->d_group, hip->d_layout, hip->d_tails, hip->d_sched, hip->d_sched_batch };
             for (size_t i = 0; i < sizeof (device_buffers) / sizeof (device_buffers [0]); ++i) arthip_free (device_buffers [i]);
         }
         if (hip->rows_cache) { arthip_fir_rows_cache_free (hip->rows_cache); free (hip->rows_cache); }
@@ -1863,6 +1864,7 @@ int resampleProcessAndFlushBatchPlanarDevice (Resample *const *cxts, int n, cons
 
 typedef struct {
     const art_s *in; art_s *out;         /* the run's first input / output frame */
+    long in_pitch, out_pitch;            /* samples between their planes (0: interleaved frames) */
     int gathered, first;                 /* blocks in the run (outputs or not), the index of its first in `results` */
     int frames; unsigned int outputs;    /* its input frames (appended to the history by its launch) and output frames */
     ArtamdPosition start;                /* the context's position before the run */
@@ -1872,7 +1874,8 @@ typedef struct {
 
 /* Plan block `k` as the single call would; gather it into the run if the general kernel is the single call's (1), else leave the context
  * as it stands (0) */
-static int sched_gather (Resample *cxt, SchedRun *run, const art_s *in, int nIn, art_s *out, int cap, double ratio, ResampleResult *res, int k)
+static int sched_gather (Resample *cxt, SchedRun *run, const art_s *in, long in_pitch, int nIn, art_s *out, long out_pitch, int cap, double ratio,
+                         ResampleResult *res, int k)
 {
     struct artamd_resampler *hip = cxt->hip;
     CallPlan p;
@@ -1885,10 +1888,13 @@ static int sched_gather (Resample *cxt, SchedRun *run, const art_s *in, int nIn,
     if (nseg < 0) return 0;                                              /* (out of memory: the single call reports it) */
     *res = p.res;
     if (res->output_generated) {
-        plan_args (cxt, &p, ratio, in, 0, out, 0, NULL, &a, &tab);
+        plan_args (cxt, &p, ratio, in, in_pitch, out, out_pitch, NULL, &a, &tab);
         a.lin_origin = hip->lin_origin + run->frames;                    /* (the run's earlier blocks are not in the history yet) */
         keep_rows (hip, &a);
-        if (!general_call (cxt, &a, &tab, res->output_generated) || !arthip_fir_schedule_accepts (&a, hip->segs, nseg, res->output_generated)) return 0;
+        /* (the matrix-core path takes interleaved frames only: a block in planes goes where the interleaved schedule's would — its single call stages for it) */
+        ArtFirArgs frames = a;
+        frames.in_pitch = frames.out_pitch = 0;
+        if (!general_call (cxt, &frames, &tab, res->output_generated) || !arthip_fir_schedule_accepts (&a, hip->segs, nseg, res->output_generated)) return 0;
         if (run->nblocks == run->block_cap) {
             const int want = run->block_cap ? 2 * run->block_cap : 16;
             ArtSchedBlock *b = realloc (run->blocks, sizeof (ArtSchedBlock) * (size_t) want);
@@ -1918,11 +1924,68 @@ static int sched_gather (Resample *cxt, SchedRun *run, const art_s *in, int nIn,
         run->floors [run->nblocks++] = lin_floor;
         run->nsegs += nseg;
     }
-    if (!run->gathered++) { run->in = in; run->out = out; run->first = k; run->start = position_of (cxt); }
+    if (!run->gathered++) { run->in = in; run->out = out; run->in_pitch = in_pitch; run->out_pitch = out_pitch; run->first = k; run->start = position_of (cxt); }
     hip->last_gathered = 1;
     run->frames += (int) res->input_used; run->outputs += res->output_generated;
     commit_position (cxt, &p.trial, res->output_generated != 0);
     return 1;
+}
+
+/* The pending run's launch arguments (nblocks > 0) — and, on the way, the upkeep of the kept rows, block by block, with the arguments and
+ * tables of the single call's launches */
+static void sched_run_args (Resample *cxt, const SchedRun *run, ArtFirArgs *a)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    const int C = cxt->numChannels;
+    ArtSegTable tab;
+    for (int i = 0; i < run->nblocks; ++i) {
+        const ArtSchedBlock *b = &run->blocks [i];
+        fill_args (cxt, a, b->ratio, run->in + (size_t) b->in_off * (run->in_pitch ? 1 : C), run->in_pitch, b->in_end - b->in_off,
+                   run->out + (size_t) b->out_off * (run->out_pitch ? 1 : C), run->out_pitch);
+        a->lin_origin = hip->lin_origin + b->in_off;
+        keep_rows (hip, a);
+        if (!a->rows_cache) continue;
+        const int nseg = b->seg_end - b->seg_begin;
+        for (int s0 = 0; s0 < nseg; s0 += ART_MAX_SEGS) {
+            const int s1 = s0 + ART_MAX_SEGS < nseg ? s0 + ART_MAX_SEGS : nseg;
+            tab.count = s1 - s0; tab.lin_floor = run->floors [i];
+            for (int q = s0; q < s1; ++q) {
+                const ArtSchedSeg *g = &run->segs [b->seg_begin + q];
+                tab.first [q - s0] = g->first; tab.lin_base [q - s0] = g->lin_base; tab.base [q - s0] = g->base;
+            }
+            a->n_begin = run->segs [b->seg_begin + s0].first;
+            a->n_end = s1 < nseg ? run->segs [b->seg_begin + s1].first : b->outputs;
+            if (a->n_end > a->n_begin) arthip_fir_rows_touch (a, &tab);
+        }
+    }
+    fill_args (cxt, a, run->blocks [0].ratio, run->in, run->in_pitch, run->frames, run->out, run->out_pitch);
+    a->roll_dst = run->frames > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;
+    a->roll_appended = run->frames;
+}
+
+static void sched_run_clear (SchedRun *run)
+{
+    run->gathered = run->nblocks = run->nsegs = run->frames = 0; run->outputs = 0;
+}
+
+/* the run's launch failed, or was never made: the context is back where it stood before the run, the run's results are { 0, 0 } */
+static void sched_run_undo (Resample *cxt, SchedRun *run, ResampleResult *results)
+{
+    cxt->outputOffset = run->start.outputOffset; cxt->inputIndex = run->start.inputIndex;
+    cxt->flags = run->start.flags; cxt->hip->floor_active = run->start.floorActive;
+    zero_results (results + run->first, NULL, run->gathered);
+    sched_run_clear (run);
+}
+
+/* the run's launch (if it has blocks: `launched`) is on the stream: the history behind it, rolled here unless the launch took the roll along */
+static void sched_run_done (Resample *cxt, SchedRun *run, int launched, int rolled)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    if (launched) { hip->last_kernel = ART_KERNEL_GENERAL; hip->last_fixed [0] = 0; }
+    if (run->frames > 0 && !rolled)
+        arthip_roll_history (hip->d_hist [hip->cur ^ 1], hip->d_hist [hip->cur], run->in, run->in_pitch, run->frames, HIST_FRAMES (cxt->numTaps), cxt->numChannels, hip->stream);
+    commit_history (hip, run->frames);
+    sched_run_clear (run);
 }
 
 /* Launch the pending run and roll the history behind it.  -1: the launch failed — nothing of it was enqueued, the context is back where it
@@ -1930,64 +1993,43 @@ static int sched_gather (Resample *cxt, SchedRun *run, const art_s *in, int nIn,
 static int sched_launch (Resample *cxt, SchedRun *run, ResampleResult *results)
 {
     struct artamd_resampler *hip = cxt->hip;
-    const int C = cxt->numChannels, H = HIST_FRAMES (cxt->numTaps);
     int rolled = 0;
 
     if (!run->gathered) return 0;
     if (run->nblocks) {
         ArtFirArgs a;
-        ArtSegTable tab;
-        /* the upkeep of the kept rows, block by block, with the arguments and tables of the single call's launches */
-        for (int i = 0; i < run->nblocks; ++i) {
-            const ArtSchedBlock *b = &run->blocks [i];
-            fill_args (cxt, &a, b->ratio, run->in + (size_t) b->in_off * C, 0, b->in_end - b->in_off, run->out + (size_t) b->out_off * C, 0);
-            a.lin_origin = hip->lin_origin + b->in_off;
-            keep_rows (hip, &a);
-            if (!a.rows_cache) continue;
-            const int nseg = b->seg_end - b->seg_begin;
-            for (int s0 = 0; s0 < nseg; s0 += ART_MAX_SEGS) {
-                const int s1 = s0 + ART_MAX_SEGS < nseg ? s0 + ART_MAX_SEGS : nseg;
-                tab.count = s1 - s0; tab.lin_floor = run->floors [i];
-                for (int q = s0; q < s1; ++q) {
-                    const ArtSchedSeg *g = &run->segs [b->seg_begin + q];
-                    tab.first [q - s0] = g->first; tab.lin_base [q - s0] = g->lin_base; tab.base [q - s0] = g->base;
-                }
-                a.n_begin = run->segs [b->seg_begin + s0].first;
-                a.n_end = s1 < nseg ? run->segs [b->seg_begin + s1].first : b->outputs;
-                if (a.n_end > a.n_begin) arthip_fir_rows_touch (&a, &tab);
-            }
-        }
-        fill_args (cxt, &a, run->blocks [0].ratio, run->in, 0, run->frames, run->out, 0);
-        a.roll_dst = run->frames > 0 ? hip->d_hist [hip->cur ^ 1] : NULL;
-        a.roll_appended = run->frames;
+        sched_run_args (cxt, run, &a);
         take_events (hip, &a);
         hip->d_sched = arthip_grow (hip->d_sched, &hip->sched_cap, arthip_fir_schedule_bytes (run->nblocks, run->nsegs));
         const int k = hip->d_sched ? arthip_fir_schedule (&a, run->blocks, run->nblocks, run->segs, run->nsegs, hip->d_sched, hip->stream) : -1;
         if (k < 0) {
             return_events (hip);
             artamd_note_failure ("resampler: schedule launch failed");
-            cxt->outputOffset = run->start.outputOffset; cxt->inputIndex = run->start.inputIndex;
-            cxt->flags = run->start.flags; hip->floor_active = run->start.floorActive;
-            zero_results (results + run->first, NULL, run->gathered);
-            run->gathered = run->nblocks = run->nsegs = run->frames = 0; run->outputs = 0;
+            sched_run_undo (cxt, run, results);
             return -1;
         }
         rolled = (k & ART_FIR_ROLLED) != 0;
-        hip->last_kernel = ART_KERNEL_GENERAL;
-        hip->last_fixed [0] = 0;
     }
-    if (run->frames > 0 && !rolled) arthip_roll_history (hip->d_hist [hip->cur ^ 1], hip->d_hist [hip->cur], run->in, 0, run->frames, H, C, hip->stream);
-    commit_history (hip, run->frames);
-    run->gathered = run->nblocks = run->nsegs = run->frames = 0; run->outputs = 0;
+    sched_run_done (cxt, run, run->nblocks != 0, rolled);
     return 0;
 }
 
-int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, const artsample_t *d_input, const int *numInputFrames,
-                                              artsample_t *d_output, const int *numOutputFrames, const double *ratios,
-                                              int flushLast, ResampleResult *results)
+/* a block's buffers: `frames` frames into the interleaved buffer, or into every plane */
+static const art_s *sched_at (const art_s *base, long pitch, size_t frames, int C) { return base ? base + frames * (pitch ? 1 : (size_t) C) : NULL; }
+
+/* a block as its single call, in the layout of the schedule's buffers */
+static ResampleResult sched_single (Resample *cxt, const art_s *in, long in_pitch, int nIn, art_s *out, long out_pitch, int cap, double ratio, int flush)
 {
-    if (numBlocks <= 0) return 0;
-    for (int k = 0; k < numBlocks; ++k) if (numInputFrames [k] < 0) return -1;
+    if (!in_pitch && !out_pitch)
+        return flush ? resampleProcessAndFlushInterleavedDevice (cxt, in, nIn, out, cap, ratio) : resampleProcessInterleavedDevice (cxt, in, nIn, out, cap, ratio);
+    return flush ? resampleProcessAndFlushPlanarDevice (cxt, in, in_pitch, nIn, out, out_pitch, cap, ratio)
+                 : resampleProcessPlanarDevice (cxt, in, in_pitch, nIn, out, out_pitch, cap, ratio);
+}
+
+/* one stream's schedule (numBlocks > 0, no negative frame count): *made = the blocks made; 0, or -1: a launch failed */
+static int schedule_one (Resample *cxt, int numBlocks, const art_s *d_input, long in_pitch, const int *numInputFrames, art_s *d_output, long out_pitch,
+                         const int *numOutputFrames, const double *ratios, int flushLast, ResampleResult *results, int *made_out)
+{
     zero_results (results, NULL, numBlocks);
     struct artamd_resampler *hip = cxt->hip;
     const int C = cxt->numChannels;
@@ -1998,16 +2040,15 @@ int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, cons
 
     ENTER_DEVICE (hip);
     for (int k = 0; k < numBlocks && !failed; ++k) {
-        const art_s *in = d_input ? d_input + in_pos * C : NULL;
-        art_s *out = d_output + out_pos * C;
+        const art_s *in = sched_at (d_input, in_pitch, in_pos, C);
+        art_s *out = (art_s *) sched_at (d_output, out_pitch, out_pos, C);
         const int flush = flushLast && k == numBlocks - 1;
         if (run.gathered && run.frames > RUN_FRAMES_MAX - numInputFrames [k] && sched_launch (cxt, &run, results)) { failed = 1; break; }
-        if (flush || !sched_gather (cxt, &run, in, numInputFrames [k], out, numOutputFrames [k], ratios [k], &results [k], k)) {
+        if (flush || !sched_gather (cxt, &run, in, in_pitch, numInputFrames [k], out, out_pitch, numOutputFrames [k], ratios [k], &results [k], k)) {
             /* the single call, behind the run before it (a failure of its own: { 0, 0 } and the count in artamdErrorCount) */
             if (sched_launch (cxt, &run, results)) { failed = 1; break; }
             const int errors = artamdErrorCount ();
-            results [k] = flush ? resampleProcessAndFlushInterleavedDevice (cxt, in, numInputFrames [k], out, numOutputFrames [k], ratios [k])
-                                : resampleProcessInterleavedDevice (cxt, in, numInputFrames [k], out, numOutputFrames [k], ratios [k]);
+            results [k] = sched_single (cxt, in, in_pitch, numInputFrames [k], out, out_pitch, numOutputFrames [k], ratios [k], flush);
             if (artamdErrorCount () != errors) { zero_results (&results [k], NULL, 1); failed = 1; break; }
         }
         made = k + 1;
@@ -2017,7 +2058,171 @@ int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, cons
     if (!failed && sched_launch (cxt, &run, results)) failed = 1;
     free (run.blocks); free (run.floors); free (run.segs);
     LEAVE_DEVICE (hip);
-    return failed ? -1 : made;
+    *made_out = made;
+    return failed ? -1 : 0;
+}
+
+int resampleProcessSchedulePlanarDevice (Resample *cxt, int numBlocks, const artsample_t *d_input, long inputPitch, const int *numInputFrames,
+                                         artsample_t *d_output, long outputPitch, const int *numOutputFrames, const double *ratios,
+                                         int flushLast, ResampleResult *results)
+{
+    if (numBlocks <= 0) return 0;
+    for (int k = 0; k < numBlocks; ++k) if (numInputFrames [k] < 0) return -1;
+    int made;
+    return schedule_one (cxt, numBlocks, d_input, inputPitch, numInputFrames, d_output, outputPitch, numOutputFrames, ratios, flushLast, results, &made) ? -1 : made;
+}
+
+int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, const artsample_t *d_input, const int *numInputFrames,
+                                              artsample_t *d_output, const int *numOutputFrames, const double *ratios,
+                                              int flushLast, ResampleResult *results)
+{
+    return resampleProcessSchedulePlanarDevice (cxt, numBlocks, d_input, 0, numInputFrames, d_output, 0, numOutputFrames, ratios, flushLast, results);
+}
+
+/* ---- the block schedules of many streams, one launch ------------------------------------------------------------------
+ * N drifting streams with K buffered blocks each: a schedule per stream is N launches, a batch per block index K.  The entries below go in
+ * ROUNDS.  In a round every live stream that may share a launch plans its next maximal run of gatherable blocks on its context, exactly as
+ * its single schedule would (sched_gather, unchanged: the same cuts); the round's runs go out together, one launch per kernel variant
+ * (arthip_fir_schedule_batch: every run keeps its own tile, the rolls ride along, one table upload); then every stream whose next block is
+ * not gatherable makes it as its single call.  A context that shares no launch is its own single schedule, made first. */
+typedef struct {
+    SchedRun run;
+    size_t in_pos, out_pos;              /* frames in front of the next block, in the stream's input and output */
+    int next;                            /* the next block to plan */
+    int live;                            /* blocks left to make */
+    int cut;                             /* the run was cut at RUN_FRAMES_MAX: its next block is the next round's first */
+} SchedStream;
+
+static int schedule_batch (Resample *const *cxts, int n, const int *numBlocks, const artsample_t *const *d_inputs, const long *in_pitches,
+                           const int *const *numInputFrames, artsample_t *const *d_outputs, const long *out_pitches,
+                           const int *const *numOutputFrames, const double *const *ratios, const int *flushLast,
+                           ResampleResult *const *results, int *blocksMade)
+{
+    if (n <= 0) return 0;
+    if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample schedule", "context")) return -1;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < numBlocks [i]; ++k) if (numInputFrames [i] [k] < 0) return -1;
+
+    struct artamd_resampler *lead = cxts [0]->hip;
+    SchedStream *st = calloc ((size_t) n, sizeof (SchedStream));
+    ArtSchedItem *items = malloc (sizeof (ArtSchedItem) * (size_t) n);
+    int *item_of = malloc (sizeof (int) * (size_t) n);
+    int launches = 0, failed = 0, live = 0;
+
+    for (int i = 0; i < n; ++i) {
+        blocksMade [i] = 0;
+        if (numBlocks [i] > 0) zero_results (results [i], NULL, numBlocks [i]);
+    }
+    if (!st || !items || !item_of) { free (st); free (items); free (item_of); artamd_note_failure ("resampler: out of memory (schedule batch)"); return -1; }
+
+    ENTER_DEVICE (lead);
+    for (int i = 0; i < n && !failed; ++i) {
+        Resample *cxt = cxts [i];
+        if (numBlocks [i] <= 0) continue;
+        if (shares_lead (cxt, lead) && !(cxt->flags & RESAMPLE_STRICT_ORDER)) { st [i].live = 1; ++live; continue; }
+        /* (sharded, another stream or device, timing on; strict order, which gathers nothing: the context's own schedule) */
+        failed = schedule_one (cxt, numBlocks [i], d_inputs [i], in_pitches ? in_pitches [i] : 0, numInputFrames [i], d_outputs [i],
+                               out_pitches ? out_pitches [i] : 0, numOutputFrames [i], ratios [i], flushLast ? flushLast [i] : 0, results [i], &blocksMade [i]);
+        ++launches;
+    }
+
+    while (live && !failed) {
+        int nitems = 0, nb = 0, ns = 0;
+        /* every live stream's next run */
+        for (int i = 0; i < n; ++i) {
+            SchedStream *s = &st [i];
+            if (!s->live) continue;
+            Resample *cxt = cxts [i];
+            const int C = cxt->numChannels;
+            const long in_pitch = in_pitches ? in_pitches [i] : 0, out_pitch = out_pitches ? out_pitches [i] : 0;
+            s->cut = 0;
+            while (s->next < numBlocks [i]) {
+                const int k = s->next, nIn = numInputFrames [i] [k];
+                if (flushLast && flushLast [i] && k == numBlocks [i] - 1) break;
+                if (s->run.gathered && s->run.frames > RUN_FRAMES_MAX - nIn) { s->cut = 1; break; }
+                if (!sched_gather (cxt, &s->run, sched_at (d_inputs [i], in_pitch, s->in_pos, C), in_pitch, nIn,
+                                   (art_s *) sched_at (d_outputs [i], out_pitch, s->out_pos, C), out_pitch, numOutputFrames [i] [k], ratios [i] [k],
+                                   &results [i] [k], k)) break;
+                ++s->next;
+                if ((int) results [i] [k].input_used != nIn) { s->next = numBlocks [i]; break; }       /* a cap too small: no later block is made */
+                s->in_pos += (size_t) nIn; s->out_pos += results [i] [k].output_generated;
+            }
+            if (s->run.nblocks) {
+                ArtSchedItem *it = &items [nitems];
+                sched_run_args (cxt, &s->run, &it->run);
+                it->blocks = s->run.blocks; it->nblocks = s->run.nblocks; it->segs = s->run.segs; it->nsegs = s->run.nsegs; it->launched = 0;
+                nb += it->nblocks; ns += it->nsegs;
+                item_of [i] = nitems++;
+            }
+        }
+        /* the round's runs, one launch per kernel variant */
+        int rc = 0;
+        if (nitems) {
+            lead->d_sched_batch = arthip_grow (lead->d_sched_batch, &lead->sched_batch_cap, arthip_fir_schedule_batch_bytes (nitems, nb, ns));
+            rc = lead->d_sched_batch ? arthip_fir_schedule_batch (items, nitems, lead->d_sched_batch, lead->stream) : -1;
+            if (rc < 0) {
+                fprintf (stderr, "artamd: resample schedule batch launch failed: %s\n", arthip_last_error ());
+                artamd_note_failure ("resampler: schedule batch launch failed");
+                failed = 1;
+            }
+            else launches += rc;
+        }
+        for (int i = 0; i < n; ++i) {
+            SchedStream *s = &st [i];
+            if (!s->live || !s->run.gathered) continue;
+            const int first = s->run.first, gathered = s->run.gathered, launched = s->run.nblocks && items [item_of [i]].launched;
+            if (failed && !launched) {
+                /* (the stream stands where it stood before its run; no later block of it is made) */
+                sched_run_undo (cxts [i], &s->run, results [i]);
+                if (first + gathered < numBlocks [i]) zero_results (results [i] + first + gathered, NULL, numBlocks [i] - first - gathered);
+                continue;
+            }
+            if (!s->run.nblocks && s->run.frames > 0) ++launches;                    /* (no output: the history roll alone) */
+            sched_run_done (cxts [i], &s->run, launched, launched);
+            blocksMade [i] = first + gathered;
+        }
+        if (failed) break;
+        /* the blocks that are single calls, behind their streams' runs */
+        for (int i = 0; i < n && !failed; ++i) {
+            SchedStream *s = &st [i];
+            if (!s->live) continue;
+            if (s->next < numBlocks [i] && !s->cut) {
+                Resample *cxt = cxts [i];
+                const int C = cxt->numChannels, k = s->next, nIn = numInputFrames [i] [k];
+                const long in_pitch = in_pitches ? in_pitches [i] : 0, out_pitch = out_pitches ? out_pitches [i] : 0;
+                const int errors = artamdErrorCount ();
+                results [i] [k] = sched_single (cxt, sched_at (d_inputs [i], in_pitch, s->in_pos, C), in_pitch, nIn,
+                                                (art_s *) sched_at (d_outputs [i], out_pitch, s->out_pos, C), out_pitch, numOutputFrames [i] [k], ratios [i] [k],
+                                                flushLast && flushLast [i] && k == numBlocks [i] - 1);
+                ++launches;
+                if (artamdErrorCount () != errors) { zero_results (&results [i] [k], NULL, 1); failed = 1; break; }
+                blocksMade [i] = ++s->next;
+                if ((int) results [i] [k].input_used != nIn) s->next = numBlocks [i];
+                s->in_pos += (size_t) nIn; s->out_pos += results [i] [k].output_generated;
+            }
+            if (s->next >= numBlocks [i]) { s->live = 0; --live; }
+        }
+    }
+    LEAVE_DEVICE (lead);
+    for (int i = 0; i < n; ++i) { free (st [i].run.blocks); free (st [i].run.floors); free (st [i].run.segs); }
+    free (st); free (items); free (item_of);
+    return failed ? -1 : launches;
+}
+
+int resampleProcessScheduleBatchInterleavedDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_inputs, const int *const *numInputFrames,
+        artsample_t *const *d_outputs, const int *const *numOutputFrames, const double *const *ratios,
+        const int *flushLast, ResampleResult *const *results, int *blocksMade)
+{
+    return schedule_batch (cxts, n, numBlocks, d_inputs, NULL, numInputFrames, d_outputs, NULL, numOutputFrames, ratios, flushLast, results, blocksMade);
+}
+
+int resampleProcessScheduleBatchPlanarDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *const *numInputFrames,
+        artsample_t *const *d_outputs, const long *outputPitches, const int *const *numOutputFrames,
+        const double *const *ratios, const int *flushLast, ResampleResult *const *results, int *blocksMade)
+{
+    return schedule_batch (cxts, n, numBlocks, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, flushLast, results, blocksMade);
 }
 
 /* what a call would consume / produce, without touching the context */

@@ -91,7 +91,8 @@ unsigned int resampleHipCutInvariantFallbacks (Resample *cxt);
 void resampleHipKeepRows (Resample *cxt, int on);
 int  resampleHipLastKernel (Resample *cxt);          /* which kernel produced the bulk of the last call */
 /* 1 when the context's last call or block ran inside a launch shared by resampleProcessBatchInterleavedDevice,
- * resampleProcessAndFlushBatchInterleavedDevice or resampleProcessScheduleInterleavedDevice, 0 when it ran as a single call (which streams of a service batch) */
+ * resampleProcessAndFlushBatchInterleavedDevice, resampleProcessScheduleInterleavedDevice or the other schedule entries below, 0 when it ran as a
+ * single call (which streams of a service batch) */
 int  resampleHipLastGathered (Resample *cxt);
 /* the matrix-core path's fixed-point kernel (regular launches, 4-byte samples): 0 = the last call did not use it, 1 = it ran,
  * 2 = it was enqueued and stood down for the f32 kernel's tile loop (an infinity or a NaN among the frames the launch reads: any finite
@@ -186,6 +187,43 @@ int resampleProcessAndFlushBatchInterleavedDevice (Resample *const *cxts, int n,
 int resampleProcessScheduleInterleavedDevice (Resample *cxt, int numBlocks, const artsample_t *d_input, const int *numInputFrames,
                                               artsample_t *d_output, const int *numOutputFrames, const double *ratios,
                                               int flushLast, ResampleResult *results);
+/* ... on channels-first buffers: exactly resampleProcessScheduleInterleavedDevice on transposed copies.  Pitches in samples, as in
+ * resampleProcessPlanarDevice below: channel c is at d_input + c * inputPitch and the blocks' inputs follow one another along every plane;
+ * block k's outputs start at frame (sum of output_generated of the blocks before it) of every output plane.  A pitch of 0 means that side is
+ * interleaved (both 0: the interleaved entry itself); a pitch may exceed the frames used and need not be a multiple of anything — what lies
+ * between a plane's last written frame and the next plane is not touched.  Gathered blocks read and write the planes as they come (the
+ * general kernel, and the history roll); a block the interleaved schedule makes as its single call is resampleProcessPlanarDevice /
+ * resampleProcessAndFlushPlanarDevice at the block's offset into the planes.  Return value and failure contract as above. */
+int resampleProcessSchedulePlanarDevice (Resample *cxt, int numBlocks, const artsample_t *d_input, long inputPitch, const int *numInputFrames,
+                                         artsample_t *d_output, long outputPitch, const int *numOutputFrames, const double *ratios,
+                                         int flushLast, ResampleResult *results);
+/* The block schedules of MANY streams, one launch: N drifting streams with K buffered blocks each pay one launch floor instead of N (a schedule
+ * per stream) or K (a batch per block index).  For every i, results [i] (numBlocks [i] entries), the samples in d_outputs [i], the context's
+ * state afterwards (position, flags, history, resampleHipLastKernel, resampleHipLastGathered, resampleHipCutInvariantFallbacks) and
+ * blocksMade [i] are exactly those of
+ *     blocksMade [i] = resampleProcessSchedulePlanarDevice (cxts [i], numBlocks [i], d_inputs [i], inputPitches [i], numInputFrames [i],
+ *                                                           d_outputs [i], outputPitches [i], numOutputFrames [i], ratios [i], flushLast [i], results [i]);
+ * (the interleaved entry: every pitch 0).  A NULL pitch array: every item interleaved on that side; flushLast may be NULL: none;
+ * numBlocks [i] <= 0 makes nothing (blocksMade [i] = 0); a cap too small ends that stream's schedule only.  A context may appear only once.
+ * A context shares launches if it is on the stream and device of cxts [0], not sharded, not in strict order and has timing off; of its blocks
+ * those the single schedule would gather into runs.  The call goes in rounds: every live stream contributes its next run of gatherable blocks,
+ * the round's runs go out together — one launch per kernel variant (channel group, interpolation, accumulator, taps class), every run cut
+ * into the tiles of its own launch, the history rolls riding along, one table upload (the table lives with cxts [0]: no allocation once warm)
+ * — then every stream whose next block is not gatherable makes it as its single call, and so on.  When every block of every stream is
+ * gatherable the whole call is one launch per kernel variant.  A context that shares no launch is its own single schedule call.
+ * Returns the number of launches enqueued, a single call or single schedule made on the side counting as one; 0 for n <= 0 or nothing to do;
+ * -1 with nothing enqueued and nothing counted if a context is NULL or appears twice or a numInputFrames [i][k] is negative; -1 if a launch
+ * failed (counted once in artamdErrorCount): every stream of the failed shared launch stands exactly where it stood before its run of that
+ * launch, that run's results are { 0, 0 }, blocksMade [i] counts the blocks made before it, no later block of any stream is made, and blocks
+ * made before the failure keep their results.  Asynchronous like the single call. */
+int resampleProcessScheduleBatchInterleavedDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_inputs, const int *const *numInputFrames,
+        artsample_t *const *d_outputs, const int *const *numOutputFrames, const double *const *ratios,
+        const int *flushLast, ResampleResult *const *results, int *blocksMade);
+int resampleProcessScheduleBatchPlanarDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *const *numInputFrames,
+        artsample_t *const *d_outputs, const long *outputPitches, const int *const *numOutputFrames,
+        const double *const *ratios, const int *flushLast, ResampleResult *const *results, int *blocksMade);
 /* planar device buffers: channel c at d_input + c*inputPitch (in samples), likewise output; a pitch of 0 on either side means that side
  * is interleaved.  Big calls are transposed through the context's interleaved staging on the device (the matrix-core kernels read
  * interleaved frames): the same samples as the interleaved entry point's, bit for bit */

@@ -149,6 +149,7 @@ def _bind(width):
         "biquadBankApplyBatchInterleavedDevice": (C.c_int, [ptr, C.c_int, ptr, ptr]),
         "biquadBankApplyPlanarDevice": (None, [ptr, ptr, C.c_long, C.c_int]),
         "biquadBankApplyBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr]),
+        "biquadBankApplyClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, C.c_int]),
         "biquadBankReset": (None, [ptr]),
         "decimateHipSetStream": (None, [DP, ptr]),
         "decimateProcessInterleavedLEDevice": (None, [DP, ptr, C.c_int, ptr]),
@@ -778,10 +779,23 @@ def _bind(width):
             raise RuntimeError("biquadBankApplyBatchPlanarDevice failed")
         return rc
 
+    def biquad_clips_planar_device(banks, d_bufs, pitches, frames, from_start=False):
+        """biquadBankApplyClipsPlanarDevice: biquad_batch_planar_device whose long time-parallel calls share launches as well (one copy
+        launch and three launches per section count and layout, whatever the number of banks).  from_start: every bank as after its
+        reset(), without a copy per bank.  Returns the launch count (raises if the call returned -1)."""
+        n = len(banks)
+        rc = lib().biquadBankApplyClipsPlanarDevice(
+            (C.c_void_p * n)(*[b.p for b in banks]), n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_bufs]),
+            None if pitches is None else (C.c_long * n)(*[int(q) for q in pitches]), (C.c_int * n)(*[int(v) for v in frames]),
+            1 if from_start else 0)
+        if rc < 0:
+            raise RuntimeError("biquadBankApplyClipsPlanarDevice failed")
+        return rc
+
     class ClipFilter:
         """Whole clips, channels-first, through a cascade of one to four second-order sections, IN PLACE: x [B, C, T] (or [C, T]) on the
-        GPU in, the same tensor out — one biquadBankApplyBatchPlanarDevice call on the tensor's own rows, no copy of the samples on the
-        way.  sections: [("lowpass" | "highpass", frequency), ...] (frequency as biquad_lowpass / biquad_highpass take it: a fraction
+        GPU in, the same tensor out — one biquadBankApplyClipsPlanarDevice call on the tensor's own rows, the clips' long runs in
+        shared launches (`launches`: how many the last call enqueued).  sections: [("lowpass" | "highpass", frequency), ...] (frequency as biquad_lowpass / biquad_highpass take it: a fraction
         of the sample rate; gain 1.0); ART's -p is two low-passes at one frequency.  Clip i is what a fresh bank makes of
         x[i, :, :lengths[i]]; x[i, :, lengths[i]:] is not touched.  Holds a pool of up to max_batch banks, reset for every call, on the
         caller's current torch stream; a larger batch is made max_batch clips at a time.  Takes and gives what ClipResampler and
@@ -800,6 +814,7 @@ def _bind(width):
                 for c in range(channels):
                     L.biquad_init(C.byref(self._sections[c * self.nsections + s]), C.byref(co), 1.0)
             self.pool = []
+            self.launches = 0
 
         def close(self):
             for b in self.pool:
@@ -826,12 +841,12 @@ def _bind(width):
                 b.set_stream(stream)
             size, xp = x.element_size(), x.data_ptr()
             pitch = x.stride(1) if Cn > 1 else 0                  # (one channel: the same call in either layout)
+            self.launches = 0
             for b0 in range(0, B, self.max_batch):
                 idx = range(b0, min(B, b0 + self.max_batch))
                 pool = self.pool[:len(idx)]
-                for b in pool:
-                    b.reset()
-                biquad_batch_planar_device(pool, [xp + i * x.stride(0) * size for i in idx], [pitch] * len(idx), [lengths[i] for i in idx])
+                self.launches += biquad_clips_planar_device(pool, [xp + i * x.stride(0) * size for i in idx], [pitch] * len(idx),
+                                                            [lengths[i] for i in idx], from_start=True)
             return whole
 
     class Stretcher:

@@ -378,6 +378,42 @@ int arthip_biquad_spec (Biquad *d_sections, int C, int S, const art_s *d_in, int
  * its stores are whole too where the two planes' addresses agree modulo 16 */
 int arthip_biquad_spec_planar (Biquad *d_sections, int C, int S, const art_s *d_in, long in_pitch, art_s *d_out, long out_pitch, int frames,
                                int L, int W, void *d_states, int *d_first_bad, unsigned int *d_repairs, void *stream);
+/* Many banks' time-parallel calls in shared launches (biquadBankApplyClipsPlanarDevice).  An item is one bank's call, with the
+ * chunk length, chunk count and warm-up its single call would use; a class is the items of one section count and one layout. */
+typedef struct {
+    const Biquad *from;                  /* coefficients and carried-in state: the bank's d_sections, or d_sections0 (fromStart) */
+    Biquad *sections;                    /* the bank's d_sections: the final state goes here */
+    const art_s *in;                     /* the call's frames, set aside in the shared scratch */
+    art_s *out;                          /* the caller's buffer */
+    long in_stride, out_stride;          /* a planar class: samples between planes; an interleaved one: values between frames */
+    void *states;                        /* arthip_biquad_spec_scratch () bytes: starts, ends, flags, as the single call lays them out */
+    int *first_bad;                      /* the bank's own */
+    unsigned int *repairs;               /* the bank's own */
+    long task0;                          /* first (chunk, channel) task of the item in the class's flattened task space */
+    int chan0;                           /* first channel of the item among the class's channels (the commit launch's threads) */
+    int C, K, L, W, frames;
+} ArtBqClip;
+typedef struct {
+    int S, planar;
+    int count, channels;                 /* items; channels of all of them */
+    long tasks;                          /* (chunk, channel) tasks of all of them */
+    size_t offset;                       /* of the class's items in the table (16-byte aligned) */
+} ArtBqClipClass;
+/* spec, check and commit launch of one class; 0 or -1 */
+int arthip_biquad_clips_launch (const ArtBqClipClass *cls, const void *d_table, void *stream);
+typedef struct {                         /* one strided copy of a grouped copy launch; everything in 4-byte words */
+    const unsigned int *src;
+    unsigned int *dst;
+    long src_pitch, dst_pitch;           /* between row starts */
+    long width, rows;                    /* words per row */
+    long groups;                         /* tasks per row: (width + 3) / 4 + 1 (16-byte groups counted from the boundary before the row) */
+    long task0;                          /* first task of the item: the sum of rows * groups of the items before it */
+} ArtCopyRows;
+int arthip_copy_rows_launch (const void *d_items, int n, long tasks, void *stream);
+/* biquadBankApplyClipsPlanarDevice with its own bound on the bytes set aside per round (roundBytes > 0; else the library's,
+ * BQ_CLIPS_ROUND_BYTES): how the tests make a small batch take several rounds — pcm_host.c */
+int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches, const int *numFrames,
+                                int fromStart, long roundBytes);
 /* ---- time stretcher (stretch_kernels.hip) ---- */
 typedef struct {
     art_s *ring [2][2];                  /* [stage][ping-pong] input rings, `room` values each */

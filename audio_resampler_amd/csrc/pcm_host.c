@@ -316,6 +316,10 @@ struct artamd_biquad_bank {
     art_s *d_slice; size_t slice_cap;
     unsigned long batch_stamp;           /* the last batch call that named this bank */
     void *d_batch; size_t batch_cap;     /* a batch call's table, when this bank leads it */
+    /* biquadBankApplyClipsPlanarDevice, when this bank leads it: the table, the round's inputs set aside, the round's chunk states */
+    void *d_clips; size_t clips_cap;
+    void *d_clips_tmp; size_t clips_tmp_cap;
+    void *d_clips_spec; size_t clips_spec_cap;
 };
 
 BiquadBank *biquadBankCreate (const Biquad *sections, int numChannels, int numSections)
@@ -572,7 +576,7 @@ void biquadBankFree (BiquadBank *b)
     if (b->ev_parent) arthip_event_destroy (b->ev_parent);
     free (b->shards); free (b->shard_first); free (b->ev_shard);
     arthip_free (b->d_sections); arthip_free (b->d_sections0); arthip_free (b->d_tmp); arthip_free (b->d_spec); arthip_free (b->d_repairs); arthip_free (b->d_first_bad); arthip_free (b->d_slice);
-    arthip_free (b->d_batch);
+    arthip_free (b->d_batch); arthip_free (b->d_clips); arthip_free (b->d_clips_tmp); arthip_free (b->d_clips_spec);
     LEAVE_DEVICE (b);
     free (b);
 }
@@ -1215,6 +1219,207 @@ int biquadBankApplyBatchPlanarDevice (BiquadBank *const *banks, int n, artsample
 }
 
 int artamd_biquad_batch_serial_max (void) { return BQ_BATCH_SERIAL_MAX; }
+
+/* ------------------------------------------------------------------------------------------
+ * Many banks' whole clips: the time-parallel form in shared launches
+ *
+ * The batch entry above leaves a long time-parallel call to its single call: four enqueues per bank, each a few waves wide.  Here
+ * those calls are gathered: every item keeps the chunk length, chunk count and warm-up of its single call (so the chunk cuts, the
+ * repairs and the bits are that call's), and the items of one (section count, layout) class share one spec, one check and one
+ * commit launch (pcm_kernels.hip, bq_clips_spec_kernel).  One grouped copy launch sets every item's frames aside — a planar
+ * item's planes at their own addresses modulo 16, as biquadBankApplyPlanarDevice places them — and, with fromStart, puts the sections
+ * of the banks that do not go through the gathered launches back to their first state.  What the batch entry gathers goes to it, in one
+ * call; sharded banks and banks on another stream or device are single calls, and so is a time-parallel call that is the only one of
+ * its list.
+ *
+ * The copies and the chunk states live with banks [0], shared by the items.  Items are taken in list order in rounds whose copies
+ * stay under BQ_CLIPS_ROUND_BYTES (an item beyond it is a round of its own): a round's launches are
+ * 1 copy + 3 per present class, at most 1 + 3 * 8.
+ * ---------------------------------------------------------------------------------------- */
+#define BQ_CLIPS_ROUND_BYTES ((size_t) 128 << 20)  /* half of the 256 MiB the chip's last-level cache holds: a round's copy and the
+                                                    * part of the callers' buffers it is written back to fit in it together, and
+                                                    * 128 MiB is some 380 one-second stereo clips of 4-byte samples — 760 planes of
+                                                    * dozens to hundreds of chunks, many waves per SIMD.  The scratch of a call stays
+                                                    * under 1.5 x (this + its chunk states, at most half as much again) whatever the batch */
+#define BQ_CLIP_CLASSES 8                          /* section counts 1-4 x (interleaved, planar) */
+
+enum { CLIP_SKIP, CLIP_SIDE, CLIP_SERIAL, CLIP_GATHERED };
+typedef struct {
+    int kind, round, cls, slot, copy_slot, chan0, K, L;
+    long task0, copy_task0, dense, pitch;
+    size_t lead, tmp_at, spec_at;        /* samples before the first frame in its 16-byte group; of the item's first frame in the copy
+                                          * buffer (samples); of its chunk states in the state buffer (bytes) */
+} ClipPlan;
+typedef struct {
+    int ncopy; long copy_tasks; size_t copy_offset;
+    size_t tmp_bytes, spec_bytes;
+    ArtBqClipClass cls [BQ_CLIP_CLASSES];
+} ClipRound;
+
+static void clip_copy_item (ArtCopyRows *it, const void *src, long src_pitch, void *dst, long dst_pitch, long width, long rows, long task0)
+{
+    it->src = src; it->dst = dst; it->src_pitch = src_pitch; it->dst_pitch = dst_pitch;
+    it->width = width; it->rows = rows; it->groups = (width + 3) / 4 + 1; it->task0 = task0;
+}
+
+int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches, const int *numFrames,
+                                int fromStart, long roundBytes)
+{
+    if (n <= 0) return 0;
+    if (artamd_batch_distinct ((const void *const *) banks, n, bank_stamp, "biquad clips", "bank")) return -1;
+    const size_t bound = roundBytes > 0 ? (size_t) roundBytes : BQ_CLIPS_ROUND_BYTES;
+    const long q = 16 / (long) sizeof (art_s), wps = (long)(sizeof (art_s) / 4);
+
+    BiquadBank *lead = banks [0];
+    ClipPlan *plan = calloc ((size_t) n, sizeof (ClipPlan));
+    ClipRound *rounds = calloc ((size_t) n + 1, sizeof (ClipRound));
+    BiquadBank **sbanks = malloc (sizeof (BiquadBank *) * (size_t) n);
+    artsample_t **sbufs = malloc (sizeof (artsample_t *) * (size_t) n);
+    long *spitches = malloc (sizeof (long) * (size_t) n);
+    int *sframes = malloc (sizeof (int) * (size_t) n);
+    unsigned char *table = NULL;
+    int launches = 0, rc = -1, nrounds = 1, nserial = 0;
+    if (!plan || !rounds || !sbanks || !sbufs || !spitches || !sframes) { pcm_fail ("biquad clips: out of host memory"); goto out; }
+
+    /* a lone time-parallel call gains nothing from the table (measured, profiles/biquad_clips.txt: 4 us behind its single call):
+     * it is made as that call */
+    int ngathered = 0;
+    for (int i = 0; i < n; ++i) {
+        const BiquadBank *b = banks [i];
+        const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
+        if (!b->nshards && b->stream == lead->stream && b->device == lead->device && L && numFrames [i] >= 2 * L && numFrames [i] > BQ_BATCH_SERIAL_MAX) ++ngathered;
+    }
+
+    /* every call's route; the calls these launches cannot take are made as their single calls, in list order */
+    for (int i = 0; i < n; ++i) {
+        BiquadBank *b = banks [i];
+        ClipPlan *p = &plan [i];
+        const int frames = numFrames [i];
+        const int chunk = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
+        p->pitch = pitches && b->C > 1 ? pitches [i] : 0;                    /* (one channel: the same call in either layout) */
+        if (b->nshards || b->stream != lead->stream || b->device != lead->device ||
+            (ngathered == 1 && chunk && frames >= 2 * chunk && frames > BQ_BATCH_SERIAL_MAX)) {
+            p->kind = CLIP_SIDE;
+            if (fromStart) biquadBankReset (b);
+            if (frames > 0) { biquadBankApplyPlanarDevice (b, d_buffers [i], p->pitch, frames); ++launches; }
+            continue;
+        }
+        const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
+        if (frames > 0 && L && frames >= 2 * L && frames > BQ_BATCH_SERIAL_MAX) {
+            /* the set-aside copy: as the single calls place theirs, + `lead` samples in front so that it starts where the caller's
+             * buffer does modulo 16 bytes (an interleaved item's copy then moves 16 bytes at a time too) */
+            p->kind = CLIP_GATHERED;
+            p->L = L; p->K = (frames + L - 1) / L;
+            p->lead = (size_t)((uintptr_t) d_buffers [i] & 15) / sizeof (art_s);
+            p->dense = p->pitch ? frames + (((p->pitch - frames) % q) + q) % q : (long) frames * b->C;      /* planar: = pitch modulo q, >= frames */
+            const size_t samples = ((p->pitch ? (size_t) p->dense * b->C : (size_t) p->dense) + p->lead + (size_t)(q - 1)) & ~(size_t)(q - 1);
+            const size_t states = (arthip_biquad_spec_scratch (b->C, b->S, frames, L) + 255) & ~(size_t) 255;
+            ClipRound *r = &rounds [nrounds - 1];
+            if (r->tmp_bytes && r->tmp_bytes + samples * sizeof (art_s) > bound) r = &rounds [nrounds++];
+            p->round = (int)(r - rounds);
+            p->tmp_at = r->tmp_bytes / sizeof (art_s) + p->lead; r->tmp_bytes += samples * sizeof (art_s);
+            p->spec_at = r->spec_bytes; r->spec_bytes += states;
+            ArtBqClipClass *c = &r->cls [p->cls = 2 * (b->S - 1) + (p->pitch != 0)];
+            c->S = b->S; c->planar = p->pitch != 0;
+            p->slot = c->count++; p->task0 = c->tasks; p->chan0 = c->channels;
+            c->tasks += (long) b->C * p->K; c->channels += b->C;
+            p->copy_slot = r->ncopy++; p->copy_task0 = r->copy_tasks;
+            r->copy_tasks += p->pitch ? (long) b->C * (((long) frames * wps + 3) / 4 + 1) : (p->dense * wps + 3) / 4 + 1;
+            continue;
+        }
+        p->kind = frames > 0 ? CLIP_SERIAL : CLIP_SKIP;
+        if (frames > 0) { sbanks [nserial] = b; sbufs [nserial] = d_buffers [i]; spitches [nserial] = p->pitch; sframes [nserial] = frames; ++nserial; }
+        if (fromStart) {                                                     /* its sections are put back by the first round's copy launch */
+            p->copy_slot = rounds [0].ncopy++; p->copy_task0 = rounds [0].copy_tasks;
+            rounds [0].copy_tasks += ((long)(sizeof (Biquad) / 4) * b->C * b->S + 3) / 4 + 1;
+        }
+    }
+
+    /* the table: per round its copies, then its classes' items; 16-byte aligned slices */
+    size_t bytes = 0, tmp_need = 0, spec_need = 0;
+    for (int r = 0; r < nrounds; ++r) {
+        rounds [r].copy_offset = bytes;
+        bytes += (sizeof (ArtCopyRows) * (size_t) rounds [r].ncopy + 15) & ~(size_t) 15;
+        for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
+            rounds [r].cls [k].offset = bytes;
+            bytes += (sizeof (ArtBqClip) * (size_t) rounds [r].cls [k].count + 15) & ~(size_t) 15;
+        }
+        if (rounds [r].tmp_bytes > tmp_need) tmp_need = rounds [r].tmp_bytes;
+        if (rounds [r].spec_bytes > spec_need) spec_need = rounds [r].spec_bytes;
+    }
+    if (!bytes && !nserial) { rc = launches; goto out; }
+
+    {
+        ENTER_DEVICE (lead);
+        rc = 0;
+        if (bytes) {
+            table = calloc (1, bytes);
+            lead->d_clips = arthip_grow (lead->d_clips, &lead->clips_cap, bytes);
+            if (tmp_need) lead->d_clips_tmp = arthip_grow (lead->d_clips_tmp, &lead->clips_tmp_cap, tmp_need);
+            if (spec_need) lead->d_clips_spec = arthip_grow (lead->d_clips_spec, &lead->clips_spec_cap, spec_need);
+            if (!table || !lead->d_clips || (tmp_need && !lead->d_clips_tmp) || (spec_need && !lead->d_clips_spec)) {
+                pcm_fail ("biquad clips: out of memory for the table or the scratch (nothing of the gathered calls launched)");
+                rc = -1;
+            }
+        }
+        for (int i = 0; i < n && !rc && bytes; ++i) {
+            const ClipPlan *p = &plan [i];
+            BiquadBank *b = banks [i];
+            if (p->kind == CLIP_SIDE) continue;
+            if (p->kind != CLIP_GATHERED) {
+                if (fromStart)
+                    clip_copy_item ((ArtCopyRows *)(table + rounds [0].copy_offset) + p->copy_slot, b->d_sections0, 0, b->d_sections, 0,
+                                    (long)(sizeof (Biquad) / 4) * b->C * b->S, 1, p->copy_task0);
+                continue;
+            }
+            const ClipRound *r = &rounds [p->round];
+            art_s *const aside = (art_s *) lead->d_clips_tmp + p->tmp_at;
+            if (p->pitch) clip_copy_item ((ArtCopyRows *)(table + r->copy_offset) + p->copy_slot, d_buffers [i], p->pitch * wps, aside, p->dense * wps,
+                                          (long) numFrames [i] * wps, b->C, p->copy_task0);
+            else clip_copy_item ((ArtCopyRows *)(table + r->copy_offset) + p->copy_slot, d_buffers [i], 0, aside, 0, p->dense * wps, 1, p->copy_task0);
+            ArtBqClip *it = (ArtBqClip *)(table + r->cls [p->cls].offset) + p->slot;
+            it->from = fromStart ? b->d_sections0 : b->d_sections; it->sections = b->d_sections;
+            it->in = aside; it->out = d_buffers [i];
+            it->in_stride = p->pitch ? p->dense : b->C; it->out_stride = p->pitch ? p->pitch : b->C;
+            it->states = (char *) lead->d_clips_spec + p->spec_at;
+            it->first_bad = b->d_first_bad; it->repairs = b->d_repairs;
+            it->task0 = p->task0; it->chan0 = p->chan0;
+            it->C = b->C; it->K = p->K; it->L = p->L; it->W = b->warmup; it->frames = numFrames [i];
+        }
+        if (!rc && bytes && arthip_table_upload (table, bytes, lead->d_clips, lead->stream)) {
+            pcm_fail ("biquad clips: the table could not be uploaded (nothing of the gathered calls launched)");
+            rc = -1;
+        }
+        for (int r = 0; r < nrounds && !rc; ++r) {
+            const ClipRound *rd = &rounds [r];
+            if (rd->ncopy) {
+                if (arthip_copy_rows_launch ((const char *) lead->d_clips + rd->copy_offset, rd->ncopy, rd->copy_tasks, lead->stream)) { pcm_fail ("biquad clips: launch failed"); rc = -1; break; }
+                ++launches;
+            }
+            if (r == 0 && nserial) {               /* what the batch entry gathers, there (behind the copy launch: their sections are put back) */
+                const int made = artamd_biquad_batch_planar (sbanks, nserial, sbufs, spitches, sframes, 0, -1);
+                if (made < 0) { rc = -1; break; }
+                launches += made;
+            }
+            for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
+                if (!rd->cls [k].count) continue;
+                if (arthip_biquad_clips_launch (&rd->cls [k], lead->d_clips, lead->stream)) { pcm_fail ("biquad clips: launch failed"); rc = -1; break; }
+                launches += 3;
+            }
+        }
+        if (!rc) rc = launches;
+        LEAVE_DEVICE (lead);
+    }
+out:
+    free (plan); free (rounds); free (sbanks); free (sbufs); free (spitches); free (sframes); free (table);
+    return rc;
+}
+
+int biquadBankApplyClipsPlanarDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches, const int *numFrames,
+                                      int fromStart)
+{
+    return artamd_biquad_clips_planar (banks, n, d_buffers, pitches, numFrames, fromStart, 0);
+}
 
 long decimateHipClipped (Decimate *cxt)
 {

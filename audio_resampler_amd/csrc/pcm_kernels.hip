@@ -1592,6 +1592,181 @@ void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_fram
     }
 }
 
+// One task of the speculative pass: chunk k of channel c of a call (C channels, K chunks of L frames, warm-up W) from `sections`.
+// The one body of the single call's kernel (biquad_spec_kernel) and of the gathered one (bq_clips_spec_kernel).
+template <int S, bool PLANAR>
+__device__ __forceinline__ void spec_task (const Biquad *sections, int c, int k, int K, int L, int W, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
+                                           spec_stride<PLANAR> out_stride, int frames, SpecState *starts, SpecState *ends)
+{
+    const int first = k * L, last = min (first + L, frames);
+
+    SectionRegs r [S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) load_section (r [s], sections [(size_t) c * S + s]);
+
+    const int begin = first - S * W;
+    if (begin > 0) {
+        // speculative start: silence behind every section
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { r [s].x [q] = 0; r [s].y [q] = 0; }
+        spec_warm_up<S, PLANAR> (r, in, stride, c, begin, W);
+    }
+    else if (first > 0)
+        // close to the start of the call: from the carried-in state through frames [0, first) — exact, nothing stored
+        spec_run<S, S, false, PLANAR> (r, in, stride, nullptr, 0, c, 0, first);
+
+    SpecState st [S];
+    get_state<S> (st, r);
+#pragma unroll
+    for (int s = 0; s < S; ++s) starts [((size_t) c * K + k) * S + s] = st [s];
+
+    spec_run<S, S, true, PLANAR> (r, in, stride, out, out_stride, c, first, last);
+
+    get_state<S> (st, r);
+#pragma unroll
+    for (int s = 0; s < S; ++s) ends [((size_t) c * K + k) * S + s] = st [s];
+}
+
+// biquad_check_kernel's body: one chunk boundary checked: flags [c][k] = chunk k did not start from the state chunk k-1 left; first_bad [c] = the first such k
+// of the channel (stays at its armed value, beyond any chunk count, when there is none).
+template <int S>
+__device__ __forceinline__ void check_task (int c, int k, int K, const SpecState *starts, const SpecState *ends, unsigned char *bad, int *first_bad)
+{
+    if (k == 0) return;
+    const bool ok = same_state<S> (starts + ((size_t) c * K + k) * S, ends + ((size_t) c * K + k - 1) * S);
+    bad [(size_t) c * K + k] = ok ? 0 : 1;
+    if (!ok) atomicMin (first_bad + c, k);
+}
+
+// biquad_commit_kernel's body, with the sections read from `from` and stored to `sections` (the single call: the same array):
+// one channel committed: repairs from the first mismatch (rare: recomputes from the exact state until it rejoins a
+// speculative trajectory — in the worst case everything, serially), then the channel's final state goes into `sections`
+// repairs: running count of
+// chunks recomputed (diagnostics).  first_bad is re-armed for the next call.
+template <int S, bool PLANAR>
+__device__ __forceinline__ void commit_channel (const Biquad *from, Biquad *sections, int c, int K, int L, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
+                                                spec_stride<PLANAR> out_stride, int frames,
+                                                const SpecState *starts, SpecState *ends, const unsigned char *bad, int *first_bad, unsigned int *repairs)
+{
+    const SpecState *st = starts + (size_t) c * K * S;
+    SpecState *en = ends + (size_t) c * K * S;
+    const unsigned char *flags = bad + (size_t) c * K;
+
+    SectionRegs r [S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) load_section (r [s], from [(size_t) c * S + s]);
+
+    int k = first_bad [c];
+    first_bad [c] = INT_MAX;
+    unsigned int redone = 0;
+    while (k < K) {
+        // chunk k again, from the exact state its predecessor left
+        put_state<S> (r, en + (size_t)(k - 1) * S);
+        const int first = k * L, last = min (first + L, frames);
+        spec_run<S, S, true, PLANAR> (r, in, stride, out, out_stride, c, first, last);
+        SpecState now [S];
+        get_state<S> (now, r);
+#pragma unroll
+        for (int s = 0; s < S; ++s) en [(size_t) k * S + s] = now [s];
+        ++redone;
+        if (k + 1 >= K) break;
+        if (same_state<S> (now, st + (size_t)(k + 1) * S)) {
+            // rejoined the speculative trajectory: everything up to the next recorded mismatch stands
+            int next = k + 2;
+            while (next < K && !flags [next]) ++next;
+            k = next;
+        }
+        else ++k;
+    }
+    if (redone) atomicAdd (repairs, redone);
+
+    put_state<S> (r, en + (size_t)(K - 1) * S);
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        // store_section, with the index counted on from `from`'s (store_section counts on from the index of the section it writes)
+        Biquad &f = sections [(size_t) c * S + s];
+        const int i = from [(size_t) c * S + s].index + frames;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { f.x [(i - k) & 3] = r [s].x [k]; f.y [(i - k) & 3] = r [s].y [k]; }
+        f.index = i;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Many banks' TIME-PARALLEL calls in shared launches (biquadBankApplyClipsPlanarDevice): biquad_spec_kernel, biquad_check_kernel and
+// biquad_commit_kernel over a table of items (ArtBqClip), one item per call.  The task space is the items' (chunk, channel) spaces
+// laid end to end; a thread finds its item by binary search over the items' first tasks (item_of) and runs the single call's body
+// with the item's own C, K, L, W and frames: the chunk cuts, and so the bits, the repairs and the final state, are the single
+// call's.  Lanes of different items (different L and K) share a wave.  One instantiation per (section count, layout).
+// ---------------------------------------------------------------------------------------------------
+template <int S, bool PLANAR>
+__global__ __launch_bounds__ (256)
+void bq_clips_spec_kernel (const ArtBqClip *items, int n, long tasks)
+{
+    const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (task >= tasks) return;
+    const ArtBqClip &a = item_of (items, n, task);
+    const long t = task - a.task0;
+    const int C = a.C, K = a.K;
+    const int c = PLANAR ? (int)(t / K) : (int)(t % C), k = PLANAR ? (int)(t % K) : (int)(t / C);
+    SpecState *const starts = (SpecState *) a.states, *const ends = starts + (size_t) C * K * S;
+    spec_task<S, PLANAR> (a.from, c, k, K, a.L, a.W, a.in, (spec_stride<PLANAR>) a.in_stride, a.out, (spec_stride<PLANAR>) a.out_stride, a.frames, starts, ends);
+}
+
+template <int S>
+__global__ __launch_bounds__ (256)
+void bq_clips_check_kernel (const ArtBqClip *items, int n, long tasks)
+{
+    const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (task >= tasks) return;
+    const ArtBqClip &a = item_of (items, n, task);
+    const long t = task - a.task0;
+    const int C = a.C, K = a.K;
+    SpecState *const starts = (SpecState *) a.states, *const ends = starts + (size_t) C * K * S;
+    check_task<S> ((int)(t / K), (int)(t % K), K, starts, ends, (unsigned char *)(ends + (size_t) C * K * S), a.first_bad);
+}
+
+// one thread per (item, channel): the item is the last whose first channel (chan0) is not beyond the thread's
+template <int S, bool PLANAR>
+__global__ __launch_bounds__ (64)
+void bq_clips_commit_kernel (const ArtBqClip *items, int n, int channels)
+{
+    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= channels) return;
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (items [mid].chan0 <= ch) lo = mid; else hi = mid - 1; }
+    const ArtBqClip &a = items [lo];
+    const int C = a.C, K = a.K;
+    SpecState *const starts = (SpecState *) a.states, *const ends = starts + (size_t) C * K * S;
+    commit_channel<S, PLANAR> (a.from, a.sections, ch - a.chan0, K, a.L, a.in, (spec_stride<PLANAR>) a.in_stride, a.out, (spec_stride<PLANAR>) a.out_stride, a.frames,
+                               starts, ends, (const unsigned char *)(ends + (size_t) C * K * S), a.first_bad, a.repairs);
+}
+
+// Many strided copies in one launch (the gathered calls' inputs set aside, and banks' sections put back to their first state): item
+// = rows of `width` 4-byte words, row starts src_pitch / dst_pitch words apart.  A task is one 16-byte group of a row, counted from
+// the 16-byte boundary at or before the row's SOURCE address: whole groups move as one 16-byte access where the destination is on a
+// boundary too (the set-aside planes are placed so), the rest word by word.
+__global__ __launch_bounds__ (256)
+void copy_rows_group_kernel (const ArtCopyRows *items, int n, long tasks)
+{
+    const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (task >= tasks) return;
+    const ArtCopyRows &a = item_of (items, n, task);
+    const long t = task - a.task0, row = t / a.groups, g = t - row * a.groups;
+    const unsigned int *const src = a.src + row * a.src_pitch;
+    unsigned int *const dst = a.dst + row * a.dst_pitch;
+    const long w0 = g * 4 - (long)(((uintptr_t) src >> 2) & 3), width = a.width;
+    if (w0 >= 0 && w0 + 4 <= width && !((uintptr_t)(dst + w0) & 15)) {
+        *reinterpret_cast<uint4 *> (dst + w0) = *reinterpret_cast<const uint4 *> (src + w0);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (w0 + j >= 0 && w0 + j < width) dst [w0 + j] = src [w0 + j];
+}
+
 // one little-endian integer sample (p: its first value byte) times g (reference decimator.c:416-450)
 __device__ __forceinline__ art_s decode_pcm (const unsigned char *p, int bits, art_s g)
 {
@@ -1902,6 +2077,35 @@ int arthip_biquad_batch_launch (const ArtBqClass *cls, const void *d_table, void
     case 3: hipLaunchKernelGGL (biquad_batch_pipe_kernel<3>, grid, block, lds, st, items, L, chunk_frames); break;
     default: hipLaunchKernelGGL (biquad_batch_pipe_kernel<4>, grid, block, lds, st, items, L, chunk_frames); break;
     }
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// the three launches of one (section count, layout) class of gathered time-parallel calls, from its slice of the uploaded table
+int arthip_biquad_clips_launch (const ArtBqClipClass *cls, const void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    const ArtBqClip *items = (const ArtBqClip *)((const char *) d_table + cls->offset);
+    const int n = cls->count, channels = cls->channels;
+    const long tasks = cls->tasks;
+    if (n <= 0) return 0;
+    if (cls->S < 1 || cls->S > MAX_CHAIN || tasks <= 0 || channels <= 0) return -1;
+    const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256), cgrid ((unsigned int)((channels + 63) / 64)), cblock (64);
+#define CLIPS_GO(SS, PL) do { \
+        hipLaunchKernelGGL ((bq_clips_spec_kernel<SS, PL>), grid, block, 0, st, items, n, tasks); \
+        hipLaunchKernelGGL (bq_clips_check_kernel<SS>, grid, block, 0, st, items, n, tasks); \
+        hipLaunchKernelGGL ((bq_clips_commit_kernel<SS, PL>), cgrid, cblock, 0, st, items, n, channels); } while (0)
+#define CLIPS_LAYOUT(SS) do { if (cls->planar) CLIPS_GO (SS, true); else CLIPS_GO (SS, false); } while (0)
+    switch (cls->S) { case 1: CLIPS_LAYOUT (1); break; case 2: CLIPS_LAYOUT (2); break; case 3: CLIPS_LAYOUT (3); break; default: CLIPS_LAYOUT (4); }
+#undef CLIPS_LAYOUT
+#undef CLIPS_GO
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// one launch of `n` strided copies (`tasks`: the sum of rows * groups over the items) from the uploaded table
+int arthip_copy_rows_launch (const void *d_items, int n, long tasks, void *stream)
+{
+    if (n <= 0 || tasks <= 0) return 0;
+    hipLaunchKernelGGL (copy_rows_group_kernel, dim3 ((unsigned int)((tasks + 255) / 256)), dim3 (256), 0, (hipStream_t) stream, (const ArtCopyRows *) d_items, n, tasks);
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 

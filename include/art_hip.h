@@ -335,6 +335,28 @@ void biquadBankApplyPlanarDevice (BiquadBank *bank, artsample_t *d_buffer, long 
  * appear only once", skipping numFrames [i] <= 0 and asynchronous operation as in the interleaved entry. */
 int biquadBankApplyBatchPlanarDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches,
                                       const int *numFrames);
+/* Whole clips of many banks: biquadBankApplyBatchPlanarDevice whose long time-parallel calls share launches too.  The samples in
+ * d_buffers [i], the state biquadBankRead (banks [i]) returns afterwards (index included) and the growth of biquadBankRepairs
+ * (banks [i]) are exactly those of biquadBankApplyPlanarDevice (banks [i], d_buffers [i], pitches ? pitches [i] : 0, numFrames [i]),
+ * preceded by biquadBankReset (banks [i]) when fromStart != 0 (no copy per bank is made for that: the gathered launches read the
+ * bank's first state where it lies, and one launch puts the other banks' sections back).  Pitches as in the batch entry: 0 for an
+ * interleaved item, a NULL array for "every item is", a one-channel bank the same call in either layout, any pitch and base.
+ * What the batch entry gathers (calls of up to 512 frames, calls shorter than two chunks, filters with no warm-up) goes to its serial
+ * launches, one per section count.  The calls it leaves to their single calls because they are time-parallel and long are gathered
+ * here: every call keeps the chunk length and warm-up of its single call, and the calls of one section count and one layout share
+ * one speculative, one check and one commit launch, behind one copy launch that sets every call's frames aside in scratch memory
+ * that lives with banks [0] (no bank grows scratch of its own through this entry).  The calls are taken in list order in rounds
+ * that set aside at most 128 MiB each (pcm_host.c: BQ_CLIPS_ROUND_BYTES; a larger call is a round of its own): 1 + 3 launches per
+ * class present in a round, at most 25.  Sharded banks and banks on another stream or device than banks [0] are single planar calls,
+ * in list order, after their own biquadBankReset when fromStart is set; so is a long time-parallel call that is the only one of the
+ * list (one clip: nothing to share).  numFrames [i] <= 0 is skipped; with fromStart the bank is
+ * still reset.  In place; the buffers of one call must not overlap (not checked).  Asynchronous on the stream of banks [0].
+ * Returns the number of kernel launches enqueued, counting each single call made on the side as one; 0 when n <= 0 or there was
+ * nothing to do; -1 with nothing enqueued if a bank appears twice or a pointer in banks is NULL; -1 if memory ran out or a launch
+ * failed (counted in artamdErrorCount): nothing is then promised about the buffers and the states of the banks of that round and
+ * of the rounds behind it. */
+int biquadBankApplyClipsPlanarDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches,
+                                      const int *numFrames, int fromStart);
 /* Puts every section's delay lines and index back to what biquadBankCreate was given (the bank keeps a copy on the device), so that
  * a pool of banks serves clip after clip without biquadBankFree / biquadBankCreate, as decimateHipReset does for decimators.
  * biquadBankRepairs is NOT reset.  Asynchronous on the bank's stream, behind every earlier call; no allocation; sharded banks too. */

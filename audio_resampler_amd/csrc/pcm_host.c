@@ -128,14 +128,16 @@ static int forget_length (const Biquad *f)
     return worst > SPEC_MAX_WARMUP ? 0 : worst + 16;
 }
 
-/* chunk length for `sections` sections with warm-up W each: the warm-up is recomputed work, keep it to about a quarter */
-static int spec_chunk (int sections, int W)
+/* The route rule: the chunk length if a call of `frames` frames through `sections` sections with warm-up W each (0: none forgets)
+ * takes the time-parallel form, else 0.  The warm-up is recomputed work: the chunk keeps it to about a quarter, and a call has two. */
+static int spec_chunk (int sections, int W, int frames)
 {
+    if (!W) return 0;
     int L = 4 * sections * W;
     L = (L + 7) & ~7;
     if (L < 128) L = 128;
     if (L > 8192) L = 8192;
-    return L;
+    return frames >= 2 * L ? L : 0;
 }
 
 static int spec_disabled (void)
@@ -224,10 +226,10 @@ static void biquad_run_host (Biquad *f, art_s *buffer, int n, int stride, int sa
     }
 
     const int W = (sample_form || spec_disabled ()) ? 0 : forget_length (f);
-    const int L = W ? spec_chunk (1, W) : 0;
+    const int L = spec_chunk (1, W, n);
     const art_s *d_result = host_scratch.d_in;
     int rc;
-    if (W && n >= 2 * L) {
+    if (L) {
         const size_t need = arthip_biquad_spec_scratch (1, 1, n, L);
         if (need > host_scratch.spec_cap) {
             arthip_free (host_scratch.d_spec);
@@ -399,50 +401,55 @@ void biquadBankSetStream (BiquadBank *b, void *stream)
     b->stream = stream;
 }
 
-/* a sharded bank's call in either layout (pitch 0: interleaved; else the planes of biquadBankApplyPlanarDevice, of which a shard
- * takes its run as the rows of its slice) */
+/* a sharded bank's call in either layout (pitch 0: interleaved; else the planes of biquadBankApplyPlanarDevice): every shard waits for
+ * the bank's stream, pulls its channel slice of the caller's buffer (peer-to-peer when it sits on another device), filters it in its
+ * own HBM and pushes it back; the bank's stream then waits for all of them */
 static void bank_sharded_call (BiquadBank *b, artsample_t *d_buffer, long pitch, int numFrames)
 {
-    {
-        /* every shard waits for the bank's stream, pulls its channel slice of the caller's buffer (peer-to-peer when it sits on
-         * another device), filters it in its own HBM and pushes it back; the bank's stream then waits for all of them */
-        const int prev = arthip_current_device (), wps = (int)(sizeof (art_s) / 4);
-        arthip_set_device (b->device);
-        arthip_event_record (b->ev_parent, b->stream);
-        for (int k = 0; k < b->nshards; ++k) {
-            BiquadBank *sh = b->shards [k];
-            const int first = b->shard_first [k], width = b->shard_first [k + 1] - first;
-            const size_t need = sizeof (art_s) * (size_t) numFrames * width;
-            arthip_set_device (sh->device);
-            arthip_stream_wait_event (sh->stream, b->ev_parent);
-            if (need > sh->slice_cap) {
-                arthip_sync (sh->stream);
-                arthip_free (sh->d_slice);
-                sh->slice_cap = need + need / 2;
-                if (!(sh->d_slice = arthip_malloc (sh->slice_cap))) {        /* (counted: this shard's channels stay unfiltered, as an ordinary bank's would) */
-                    sh->slice_cap = 0;
-                    pcm_fail ("sharded biquad bank: device allocation failed (a shard's channels left unfiltered)");
-                    arthip_event_record (b->ev_shard [k], sh->stream);
-                    continue;
-                }
-            }
-            if (pitch) {
-                artsample_t *planes = d_buffer + (size_t) first * pitch;
-                arthip_slice_copy (sh->d_slice, (size_t) numFrames * wps, planes, (size_t) pitch * wps, numFrames * wps, (size_t) width, sh->stream);
-                biquadBankApplyPlanarDevice (sh, sh->d_slice, numFrames, numFrames);
-                arthip_slice_copy (planes, (size_t) pitch * wps, sh->d_slice, (size_t) numFrames * wps, numFrames * wps, (size_t) width, sh->stream);
+    const int prev = arthip_current_device (), wps = (int)(sizeof (art_s) / 4);
+    arthip_set_device (b->device);
+    arthip_event_record (b->ev_parent, b->stream);
+    for (int k = 0; k < b->nshards; ++k) {
+        BiquadBank *sh = b->shards [k];
+        const int first = b->shard_first [k], width = b->shard_first [k + 1] - first;
+        const size_t need = sizeof (art_s) * (size_t) numFrames * width;
+        arthip_set_device (sh->device);
+        arthip_stream_wait_event (sh->stream, b->ev_parent);
+        if (need > sh->slice_cap) {
+            arthip_sync (sh->stream);
+            arthip_free (sh->d_slice);
+            sh->slice_cap = need + need / 2;
+            if (!(sh->d_slice = arthip_malloc (sh->slice_cap))) {        /* (counted: this shard's channels stay unfiltered, as an ordinary bank's would) */
+                sh->slice_cap = 0;
+                pcm_fail ("sharded biquad bank: device allocation failed (a shard's channels left unfiltered)");
                 arthip_event_record (b->ev_shard [k], sh->stream);
                 continue;
             }
-            arthip_slice_copy (sh->d_slice, (size_t) width * wps, d_buffer + first, (size_t) b->C * wps, width * wps, (size_t) numFrames, sh->stream);
-            biquadBankApplyInterleavedDevice (sh, sh->d_slice, numFrames);
-            arthip_slice_copy (d_buffer + first, (size_t) b->C * wps, sh->d_slice, (size_t) width * wps, width * wps, (size_t) numFrames, sh->stream);
-            arthip_event_record (b->ev_shard [k], sh->stream);
         }
-        arthip_set_device (b->device);
-        for (int k = 0; k < b->nshards; ++k) arthip_stream_wait_event (b->stream, b->ev_shard [k]);
-        if (prev >= 0) arthip_set_device (prev);
+        /* the slice as rows, dense in d_slice: a planar shard's planes, an interleaved one's frames of `width` channels */
+        artsample_t *const mine = d_buffer + (pitch ? (size_t) first * pitch : (size_t) first);
+        const int row = (pitch ? numFrames : width) * wps;
+        const size_t rows = pitch ? (size_t) width : (size_t) numFrames, apart = (size_t)(pitch ? pitch : b->C) * wps;
+        arthip_slice_copy (sh->d_slice, (size_t) row, mine, apart, row, rows, sh->stream);
+        biquadBankApplyPlanarDevice (sh, sh->d_slice, pitch ? numFrames : 0, numFrames);       /* (pitch 0: the interleaved call) */
+        arthip_slice_copy (mine, apart, sh->d_slice, (size_t) row, row, rows, sh->stream);
+        arthip_event_record (b->ev_shard [k], sh->stream);
     }
+    arthip_set_device (b->device);
+    for (int k = 0; k < b->nshards; ++k) arthip_stream_wait_event (b->stream, b->ev_shard [k]);
+    if (prev >= 0) arthip_set_device (prev);
+}
+
+/* a bank's call can go into launches on `lead`'s stream: an ordinary bank on the same stream and device */
+static int bank_shares_launch (const BiquadBank *b, const BiquadBank *lead) { return !b->nshards && b->stream == lead->stream && b->device == lead->device; }
+
+/* Where a call's input is set aside: *lead samples into the copy buffer, its planes the returned pitch apart (the caller's pitch
+ * modulo q, the samples of 16 bytes, and at least `frames`): the copy and its every plane start at the caller's address modulo 16. */
+static long aside_placement (const void *base, long pitch, int frames, size_t *lead)
+{
+    const long q = 16 / (long) sizeof (art_s);
+    *lead = (size_t)((uintptr_t) base & 15) / sizeof (art_s);
+    return frames + (((pitch - frames) % q) + q) % q;
 }
 
 /* the time-parallel form's buffers, each grown by half as much again when a call needs more: d_tmp for `samples` samples (the
@@ -469,9 +476,9 @@ void biquadBankApplyInterleavedDevice (BiquadBank *b, artsample_t *d_buffer, int
     if (numFrames <= 0) return;
     if (b->nshards) { bank_sharded_call (b, d_buffer, 0, numFrames); return; }
     ENTER_DEVICE (b);
-    const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
+    const int L = spec_chunk (b->S, b->warmup, numFrames);
 
-    if (L && numFrames >= 2 * L) {
+    if (L) {
         const size_t samples = (size_t) numFrames * b->C, need = arthip_biquad_spec_scratch (b->C, b->S, numFrames, L);
         if (bank_spec_reserve (b, samples, need)) {
             arthip_d2d (b->d_tmp, d_buffer, samples * sizeof (art_s), b->stream);
@@ -499,23 +506,20 @@ void biquadBankApplyPlanarDevice (BiquadBank *b, artsample_t *d_buffer, long pit
     if (b->C == 1) pitch = 0;
     if (!pitch) { biquadBankApplyInterleavedDevice (b, d_buffer, numFrames); return; }
     if (b->nshards) { bank_sharded_call (b, d_buffer, pitch, numFrames); return; }
-    const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
+    const int L = spec_chunk (b->S, b->warmup, numFrames);
 
-    if (L && numFrames >= 2 * L) {
+    if (L) {
         ENTER_DEVICE (b);
-        const long q = 16 / (long) sizeof (art_s);
-        const long dense = numFrames + (((pitch - numFrames) % q) + q) % q;                /* = pitch modulo q, >= numFrames */
-        const size_t lead = (size_t)((uintptr_t) d_buffer & 15) / sizeof (art_s);
+        size_t lead;
+        const long dense = aside_placement (d_buffer, pitch, numFrames, &lead);
         const size_t samples = (size_t) dense * b->C + lead, need = arthip_biquad_spec_scratch (b->C, b->S, numFrames, L);
-        if (bank_spec_reserve (b, samples, need) &&
+        const int done = bank_spec_reserve (b, samples, need) &&
             !arthip_copy2d (b->d_tmp + lead, (size_t) dense * sizeof (art_s), d_buffer, (size_t) pitch * sizeof (art_s),
                             (size_t) numFrames * sizeof (art_s), (size_t) b->C, b->stream) &&
             !arthip_biquad_spec_planar (b->d_sections, b->C, b->S, b->d_tmp + lead, dense, d_buffer, pitch, numFrames, L, b->warmup, b->d_spec,
-                                        b->d_first_bad, b->d_repairs, b->stream)) {
-            LEAVE_DEVICE (b);
-            return;
-        }
+                                        b->d_first_bad, b->d_repairs, b->stream);
         LEAVE_DEVICE (b);
+        if (done) return;
         bank_spec_unavailable ();
     }
     artamd_biquad_batch_planar (&b, 1, &d_buffer, &pitch, &numFrames, 0, INT_MAX);       /* (INT_MAX: never handed back to this call) */
@@ -1143,8 +1147,7 @@ int artamd_biquad_batch_planar (BiquadBank *const *banks, int n, artsample_t *co
         BiquadBank *b = banks [i];
         gathered [i] = 0;
         if (numFrames [i] <= 0) continue;
-        const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
-        if (b->nshards || b->stream != lead->stream || b->device != lead->device || (L && numFrames [i] >= 2 * L && numFrames [i] > serialMax)) {
+        if (!bank_shares_launch (b, lead) || (spec_chunk (b->S, b->warmup, numFrames [i]) && numFrames [i] > serialMax)) {
             biquadBankApplyPlanarDevice (b, d_buffers [i], pitches ? pitches [i] : 0, numFrames [i]);       /* (pitch 0: the interleaved call) */
             ++launches;
             continue;
@@ -1278,42 +1281,39 @@ int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *co
     long *spitches = malloc (sizeof (long) * (size_t) n);
     int *sframes = malloc (sizeof (int) * (size_t) n);
     unsigned char *table = NULL;
-    int launches = 0, rc = -1, nrounds = 1, nserial = 0;
+    int launches = 0, rc = -1, nrounds = 1, nserial = 0, ngathered = 0, only = -1;
     if (!plan || !rounds || !sbanks || !sbufs || !spitches || !sframes) { pcm_fail ("biquad clips: out of host memory"); goto out; }
 
-    /* a lone time-parallel call gains nothing from the table (measured, profiles/biquad_clips.txt: 4 us behind its single call):
-     * it is made as that call */
-    int ngathered = 0;
+    /* every call's route.  A lone time-parallel call gains nothing from the table (measured, profiles/biquad_clips.txt: 4 us behind
+     * its single call): it is made as that call */
     for (int i = 0; i < n; ++i) {
         const BiquadBank *b = banks [i];
-        const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
-        if (!b->nshards && b->stream == lead->stream && b->device == lead->device && L && numFrames [i] >= 2 * L && numFrames [i] > BQ_BATCH_SERIAL_MAX) ++ngathered;
+        ClipPlan *p = &plan [i];
+        const int frames = numFrames [i];
+        p->pitch = pitches && b->C > 1 ? pitches [i] : 0;                    /* (one channel: the same call in either layout) */
+        if (!bank_shares_launch (b, lead)) p->kind = CLIP_SIDE;
+        else if (frames > BQ_BATCH_SERIAL_MAX && (p->L = spec_chunk (b->S, b->warmup, frames)) != 0) { p->kind = CLIP_GATHERED; ++ngathered; only = i; }
+        else p->kind = frames > 0 ? CLIP_SERIAL : CLIP_SKIP;
     }
+    if (ngathered == 1) plan [only].kind = CLIP_SIDE;
 
-    /* every call's route; the calls these launches cannot take are made as their single calls, in list order */
+    /* the calls these launches cannot take are made as their single calls, in list order; the others get their places */
     for (int i = 0; i < n; ++i) {
         BiquadBank *b = banks [i];
         ClipPlan *p = &plan [i];
         const int frames = numFrames [i];
-        const int chunk = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
-        p->pitch = pitches && b->C > 1 ? pitches [i] : 0;                    /* (one channel: the same call in either layout) */
-        if (b->nshards || b->stream != lead->stream || b->device != lead->device ||
-            (ngathered == 1 && chunk && frames >= 2 * chunk && frames > BQ_BATCH_SERIAL_MAX)) {
-            p->kind = CLIP_SIDE;
+        if (p->kind == CLIP_SIDE) {
             if (fromStart) biquadBankReset (b);
             if (frames > 0) { biquadBankApplyPlanarDevice (b, d_buffers [i], p->pitch, frames); ++launches; }
             continue;
         }
-        const int L = b->warmup ? spec_chunk (b->S, b->warmup) : 0;
-        if (frames > 0 && L && frames >= 2 * L && frames > BQ_BATCH_SERIAL_MAX) {
-            /* the set-aside copy: as the single calls place theirs, + `lead` samples in front so that it starts where the caller's
-             * buffer does modulo 16 bytes (an interleaved item's copy then moves 16 bytes at a time too) */
-            p->kind = CLIP_GATHERED;
-            p->L = L; p->K = (frames + L - 1) / L;
-            p->lead = (size_t)((uintptr_t) d_buffers [i] & 15) / sizeof (art_s);
-            p->dense = p->pitch ? frames + (((p->pitch - frames) % q) + q) % q : (long) frames * b->C;      /* planar: = pitch modulo q, >= frames */
+        if (p->kind == CLIP_GATHERED) {
+            /* the set-aside copy: placed as the single call's (an interleaved item's copy then moves 16 bytes at a time too) */
+            p->K = (frames + p->L - 1) / p->L;
+            p->dense = aside_placement (d_buffers [i], p->pitch, frames, &p->lead);
+            if (!p->pitch) p->dense = (long) frames * b->C;
             const size_t samples = ((p->pitch ? (size_t) p->dense * b->C : (size_t) p->dense) + p->lead + (size_t)(q - 1)) & ~(size_t)(q - 1);
-            const size_t states = (arthip_biquad_spec_scratch (b->C, b->S, frames, L) + 255) & ~(size_t) 255;
+            const size_t states = (arthip_biquad_spec_scratch (b->C, b->S, frames, p->L) + 255) & ~(size_t) 255;
             ClipRound *r = &rounds [nrounds - 1];
             if (r->tmp_bytes && r->tmp_bytes + samples * sizeof (art_s) > bound) r = &rounds [nrounds++];
             p->round = (int)(r - rounds);
@@ -1327,8 +1327,7 @@ int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *co
             r->copy_tasks += p->pitch ? (long) b->C * (((long) frames * wps + 3) / 4 + 1) : (p->dense * wps + 3) / 4 + 1;
             continue;
         }
-        p->kind = frames > 0 ? CLIP_SERIAL : CLIP_SKIP;
-        if (frames > 0) { sbanks [nserial] = b; sbufs [nserial] = d_buffers [i]; spitches [nserial] = p->pitch; sframes [nserial] = frames; ++nserial; }
+        if (p->kind == CLIP_SERIAL) { sbanks [nserial] = b; sbufs [nserial] = d_buffers [i]; spitches [nserial] = p->pitch; sframes [nserial] = frames; ++nserial; }
         if (fromStart) {                                                     /* its sections are put back by the first round's copy launch */
             p->copy_slot = rounds [0].ncopy++; p->copy_task0 = rounds [0].copy_tasks;
             rounds [0].copy_tasks += ((long)(sizeof (Biquad) / 4) * b->C * b->S + 3) / 4 + 1;

@@ -1592,8 +1592,14 @@ void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_fram
     }
 }
 
+// The three passes as functions of one task, for the gathered kernels (bq_clips_*_kernel).  They are COPIES of the bodies of
+// biquad_spec_kernel, biquad_check_kernel and biquad_commit_kernel: a change to one goes into the other.  With the single kernels
+// calling these functions they compile to other code, and each was slower on an MI355X than as it stands (single call against the
+// build with the copies, profiles/biquad_shared_body.txt): the 8-byte biquad_spec_kernel<4, interleaved> 308.8 -> 353.2 us and
+// 318.8 -> 368.8 us at the same 254 VGPRs, biquad_check_kernel up to 0.5 us in nine of ten traced cases (S = 3: 4.98 -> 5.32 us), the
+// 4-byte biquad_commit_kernel<2, interleaved> 174.4 -> 181.5 us in a call with 35 repaired chunks.
+//
 // One task of the speculative pass: chunk k of channel c of a call (C channels, K chunks of L frames, warm-up W) from `sections`.
-// The one body of the single call's kernel (biquad_spec_kernel) and of the gathered one (bq_clips_spec_kernel).
 template <int S, bool PLANAR>
 __device__ __forceinline__ void spec_task (const Biquad *sections, int c, int k, int K, int L, int W, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
                                            spec_stride<PLANAR> out_stride, int frames, SpecState *starts, SpecState *ends)
@@ -1629,8 +1635,7 @@ __device__ __forceinline__ void spec_task (const Biquad *sections, int c, int k,
     for (int s = 0; s < S; ++s) ends [((size_t) c * K + k) * S + s] = st [s];
 }
 
-// biquad_check_kernel's body: one chunk boundary checked: flags [c][k] = chunk k did not start from the state chunk k-1 left; first_bad [c] = the first such k
-// of the channel (stays at its armed value, beyond any chunk count, when there is none).
+// biquad_check_kernel's body (a copy): one chunk boundary checked.
 template <int S>
 __device__ __forceinline__ void check_task (int c, int k, int K, const SpecState *starts, const SpecState *ends, unsigned char *bad, int *first_bad)
 {
@@ -1640,11 +1645,8 @@ __device__ __forceinline__ void check_task (int c, int k, int K, const SpecState
     if (!ok) atomicMin (first_bad + c, k);
 }
 
-// biquad_commit_kernel's body, with the sections read from `from` and stored to `sections` (the single call: the same array):
-// one channel committed: repairs from the first mismatch (rare: recomputes from the exact state until it rejoins a
-// speculative trajectory — in the worst case everything, serially), then the channel's final state goes into `sections`
-// repairs: running count of
-// chunks recomputed (diagnostics).  first_bad is re-armed for the next call.
+// biquad_commit_kernel's body (a copy), with the sections read from `from` and stored to `sections`, which the single call reads
+// and stores in one array: one channel committed.
 template <int S, bool PLANAR>
 __device__ __forceinline__ void commit_channel (const Biquad *from, Biquad *sections, int c, int K, int L, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
                                                 spec_stride<PLANAR> out_stride, int frames,
@@ -1695,9 +1697,9 @@ __device__ __forceinline__ void commit_channel (const Biquad *from, Biquad *sect
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Many banks' TIME-PARALLEL calls in shared launches (biquadBankApplyClipsPlanarDevice): biquad_spec_kernel, biquad_check_kernel and
-// biquad_commit_kernel over a table of items (ArtBqClip), one item per call.  The task space is the items' (chunk, channel) spaces
-// laid end to end; a thread finds its item by binary search over the items' first tasks (item_of) and runs the single call's body
+// Many banks' TIME-PARALLEL calls in shared launches (biquadBankApplyClipsPlanarDevice): the passes of biquad_spec_kernel,
+// biquad_check_kernel and biquad_commit_kernel over a table of items (ArtBqClip), one item per call.  The task space is the items' (chunk, channel) spaces
+// laid end to end; a thread finds its item by binary search over the items' first tasks (item_of) and runs the copy of the single call's body
 // with the item's own C, K, L, W and frames: the chunk cuts, and so the bits, the repairs and the final state, are the single
 // call's.  Lanes of different items (different L and K) share a wave.  One instantiation per (section count, layout).
 // ---------------------------------------------------------------------------------------------------

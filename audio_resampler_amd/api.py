@@ -159,6 +159,7 @@ def _bind(width):
         "decimateProcessPlanarLEDevice": (None, [DP, ptr, C.c_long, C.c_int, ptr, C.c_long]),
         "decimateProcessBatchPlanarLEDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr]),
         "decimateHipReset": (None, [DP]),
+        "decimateProcessClipsPlanarLEDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "artamdErrorCount": (C.c_int, []),
         "artamdPeriodMultiple": (C.c_int, [C.c_int]),
         "artamdPeriodMultipleRows": (C.c_int, [C.c_int, C.c_int]),
@@ -184,6 +185,7 @@ def _bind(width):
         "resampleProcessAndFlushPlanarDevice": (ResampleResult, [RP, ptr, C.c_long, C.c_int, ptr, C.c_long, C.c_int, C.c_double]),
         "resampleProcessBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleProcessAndFlushClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "stretchProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "artamdStretchClipCapacity": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double]),
         "resampleProcessSchedulePlanarDevice": (C.c_int, [RP, C.c_int, ptr, C.c_long, ptr, ptr, C.c_long, ptr, ptr, C.c_int, ptr]),
@@ -534,7 +536,7 @@ def _bind(width):
             raise RuntimeError("resampleProcessAndFlushBatchInterleavedDevice failed")
         return [(r.input_used, r.output_generated) for r in res]
 
-    def _batch_planar(name, resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios):
+    def _batch_planar(name, resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios, *more):
         n = len(resamplers)
         ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])
         res = (ResampleResult * n)()
@@ -542,7 +544,7 @@ def _bind(width):
         rc = getattr(lib(), name)(
             ctx, n, (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_ins]), pitches(in_pitches), (C.c_int * n)(*[int(v) for v in n_ins]),
             (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches), (C.c_int * n)(*[int(v) for v in out_caps]),
-            (C.c_double * n)(*[float(v) for v in ratios]), res)
+            (C.c_double * n)(*[float(v) for v in ratios]), *more, res)
         if rc:
             raise RuntimeError(name + " failed")
         return [(r.input_used, r.output_generated) for r in res]
@@ -559,6 +561,12 @@ def _bind(width):
         process_batch_planar_device; a d_ins entry may be None with n_ins 0: a pure flush).  The flushes write behind the process
         calls' frames in every plane.  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
         return _batch_planar("resampleProcessAndFlushBatchPlanarDevice", resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios)
+
+    def process_and_flush_clips_planar_device(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios, from_start=False):
+        """resampleProcessAndFlushClipsPlanarDevice: process_and_flush_batch_planar_device, with from_start every context first as after
+        its reset() — the contexts on the first one's stream put back by one zeroing launch for all of them, no memset per context."""
+        return _batch_planar("resampleProcessAndFlushClipsPlanarDevice", resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios,
+                             1 if from_start else 0)
 
     def _schedule_batch(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last):
         n = len(resamplers)
@@ -606,10 +614,10 @@ def _bind(width):
 
     class ClipResampler:
         """Whole clips, channels-first, from one fixed rate to another: x [B, C, T] (or [C, T]) on the GPU in, (y [B, C, Tout_max],
-        out_lengths) out — one resampleProcessAndFlushBatchPlanarDevice call on the tensor's own rows, no copy of the samples on the way.
+        out_lengths) out — one resampleProcessAndFlushClipsPlanarDevice call on the tensor's own rows, no copy of the samples on the way.
         Clip i is what a fresh fixed-ratio context makes of x[i, :, :lengths[i]] with resampleProcessAndFlushPlanarDevice (its lead-in
-        of half a filter length included); y[i, :, out_lengths[i]:] is zero.  Holds a pool of up to max_batch contexts, reset for every
-        call; a larger batch is made max_batch clips at a time."""
+        of half a filter length included); y[i, :, out_lengths[i]:] is zero.  Holds a pool of up to max_batch contexts, started afresh by
+        every call (one zeroing launch for all of them); a larger batch is made max_batch clips at a time."""
 
         def __init__(self, channels, src_rate, dst_rate, taps=380, filters=380, flags=BLACKMAN_HARRIS | SUBSAMPLE_INTERPOLATE | INCLUDE_LOWPASS,
                      max_batch=1024):
@@ -648,7 +656,8 @@ def _bind(width):
             stream = torch.cuda.current_stream(x.device).cuda_stream
             for r in self.pool[:min(B, self.max_batch)]:
                 r.set_stream(stream)
-                r.reset()
+            if any(v not in self._expected for v in lengths):
+                self.pool[0].reset()                              # (the dry run of a new length wants one context at its start)
             rooms = [self._room(v) for v in lengths]
             y = torch.zeros(B, Cn, max(rooms, default=0), dtype=x.dtype, device=x.device)
             size = x.element_size()
@@ -657,13 +666,10 @@ def _bind(width):
             made = []
             for b0 in range(0, B, self.max_batch):
                 idx = range(b0, min(B, b0 + self.max_batch))
-                if b0:
-                    for r in self.pool[:len(idx)]:
-                        r.reset()
-                got = process_and_flush_batch_planar_device(
+                got = process_and_flush_clips_planar_device(
                     self.pool[:len(idx)], [xp + i * x.stride(0) * size for i in idx], [in_pitch] * len(idx), [lengths[i] for i in idx],
                     [yp + i * y.stride(0) * size for i in idx], [out_pitch] * len(idx), [rooms[i] for i in idx],
-                    [self.ratio] * len(idx))
+                    [self.ratio] * len(idx), from_start=True)
                 made += [g for _, g in got]
             out_lengths = torch.tensor(made, dtype=torch.int64)
             return y[:, :, :max(made, default=0)], out_lengths
@@ -694,23 +700,41 @@ def _bind(width):
             raise RuntimeError("decimateProcessBatchPlanarLEDevice failed")
         return rc
 
+    def decimate_clips_planar_device(decimators, d_ins, in_pitches, n_ins, d_outs, out_pitches, from_start=False, d_clip_counts=None):
+        """decimateProcessClipsPlanarLEDevice: decimate_batch_planar_device, with from_start every context first as after its reset()
+        — the shared launches read each context's first state from the image its constructor left, no copy per context — and with
+        d_clip_counts (len(decimators) uint64 / int64 entries of device memory) entry i SET to item i's count of clipped samples by
+        the launches themselves, to be read with one download behind the call.  Returns the launch count (raises on -1)."""
+        n = len(decimators)
+        ctx = (C.c_void_p * n)(*[C.cast(d.p, C.c_void_p) for d in decimators])
+        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
+        rc = lib().decimateProcessClipsPlanarLEDevice(
+            ctx, n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), pitches(in_pitches), (C.c_int * n)(*[int(v) for v in n_ins]),
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches), 1 if from_start else 0,
+            None if d_clip_counts is None else _dev_ptr(d_clip_counts))
+        if rc < 0:
+            raise RuntimeError("decimateProcessClipsPlanarLEDevice failed")
+        return rc
+
     class ClipDecimator:
         """Whole clips, channels-first, to integer PCM: x [B, C, T] (or [C, T]) on the GPU in, (pcm uint8 [B, C, T * nbytes], clipped)
-        out — one decimateProcessBatchPlanarLEDevice call on the tensor's own rows, no copy of the samples on the way.  Clip i is what
+        out — one decimateProcessClipsPlanarLEDevice call on the tensor's own rows, no copy of the samples on the way.  Clip i is what
         a fresh Decimator makes of x[i, :, :lengths[i]]; pcm[i, :, lengths[i] * nbytes:] is zero; clipped[i] is clip i's count of
-        clipped samples (reading it waits for the call).  Holds a pool of up to max_batch contexts, reset for every call, on the
-        caller's current torch stream; a larger batch is made max_batch clips at a time.  Takes ClipResampler's (y, out_lengths) as
-        they come."""
+        clipped samples (counted by the launches into one device tensor, read with one download: that waits for the call).  Holds a
+        pool of up to max_batch contexts, started afresh by every call without an operation per context, on the caller's current
+        torch stream; a larger batch is made max_batch clips at a time (`launches`: how many the last call enqueued).  Takes
+        ClipResampler's (y, out_lengths) as they come."""
 
         def __init__(self, channels, bits, nbytes, gain, rate, flags, max_batch=1024):
             self.channels, self.bits, self.nbytes, self.max_batch = channels, bits, nbytes, max(1, int(max_batch))
             self._init = (channels, bits, nbytes, gain, rate, flags)
-            self.pool, self._seen = [], []                       # the contexts and their clip counters' totals after the last call
+            self.pool = []
+            self.launches = 0
 
         def close(self):
             for d in self.pool:
                 d.close()
-            self.pool, self._seen = [], []
+            self.pool = []
 
         def as_int(self, pcm):
             """pcm of 2 or 4 bytes per sample as int16 / int32 [B, C, T] (a view: little-endian samples on a little-endian host)"""
@@ -733,7 +757,6 @@ def _bind(width):
                 raise ValueError("lengths: one entry per clip, 0 .. T")
             while len(self.pool) < min(B, self.max_batch):
                 self.pool.append(Decimator(*self._init))
-                self._seen.append(0)
             stream = torch.cuda.current_stream(x.device).cuda_stream
             for d in self.pool[:min(B, self.max_batch)]:
                 d.set_stream(stream)
@@ -741,20 +764,15 @@ def _bind(width):
             size = x.element_size()
             xp, pp = x.data_ptr(), pcm.data_ptr()
             in_pitch, out_pitch = (x.stride(1), pcm.stride(1)) if Cn > 1 else (0, 0)     # (one channel: the same call in either layout)
-            clipped = []
+            counts = torch.empty(B, dtype=torch.int64, device=x.device)     # (every entry is set by the call that takes its clip)
+            self.launches = 0
             for b0 in range(0, B, self.max_batch):
                 idx = range(b0, min(B, b0 + self.max_batch))
-                pool = self.pool[:len(idx)]
-                for d in pool:
-                    d.reset()
-                before = self._seen[:len(pool)]                     # (only this object's calls move the pool's counters)
-                decimate_batch_planar_device(
-                    pool, [xp + i * x.stride(0) * size for i in idx], [in_pitch] * len(idx), [lengths[i] for i in idx],
-                    [pp + i * pcm.stride(0) for i in idx], [out_pitch] * len(idx))
-                after = [d.clipped() for d in pool]
-                self._seen[:len(pool)] = after
-                clipped += [a - b for a, b in zip(after, before)]
-            return pcm, torch.tensor(clipped, dtype=torch.int64)
+                self.launches += decimate_clips_planar_device(
+                    self.pool[:len(idx)], [xp + i * x.stride(0) * size for i in idx], [in_pitch] * len(idx), [lengths[i] for i in idx],
+                    [pp + i * pcm.stride(0) for i in idx], [out_pitch] * len(idx), from_start=True,
+                    d_clip_counts=counts.data_ptr() + 8 * b0)
+            return pcm, counts.cpu()
 
     def biquad_batch_device(banks, d_bufs, frames):
         """biquadBankApplyBatchInterleavedDevice over a list of BiquadBank objects: one launch per section count for the banks on

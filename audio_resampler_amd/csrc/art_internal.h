@@ -316,6 +316,21 @@ typedef struct {                         /* one context of a time-parallel launc
     int C, frames, bits, bytes, dither_type;
     long in_pitch, out_pitch;            /* samples / bytes between the planes of that side; 0: that side is interleaved */
 } ArtDecTask;
+/* The clips entry's records (decimateProcessClipsPlanarLEDevice): the batch entry's, plus where the first state is read from (the
+ * image decimateInit left, with fromStart; else the live state, which is always what is written) and the item's own clip count.
+ * Record types of their own and kernels of their own (over the same bodies): the batch entry's kernels and tables stay what they were. */
+typedef struct {
+    ArtDecLane lane;
+    const art_s *feedback_from;          /* what lane.feedback / lane.gen / lane.shaper start from */
+    const uint32_t *gen_from;
+    const Biquad *shaper_from;
+    unsigned long long *item_clipped;    /* &d_clipCounts [item], or NULL: this call's clipped samples of the lane are added here too */
+} ArtDecClipLane;
+typedef struct {
+    ArtDecTask task;                     /* (task.feedback and task.gens are only read: with fromStart they point into the image) */
+    unsigned long long *item_clipped;
+    long task0;                          /* task.task0 again, where the kernels' search over the items looks for it */
+} ArtDecClipTask;
 typedef struct {                         /* a class's slice of a batch call's table (16-byte aligned) */
     int count;                           /* items; in a serial class, lanes (a multiple of `lanes`: empty lanes pad the last workgroup) */
     int lanes;                           /* serial classes: lanes per workgroup */
@@ -326,6 +341,7 @@ typedef struct {
     int order, dither;                   /* the shaper order (0: none) and whether dither is on: every item of the class shares them */
     long tasks;                          /* time-parallel: total tasks */
     int pitched;                         /* an item of the class has a planar side: the kernel's PITCHED instantiation */
+    int clips;                           /* the items are the clips entry's records (ArtDecClipLane / ArtDecClipTask) and run its kernels */
     ArtBatchSlice slice;
 } ArtDecClass;
 #define ART_DEC_SEG 32                   /* frames of one channel per task of the time-parallel kernels (even: generator pairs) */
@@ -340,6 +356,10 @@ int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *cons
 /* ... and decimateProcessBatchPlanarLEDevice likewise: the one body of both layouts (NULL pitch arrays: artamd_decimate_batch) */
 int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
                                   const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches, int lanes);
+/* ... and decimateProcessClipsPlanarLEDevice: the same body once more, with the clips entry's records when fromStart or d_clipCounts ask for them */
+int artamd_decimate_clips_planar (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                  const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches, int lanes,
+                                  int fromStart, unsigned long long *d_clipCounts);
 int arthip_biquad_chain (Biquad *d_sections, int C, int S, art_s *d_buf, int frames, int stride, void *stream);
 /* Many banks' calls, one launch per section count (biquadBankApplyBatchInterleavedDevice).  A lane is one channel of one bank;
  * each class's lanes are one slice of the call's table (16-byte aligned), uploaded with arthip_table_upload. */
@@ -410,6 +430,13 @@ typedef struct {                         /* one strided copy of a grouped copy l
     long task0;                          /* first task of the item: the sum of rows * groups of the items before it */
 } ArtCopyRows;
 int arthip_copy_rows_launch (const void *d_items, int n, long tasks, void *stream);
+typedef struct {                         /* one run of a grouped zeroing launch (layout_kernels.hip): `words` 4-byte words from `ptr` on */
+    unsigned int *ptr;                   /* 4-byte aligned */
+    long words;
+    long task0;                          /* first task of the item: a task clears up to 4 words, (words + 3) / 4 + 1 tasks per item */
+} ArtZeroRun;
+/* every run cleared in one launch: fills the items' task0, uploads them to d_table (n items of device memory) and launches; 0 or -1 */
+int arthip_zero_runs (ArtZeroRun *items, int n, void *d_table, void *stream);
 /* biquadBankApplyClipsPlanarDevice with its own bound on the bytes set aside per round (roundBytes > 0; else the library's,
  * BQ_CLIPS_ROUND_BYTES): how the tests make a small batch take several rounds — pcm_host.c */
 int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches, const int *numFrames,

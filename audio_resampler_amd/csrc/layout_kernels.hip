@@ -147,9 +147,42 @@ void transpose_group_kernel (const ArtLayoutItem *items, int n)
     }
 }
 
+// Many runs of device memory cleared in one launch (resampleProcessAndFlushClipsPlanarDevice: both history buffers of every context of a
+// batch, where resampleReset issues two memsets per context).  A task is one 16-byte group counted from the boundary before its run:
+// whole aligned stores inside the run, single words at its ends; nothing outside [ptr, ptr + words) is written.
+__global__ __launch_bounds__ (256)
+void zero_runs_group_kernel (const ArtZeroRun *items, int n, long tasks)
+{
+    const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (task >= tasks) return;
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (items [mid].task0 <= task) lo = mid; else hi = mid - 1; }
+    const ArtZeroRun &it = items [lo];
+    const long w0 = (task - it.task0) * 4 - (long)(((uintptr_t) it.ptr >> 2) & 3), words = it.words;
+    if (w0 >= 0 && w0 + 4 <= words) { *reinterpret_cast<uint4 *> (it.ptr + w0) = make_uint4 (0u, 0u, 0u, 0u); return; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (w0 + j >= 0 && w0 + j < words) it.ptr [w0 + j] = 0u;
+}
+
 } // namespace
 
 extern "C" {
+
+// items [k].task0 is filled here; d_table: device memory of n items (stream order protects it)
+int arthip_zero_runs (ArtZeroRun *items, int n, void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    long tasks = 0;
+    for (int k = 0; k < n; ++k) {
+        items [k].task0 = tasks;
+        if (items [k].words > 0) tasks += (items [k].words + 3) / 4 + 1;
+    }
+    if (n <= 0 || tasks <= 0) return 0;
+    if (arthip_table_upload (items, sizeof (ArtZeroRun) * (size_t) n, d_table, stream)) return -1;
+    hipLaunchKernelGGL (zero_runs_group_kernel, dim3 ((unsigned int)((tasks + 255) / 256)), dim3 (256), 0, st, (const ArtZeroRun *) d_table, n, tasks);
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
 
 // items [k].tile and .task0 are filled here; d_table: device memory of n items (reused call after call: stream order protects it)
 int arthip_transpose_group (ArtLayoutItem *items, int n, int to_planar, void *d_table, void *stream)

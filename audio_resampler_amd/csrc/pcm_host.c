@@ -839,6 +839,7 @@ static void dec_swap_if (Decimate *cxt, int rc)
 }
 
 static int dec_reserve (Decimate *cxt, size_t in_bytes, size_t out_bytes);
+static void clip_copy_item (ArtCopyRows *it, const void *src, long src_pitch, void *dst, long dst_pitch, long width, long rows, long task0);
 
 /* a leaf context's call with a pitch on either side (0: interleaved); a one-channel context is the same call in either layout */
 static void dec_leaf_pitched (Decimate *cxt, const art_s *d_input, long in_pitch, int frames, unsigned char *d_output, long out_pitch)
@@ -964,13 +965,31 @@ static int lane_order (const void *pa, const void *pb)     /* longest first; the
 
 static unsigned long *dec_stamp (const void *cxt) { return &((const Decimate *) cxt)->hip->batch_stamp; }
 
-/* lanes > 0: every serial class gets that many lanes per workgroup (the measurements of the rule); 0: the rule */
-int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
-                                  const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches, int lanes)
+/* a context's state as decimateHipReset leaves it, host side only (the device side is the caller's: the gathered launches read
+ * the image): the generators live in the first of the two arrays, the mirrors are fresh */
+static void dec_host_from_start (Decimate *cxt)
+{
+    if (cxt->hip->d_gens > cxt->hip->d_gens_alt) dec_swap_if (cxt, 1);
+    dec_fresh_mirrors (cxt);
+}
+
+/* where the image (d_state0) holds what `live` points to in the state block */
+static const void *dec_image_of (const struct artamd_decimator *hip, const void *live)
+{
+    return live ? hip->d_state0 + ((const unsigned char *) live - hip->d_state) : NULL;
+}
+
+/* lanes > 0: every serial class gets that many lanes per workgroup (the measurements of the rule); 0: the rule.
+ * fromStart / d_clipCounts: decimateProcessClipsPlanarLEDevice (art_hip.h); with neither, the batch entries' records and kernels */
+int artamd_decimate_clips_planar (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                  const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches, int lanes,
+                                  int fromStart, unsigned long long *d_clipCounts)
 {
     if (n <= 0) return 0;
     if (artamd_batch_distinct ((const void *const *) cxts, n, dec_stamp, "decimate", "context")) return -1;
 
+    const int clips = fromStart || d_clipCounts;                   /* the clips entry's records and instantiations */
+    const size_t lane_size = clips ? sizeof (ArtDecClipLane) : sizeof (ArtDecLane), task_size = clips ? sizeof (ArtDecClipTask) : sizeof (ArtDecTask);
     struct artamd_decimator *lead = cxts [0]->hip;
     ArtDecArgs *args = malloc (sizeof (ArtDecArgs) * (size_t) n);
     int *cls_of = malloc (sizeof (int) * (size_t) n);
@@ -978,40 +997,66 @@ int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_
     ArtDecClass cls [DEC_BATCH_CLASSES];
     DecLaneRef *refs = NULL;
     unsigned char *table = NULL;
-    int launches = 0, rc = -1, most = 0;
+    int launches = 0, rc = -1, most = 0, nrestore = 0;
+    long restore_tasks = 0;
     if (!args || !cls_of || !pitch) { pcm_fail ("decimate batch: out of host memory"); goto out; }
     memset (cls, 0, sizeof (cls));
     for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
         cls [k].serial = k >= 2;
         cls [k].order = k >= 2 ? (k - 2) / 2 : 0;
         cls [k].dither = k >= 2 ? (k - 2) & 1 : k;
+        cls [k].clips = clips;
+    }
+
+    if (d_clipCounts) {            /* every entry 0, in stream order before anything is counted */
+        ENTER_DEVICE (lead);
+        const int failed = arthip_zero (d_clipCounts, sizeof (unsigned long long) * (size_t) n, lead->stream);
+        LEAVE_DEVICE (lead);
+        if (failed) { pcm_fail ("decimate clips: the clip counts could not be cleared (nothing launched)"); goto out; }
+        ++launches;
     }
 
     /* the contexts this launch cannot take are made as their single calls, in list order */
     for (int i = 0; i < n; ++i) {
         struct artamd_decimator *hip = cxts [i]->hip;
+        const int frames = numInputFrames [i];
         cls_of [i] = -1;
-        if (numInputFrames [i] <= 0) continue;
         const int planes = cxts [i]->numChannels > 1;              /* (one channel: the same call in either layout) */
         const long ip = pitch [2 * i] = planes && inputPitches ? inputPitches [i] : 0;
         const long op = pitch [2 * i + 1] = planes && outputPitches ? outputPitches [i] : 0;
         if (hip->nshards || hip->stream != lead->stream || hip->device != lead->device) {
-            decimateProcessPlanarLEDevice (cxts [i], d_inputs [i], ip, numInputFrames [i], d_outputs [i], op);
+            if (fromStart) decimateHipReset (cxts [i]);
+            if (frames <= 0) continue;
+            const long before = d_clipCounts ? decimateHipClipped (cxts [i]) : 0;
+            decimateProcessPlanarLEDevice (cxts [i], d_inputs [i], ip, frames, d_outputs [i], op);
             ++launches;
+            if (d_clipCounts) {    /* (synchronises: the read-backs, and the upload from this frame) */
+                const unsigned long long made = (unsigned long long)(decimateHipClipped (cxts [i]) - before);
+                ENTER_DEVICE (lead);
+                if (arthip_h2d (&d_clipCounts [i], &made, sizeof (made), lead->stream) || arthip_sync (lead->stream))
+                    pcm_fail ("decimate clips: a clip count could not be uploaded");
+                LEAVE_DEVICE (lead);
+            }
+            continue;
+        }
+        if (frames <= 0) {
+            cls_of [i] = fromStart ? -2 : -1;                      /* -2: only put back, by the one grouped copy of such contexts */
+            if (fromStart) { ++nrestore; restore_tasks += ((long)(hip->state_bytes - 16) / 4 + 3) / 4 + 1; }
             continue;
         }
         ArtDecArgs *a = &args [i];
         dec_args (cxts [i], a);
-        const int k = numInputFrames [i] >= 64 && !a->shaping_on ? (a->dither_on != 0)
+        if (fromStart && a->gens > a->gens_next) { uint32_t *t = a->gens; a->gens = a->gens_next; a->gens_next = t; }       /* as dec_host_from_start will leave them */
+        const int k = frames >= 64 && !a->shaping_on ? (a->dither_on != 0)
                     : 2 + 2 * (a->shaping_on ? (a->shaping_order >= 1 && a->shaping_order <= 4 ? a->shaping_order : 4) : 0) + (a->dither_on != 0);
         cls_of [i] = k;
         if (ip || op) cls [k].pitched = 1;
         if (cls [k].serial) { cls [k].slice.count += a->C; if (a->C > most) most = a->C; }
-        else { cls [k].tasks += (long) a->C * ((numInputFrames [i] + ART_DEC_SEG - 1) / ART_DEC_SEG); cls [k].slice.count++; }
+        else { cls [k].tasks += (long) a->C * ((frames + ART_DEC_SEG - 1) / ART_DEC_SEG); cls [k].slice.count++; }
     }
 
-    /* the table: every present class's items, 16-byte aligned slices */
-    size_t bytes = 0;
+    /* the table: the contexts that are only put back, then every present class's items, 16-byte aligned slices */
+    size_t bytes = (sizeof (ArtCopyRows) * (size_t) nrestore + 15) & ~(size_t) 15;
     int maxlanes = 0;
     for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
         if (!cls [k].slice.count) continue;
@@ -1021,26 +1066,45 @@ int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_
             if (cls [k].slice.count > maxlanes) maxlanes = cls [k].slice.count;
         }
         cls [k].slice.offset = bytes;
-        bytes += ((cls [k].serial ? sizeof (ArtDecLane) : sizeof (ArtDecTask)) * (size_t) cls [k].slice.count + 15) & ~(size_t) 15;
+        bytes += ((cls [k].serial ? lane_size : task_size) * (size_t) cls [k].slice.count + 15) & ~(size_t) 15;
     }
     if (!bytes) { rc = launches; goto out; }
     table = calloc (1, bytes);
     refs = maxlanes ? malloc (sizeof (DecLaneRef) * (size_t) maxlanes) : NULL;
     if (!table || (maxlanes && !refs)) { pcm_fail ("decimate batch: out of host memory"); goto out; }
+    if (nrestore) {
+        ArtCopyRows *it = (ArtCopyRows *) table;
+        long task0 = 0;
+        for (int i = 0; i < n; ++i) {
+            if (cls_of [i] != -2) continue;
+            const struct artamd_decimator *hip = cxts [i]->hip;    /* (all but the clip counter, as decimateHipReset) */
+            clip_copy_item (it, hip->d_state0 + 16, 0, hip->d_state + 16, 0, (long)(hip->state_bytes - 16) / 4, 1, task0);
+            task0 += it->groups;
+            ++it;
+        }
+    }
     for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
         if (!cls [k].slice.count) continue;
         if (!cls [k].serial) {
-            ArtDecTask *t = (ArtDecTask *)(table + cls [k].slice.offset);
             long task0 = 0;
             for (int i = 0, j = 0; i < n; ++i) {
                 if (cls_of [i] != k) continue;
                 const ArtDecArgs *a = &args [i];
-                ArtDecTask *it = &t [j++];
+                unsigned char *const rec = table + cls [k].slice.offset + task_size * (size_t) j++;
+                ArtDecTask *it = clips ? &((ArtDecClipTask *) rec)->task : (ArtDecTask *) rec;
                 it->in = d_inputs [i]; it->out = d_outputs [i];
                 it->feedback = a->feedback; it->gens = a->gens; it->gens_next = a->gens_next; it->clipped = a->clipped;
                 it->task0 = task0; it->scale = a->scale;
                 it->C = a->C; it->frames = numInputFrames [i]; it->bits = a->bits; it->bytes = a->bytes; it->dither_type = a->dither_type;
                 it->in_pitch = pitch [2 * i]; it->out_pitch = pitch [2 * i + 1];
+                if (clips) {
+                    ArtDecClipTask *ct = (ArtDecClipTask *) rec;
+                    ct->task0 = task0; ct->item_clipped = d_clipCounts ? &d_clipCounts [i] : NULL;
+                    if (fromStart) {                               /* both are only read by this form */
+                        it->feedback = (art_s *) dec_image_of (cxts [i]->hip, a->feedback);
+                        it->gens = (uint32_t *) dec_image_of (cxts [i]->hip, a->gens);
+                    }
+                }
                 task0 += (long) a->C * ((numInputFrames [i] + ART_DEC_SEG - 1) / ART_DEC_SEG);
             }
             continue;
@@ -1050,17 +1114,26 @@ int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_
             if (cls_of [i] == k)
                 for (int c = 0; c < args [i].C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numInputFrames [i]; ++m; }
         qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
-        ArtDecLane *l = (ArtDecLane *)(table + cls [k].slice.offset);       /* (the padding lanes stay zero: 0 frames) */
-        for (int j = 0; j < m; ++j) {
+        for (int j = 0; j < m; ++j) {                                       /* (the padding lanes stay zero: 0 frames) */
             const int i = refs [j].ctx, c = refs [j].channel;
             const ArtDecArgs *a = &args [i];
             const long ip = pitch [2 * i], op = pitch [2 * i + 1];
-            l [j].in = d_inputs [i] + (ip ? c * ip : c); l [j].out = d_outputs [i] + (op ? c * op : (long) c * a->bytes);
-            l [j].feedback = a->feedback + c;
-            l [j].gen = a->dither_on ? a->gens + c : NULL;
-            l [j].shaper = a->shaping_on ? a->shapers + c : NULL;
-            l [j].clipped = a->clipped; l [j].scale = a->scale;
-            l [j].stride = ip ? 1 : a->C; l [j].out_stride = op ? 1 : a->C; l [j].frames = numInputFrames [i]; l [j].bits = a->bits; l [j].bytes = a->bytes; l [j].dither_type = a->dither_type;
+            unsigned char *const rec = table + cls [k].slice.offset + lane_size * (size_t) j;
+            ArtDecLane *l = clips ? &((ArtDecClipLane *) rec)->lane : (ArtDecLane *) rec;
+            l->in = d_inputs [i] + (ip ? c * ip : c); l->out = d_outputs [i] + (op ? c * op : (long) c * a->bytes);
+            l->feedback = a->feedback + c;
+            l->gen = a->dither_on ? a->gens + c : NULL;
+            l->shaper = a->shaping_on ? a->shapers + c : NULL;
+            l->clipped = a->clipped; l->scale = a->scale;
+            l->stride = ip ? 1 : a->C; l->out_stride = op ? 1 : a->C; l->frames = numInputFrames [i]; l->bits = a->bits; l->bytes = a->bytes; l->dither_type = a->dither_type;
+            if (clips) {
+                ArtDecClipLane *cl = (ArtDecClipLane *) rec;
+                const struct artamd_decimator *hip = cxts [i]->hip;
+                cl->feedback_from = fromStart ? dec_image_of (hip, l->feedback) : l->feedback;
+                cl->gen_from = fromStart ? dec_image_of (hip, l->gen) : l->gen;
+                cl->shaper_from = fromStart ? dec_image_of (hip, l->shaper) : l->shaper;
+                cl->item_clipped = d_clipCounts ? &d_clipCounts [i] : NULL;
+            }
         }
     }
 
@@ -1071,13 +1144,23 @@ int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_
             pcm_fail ("decimate batch: the table could not be uploaded (nothing launched)");
         else {
             rc = 0;
+            if (nrestore) {
+                if (arthip_copy_rows_launch (lead->d_batch, nrestore, restore_tasks, lead->stream)) { pcm_fail ("decimate clips: launch failed"); rc = -1; }
+                else {
+                    ++launches;
+                    for (int i = 0; i < n; ++i)
+                        if (cls_of [i] == -2) dec_host_from_start (cxts [i]);
+                }
+            }
             for (int k = 0; k < DEC_BATCH_CLASSES && !rc; ++k) {
                 if (!cls [k].slice.count) continue;
                 if (arthip_decimate_batch_launch (&cls [k], lead->d_batch, lead->stream)) { pcm_fail ("decimate batch: launch failed"); rc = -1; break; }
                 ++launches;
-                if (!cls [k].serial)          /* the time-parallel form left the generator state in gens_next: as dec_swap_if */
-                    for (int i = 0; i < n; ++i)
-                        if (cls_of [i] == k) dec_swap_if (cxts [i], 1);
+                for (int i = 0; i < n; ++i) {
+                    if (cls_of [i] != k) continue;
+                    if (fromStart) dec_host_from_start (cxts [i]);         /* the launch read the image and wrote the live state */
+                    if (!cls [k].serial) dec_swap_if (cxts [i], 1);        /* the time-parallel form left the generator state in gens_next */
+                }
             }
             if (!rc) rc = launches;
         }
@@ -1086,6 +1169,19 @@ int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_
 out:
     free (args); free (cls_of); free (pitch); free (refs); free (table);
     return rc;
+}
+
+int artamd_decimate_batch_planar (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                  const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches, int lanes)
+{
+    return artamd_decimate_clips_planar (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, lanes, 0, NULL);
+}
+
+int decimateProcessClipsPlanarLEDevice (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                        const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches,
+                                        int fromStart, unsigned long long *d_clipCounts)
+{
+    return artamd_decimate_clips_planar (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, 0, fromStart != 0, d_clipCounts);
 }
 
 int artamd_decimate_batch (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,

@@ -1045,9 +1045,29 @@ __device__ __forceinline__ void dec_store_unit (unsigned char *p, int n, int nby
 // frames [n0, n0 + DEC_SEG) of channel c of item `a`, the generator jumped to n0.  PITCHED: either side may be planar — a planar
 // input is read as one run, a planar output packed into 16-byte stores; without it both sides are interleaved and the pitches are
 // not looked at.  The channel's last task leaves the generator state in gens_next (the rest still read gens; the host swaps them).
-template <bool DITHER, bool PITCHED>
-__device__ __forceinline__ void dec_parallel_task (const ArtDecTask &a, int c, long n0)
+// The clips entry's records (decimateProcessClipsPlanarLEDevice) carry the batch entry's and more; the kernel bodies are instantiated
+// per record type, for kernels of their own, so the batch entry's kernels are the code they were.  What a body asks of its record:
+__device__ __forceinline__ const ArtDecTask &dec_task (const ArtDecTask &t) { return t; }
+__device__ __forceinline__ const ArtDecTask &dec_task (const ArtDecClipTask &t) { return t.task; }
+__device__ __forceinline__ void dec_count_item (const ArtDecTask &, unsigned long long) {}
+__device__ __forceinline__ void dec_count_item (const ArtDecClipTask &t, unsigned long long n) { if (t.item_clipped) atomicAdd (t.item_clipped, n); }
+__device__ __forceinline__ const ArtDecLane &dec_lane (const ArtDecLane &l) { return l; }
+__device__ __forceinline__ const ArtDecLane &dec_lane (const ArtDecClipLane &l) { return l.lane; }
+__device__ __forceinline__ const art_s *dec_feedback_from (const ArtDecLane &l) { return l.feedback; }
+__device__ __forceinline__ const art_s *dec_feedback_from (const ArtDecClipLane &l) { return l.feedback_from; }
+__device__ __forceinline__ const uint32_t *dec_gen_from (const ArtDecLane &l) { return l.gen; }
+__device__ __forceinline__ const uint32_t *dec_gen_from (const ArtDecClipLane &l) { return l.gen_from; }
+__device__ __forceinline__ const Biquad *dec_shaper_from (const ArtDecLane &l) { return l.shaper; }
+__device__ __forceinline__ const Biquad *dec_shaper_from (const ArtDecClipLane &l) { return l.shaper_from; }
+__device__ __forceinline__ void dec_shaper_index (const ArtDecLane &) {}                 // (store_section steps the live record's index:
+__device__ __forceinline__ void dec_shaper_index (const ArtDecClipLane &l) { l.lane.shaper->index = l.shaper_from->index; }   // the source's first)
+__device__ __forceinline__ void dec_count_item (const ArtDecLane &, unsigned long long) {}
+__device__ __forceinline__ void dec_count_item (const ArtDecClipLane &l, unsigned long long n) { if (l.item_clipped) atomicAdd (l.item_clipped, n); }
+
+template <bool DITHER, bool PITCHED, typename Task = ArtDecTask>
+__device__ __forceinline__ void dec_parallel_task (const Task &item, int c, long n0)
 {
+    const ArtDecTask &a = dec_task (item);
     const art_s *const in = a.in;
     unsigned char *const out = a.out;
     const long in_pitch = PITCHED ? a.in_pitch : 0, out_pitch = PITCHED ? a.out_pitch : 0;
@@ -1073,7 +1093,7 @@ __device__ __forceinline__ void dec_parallel_task (const ArtDecTask &a, int c, l
     else for (int i = 0; i < cnt; ++i) one (i, in [(size_t)(n0 + i) * C + c]);
     if (out_pitch) pk.end ();
     if (DITHER && n0 + cnt == a.frames) a.gens_next [c] = g;
-    if (clips) atomicAdd (a.clipped, (unsigned long long) clips);
+    if (clips) { atomicAdd (a.clipped, (unsigned long long) clips); dec_count_item (item, (unsigned long long) clips); }
 }
 
 template <int ORDER, bool DITHER, bool PITCHED = false>                  // ORDER 0 = no noise shaping
@@ -1335,9 +1355,10 @@ constexpr int DEC_BATCH_RUN = 60;                  // frames per chunk at most: 
 // PITCHED: a class with a planar side among its lanes.  A lane's side is a run of consecutive frames exactly when its stride there is 1
 // (a plane, or a one-channel stream): the helper waves then move that lane's side of a chunk unit by unit, and every other lane's
 // element by element as before.
-template <int ORDER, bool DITHER, bool PITCHED = false>                  // ORDER 0: no noise shaping (calls under 64 frames)
-__global__ __launch_bounds__ (ST_THREADS)
-void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_frames)
+// Lane: the record type (the kernels proper follow the body).  An ArtDecClipLane reads its first state from where the record says (the context's initial image, or the
+// live state) and counts its clipped samples for its item as well.
+template <int ORDER, bool DITHER, bool PITCHED, typename Lane>            // ORDER 0: no noise shaping (calls under 64 frames)
+__device__ __forceinline__ void dec_batch_pipe_body (const Lane *table, int lanes, int chunk_frames)
 {
     extern __shared__ __attribute__ ((aligned (16))) unsigned char dec_lds [];
     const int pitch = chunk_frames + 4, span = lanes * pitch;
@@ -1351,20 +1372,21 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
     __shared__ int s_ostride [PITCHED ? 64 : 1];                        // PITCHED: the output's stride in frames (s_stride: the input's)
     __shared__ unsigned int s_clips [64];
     const int tid = threadIdx.x, wave = tid >> 6;
-    const ArtDecLane *const mine = table + (size_t) blockIdx.x * lanes;
+    const Lane *const mine = table + (size_t) blockIdx.x * lanes;
 
     art_s fb = 0; SectionRegs sh; int my_frames = 0;
     if (tid < lanes) {
-        const ArtDecLane &d = mine [tid];
+        const Lane &rec = mine [tid];
+        const ArtDecLane &d = dec_lane (rec);
         s_in [tid] = d.in; s_out [tid] = d.out; s_scale [tid] = d.scale; s_stride [tid] = d.stride; s_frames [tid] = d.frames;
         s_fmt [tid] = d.bits | (d.bytes << 8) | ((d.dither_type + 1) << 16);
         s_clips [tid] = 0;
         if (PITCHED) s_ostride [tid] = d.out_stride;
         my_frames = d.frames;
         if (my_frames > 0) {
-            fb = *d.feedback;
-            if (DITHER) s_gen [0][tid] = *d.gen;
-            if (ORDER) load_section (sh, *d.shaper);
+            fb = *dec_feedback_from (rec);
+            if (DITHER) s_gen [0][tid] = *dec_gen_from (rec);
+            if (ORDER) load_section (sh, *dec_shaper_from (rec));
         }
     }
     __syncthreads ();
@@ -1442,12 +1464,28 @@ void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_f
     __syncthreads ();
 
     if (tid < lanes && my_frames > 0) {
-        const ArtDecLane &d = mine [tid];
+        const Lane &rec = mine [tid];
+        const ArtDecLane &d = dec_lane (rec);
         *d.feedback = fb;
         if (DITHER) *d.gen = s_gen [((my_frames + chunk_frames - 1) / chunk_frames) & 1][tid];
-        if (ORDER) store_section (*d.shaper, sh, my_frames, true);
-        if (s_clips [tid]) atomicAdd (d.clipped, (unsigned long long) s_clips [tid]);
+        if (ORDER) { dec_shaper_index (rec); store_section (*d.shaper, sh, my_frames, true); }
+        if (s_clips [tid]) { atomicAdd (d.clipped, (unsigned long long) s_clips [tid]); dec_count_item (rec, (unsigned long long) s_clips [tid]); }
     }
+}
+
+template <int ORDER, bool DITHER, bool PITCHED = false>
+__global__ __launch_bounds__ (ST_THREADS)
+void decimate_batch_pipe_kernel (const ArtDecLane *table, int lanes, int chunk_frames)
+{
+    dec_batch_pipe_body<ORDER, DITHER, PITCHED> (table, lanes, chunk_frames);
+}
+
+// ... over the clips entry's records; always PITCHED, which takes interleaved lanes as well
+template <int ORDER, bool DITHER>
+__global__ __launch_bounds__ (ST_THREADS)
+void decimate_clips_pipe_kernel (const ArtDecClipLane *table, int lanes, int chunk_frames)
+{
+    dec_batch_pipe_body<ORDER, DITHER, true> (table, lanes, chunk_frames);
 }
 
 // the item a task of a flattened task space belongs to: the last whose first task is <= task (items [0].task0 == 0, ascending)
@@ -1461,22 +1499,36 @@ __device__ __forceinline__ const Item &item_of (const Item *items, int n, long t
 
 // decimate_parallel_kernel over a flattened task space: (context, channel, DEC_SEG-frame segment).  A thread finds its context by
 // binary search over the contexts' first tasks (item_of).
-template <bool DITHER, bool PITCHED = false>      // PITCHED: a class with a planar side among its items
-__global__ __launch_bounds__ (256)
-void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
+template <bool DITHER, bool PITCHED, typename Task>
+__device__ __forceinline__ void dec_batch_parallel_body (const Task *items, int n, long tasks)
 {
     const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
     if (task >= tasks) return;
-    const ArtDecTask &a = item_of (items, n, task);
+    const Task &item = item_of (items, n, task);
+    const ArtDecTask &a = dec_task (item);
     const long t = task - a.task0;
     if (PITCHED && (a.in_pitch || a.out_pitch)) {  // neighbouring threads are neighbouring segments of one plane
         const long segs = (a.frames + DEC_SEG - 1) / DEC_SEG;
         const int c = (int)(t / segs);
-        dec_parallel_task<DITHER, true> (a, c, (t - c * segs) * DEC_SEG);
+        dec_parallel_task<DITHER, true> (item, c, (t - c * segs) * DEC_SEG);
         return;
     }
     const long n0 = (t / a.C) * DEC_SEG;           // (an interleaved item of a PITCHED class as well) neighbouring threads are
-    if (n0 < a.frames) dec_parallel_task<DITHER, false> (a, (int)(t % a.C), n0);       // neighbouring channels of the same frames
+    if (n0 < a.frames) dec_parallel_task<DITHER, false> (item, (int)(t % a.C), n0);    // neighbouring channels of the same frames
+}
+
+template <bool DITHER, bool PITCHED = false>      // PITCHED: a class with a planar side among its items
+__global__ __launch_bounds__ (256)
+void decimate_batch_parallel_kernel (const ArtDecTask *items, int n, long tasks)
+{
+    dec_batch_parallel_body<DITHER, PITCHED> (items, n, tasks);
+}
+
+template <bool DITHER>                             // ... over the clips entry's records; always PITCHED
+__global__ __launch_bounds__ (256)
+void decimate_clips_parallel_kernel (const ArtDecClipTask *items, int n, long tasks)
+{
+    dec_batch_parallel_body<DITHER, true> (items, n, tasks);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1904,6 +1956,28 @@ static DecBatchPipeKernel dec_batch_pipe_kernel (int order, bool dither, bool pi
     }
     return dec_pipe_lds_allowed (k, order, dither, pitched, done);
 }
+// the clips entry's kernels
+typedef void (*DecClipsPipeKernel) (const ArtDecClipLane *, int, int);
+typedef void (*DecClipsParallelKernel) (const ArtDecClipTask *, int, long);
+static DecClipsParallelKernel dec_clips_parallel_kernel (bool dither)
+{
+    return dither ? decimate_clips_parallel_kernel<true> : decimate_clips_parallel_kernel<false>;
+}
+#define DEC_PICK_CLIPS(O) (dither ? decimate_clips_pipe_kernel<O, true> : decimate_clips_pipe_kernel<O, false>)
+static DecClipsPipeKernel dec_clips_pipe_kernel (int order, bool dither)
+{
+    static bool done [5][2][2];
+    DecClipsPipeKernel k;
+    switch (order) {
+        case 0: k = DEC_PICK_CLIPS (0); break;
+        case 1: k = DEC_PICK_CLIPS (1); break;
+        case 2: k = DEC_PICK_CLIPS (2); break;
+        case 3: k = DEC_PICK_CLIPS (3); break;
+        default: k = DEC_PICK_CLIPS (4); break;
+    }
+    return dec_pipe_lds_allowed (k, order, dither, true, done);
+}
+#undef DEC_PICK_CLIPS
 #undef DEC_PICK3
 #undef DEC_PICK2
 
@@ -2048,14 +2122,23 @@ int arthip_decimate_batch_launch (const ArtDecClass *cls, const void *d_table, v
     const void *items = (const char *) d_table + cls->slice.offset;
     if (cls->slice.count <= 0) return 0;
     if (!cls->serial) {
-        hipLaunchKernelGGL (dec_batch_parallel_kernel (cls->dither != 0, cls->pitched != 0), dim3 ((unsigned int)((cls->tasks + 255) / 256)), dim3 (256), 0, st,
-                            (const ArtDecTask *) items, cls->slice.count, cls->tasks);
+        const dim3 grid ((unsigned int)((cls->tasks + 255) / 256));
+        if (cls->clips)
+            hipLaunchKernelGGL (dec_clips_parallel_kernel (cls->dither != 0), grid, dim3 (256), 0, st, (const ArtDecClipTask *) items, cls->slice.count, cls->tasks);
+        else
+            hipLaunchKernelGGL (dec_batch_parallel_kernel (cls->dither != 0, cls->pitched != 0), grid, dim3 (256), 0, st,
+                                (const ArtDecTask *) items, cls->slice.count, cls->tasks);
         return hipGetLastError () == hipSuccess ? 0 : -1;
     }
     const int L = cls->slice.lanes;
     if (L < 1 || L > 64 || cls->slice.count % L) return -1;
     const int chunk_frames = batch_chunk_frames (L, DEC_BATCH_RUN);
     const size_t lds = (size_t) 5 * L * (chunk_frames + 4) * sizeof (art_s);          // <= DEC_PIPE_LDS (80 KiB)
+    if (cls->clips) {
+        hipLaunchKernelGGL (dec_clips_pipe_kernel (cls->order, cls->dither != 0), dim3 ((unsigned int)(cls->slice.count / L)), dim3 (ST_THREADS), lds, st,
+                            (const ArtDecClipLane *) items, L, chunk_frames);
+        return hipGetLastError () == hipSuccess ? 0 : -1;
+    }
     hipLaunchKernelGGL (dec_batch_pipe_kernel (cls->order, cls->dither != 0, cls->pitched != 0), dim3 ((unsigned int)(cls->slice.count / L)), dim3 (ST_THREADS), lds, st,
                         (const ArtDecLane *) items, L, chunk_frames);
     return hipGetLastError () == hipSuccess ? 0 : -1;

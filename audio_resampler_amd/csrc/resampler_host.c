@@ -722,6 +722,20 @@ void resampleFree (Resample *cxt)
     free (cxt);
 }
 
+/* the host part of resampleReset (the device part: both history buffers zero, in stream order before the next call) */
+static void reset_host (Resample *cxt)
+{
+    struct artamd_resampler *hip = cxt->hip;
+    hip->floor_active = 0; hip->lin_origin = 0;
+    cxt->outputOffset = cxt->numTaps / 2;
+    cxt->inputIndex = cxt->numTaps;
+
+    if (cxt->flags & EXTRAPOLATE_ENDPOINTS)
+        cxt->flags |= EXTRAPOLATE_PREFILL;
+
+    cxt->flags &= ~RESAMPLER_FLUSHED;
+}
+
 void resampleReset (Resample *cxt)
 {
     struct artamd_resampler *hip = cxt->hip;
@@ -736,14 +750,7 @@ void resampleReset (Resample *cxt)
         arthip_zero (hip->d_hist [1], hist_bytes, hip->stream);
         LEAVE_DEVICE (hip);
     }
-    hip->floor_active = 0; hip->lin_origin = 0;
-    cxt->outputOffset = cxt->numTaps / 2;
-    cxt->inputIndex = cxt->numTaps;
-
-    if (cxt->flags & EXTRAPOLATE_ENDPOINTS)
-        cxt->flags |= EXTRAPOLATE_PREFILL;
-
-    cxt->flags &= ~RESAMPLER_FLUSHED;
+    reset_host (cxt);
 }
 
 double resampleGetLowpassRatio (Resample *cxt) { return cxt->lowpassRatio; }
@@ -1746,20 +1753,20 @@ out:
 /* both batch entries: the process phase, then (and_flush) the flushes */
 static int batch_entry (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *in_pitches, const int *numInputFrames,
                         artsample_t *const *d_outputs, const long *out_pitches, const int *numOutputFrames, const double *ratios,
-                        ResampleResult *results, int and_flush);
+                        ResampleResult *results, int and_flush, int from_start);
 
 int resampleProcessBatchInterleavedDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const int *numInputFrames,
                                            artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
                                            ResampleResult *results)
 {
-    return batch_entry (cxts, n, d_inputs, NULL, numInputFrames, d_outputs, NULL, numOutputFrames, ratios, results, 0);
+    return batch_entry (cxts, n, d_inputs, NULL, numInputFrames, d_outputs, NULL, numOutputFrames, ratios, results, 0, 0);
 }
 
 int resampleProcessBatchPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
                                       const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
                                       const int *numOutputFrames, const double *ratios, ResampleResult *results)
 {
-    return batch_entry (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, results, 0);
+    return batch_entry (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, results, 0, 0);
 }
 
 /* ---- many whole clips, one launch per stage ------------------------------------------------------------------------
@@ -1820,15 +1827,55 @@ out:
     return rc;
 }
 
+/* resampleReset for every context of a list, on the lead's device: the contexts on the lead's stream and device that are not sharded share ONE
+ * zeroing launch over both history buffers of each (so it is right whichever of the two is current), its table in the lead's batch table (the
+ * batch launches that follow rewrite it in stream order); the others get their own resampleReset.  0, or -1 with no context reset. */
+static int batch_from_start (Resample *const *cxts, int n)
+{
+    struct artamd_resampler *lead = cxts [0]->hip;
+    ArtZeroRun *runs = malloc (sizeof (ArtZeroRun) * 2 * (size_t) n);
+    int nruns = 0, rc = -1;
+    if (!runs) goto out;
+    for (int i = 0; i < n; ++i) {
+        const struct artamd_resampler *hip = cxts [i]->hip;
+        if (hip->nshards || hip->stream != lead->stream || hip->device != lead->device) continue;
+        const long words = (long)(sizeof (art_s) / 4) * HIST_FRAMES (cxts [i]->numTaps) * cxts [i]->numChannels;
+        for (int h = 0; h < 2; ++h) { runs [nruns].ptr = (unsigned int *) hip->d_hist [h]; runs [nruns].words = words; ++nruns; }
+    }
+    if (nruns) {
+        const size_t need = sizeof (ArtZeroRun) * (size_t) nruns;
+        if (need > lead->batch_cap) lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, need);
+        if (!lead->d_batch || arthip_zero_runs (runs, nruns, lead->d_batch, lead->stream)) {
+            fprintf (stderr, "artamd: resample clips: the zeroing launch failed: %s\n", arthip_last_error ());
+            goto out;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        const struct artamd_resampler *hip = cxts [i]->hip;
+        if (hip->nshards || hip->stream != lead->stream || hip->device != lead->device) resampleReset (cxts [i]);
+        else reset_host (cxts [i]);
+    }
+    rc = 0;
+out:
+    free (runs);
+    return rc;
+}
+
 static int batch_entry (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *in_pitches, const int *numInputFrames,
                         artsample_t *const *d_outputs, const long *out_pitches, const int *numOutputFrames, const double *ratios,
-                        ResampleResult *results, int and_flush)
+                        ResampleResult *results, int and_flush, int from_start)
 {
     if (n <= 0) return 0;
     if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample", "context")) return -1;
     struct artamd_resampler *lead = cxts [0]->hip;
     BatchIo *io = malloc (sizeof (BatchIo) * (size_t) n);
     ENTER_DEVICE (lead);
+    if (io && from_start && batch_from_start (cxts, n)) {
+        artamd_note_failure ("resampler: the clips entry could not put its contexts back (nothing enqueued)");
+        LEAVE_DEVICE (lead);
+        free (io);
+        return -1;
+    }
     int rc = io ? batch_process (cxts, n, d_inputs, in_pitches, numInputFrames, d_outputs, out_pitches, numOutputFrames, ratios, results, io) : -1;
     if (and_flush) {
         if (!rc) rc = batch_flush (cxts, n, in_pitches, numInputFrames, d_outputs, out_pitches, numOutputFrames, ratios, results);
@@ -1843,14 +1890,21 @@ int resampleProcessAndFlushBatchInterleavedDevice (Resample *const *cxts, int n,
                                                    artsample_t *const *d_outputs, const int *numOutputFrames, const double *ratios,
                                                    ResampleResult *results)
 {
-    return batch_entry (cxts, n, d_inputs, NULL, numInputFrames, d_outputs, NULL, numOutputFrames, ratios, results, 1);
+    return batch_entry (cxts, n, d_inputs, NULL, numInputFrames, d_outputs, NULL, numOutputFrames, ratios, results, 1, 0);
 }
 
 int resampleProcessAndFlushBatchPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
                                               const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
                                               const int *numOutputFrames, const double *ratios, ResampleResult *results)
 {
-    return batch_entry (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, results, 1);
+    return batch_entry (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, results, 1, 0);
+}
+
+int resampleProcessAndFlushClipsPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                              const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
+                                              const int *numOutputFrames, const double *ratios, int fromStart, ResampleResult *results)
+{
+    return batch_entry (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, results, 1, fromStart != 0);
 }
 
 /* ---- consecutive blocks of one stream, one launch --------------------------------------------------------------------

@@ -258,6 +258,21 @@ int resampleProcessBatchPlanarDevice (Resample *const *cxts, int n, const artsam
 int resampleProcessAndFlushBatchPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
                                               const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
                                               const int *numOutputFrames, const double *ratios, ResampleResult *results);
+/* Whole clips from a fresh start: exactly resampleReset (cxts [i]) for every i when fromStart != 0, then
+ * resampleProcessAndFlushBatchPlanarDevice on the same arguments — the same results, samples and observable context state.  With
+ * fromStart == 0 it is that entry.
+ * The host part of the reset is resampleReset's own (position, input index, the floor and linear origins, the EXTRAPOLATE_PREFILL
+ * history, re-arming a flushed context; the kept filter rows stay).  The device part, for the contexts that share cxts [0]'s stream and
+ * device and are not sharded, is ONE launch in front of the batch's: a grouped zeroing kernel (zero_runs_group_kernel) over a table of
+ * (pointer, length) runs that rides in the lead context's batch table clears both history buffers of every such context — so it is right
+ * for either value of the context's current-buffer index — instead of two memsets per context; once warm it allocates nothing.  Sharded
+ * contexts and contexts on another stream or device get their own resampleReset.
+ * Refusals and failure as in the batch entry; a refusal (-1: a NULL context or one listed twice) happens before any context is reset.  The
+ * reset is made before the batch entry's launches: after one of THOSE failed the contexts stand as after resampleReset.  If the zeroing launch
+ * itself cannot be made, the call returns -1 with no context reset and nothing enqueued (counted in artamdErrorCount). */
+int resampleProcessAndFlushClipsPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                              const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
+                                              const int *numOutputFrames, const double *ratios, int fromStart, ResampleResult *results);
 
 /* ---- host-only building blocks (no GPU needed; used by the CPU test-suite) ---- */
 /* (numFilters+1) x numTaps bank exactly as resampleInit builds it (reference resampler.c:149-168, 1090-1133) */
@@ -426,6 +441,35 @@ int decimateProcessBatchPlanarLEDevice (Decimate *const *cxts, int n, const arts
  * without decimateFree / decimateInit.  The clip counter is NOT reset (decimateHipClipped: total since init).  Asynchronous on the
  * context's stream, behind every earlier call; no allocation; sharded contexts too. */
 void decimateHipReset (Decimate *cxt);
+/* Whole clips from a fresh start, in the batch entry's shared launches.  For every item i the call leaves exactly what
+ *     if (fromStart) decimateHipReset (cxts [i]);
+ *     decimateProcessPlanarLEDevice (cxts [i], d_inputs [i], inputPitches ? inputPitches [i] : 0, numInputFrames [i],
+ *                                    d_outputs [i], outputPitches ? outputPitches [i] : 0);
+ * leaves: the output bytes, the context's running clip total (decimateHipClipped), the device state, the host mirrors (feedback,
+ * tpdf_generators, noise_shapers) and which of the two generator arrays is live.  Pitches as in decimateProcessBatchPlanarLEDevice.
+ * An item with numInputFrames [i] <= 0 is skipped; with fromStart its context is still put back.  fromStart == 0 with
+ * d_clipCounts == NULL is decimateProcessBatchPlanarLEDevice itself.
+ * No operation per context: the gathered launches (the contexts on the stream and device of cxts [0] that are not sharded) read
+ * every context's first values from the image decimateInit left, where it lies, and write the live state; no copy, memset or
+ * launch is issued per gathered context and nothing in the gathered path synchronises.  (They are kernels of their
+ * own — the batch entry's kernel bodies over records of their own; the batch entry's kernels and tables are what they were.)  Zero-frame contexts that
+ * are only put back share ONE grouped copy launch, whatever their number.
+ * d_clipCounts: NULL, or n entries of device memory on cxts [0]'s device.  Entry i is SET to the number of samples of item i this
+ * call clipped (skipped items: 0): the call clears the n entries with one operation on cxts [0]'s stream, and the gathered
+ * kernels add what they add to the context's total to the item's entry as well.  Read all of them with one download, in stream
+ * order behind the call.
+ * Contexts made on the side — sharded contexts and contexts on another stream or device than cxts [0] — get their own
+ * decimateHipReset (with fromStart) and their single planar call, in list order; with d_clipCounts their entry is the difference
+ * of decimateHipClipped after and before, uploaded on cxts [0]'s stream: this rare path SYNCHRONISES (that context's stream, and
+ * cxts [0]'s).
+ * Returns the launch count of decimateProcessBatchPlanarLEDevice for the same list, plus one when d_clipCounts is cleared, plus
+ * one when fromStart meets zero-frame gathered contexts (their grouped copy): it does not depend on n within a class.  0 for
+ * n <= 0; -1 with nothing enqueued, nothing reset and nothing counted if a context is NULL or listed twice; -1 if a launch failed
+ * (counted in artamdErrorCount): no separate reset was issued, so the contexts of the failed launch keep the device state, the
+ * mirrors and the generator arrays they had before the call. */
+int decimateProcessClipsPlanarLEDevice (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
+                                        const int *numInputFrames, unsigned char *const *d_outputs, const long *outputPitches,
+                                        int fromStart, unsigned long long *d_clipCounts);
 void floatIntegersLEDevice (const unsigned char *d_input, double inputGain, int inputBits, int inputBytes, int inputStride,
                             artsample_t *d_output, int numSamples, void *hipStream);
 /* Many buffers' integer PCM to samples in ONE launch: item i leaves exactly the bits of floatIntegersLEDevice (d_inputs [i],

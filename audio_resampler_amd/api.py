@@ -186,6 +186,7 @@ def _bind(width):
         "resampleProcessBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleProcessAndFlushClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
+        "resampleAdjointClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "stretchProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "artamdStretchClipCapacity": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double]),
         "resampleProcessSchedulePlanarDevice": (C.c_int, [RP, C.c_int, ptr, C.c_long, ptr, ptr, C.c_long, ptr, ptr, C.c_int, ptr]),
@@ -568,6 +569,54 @@ def _bind(width):
         return _batch_planar("resampleProcessAndFlushClipsPlanarDevice", resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios,
                              1 if from_start else 0)
 
+    def adjoint_clips_planar_device(resamplers, d_gouts, gout_pitches, n_outs, d_gins, gin_pitches, n_ins, ratios):
+        """resampleAdjointClipsPlanarDevice: the gradient of whole clips.  Item i: frames 0 .. n_ins[i]-1 of every channel of d_gins[i] are
+        set to the transpose of the clips entry's map (a fresh context of resamplers[i]'s parameters, process then flush) applied to the
+        first n_outs[i] frames of d_gouts[i]; pitches as in process_batch_planar_device.  The contexts are only read, and one may be
+        listed any number of times.  Returns the launch count (raises if the call returned -1)."""
+        n = len(resamplers)
+        ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])
+        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
+        rc = lib().resampleAdjointClipsPlanarDevice(
+            ctx, n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_gouts]), pitches(gout_pitches), (C.c_int * n)(*[int(v) for v in n_outs]),
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_gins]), pitches(gin_pitches), (C.c_int * n)(*[int(v) for v in n_ins]),
+            (C.c_double * n)(*[float(v) for v in ratios]))
+        if rc < 0:
+            raise RuntimeError("resampleAdjointClipsPlanarDevice failed")
+        return rc
+
+    def _clip_resample_grad():
+        """the torch.autograd.Function that attaches a ClipResampler's output to the graph (made on first use: torch is imported late)"""
+        if "clip_grad" not in _state:
+            import torch
+
+            class ClipResampleGrad(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, x, y, clip, lengths, made):
+                    ctx.clip, ctx.lengths, ctx.made, ctx.x_shape = clip, lengths, made, x.shape
+                    return y.view_as(y)
+
+                @staticmethod
+                @torch.autograd.function.once_differentiable
+                def backward(ctx, gy):
+                    clip, lengths, made = ctx.clip, ctx.lengths, ctx.made
+                    B, Cn, T = ctx.x_shape
+                    if not clip.pool:
+                        raise RuntimeError("the ClipResampler was closed before backward")
+                    if (gy.shape[2] and gy.stride(2) != 1) or (Cn > 1 and gy.stride(1) < gy.shape[2]) or (B > 1 and gy.stride(0) < 1):
+                        gy = gy.contiguous()                      # (frames of a channel consecutive, planes and clips apart)
+                    gx = torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device)     # (zero at and past lengths[i])
+                    clip.pool[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
+                    size = gy.element_size()
+                    gy_pitch, gx_pitch = (gy.stride(1), gx.stride(1)) if Cn > 1 else (0, 0)
+                    adjoint_clips_planar_device(
+                        [clip.pool[0]] * B, [gy.data_ptr() + i * gy.stride(0) * size for i in range(B)], [gy_pitch] * B, made,
+                        [gx.data_ptr() + i * gx.stride(0) * size for i in range(B)], [gx_pitch] * B, lengths, [clip.ratio] * B)
+                    return gx, None, None, None, None
+
+            _state["clip_grad"] = ClipResampleGrad
+        return _state["clip_grad"]
+
     def _schedule_batch(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last):
         n = len(resamplers)
         if not (len(d_ins) == len(n_ins) == len(d_outs) == len(caps) == len(ratios) == n):
@@ -617,7 +666,10 @@ def _bind(width):
         out_lengths) out — one resampleProcessAndFlushClipsPlanarDevice call on the tensor's own rows, no copy of the samples on the way.
         Clip i is what a fresh fixed-ratio context makes of x[i, :, :lengths[i]] with resampleProcessAndFlushPlanarDevice (its lead-in
         of half a filter length included); y[i, :, out_lengths[i]:] is zero.  Holds a pool of up to max_batch contexts, started afresh by
-        every call (one zeroing launch for all of them); a larger batch is made max_batch clips at a time."""
+        every call (one zeroing launch for all of them); a larger batch is made max_batch clips at a time.
+        Differentiable once: where x requires grad (and grad mode is on) y is attached to the graph, and backward is ONE
+        resampleAdjointClipsPlanarDevice call on the rows of grad_y (the exact transpose, tap by tap: the stage is linear) that gives a
+        gradient shaped like x, zero at and past lengths[i]; out_lengths carries no gradient.  Without gradients the call is unchanged."""
 
         def __init__(self, channels, src_rate, dst_rate, taps=380, filters=380, flags=BLACKMAN_HARRIS | SUBSAMPLE_INTERPOLATE | INCLUDE_LOWPASS,
                      max_batch=1024):
@@ -672,7 +724,10 @@ def _bind(width):
                     [self.ratio] * len(idx), from_start=True)
                 made += [g for _, g in got]
             out_lengths = torch.tensor(made, dtype=torch.int64)
-            return y[:, :, :max(made, default=0)], out_lengths
+            y = y[:, :, :max(made, default=0)]
+            if x.requires_grad and torch.is_grad_enabled():      # (the samples above are the detached call's; backward is the adjoint kernel)
+                y = _clip_resample_grad().apply(x, y, self, lengths, made)
+            return y, out_lengths
 
     def decimate_batch_device(decimators, d_ins, n_ins, d_outs):
         """decimateProcessBatchInterleavedLEDevice over a list of Decimator objects: one launch per class of work for the

@@ -236,6 +236,30 @@ typedef struct {
 } ArtSchedItem;
 size_t arthip_fir_schedule_batch_bytes (int nitems, int nblocks, int nsegs);
 int arthip_fir_schedule_batch (ArtSchedItem *items, int n, void *d_table, void *stream);
+/* ---- fir_adjoint.hip: the transpose of the whole-clip interpolator (resampleAdjointClipsPlanarDevice) ----
+ * An item is one clip: gx [0, in_frames) of every channel = the sum over the clip's outputs n, ascending, of weight (n, j) * gy [n].  The outputs
+ * are those of two planned calls from a fresh context — phase 0 the process call, phase 1 the flush — whose linear spaces hold input frame j at
+ * H + j and at H + j - in_frames (the history after the roll); the flush reads nothing below its lin_floor.  Each phase's segments are
+ * seg_count [p] entries from seg_first [p] on in the call's segment list. */
+typedef struct {
+    const art_s *bank;                   /* device, (F+1) x T */
+    const art_s *gy;                     /* gradient of the outputs: gy_frames frames, the rest of the clip's outputs count as zero */
+    art_s *gx;                           /* gradient of the inputs: in_frames frames are SET */
+    long gy_pitch, gx_pitch;             /* samples between planes; 0: that side interleaved */
+    double ratio;                        /* the effective ratio (locate: a.ratio) */
+    unsigned int outputs [2];            /* output frames of the two phases */
+    unsigned int gy_frames;
+    unsigned int tile0;                  /* first tile of the item in its launch (filled by arthip_fir_adjoint) */
+    int seg_first [2], seg_count [2];
+    int lin_floor;                       /* the flush's (INT_MIN: none) */
+    int in_frames, C, T, F;              /* in_frames > 0 */
+    int interpolate, lowpass;
+} ArtAdjItem;
+size_t arthip_fir_adjoint_bytes (int nitems, int nsegs);
+/* One launch per kernel variant present (channel-group width x interpolating or not) over the items' tiles of input frames.  The items (reordered
+ * by variant) and the nsegs segments go to d_table (device memory of arthip_fir_adjoint_bytes bytes, reused call after call: stream order protects
+ * it) in one upload.  Returns the number of launches enqueued, or -1 (a launch failed; nothing enqueued where the upload could not be made). */
+int arthip_fir_adjoint (const ArtAdjItem *items, int n, const ArtamdSegment *segs, int nsegs, void *d_table, void *stream);
 /* the upkeep every launch of a rational-ratio stream does for the rows kept across calls (arthip_fir calls it itself) */
 void arthip_fir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs);
 /* new_hist[H][C] = last H frames of (hist ++ in[0..appended)); in may be NULL => zeros appended */

@@ -52,7 +52,9 @@ __device__ __forceinline__ art_s load_frame_flat (const ArtFirArgs &a, int lin_f
 }
 
 // last segment whose first output is <= n
-__device__ __forceinline__ int find_segment (const ArtSegTable &segs, unsigned int n)
+// (Segs: ArtSegTable, or anything with its count / first [] / lin_base [] / base [] — fir_adjoint.hip's view of a table in device memory)
+template <typename Segs>
+__device__ __forceinline__ int find_segment (const Segs &segs, unsigned int n)
 {
     int lo = 0, hi = segs.count - 1;
     while (lo < hi) {
@@ -63,8 +65,9 @@ __device__ __forceinline__ int find_segment (const ArtSegTable &segs, unsigned i
 }
 
 // exact replay of the reference's per-output position arithmetic (fp64, un-fused)
-template <bool INTERP>
-__device__ __forceinline__ Pos locate (const ArtFirArgs &a, const ArtSegTable &segs, unsigned int n)
+// (Args: ArtFirArgs, or anything with its ratio and F)
+template <bool INTERP, typename Args, typename Segs>
+__device__ __forceinline__ Pos locate (const Args &a, const Segs &segs, unsigned int n)
 {
     const int e = find_segment (segs, n);
     const double step = n ? (double) n / a.ratio : 0.0;

@@ -1907,6 +1907,103 @@ int resampleProcessAndFlushClipsPlanarDevice (Resample *const *cxts, int n, cons
     return batch_entry (cxts, n, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, results, 1, fromStart != 0);
 }
 
+/* ---- the gradient of whole clips ---------------------------------------------------------------------------------------
+ * resampleAdjointClipsPlanarDevice (art_hip.h): gx = A^T gy for the linear map A the clips entry applies from a fresh start.  The host's
+ * part is the planner's: a clip's outputs are those of two calls replayed on a fresh POSITION (no context is touched) — the process
+ * call of the clip's frames, then the flush's call of silence, each with all the room it can use.  Their segments go to the device as
+ * they are; fir_adjoint.hip places every output with the forward's own locate (). */
+typedef struct { ArtamdSegment *segs; int count, cap; } AdjointSegs;
+
+/* one planned call appended to the list; returns its segment count, -1 out of memory */
+static int adjoint_plan_call (ArtamdPosition *pos, int nIn, int cap, double ratio, ResampleResult *res, int *lin_floor, AdjointSegs *list)
+{
+    for (;;) {
+        ArtamdPosition trial = *pos;
+        const int nseg = artamdPlanCall (&trial, nIn, cap, ratio, res, list->segs + list->count, list->cap - list->count, lin_floor);
+        if (nseg <= list->cap - list->count) { *pos = trial; list->count += nseg; return nseg; }
+        ArtamdSegment *grown = realloc (list->segs, sizeof (ArtamdSegment) * ((size_t) list->count + nseg + 64));
+        if (!grown) return -1;
+        list->segs = grown; list->cap = list->count + nseg + 64;
+    }
+}
+
+/* the clip of nIn frames a fresh context of cxt's parameters would make at `ratio`: both phases' outputs and segments; 0 or -1 */
+static int adjoint_plan (const Resample *cxt, int nIn, double ratio, ArtAdjItem *it, AdjointSegs *list)
+{
+    ArtamdPosition pos;
+    ResampleResult res;
+    int lin_floor;
+
+    /* (the position resampleReset leaves) */
+    pos.numTaps = cxt->numTaps; pos.numFilters = cxt->numFilters; pos.flags = cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL);
+    pos.inputIndex = cxt->numTaps; pos.floorActive = 0; pos.outputOffset = cxt->numTaps / 2; pos.fixedRatio = cxt->fixedRatio;
+
+    memset (it, 0, sizeof (*it));
+    it->seg_first [0] = list->count;
+    if ((it->seg_count [0] = adjoint_plan_call (&pos, nIn, INT_MAX, ratio, &res, &lin_floor, list)) < 0) return -1;
+    it->outputs [0] = res.output_generated;
+    if ((int) res.input_used != nIn) return -1;        /* (cannot happen with that much room) */
+    it->seg_first [1] = list->count;
+    if ((it->seg_count [1] = adjoint_plan_call (&pos, -1, INT_MAX - (int) it->outputs [0], ratio, &res, &lin_floor, list)) < 0) return -1;
+    it->outputs [1] = res.output_generated;
+    it->lin_floor = lin_floor;
+
+    it->bank = cxt->hip->d_bank;
+    it->ratio = (cxt->flags & RESAMPLE_FIXED_RATIO) ? cxt->fixedRatio : ratio;
+    it->in_frames = nIn; it->C = cxt->numChannels; it->T = cxt->numTaps; it->F = cxt->numFilters;
+    it->interpolate = (cxt->flags & SUBSAMPLE_INTERPOLATE) != 0;
+    it->lowpass = (cxt->flags & INCLUDE_LOWPASS) != 0;
+    return 0;
+}
+
+int resampleAdjointClipsPlanarDevice (Resample *const *cxts, int n,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
+        artsample_t *const *d_gradInputs, const long *gradInputPitches, const int *numInputFrames,
+        const double *ratios)
+{
+    if (n <= 0) return 0;
+    if (!cxts || !d_gradOutputs || !numOutputFrames || !d_gradInputs || !numInputFrames || !ratios) return -1;
+    for (int i = 0; i < n; ++i) if (!cxts [i]) return -1;
+
+    struct artamd_resampler *lead = cxts [0]->hip;
+    for (int i = 0; i < n; ++i) {
+        const struct artamd_resampler *hip = cxts [i]->hip;
+        if (numInputFrames [i] < 0 || numOutputFrames [i] < 0) return -1;
+        if (numInputFrames [i] > 0 && (!d_gradOutputs [i] || !d_gradInputs [i])) return -1;
+        if ((cxts [i]->flags & EXTRAPOLATE_ENDPOINTS) || hip->nshards || hip->device != lead->device || hip->stream != lead->stream) return -1;
+    }
+
+    /* every item is planned (numOutputFrames [i] <= M_i is asked of an empty clip too); the empty ones are no items of the launches */
+    ArtAdjItem *items = malloc (sizeof (ArtAdjItem) * (size_t) n);
+    AdjointSegs list = { NULL, 0, 0 };
+    int live = 0, rc = -1, refused = 0;
+    if (!items) goto out;
+    for (int i = 0; i < n; ++i) {
+        ArtAdjItem *it = &items [live];
+        const int kept = list.count;
+        if (adjoint_plan (cxts [i], numInputFrames [i], ratios [i], it, &list)) goto out;
+        if ((unsigned long) numOutputFrames [i] > (unsigned long) it->outputs [0] + it->outputs [1]) { refused = 1; goto out; }
+        if (!numInputFrames [i]) { list.count = kept; continue; }
+        it->gy = d_gradOutputs [i]; it->gy_pitch = gradOutputPitches ? gradOutputPitches [i] : 0; it->gy_frames = (unsigned int) numOutputFrames [i];
+        it->gx = d_gradInputs [i]; it->gx_pitch = gradInputPitches ? gradInputPitches [i] : 0;
+        ++live;
+    }
+    if (!live) { rc = 0; goto out; }
+
+    {
+        ENTER_DEVICE (lead);
+        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_adjoint_bytes (live, list.count));
+        rc = lead->d_batch ? arthip_fir_adjoint (items, live, list.segs, list.count, lead->d_batch, lead->stream) : -1;
+        if (rc < 0) fprintf (stderr, "artamd: resample adjoint: launch failed: %s\n", arthip_last_error ());
+        LEAVE_DEVICE (lead);
+    }
+out:
+    if (rc < 0 && !refused) artamd_note_failure ("resampler: a launch of the clips adjoint failed");
+    free (items);
+    free (list.segs);
+    return rc;
+}
+
 /* ---- consecutive blocks of one stream, one launch --------------------------------------------------------------------
  * An ASRC loop makes a call per block with that block's ratio; each call is a launch with its own planning, staging and launch floor.
  * Where the caller knows the next blocks' ratios, resampleProcessScheduleInterleavedDevice plans them one after the other on the context

@@ -273,6 +273,39 @@ int resampleProcessAndFlushBatchPlanarDevice (Resample *const *cxts, int n, cons
 int resampleProcessAndFlushClipsPlanarDevice (Resample *const *cxts, int n, const artsample_t *const *d_inputs, const long *inputPitches,
                                               const int *numInputFrames, artsample_t *const *d_outputs, const long *outputPitches,
                                               const int *numOutputFrames, const double *ratios, int fromStart, ResampleResult *results);
+/* The gradient of whole clips: the adjoint (transpose) of what the clips entry above computes.  Per channel, let A_i be the linear map
+ * x [numInputFrames [i]] -> y [M_i] that resampleProcessAndFlushClipsPlanarDevice (..., fromStart = 1, ...) applies, with enough room, to a
+ * context of the taps, filters, low-pass, flags and fixed ratio of cxts [i] at ratios [i]: the context as resampleReset leaves it, the process
+ * call, then the flush; M_i is their total output.  Frames 0 .. numInputFrames [i] - 1 of every plane of d_gradInputs [i] are SET to
+ * A_i^T gy_i, where gy_i is the first numOutputFrames [i] frames of d_gradOutputs [i]; the output frames from numOutputFrames [i] up to M_i
+ * count as zero gradient (a forward call whose cap cut it short).  Nothing else is written.
+ * Pitches as in the sibling entries: in samples, 0 for an interleaved side of an item, a NULL array for "every item is", any pitch and base
+ * alignment the sample type allows, a one-channel context the same call in either layout.
+ * Every output's position — window start ip - T/2 + 1, filter row fi, frac — is the one the forward kernels' own locate () (fir_common.hip.h)
+ * gives it from the planner's segments: two artamdPlanCall replays from a fresh position (the process call, then the flush's call of silence),
+ * no context touched.  The weight of output n on input j, k = j - (ip (n) - T/2 + 1):
+ *   interpolating     w = (artsample_t)((double) h [fi][k] * (1.0 - frac) + (double) h [fi+1][k] * frac)
+ *   nearest filter    w = h [fi][k]; without a low-pass and with fi % F == 0 the reference's pass-through: 1 on the sample it copies, 0 elsewhere
+ * and gx [j] = sum over n, ascending, of w * gy [n], one fused multiply-add per term in artsample_t (fir_adjoint.hip is compiled with
+ * -ffp-contract=off: nothing else is fused).  (The kernel takes the outputs in groups of four without a branch: between a frame's own terms it
+ * may add w * gy [n] with w = 0 for an output of the group whose window does not hold the frame, which leaves a sum of finite terms bit for
+ * bit as it was; a non-finite gy [n] may so reach frames next to its window, as it would in a dense product.)  There is ONE arithmetic: the mode flags that only choose the forward's (RESAMPLE_STRICT_ORDER,
+ * EXTEND_CONVOLUTION_MATH, the kernel preference, the cut-invariant policy) change nothing here, and gx [j] is the same bit for bit whatever
+ * the batch, the item's place in it, the layout, the pitch or the tile of input frames it falls into.  The kernel gathers — a workgroup owns a
+ * tile of consecutive input frames and walks the contiguous range of outputs whose windows touch it — so there are no atomics.
+ * The contexts are only READ (bank pointer and parameters): no position, history, flag, kept row or resampleHipLast* report changes, and a
+ * context may appear any number of times (one context can serve a whole batch).
+ * Asynchronous on the stream of cxts [0]; one launch per kernel variant present (channel-group width 1, 2, 4, 8 x interpolating or not),
+ * whatever n; the table rides in the lead context's batch table: no allocation once warm.
+ * Returns the number of launches enqueued; 0 for n <= 0 and for a list whose every item has numInputFrames [i] == 0 (such an item writes
+ * nothing).  -1 with nothing enqueued and nothing counted for a NULL context, a NULL buffer of an item with numInputFrames [i] > 0, a negative
+ * count, numOutputFrames [i] > M_i, a context with EXTRAPOLATE_ENDPOINTS (its end-point fits are not linear), a sharded context, a context
+ * on another device or stream than cxts [0].  -1 if a launch failed (counted in artamdErrorCount): the gradient buffers are then unspecified.
+ * Gradient inputs must not overlap gradient outputs (not checked). */
+int resampleAdjointClipsPlanarDevice (Resample *const *cxts, int n,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
+        artsample_t *const *d_gradInputs, const long *gradInputPitches, const int *numInputFrames,
+        const double *ratios);
 
 /* ---- host-only building blocks (no GPU needed; used by the CPU test-suite) ---- */
 /* (numFilters+1) x numTaps bank exactly as resampleInit builds it (reference resampler.c:149-168, 1090-1133) */

@@ -74,6 +74,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc (const void *base, u
     return __builtin_amdgcn_make_buffer_rsrc (const_cast<void *> (base), 0, (int) bytes, 0x00020000);
 }
 
+// Store policies of the matrix kernels' bulk stores: the aux argument of the raw buffer stores (gfx940+: bit 0 sc0, bit 1 nt, bit 4 sc1).
+// 0 = write-back: the lines stay dirty in the writing XCD's L2 until something evicts them or the kernel ends; sc1 = written through to memory.
+// One constant per site, each the winner of its own alternating A/B on one box (tools/micro/store_policy_ab.sh; all runs: profiles/store_policy.txt).
+constexpr int ST_SLAB_OUT = 16;           // fir_i8_slab_kernel's outputs, 8 channels up: kernel 95.3 -> 89.6 us, step 124.5 -> 118.7 (8 ch x 1M frames; nt 95.4, sc0|sc1 = sc1; 4 ch: + 0.3, stays 0)
+constexpr int ST_PLANES = 16;             // the quantise pass's digit planes and head: step level at 8 ch (127.9 -> 127.7), 161.6 -> 159.8 at 32 ch x 262,144 (nt: 162.7)
+constexpr int ST_TILE32_OUT = 17;         // the 32-slot fixed-point kernels' outputs, 8 channels up: step 40.0 -> 39.0 us at 8 ch x 131,072 (sc1 39.4, nt 39.8)
+constexpr int ST_STREAM_OUT = 0;          // the f32 streaming kernels' outputs: nothing wins (8 ch x 1M: sc1 + 0.7 us, sc0|sc1 level, nt + 2.1; 2 ch 380 taps: + 2.3, + 2.3, + 8.5)
+
 template <int VEC> struct VecLoad;
 template <> struct VecLoad<1> { static __device__ __forceinline__ void load (float *dst, __amdgpu_buffer_rsrc_t r, unsigned int off) {
     dst [0] = __uint_as_float (__builtin_amdgcn_raw_buffer_load_b32 (r, (int) off, 0, 0)); } };

@@ -233,12 +233,12 @@ __device__ __forceinline__ void stage_slice (const ArtFirArgs &a, const MfmaGeom
             unsigned int sd [4], pl [4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                if constexpr (HEAD) __builtin_amdgcn_raw_buffer_store_b32 (v [k] [t], r_head, (int) voff_head, (int)((unsigned int)(4 * k * per_k + t) * row), 0);
+                if constexpr (HEAD) __builtin_amdgcn_raw_buffer_store_b32 (v [k] [t], r_head, (int) voff_head, (int)((unsigned int)(4 * k * per_k + t) * row), ST_PLANES);
                 sd [t] = digits_of (__float2int_rn (ldexpf (__uint_as_float (v [k] [t]), shift)));   // (a channel with an infinity or a NaN: garbage, the launch is flagged)
             }
             to_planes (sd, pl);
 #pragma unroll
-            for (int pn = 0; pn < 4; ++pn) __builtin_amdgcn_raw_buffer_store_b32 (pl [pn], r_out, (int) voff_out, (int)((unsigned int) pn * q.eb_plane_bytes + (unsigned int)(k * per_k) * row), 0);
+            for (int pn = 0; pn < 4; ++pn) __builtin_amdgcn_raw_buffer_store_b32 (pl [pn], r_out, (int) voff_out, (int)((unsigned int) pn * q.eb_plane_bytes + (unsigned int)(k * per_k) * row), ST_PLANES);
         }
     }
 }
@@ -750,18 +750,13 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
             matrix_roll (a.roll_dst, a.hist, a.in, a.in_frames, a.H, a.C, a.roll_appended, e);
     }
     const int W = sl.wgs_per_xcd;
-    // (stand-by: as fir_i8_stream_kernel — the f32 streaming kernel's tile loop on this kernel's workgroups and LDS)
-    if (*q.flag == q.epoch) {
-        constexpr int MF_PPW = MF_COLS / CG > MF_MAX_PPW ? MF_MAX_PPW : MF_COLS / CG;
-        (void) MF_PPW;
-        stand_by_tiles<CG, PASS> (a, g, W, *reinterpret_cast<float (*) [2] [32 * MF_LD]> (&smem_ [0]), *reinterpret_cast<float (*) [2] [MF_COLS * MF_LD]> (&smem_ [SL_BUF]));
-        return;
-    }
+    // (the stand-by flag: written by the quantise pass, read-only here — through the scalar cache, issued with the tile table's loads below and
+    // examined behind the first chunk's pieces: a vector load and a branch on it here put a memory round trip in front of everything else)
+    const unsigned int flag_v = *(const __attribute__ ((address_space (4))) unsigned int *) q.flag;
 
     const int xcd = blockIdx.x & 7, rank = blockIdx.x >> 3;
     const int nsub = q.ktot / I8_KC, nch = (nsub + 1) >> 1;    // 32-tap images per tile; 64-tap chunks (the last may hold one image)
-    const int L = sl.live [xcd];
-    if (L <= 0) return;
+    const int L = max (sl.live [xcd], 0);                     // (a workgroup without a tile goes through the prologue with an empty stream: its pieces fetch nothing)
     // ---- this workgroup's work: D whole tiles (rank, rank + W, ...), then chunks [lo, hi) of the run of S tiles behind them
     int D, S;
     {
@@ -773,7 +768,6 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
     const int lo = S && rank < Weff ? (rank * Ct) / Weff : 0, hi = S && rank < Weff ? ((rank + 1) * Ct) / Weff : 0;
     const int t_first = lo / nch, t_last = hi > lo ? (hi - 1) / nch : t_first - 1;
     const int nseg = D + (t_last - t_first + 1);
-    if (nseg == 0) return;
     // segment k -> tile of the XCD's list and its chunks [c0, c1)
     auto segment = [&] (int k, int &within, int &c0, int &c1) {
         if (k < D) { within = rank + k * W; c0 = 0; c1 = nch; }
@@ -885,6 +879,17 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
     next_chunk ();
 #pragma unroll
     for (int idx = 0; idx < 10; ++idx) piece (0, idx);
+    // (stand-by: as fir_i8_stream_kernel — the f32 streaming kernel's tile loop on this kernel's workgroups and LDS, once the pieces in flight to it have landed)
+    if (flag_v == q.epoch) {
+        constexpr int MF_PPW = MF_COLS / CG > MF_MAX_PPW ? MF_MAX_PPW : MF_COLS / CG;
+        (void) MF_PPW;
+        asm volatile ("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier ();
+        asm volatile ("" ::: "memory");
+        stand_by_tiles<CG, PASS> (a, g, W, *reinterpret_cast<float (*) [2] [32 * MF_LD]> (&smem_ [0]), *reinterpret_cast<float (*) [2] [MF_COLS * MF_LD]> (&smem_ [SL_BUF]));
+        return;
+    }
+    if (nseg == 0) return;
     asm volatile ("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier ();                            // chunk 0 has landed
     asm volatile ("" ::: "memory");
@@ -1133,10 +1138,11 @@ void fir_i8_slab_kernel (ArtFirArgs a, MfmaGeom g, I8Geom q, I8Slab sl)
                     }
                     u32x4 v; v.x = t [0]; v.y = t [1]; v.z = t [2]; v.w = t [3];
                     const int i_const = h * 32 + 8 * rb;      // compile-time part of the slot
-                    const int i = i_const + 4 * (lane >> 5) + qm;
+                    const int i = i_const + 4 * (lane_e >> 5) + qm;
                     // (a slot past the period goes out of the resource's range, as frames at or past n_end do, and is dropped)
-                    const unsigned int off = i < rows_valid && (i >= lo || (lane & 31) >= CG) ? q_off + (unsigned int)(i_const * CG) * 4u : 0xfffffff0u;
-                    __builtin_amdgcn_raw_buffer_store_b128 (v, rs_out, (int) off, 0, 0);
+                    const unsigned int off = i < rows_valid && (i >= lo || (lane_e & 31) >= CG) ? q_off + (unsigned int)(i_const * CG) * 4u : 0xfffffff0u;
+                    // (a 4-channel stream's quad writes 64 contiguous bytes, half a line: written through they cost the kernel 0.8 us of 56 at 1M frames — default there)
+                    __builtin_amdgcn_raw_buffer_store_b128 (v, rs_out, (int) off, 0, CG >= 8 ? ST_SLAB_OUT : 0);
                 }
         }
     }

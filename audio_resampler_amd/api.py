@@ -150,6 +150,7 @@ def _bind(width):
         "biquadBankApplyPlanarDevice": (None, [ptr, ptr, C.c_long, C.c_int]),
         "biquadBankApplyBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr]),
         "biquadBankApplyClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, C.c_int]),
+        "biquadBankFilterClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, C.c_int]),
         "biquadBankReset": (None, [ptr]),
         "decimateHipSetStream": (None, [DP, ptr]),
         "decimateProcessInterleavedLEDevice": (None, [DP, ptr, C.c_int, ptr]),
@@ -865,6 +866,67 @@ def _bind(width):
             raise RuntimeError("biquadBankApplyClipsPlanarDevice failed")
         return rc
 
+    def biquad_filter_clips_planar_device(banks, d_ins, in_pitches, d_outs, out_pitches, frames, reversed=False):
+        """biquadBankFilterClipsPlanarDevice: whole clips out of place from the banks' first state — item i: frames 0 .. frames[i]-1 of
+        every channel of d_outs[i] are what a fresh bank of banks[i]'s sections makes of d_ins[i] (which is only read); reversed: with
+        time running backwards, which is the transpose of the forward map (its gradient).  Pitches as in biquad_clips_planar_device,
+        one list per side.  The banks are only read, and one may be listed any number of times.  Returns the launch count (raises if
+        the call returned -1)."""
+        n = len(banks)
+        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
+        rc = lib().biquadBankFilterClipsPlanarDevice(
+            (C.c_void_p * n)(*[b.p for b in banks]), n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), pitches(in_pitches),
+            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches), (C.c_int * n)(*[int(v) for v in frames]),
+            1 if reversed else 0)
+        if rc < 0:
+            raise RuntimeError("biquadBankFilterClipsPlanarDevice failed")
+        return rc
+
+    def _clip_filter_rows(bank, src, dst, lengths, reversed):
+        """one biquad_filter_clips_planar_device call on the rows of src [B, C, T] into those of dst, `bank` listed B times"""
+        B, Cn, _ = src.shape
+        size = src.element_size()
+        src_pitch, dst_pitch = (src.stride(1), dst.stride(1)) if Cn > 1 else (0, 0)     # (one channel: the same call in either layout)
+        return biquad_filter_clips_planar_device(
+            [bank] * B, [src.data_ptr() + i * src.stride(0) * size for i in range(B)], [src_pitch] * B,
+            [dst.data_ptr() + i * dst.stride(0) * size for i in range(B)], [dst_pitch] * B, lengths, reversed=reversed)
+
+    def _rows_apart(t):
+        """frames of a channel consecutive, planes and clips apart: what the planar entries take as it is"""
+        B, Cn, T = t.shape
+        return not ((T and t.stride(2) != 1) or (Cn > 1 and t.stride(1) < T) or (B > 1 and t.stride(0) < max(Cn * T, 1)))
+
+    def _clip_filter_grad():
+        """the torch.autograd.Function that attaches a ClipFilter's out-of-place output to the graph (made on first use: torch is
+        imported late)"""
+        if "filter_grad" not in _state:
+            import torch
+
+            class ClipFilterGrad(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, x, y, clip, lengths):
+                    ctx.clip, ctx.lengths = clip, lengths
+                    return y.view_as(y)
+
+                @staticmethod
+                @torch.autograd.function.once_differentiable
+                def backward(ctx, gy):
+                    clip, lengths = ctx.clip, ctx.lengths
+                    if not clip.pool:
+                        raise RuntimeError("the ClipFilter was closed before backward")
+                    if not _rows_apart(gy):
+                        gy = gy.contiguous()
+                    T = gy.shape[2]
+                    # frames at and past lengths[i] went through as they were: so does their gradient
+                    gx = gy.clone(memory_format=torch.contiguous_format) if any(v < T for v in lengths) else \
+                        torch.empty(gy.shape, dtype=gy.dtype, device=gy.device)
+                    clip.pool[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
+                    _clip_filter_rows(clip.pool[0], gy, gx, lengths, True)
+                    return gx, None, None, None
+
+            _state["filter_grad"] = ClipFilterGrad
+        return _state["filter_grad"]
+
     class ClipFilter:
         """Whole clips, channels-first, through a cascade of one to four second-order sections, IN PLACE: x [B, C, T] (or [C, T]) on the
         GPU in, the same tensor out — one biquadBankApplyClipsPlanarDevice call on the tensor's own rows, the clips' long runs in
@@ -872,7 +934,14 @@ def _bind(width):
         of the sample rate; gain 1.0); ART's -p is two low-passes at one frequency.  Clip i is what a fresh bank makes of
         x[i, :, :lengths[i]]; x[i, :, lengths[i]:] is not touched.  Holds a pool of up to max_batch banks, reset for every call, on the
         caller's current torch stream; a larger batch is made max_batch clips at a time.  Takes and gives what ClipResampler and
-        ClipDecimator take."""
+        ClipDecimator take.
+
+        Differentiable: when x requires grad (and grad mode is on) x is NOT written.  The call returns a new tensor with exactly the
+        values the in-place call would have left in x (x[i, :, lengths[i]:] copied through), made by one
+        biquadBankFilterClipsPlanarDevice call that lists the pool's first bank once per clip and attached to the graph by a
+        once-differentiable autograd.Function.  Its backward is the same entry with time reversed on the rows of grad_y — the exact
+        transpose of the forward map, from the same kernels — with the gradient at and past lengths[i] passed through; it raises
+        after close().  A non-contiguous x is taken through .contiguous() on this path."""
 
         def __init__(self, channels, sections, max_batch=1024):
             sections = list(sections)
@@ -901,12 +970,25 @@ def _bind(width):
                 x = x.unsqueeze(0)
             if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
                 raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
-            if x.shape[2] and x.stride(2) != 1:
+            tracked = x.requires_grad and torch.is_grad_enabled()
+            if x.shape[2] and x.stride(2) != 1 and not tracked:
                 raise ValueError("in place: the frames of a channel must be consecutive (stride 1 along T)")
             B, Cn, T = x.shape
             lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
             if len(lengths) != B or any(v < 0 or v > T for v in lengths):
                 raise ValueError("lengths: one entry per clip, 0 .. T")
+            if tracked:
+                # out of place, for autograd: x and everything the graph saved stay as they are
+                if not self.pool:
+                    self.pool.append(BiquadBank(self._sections, Cn, self.nsections))
+                self.pool[0].set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+                src = x if _rows_apart(x) else x.contiguous()
+                with torch.no_grad():
+                    y = src.clone(memory_format=torch.contiguous_format) if any(v < T for v in lengths) else \
+                        torch.empty(src.shape, dtype=src.dtype, device=src.device)
+                    self.launches = _clip_filter_rows(self.pool[0], src, y, lengths, False) if B else 0
+                y = _clip_filter_grad().apply(src, y, self, lengths)
+                return y[0] if whole.dim() == 2 else y
             while len(self.pool) < min(B, self.max_batch):
                 self.pool.append(BiquadBank(self._sections, Cn, self.nsections))
             stream = torch.cuda.current_stream(x.device).cuda_stream

@@ -445,6 +445,23 @@ typedef struct {
 } ArtBqClipClass;
 /* spec, check and commit launch of one class; 0 or -1 */
 int arthip_biquad_clips_launch (const ArtBqClipClass *cls, const void *d_table, void *stream);
+/* Many whole clips OUT OF PLACE from the banks' first state, forwards or with time reversed (biquadBankFilterClipsPlanarDevice).
+ * The time-parallel items are ArtBqClip records in ArtBqClipClass classes again, with these differences: `from` is the bank's
+ * d_sections0 and `sections` is NULL (nothing is stored back), `in` is the caller's input where it lies, `first_bad` points behind
+ * the item's own `states` (C ints, armed by the spec launch) and `repairs` is the leading bank's counter.  Reversed: frame n of
+ * the recurrence lives at address frames - 1 - n on both sides.  Spec, check and commit launch of one class; 0 or -1 */
+int arthip_biquad_filter_clips_launch (const ArtBqClipClass *cls, const void *d_table, int reversed, void *stream);
+/* ... and their serial route: a lane is one channel of one item, read at `in` and written at `out` */
+typedef struct {
+    const Biquad *sections;              /* the bank's d_sections0 + channel * S: only read */
+    const art_s *in;                     /* the item's input + channel (or plane); frame f at in [f * in_stride] */
+    art_s *out;                          /* likewise */
+    int in_stride, out_stride, frames;   /* frames 0: an empty lane (padding of the last workgroup) */
+} ArtBqFilterLane;
+int arthip_biquad_filter_batch_launch (const ArtBqClass *cls, const void *d_table, int reversed, void *stream);
+/* biquadBankFilterClipsPlanarDevice with a byte bound per round (roundBytes > 0; else the library's): the tests' three rounds — pcm_host.c */
+int artamd_biquad_filter_clips_planar (BiquadBank *const *banks, int n, const artsample_t *const *d_ins, const long *in_pitches,
+                                       artsample_t *const *d_outs, const long *out_pitches, const int *numFrames, int reversed, long roundBytes);
 typedef struct {                         /* one strided copy of a grouped copy launch; everything in 4-byte words */
     const unsigned int *src;
     unsigned int *dst;

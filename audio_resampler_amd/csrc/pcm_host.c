@@ -318,7 +318,8 @@ struct artamd_biquad_bank {
     art_s *d_slice; size_t slice_cap;
     unsigned long batch_stamp;           /* the last batch call that named this bank */
     void *d_batch; size_t batch_cap;     /* a batch call's table, when this bank leads it */
-    /* biquadBankApplyClipsPlanarDevice, when this bank leads it: the table, the round's inputs set aside, the round's chunk states */
+    /* biquadBankApplyClipsPlanarDevice, when this bank leads it: the table, the round's inputs set aside, the round's chunk states
+     * (biquadBankFilterClipsPlanarDevice: the table and the chunk states with the items' mismatch flags; nothing is set aside) */
     void *d_clips; size_t clips_cap;
     void *d_clips_tmp; size_t clips_tmp_cap;
     void *d_clips_spec; size_t clips_spec_cap;
@@ -1514,6 +1515,170 @@ int biquadBankApplyClipsPlanarDevice (BiquadBank *const *banks, int n, artsample
                                       int fromStart)
 {
     return artamd_biquad_clips_planar (banks, n, d_buffers, pitches, numFrames, fromStart, 0);
+}
+
+/* ------------------------------------------------------------------------------------------
+ * Whole clips out of place from the banks' first state, forwards or with time reversed (biquadBankFilterClipsPlanarDevice, art_hip.h)
+ *
+ * The routes and the chunk cuts are the clips entry's (reversed: on the reversed sequence), but the kernels read the caller's input
+ * where it lies and write the caller's output: no set-aside copy, no state stored back, nothing of a bank written.  So there is no
+ * side route (a bank on another stream is only read: its first state never changes after biquadBankCreate), a lone time-parallel
+ * item goes through the gathered launches, and the serial items have a kernel of their own that reads one side and writes the other.
+ * Rounds are cut on the chunk-state bytes, the only scratch; each item's mismatch flags (C ints) lie behind its chunk states and
+ * are armed by the speculative launch.  One table for the whole call: per round its classes' items, then the serial classes' lanes.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct { int kind, round, cls, slot, chan0, K, L; long task0, in_pitch, out_pitch; size_t spec_at, flags_at; } FilterPlan;
+typedef struct { size_t spec_bytes; ArtBqClipClass cls [BQ_CLIP_CLASSES]; } FilterRound;
+
+/* samples from the first to behind the last one of an item's side */
+static size_t filter_extent (int C, long pitch, int frames) { return pitch ? (size_t)(C - 1) * (size_t) pitch + (size_t) frames : (size_t) frames * C; }
+
+int artamd_biquad_filter_clips_planar (BiquadBank *const *banks, int n, const artsample_t *const *d_ins, const long *in_pitches,
+                                       artsample_t *const *d_outs, const long *out_pitches, const int *numFrames, int reversed, long roundBytes)
+{
+    if (n <= 0) return 0;
+    if (!banks || !banks [0] || !numFrames || !d_ins || !d_outs) return -1;
+    const size_t bound = roundBytes > 0 ? (size_t) roundBytes : BQ_CLIPS_ROUND_BYTES;
+    BiquadBank *lead = banks [0];
+
+    /* the refusals: before anything is allocated or enqueued, and not counted */
+    for (int i = 0; i < n; ++i) {
+        const BiquadBank *b = banks [i];
+        if (numFrames [i] <= 0) continue;
+        if (!b || !d_ins [i] || !d_outs [i] || b->nshards || b->device != lead->device) return -1;
+        const long ip = in_pitches && b->C > 1 ? in_pitches [i] : 0, op = out_pitches && b->C > 1 ? out_pitches [i] : 0;
+        if (!ip != !op || ip < 0 || op < 0 || (ip && ip < numFrames [i]) || (op && op < numFrames [i])) return -1;
+        const uintptr_t in0 = (uintptr_t) d_ins [i], in1 = in0 + filter_extent (b->C, ip, numFrames [i]) * sizeof (art_s);
+        const uintptr_t out0 = (uintptr_t) d_outs [i], out1 = out0 + filter_extent (b->C, op, numFrames [i]) * sizeof (art_s);
+        if (in0 < out1 && out0 < in1) return -1;
+    }
+    if (lead->nshards) return -1;
+
+    FilterPlan *plan = calloc ((size_t) n, sizeof (FilterPlan));
+    FilterRound *rounds = calloc ((size_t) n + 1, sizeof (FilterRound));
+    DecLaneRef *refs = NULL;
+    unsigned char *table = NULL;
+    ArtBqClass ser [4];
+    int launches = 0, rc = -1, nrounds = 1, maxlanes = 0;
+    memset (ser, 0, sizeof (ser));
+    if (!plan || !rounds) { pcm_fail ("biquad filter clips: out of host memory"); goto out; }
+
+    /* every item's route (the clips entry's rule) and place */
+    for (int i = 0; i < n; ++i) {
+        const BiquadBank *b = banks [i];
+        FilterPlan *p = &plan [i];
+        const int frames = numFrames [i];
+        if (frames <= 0) { p->kind = CLIP_SKIP; continue; }
+        p->in_pitch = in_pitches && b->C > 1 ? in_pitches [i] : 0;              /* (one channel: the same call in either layout) */
+        p->out_pitch = out_pitches && b->C > 1 ? out_pitches [i] : 0;
+        if (frames > BQ_BATCH_SERIAL_MAX && (p->L = spec_chunk (b->S, b->warmup, frames)) != 0) {
+            p->kind = CLIP_GATHERED;
+            p->K = (frames + p->L - 1) / p->L;
+            const size_t states = arthip_biquad_spec_scratch (b->C, b->S, frames, p->L);         /* (a multiple of 32 bytes: the flags lie aligned behind it) */
+            const size_t need = (states + sizeof (int) * (size_t) b->C + 255) & ~(size_t) 255;
+            FilterRound *r = &rounds [nrounds - 1];
+            if (r->spec_bytes && r->spec_bytes + need > bound) r = &rounds [nrounds++];
+            p->round = (int)(r - rounds);
+            p->spec_at = r->spec_bytes; p->flags_at = p->spec_at + states; r->spec_bytes += need;
+            ArtBqClipClass *c = &r->cls [p->cls = 2 * (b->S - 1) + (p->in_pitch != 0)];
+            c->S = b->S; c->planar = p->in_pitch != 0;
+            p->slot = c->count++; p->task0 = c->tasks; p->chan0 = c->channels;
+            c->tasks += (long) b->C * p->K; c->channels += b->C;
+        }
+        else { p->kind = CLIP_SERIAL; ser [b->S - 1].slice.count += b->C; }
+    }
+
+    /* the table: per round its classes' items, then the serial classes' lanes (+ empty lanes up to whole workgroups); 16-byte aligned slices */
+    size_t bytes = 0, spec_need = 0;
+    for (int r = 0; r < nrounds; ++r) {
+        for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
+            rounds [r].cls [k].offset = bytes;
+            bytes += (sizeof (ArtBqClip) * (size_t) rounds [r].cls [k].count + 15) & ~(size_t) 15;
+        }
+        if (rounds [r].spec_bytes > spec_need) spec_need = rounds [r].spec_bytes;
+    }
+    for (int k = 0; k < 4; ++k) {
+        if (!ser [k].slice.count) continue;
+        ser [k].S = k + 1;
+        ser [k].slice.lanes = arthip_biquad_batch_lanes (ser [k].slice.count);
+        ser [k].slice.count = (ser [k].slice.count + ser [k].slice.lanes - 1) / ser [k].slice.lanes * ser [k].slice.lanes;
+        if (ser [k].slice.count > maxlanes) maxlanes = ser [k].slice.count;
+        ser [k].slice.offset = bytes;
+        bytes += (sizeof (ArtBqFilterLane) * (size_t) ser [k].slice.count + 15) & ~(size_t) 15;
+    }
+    if (!bytes) { rc = 0; goto out; }
+    table = calloc (1, bytes);
+    refs = malloc (sizeof (DecLaneRef) * (size_t)(maxlanes ? maxlanes : 1));
+    if (!table || !refs) { pcm_fail ("biquad filter clips: out of host memory"); goto out; }
+
+    {
+        ENTER_DEVICE (lead);
+        rc = 0;
+        lead->d_clips = arthip_grow (lead->d_clips, &lead->clips_cap, bytes);
+        if (spec_need) lead->d_clips_spec = arthip_grow (lead->d_clips_spec, &lead->clips_spec_cap, spec_need);
+        if (!lead->d_clips || (spec_need && !lead->d_clips_spec)) {
+            pcm_fail ("biquad filter clips: out of memory for the table or the chunk states (nothing launched)");
+            rc = -1;
+        }
+        for (int i = 0; i < n && !rc; ++i) {
+            const FilterPlan *p = &plan [i];
+            const BiquadBank *b = banks [i];
+            if (p->kind != CLIP_GATHERED) continue;
+            ArtBqClip *it = (ArtBqClip *)(table + rounds [p->round].cls [p->cls].offset) + p->slot;
+            it->from = b->d_sections0; it->sections = NULL;
+            it->in = d_ins [i]; it->out = d_outs [i];
+            it->in_stride = p->in_pitch ? p->in_pitch : b->C; it->out_stride = p->out_pitch ? p->out_pitch : b->C;
+            it->states = (char *) lead->d_clips_spec + p->spec_at;
+            it->first_bad = (int *)((char *) lead->d_clips_spec + p->flags_at); it->repairs = lead->d_repairs;
+            it->task0 = p->task0; it->chan0 = p->chan0;
+            it->C = b->C; it->K = p->K; it->L = p->L; it->W = b->warmup; it->frames = numFrames [i];
+        }
+        for (int k = 0; k < 4 && !rc; ++k) {
+            if (!ser [k].slice.count) continue;
+            int m = 0;
+            for (int i = 0; i < n; ++i)
+                if (plan [i].kind == CLIP_SERIAL && banks [i]->S == k + 1)
+                    for (int c = 0; c < banks [i]->C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numFrames [i]; ++m; }
+            qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
+            ArtBqFilterLane *l = (ArtBqFilterLane *)(table + ser [k].slice.offset);      /* (the padding lanes stay zero: 0 frames) */
+            for (int j = 0; j < m; ++j) {
+                const int i = refs [j].ctx, c = refs [j].channel;
+                const BiquadBank *b = banks [i];
+                const FilterPlan *p = &plan [i];
+                l [j].sections = b->d_sections0 + (size_t) c * b->S;
+                l [j].in = d_ins [i] + (p->in_pitch ? (size_t) c * p->in_pitch : (size_t) c);
+                l [j].out = d_outs [i] + (p->out_pitch ? (size_t) c * p->out_pitch : (size_t) c);
+                l [j].in_stride = p->in_pitch ? 1 : b->C; l [j].out_stride = p->out_pitch ? 1 : b->C;
+                l [j].frames = refs [j].frames;
+            }
+        }
+        if (!rc && arthip_table_upload (table, bytes, lead->d_clips, lead->stream)) {
+            pcm_fail ("biquad filter clips: the table could not be uploaded (nothing launched)");
+            rc = -1;
+        }
+        for (int k = 0; k < 4 && !rc; ++k) {
+            if (!ser [k].slice.count) continue;
+            if (arthip_biquad_filter_batch_launch (&ser [k], lead->d_clips, reversed != 0, lead->stream)) { pcm_fail ("biquad filter clips: launch failed"); rc = -1; break; }
+            ++launches;
+        }
+        for (int r = 0; r < nrounds && !rc; ++r)
+            for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
+                if (!rounds [r].cls [k].count) continue;
+                if (arthip_biquad_filter_clips_launch (&rounds [r].cls [k], lead->d_clips, reversed != 0, lead->stream)) { pcm_fail ("biquad filter clips: launch failed"); rc = -1; break; }
+                launches += 3;
+            }
+        if (!rc) rc = launches;
+        LEAVE_DEVICE (lead);
+    }
+out:
+    free (plan); free (rounds); free (refs); free (table);
+    return rc;
+}
+
+int biquadBankFilterClipsPlanarDevice (BiquadBank *const *banks, int n, const artsample_t *const *d_ins, const long *in_pitches,
+                                       artsample_t *const *d_outs, const long *out_pitches, const int *numFrames, int reversed)
+{
+    return artamd_biquad_filter_clips_planar (banks, n, d_ins, in_pitches, d_outs, out_pitches, numFrames, reversed, 0);
 }
 
 long decimateHipClipped (Decimate *cxt)

@@ -1798,6 +1798,355 @@ void bq_clips_commit_kernel (const ArtBqClip *items, int n, int channels)
                                starts, ends, (const unsigned char *)(ends + (size_t) C * K * S), a.first_bad, a.repairs);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Whole clips OUT OF PLACE from the banks' first state, forwards or with TIME REVERSED (biquadBankFilterClipsPlanarDevice): the
+// gathered passes once more, reading the caller's input where it lies (no set-aside copy) and storing no state back.  REV: frame n
+// of the recurrence lives at address frames - 1 - n on both sides, so the item's L, W and K — computed by the host as ever — cut the
+// REVERSED sequence where the forward call would cut it, and the arithmetic per frame is the forward call's in the same order.
+// From rest, that is the transpose of the forward map (art_hip.h).  The bodies below are COPIES of spec_run_plane, spec_run,
+// spec_warm_up, spec_task and commit_channel with a direction (the forward direction calls spec_run itself): the existing kernels
+// keep their text, and with it their instructions and register rows (profiles/biquad_filter_clips.txt).
+// The check pass has no direction and no buffers: bq_clips_check_kernel is launched as it is.  An item's first_bad lies behind its
+// own chunk states and is armed by the spec pass (task k = 0 of every channel), the launch before the check.
+// ---------------------------------------------------------------------------------------------------
+
+// spec_run_plane with time reversed: the addresses [lo, hi) of a plane walked DOWNWARDS from hi - 1.  Cut at the 16-byte boundaries
+// of the run's own address: single frames down to the first boundary, batches of U frames by 16-byte loads below it (two batches in
+// flight), single frames under the last whole batch; 16-byte stores where `out` is aligned as `in` is.  Within a batch the frames
+// are taken from the highest address down.
+template <int ACTIVE, bool STORE>
+__device__ __forceinline__ void rev_run_plane (SectionRegs *r, const art_s *in, art_s *out, int lo, int hi)
+{
+    constexpr int U = 8, Q = 16 / (int) sizeof (art_s);                   // Q frames to 16 bytes
+    typedef art_s vecq __attribute__ ((ext_vector_type (Q)));
+    auto one = [&] (int a) {
+        art_s v = in [a];
+#pragma unroll
+        for (int s = 0; s < ACTIVE; ++s) v = step_buffer_order (r [s], v);
+        if constexpr (STORE) out [a] = v;
+    };
+    int p = hi;                                                           // everything from p up is done
+    const int head = min (hi - lo, (int)(((uintptr_t)(in + hi) / sizeof (art_s)) & (Q - 1)));
+    for (const int e = hi - head; p > e; ) { --p; one (p); }
+    bool whole = false;                                                   // (in + p is on a boundary now, or p == lo)
+    if constexpr (STORE) whole = !((uintptr_t)(out + p) & 15);
+    auto fetch = [&] (art_s (&v) [U], int top) {                          // the U frames under `top`, v [j] from address top - U + j
+#pragma unroll
+        for (int q = 0; q < U / Q; ++q) {
+            const vecq t = *reinterpret_cast<const vecq *> (in + top - U + q * Q);
+#pragma unroll
+            for (int j = 0; j < Q; ++j) v [q * Q + j] = t [j];
+        }
+    };
+    auto work = [&] (art_s (&v) [U], int top) {
+#pragma unroll
+        for (int u = U - 1; u >= 0; --u) {
+#pragma unroll
+            for (int s = 0; s < ACTIVE; ++s) v [u] = step_buffer_order (r [s], v [u]);
+        }
+        if constexpr (STORE) {
+            if (whole) {
+#pragma unroll
+                for (int q = 0; q < U / Q; ++q) {
+                    vecq t;
+#pragma unroll
+                    for (int j = 0; j < Q; ++j) t [j] = v [q * Q + j];
+                    *reinterpret_cast<vecq *> (out + top - U + q * Q) = t;
+                }
+            }
+            else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) out [top - U + u] = v [u];
+            }
+        }
+    };
+    const int batches = (p - lo) / U;
+    if (batches > 0) {
+        art_s cur [U], nxt [U];
+        fetch (cur, p);
+        for (int b = 0; b < batches; ++b, p -= U) {
+            const bool more = b + 1 < batches;
+            if (more) fetch (nxt, p - U);                  // in flight while this batch's dependent chain runs
+            work (cur, p);
+            if (more) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) cur [u] = nxt [u];
+            }
+        }
+    }
+    while (p > lo) { --p; one (p); }
+}
+
+// spec_run with a direction: frames [from, to) of the recurrence of channel c of a call of `frames` frames.  Forwards it IS spec_run.
+template <int S, int ACTIVE, bool STORE, bool PLANAR, bool REV>
+__device__ __forceinline__ void dir_run (SectionRegs *r, const art_s *in, spec_stride<PLANAR> stride, art_s *out, spec_stride<PLANAR> out_stride,
+                                         int c, int from, int to, int frames)
+{
+    if constexpr (!REV) spec_run<S, ACTIVE, STORE, PLANAR> (r, in, stride, out, out_stride, c, from, to);
+    else if constexpr (PLANAR)
+        rev_run_plane<ACTIVE, STORE> (r, in + (size_t) c * stride, STORE ? out + (size_t) c * out_stride : nullptr, frames - to, frames - from);
+    else {
+        // the interleaved form of spec_run, frame n at row frames - 1 - n
+        constexpr int U = 8;
+        const int top = frames - 1;
+        auto fetch = [&] (art_s (&v) [U], int n) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) v [u] = in [(size_t)(top - n - u) * stride + c];
+        };
+        auto work = [&] (art_s (&v) [U], int n) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int s = 0; s < ACTIVE; ++s) v [u] = step_buffer_order (r [s], v [u]);
+            }
+            if (STORE) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) out [(size_t)(top - n - u) * out_stride + c] = v [u];
+            }
+        };
+        int n = from;
+        const int batches = (to - from) / U;
+        if (batches > 0) {
+            art_s cur [U], nxt [U];
+            fetch (cur, n);
+            for (int b = 0; b < batches; ++b, n += U) {
+                const bool more = b + 1 < batches;
+                if (more) fetch (nxt, n + U);              // in flight while this batch's dependent chain runs
+                work (cur, n);
+                if (more) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) cur [u] = nxt [u];
+                }
+            }
+        }
+        for (; n < to; ++n) {
+            art_s v = in [(size_t)(top - n) * stride + c];
+#pragma unroll
+            for (int s = 0; s < ACTIVE; ++s) v = step_buffer_order (r [s], v);
+            if (STORE) out [(size_t)(top - n) * out_stride + c] = v;
+        }
+    }
+}
+
+// spec_warm_up with a direction
+template <int S, bool PLANAR, bool REV, int J = 0>
+__device__ __forceinline__ void dir_warm_up (SectionRegs *r, const art_s *in, spec_stride<PLANAR> stride, int c, int begin, int W, int frames)
+{
+    if constexpr (J < S) {
+        dir_run<S, J + 1, false, PLANAR, REV> (r, in, stride, nullptr, 0, c, begin + J * W, begin + (J + 1) * W, frames);
+        dir_warm_up<S, PLANAR, REV, J + 1> (r, in, stride, c, begin, W, frames);
+    }
+}
+
+// spec_task (a copy) with a direction
+template <int S, bool PLANAR, bool REV>
+__device__ __forceinline__ void filter_spec_task (const Biquad *sections, int c, int k, int K, int L, int W, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
+                                                  spec_stride<PLANAR> out_stride, int frames, SpecState *starts, SpecState *ends)
+{
+    const int first = k * L, last = min (first + L, frames);
+
+    SectionRegs r [S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) load_section (r [s], sections [(size_t) c * S + s]);
+
+    const int begin = first - S * W;
+    if (begin > 0) {
+        // speculative start: silence behind every section
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { r [s].x [q] = 0; r [s].y [q] = 0; }
+        dir_warm_up<S, PLANAR, REV> (r, in, stride, c, begin, W, frames);
+    }
+    else if (first > 0)
+        // close to the start of the sequence: from the first state through frames [0, first) — exact, nothing stored
+        dir_run<S, S, false, PLANAR, REV> (r, in, stride, nullptr, 0, c, 0, first, frames);
+
+    SpecState st [S];
+    get_state<S> (st, r);
+#pragma unroll
+    for (int s = 0; s < S; ++s) starts [((size_t) c * K + k) * S + s] = st [s];
+
+    dir_run<S, S, true, PLANAR, REV> (r, in, stride, out, out_stride, c, first, last, frames);
+
+    get_state<S> (st, r);
+#pragma unroll
+    for (int s = 0; s < S; ++s) ends [((size_t) c * K + k) * S + s] = st [s];
+}
+
+// commit_channel (a copy) with a direction and without its last part: no state goes back anywhere, and first_bad is not re-armed
+// (the next call's spec pass arms its own)
+template <int S, bool PLANAR, bool REV>
+__device__ __forceinline__ void filter_commit_channel (const Biquad *from, int c, int K, int L, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
+                                                       spec_stride<PLANAR> out_stride, int frames,
+                                                       const SpecState *starts, SpecState *ends, const unsigned char *bad, const int *first_bad, unsigned int *repairs)
+{
+    int k = first_bad [c];
+    if (k >= K) return;
+    const SpecState *st = starts + (size_t) c * K * S;
+    SpecState *en = ends + (size_t) c * K * S;
+    const unsigned char *flags = bad + (size_t) c * K;
+
+    SectionRegs r [S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) load_section (r [s], from [(size_t) c * S + s]);
+
+    unsigned int redone = 0;
+    while (k < K) {
+        // chunk k again, from the exact state its predecessor left
+        put_state<S> (r, en + (size_t)(k - 1) * S);
+        const int first = k * L, last = min (first + L, frames);
+        dir_run<S, S, true, PLANAR, REV> (r, in, stride, out, out_stride, c, first, last, frames);
+        SpecState now [S];
+        get_state<S> (now, r);
+#pragma unroll
+        for (int s = 0; s < S; ++s) en [(size_t) k * S + s] = now [s];
+        ++redone;
+        if (k + 1 >= K) break;
+        if (same_state<S> (now, st + (size_t)(k + 1) * S)) {
+            // rejoined the speculative trajectory: everything up to the next recorded mismatch stands
+            int next = k + 2;
+            while (next < K && !flags [next]) ++next;
+            k = next;
+        }
+        else ++k;
+    }
+    if (redone) atomicAdd (repairs, redone);
+}
+
+template <int S, bool PLANAR, bool REV>
+__global__ __launch_bounds__ (256)
+void bq_filter_spec_kernel (const ArtBqClip *items, int n, long tasks)
+{
+    const long task = (long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (task >= tasks) return;
+    const ArtBqClip &a = item_of (items, n, task);
+    const long t = task - a.task0;
+    const int C = a.C, K = a.K;
+    const int c = PLANAR ? (int)(t / K) : (int)(t % C), k = PLANAR ? (int)(t % K) : (int)(t / C);
+    SpecState *const starts = (SpecState *) a.states, *const ends = starts + (size_t) C * K * S;
+    if (k == 0) a.first_bad [c] = INT_MAX;
+    filter_spec_task<S, PLANAR, REV> (a.from, c, k, K, a.L, a.W, a.in, (spec_stride<PLANAR>) a.in_stride, a.out, (spec_stride<PLANAR>) a.out_stride, a.frames, starts, ends);
+}
+
+template <int S, bool PLANAR, bool REV>
+__global__ __launch_bounds__ (64)
+void bq_filter_commit_kernel (const ArtBqClip *items, int n, int channels)
+{
+    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ch >= channels) return;
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (items [mid].chan0 <= ch) lo = mid; else hi = mid - 1; }
+    const ArtBqClip &a = items [lo];
+    const int C = a.C, K = a.K;
+    SpecState *const starts = (SpecState *) a.states, *const ends = starts + (size_t) C * K * S;
+    filter_commit_channel<S, PLANAR, REV> (a.from, ch - a.chan0, K, a.L, a.in, (spec_stride<PLANAR>) a.in_stride, a.out, (spec_stride<PLANAR>) a.out_stride, a.frames,
+                                           starts, ends, (const unsigned char *)(ends + (size_t) C * K * S), a.first_bad, a.repairs);
+}
+
+// ... and their serial route: biquad_batch_pipe_kernel (a copy) over lanes that are read on one side and written on the other,
+// from sections that are only read.  bq_move_chunk with the two sides: forwards a plane on a 16-byte boundary moves 16 bytes at a
+// time on whichever side it is; reversed, frame n of a lane of `count` frames lives at address count - 1 - n, one sample at a time
+// (the lanes of a workgroup differ in count, so a tile row and a plane share no 16-byte cut).
+template <bool LOAD, bool REV>
+__device__ __forceinline__ void bq_filter_move_chunk (art_s *tile, int pitch, int lanes, int f0, int nf, int first, int step,
+                                                      const art_s *const *ins, art_s *const *outs, const int *in_strides, const int *out_strides, const int *counts)
+{
+    for (int e = first; e < nf * lanes; e += step) {
+        const int c = e / nf, f = e - c * nf;
+        const int left = counts [c] - (f0 + f);
+        if (left <= 0) continue;
+        const int stride = LOAD ? in_strides [c] : out_strides [c];
+        art_s *const t = tile + c * pitch + f;
+        if constexpr (REV) {
+            const size_t at = (size_t)(left - 1) * stride;
+            if (LOAD) *t = ins [c][at]; else outs [c][at] = *t;
+        }
+        else {
+            const size_t at = (size_t)(f0 + f) * stride;
+            if (bq_plane_aligned (LOAD ? ins [c] : outs [c], stride)) {
+                if (left >= BQ_Q - (f & (BQ_Q - 1))) {
+                    if (!(f & (BQ_Q - 1))) {
+                        if (LOAD) *reinterpret_cast<bq_vecq *> (t) = *reinterpret_cast<const bq_vecq *> (ins [c] + at);
+                        else *reinterpret_cast<bq_vecq *> (outs [c] + at) = *reinterpret_cast<const bq_vecq *> (t);
+                    }
+                    continue;
+                }
+            }
+            if (LOAD) *t = ins [c][at]; else outs [c][at] = *t;
+        }
+    }
+}
+
+template <int S, bool REV>
+__global__ __launch_bounds__ (ST_THREADS)
+void bq_filter_pipe_kernel (const ArtBqFilterLane *table, int lanes, int chunk_frames)
+{
+    extern __shared__ __attribute__ ((aligned (16))) unsigned char bq_lds [];
+    const int pitch = chunk_frames + 4, span = lanes * pitch;
+    art_s *const tiles = (art_s *) bq_lds;                                // [3][lanes][pitch]
+    __shared__ const art_s *s_in [64];
+    __shared__ art_s *s_out [64];
+    __shared__ int s_in_stride [64], s_out_stride [64], s_frames [64];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const ArtBqFilterLane *const mine = table + (size_t) blockIdx.x * lanes;
+
+    SectionRegs r [S];
+    int my_frames = 0;
+    if (tid < lanes) {
+        const ArtBqFilterLane &d = mine [tid];
+        s_in [tid] = d.in; s_out [tid] = d.out; s_in_stride [tid] = d.in_stride; s_out_stride [tid] = d.out_stride; s_frames [tid] = d.frames;
+        my_frames = d.frames;
+        if (my_frames > 0) {
+#pragma unroll
+            for (int s = 0; s < S; ++s) load_section (r [s], d.sections [s]);
+        }
+    }
+    __syncthreads ();
+    int frames = 0;
+    for (int c = 0; c < lanes; ++c) frames = max (frames, s_frames [c]);
+    const int nchunks = (frames + chunk_frames - 1) / chunk_frames;
+    constexpr int HELPERS = ST_THREADS - 64;
+
+    for (int it = -1; it <= nchunks; ++it) {
+        if (wave >= 1) {
+            const int ht = tid - 64;
+            if (it + 1 < nchunks) {                // ---- load chunk it+1
+                const int k = it + 1, f0 = k * chunk_frames;
+                bq_filter_move_chunk<true, REV> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS,
+                                                 s_in, s_out, s_in_stride, s_out_stride, s_frames);
+            }
+            if (it >= 1) {                         // ---- store chunk it-1
+                const int k = it - 1, f0 = k * chunk_frames;
+                bq_filter_move_chunk<false, REV> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS,
+                                                  s_in, s_out, s_in_stride, s_out_stride, s_frames);
+            }
+        }
+        else if (tid < lanes && it >= 0 && it < nchunks && it * chunk_frames < my_frames) {     // ---- the cascade over chunk it
+            const int f0 = it * chunk_frames, nf = min (chunk_frames, my_frames - f0);
+            art_s *row = tiles + (it % 3) * span + tid * pitch;
+            typedef art_s vec4 __attribute__ ((ext_vector_type (4)));
+            int f = 0;
+            for (; f + 4 <= nf; f += 4) {
+                vec4 v = *reinterpret_cast<const vec4 *> (row + f);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int s = 0; s < S; ++s) v [u] = step_buffer_order (r [s], v [u]);
+                *reinterpret_cast<vec4 *> (row + f) = v;
+            }
+            for (; f < nf; ++f) {
+                art_s v = row [f];
+#pragma unroll
+                for (int s = 0; s < S; ++s) v = step_buffer_order (r [s], v);
+                row [f] = v;
+            }
+        }
+        // LDS-only barrier, as in biquad_batch_pipe_kernel: nobody reads global memory that this launch writes
+        asm volatile ("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+}
+
 // Many strided copies in one launch (the gathered calls' inputs set aside, and banks' sections put back to their first state): item
 // = rows of `width` 4-byte words, row starts src_pitch / dst_pitch words apart.  A task is one 16-byte group of a row, counted from
 // the 16-byte boundary at or before the row's SOURCE address: whole groups move as one 16-byte access where the destination is on a
@@ -2183,6 +2532,47 @@ int arthip_biquad_clips_launch (const ArtBqClipClass *cls, const void *d_table, 
     switch (cls->S) { case 1: CLIPS_LAYOUT (1); break; case 2: CLIPS_LAYOUT (2); break; case 3: CLIPS_LAYOUT (3); break; default: CLIPS_LAYOUT (4); }
 #undef CLIPS_LAYOUT
 #undef CLIPS_GO
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// the same three launches out of place and with a direction (biquadBankFilterClipsPlanarDevice): the spec pass arms the items' flags
+int arthip_biquad_filter_clips_launch (const ArtBqClipClass *cls, const void *d_table, int reversed, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    const ArtBqClip *items = (const ArtBqClip *)((const char *) d_table + cls->offset);
+    const int n = cls->count, channels = cls->channels;
+    const long tasks = cls->tasks;
+    if (n <= 0) return 0;
+    if (cls->S < 1 || cls->S > MAX_CHAIN || tasks <= 0 || channels <= 0) return -1;
+    const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256), cgrid ((unsigned int)((channels + 63) / 64)), cblock (64);
+#define FILTER_GO(SS, PL, RV) do { \
+        hipLaunchKernelGGL ((bq_filter_spec_kernel<SS, PL, RV>), grid, block, 0, st, items, n, tasks); \
+        hipLaunchKernelGGL (bq_clips_check_kernel<SS>, grid, block, 0, st, items, n, tasks); \
+        hipLaunchKernelGGL ((bq_filter_commit_kernel<SS, PL, RV>), cgrid, cblock, 0, st, items, n, channels); } while (0)
+#define FILTER_DIR(SS, PL) do { if (reversed) FILTER_GO (SS, PL, true); else FILTER_GO (SS, PL, false); } while (0)
+#define FILTER_LAYOUT(SS) do { if (cls->planar) FILTER_DIR (SS, true); else FILTER_DIR (SS, false); } while (0)
+    switch (cls->S) { case 1: FILTER_LAYOUT (1); break; case 2: FILTER_LAYOUT (2); break; case 3: FILTER_LAYOUT (3); break; default: FILTER_LAYOUT (4); }
+#undef FILTER_LAYOUT
+#undef FILTER_DIR
+#undef FILTER_GO
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// ... and one launch of one serial class of it (ArtBqFilterLane lanes), sized as arthip_biquad_batch_launch sizes its own
+int arthip_biquad_filter_batch_launch (const ArtBqClass *cls, const void *d_table, int reversed, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    const ArtBqFilterLane *items = (const ArtBqFilterLane *)((const char *) d_table + cls->slice.offset);
+    const int L = cls->slice.lanes;
+    if (cls->slice.count <= 0) return 0;
+    if (L < 1 || L > 64 || cls->slice.count % L || cls->S < 1 || cls->S > 4) return -1;
+    const int chunk_frames = batch_chunk_frames (L, BQ_BATCH_RUN);
+    const size_t lds = (size_t) 3 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 3 DEC_CHUNK samples (48 KiB)
+    const dim3 grid ((unsigned int)(cls->slice.count / L)), block (ST_THREADS);
+#define FILTER_PIPE(SS) do { if (reversed) hipLaunchKernelGGL ((bq_filter_pipe_kernel<SS, true>), grid, block, lds, st, items, L, chunk_frames); \
+                             else hipLaunchKernelGGL ((bq_filter_pipe_kernel<SS, false>), grid, block, lds, st, items, L, chunk_frames); } while (0)
+    switch (cls->S) { case 1: FILTER_PIPE (1); break; case 2: FILTER_PIPE (2); break; case 3: FILTER_PIPE (3); break; default: FILTER_PIPE (4); }
+#undef FILTER_PIPE
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 

@@ -405,6 +405,27 @@ int biquadBankApplyBatchPlanarDevice (BiquadBank *const *banks, int n, artsample
  * of the rounds behind it. */
 int biquadBankApplyClipsPlanarDevice (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches,
                                       const int *numFrames, int fromStart);
+/* Whole clips OUT OF PLACE, forwards or with time reversed: what autograd needs of the stage above (ClipFilter).  Frames
+ * 0 .. numFrames [i] - 1 of every channel of d_outs [i] are set to what a bank with banks [i]'s sections, in the state
+ * biquadBankCreate left (the first state fromStart reads), makes of d_ins [i]; d_ins [i] is only read.  reversed != 0: time runs
+ * backwards — frame numFrames [i] - 1 - m of the output is, bit for bit, frame m of what that fresh bank makes of the sequence
+ * u [m] = in [numFrames [i] - 1 - m].  From rest that is the TRANSPOSE of the forward map of the whole clip (a cascade from rest
+ * is a product of lower-triangular Toeplitz matrices; they commute, and time reversal on both sides transposes each), so it is the
+ * gradient of the forward call.  Pitches as in biquadBankApplyClipsPlanarDevice (0: interleaved; a NULL list: every item is); the
+ * two sides' pitches of an item may differ, but both are zero or both are not, unless the bank has one channel.
+ * The banks are only READ: no section state, index, mismatch flag or repairs counter of banks [i] is written, so a bank may be
+ * listed any number of times (one bank for a whole batch), also while it is in the middle of a stream of its own.  The routes are
+ * the clips entry's: more than 512 frames and at least two chunks of a filter that forgets is time-parallel (the chunk cuts of the
+ * forward call, made on the reversed sequence when reversed; one speculative, one check and one commit launch per section count and
+ * layout, a lone item too), everything else one serial launch per section count.  No copy launch: the kernels read the input where
+ * it lies.  The chunk states and the items' mismatch flags live in scratch of banks [0], in rounds of at most 128 MiB of chunk
+ * states; chunks that had to be recomputed are added to biquadBankRepairs (banks [0]).  Asynchronous on the stream of banks [0].
+ * Returns the number of kernel launches enqueued (0: nothing to do); numFrames [i] <= 0 is skipped.  -1 with nothing enqueued and
+ * nothing counted: a NULL bank or buffer of an item with frames, a sharded bank, a bank on another device than banks [0], an item
+ * with one side planar and one interleaved (or a pitch that is negative or smaller than its frame count), an item whose input and
+ * output ranges overlap.  -1, counted in artamdErrorCount: memory ran out or a launch failed. */
+int biquadBankFilterClipsPlanarDevice (BiquadBank *const *banks, int n, const artsample_t *const *d_ins, const long *in_pitches,
+                                       artsample_t *const *d_outs, const long *out_pitches, const int *numFrames, int reversed);
 /* Puts every section's delay lines and index back to what biquadBankCreate was given (the bank keeps a copy on the device), so that
  * a pool of banks serves clip after clip without biquadBankFree / biquadBankCreate, as decimateHipReset does for decimators.
  * biquadBankRepairs is NOT reset.  Asynchronous on the bank's stream, behind every earlier call; no allocation; sharded banks too. */

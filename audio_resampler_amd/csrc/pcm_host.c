@@ -140,6 +140,10 @@ static int spec_chunk (int sections, int W, int frames)
     return frames >= 2 * L ? L : 0;
 }
 
+/* ... and the rule of the entries that gather calls: a call goes the time-parallel way there if its single call would AND it is
+ * longer than serialMax frames (BQ_BATCH_SERIAL_MAX below: up to there one serial lane of a shared launch is faster) */
+static int gathered_chunk (int sections, int W, int frames, int serialMax) { return frames > serialMax ? spec_chunk (sections, W, frames) : 0; }
+
 static int spec_disabled (void)
 {
     static int cached = -1;
@@ -1244,7 +1248,7 @@ int artamd_biquad_batch_planar (BiquadBank *const *banks, int n, artsample_t *co
         BiquadBank *b = banks [i];
         gathered [i] = 0;
         if (numFrames [i] <= 0) continue;
-        if (!bank_shares_launch (b, lead) || (spec_chunk (b->S, b->warmup, numFrames [i]) && numFrames [i] > serialMax)) {
+        if (!bank_shares_launch (b, lead) || gathered_chunk (b->S, b->warmup, numFrames [i], serialMax)) {
             biquadBankApplyPlanarDevice (b, d_buffers [i], pitches ? pitches [i] : 0, numFrames [i]);       /* (pitch 0: the interleaved call) */
             ++launches;
             continue;
@@ -1344,17 +1348,53 @@ int artamd_biquad_batch_serial_max (void) { return BQ_BATCH_SERIAL_MAX; }
 #define BQ_CLIP_CLASSES 8                          /* section counts 1-4 x (interleaved, planar) */
 
 enum { CLIP_SKIP, CLIP_SIDE, CLIP_SERIAL, CLIP_GATHERED };
+/* an item's route and, for a gathered one, its place: round, class, slot, first channel and first task in the class, chunk count
+ * and length, and where its chunk states lie in the state buffer (bytes).  The leading part of both entries' plans */
+typedef struct { int kind, round, cls, slot, chan0, K, L; long task0; size_t spec_at; } ClipPlace;
 typedef struct {
-    int kind, round, cls, slot, copy_slot, chan0, K, L;
-    long task0, copy_task0, dense, pitch;
-    size_t lead, tmp_at, spec_at;        /* samples before the first frame in its 16-byte group; of the item's first frame in the copy
-                                          * buffer (samples); of its chunk states in the state buffer (bytes) */
+    ClipPlace at;
+    int copy_slot;
+    long copy_task0, dense, pitch;
+    size_t lead, tmp_at;                 /* samples before the first frame in its 16-byte group; of the item's first frame in the copy
+                                          * buffer (samples) */
 } ClipPlan;
 typedef struct {
     int ncopy; long copy_tasks; size_t copy_offset;
     size_t tmp_bytes, spec_bytes;
     ArtBqClipClass cls [BQ_CLIP_CLASSES];
 } ClipRound;
+
+/* The one copy of the gathered items' bookkeeping, for this entry and the out-of-place one below.
+ * clip_place: a gathered item of `frames` frames (p->L set by the route rule) takes its place in its (section count, layout) class
+ * of its round's `classes`, which count on */
+static void clip_place (ClipPlace *p, ArtBqClipClass *classes, const BiquadBank *b, int frames, int planar)
+{
+    p->K = (frames + p->L - 1) / p->L;
+    ArtBqClipClass *c = &classes [p->cls = 2 * (b->S - 1) + (planar != 0)];
+    c->S = b->S; c->planar = planar != 0;
+    p->slot = c->count++; p->task0 = c->tasks; p->chan0 = c->channels;
+    c->tasks += (long) b->C * p->K; c->channels += b->C;
+}
+
+/* the table's slices of one round's classes from `bytes` on, 16-byte aligned; the bytes behind them */
+static size_t clip_classes_layout (ArtBqClipClass *classes, size_t bytes)
+{
+    for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
+        classes [k].offset = bytes;
+        bytes += (sizeof (ArtBqClip) * (size_t) classes [k].count + 15) & ~(size_t) 15;
+    }
+    return bytes;
+}
+
+/* a placed item's record in the table, with the fields both entries set alike; the buffers, sections and flags are the caller's */
+static ArtBqClip *clip_item (unsigned char *table, const ArtBqClipClass *classes, const ClipPlace *p, const BiquadBank *b, int frames, void *states)
+{
+    ArtBqClip *it = (ArtBqClip *)(table + classes [p->cls].offset) + p->slot;
+    it->task0 = p->task0; it->chan0 = p->chan0;
+    it->C = b->C; it->K = p->K; it->L = p->L; it->W = b->warmup; it->frames = frames;
+    it->states = states;
+    return it;
+}
 
 static void clip_copy_item (ArtCopyRows *it, const void *src, long src_pitch, void *dst, long dst_pitch, long width, long rows, long task0)
 {
@@ -1388,43 +1428,39 @@ int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *co
         ClipPlan *p = &plan [i];
         const int frames = numFrames [i];
         p->pitch = pitches && b->C > 1 ? pitches [i] : 0;                    /* (one channel: the same call in either layout) */
-        if (!bank_shares_launch (b, lead)) p->kind = CLIP_SIDE;
-        else if (frames > BQ_BATCH_SERIAL_MAX && (p->L = spec_chunk (b->S, b->warmup, frames)) != 0) { p->kind = CLIP_GATHERED; ++ngathered; only = i; }
-        else p->kind = frames > 0 ? CLIP_SERIAL : CLIP_SKIP;
+        if (!bank_shares_launch (b, lead)) p->at.kind = CLIP_SIDE;
+        else if ((p->at.L = gathered_chunk (b->S, b->warmup, frames, BQ_BATCH_SERIAL_MAX)) != 0) { p->at.kind = CLIP_GATHERED; ++ngathered; only = i; }
+        else p->at.kind = frames > 0 ? CLIP_SERIAL : CLIP_SKIP;
     }
-    if (ngathered == 1) plan [only].kind = CLIP_SIDE;
+    if (ngathered == 1) plan [only].at.kind = CLIP_SIDE;
 
     /* the calls these launches cannot take are made as their single calls, in list order; the others get their places */
     for (int i = 0; i < n; ++i) {
         BiquadBank *b = banks [i];
         ClipPlan *p = &plan [i];
         const int frames = numFrames [i];
-        if (p->kind == CLIP_SIDE) {
+        if (p->at.kind == CLIP_SIDE) {
             if (fromStart) biquadBankReset (b);
             if (frames > 0) { biquadBankApplyPlanarDevice (b, d_buffers [i], p->pitch, frames); ++launches; }
             continue;
         }
-        if (p->kind == CLIP_GATHERED) {
+        if (p->at.kind == CLIP_GATHERED) {
             /* the set-aside copy: placed as the single call's (an interleaved item's copy then moves 16 bytes at a time too) */
-            p->K = (frames + p->L - 1) / p->L;
             p->dense = aside_placement (d_buffers [i], p->pitch, frames, &p->lead);
             if (!p->pitch) p->dense = (long) frames * b->C;
             const size_t samples = ((p->pitch ? (size_t) p->dense * b->C : (size_t) p->dense) + p->lead + (size_t)(q - 1)) & ~(size_t)(q - 1);
-            const size_t states = (arthip_biquad_spec_scratch (b->C, b->S, frames, p->L) + 255) & ~(size_t) 255;
+            const size_t states = (arthip_biquad_spec_scratch (b->C, b->S, frames, p->at.L) + 255) & ~(size_t) 255;
             ClipRound *r = &rounds [nrounds - 1];
             if (r->tmp_bytes && r->tmp_bytes + samples * sizeof (art_s) > bound) r = &rounds [nrounds++];
-            p->round = (int)(r - rounds);
+            p->at.round = (int)(r - rounds);
             p->tmp_at = r->tmp_bytes / sizeof (art_s) + p->lead; r->tmp_bytes += samples * sizeof (art_s);
-            p->spec_at = r->spec_bytes; r->spec_bytes += states;
-            ArtBqClipClass *c = &r->cls [p->cls = 2 * (b->S - 1) + (p->pitch != 0)];
-            c->S = b->S; c->planar = p->pitch != 0;
-            p->slot = c->count++; p->task0 = c->tasks; p->chan0 = c->channels;
-            c->tasks += (long) b->C * p->K; c->channels += b->C;
+            p->at.spec_at = r->spec_bytes; r->spec_bytes += states;
+            clip_place (&p->at, r->cls, b, frames, p->pitch != 0);
             p->copy_slot = r->ncopy++; p->copy_task0 = r->copy_tasks;
             r->copy_tasks += p->pitch ? (long) b->C * (((long) frames * wps + 3) / 4 + 1) : (p->dense * wps + 3) / 4 + 1;
             continue;
         }
-        if (p->kind == CLIP_SERIAL) { sbanks [nserial] = b; sbufs [nserial] = d_buffers [i]; spitches [nserial] = p->pitch; sframes [nserial] = frames; ++nserial; }
+        if (p->at.kind == CLIP_SERIAL) { sbanks [nserial] = b; sbufs [nserial] = d_buffers [i]; spitches [nserial] = p->pitch; sframes [nserial] = frames; ++nserial; }
         if (fromStart) {                                                     /* its sections are put back by the first round's copy launch */
             p->copy_slot = rounds [0].ncopy++; p->copy_task0 = rounds [0].copy_tasks;
             rounds [0].copy_tasks += ((long)(sizeof (Biquad) / 4) * b->C * b->S + 3) / 4 + 1;
@@ -1436,10 +1472,7 @@ int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *co
     for (int r = 0; r < nrounds; ++r) {
         rounds [r].copy_offset = bytes;
         bytes += (sizeof (ArtCopyRows) * (size_t) rounds [r].ncopy + 15) & ~(size_t) 15;
-        for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
-            rounds [r].cls [k].offset = bytes;
-            bytes += (sizeof (ArtBqClip) * (size_t) rounds [r].cls [k].count + 15) & ~(size_t) 15;
-        }
+        bytes = clip_classes_layout (rounds [r].cls, bytes);
         if (rounds [r].tmp_bytes > tmp_need) tmp_need = rounds [r].tmp_bytes;
         if (rounds [r].spec_bytes > spec_need) spec_need = rounds [r].spec_bytes;
     }
@@ -1461,26 +1494,23 @@ int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *co
         for (int i = 0; i < n && !rc && bytes; ++i) {
             const ClipPlan *p = &plan [i];
             BiquadBank *b = banks [i];
-            if (p->kind == CLIP_SIDE) continue;
-            if (p->kind != CLIP_GATHERED) {
+            if (p->at.kind == CLIP_SIDE) continue;
+            if (p->at.kind != CLIP_GATHERED) {
                 if (fromStart)
                     clip_copy_item ((ArtCopyRows *)(table + rounds [0].copy_offset) + p->copy_slot, b->d_sections0, 0, b->d_sections, 0,
                                     (long)(sizeof (Biquad) / 4) * b->C * b->S, 1, p->copy_task0);
                 continue;
             }
-            const ClipRound *r = &rounds [p->round];
+            const ClipRound *r = &rounds [p->at.round];
             art_s *const aside = (art_s *) lead->d_clips_tmp + p->tmp_at;
             if (p->pitch) clip_copy_item ((ArtCopyRows *)(table + r->copy_offset) + p->copy_slot, d_buffers [i], p->pitch * wps, aside, p->dense * wps,
                                           (long) numFrames [i] * wps, b->C, p->copy_task0);
             else clip_copy_item ((ArtCopyRows *)(table + r->copy_offset) + p->copy_slot, d_buffers [i], 0, aside, 0, p->dense * wps, 1, p->copy_task0);
-            ArtBqClip *it = (ArtBqClip *)(table + r->cls [p->cls].offset) + p->slot;
+            ArtBqClip *it = clip_item (table, r->cls, &p->at, b, numFrames [i], (char *) lead->d_clips_spec + p->at.spec_at);
             it->from = fromStart ? b->d_sections0 : b->d_sections; it->sections = b->d_sections;
             it->in = aside; it->out = d_buffers [i];
             it->in_stride = p->pitch ? p->dense : b->C; it->out_stride = p->pitch ? p->pitch : b->C;
-            it->states = (char *) lead->d_clips_spec + p->spec_at;
             it->first_bad = b->d_first_bad; it->repairs = b->d_repairs;
-            it->task0 = p->task0; it->chan0 = p->chan0;
-            it->C = b->C; it->K = p->K; it->L = p->L; it->W = b->warmup; it->frames = numFrames [i];
         }
         if (!rc && bytes && arthip_table_upload (table, bytes, lead->d_clips, lead->stream)) {
             pcm_fail ("biquad clips: the table could not be uploaded (nothing of the gathered calls launched)");
@@ -1527,7 +1557,7 @@ int biquadBankApplyClipsPlanarDevice (BiquadBank *const *banks, int n, artsample
  * Rounds are cut on the chunk-state bytes, the only scratch; each item's mismatch flags (C ints) lie behind its chunk states and
  * are armed by the speculative launch.  One table for the whole call: per round its classes' items, then the serial classes' lanes.
  * ---------------------------------------------------------------------------------------- */
-typedef struct { int kind, round, cls, slot, chan0, K, L; long task0, in_pitch, out_pitch; size_t spec_at, flags_at; } FilterPlan;
+typedef struct { ClipPlace at; long in_pitch, out_pitch; size_t flags_at; } FilterPlan;
 typedef struct { size_t spec_bytes; ArtBqClipClass cls [BQ_CLIP_CLASSES]; } FilterRound;
 
 /* samples from the first to behind the last one of an item's side */
@@ -1568,33 +1598,26 @@ int artamd_biquad_filter_clips_planar (BiquadBank *const *banks, int n, const ar
         const BiquadBank *b = banks [i];
         FilterPlan *p = &plan [i];
         const int frames = numFrames [i];
-        if (frames <= 0) { p->kind = CLIP_SKIP; continue; }
+        if (frames <= 0) { p->at.kind = CLIP_SKIP; continue; }
         p->in_pitch = in_pitches && b->C > 1 ? in_pitches [i] : 0;              /* (one channel: the same call in either layout) */
         p->out_pitch = out_pitches && b->C > 1 ? out_pitches [i] : 0;
-        if (frames > BQ_BATCH_SERIAL_MAX && (p->L = spec_chunk (b->S, b->warmup, frames)) != 0) {
-            p->kind = CLIP_GATHERED;
-            p->K = (frames + p->L - 1) / p->L;
-            const size_t states = arthip_biquad_spec_scratch (b->C, b->S, frames, p->L);         /* (a multiple of 32 bytes: the flags lie aligned behind it) */
+        if ((p->at.L = gathered_chunk (b->S, b->warmup, frames, BQ_BATCH_SERIAL_MAX)) != 0) {
+            p->at.kind = CLIP_GATHERED;
+            const size_t states = arthip_biquad_spec_scratch (b->C, b->S, frames, p->at.L);         /* (a multiple of 32 bytes: the flags lie aligned behind it) */
             const size_t need = (states + sizeof (int) * (size_t) b->C + 255) & ~(size_t) 255;
             FilterRound *r = &rounds [nrounds - 1];
             if (r->spec_bytes && r->spec_bytes + need > bound) r = &rounds [nrounds++];
-            p->round = (int)(r - rounds);
-            p->spec_at = r->spec_bytes; p->flags_at = p->spec_at + states; r->spec_bytes += need;
-            ArtBqClipClass *c = &r->cls [p->cls = 2 * (b->S - 1) + (p->in_pitch != 0)];
-            c->S = b->S; c->planar = p->in_pitch != 0;
-            p->slot = c->count++; p->task0 = c->tasks; p->chan0 = c->channels;
-            c->tasks += (long) b->C * p->K; c->channels += b->C;
+            p->at.round = (int)(r - rounds);
+            p->at.spec_at = r->spec_bytes; p->flags_at = p->at.spec_at + states; r->spec_bytes += need;
+            clip_place (&p->at, r->cls, b, frames, p->in_pitch != 0);
         }
-        else { p->kind = CLIP_SERIAL; ser [b->S - 1].slice.count += b->C; }
+        else { p->at.kind = CLIP_SERIAL; ser [b->S - 1].slice.count += b->C; }
     }
 
     /* the table: per round its classes' items, then the serial classes' lanes (+ empty lanes up to whole workgroups); 16-byte aligned slices */
     size_t bytes = 0, spec_need = 0;
     for (int r = 0; r < nrounds; ++r) {
-        for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
-            rounds [r].cls [k].offset = bytes;
-            bytes += (sizeof (ArtBqClip) * (size_t) rounds [r].cls [k].count + 15) & ~(size_t) 15;
-        }
+        bytes = clip_classes_layout (rounds [r].cls, bytes);
         if (rounds [r].spec_bytes > spec_need) spec_need = rounds [r].spec_bytes;
     }
     for (int k = 0; k < 4; ++k) {
@@ -1623,21 +1646,18 @@ int artamd_biquad_filter_clips_planar (BiquadBank *const *banks, int n, const ar
         for (int i = 0; i < n && !rc; ++i) {
             const FilterPlan *p = &plan [i];
             const BiquadBank *b = banks [i];
-            if (p->kind != CLIP_GATHERED) continue;
-            ArtBqClip *it = (ArtBqClip *)(table + rounds [p->round].cls [p->cls].offset) + p->slot;
+            if (p->at.kind != CLIP_GATHERED) continue;
+            ArtBqClip *it = clip_item (table, rounds [p->at.round].cls, &p->at, b, numFrames [i], (char *) lead->d_clips_spec + p->at.spec_at);
             it->from = b->d_sections0; it->sections = NULL;
             it->in = d_ins [i]; it->out = d_outs [i];
             it->in_stride = p->in_pitch ? p->in_pitch : b->C; it->out_stride = p->out_pitch ? p->out_pitch : b->C;
-            it->states = (char *) lead->d_clips_spec + p->spec_at;
             it->first_bad = (int *)((char *) lead->d_clips_spec + p->flags_at); it->repairs = lead->d_repairs;
-            it->task0 = p->task0; it->chan0 = p->chan0;
-            it->C = b->C; it->K = p->K; it->L = p->L; it->W = b->warmup; it->frames = numFrames [i];
         }
         for (int k = 0; k < 4 && !rc; ++k) {
             if (!ser [k].slice.count) continue;
             int m = 0;
             for (int i = 0; i < n; ++i)
-                if (plan [i].kind == CLIP_SERIAL && banks [i]->S == k + 1)
+                if (plan [i].at.kind == CLIP_SERIAL && banks [i]->S == k + 1)
                     for (int c = 0; c < banks [i]->C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numFrames [i]; ++m; }
             qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
             ArtBqFilterLane *l = (ArtBqFilterLane *)(table + ser [k].slice.offset);      /* (the padding lanes stay zero: 0 frames) */

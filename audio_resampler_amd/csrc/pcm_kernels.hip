@@ -163,27 +163,30 @@ __device__ __forceinline__ void put_state (SectionRegs *r, const SpecState *src)
 // PLANAR instantiations take pitches (samples between planes) where the interleaved ones take strides
 template <bool PLANAR> using spec_stride = typename std::conditional<PLANAR, long, int>::type;
 
-// spec_run over a plane: frames [from, to) are consecutive at in + from (and out + from).  The run is cut at the 16-byte boundaries
-// of its own address: single frames up to the first boundary, batches of U frames by 16-byte loads from there (two batches in
-// flight, as below), single frames behind the last whole batch.  Stores are 16 bytes too where `out` is aligned as `in` is.  The
-// arithmetic is the interleaved form's, frame by frame in the same order.
-template <int ACTIVE, bool STORE>
-__device__ __forceinline__ void spec_run_plane (SectionRegs *r, const art_s *in, art_s *out, int from, int to)
+// A run over a plane, the one copy for every time-parallel kernel: the addresses [lo, hi) of `in` (and `out`) taken upwards from
+// lo, or REV: DOWNWARDS from hi - 1.  The run is cut at the 16-byte boundaries of its own address: single frames up (down) to the
+// first boundary, batches of U frames by 16-byte loads from there (two batches in flight, as below), single frames behind the last
+// whole batch.  Stores are 16 bytes too where `out` is aligned as `in` is.  Within a batch the frames are taken in the run's
+// direction; the arithmetic is the interleaved form's, frame by frame in the same order.
+template <int ACTIVE, bool STORE, bool REV = false>
+__device__ __forceinline__ void run_plane (SectionRegs *r, const art_s *in, art_s *out, int lo, int hi)
 {
     constexpr int U = 8, Q = 16 / (int) sizeof (art_s);                   // Q frames to 16 bytes
     typedef art_s vecq __attribute__ ((ext_vector_type (Q)));
-    auto one = [&] (int n) {
-        art_s v = in [n];
+    auto one = [&] (int a) {
+        art_s v = in [a];
 #pragma unroll
         for (int s = 0; s < ACTIVE; ++s) v = step_buffer_order (r [s], v);
-        if constexpr (STORE) out [n] = v;
+        if constexpr (STORE) out [a] = v;
     };
-    int n = from;
-    const int head = min (to - from, (int)((Q - (int)(((uintptr_t)(in + from) / sizeof (art_s)) & (Q - 1))) & (Q - 1)));
-    for (const int e = from + head; n < e; ++n) one (n);
-    bool whole = false;                                                   // (in + n is on a boundary now, or n == to)
+    auto past = [&] (int a) { return (int)(((uintptr_t)(in + a) / sizeof (art_s)) & (Q - 1)); };        // samples of in + a beyond a boundary
+    int n = REV ? hi : lo;                                                // done: everything below n, REV: everything from n up
+    const int head = min (hi - lo, REV ? past (hi) : (Q - past (lo)) & (Q - 1));
+    if constexpr (REV) for (const int e = n - head; n > e; ) { --n; one (n); }
+    else for (const int e = n + head; n < e; ++n) one (n);
+    bool whole = false;                                                   // (in + n is on a boundary now, or the run is over)
     if constexpr (STORE) whole = !((uintptr_t)(out + n) & 15);
-    auto fetch = [&] (art_s (&v) [U], int at) {
+    auto fetch = [&] (art_s (&v) [U], int at) {                           // the U frames from address `at` up
 #pragma unroll
         for (int q = 0; q < U / Q; ++q) {
             const vecq t = *reinterpret_cast<const vecq *> (in + at + q * Q);
@@ -193,7 +196,8 @@ __device__ __forceinline__ void spec_run_plane (SectionRegs *r, const art_s *in,
     };
     auto work = [&] (art_s (&v) [U], int at) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
+        for (int i = 0; i < U; ++i) {
+            const int u = REV ? U - 1 - i : i;
 #pragma unroll
             for (int s = 0; s < ACTIVE; ++s) v [u] = step_buffer_order (r [s], v [u]);
         }
@@ -213,24 +217,27 @@ __device__ __forceinline__ void spec_run_plane (SectionRegs *r, const art_s *in,
             }
         }
     };
-    const int batches = (to - n) / U;
+    constexpr int STEP = REV ? -U : U, LOW = REV ? -U : 0;                // a batch at n: the addresses from n + LOW up
+    const int batches = (REV ? n - lo : hi - n) / U;
     if (batches > 0) {
         art_s cur [U], nxt [U];
-        fetch (cur, n);
-        for (int b = 0; b < batches; ++b, n += U) {
+        fetch (cur, n + LOW);
+        for (int b = 0; b < batches; ++b, n += STEP) {
             const bool more = b + 1 < batches;
-            if (more) fetch (nxt, n + U);                  // in flight while this batch's dependent chain runs
-            work (cur, n);
+            if (more) fetch (nxt, n + STEP + LOW);         // in flight while this batch's dependent chain runs
+            work (cur, n + LOW);
             if (more) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) cur [u] = nxt [u];
             }
         }
     }
-    for (; n < to; ++n) one (n);
+    if constexpr (REV) while (n > lo) { --n; one (n); }
+    else for (; n < hi; ++n) one (n);
 }
 
-// frames [from, to) of channel c through sections 0 .. ACTIVE-1, exact order; STORE: the results go to `out`.
+// frames [from, to) of channel c through sections 0 .. ACTIVE-1, exact order; STORE: the results go to `out`.  The one forward run
+// of every time-parallel kernel, single or gathered.
 // The recurrence is latency-bound and a lane's loads are independent of it: two batches of U frames are kept in flight
 // (the next batch's loads are issued before the current batch's dependent chain starts).
 template <int S, int ACTIVE, bool STORE, bool PLANAR = false>
@@ -238,7 +245,7 @@ __device__ __forceinline__ void spec_run (SectionRegs *r, const art_s *in, spec_
                                           int c, int from, int to)
 {
     if constexpr (PLANAR) {
-        spec_run_plane<ACTIVE, STORE> (r, in + (size_t) c * stride, STORE ? out + (size_t) c * out_stride : nullptr, from, to);
+        run_plane<ACTIVE, STORE> (r, in + (size_t) c * stride, STORE ? out + (size_t) c * out_stride : nullptr, from, to);
         return;
     }
     else {
@@ -282,14 +289,71 @@ __device__ __forceinline__ void spec_run (SectionRegs *r, const art_s *in, spec_
     }
 }
 
+// spec_run with a direction, for the gathered kernels: frames [from, to) of the recurrence of channel c of a call of `frames` frames.
+// Forwards it IS spec_run, and a reversed plane is run_plane downwards.  The reversed INTERLEAVED run is a COPY of spec_run's
+// interleaved branch, frame n at row frames - 1 - n: a change to one goes into the other.  With REV as a parameter of spec_run
+// itself (three formulations of the row: frames - 1 - n, top - n - u, a pointer walked down) the single kernels kept their
+// instructions, but the reversed interleaved kernels of four sections needed more registers: 4-byte bq_filter_commit_kernel<4,
+// false, true> 162 -> 169 VGPRs, 8-byte 225 -> 258 with 2 AGPRs, 8-byte bq_filter_spec_kernel<4, false, true> 250 -> 262 with 6
+// AGPRs (profiles/biquad_one_body.txt).
+template <int S, int ACTIVE, bool STORE, bool PLANAR, bool REV>
+__device__ __forceinline__ void dir_run (SectionRegs *r, const art_s *in, spec_stride<PLANAR> stride, art_s *out, spec_stride<PLANAR> out_stride,
+                                         int c, int from, int to, int frames)
+{
+    if constexpr (!REV) spec_run<S, ACTIVE, STORE, PLANAR> (r, in, stride, out, out_stride, c, from, to);
+    else if constexpr (PLANAR)
+        run_plane<ACTIVE, STORE, true> (r, in + (size_t) c * stride, STORE ? out + (size_t) c * out_stride : nullptr, frames - to, frames - from);
+    else {
+        // the interleaved form of spec_run, frame n at row frames - 1 - n
+        constexpr int U = 8;
+        const int top = frames - 1;
+        auto fetch = [&] (art_s (&v) [U], int n) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) v [u] = in [(size_t)(top - n - u) * stride + c];
+        };
+        auto work = [&] (art_s (&v) [U], int n) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int s = 0; s < ACTIVE; ++s) v [u] = step_buffer_order (r [s], v [u]);
+            }
+            if (STORE) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) out [(size_t)(top - n - u) * out_stride + c] = v [u];
+            }
+        };
+        int n = from;
+        const int batches = (to - from) / U;
+        if (batches > 0) {
+            art_s cur [U], nxt [U];
+            fetch (cur, n);
+            for (int b = 0; b < batches; ++b, n += U) {
+                const bool more = b + 1 < batches;
+                if (more) fetch (nxt, n + U);              // in flight while this batch's dependent chain runs
+                work (cur, n);
+                if (more) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) cur [u] = nxt [u];
+                }
+            }
+        }
+        for (; n < to; ++n) {
+            art_s v = in [(size_t)(top - n) * stride + c];
+#pragma unroll
+            for (int s = 0; s < ACTIVE; ++s) v = step_buffer_order (r [s], v);
+            if (STORE) out [(size_t)(top - n) * out_stride + c] = v;
+        }
+    }
+}
+
 // the warm-up of a speculative chunk: W frames with section 0 alone, W more with sections 0-1, ... (section s joins (S - s) W
 // frames before the chunk's first frame, fed by sections that have already converged)
-template <int S, bool PLANAR, int J = 0>
-__device__ __forceinline__ void spec_warm_up (SectionRegs *r, const art_s *in, spec_stride<PLANAR> stride, int c, int begin, int W)
+template <int S, bool PLANAR, bool REV = false, int J = 0>
+__device__ __forceinline__ void spec_warm_up (SectionRegs *r, const art_s *in, spec_stride<PLANAR> stride, int c, int begin, int W, int frames = 0)
 {
     if constexpr (J < S) {
-        spec_run<S, J + 1, false, PLANAR> (r, in, stride, nullptr, 0, c, begin + J * W, begin + (J + 1) * W);
-        spec_warm_up<S, PLANAR, J + 1> (r, in, stride, c, begin, W);
+        dir_run<S, J + 1, false, PLANAR, REV> (r, in, stride, nullptr, 0, c, begin + J * W, begin + (J + 1) * W, frames);
+        spec_warm_up<S, PLANAR, REV, J + 1> (r, in, stride, c, begin, W, frames);
     }
 }
 
@@ -1543,52 +1607,63 @@ typedef art_s bq_vecq __attribute__ ((ext_vector_type (BQ_Q)));
 // a lane whose frames are consecutive (a plane, or a one-channel bank) from a 16-byte boundary: the helper waves move it 16 bytes at a time
 __device__ __forceinline__ bool bq_plane_aligned (const art_s *buf, int stride) { return stride == 1 && !((uintptr_t) buf & 15); }
 
-// The helper waves' move of one chunk (frames [f0, f0 + nf) of every lane) between the lanes' buffers and an LDS tile, LOAD: into
-// the tile.  Task e = (lane c, frame f), a thread walks one lane's frames.  A plane on a 16-byte boundary (f0 is a multiple of 4)
-// goes 16 bytes at a time: the first thread of every whole group of BQ_Q frames moves the group.
-template <bool LOAD>
+// The helper waves' move of one chunk (frames [f0, f0 + nf) of every lane) between one side of the lanes' buffers and an LDS tile,
+// LOAD: into the tile; the one copy for both pipe kernels.  Task e = (lane c, frame f), a thread walks one lane's frames.  A plane
+// on a 16-byte boundary (f0 is a multiple of 4) goes 16 bytes at a time: the first thread of every whole group of BQ_Q frames moves
+// the group.  REV: frame n of a lane of `count` frames lives at address count - 1 - n, one sample at a time (the lanes of a
+// workgroup differ in count, so a tile row and a plane share no 16-byte cut).
+template <bool LOAD, bool REV>
 __device__ __forceinline__ void bq_move_chunk (art_s *tile, int pitch, int lanes, int f0, int nf, int first, int step,
-                                               art_s *const *bufs, const int *strides, const int *counts)
+                                               typename std::conditional<LOAD, const art_s, art_s>::type *const *bufs, const int *strides, const int *counts)
 {
     for (int e = first; e < nf * lanes; e += step) {
         const int c = e / nf, f = e - c * nf;
         const int left = counts [c] - (f0 + f);
         if (left <= 0) continue;
-        art_s *const g = bufs [c] + (size_t)(f0 + f) * strides [c], *const t = tile + c * pitch + f;
-        if (bq_plane_aligned (bufs [c], strides [c])) {
-            if (left >= BQ_Q - (f & (BQ_Q - 1))) {
-                if (!(f & (BQ_Q - 1))) {
-                    if (LOAD) *reinterpret_cast<bq_vecq *> (t) = *reinterpret_cast<const bq_vecq *> (g);
-                    else *reinterpret_cast<bq_vecq *> (g) = *reinterpret_cast<const bq_vecq *> (t);
+        const int stride = strides [c];
+        art_s *const t = tile + c * pitch + f;
+        const size_t at = (size_t)(REV ? left - 1 : f0 + f) * stride;
+        if constexpr (!REV) {
+            if (bq_plane_aligned (bufs [c], stride)) {
+                if (left >= BQ_Q - (f & (BQ_Q - 1))) {
+                    if (!(f & (BQ_Q - 1))) {
+                        if constexpr (LOAD) *reinterpret_cast<bq_vecq *> (t) = *reinterpret_cast<const bq_vecq *> (bufs [c] + at);
+                        else *reinterpret_cast<bq_vecq *> (bufs [c] + at) = *reinterpret_cast<const bq_vecq *> (t);
+                    }
+                    continue;
                 }
-                continue;
             }
         }
-        if (LOAD) *t = *g; else *g = *t;
+        if constexpr (LOAD) *t = bufs [c][at]; else bufs [c][at] = *t;
     }
 }
 
 constexpr int BQ_BATCH_RUN = 60;                   // frames per chunk at most (the decimator batch's: fill and drain cost two chunks)
 
+// The pipeline, the one copy for both pipe kernels: Lane = ArtBqLane filters in place and stores the state back, ArtBqFilterLane
+// reads one side, writes the other (REV: with time reversed) and stores no state.
 // LDS: three tiles [lanes][chunk_frames + 4] (the pitch is a multiple of 4: one ds_read_b128 feeds the serial lane 4 float frames),
 // sized by the launcher from `lanes`.  A lane with fewer frames than the workgroup's longest sits the rest out.
-template <int S>
-__global__ __launch_bounds__ (ST_THREADS)
-void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_frames)
+template <int S, bool REV, typename Lane>
+__device__ __forceinline__ void bq_pipe_body (const Lane *table, int lanes, int chunk_frames)
 {
+    constexpr bool IN_PLACE = std::is_same<Lane, ArtBqLane>::value;
     extern __shared__ __attribute__ ((aligned (16))) unsigned char bq_lds [];
     const int pitch = chunk_frames + 4, span = lanes * pitch;
     art_s *const tiles = (art_s *) bq_lds;                                // [3][lanes][pitch]
-    __shared__ art_s *s_buf [64];
-    __shared__ int s_stride [64], s_frames [64];
+    __shared__ const art_s *s_in [64];                                    // (in place: the output side's arrays alone are used)
+    __shared__ art_s *s_out [64];
+    __shared__ int s_in_stride [64], s_out_stride [64], s_frames [64];
     const int tid = threadIdx.x, wave = tid >> 6;
-    const ArtBqLane *const mine = table + (size_t) blockIdx.x * lanes;
+    const Lane *const mine = table + (size_t) blockIdx.x * lanes;
 
     SectionRegs r [S];
     int my_frames = 0;
     if (tid < lanes) {
-        const ArtBqLane &d = mine [tid];
-        s_buf [tid] = d.buf; s_stride [tid] = d.stride; s_frames [tid] = d.frames;
+        const Lane &d = mine [tid];
+        if constexpr (IN_PLACE) { s_out [tid] = d.buf; s_out_stride [tid] = d.stride; }
+        else { s_in [tid] = d.in; s_out [tid] = d.out; s_in_stride [tid] = d.in_stride; s_out_stride [tid] = d.out_stride; }
+        s_frames [tid] = d.frames;
         my_frames = d.frames;
         if (my_frames > 0) {
 #pragma unroll
@@ -1606,11 +1681,12 @@ void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_fram
             const int ht = tid - 64;
             if (it + 1 < nchunks) {                // ---- load chunk it+1
                 const int k = it + 1, f0 = k * chunk_frames;
-                bq_move_chunk<true> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS, s_buf, s_stride, s_frames);
+                if constexpr (IN_PLACE) bq_move_chunk<true, REV> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS, s_out, s_out_stride, s_frames);
+                else bq_move_chunk<true, REV> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS, s_in, s_in_stride, s_frames);
             }
             if (it >= 1) {                         // ---- store chunk it-1
                 const int k = it - 1, f0 = k * chunk_frames;
-                bq_move_chunk<false> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS, s_buf, s_stride, s_frames);
+                bq_move_chunk<false, REV> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS, s_out, s_out_stride, s_frames);
             }
         }
         else if (tid < lanes && it >= 0 && it < nchunks && it * chunk_frames < my_frames) {     // ---- the cascade over chunk it
@@ -1637,22 +1713,36 @@ void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_fram
         asm volatile ("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
 
-    if (tid < lanes && my_frames > 0) {
-        Biquad *const sections = mine [tid].sections;
+    if constexpr (IN_PLACE) {
+        if (tid < lanes && my_frames > 0) {
+            Biquad *const sections = mine [tid].sections;
 #pragma unroll
-        for (int s = 0; s < S; ++s) store_section (sections [s], r [s], my_frames, false);
+            for (int s = 0; s < S; ++s) store_section (sections [s], r [s], my_frames, false);
+        }
     }
 }
 
-// The three passes as functions of one task, for the gathered kernels (bq_clips_*_kernel).  They are COPIES of the bodies of
-// biquad_spec_kernel, biquad_check_kernel and biquad_commit_kernel: a change to one goes into the other.  With the single kernels
-// calling these functions they compile to other code, and each was slower on an MI355X than as it stands (single call against the
-// build with the copies, profiles/biquad_shared_body.txt): the 8-byte biquad_spec_kernel<4, interleaved> 308.8 -> 353.2 us and
-// 318.8 -> 368.8 us at the same 254 VGPRs, biquad_check_kernel up to 0.5 us in nine of ten traced cases (S = 3: 4.98 -> 5.32 us), the
-// 4-byte biquad_commit_kernel<2, interleaved> 174.4 -> 181.5 us in a call with 35 repaired chunks.
+template <int S>
+__global__ __launch_bounds__ (ST_THREADS)
+void biquad_batch_pipe_kernel (const ArtBqLane *table, int lanes, int chunk_frames)
+{
+    bq_pipe_body<S, false> (table, lanes, chunk_frames);
+}
+
+// The passes as functions of one task, for the gathered kernels (bq_clips_*_kernel and bq_filter_*_kernel).  The runs themselves
+// (run_plane, spec_run, spec_warm_up) are shared with the single call's kernels.  spec_task and repair_chunks are the one place for
+// the gathered family's speculative task and repair loop.  COPIES, exactly these: biquad_spec_kernel and biquad_commit_kernel keep
+// bodies of their own with spec_task's and repair_chunks' text, and check_task (which feeds bq_clips_check_kernel) is a copy of
+// biquad_check_kernel's: a change to one goes into the other.  With the single kernels calling these functions they
+// compile to other code, and each was slower on an MI355X than as it stands (single call against the build with the copies,
+// profiles/biquad_shared_body.txt): the 8-byte biquad_spec_kernel<4, interleaved> 308.8 -> 353.2 us and 318.8 -> 368.8 us at the
+// same 254 VGPRs, biquad_check_kernel up to 0.5 us in nine of ten traced cases (S = 3: 4.98 -> 5.32 us), the 4-byte
+// biquad_commit_kernel<2, interleaved> 174.4 -> 181.5 us in a call with 35 repaired chunks.  The gathered family under one body:
+// profiles/biquad_one_body.txt.
 //
-// One task of the speculative pass: chunk k of channel c of a call (C channels, K chunks of L frames, warm-up W) from `sections`.
-template <int S, bool PLANAR>
+// One task of the speculative pass: chunk k of channel c of a call (C channels, K chunks of L frames, warm-up W) from `sections`,
+// forwards or (REV) over the reversed sequence.
+template <int S, bool PLANAR, bool REV>
 __device__ __forceinline__ void spec_task (const Biquad *sections, int c, int k, int K, int L, int W, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
                                            spec_stride<PLANAR> out_stride, int frames, SpecState *starts, SpecState *ends)
 {
@@ -1669,18 +1759,18 @@ __device__ __forceinline__ void spec_task (const Biquad *sections, int c, int k,
         for (int s = 0; s < S; ++s)
 #pragma unroll
             for (int q = 0; q < 4; ++q) { r [s].x [q] = 0; r [s].y [q] = 0; }
-        spec_warm_up<S, PLANAR> (r, in, stride, c, begin, W);
+        spec_warm_up<S, PLANAR, REV> (r, in, stride, c, begin, W, frames);
     }
     else if (first > 0)
-        // close to the start of the call: from the carried-in state through frames [0, first) — exact, nothing stored
-        spec_run<S, S, false, PLANAR> (r, in, stride, nullptr, 0, c, 0, first);
+        // close to the start of the sequence: from the carried-in state through frames [0, first) — exact, nothing stored
+        dir_run<S, S, false, PLANAR, REV> (r, in, stride, nullptr, 0, c, 0, first, frames);
 
     SpecState st [S];
     get_state<S> (st, r);
 #pragma unroll
     for (int s = 0; s < S; ++s) starts [((size_t) c * K + k) * S + s] = st [s];
 
-    spec_run<S, S, true, PLANAR> (r, in, stride, out, out_stride, c, first, last);
+    dir_run<S, S, true, PLANAR, REV> (r, in, stride, out, out_stride, c, first, last, frames);
 
     get_state<S> (st, r);
 #pragma unroll
@@ -1697,29 +1787,20 @@ __device__ __forceinline__ void check_task (int c, int k, int K, const SpecState
     if (!ok) atomicMin (first_bad + c, k);
 }
 
-// biquad_commit_kernel's body (a copy), with the sections read from `from` and stored to `sections`, which the single call reads
-// and stores in one array: one channel committed.
-template <int S, bool PLANAR>
-__device__ __forceinline__ void commit_channel (const Biquad *from, Biquad *sections, int c, int K, int L, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
-                                                spec_stride<PLANAR> out_stride, int frames,
-                                                const SpecState *starts, SpecState *ends, const unsigned char *bad, int *first_bad, unsigned int *repairs)
+// The repair loop of one channel from its first mismatch k (biquad_commit_kernel's): every chunk that did not start from the state
+// its predecessor left is computed again from that state, until the run rejoins a speculative trajectory.  `en` [K - 1] is the
+// channel's exact final state afterwards.
+template <int S, bool PLANAR, bool REV>
+__device__ __forceinline__ void repair_chunks (SectionRegs *r, int k, int c, int K, int L, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
+                                               spec_stride<PLANAR> out_stride, int frames, const SpecState *st, SpecState *en, const unsigned char *flags,
+                                               unsigned int *repairs)
 {
-    const SpecState *st = starts + (size_t) c * K * S;
-    SpecState *en = ends + (size_t) c * K * S;
-    const unsigned char *flags = bad + (size_t) c * K;
-
-    SectionRegs r [S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) load_section (r [s], from [(size_t) c * S + s]);
-
-    int k = first_bad [c];
-    first_bad [c] = INT_MAX;
     unsigned int redone = 0;
     while (k < K) {
         // chunk k again, from the exact state its predecessor left
         put_state<S> (r, en + (size_t)(k - 1) * S);
         const int first = k * L, last = min (first + L, frames);
-        spec_run<S, S, true, PLANAR> (r, in, stride, out, out_stride, c, first, last);
+        dir_run<S, S, true, PLANAR, REV> (r, in, stride, out, out_stride, c, first, last, frames);
         SpecState now [S];
         get_state<S> (now, r);
 #pragma unroll
@@ -1735,6 +1816,24 @@ __device__ __forceinline__ void commit_channel (const Biquad *from, Biquad *sect
         else ++k;
     }
     if (redone) atomicAdd (repairs, redone);
+}
+
+// One channel committed in place (bq_clips_commit_kernel): repaired, first_bad re-armed for the next call, and the final state
+// stored — the sections read from `from` and stored to `sections`, which the single call reads and stores in one array.
+template <int S, bool PLANAR>
+__device__ __forceinline__ void commit_channel (const Biquad *from, Biquad *sections, int c, int K, int L, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
+                                                spec_stride<PLANAR> out_stride, int frames,
+                                                const SpecState *starts, SpecState *ends, const unsigned char *bad, int *first_bad, unsigned int *repairs)
+{
+    SpecState *en = ends + (size_t) c * K * S;
+
+    SectionRegs r [S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) load_section (r [s], from [(size_t) c * S + s]);
+
+    const int k = first_bad [c];
+    first_bad [c] = INT_MAX;
+    repair_chunks<S, PLANAR, false> (r, k, c, K, L, in, stride, out, out_stride, frames, starts + (size_t) c * K * S, en, bad + (size_t) c * K, repairs);
 
     put_state<S> (r, en + (size_t)(K - 1) * S);
 #pragma unroll
@@ -1748,10 +1847,27 @@ __device__ __forceinline__ void commit_channel (const Biquad *from, Biquad *sect
     }
 }
 
+// One channel committed out of place (bq_filter_commit_kernel): repaired only — no state goes back anywhere, and first_bad is not
+// re-armed (the next call's spec pass arms its own).
+template <int S, bool PLANAR, bool REV>
+__device__ __forceinline__ void filter_commit_channel (const Biquad *from, int c, int K, int L, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
+                                                       spec_stride<PLANAR> out_stride, int frames,
+                                                       const SpecState *starts, SpecState *ends, const unsigned char *bad, const int *first_bad, unsigned int *repairs)
+{
+    const int k = first_bad [c];
+    if (k >= K) return;
+
+    SectionRegs r [S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) load_section (r [s], from [(size_t) c * S + s]);
+
+    repair_chunks<S, PLANAR, REV> (r, k, c, K, L, in, stride, out, out_stride, frames, starts + (size_t) c * K * S, ends + (size_t) c * K * S, bad + (size_t) c * K, repairs);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Many banks' TIME-PARALLEL calls in shared launches (biquadBankApplyClipsPlanarDevice): the passes of biquad_spec_kernel,
 // biquad_check_kernel and biquad_commit_kernel over a table of items (ArtBqClip), one item per call.  The task space is the items' (chunk, channel) spaces
-// laid end to end; a thread finds its item by binary search over the items' first tasks (item_of) and runs the copy of the single call's body
+// laid end to end; a thread finds its item by binary search over the items' first tasks (item_of) and runs the single call's passes (spec_task, check_task, commit_channel)
 // with the item's own C, K, L, W and frames: the chunk cuts, and so the bits, the repairs and the final state, are the single
 // call's.  Lanes of different items (different L and K) share a wave.  One instantiation per (section count, layout).
 // ---------------------------------------------------------------------------------------------------
@@ -1766,7 +1882,7 @@ void bq_clips_spec_kernel (const ArtBqClip *items, int n, long tasks)
     const int C = a.C, K = a.K;
     const int c = PLANAR ? (int)(t / K) : (int)(t % C), k = PLANAR ? (int)(t % K) : (int)(t / C);
     SpecState *const starts = (SpecState *) a.states, *const ends = starts + (size_t) C * K * S;
-    spec_task<S, PLANAR> (a.from, c, k, K, a.L, a.W, a.in, (spec_stride<PLANAR>) a.in_stride, a.out, (spec_stride<PLANAR>) a.out_stride, a.frames, starts, ends);
+    spec_task<S, PLANAR, false> (a.from, c, k, K, a.L, a.W, a.in, (spec_stride<PLANAR>) a.in_stride, a.out, (spec_stride<PLANAR>) a.out_stride, a.frames, starts, ends);
 }
 
 template <int S>
@@ -1803,217 +1919,12 @@ void bq_clips_commit_kernel (const ArtBqClip *items, int n, int channels)
 // gathered passes once more, reading the caller's input where it lies (no set-aside copy) and storing no state back.  REV: frame n
 // of the recurrence lives at address frames - 1 - n on both sides, so the item's L, W and K — computed by the host as ever — cut the
 // REVERSED sequence where the forward call would cut it, and the arithmetic per frame is the forward call's in the same order.
-// From rest, that is the transpose of the forward map (art_hip.h).  The bodies below are COPIES of spec_run_plane, spec_run,
-// spec_warm_up, spec_task and commit_channel with a direction (the forward direction calls spec_run itself): the existing kernels
-// keep their text, and with it their instructions and register rows (profiles/biquad_filter_clips.txt).
+// From rest, that is the transpose of the forward map (art_hip.h).  The direction is a parameter of run_plane, spec_warm_up,
+// spec_task and repair_chunks, and forwards they are the in-place entry's instantiations; dir_run holds the one copy left, the
+// reversed interleaved run.
 // The check pass has no direction and no buffers: bq_clips_check_kernel is launched as it is.  An item's first_bad lies behind its
 // own chunk states and is armed by the spec pass (task k = 0 of every channel), the launch before the check.
 // ---------------------------------------------------------------------------------------------------
-
-// spec_run_plane with time reversed: the addresses [lo, hi) of a plane walked DOWNWARDS from hi - 1.  Cut at the 16-byte boundaries
-// of the run's own address: single frames down to the first boundary, batches of U frames by 16-byte loads below it (two batches in
-// flight), single frames under the last whole batch; 16-byte stores where `out` is aligned as `in` is.  Within a batch the frames
-// are taken from the highest address down.
-template <int ACTIVE, bool STORE>
-__device__ __forceinline__ void rev_run_plane (SectionRegs *r, const art_s *in, art_s *out, int lo, int hi)
-{
-    constexpr int U = 8, Q = 16 / (int) sizeof (art_s);                   // Q frames to 16 bytes
-    typedef art_s vecq __attribute__ ((ext_vector_type (Q)));
-    auto one = [&] (int a) {
-        art_s v = in [a];
-#pragma unroll
-        for (int s = 0; s < ACTIVE; ++s) v = step_buffer_order (r [s], v);
-        if constexpr (STORE) out [a] = v;
-    };
-    int p = hi;                                                           // everything from p up is done
-    const int head = min (hi - lo, (int)(((uintptr_t)(in + hi) / sizeof (art_s)) & (Q - 1)));
-    for (const int e = hi - head; p > e; ) { --p; one (p); }
-    bool whole = false;                                                   // (in + p is on a boundary now, or p == lo)
-    if constexpr (STORE) whole = !((uintptr_t)(out + p) & 15);
-    auto fetch = [&] (art_s (&v) [U], int top) {                          // the U frames under `top`, v [j] from address top - U + j
-#pragma unroll
-        for (int q = 0; q < U / Q; ++q) {
-            const vecq t = *reinterpret_cast<const vecq *> (in + top - U + q * Q);
-#pragma unroll
-            for (int j = 0; j < Q; ++j) v [q * Q + j] = t [j];
-        }
-    };
-    auto work = [&] (art_s (&v) [U], int top) {
-#pragma unroll
-        for (int u = U - 1; u >= 0; --u) {
-#pragma unroll
-            for (int s = 0; s < ACTIVE; ++s) v [u] = step_buffer_order (r [s], v [u]);
-        }
-        if constexpr (STORE) {
-            if (whole) {
-#pragma unroll
-                for (int q = 0; q < U / Q; ++q) {
-                    vecq t;
-#pragma unroll
-                    for (int j = 0; j < Q; ++j) t [j] = v [q * Q + j];
-                    *reinterpret_cast<vecq *> (out + top - U + q * Q) = t;
-                }
-            }
-            else {
-#pragma unroll
-                for (int u = 0; u < U; ++u) out [top - U + u] = v [u];
-            }
-        }
-    };
-    const int batches = (p - lo) / U;
-    if (batches > 0) {
-        art_s cur [U], nxt [U];
-        fetch (cur, p);
-        for (int b = 0; b < batches; ++b, p -= U) {
-            const bool more = b + 1 < batches;
-            if (more) fetch (nxt, p - U);                  // in flight while this batch's dependent chain runs
-            work (cur, p);
-            if (more) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) cur [u] = nxt [u];
-            }
-        }
-    }
-    while (p > lo) { --p; one (p); }
-}
-
-// spec_run with a direction: frames [from, to) of the recurrence of channel c of a call of `frames` frames.  Forwards it IS spec_run.
-template <int S, int ACTIVE, bool STORE, bool PLANAR, bool REV>
-__device__ __forceinline__ void dir_run (SectionRegs *r, const art_s *in, spec_stride<PLANAR> stride, art_s *out, spec_stride<PLANAR> out_stride,
-                                         int c, int from, int to, int frames)
-{
-    if constexpr (!REV) spec_run<S, ACTIVE, STORE, PLANAR> (r, in, stride, out, out_stride, c, from, to);
-    else if constexpr (PLANAR)
-        rev_run_plane<ACTIVE, STORE> (r, in + (size_t) c * stride, STORE ? out + (size_t) c * out_stride : nullptr, frames - to, frames - from);
-    else {
-        // the interleaved form of spec_run, frame n at row frames - 1 - n
-        constexpr int U = 8;
-        const int top = frames - 1;
-        auto fetch = [&] (art_s (&v) [U], int n) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) v [u] = in [(size_t)(top - n - u) * stride + c];
-        };
-        auto work = [&] (art_s (&v) [U], int n) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int s = 0; s < ACTIVE; ++s) v [u] = step_buffer_order (r [s], v [u]);
-            }
-            if (STORE) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) out [(size_t)(top - n - u) * out_stride + c] = v [u];
-            }
-        };
-        int n = from;
-        const int batches = (to - from) / U;
-        if (batches > 0) {
-            art_s cur [U], nxt [U];
-            fetch (cur, n);
-            for (int b = 0; b < batches; ++b, n += U) {
-                const bool more = b + 1 < batches;
-                if (more) fetch (nxt, n + U);              // in flight while this batch's dependent chain runs
-                work (cur, n);
-                if (more) {
-#pragma unroll
-                    for (int u = 0; u < U; ++u) cur [u] = nxt [u];
-                }
-            }
-        }
-        for (; n < to; ++n) {
-            art_s v = in [(size_t)(top - n) * stride + c];
-#pragma unroll
-            for (int s = 0; s < ACTIVE; ++s) v = step_buffer_order (r [s], v);
-            if (STORE) out [(size_t)(top - n) * out_stride + c] = v;
-        }
-    }
-}
-
-// spec_warm_up with a direction
-template <int S, bool PLANAR, bool REV, int J = 0>
-__device__ __forceinline__ void dir_warm_up (SectionRegs *r, const art_s *in, spec_stride<PLANAR> stride, int c, int begin, int W, int frames)
-{
-    if constexpr (J < S) {
-        dir_run<S, J + 1, false, PLANAR, REV> (r, in, stride, nullptr, 0, c, begin + J * W, begin + (J + 1) * W, frames);
-        dir_warm_up<S, PLANAR, REV, J + 1> (r, in, stride, c, begin, W, frames);
-    }
-}
-
-// spec_task (a copy) with a direction
-template <int S, bool PLANAR, bool REV>
-__device__ __forceinline__ void filter_spec_task (const Biquad *sections, int c, int k, int K, int L, int W, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
-                                                  spec_stride<PLANAR> out_stride, int frames, SpecState *starts, SpecState *ends)
-{
-    const int first = k * L, last = min (first + L, frames);
-
-    SectionRegs r [S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) load_section (r [s], sections [(size_t) c * S + s]);
-
-    const int begin = first - S * W;
-    if (begin > 0) {
-        // speculative start: silence behind every section
-#pragma unroll
-        for (int s = 0; s < S; ++s)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { r [s].x [q] = 0; r [s].y [q] = 0; }
-        dir_warm_up<S, PLANAR, REV> (r, in, stride, c, begin, W, frames);
-    }
-    else if (first > 0)
-        // close to the start of the sequence: from the first state through frames [0, first) — exact, nothing stored
-        dir_run<S, S, false, PLANAR, REV> (r, in, stride, nullptr, 0, c, 0, first, frames);
-
-    SpecState st [S];
-    get_state<S> (st, r);
-#pragma unroll
-    for (int s = 0; s < S; ++s) starts [((size_t) c * K + k) * S + s] = st [s];
-
-    dir_run<S, S, true, PLANAR, REV> (r, in, stride, out, out_stride, c, first, last, frames);
-
-    get_state<S> (st, r);
-#pragma unroll
-    for (int s = 0; s < S; ++s) ends [((size_t) c * K + k) * S + s] = st [s];
-}
-
-// commit_channel (a copy) with a direction and without its last part: no state goes back anywhere, and first_bad is not re-armed
-// (the next call's spec pass arms its own)
-template <int S, bool PLANAR, bool REV>
-__device__ __forceinline__ void filter_commit_channel (const Biquad *from, int c, int K, int L, const art_s *in, spec_stride<PLANAR> stride, art_s *out,
-                                                       spec_stride<PLANAR> out_stride, int frames,
-                                                       const SpecState *starts, SpecState *ends, const unsigned char *bad, const int *first_bad, unsigned int *repairs)
-{
-    int k = first_bad [c];
-    if (k >= K) return;
-    const SpecState *st = starts + (size_t) c * K * S;
-    SpecState *en = ends + (size_t) c * K * S;
-    const unsigned char *flags = bad + (size_t) c * K;
-
-    SectionRegs r [S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) load_section (r [s], from [(size_t) c * S + s]);
-
-    unsigned int redone = 0;
-    while (k < K) {
-        // chunk k again, from the exact state its predecessor left
-        put_state<S> (r, en + (size_t)(k - 1) * S);
-        const int first = k * L, last = min (first + L, frames);
-        dir_run<S, S, true, PLANAR, REV> (r, in, stride, out, out_stride, c, first, last, frames);
-        SpecState now [S];
-        get_state<S> (now, r);
-#pragma unroll
-        for (int s = 0; s < S; ++s) en [(size_t) k * S + s] = now [s];
-        ++redone;
-        if (k + 1 >= K) break;
-        if (same_state<S> (now, st + (size_t)(k + 1) * S)) {
-            // rejoined the speculative trajectory: everything up to the next recorded mismatch stands
-            int next = k + 2;
-            while (next < K && !flags [next]) ++next;
-            k = next;
-        }
-        else ++k;
-    }
-    if (redone) atomicAdd (repairs, redone);
-}
-
 template <int S, bool PLANAR, bool REV>
 __global__ __launch_bounds__ (256)
 void bq_filter_spec_kernel (const ArtBqClip *items, int n, long tasks)
@@ -2026,7 +1937,7 @@ void bq_filter_spec_kernel (const ArtBqClip *items, int n, long tasks)
     const int c = PLANAR ? (int)(t / K) : (int)(t % C), k = PLANAR ? (int)(t % K) : (int)(t / C);
     SpecState *const starts = (SpecState *) a.states, *const ends = starts + (size_t) C * K * S;
     if (k == 0) a.first_bad [c] = INT_MAX;
-    filter_spec_task<S, PLANAR, REV> (a.from, c, k, K, a.L, a.W, a.in, (spec_stride<PLANAR>) a.in_stride, a.out, (spec_stride<PLANAR>) a.out_stride, a.frames, starts, ends);
+    spec_task<S, PLANAR, REV> (a.from, c, k, K, a.L, a.W, a.in, (spec_stride<PLANAR>) a.in_stride, a.out, (spec_stride<PLANAR>) a.out_stride, a.frames, starts, ends);
 }
 
 template <int S, bool PLANAR, bool REV>
@@ -2044,107 +1955,13 @@ void bq_filter_commit_kernel (const ArtBqClip *items, int n, int channels)
                                            starts, ends, (const unsigned char *)(ends + (size_t) C * K * S), a.first_bad, a.repairs);
 }
 
-// ... and their serial route: biquad_batch_pipe_kernel (a copy) over lanes that are read on one side and written on the other,
-// from sections that are only read.  bq_move_chunk with the two sides: forwards a plane on a 16-byte boundary moves 16 bytes at a
-// time on whichever side it is; reversed, frame n of a lane of `count` frames lives at address count - 1 - n, one sample at a time
-// (the lanes of a workgroup differ in count, so a tile row and a plane share no 16-byte cut).
-template <bool LOAD, bool REV>
-__device__ __forceinline__ void bq_filter_move_chunk (art_s *tile, int pitch, int lanes, int f0, int nf, int first, int step,
-                                                      const art_s *const *ins, art_s *const *outs, const int *in_strides, const int *out_strides, const int *counts)
-{
-    for (int e = first; e < nf * lanes; e += step) {
-        const int c = e / nf, f = e - c * nf;
-        const int left = counts [c] - (f0 + f);
-        if (left <= 0) continue;
-        const int stride = LOAD ? in_strides [c] : out_strides [c];
-        art_s *const t = tile + c * pitch + f;
-        if constexpr (REV) {
-            const size_t at = (size_t)(left - 1) * stride;
-            if (LOAD) *t = ins [c][at]; else outs [c][at] = *t;
-        }
-        else {
-            const size_t at = (size_t)(f0 + f) * stride;
-            if (bq_plane_aligned (LOAD ? ins [c] : outs [c], stride)) {
-                if (left >= BQ_Q - (f & (BQ_Q - 1))) {
-                    if (!(f & (BQ_Q - 1))) {
-                        if (LOAD) *reinterpret_cast<bq_vecq *> (t) = *reinterpret_cast<const bq_vecq *> (ins [c] + at);
-                        else *reinterpret_cast<bq_vecq *> (outs [c] + at) = *reinterpret_cast<const bq_vecq *> (t);
-                    }
-                    continue;
-                }
-            }
-            if (LOAD) *t = ins [c][at]; else outs [c][at] = *t;
-        }
-    }
-}
-
+// ... and their serial route: the pipeline of biquad_batch_pipe_kernel (bq_pipe_body) over lanes that are read on one side and
+// written on the other, from sections that are only read.
 template <int S, bool REV>
 __global__ __launch_bounds__ (ST_THREADS)
 void bq_filter_pipe_kernel (const ArtBqFilterLane *table, int lanes, int chunk_frames)
 {
-    extern __shared__ __attribute__ ((aligned (16))) unsigned char bq_lds [];
-    const int pitch = chunk_frames + 4, span = lanes * pitch;
-    art_s *const tiles = (art_s *) bq_lds;                                // [3][lanes][pitch]
-    __shared__ const art_s *s_in [64];
-    __shared__ art_s *s_out [64];
-    __shared__ int s_in_stride [64], s_out_stride [64], s_frames [64];
-    const int tid = threadIdx.x, wave = tid >> 6;
-    const ArtBqFilterLane *const mine = table + (size_t) blockIdx.x * lanes;
-
-    SectionRegs r [S];
-    int my_frames = 0;
-    if (tid < lanes) {
-        const ArtBqFilterLane &d = mine [tid];
-        s_in [tid] = d.in; s_out [tid] = d.out; s_in_stride [tid] = d.in_stride; s_out_stride [tid] = d.out_stride; s_frames [tid] = d.frames;
-        my_frames = d.frames;
-        if (my_frames > 0) {
-#pragma unroll
-            for (int s = 0; s < S; ++s) load_section (r [s], d.sections [s]);
-        }
-    }
-    __syncthreads ();
-    int frames = 0;
-    for (int c = 0; c < lanes; ++c) frames = max (frames, s_frames [c]);
-    const int nchunks = (frames + chunk_frames - 1) / chunk_frames;
-    constexpr int HELPERS = ST_THREADS - 64;
-
-    for (int it = -1; it <= nchunks; ++it) {
-        if (wave >= 1) {
-            const int ht = tid - 64;
-            if (it + 1 < nchunks) {                // ---- load chunk it+1
-                const int k = it + 1, f0 = k * chunk_frames;
-                bq_filter_move_chunk<true, REV> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS,
-                                                 s_in, s_out, s_in_stride, s_out_stride, s_frames);
-            }
-            if (it >= 1) {                         // ---- store chunk it-1
-                const int k = it - 1, f0 = k * chunk_frames;
-                bq_filter_move_chunk<false, REV> (tiles + (k % 3) * span, pitch, lanes, f0, min (chunk_frames, frames - f0), ht, HELPERS,
-                                                  s_in, s_out, s_in_stride, s_out_stride, s_frames);
-            }
-        }
-        else if (tid < lanes && it >= 0 && it < nchunks && it * chunk_frames < my_frames) {     // ---- the cascade over chunk it
-            const int f0 = it * chunk_frames, nf = min (chunk_frames, my_frames - f0);
-            art_s *row = tiles + (it % 3) * span + tid * pitch;
-            typedef art_s vec4 __attribute__ ((ext_vector_type (4)));
-            int f = 0;
-            for (; f + 4 <= nf; f += 4) {
-                vec4 v = *reinterpret_cast<const vec4 *> (row + f);
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int s = 0; s < S; ++s) v [u] = step_buffer_order (r [s], v [u]);
-                *reinterpret_cast<vec4 *> (row + f) = v;
-            }
-            for (; f < nf; ++f) {
-                art_s v = row [f];
-#pragma unroll
-                for (int s = 0; s < S; ++s) v = step_buffer_order (r [s], v);
-                row [f] = v;
-            }
-        }
-        // LDS-only barrier, as in biquad_batch_pipe_kernel: nobody reads global memory that this launch writes
-        asm volatile ("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
+    bq_pipe_body<S, REV> (table, lanes, chunk_frames);
 }
 
 // Many strided copies in one launch (the gathered calls' inputs set aside, and banks' sections put back to their first state): item
@@ -2354,6 +2171,41 @@ static int biquad_spec_launch (Biquad *d_sections, int C, int S, const art_s *d_
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
+// kernel<1 .. 4, ...> by the section count
+#define BQ_PICK_S(S, kernel, ...) ((S) == 1 ? kernel<1, ##__VA_ARGS__> : (S) == 2 ? kernel<2, ##__VA_ARGS__> : (S) == 3 ? kernel<3, ##__VA_ARGS__> : kernel<4, ##__VA_ARGS__>)
+
+// one launch of one serial class from its slice of the uploaded table: lanes, LDS and grid for either pipe kernel
+template <typename Lane>
+static int bq_pipe_launch (void (*kernel) (const Lane *, int, int), const ArtBqClass *cls, const void *d_table, void *stream)
+{
+    const Lane *items = (const Lane *)((const char *) d_table + cls->slice.offset);
+    const int L = cls->slice.lanes;
+    if (cls->slice.count <= 0) return 0;
+    if (L < 1 || L > 64 || cls->slice.count % L || cls->S < 1 || cls->S > 4) return -1;
+    const int chunk_frames = batch_chunk_frames (L, BQ_BATCH_RUN);
+    const size_t lds = (size_t) 3 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 3 DEC_CHUNK samples (48 KiB)
+    hipLaunchKernelGGL (kernel, dim3 ((unsigned int)(cls->slice.count / L)), dim3 (ST_THREADS), lds, (hipStream_t) stream, items, L, chunk_frames);
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+// the three launches of one (section count, layout) class of gathered time-parallel calls, from its slice of the uploaded table:
+// the entry's spec kernel, the check pass (it has no layout and no direction) and the entry's commit kernel
+static int bq_clips_launch (void (*spec) (const ArtBqClip *, int, long), void (*commit) (const ArtBqClip *, int, int), const ArtBqClipClass *cls,
+                            const void *d_table, void *stream)
+{
+    hipStream_t st = (hipStream_t) stream;
+    const ArtBqClip *items = (const ArtBqClip *)((const char *) d_table + cls->offset);
+    const int n = cls->count, channels = cls->channels;
+    const long tasks = cls->tasks;
+    if (n <= 0) return 0;
+    if (cls->S < 1 || cls->S > MAX_CHAIN || tasks <= 0 || channels <= 0) return -1;
+    const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256);
+    hipLaunchKernelGGL (spec, grid, block, 0, st, items, n, tasks);
+    hipLaunchKernelGGL (BQ_PICK_S (cls->S, bq_clips_check_kernel), grid, block, 0, st, items, n, tasks);
+    hipLaunchKernelGGL (commit, dim3 ((unsigned int)((channels + 63) / 64)), dim3 (64), 0, st, items, n, channels);
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
 extern "C" {
 
 // The time-parallel bit-exact cascade (biquad_spec_kernel): `d_in` -> `d_out` (distinct buffers), frames x C with the given
@@ -2497,83 +2349,28 @@ int arthip_biquad_batch_lanes (int lanes) { return batch_lanes (lanes, BQ_BATCH_
 
 int arthip_biquad_batch_launch (const ArtBqClass *cls, const void *d_table, void *stream)
 {
-    hipStream_t st = (hipStream_t) stream;
-    const ArtBqLane *items = (const ArtBqLane *)((const char *) d_table + cls->slice.offset);
-    const int L = cls->slice.lanes;
-    if (cls->slice.count <= 0) return 0;
-    if (L < 1 || L > 64 || cls->slice.count % L || cls->S < 1 || cls->S > 4) return -1;
-    const int chunk_frames = batch_chunk_frames (L, BQ_BATCH_RUN);
-    const size_t lds = (size_t) 3 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 3 DEC_CHUNK samples (48 KiB)
-    const dim3 grid ((unsigned int)(cls->slice.count / L)), block (ST_THREADS);
-    switch (cls->S) {
-    case 1: hipLaunchKernelGGL (biquad_batch_pipe_kernel<1>, grid, block, lds, st, items, L, chunk_frames); break;
-    case 2: hipLaunchKernelGGL (biquad_batch_pipe_kernel<2>, grid, block, lds, st, items, L, chunk_frames); break;
-    case 3: hipLaunchKernelGGL (biquad_batch_pipe_kernel<3>, grid, block, lds, st, items, L, chunk_frames); break;
-    default: hipLaunchKernelGGL (biquad_batch_pipe_kernel<4>, grid, block, lds, st, items, L, chunk_frames); break;
-    }
-    return hipGetLastError () == hipSuccess ? 0 : -1;
+    return bq_pipe_launch<ArtBqLane> (BQ_PICK_S (cls->S, biquad_batch_pipe_kernel), cls, d_table, stream);
 }
 
-// the three launches of one (section count, layout) class of gathered time-parallel calls, from its slice of the uploaded table
+// ... and of one serial class of the out-of-place entry (ArtBqFilterLane lanes)
+int arthip_biquad_filter_batch_launch (const ArtBqClass *cls, const void *d_table, int reversed, void *stream)
+{
+    return bq_pipe_launch<ArtBqFilterLane> (reversed ? BQ_PICK_S (cls->S, bq_filter_pipe_kernel, true) : BQ_PICK_S (cls->S, bq_filter_pipe_kernel, false), cls, d_table, stream);
+}
+
 int arthip_biquad_clips_launch (const ArtBqClipClass *cls, const void *d_table, void *stream)
 {
-    hipStream_t st = (hipStream_t) stream;
-    const ArtBqClip *items = (const ArtBqClip *)((const char *) d_table + cls->offset);
-    const int n = cls->count, channels = cls->channels;
-    const long tasks = cls->tasks;
-    if (n <= 0) return 0;
-    if (cls->S < 1 || cls->S > MAX_CHAIN || tasks <= 0 || channels <= 0) return -1;
-    const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256), cgrid ((unsigned int)((channels + 63) / 64)), cblock (64);
-#define CLIPS_GO(SS, PL) do { \
-        hipLaunchKernelGGL ((bq_clips_spec_kernel<SS, PL>), grid, block, 0, st, items, n, tasks); \
-        hipLaunchKernelGGL (bq_clips_check_kernel<SS>, grid, block, 0, st, items, n, tasks); \
-        hipLaunchKernelGGL ((bq_clips_commit_kernel<SS, PL>), cgrid, cblock, 0, st, items, n, channels); } while (0)
-#define CLIPS_LAYOUT(SS) do { if (cls->planar) CLIPS_GO (SS, true); else CLIPS_GO (SS, false); } while (0)
-    switch (cls->S) { case 1: CLIPS_LAYOUT (1); break; case 2: CLIPS_LAYOUT (2); break; case 3: CLIPS_LAYOUT (3); break; default: CLIPS_LAYOUT (4); }
-#undef CLIPS_LAYOUT
-#undef CLIPS_GO
-    return hipGetLastError () == hipSuccess ? 0 : -1;
+    if (cls->planar) return bq_clips_launch (BQ_PICK_S (cls->S, bq_clips_spec_kernel, true), BQ_PICK_S (cls->S, bq_clips_commit_kernel, true), cls, d_table, stream);
+    return bq_clips_launch (BQ_PICK_S (cls->S, bq_clips_spec_kernel, false), BQ_PICK_S (cls->S, bq_clips_commit_kernel, false), cls, d_table, stream);
 }
 
 // the same three launches out of place and with a direction (biquadBankFilterClipsPlanarDevice): the spec pass arms the items' flags
 int arthip_biquad_filter_clips_launch (const ArtBqClipClass *cls, const void *d_table, int reversed, void *stream)
 {
-    hipStream_t st = (hipStream_t) stream;
-    const ArtBqClip *items = (const ArtBqClip *)((const char *) d_table + cls->offset);
-    const int n = cls->count, channels = cls->channels;
-    const long tasks = cls->tasks;
-    if (n <= 0) return 0;
-    if (cls->S < 1 || cls->S > MAX_CHAIN || tasks <= 0 || channels <= 0) return -1;
-    const dim3 grid ((unsigned int)((tasks + 255) / 256)), block (256), cgrid ((unsigned int)((channels + 63) / 64)), cblock (64);
-#define FILTER_GO(SS, PL, RV) do { \
-        hipLaunchKernelGGL ((bq_filter_spec_kernel<SS, PL, RV>), grid, block, 0, st, items, n, tasks); \
-        hipLaunchKernelGGL (bq_clips_check_kernel<SS>, grid, block, 0, st, items, n, tasks); \
-        hipLaunchKernelGGL ((bq_filter_commit_kernel<SS, PL, RV>), cgrid, cblock, 0, st, items, n, channels); } while (0)
-#define FILTER_DIR(SS, PL) do { if (reversed) FILTER_GO (SS, PL, true); else FILTER_GO (SS, PL, false); } while (0)
-#define FILTER_LAYOUT(SS) do { if (cls->planar) FILTER_DIR (SS, true); else FILTER_DIR (SS, false); } while (0)
-    switch (cls->S) { case 1: FILTER_LAYOUT (1); break; case 2: FILTER_LAYOUT (2); break; case 3: FILTER_LAYOUT (3); break; default: FILTER_LAYOUT (4); }
-#undef FILTER_LAYOUT
-#undef FILTER_DIR
+#define FILTER_GO(PL, RV) bq_clips_launch (BQ_PICK_S (cls->S, bq_filter_spec_kernel, PL, RV), BQ_PICK_S (cls->S, bq_filter_commit_kernel, PL, RV), cls, d_table, stream)
+    if (cls->planar) return reversed ? FILTER_GO (true, true) : FILTER_GO (true, false);
+    return reversed ? FILTER_GO (false, true) : FILTER_GO (false, false);
 #undef FILTER_GO
-    return hipGetLastError () == hipSuccess ? 0 : -1;
-}
-
-// ... and one launch of one serial class of it (ArtBqFilterLane lanes), sized as arthip_biquad_batch_launch sizes its own
-int arthip_biquad_filter_batch_launch (const ArtBqClass *cls, const void *d_table, int reversed, void *stream)
-{
-    hipStream_t st = (hipStream_t) stream;
-    const ArtBqFilterLane *items = (const ArtBqFilterLane *)((const char *) d_table + cls->slice.offset);
-    const int L = cls->slice.lanes;
-    if (cls->slice.count <= 0) return 0;
-    if (L < 1 || L > 64 || cls->slice.count % L || cls->S < 1 || cls->S > 4) return -1;
-    const int chunk_frames = batch_chunk_frames (L, BQ_BATCH_RUN);
-    const size_t lds = (size_t) 3 * L * (chunk_frames + 4) * sizeof (art_s);          // <= 3 DEC_CHUNK samples (48 KiB)
-    const dim3 grid ((unsigned int)(cls->slice.count / L)), block (ST_THREADS);
-#define FILTER_PIPE(SS) do { if (reversed) hipLaunchKernelGGL ((bq_filter_pipe_kernel<SS, true>), grid, block, lds, st, items, L, chunk_frames); \
-                             else hipLaunchKernelGGL ((bq_filter_pipe_kernel<SS, false>), grid, block, lds, st, items, L, chunk_frames); } while (0)
-    switch (cls->S) { case 1: FILTER_PIPE (1); break; case 2: FILTER_PIPE (2); break; case 3: FILTER_PIPE (3); break; default: FILTER_PIPE (4); }
-#undef FILTER_PIPE
-    return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 
 // one launch of `n` strided copies (`tasks`: the sum of rows * groups over the items) from the uploaded table

@@ -489,3 +489,167 @@ def test_autograd_gradcheck_on_the_8_byte_build():
     x = torch.from_numpy(0.25 * np.random.default_rng(81).standard_normal((2, 2, 40))).cuda().requires_grad_()
     assert torch.autograd.gradcheck(lambda t: cf(t, [40, 23]), (x,), eps=1e-6, atol=1e-7, rtol=1e-6)
     cf.close()
+
+
+# ---- 11. the shared runs' address arithmetic at its edges --------------------------------------------------------------------------
+# One copy of the plane run, the interleaved run, the pipeline and its chunk mover serves this entry in both directions and the
+# in-place entry: every way the runs cut a plane, at every alignment of either side.
+EDGE_FRAMES = [513, 514, 519, 520, 521, 528]    # behind four chunks of 128: a last chunk of 1, 2, 7, 8, 9 and 16 frames (head only, no
+                                                # whole batch, one batch exactly, a batch and a tail), and every chunk in front of it
+SERIAL_FRAMES = [1, 3, 4, 5, 59, 60, 61, 121]   # the pipeline's chunk is 60 frames: a lane that sits out, both sides of the cut, a third chunk
+
+
+def _q(M):
+    return 16 // (_width(M) // 8)                # samples to 16 bytes
+
+
+def _quick_sections(M, ch):
+    """one order-1 section per channel whose pole (0.15, 0.14, ...) is forgotten within 15 frames (8-byte: 26): the shortest chunk"""
+    secs = (M.Biquad * ch)()
+    for c in range(ch):
+        co = M.BiquadCoefficients(a0=0.3, a1=0.2 + 0.01 * c, b1=-0.15 + 0.01 * c)
+        M.lib().biquad_init(C.byref(secs[c]), C.byref(co), 1.0)
+    return secs
+
+
+def _edge_filter(M, forced, monkeypatch):
+    """(S, sections of a 2-channel bank, a function that makes such a bank, chunk length).  forced: ART's post-filter with the warm-up
+    forced to 2 frames — chunks of 128 in both builds, and nearly every chunk repaired by the commit pass; else a filter with its
+    own warm-up: no repairs, what the speculative pass stored is what is compared"""
+    if forced:
+        monkeypatch.setenv("ARTAMD_BIQUAD_WARMUP", "2")
+        S, secs = 2, TB._sections(M, 2, 2, "post")
+    else:
+        S, secs = 1, _quick_sections(M, 2)
+    L = TC._chunk(M, secs, S)
+    banks = []
+
+    def make(count):
+        if forced:
+            monkeypatch.setenv("ARTAMD_BIQUAD_WARMUP", "2")
+        banks.extend(M.BiquadBank(secs, 2, S) for _ in range(count))
+        monkeypatch.delenv("ARTAMD_BIQUAD_WARMUP", raising=False)
+        return banks[-count:]
+    monkeypatch.delenv("ARTAMD_BIQUAD_WARMUP", raising=False)
+    return S, secs, make, L
+
+
+def _edge_specs(M, S, L, out_offsets=True):
+    """2-channel planar items, one for each length and each start of the input plane within 16 bytes and (out_offsets) of the
+    output plane; the pitch is a multiple of 16 bytes, so that both planes of an item start alike"""
+    q, smax = _q(M), TB._serial_max(M)
+    specs = [dict(ch=2, S=S, kind=None, frames=n, planar=True, extra=(-n) % q, offset=oi, out_offset=oo, L=L, gathered=True)
+             for n in EDGE_FRAMES for oi in range(q) for oo in (range(q) if out_offsets else [oi])]
+    assert L and all(s["frames"] >= 2 * L and s["frames"] > smax for s in specs)
+    return specs
+
+
+def _serial_specs(M, out_offsets=True):
+    """serial lanes of every length: 3-channel planar items at each start of either plane within 16 bytes, and an interleaved item
+    in their middle wide enough for the class to pass 512 lanes — from there on the lane rule puts two lanes into a workgroup, and
+    with an odd lane count per length the pairs straddle the items, the layouts and the lengths"""
+    q, specs = _q(M), []
+    for n in SERIAL_FRAMES:
+        planar = [dict(ch=3, S=2, kind="hand", frames=n, planar=True, extra=(-n) % q, offset=oi, out_offset=oo, L=0, gathered=False)
+                  for oi in range(q) for oo in (range(q) if out_offsets else [oi])]
+        wide = 65 - 3 * len(planar) if 3 * len(planar) < 32 else 33
+        wide += (3 * len(planar) + wide + 1) % 2
+        inter = dict(ch=wide, S=2, kind="hand", frames=n, planar=False, extra=0, offset=1, out_offset=0, L=0, gathered=False)
+        specs += planar[:len(planar) // 2] + [inter] + planar[len(planar) // 2:]
+    lanes = sum(s["ch"] for s in specs)
+    assert lanes // len(SERIAL_FRAMES) % 2 == 1 and lanes > 512 and M.lib().arthip_biquad_batch_lanes(lanes) == 2
+    return specs
+
+
+_own_out = lambda s, i: (s["extra"], s["out_offset"])
+
+
+@pytest.mark.parametrize("width,forced", [(32, False), (32, True), (64, False), (64, True)])
+def test_plane_runs_at_every_alignment_and_tail_in_both_directions(monkeypatch, width, forced):
+    M = A.binding(width)
+    S, secs, make, L = _edge_filter(M, forced, monkeypatch)
+    assert L == 128 or (width == 64 and not forced)
+    specs = _edge_specs(M, S, L)
+    assert len(specs) == len(EDGE_FRAMES) * _q(M) ** 2
+    (bank,) = make(1)
+    xs = [_signal(2, s["frames"], 1100 + i, _dtype(M)) for i, s in enumerate(specs)]
+    hx = [x.cpu().numpy() for x in xs]
+    for reverse, oracle in ((0, _oracle_forward), (1, _oracle_reversed)):
+        before = bank.repairs()
+        rc, ins, outs = _run(M, specs, [bank] * len(specs), xs, reverse, out_layout=_own_out)
+        assert rc == CLASS_LAUNCHES, (reverse, rc)
+        _check_against_oracle(M, specs, xs, ins, outs, [oracle(M, secs, S, h) for h in hx], (width, forced, reverse))
+        assert (bank.repairs() > before) == forced, (width, forced, reverse)
+    bank.close()
+
+
+@pytest.mark.parametrize("width", [32, 64])
+def test_serial_lanes_of_every_length_and_alignment_in_both_directions(width):
+    M = A.binding(width)
+    specs = _serial_specs(M)
+    by_ch = {ch: _bank(M, dict(ch=ch, S=2, kind="hand")) for ch in {s["ch"] for s in specs}}
+    secs = {ch: TB._sections(M, ch, 2, "hand") for ch in by_ch}
+    xs = [_signal(s["ch"], s["frames"], 1300 + i, _dtype(M)) for i, s in enumerate(specs)]
+    hx = [x.cpu().numpy() for x in xs]
+    for reverse, oracle in ((0, _oracle_forward), (1, _oracle_reversed)):
+        rc, ins, outs = _run(M, specs, [by_ch[s["ch"]] for s in specs], xs, reverse, out_layout=_own_out)
+        assert rc == 1, (reverse, rc)
+        _check_against_oracle(M, specs, xs, ins, outs, [oracle(M, secs[s["ch"]], 2, h) for s, h in zip(specs, hx)], (width, reverse))
+    for b in by_ch.values():
+        b.close()
+
+
+def _oracle_in_place(M, secs, S, x):
+    """_oracle_forward, and the sections as the oracle leaves them"""
+    OB = O.binding(_width(M))
+    OL = OB.load_oracle()
+    y = np.ascontiguousarray(x, dtype=_np(M)).copy()
+    ch, n = y.shape
+    left = [OB.Biquad.from_buffer_copy(bytes(memoryview(secs[k]))) for k in range(ch * S)]
+    for c in range(ch):
+        for s in range(S):
+            OL.ora_biquad_buffer(C.byref(left[c * S + s]), C.cast(y[c].ctypes.data, OB.f32p), n, 1)
+    return y, left
+
+
+def _clips_entry_equals_the_oracle(M, specs, banks, sections, what):
+    """biquadBankApplyClipsPlanarDevice from the start on dirty banks: the bits in place, the padding and the final bank state"""
+    xs = [_signal(s["ch"], s["frames"], 1500 + i, _dtype(M)) for i, s in enumerate(specs)]
+    bufs = [_lay(s, x) for s, x in zip(specs, xs)]
+    for b, s in zip(banks, specs):                                       # (from the start: what a bank went through before does not count)
+        b.apply_device(_signal(s["ch"], 9, 3, _dtype(M)).t().contiguous(), 9)
+    torch.cuda.synchronize()
+    rc = M.biquad_clips_planar_device(banks, [p.ptr for p in bufs], [p.pitch if s["planar"] else 0 for s, p in zip(specs, bufs)],
+                                      [s["frames"] for s in specs], from_start=True)
+    torch.cuda.synchronize()
+    hist = lambda q, arr: [arr[(q.index - i) & 3] for i in range(4)]
+    for i, (s, p, x, b) in enumerate(zip(specs, bufs, xs, banks)):
+        want, left = _oracle_in_place(M, sections(s), s["S"], x.cpu().numpy())
+        assert p.padding_untouched(), (what, i, s)
+        assert _same_bits(_unlay(s, p).cpu().numpy(), want), (what, i, s)
+        st = b.read()
+        for k in range(s["ch"] * s["S"]):
+            assert hist(st[k], st[k].x) == hist(left[k], left[k].x) and hist(st[k], st[k].y) == hist(left[k], left[k].y), (what, i, k, s)
+    return rc
+
+
+@pytest.mark.parametrize("width,forced", [(32, False), (32, True), (64, False), (64, True)])
+def test_the_in_place_entry_on_the_same_planes(monkeypatch, width, forced):
+    M = A.binding(width)
+    S, secs, make, L = _edge_filter(M, forced, monkeypatch)
+    specs = _edge_specs(M, S, L, out_offsets=False)
+    banks = make(len(specs))
+    assert _clips_entry_equals_the_oracle(M, specs, banks, lambda s: secs, (width, forced)) == TC.ROUND_LAUNCHES
+    for b in banks:
+        b.close()
+
+
+@pytest.mark.parametrize("width", [32, 64])
+def test_the_in_place_entry_on_the_same_serial_lanes(width):
+    M = A.binding(width)
+    specs = _serial_specs(M, out_offsets=False)
+    banks = [_bank(M, s) for s in specs]
+    rc = _clips_entry_equals_the_oracle(M, specs, banks, lambda s: TB._sections(M, s["ch"], 2, "hand"), width)
+    assert rc == 2                                                       # the copy launch that puts the sections back, and one class
+    for b in banks:
+        b.close()

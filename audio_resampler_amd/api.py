@@ -190,6 +190,9 @@ def _bind(width):
         "resampleAdjointClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "stretchProcessAndFlushBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "artamdStretchClipCapacity": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double]),
+        "artamdStretchLogCapacity": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]),
+        "stretchProcessAndFlushLoggedBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "stretchAdjointClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleProcessSchedulePlanarDevice": (C.c_int, [RP, C.c_int, ptr, C.c_long, ptr, ptr, C.c_long, ptr, ptr, C.c_int, ptr]),
         "resampleProcessScheduleBatchInterleavedDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleProcessScheduleBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
@@ -1012,7 +1015,7 @@ def _bind(width):
             self.p = self.L.stretchInit(shortest, longest, channels, flags)
             if not self.p:
                 raise RuntimeError("stretchInit failed (bad periods or channels, or no MI355X visible — there is no CPU path)")
-            self.channels, self.longest, self.flags = channels, longest, flags
+            self.channels, self.shortest, self.longest, self.flags = channels, shortest, longest, flags
 
         def close(self):
             if getattr(self, "p", None):
@@ -1041,6 +1044,78 @@ def _bind(width):
             raise RuntimeError("stretchProcessAndFlushBatchPlanarDevice failed")
         return list(produced[:n])
 
+    STRETCH_COPY = -2**31                                 # ARTAMD_STRETCH_COPY: `to` of a segment that copies
+
+    def stretch_clips_logged_batch_planar_device(ctxs, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios, d_logs, log_caps):
+        """stretchProcessAndFlushLoggedBatchPlanarDevice: stretch_clips_batch_planar_device from a fresh start that also writes the splice
+        logs (art_hip.h: int32 records out, count, from, to, in values).  d_logs: per clip a pair of device addresses (the second None
+        for a single stage), log_caps: per clip a pair of capacities in segments, at least artamdStretchLogCapacity each.  Returns
+        (frames made per clip, (segments of stage 1, of stage 2) per clip); raises if the call returned -1."""
+        n = len(ctxs)
+        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
+        produced, counts = (C.c_int * max(n, 1))(), (C.c_int * max(2 * n, 1))()
+        rc = lib().stretchProcessAndFlushLoggedBatchPlanarDevice(
+            (C.c_void_p * n)(*[c.p for c in ctxs]), n, (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_ins]), pitches(in_pitches),
+            (C.c_int * n)(*[int(v) for v in n_ins]), (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches),
+            (C.c_int * n)(*[int(v) for v in out_caps]), (C.c_double * n)(*[float(v) for v in ratios]), produced,
+            (C.c_void_p * (2 * n))(*[None if d is None else _dev_ptr(d) for pair in d_logs for d in pair]),
+            (C.c_int * (2 * n))(*[int(v) for pair in log_caps for v in pair]), counts)
+        if rc < 0:
+            raise RuntimeError("stretchProcessAndFlushLoggedBatchPlanarDevice failed")
+        return list(produced[:n]), [(counts[2 * i], counts[2 * i + 1]) for i in range(n)]
+
+    def stretch_adjoint_clips_planar_device(ctxs, d_logs, log_counts, d_gouts, gout_pitches, n_outs, d_gins, gin_pitches, n_ins):
+        """stretchAdjointClipsPlanarDevice: the gradient of logged clips.  Item i: frames 0 .. n_ins[i]-1 of every channel of d_gins[i] are
+        set to the transpose of the map its logs spell out (d_logs, log_counts: pairs per clip, as the logged entry took and gave them)
+        applied to the first n_outs[i] frames of d_gouts[i]; pitches as in stretch_clips_batch_planar_device.  The contexts are only read,
+        and one may be listed any number of times.  Returns the launch count (raises if the call returned -1)."""
+        n = len(ctxs)
+        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
+        rc = lib().stretchAdjointClipsPlanarDevice(
+            (C.c_void_p * n)(*[c.p for c in ctxs]), n,
+            (C.c_void_p * (2 * n))(*[None if d is None else _dev_ptr(d) for pair in d_logs for d in pair]),
+            (C.c_int * (2 * n))(*[int(v) for pair in log_counts for v in pair]),
+            (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_gouts]), pitches(gout_pitches), (C.c_int * n)(*[int(v) for v in n_outs]),
+            (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_gins]), pitches(gin_pitches), (C.c_int * n)(*[int(v) for v in n_ins]))
+        if rc < 0:
+            raise RuntimeError("stretchAdjointClipsPlanarDevice failed")
+        return rc
+
+    def _clip_stretch_grad():
+        """the torch.autograd.Function that attaches a ClipStretcher's output to the graph (made on first use: torch is imported late)"""
+        if "stretch_grad" not in _state:
+            import torch
+
+            class ClipStretchGrad(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, x, y, clip, record):
+                    ctx.clip, ctx.record, ctx.x_shape = clip, record, x.shape
+                    return y.view_as(y)
+
+                @staticmethod
+                @torch.autograd.function.once_differentiable
+                def backward(ctx, gy):
+                    clip = ctx.clip
+                    owners, logs, counts, lengths, made, _ = ctx.record   # (logs: addresses inside the device tensor the record keeps alive)
+                    B, Cn, T = ctx.x_shape
+                    if any(o.p is None for o in owners):
+                        raise RuntimeError("the ClipStretcher was closed before backward")
+                    if not _rows_apart(gy):
+                        gy = gy.contiguous()
+                    gx = torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device)     # (zero at and past lengths[i])
+                    if B:
+                        owners[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
+                        size = gy.element_size()
+                        gy_pitch, gx_pitch = (gy.stride(1), gx.stride(1)) if Cn > 1 else (0, 0)
+                        stretch_adjoint_clips_planar_device(
+                            owners, logs, counts, [gy.data_ptr() + i * gy.stride(0) * size for i in range(B)], [gy_pitch] * B,
+                            [min(m, gy.shape[2]) for m in made],
+                            [gx.data_ptr() + i * gx.stride(0) * size for i in range(B)], [gx_pitch] * B, lengths)
+                    return gx, None, None, None
+
+            _state["stretch_grad"] = ClipStretchGrad
+        return _state["stretch_grad"]
+
     class ClipStretcher:
         """Whole clips, channels-first, stretched in time without a change of pitch: x [B, C, T] (or [C, T]) on the GPU and a ratio
         (output length over input length, as stretchProcess takes it; a float, or one value per clip) in, (y [B, C, Tout_max],
@@ -1051,12 +1126,23 @@ def _bind(width):
         flags make one pool.  Ratios outside 0.25 .. 4 (0.5 .. 2 for given flags without STRETCH_DUAL_FLAG) and more than two channels
         raise.  Runs on the caller's current torch stream; a larger batch is made max_batch clips at a time.  Its output feeds
         ClipResampler as it comes: a pitch shift by `pitch` at a tempo change `tempo` is ClipStretcher at the ratio pitch / tempo
-        followed by ClipResampler from rate * pitch to rate."""
+        followed by ClipResampler from rate * pitch to rate.
 
-        def __init__(self, channels, rate, flags=None, max_batch=1024):
+        Differentiable: when x requires grad (and grad mode is on) the same clips go through stretchProcessAndFlushLoggedBatchPlanarDevice
+        — the same samples and lengths, bit for bit — which also records every splice; the logs stay on the device, held by a
+        once-differentiable autograd.Function that attaches y to the graph.  The period search's choices are piecewise constant in
+        the samples, so between their boundaries a clip is the sparse linear map its log spells out, and backward is that map's
+        transpose (stretchAdjointClipsPlanarDevice, one call for the whole batch, both pools together) on the rows of grad_y: the
+        gradient is shaped like x and zero at and past lengths[i]; the ratio and out_lengths carry none.  Backward raises after close().
+        segments=True: the call returns a third value, per clip a list of one or two int32 numpy arrays [n, 4] (out, count, from, to in
+        VALUES, frame * channels + channel; to == STRETCH_COPY: a copy) — the exact time map from input to output, for labels that must
+        follow a stretched clip; with or without grad, at the price of the logged entry and one download."""
+
+        def __init__(self, channels, rate, flags=None, max_batch=1024, segments=False):
             if channels not in (1, 2):
                 raise ValueError("mono or stereo only")
             self.channels, self.rate, self.flags, self.max_batch = channels, int(rate), flags, max(1, int(max_batch))
+            self.segments = bool(segments)
             self.shortest, self.longest = self.rate // 350, self.rate // 50
             self.pools = {}                                      # flags -> contexts
 
@@ -1104,6 +1190,24 @@ def _bind(width):
                     rooms[i] = L.artamdStretchClipCapacity(self.longest, flags, lengths[i], ratios[i])
                     if rooms[i] < 0:
                         raise ValueError("clip too long")
+            tracked = x.requires_grad and torch.is_grad_enabled()
+            logged = tracked or self.segments
+            if logged:
+                # one tensor of records for the call; clip i's stages at caps_at[i] and behind
+                stages = {i: (2 if flags & STRETCH_DUAL_FLAG else 1) for flags, idx in groups.items() for i in idx}
+                caps = [[0, 0] for _ in range(B)]
+                for flags, idx in groups.items():
+                    for i in idx:
+                        for s in range(stages[i]):
+                            caps[i][s] = L.artamdStretchLogCapacity(self.shortest, self.longest, flags, lengths[i], ratios[i], s)
+                starts, total = [], 0
+                for i in range(B):
+                    starts.append((total, total + caps[i][0]))
+                    total += caps[i][0] + caps[i][1]
+                records = torch.empty(max(total, 1), 4, dtype=torch.int32, device=x.device)
+                log_ptrs = [(records.data_ptr() + 16 * starts[i][0], records.data_ptr() + 16 * starts[i][1] if stages[i] == 2 else None)
+                            for i in range(B)]
+                counts = [(0, 0)] * B
             stream = torch.cuda.current_stream(x.device).cuda_stream
             y = torch.zeros(B, Cn, max(rooms, default=0), dtype=x.dtype, device=x.device)
             size = x.element_size()
@@ -1118,14 +1222,31 @@ def _bind(width):
                     s.set_stream(stream)
                 for b0 in range(0, len(idx), self.max_batch):
                     part = idx[b0:b0 + self.max_batch]
-                    got = stretch_clips_batch_planar_device(
-                        pool[:len(part)], [xp + i * x.stride(0) * size for i in part], [in_pitch] * len(part), [lengths[i] for i in part],
-                        [yp + i * y.stride(0) * size for i in part], [out_pitch] * len(part), [rooms[i] for i in part],
-                        [ratios[i] for i in part], from_start=True)
+                    args = (pool[:len(part)], [xp + i * x.stride(0) * size for i in part], [in_pitch] * len(part), [lengths[i] for i in part],
+                            [yp + i * y.stride(0) * size for i in part], [out_pitch] * len(part), [rooms[i] for i in part],
+                            [ratios[i] for i in part])
+                    if logged:
+                        got, cnt = stretch_clips_logged_batch_planar_device(*args, [log_ptrs[i] for i in part], [caps[i] for i in part])
+                        for i, c in zip(part, cnt):
+                            counts[i] = c
+                    else:
+                        got = stretch_clips_batch_planar_device(*args, from_start=True)
                     for i, g in zip(part, got):
                         made[i] = g
             out_lengths = torch.tensor(made, dtype=torch.int64)
-            return y[:, :, :max(made, default=0)], out_lengths
+            y = y[:, :, :max(made, default=0)]
+            if tracked:
+                # the adjoint only reads its contexts: each clip's pool's first one stands for it
+                owners = [None] * B
+                for flags, idx in groups.items():
+                    for i in idx:
+                        owners[i] = self.pools[flags][0]
+                y = _clip_stretch_grad().apply(x, y, self, (owners, log_ptrs, counts, lengths, made, records))
+            if self.segments:
+                host = records.cpu().numpy()
+                maps = [[host[starts[i][s]:starts[i][s] + counts[i][s]].copy() for s in range(stages[i])] for i in range(B)]
+                return y, out_lengths, maps
+            return y, out_lengths
 
     def ingest_batch_device(d_ins, gains, bits, nbytes, strides, d_outs, counts, stream=None):
         """floatIntegersBatchLEDevice: item i as floatIntegersLEDevice (d_ins[i], gains[i], bits[i], nbytes[i], strides[i], d_outs[i],

@@ -504,6 +504,31 @@ int arthip_stretch_batch (const ArtStretchItem *d_items, ArtStretchDone *d_done,
  * the output at out + c * out_pitch (0: that side interleaved).  No bounds checks: the caller has made sure `out` holds it all */
 typedef struct { ArtStretchArgs args; const art_s *in; art_s *out; long in_pitch, out_pitch; double ratio; int frames, from_start; } ArtStretchClip;
 int arthip_stretch_clips (const ArtStretchClip *d_items, ArtStretchDone *d_done, int n, void *stream);
+/* the same launch from a fresh start (from_start is taken as set) with the splice log (art_hip.h) written: item i's stages write their
+ * segments to d_logs [i].seg [0 / 1] (the second unused for a single stage) and their number to d_counts [2 i], [2 i + 1].  No bounds
+ * checks on the logs either */
+typedef struct { ArtamdStretchSegment *seg [2]; } ArtStretchLogs;
+int arthip_stretch_clips_logged (const ArtStretchClip *d_items, ArtStretchDone *d_done, const ArtStretchLogs *d_logs, int *d_counts, int n, void *stream);
+
+/* ---- transpose of a logged stage (stretch_adjoint.hip) ---- */
+/* One stage of one clip: gx [v] for the values v < gx_values of the stage's input stream from the segments of `log`, terms at outputs
+ * o >= gy_values dropped.  Values are addressed as the forward addresses them: value v is channel v % channels of frame v / channels, at
+ * base + channel * pitch + frame (pitch != 0) or base + v (pitch 0: interleaved).  `mid` != NULL (a cascaded pair): the count of the
+ * intermediate stream — gx_values of its second stage (mid_is_gx), gy_values of its first — is read on the device: the end of the last
+ * of the mid_count segments of stage 1's log (0 for none); the host's figure is then only the bound the tiles were laid out for.
+ * A segment reads nothing below from - back and nothing at or above from + ahead (values): a longest period, the ring. */
+typedef struct {
+    const ArtamdStretchSegment *log, *mid;
+    const art_s *gy; art_s *gx;
+    long gy_pitch, gx_pitch;
+    int count, mid_count, mid_is_gx;
+    int gy_values, gx_values;
+    int channels, back, ahead;
+    unsigned int tile0;                  /* first workgroup of the item in its launch (filled by arthip_stretch_adjoint) */
+    int pad;
+} ArtStretchAdjItem;
+/* uploads the n items to d_table (n items of device memory) and launches one workgroup per tile of each; 0 or -1 */
+int arthip_stretch_adjoint (ArtStretchAdjItem *items, int n, void *d_table, void *stream);
 
 /* a failure of an entry point that cannot return one (the reference's ABI has no error codes): printed, counted (artamdErrorCount /
  * artamdLastError), fatal under ARTAMD_ABORT_ON_ERROR=1 — pcm_host.c */

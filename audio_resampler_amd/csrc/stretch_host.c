@@ -271,16 +271,50 @@ int artamdStretchClipCapacity (int longest_period, int flags, int num_samples, d
     return frames > 0x7fffffff ? -1 : (int) frames;     /* (-1: more than an int holds) */
 }
 
-/* Whole clips in ONE launch and one synchronisation: art_hip.h.  Everything is checked before anything is enqueued. */
-int stretchProcessAndFlushBatchPlanarDevice (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const long *inputPitches,
-                                             const int *num_samples, artsample_t *const *d_outputs, const long *outputPitches,
-                                             const int *outputCaps, const double *ratios, int fromStart, int *produced)
+/* Segments a stage can write (art_hip.h).  A step needs the mark to move on by its period at least (p for the 2:1 step, 2 p for the
+ * others; the quick 2:1 step makes two fades and moves on by 2 p) and p is never below the shortest period, so a stage that is fed
+ * `fed` frames in all takes at most fed / shortest steps, of three segments at the most (the 3:2 step).  Beyond the steps a stage
+ * writes one segment per feed call that ends in the pass-through, and one per flush (drain's pending copy), of which the clip kernel
+ * makes four at the most.  Stage 0 is fed once.  Stage 1 is fed once per step of stage 0, once by stage 0's pass-through and once per
+ * flush of stage 0, and what it is fed in all is what stage 0 makes: at most stage_bound (). */
+int artamdStretchLogCapacity (int shortest_period, int longest_period, int flags, int num_samples, double ratio, int stage)
+{
+    const int fast = (flags & STRETCH_FAST_FLAG) != 0, dual = (flags & STRETCH_DUAL_FLAG) != 0;
+    double here = ratio;
+
+    if (artamdStretchClipCapacity (longest_period, flags, num_samples, ratio) < 0) return -1;
+    if (fast) { longest_period = (longest_period + 1) & ~1; shortest_period &= ~1; }
+    if (shortest_period < 1 || stage < 0 || stage > 1) return -1;
+    if (stage == 1 && !dual) return 0;
+    if (num_samples < 0) num_samples = 0;
+    const long long steps0 = num_samples / shortest_period;
+    long long segments = 3 * steps0 + 1 + 4;
+    if (stage == 1) {
+        if (here < 0.5) here = 0.5; else if (here > 2.0) here = 2.0;     /* stage 0's share of the ratio */
+        const long long fed = stage_bound (num_samples, longest_period, fast, here);
+        segments = 3 * (fed / shortest_period) + (steps0 + 1 + 4) + 4;
+    }
+    return segments > 0x7fffffff ? -1 : (int) segments;
+}
+
+/* Whole clips in ONE launch and one synchronisation: art_hip.h.  Everything is checked before anything is enqueued.  With d_logs the
+ * logging kernel, from a fresh start, and the segment counts in the same read-back. */
+static int clips_call (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const long *inputPitches,
+                       const int *num_samples, artsample_t *const *d_outputs, const long *outputPitches,
+                       const int *outputCaps, const double *ratios, int fromStart, int *produced,
+                       ArtamdStretchSegment *const *d_logs, const int *logCaps, int *logCounts, int logged)
 {
     if (n <= 0) return 0;
     if (!cxts || !num_samples || !d_outputs || !outputCaps || !ratios || !produced) return -1;
+    if (logged && (!d_logs || !logCaps || !logCounts)) return -1;
     for (int i = 0; i < n; ++i) {
         const Stretch *c = cxts [i];
         if (!c || !c->hip) return -1;
+        for (int s = 0; logged && s < (c->next ? 2 : 1); ++s) {
+            const int segments = artamdStretchLogCapacity (c->shortest / c->num_chans, c->longest / c->num_chans,
+                                                           (c->fast_mode ? STRETCH_FAST_FLAG : 0) | (c->next ? STRETCH_DUAL_FLAG : 0), num_samples [i], ratios [i], s);
+            if (!d_logs [2 * i + s] || segments < 0 || logCaps [2 * i + s] < segments) return -1;
+        }
         const int need = artamdStretchClipCapacity (c->longest / c->num_chans, (c->fast_mode ? STRETCH_FAST_FLAG : 0) | (c->next ? STRETCH_DUAL_FLAG : 0),
                                                     num_samples [i], ratios [i]);
         if (!d_outputs [i] || (num_samples [i] > 0 && (!d_samples || !d_samples [i])) || need < 0 || outputCaps [i] < need) return -1;
@@ -291,13 +325,17 @@ int stretchProcessAndFlushBatchPlanarDevice (Stretch *const *cxts, int n, const 
     if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "stretch", "context")) return -1;
 
     struct artamd_stretch *lead = cxts [0]->hip;
-    const size_t items_bytes = ((size_t) n * sizeof (ArtStretchClip) + 63) & ~(size_t) 63, done_bytes = (size_t) n * sizeof (ArtStretchDone);
+    /* the table: the clips, then (logged) their log pointers; what comes back: the results, then (logged) two counts per clip */
+    const size_t clips_bytes = ((size_t) n * sizeof (ArtStretchClip) + 63) & ~(size_t) 63;
+    const size_t items_bytes = clips_bytes + (logged ? ((size_t) n * sizeof (ArtStretchLogs) + 63) & ~(size_t) 63 : 0);
+    const size_t results_bytes = (size_t) n * sizeof (ArtStretchDone), done_bytes = results_bytes + (logged ? (size_t) n * 2 * sizeof (int) : 0);
     ArtStretchClip *items = malloc (items_bytes);
     ArtStretchDone *done = malloc (done_bytes);
     int rc = -1;
 
     lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, items_bytes + done_bytes);
     if (!items || !done || !lead->d_batch) goto out;
+    ArtStretchLogs *logs = (ArtStretchLogs *)((char *) items + clips_bytes);
 
     for (int i = 0; i < n; ++i) {
         items [i].args = cxts [i]->hip->args;
@@ -308,11 +346,14 @@ int stretchProcessAndFlushBatchPlanarDevice (Stretch *const *cxts, int n, const 
         items [i].ratio = ratios [i];
         items [i].frames = num_samples [i] > 0 ? num_samples [i] : 0;
         items [i].from_start = fromStart != 0;
+        if (logged) { logs [i].seg [0] = d_logs [2 * i]; logs [i].seg [1] = cxts [i]->next ? d_logs [2 * i + 1] : NULL; }
     }
 
     ArtStretchDone *d_done = (ArtStretchDone *)((char *) lead->d_batch + items_bytes);
-    if (arthip_h2d (lead->d_batch, items, (size_t) n * sizeof (ArtStretchClip), lead->stream) ||
-        arthip_stretch_clips ((const ArtStretchClip *) lead->d_batch, d_done, n, lead->stream) ||
+    if (arthip_h2d (lead->d_batch, items, logged ? clips_bytes + (size_t) n * sizeof (ArtStretchLogs) : (size_t) n * sizeof (ArtStretchClip), lead->stream) ||
+        (logged ? arthip_stretch_clips_logged ((const ArtStretchClip *) lead->d_batch, d_done, (const ArtStretchLogs *)((char *) lead->d_batch + clips_bytes),
+                                               (int *)((char *) d_done + results_bytes), n, lead->stream)
+                : arthip_stretch_clips ((const ArtStretchClip *) lead->d_batch, d_done, n, lead->stream)) ||
         arthip_d2h (done, d_done, done_bytes, lead->stream) || arthip_sync (lead->stream)) {
         fprintf (stderr, "artamd: stretch clip launch failed: %s\n", arthip_last_error ());
         artamd_note_failure ("stretch: the whole-clip launch failed");
@@ -320,9 +361,104 @@ int stretchProcessAndFlushBatchPlanarDevice (Stretch *const *cxts, int n, const 
     }
 
     for (int i = 0; i < n; ++i) mirror_state (cxts [i], &done [i], &produced [i]);
+    if (logged) memcpy (logCounts, (const char *) done + results_bytes, (size_t) n * 2 * sizeof (int));
     rc = 0;
 out:
     free (items); free (done);
+    return rc;
+}
+
+int stretchProcessAndFlushBatchPlanarDevice (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const long *inputPitches,
+                                             const int *num_samples, artsample_t *const *d_outputs, const long *outputPitches,
+                                             const int *outputCaps, const double *ratios, int fromStart, int *produced)
+{
+    return clips_call (cxts, n, d_samples, inputPitches, num_samples, d_outputs, outputPitches, outputCaps, ratios, fromStart, produced, NULL, NULL, NULL, 0);
+}
+
+int stretchProcessAndFlushLoggedBatchPlanarDevice (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const long *inputPitches,
+                                                   const int *num_samples, artsample_t *const *d_outputs, const long *outputPitches,
+                                                   const int *outputCaps, const double *ratios, int *produced,
+                                                   ArtamdStretchSegment *const *d_logs, const int *logCaps, int *logCounts)
+{
+    return clips_call (cxts, n, d_samples, inputPitches, num_samples, d_outputs, outputPitches, outputCaps, ratios, 1, produced, d_logs, logCaps, logCounts, 1);
+}
+
+/* The gradient of logged clips: art_hip.h.  Everything is checked before anything is enqueued; the contexts are only read.  The table
+ * (one item per stage) and the pairs' intermediate gradients ride in the lead context's batch buffer. */
+int stretchAdjointClipsPlanarDevice (Stretch *const *cxts, int n, const ArtamdStretchSegment *const *d_logs, const int *logCounts,
+                                     const artsample_t *const *d_gouts, const long *goutPitches, const int *n_outs,
+                                     artsample_t *const *d_gins, const long *ginPitches, const int *n_ins)
+{
+    if (n <= 0) return 0;
+    if (!cxts || !d_logs || !logCounts || !d_gouts || !n_outs || !d_gins || !n_ins) return -1;
+    int last = 0, first = 0;                            /* items of the two launches */
+    size_t mid_values = 0;
+    for (int i = 0; i < n; ++i) {
+        const Stretch *c = cxts [i];
+        if (!c || !c->hip || n_ins [i] < 0 || n_outs [i] < 0) return -1;
+        for (int s = 0; s < (c->next ? 2 : 1); ++s)
+            if (logCounts [2 * i + s] < 0 || (logCounts [2 * i + s] > 0 && !d_logs [2 * i + s])) return -1;
+        if (!n_ins [i]) continue;                       /* (nothing to write: the item takes no further part) */
+        for (int s = 0; s < (c->next ? 2 : 1); ++s) {   /* (a count above what n_ins [i] frames can log at any ratio is not this clip's) */
+            const int cap = artamdStretchLogCapacity (c->shortest / c->num_chans, c->longest / c->num_chans,
+                                                      (c->fast_mode ? STRETCH_FAST_FLAG : 0) | (c->next ? STRETCH_DUAL_FLAG : 0), n_ins [i], 2.0, s);
+            if (logCounts [2 * i + s] > cap) return -1;
+        }
+        const long gy_pitch = goutPitches ? goutPitches [i] : 0, gx_pitch = ginPitches ? ginPitches [i] : 0;
+        if (!d_gins [i] || (n_outs [i] > 0 && !d_gouts [i])) return -1;
+        if (c->num_chans > 1 && ((gy_pitch && gy_pitch < n_outs [i]) || (gx_pitch && gx_pitch < n_ins [i]))) return -1;
+        const long long values = (long long) n_ins [i] * c->num_chans, outs = (long long) n_outs [i] * c->num_chans;
+        const long long mid = c->next ? stage_bound (n_ins [i], c->longest / c->num_chans, c->fast_mode, 2.0) * c->num_chans : 0;
+        if (values > 0x7fffffff || outs > 0x7fffffff || mid > 0x7fffffff) return -1;
+        ++last;
+        if (c->next) { ++first; mid_values += (size_t) mid; }
+    }
+    if (!last) return 0;
+
+    struct artamd_stretch *lead = cxts [0]->hip;
+    const size_t table_bytes = ((size_t)(last + first) * sizeof (ArtStretchAdjItem) + 63) & ~(size_t) 63;
+    ArtStretchAdjItem *items = calloc ((size_t)(last + first), sizeof (ArtStretchAdjItem));
+    int rc = -1, launches = 0;
+
+    lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, table_bytes + mid_values * sizeof (art_s));
+    if (!items || !lead->d_batch) goto out;
+
+    art_s *d_mid = (art_s *)((char *) lead->d_batch + table_bytes);
+    ArtStretchAdjItem *a = items, *b = items + last;   /* the stage that wrote the output; the pairs' first stage */
+    for (int i = 0; i < n; ++i) {
+        const Stretch *c = cxts [i];
+        if (!n_ins [i]) continue;
+        const int C = c->num_chans;
+        a->channels = C; a->back = c->longest; a->ahead = c->inbuff_samples;
+        a->gy = d_gouts [i]; a->gy_pitch = C > 1 && goutPitches ? goutPitches [i] : 0; a->gy_values = n_outs [i] * C;
+        if (!c->next) {
+            a->log = d_logs [2 * i]; a->count = logCounts [2 * i];
+            a->gx = d_gins [i]; a->gx_pitch = C > 1 && ginPitches ? ginPitches [i] : 0; a->gx_values = n_ins [i] * C;
+        }
+        else {
+            const int mid = (int)(stage_bound (n_ins [i], c->longest / C, c->fast_mode, 2.0) * C);
+            a->log = d_logs [2 * i + 1]; a->count = logCounts [2 * i + 1];
+            a->mid = d_logs [2 * i]; a->mid_count = logCounts [2 * i]; a->mid_is_gx = 1;
+            a->gx = d_mid; a->gx_pitch = 0; a->gx_values = mid;
+            *b = *a;
+            b->log = d_logs [2 * i]; b->count = logCounts [2 * i]; b->mid_is_gx = 0;
+            b->gy = d_mid; b->gy_pitch = 0; b->gy_values = mid;
+            b->gx = d_gins [i]; b->gx_pitch = C > 1 && ginPitches ? ginPitches [i] : 0; b->gx_values = n_ins [i] * C;
+            ++b;
+            d_mid += mid;
+        }
+        ++a;
+    }
+
+    if (arthip_stretch_adjoint (items, last, lead->d_batch, lead->stream) ||
+        (++launches, first && arthip_stretch_adjoint (items + last, first, (ArtStretchAdjItem *) lead->d_batch + last, lead->stream))) {
+        fprintf (stderr, "artamd: stretch adjoint launch failed: %s\n", arthip_last_error ());
+        artamd_note_failure ("stretch: the adjoint launch failed");
+        goto out;
+    }
+    rc = launches + (first ? 1 : 0);
+out:
+    free (items);
     return rc;
 }
 

@@ -224,6 +224,40 @@ __device__ __forceinline__ void split_ratio (bool paired, double &ratio, double 
     else if (ratio > 2.0) { rest = ratio / 2.0; ratio = 2.0; }
 }
 
+// The splice log (art_hip.h): what feed / drain record of every copy_values / crossfade that writes a stage's output.  NoLog records
+// nothing and costs nothing: the kernels without a log are what they were.  SpliceLog is a stage's entry of the table the logging
+// kernel keeps in LDS.  Only thread 0 reads or writes an entry, so it needs no barrier; the arguments are scalars every thread carries.
+struct NoLog {
+    __device__ __forceinline__ void copy (int, int) const {}
+    __device__ __forceinline__ void fade (int, int, int) const {}
+    __device__ __forceinline__ void moved (int) const {}
+    __device__ __forceinline__ NoLog next () const { return NoLog {}; }
+};
+
+struct LogStage {
+    ArtamdStretchSegment *seg; int count;
+    int base;                                      // stream index of ring [cur][0]: -hi at the start, moved on by every compaction
+    int out;                                       // values the stage has written
+};
+
+struct SpliceLog {
+    LogStage *s;
+    __device__ __forceinline__ void put (int n, int from, int to) const
+    {
+        if (threadIdx.x == 0 && n > 0) {
+            ArtamdStretchSegment r; r.out = s->out; r.count = n; r.from = from; r.to = to;
+            s->seg [s->count] = r;
+            s->count += 1; s->out += n;
+        }
+    }
+    // n values from ring index `from`; a fade of n values from ring index `from` to ring index `to`
+    __device__ __forceinline__ void copy (int from, int n) const { if (threadIdx.x == 0) put (n, s->base + from, ARTAMD_STRETCH_COPY); }
+    __device__ __forceinline__ void fade (int from, int to, int n) const { if (threadIdx.x == 0) put (n, s->base + from, s->base + to); }
+    // the ring was compacted: what was at index `by` is now at 0
+    __device__ __forceinline__ void moved (int by) const { if (threadIdx.x == 0) s->base += by; }
+    __device__ __forceinline__ SpliceLog next () const { return SpliceLog { s + 1 }; }
+};
+
 // One stage consuming `values` input values.  PAIRED: this is stage 1 of a cascade and hands every step's output to
 // stage 2 (the same function, unpaired).  Returns FRAMES written to `out` (by the last stage).
 template <bool PAIRED, class OUT>
@@ -232,9 +266,9 @@ __device__ __forceinline__ auto step_output (art_s *between, OUT out)
     if constexpr (PAIRED) return between; else return out;
 }
 
-template <bool PAIRED, class IN, class OUT>
+template <bool PAIRED, class IN, class OUT, class LOG = NoLog>
 __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &L, IN in, int values,
-                     OUT out, double ratio)
+                     OUT out, double ratio, LOG log = LOG {})
 {
     const StretchStage &S = stages [0];
     StretchState st = states [0];                  // every thread reads the same words; thread 0 writes them back
@@ -272,11 +306,13 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
 
             if (step == 0.5) {
                 crossfade (dst + made, at, at + p, p);
+                log.fade (st.mark, st.mark + p, p);
                 st.drift += p - (p * 2.0 * ratio);
                 made += p; st.mark += p * 2;
             }
             else if (step == 1.0) {
                 copy_values (dst + made, at, p * 2);
+                log.copy (st.mark, p * 2);
                 if (ratio != 1.0) st.drift += (p * 2.0) - (p * 2.0 * ratio);
                 else st.drift = 0;
                 made += p * 2; st.mark += p * 2;
@@ -285,12 +321,14 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
                 copy_values (dst + made, at, p);
                 crossfade (dst + made + p, at + p, at, p);
                 copy_values (dst + made + p * 2, at + p, p);
+                log.copy (st.mark, p); log.fade (st.mark + p, st.mark, p); log.copy (st.mark + p, p);
                 st.drift += (p * 3.0) - (p * 2.0 * ratio);
                 made += p * 3; st.mark += p * 2;
             }
             else {                                 // 2.0
                 for (int rep = 0; rep < (S.quick ? 2 : 1); ++rep) {
                     crossfade (dst + made, ring + st.mark, ring + st.mark - p, p * 2);
+                    log.fade (st.mark, st.mark - p, p * 2);
                     st.drift += (p * 2.0) - (p * ratio);
                     made += p * 2; st.mark += p;
                 }
@@ -298,7 +336,7 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
             __syncthreads ();                      // step output complete (stage 2 / compaction read it)
 
             if constexpr (PAIRED) {
-                made_next += feed<false> (stages + 1, states + 1, L, (const art_s *) dst, made, out + made_next * S.channels, rest);
+                made_next += feed<false> (stages + 1, states + 1, L, (const art_s *) dst, made, out + made_next * S.channels, rest, log.next ());
                 made = 0;
             }
 
@@ -306,6 +344,7 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
             const int keep = S.room - st.mark + S.hi;
             copy_values (S.ring [st.cur ^ 1], ring + st.mark - S.hi, keep);
             st.cur ^= 1;
+            log.moved (st.mark - S.hi);
             st.fill -= st.mark - S.hi;
             st.mark = S.hi;
             __syncthreads ();
@@ -315,8 +354,9 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
     if (ratio == 1.0 && st.drift == 0.0 && st.fill != st.mark) {        // nothing to stretch: pass the pending values on
         art_s *ring = S.ring [st.cur];
         const int pending = st.fill - st.mark;
+        log.copy (st.mark, pending);               // (a pair's first stage hands the values over where they lie: its output all the same)
         if constexpr (PAIRED)
-            made_next += feed<false> (stages + 1, states + 1, L, (const art_s *)(ring + st.mark), pending, out + made_next * S.channels, rest);
+            made_next += feed<false> (stages + 1, states + 1, L, (const art_s *)(ring + st.mark), pending, out + made_next * S.channels, rest, log.next ());
         else {
             copy_values (dst + made, ring + st.mark, pending);
             made += pending;
@@ -324,6 +364,7 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
         __syncthreads ();
         copy_values (S.ring [st.cur ^ 1], ring + st.fill - S.hi, S.hi);
         st.cur ^= 1;
+        log.moved (st.fill - S.hi);
         st.fill = st.mark = S.hi;
         __syncthreads ();
     }
@@ -334,17 +375,18 @@ __device__ int feed (const StretchStage *stages, StretchState *states, Scratch &
 }
 
 // everything still buffered, at normal speed (stretch.c:335-356)
-template <bool PAIRED, class OUT>
-__device__ int drain (const StretchStage *stages, StretchState *states, Scratch &L, OUT out)
+template <bool PAIRED, class OUT, class LOG = NoLog>
+__device__ int drain (const StretchStage *stages, StretchState *states, Scratch &L, OUT out, LOG log = LOG {})
 {
     const StretchStage &S = stages [0];
     StretchState st = states [0];
     __syncthreads ();
     const int pending = st.fill - st.mark;
     int frames = 0;
+    log.copy (st.mark, pending);                   // (nothing for nothing pending)
     if constexpr (PAIRED) {
-        if (pending) frames = feed<false> (stages + 1, states + 1, L, (const art_s *)(S.ring [st.cur] + st.mark), pending, out, 1.0);
-        if (!frames) frames = drain<false> (stages + 1, states + 1, L, out);
+        if (pending) frames = feed<false> (stages + 1, states + 1, L, (const art_s *)(S.ring [st.cur] + st.mark), pending, out, 1.0, log.next ());
+        if (!frames) frames = drain<false> (stages + 1, states + 1, L, out, log.next ());
     }
     else {
         copy_values (out, S.ring [st.cur] + st.mark, pending);
@@ -454,12 +496,58 @@ void stretch_clip_kernel (const ArtStretchClip *items, ArtStretchDone *done)
     if (threadIdx.x == 0) report (done [blockIdx.x], made, state);
 }
 
+// The same from a fresh start, with every splice recorded (art_hip.h): thread 0 writes one 16-byte record per copy_values / crossfade
+// that makes output; counts [2 b], [2 b + 1]: the segments of clip b's stages.  The body repeats stretch_clip_kernel's, with the log
+// handed to feed / drain, instead of sharing a function with it: that kernel's code object is then, instruction for instruction,
+// what it was without the log.
+__global__ __launch_bounds__ (ST_WG)
+void stretch_clip_logged_kernel (const ArtStretchClip *items, ArtStretchDone *done, const ArtStretchLogs *logs, int *counts)
+{
+    __shared__ Scratch L;
+    __shared__ StretchStage stage [2];
+    __shared__ RowsLayout layout [2];
+    __shared__ LogStage table [2];
+    const ArtStretchClip &it = items [blockIdx.x];
+    if (threadIdx.x == 0) {
+        unpack (it.args, stage, L); layout [0].set (it.in_pitch, it.args.channels); layout [1].set (it.out_pitch, it.args.channels);
+        for (int s = 0; s < 2; ++s) { table [s].seg = logs [blockIdx.x].seg [s]; table [s].count = 0; table [s].base = -it.args.hi; table [s].out = 0; }
+    }
+    StretchState *state = (StretchState *) it.args.state;
+    const int C = it.args.channels, paired = it.args.paired;
+    for (int s = 0; s < (paired ? 2 : 1); ++s) {       // what stretchInit left, always
+        art_s *ring = (art_s *) it.args.ring [s][0];
+        for (int i = threadIdx.x; i < it.args.hi; i += ST_WG) ring [i] = 0;
+        if (threadIdx.x == 0) { StretchState st; st.mark = st.fill = it.args.hi; st.cur = 0; st.pad = 0; st.drift = 0.0; state [s] = st; }
+    }
+    __syncthreads ();
+    const Rows<const art_s> in { it.in, &layout [0] };
+    const Rows<art_s> out { it.out, &layout [1] };
+    const SpliceLog log { table };
+    int made = 0;
+    if (it.frames > 0)
+        made = paired ? feed<true> (stage, state, L, in, it.frames * C, out, it.ratio, log) : feed<false> (stage, state, L, in, it.frames * C, out, it.ratio, log);
+    for (int round = 0; round < 4; ++round) {
+        const int more = paired ? drain<true> (stage, state, L, out + made * C, log) : drain<false> (stage, state, L, out + made * C, log);
+        if (!more) break;
+        made += more;
+    }
+    __syncthreads ();
+    if (threadIdx.x == 0) { report (done [blockIdx.x], made, state); counts [2 * blockIdx.x] = table [0].count; counts [2 * blockIdx.x + 1] = table [1].count; }
+}
+
 } // namespace
 
 extern "C" int arthip_stretch_clips (const ArtStretchClip *d_items, ArtStretchDone *d_done, int n, void *stream)
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL (stretch_clip_kernel, dim3 (n), dim3 (ST_WG), 0, (hipStream_t) stream, d_items, d_done);
+    return hipGetLastError () == hipSuccess ? 0 : -1;
+}
+
+extern "C" int arthip_stretch_clips_logged (const ArtStretchClip *d_items, ArtStretchDone *d_done, const ArtStretchLogs *d_logs, int *d_counts, int n, void *stream)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL (stretch_clip_logged_kernel, dim3 (n), dim3 (ST_WG), 0, (hipStream_t) stream, d_items, d_done, d_logs, d_counts);
     return hipGetLastError () == hipSuccess ? 0 : -1;
 }
 

@@ -591,6 +591,67 @@ int stretchProcessAndFlushBatchPlanarDevice (Stretch *const *cxts, int n, const 
  * Host arithmetic only: no context, no device.  -1: a longest period out of range, or more frames than an int holds. */
 int artamdStretchClipCapacity (int longest_period, int flags, int num_samples, double ratio);
 
+/* ---- the splice log and the gradient of whole stretched clips ---- */
+/* What a stage of the stretcher did to a whole clip from a fresh start, as the list of its splices.  Every output value of a stage is a
+ * copy of one value of its input stream or a cross-fade of two, so with the period search's choices held fixed the stage is a sparse
+ * linear map y = A x with at most two non-zeros per row, and the log IS that map.  Indices count VALUES (frame * channels + channel),
+ * as the kernel indexes its rings: with two channels the fade weight of value i differs between the two channels of a frame.
+ *   to == ARTAMD_STRETCH_COPY   y [out + i] = x [from + i]                                                  for 0 <= i < count
+ *   otherwise (a fade)          y [out + i] = (x [from + i] * (count - i) + x [to + i] * i) / count          (artsample_t, unfused)
+ * `from` / `to` are relative to the first value of the stage's input stream; negative indices are the silence stretchInit leaves in
+ * front of the mark (at most one longest period) and read as zero.  Segments lie in output order and partition the stage's output:
+ * out of each is out + count of the one before, the first is 0, no count is 0; `from` never falls from a segment to the next.  A
+ * cascaded pair (STRETCH_DUAL_FLAG) has two logs: stage 2's input stream is stage 1's output stream, in the order it was handed over. */
+#define ARTAMD_STRETCH_COPY  (-2147483647 - 1)
+typedef struct { int out, count, from, to; } ArtamdStretchSegment;   /* 16 bytes */
+/* segments stage `stage` (0, or 1: the second of a STRETCH_DUAL_FLAG pair) of a context made with these periods (frames, as given to
+ * stretchInit) and flags can write for a clip of num_samples frames at this ratio, from a fresh start.  A step moves the mark on by at
+ * least one shortest period and writes three segments at the most, so a stage that is fed n frames writes at most 3 * (n / shortest)
+ * of them in steps; the rest is one segment per time the stage is fed (the pass-through of a ratio of 1) and one per flush.  Stage 0 is
+ * fed once, num_samples frames, and flushed four times at the most; stage 1 is fed once per step of stage 0, once by its pass-through
+ * and once per flush, in all no more than the bound artamdStretchClipCapacity chains for stage 0's output, and flushed four times.
+ * Host arithmetic only.  0 for stage 1 without STRETCH_DUAL_FLAG; -1 where artamdStretchClipCapacity gives -1, for a shortest period
+ * below 1, a stage other than 0 or 1, or more than an int holds. */
+int artamdStretchLogCapacity (int shortest_period, int longest_period, int flags, int num_samples, double ratio, int stage);
+/* stretchProcessAndFlushBatchPlanarDevice (..., fromStart = 1, ...) that also writes the logs: the same kernel body with the records
+ * added, so the outputs, produced [] and the state left in the contexts are bit for bit that entry's; still one launch and one
+ * synchronisation.  d_logs: 2 n device pointers, item i's stages at [2 i] and [2 i + 1] (the second ignored, and may be NULL, for a
+ * single stage); logCaps: 2 n capacities in segments; logCounts: 2 n counts, host memory, filled from the read-back that brings
+ * produced [] (0 for the absent second stage).  Only clips from a fresh start are logged: a context that continues an earlier call has
+ * no well-defined map of its own.
+ * Returns as that entry.  Refuses (-1, nothing enqueued, nothing counted in artamdErrorCount) what that entry refuses, and a NULL d_logs,
+ * logCaps or logCounts, a NULL log of a stage the context has, or a logCaps entry below artamdStretchLogCapacity: the device code does
+ * not check bounds. */
+int stretchProcessAndFlushLoggedBatchPlanarDevice (Stretch *const *cxts, int n, const artsample_t *const *d_samples, const long *inputPitches,
+                                                   const int *num_samples, artsample_t *const *d_outputs, const long *outputPitches,
+                                                   const int *outputCaps, const double *ratios, int *produced,
+                                                   ArtamdStretchSegment *const *d_logs, const int *logCaps, int *logCounts);
+/* The gradient of logged clips.  Item i: frames 0 .. n_ins [i] - 1 of every channel of d_gins [i] are SET to A_i^T applied to the first
+ * n_outs [i] frames of d_gouts [i], A_i the map of the logs at d_logs [2 i], [2 i + 1] with logCounts [2 i], [2 i + 1] segments (as the
+ * logged entry left them; for a pair A_i = A2 A1); nothing else is written.  Pitches as in the forward: in samples, 0 for an interleaved
+ * side of an item, a NULL array for "every item is"; one channel is the same call in either layout.
+ * The contract, per stage, for input value v (C = channels):
+ *   a term of v is (gy [o] * (artsample_t) w) / (artsample_t) count for each fade with v = from + i (w = count - i) or v = to + i (w = i),
+ *   o = out + i, 0 <= i < count — two roundings, weights of zero included — and gy [o] itself for a copy;
+ *   gx [v] is the sum of v's terms in ascending o, each added with a plain addition (no contraction), from +0;
+ *   terms with o >= n_outs [i] * C are dropped; a value no segment reads is exactly 0.
+ * So gx [v] does not depend on the batch, the item's place in it, the layouts, the tile or the chunking.  The kernel gathers: a workgroup
+ * owns a tile of consecutive input values, and walks the one contiguous range of the log that can touch it — no atomics.
+ * For a pair the gradient of the intermediate stream (as many values as stage 1 made: the end of its last segment, read from the log on
+ * the device) is scratch of cxts [0], sized by what stage 1 can make of n_ins [i] frames at its largest ratio.
+ * The contexts are only READ (channels, stage count, periods, and the stream and scratch of cxts [0]): one context may be listed any
+ * number of times.  Asynchronous on the stream of cxts [0].  Launches: one per stage present in the batch — the stage that wrote the
+ * output for every item, then the first stage of the pairs — two at the most whatever n; their number is returned; an item with
+ * n_ins [i] == 0 writes nothing and launches nothing.  0 for n <= 0.
+ * -1 with nothing enqueued and nothing counted for a NULL list (pitch arrays apart), a NULL context, a NULL log of a stage the context
+ * has, a negative count, a logCounts entry above artamdStretchLogCapacity for n_ins [i] frames at a ratio of 2 (no log of such a clip is
+ * that long), a NULL gradient buffer of an item with n_ins [i] > 0, and with two channels a non-zero pitch below the item's
+ * frames on that side.  -1 if a launch failed (counted in artamdErrorCount): the gradient buffers are then unspecified.
+ * Gradient inputs must not overlap gradient outputs or the logs (not checked). */
+int stretchAdjointClipsPlanarDevice (Stretch *const *cxts, int n, const ArtamdStretchSegment *const *d_logs, const int *logCounts,
+                                     const artsample_t *const *d_gouts, const long *goutPitches, const int *n_outs,
+                                     artsample_t *const *d_gins, const long *ginPitches, const int *n_ins);
+
 #ifdef __cplusplus
 }
 #endif

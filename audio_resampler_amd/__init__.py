@@ -16,7 +16,7 @@ from .api import (  # noqa: F401
     process_batch_device, process_batch_planar_device, process_and_flush_batch_planar_device, ClipResampler,
     process_schedule_batch_device, process_schedule_batch_planar_device,
     decimate_batch_planar_device, decimate_clips_planar_device, process_and_flush_clips_planar_device, adjoint_clips_planar_device, ClipDecimator, biquad_batch_planar_device, biquad_clips_planar_device, ClipFilter,
-    biquad_filter_clips_planar_device,
+    biquad_filter_clips_planar_device, lag_products_batch_device, ClipBiquad,
     STRETCH_FAST_FLAG, STRETCH_DUAL_FLAG, Stretcher, stretch_clips_batch_planar_device, ClipStretcher,
     stretch_clips_logged_batch_planar_device, stretch_adjoint_clips_planar_device, STRETCH_COPY,
 )

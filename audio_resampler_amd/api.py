@@ -168,6 +168,7 @@ def _bind(width):
         "floatIntegersLEDevice": (None, [ptr, C.c_double, C.c_int, C.c_int, C.c_int, ptr, C.c_int, ptr]),
         "floatIntegersBatchLEDevice": (C.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         "artamdExtrapolateBatchDevice": (C.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
+        "artamdLagProductsBatchDevice": (C.c_int, [ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr]),
         # stretch.h
         "stretchInit": (ptr, [C.c_int, C.c_int, C.c_int, C.c_int]),
         "stretchGetOutputCapacity": (C.c_int, [ptr, C.c_int, C.c_double]),
@@ -232,7 +233,7 @@ def _bind(width):
 
     def _dev_ptr(t):
         """address of a torch CUDA tensor (or a raw int)."""
-        return t if isinstance(t, int) else (t.data_ptr() if t is not None else None)
+        return t if isinstance(t, int) else int(t) if isinstance(t, np.integer) else (t.data_ptr() if t is not None else None)
 
 
     class Resampler:
@@ -1007,6 +1008,238 @@ def _bind(width):
                                                             [lengths[i] for i in idx], from_start=True)
             return whole
 
+    def _plane_ptrs(t):
+        """addresses of the planes of t [..., T] (frames consecutive) as a numpy array of t's leading shape"""
+        at = np.zeros(tuple(t.shape[:-1]), np.int64)
+        for d in range(t.dim() - 1):
+            at = at + (np.arange(t.shape[d], dtype=np.int64) * t.stride(d)).reshape([-1 if k == d else 1 for k in range(t.dim() - 1)])
+        return t.data_ptr() + at * t.element_size()
+
+    def _clip_ptrs(t):
+        """addresses of the clips of t [..., C, T] and the pitch the planar entries take for them (0: one channel)"""
+        return _plane_ptrs(t)[..., 0], (t.stride(-2) if t.shape[-2] > 1 else 0)
+
+    class _BiquadBankSet:
+        """the banks one set of ClipBiquad coefficient values needs, made on first use: the whole cascade; for the coefficient
+        gradient its prefixes 1..s, its suffixes s+1..S and each section's all-pole part.  co: numpy [C, S, 9], the build's dtype."""
+
+        def __init__(self, co):
+            self.co, (self.channels, self.nsections, _) = co, co.shape
+            self.banks = {}
+
+        def bank(self, kind, s=0):
+            """'full'; ('prefix', s): sections 1..s; ('suffix', s): sections s+1..S; ('pole', s): 1 / (1 + b1 z^-1 + ...) of section s"""
+            Cn, S = self.channels, self.nsections
+            if (kind == "prefix" and s == S) or (kind == "suffix" and s == 0):
+                kind, s = "full", 0
+            if (kind, s) not in self.banks:
+                which = {"full": range(S), "prefix": range(s), "suffix": range(s, S), "pole": [s - 1]}[kind]
+                L = lib()
+                secs = (Biquad * (Cn * len(which)))()
+                for c in range(Cn):
+                    for j, k in enumerate(which):
+                        v = [float(q) for q in self.co[c, k]]
+                        if kind == "pole":
+                            v[:5] = [1.0, 0.0, 0.0, 0.0, 0.0]
+                        L.biquad_init(C.byref(secs[c * len(which) + j]), C.byref(BiquadCoefficients(*v)), 1.0)
+                self.banks[(kind, s)] = BiquadBank(secs, Cn, len(which))
+            return self.banks[(kind, s)]
+
+        def close(self):
+            for b in self.banks.values():
+                b.close()
+            self.banks = {}
+
+    def _clip_biquad_grad():
+        """the torch.autograd.Function of ClipBiquad (made on first use: torch is imported late)"""
+        if "biquad_grad" not in _state:
+            import torch
+
+            class ClipBiquadGrad(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, x, coefficients, y, kept, clip, banks, lengths):
+                    ctx.clip, ctx.banks, ctx.lengths, ctx.generation, ctx.co = clip, banks, lengths, clip._generation, coefficients
+                    ctx.save_for_backward(x, y, kept)
+                    return y.view_as(y)
+
+                @staticmethod
+                @torch.autograd.function.once_differentiable
+                def backward(ctx, gy):
+                    clip, banks, lengths = ctx.clip, ctx.banks, ctx.lengths
+                    if clip._generation != ctx.generation:
+                        raise RuntimeError("the ClipBiquad was closed before backward")
+                    x, y, kept = ctx.saved_tensors
+                    need_x, need_co = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+                    if not _rows_apart(gy):
+                        gy = gy.contiguous()
+                    B, Cn, T = gy.shape
+                    S = banks.nsections
+                    stream = torch.cuda.current_stream(gy.device).cuda_stream
+                    gx = None
+                    if need_x:
+                        # frames at and past lengths[i] went through as they were: so does their gradient
+                        gx = gy.clone(memory_format=torch.contiguous_format) if any(v < T for v in lengths) else \
+                            torch.empty(gy.shape, dtype=gy.dtype, device=gy.device)
+                    gy_ptrs, gy_pitch = _clip_ptrs(gy)
+                    clip.backward_launches = [0, 0, 0]
+                    if not need_co:
+                        banks.bank("full").set_stream(stream)
+                        clip.backward_launches[0] = _clip_filter_rows(banks.bank("full"), gy, gx, lengths, True) if B else 0
+                        return gx, None, None, None, None, None, None
+                    # g_s, s = 0 .. S-1: grad_y through the reversed sections s+1 .. S (g_0 is grad_x; g_S is grad_y itself)
+                    g = torch.empty((max(S - 1, 0), B, Cn, T), dtype=gy.dtype, device=gy.device)
+                    outs = ([(0, gx)] if need_x else []) + [(s, g[s - 1]) for s in range(1, S)]
+                    if outs and B:
+                        call = [banks.bank("suffix", s) for s, _ in outs for _ in range(B)]
+                        call[0].set_stream(stream)
+                        optr = np.concatenate([_clip_ptrs(o)[0] for _, o in outs])
+                        pitch = [gy_pitch] * len(call)
+                        clip.backward_launches[0] = biquad_filter_clips_planar_device(
+                            call, np.tile(gy_ptrs, len(outs)), pitch, optr, [T if Cn > 1 else 0] * len(call), lengths * len(outs), reversed=True)
+                    # u_s, s = 1 .. S: g_s through the all-pole part of section s, reversed
+                    u = torch.empty((S, B, Cn, T), dtype=gy.dtype, device=gy.device)
+                    sums = torch.zeros((B, Cn, S, 9), dtype=torch.float64, device=gy.device)
+                    if B:
+                        call = [banks.bank("pole", s) for s in range(1, S + 1) for _ in range(B)]
+                        call[0].set_stream(stream)
+                        iptr = np.concatenate([_clip_ptrs(g[s - 1])[0] for s in range(1, S)] + [gy_ptrs])
+                        ipitch = [T if Cn > 1 else 0] * ((S - 1) * B) + [gy_pitch] * B
+                        clip.backward_launches[1] = biquad_filter_clips_planar_device(
+                            call, iptr, ipitch, _clip_ptrs(u)[0].reshape(-1), [T if Cn > 1 else 0] * (S * B), lengths * S, reversed=True)
+                        # the lagged sums: per clip, channel and section (u_s, y_{s-1}, lags 0..4) and (u_s, y_s, lags 1..4)
+                        up = _plane_ptrs(u).transpose(1, 2, 0)                                     # [B, C, S]
+                        ys = [_plane_ptrs(x)] + [_plane_ptrs(kept[s]) for s in range(S - 1)] + [_plane_ptrs(y)]
+                        before, after = np.stack(ys[:-1], axis=-1), np.stack(ys[1:], axis=-1)      # y_{s-1}, y_s: [B, C, S]
+                        sp = _plane_ptrs(sums)
+                        frames = np.broadcast_to(np.asarray(lengths, np.int64).reshape(B, 1, 1), (B, Cn, S))
+                        rows = lambda a, b: np.concatenate([a.reshape(-1), b.reshape(-1)])
+                        count = B * Cn * S
+                        clip.backward_launches[2] = lag_products_batch_device(
+                            rows(up, up), rows(before, after), rows(frames, frames), [0] * count + [1] * count, [5] * count + [4] * count,
+                            rows(sp, sp + 5 * 8), stream=stream)
+                    sums = sums.sum(0)
+                    if ctx.co.dim() == 2:
+                        sums = sums.sum(0)
+                    sums[..., 5:] = -sums[..., 5:]
+                    return gx, sums.to(dtype=ctx.co.dtype).to(ctx.co.device), None, None, None, None, None
+
+            _state["biquad_grad"] = ClipBiquadGrad
+        return _state["biquad_grad"]
+
+    class ClipBiquad:
+        """Whole clips, channels-first, through a cascade of one to four sections whose COEFFICIENTS can be learnt: x [B, C, T] (or
+        [C, T]) on the GPU in, y out — always a NEW tensor, x is never written.  coefficients: a tensor [S, 9] (one cascade for every
+        channel) or [channels, S, 9], 1 <= S <= 4, columns a0..a4, b1..b4 of (a0 + a1 z^-1 + ... + a4 z^-4) / (1 + b1 z^-1 + ... +
+        b4 z^-4) (biquad.h), of the build's sample type — so the filter runs on the parameter's exact values — on the CPU or the GPU.
+        It is held by reference (the caller's nn.Parameter) and read at every call: the banks (biquad_init with gain 1.0) are cached
+        on its _version and data_ptr and rebuilt only when those change; a GPU tensor costs one small download per rebuild.
+        ClipBiquad.design(sections) gives the [S, 9] values ClipFilter builds for the same sections.
+
+        y[i, :, :lengths[i]] is, bit for bit, what biquad_filter_clips_planar_device makes of a fresh bank of those sections;
+        y[i, :, lengths[i]:] is x copied through.  A non-contiguous x is taken through .contiguous(); work runs on the current torch
+        stream; `launches`: the kernel launches the last forward call enqueued.
+
+        Differentiable in x and in the coefficients (once).  Nothing tracked, or only x: one filter call with B items; grad_x is the
+        same entry with time reversed, as in ClipFilter.  coefficients.requires_grad (grad mode on): the forward is ONE filter call
+        whose items are the prefixes 1..s of every clip's cascade (y_1 .. y_{S-1} are kept), and the backward is one reversed call
+        for g_s = grad_y through sections s+1..S (g_0 is grad_x), one reversed call through each section's all-pole part for u_s, and
+        ONE artamdLagProductsBatchDevice call of 2 B C S rows:
+            dL/da_k (section s) =  sum_{t >= k} u_s[t] y_{s-1}[t-k], k = 0..4;   dL/db_k (section s) = -sum_{t >= k} u_s[t] y_s[t-k], k = 1..4
+        summed in fp64 over clips (and channels, for [S, 9]), cast to the coefficients' dtype and moved to their device
+        (`backward_launches`: the three calls' launch counts).  All nine columns get a gradient, whatever order biquad_init derived.
+        Frames at and past lengths[i] add nothing to it; their grad_y passes through to grad_x.  The backward holds the banks of its
+        forward call (a rebuild in between does not change it) and raises after close().
+
+        Filters that do not forget within 1,024 frames take the entry's serial route, as everywhere: correct, but slow on long clips."""
+
+        def __init__(self, channels, coefficients):
+            self.channels, self.coefficients = int(channels), coefficients
+            self._check()
+            self._banks, self._key, self._generation = None, None, 0
+            self.launches, self.backward_launches = 0, [0, 0, 0]
+
+        def _check(self):
+            import torch
+            co = self.coefficients
+            if not isinstance(co, torch.Tensor) or co.dtype != getattr(torch, smp_torch):
+                raise ValueError(f"coefficients: a {smp_torch} tensor")
+            if co.dim() not in (2, 3) or co.shape[-1] != 9 or not 1 <= co.shape[-2] <= 4 or (co.dim() == 3 and co.shape[0] != self.channels):
+                raise ValueError(f"coefficients: [S, 9] or [{self.channels}, S, 9], one to four sections")
+
+        @staticmethod
+        def design(sections):
+            """[("lowpass" | "highpass", frequency), ...] -> tensor [S, 9] of the build's dtype (on the CPU; needs no GPU): the values
+            ClipFilter builds for the same sections"""
+            import torch
+            sections = list(sections)
+            if not 1 <= len(sections) <= 4 or any(kind not in ("lowpass", "highpass") for kind, _ in sections):
+                raise ValueError('sections: one to four of ("lowpass" | "highpass", frequency)')
+            L = lib()
+            rows = []
+            for kind, freq in sections:
+                co = BiquadCoefficients()
+                (L.biquad_lowpass if kind == "lowpass" else L.biquad_highpass)(C.byref(co), float(freq))
+                rows.append([getattr(co, n) for n, _ in BiquadCoefficients._fields_])
+            return torch.tensor(rows, dtype=getattr(torch, smp_torch))
+
+        def close(self):
+            if self._banks is not None:
+                self._banks.close()
+            self._banks, self._key = None, None
+            self._generation += 1
+
+        def _bank_set(self):
+            co = self.coefficients
+            key = (co._version, co.data_ptr())
+            if self._banks is None or key != self._key:
+                self._check()
+                host = co.detach().cpu().numpy().astype(smp_np, copy=True)             # (a GPU tensor: the one small download)
+                if host.ndim == 2:
+                    host = np.broadcast_to(host, (self.channels,) + host.shape)
+                # (the set before is not closed here: a graph made from it may still run its backward; it goes with its last holder)
+                self._banks, self._key = _BiquadBankSet(np.ascontiguousarray(host)), key
+            return self._banks
+
+        def __call__(self, x, lengths=None):
+            import torch
+            whole = x
+            if x.dim() == 2:
+                x = x.unsqueeze(0)
+            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
+                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
+            B, Cn, T = x.shape
+            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
+                raise ValueError("lengths: one entry per clip, 0 .. T")
+            banks = self._bank_set()
+            S = banks.nsections
+            grad = torch.is_grad_enabled()
+            track_x, track_co = grad and x.requires_grad, grad and self.coefficients.requires_grad
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            src = x if _rows_apart(x) else x.contiguous()
+            with torch.no_grad():
+                y = src.clone(memory_format=torch.contiguous_format) if any(v < T for v in lengths) else \
+                    torch.empty(src.shape, dtype=src.dtype, device=src.device)
+                kept = None
+                self.launches = 0
+                if not track_co:
+                    banks.bank("full").set_stream(stream)
+                    if B:
+                        self.launches = _clip_filter_rows(banks.bank("full"), src, y, lengths, False)
+                else:
+                    # one call: the prefixes 1 .. s of every clip's cascade; y_1 .. y_{S-1} are kept for the coefficient gradient
+                    kept = torch.empty((S - 1, B, Cn, T), dtype=src.dtype, device=src.device)
+                    if B:
+                        call = [banks.bank("prefix", s) for s in range(1, S + 1) for _ in range(B)]
+                        call[0].set_stream(stream)
+                        iptr, ipitch = _clip_ptrs(src)
+                        optr = np.concatenate([_clip_ptrs(kept[s])[0] for s in range(S - 1)] + [_clip_ptrs(y)[0]])
+                        self.launches = biquad_filter_clips_planar_device(
+                            call, np.tile(iptr, S), [ipitch] * (S * B), optr, [T if Cn > 1 else 0] * (S * B), lengths * S, reversed=False)
+            if track_x or track_co:
+                y = _clip_biquad_grad().apply(src, self.coefficients, y, kept, self, banks, lengths)
+            return y[0] if whole.dim() == 2 else y
+
     class Stretcher:
         """Owner of a Stretch * (stretch.h): periods in frames, one or two channels, flags STRETCH_FAST_FLAG | STRETCH_DUAL_FLAG"""
 
@@ -1274,6 +1507,23 @@ def _bind(width):
             (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), (C.c_int * n)(*[int(v) for v in extras]), n, st)
         if rc < 0:
             raise RuntimeError("artamdExtrapolateBatchDevice failed")
+        return rc
+
+    def lag_products_batch_device(d_us, d_vs, frames, first_lags, num_lags, d_sums, stream=None):
+        """artamdLagProductsBatchDevice: row i sets d_sums[i][q] (doubles), q = 0 .. num_lags[i] - 1, to the fp64 sum over
+        t = k .. frames[i] - 1 of d_us[i][t] * d_vs[i][t - k], k = first_lags[i] + q (k < 8), all rows in two launches on `stream` (a
+        torch stream, a raw address or None: the null stream).  Rows are planes with stride 1; the lists may be numpy arrays of
+        addresses and counts.  Returns the launch count (raises if the call returned -1)."""
+        n = len(d_us)
+        st = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        ptrs = lambda v: np.ascontiguousarray(v if isinstance(v, np.ndarray) else [_dev_ptr(d) or 0 for d in v], dtype=np.uintp)
+        ints = lambda v: np.ascontiguousarray(v, dtype=np.intc)
+        keep = [ptrs(d_us), ptrs(d_vs), ints(frames), ints(first_lags), ints(num_lags), ptrs(d_sums)]
+        if any(len(a) != n for a in keep):
+            raise ValueError("lag_products_batch_device: one entry per row in every list")
+        rc = lib().artamdLagProductsBatchDevice(*[a.ctypes.data for a in keep[:5]], keep[5].ctypes.data, n, st)
+        if rc < 0:
+            raise RuntimeError("artamdLagProductsBatchDevice failed")
         return rc
 
     return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k != "width"}, width=width)

@@ -552,6 +552,21 @@ int arthip_ingest_batch (const ArtIngestItem *items, int n, long tasks, void *st
 /* an item's head for this output address: (address - head * sizeof (art_s)) % 16 == 0 when the address is sample-aligned — pcm_host.c */
 int artamd_ingest_head (const void *d_output);
 
+/* ---- lag_products.hip: lagged inner products of whole rows (artamdLagProductsBatchDevice) ----
+ * A task is a tile of ART_LAG_TILE consecutive frames of one row; a row's sums are its tiles' partials added in ascending order. */
+#define ART_LAG_MAX 8                    /* ARTAMD_LAG_PRODUCTS_MAX: lags 0 .. 7 */
+#define ART_LAG_TILE 4096
+typedef struct {
+    const art_s *u, *v;
+    double *sums;                        /* `lags` values */
+    long task0;                          /* first task of this row in the call's flattened task space */
+    int frames, first, lags, pad;        /* frames > 0; first >= 0, lags >= 1, first + lags <= ART_LAG_MAX */
+} ArtLagRow;
+/* the checked arguments of artamdLagProductsBatchDevice (`live` rows with numFrames > 0): builds and uploads the table (per-device
+ * scratch of the process, with the partials) and enqueues the two launches on `stream`; the launch count, or -1 */
+int arthip_lag_products (const art_s *const *d_u, const art_s *const *d_v, const int *frames, const int *first, const int *lags,
+                         double *const *d_sums, int n, int live, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

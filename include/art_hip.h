@@ -551,6 +551,31 @@ int floatIntegersBatchLEDevice (const unsigned char *const *d_inputs, const doub
 int artamdExtrapolateBatchDevice (const artsample_t *const *d_known, const int *counts, const int *strides, const int *backward,
                                   artsample_t *const *d_out, const int *extras, int n, void *hipStream);
 
+/* ---- lagged inner products of whole rows, device pointers ---- */
+/* one more than the largest lag a row may ask for (lags 0 .. 7: a section's a0..a4 and b1..b4 need 0..4 and 1..4) */
+#define ARTAMD_LAG_PRODUCTS_MAX 8
+/* Lagged inner products of n rows in shared launches: what the coefficient gradients of a biquad cascade are made of (ClipBiquad).
+ * Row i, for k = firstLags [i] .. firstLags [i] + numLags [i] - 1:
+ *     d_sums [i][k - firstLags [i]] is SET to sum_{t = k}^{numFrames [i] - 1} (double) d_u [i][t] * (double) d_v [i][t - k]
+ * Rows are planes with stride 1 (a plane is an item, as in floatIntegersBatchLEDevice), aligned to their sample size; d_u [i] and
+ * d_v [i] are only read and may be one row.  A lag k >= numFrames [i] is set to 0; a row with numFrames [i] <= 0 is skipped and its
+ * sums are not touched.  Products and sums are fp64 in both builds (the 4-byte build's products are exact) and the output is
+ * double in both; no floating-point atomics.
+ * Deterministic: a row is cut into tiles of one fixed length, each tile's partial is one fixed tree over the row's frames, and a
+ * row's sum is its tiles' partials added in ascending tile order — so the bits of a row's sums do not depend on the other rows of
+ * the call, the row's place in the list, the base alignment of d_u [i] and d_v [i] (16-byte loads where the address allows, single
+ * accesses at the head and the tail) or the stream.
+ * Work is spread over (row, tile) tasks, so a few long rows fill the chip as many short ones do: one launch for the tiles'
+ * partials and one small launch that finishes every row.  The table and the partials live in per-device scratch of the process,
+ * grown under a lock (calls of different threads take turns to enqueue; a call on another stream than the last one's waits for it
+ * on the device); nothing is allocated once warm.  Asynchronous on hipStream (NULL: the null stream), on the current device, like
+ * floatIntegersBatchLEDevice; the argument arrays may be reused as soon as the call returns.
+ * Returns the number of kernel launches enqueued (2); 0 when n <= 0 or every row is skipped; -1 with nothing enqueued and nothing
+ * counted if a live row has a NULL pointer, firstLags [i] < 0, numLags [i] < 1 or firstLags [i] + numLags [i] >
+ * ARTAMD_LAG_PRODUCTS_MAX (or an argument array is NULL); -1 if memory ran out or a launch failed (counted in artamdErrorCount). */
+int artamdLagProductsBatchDevice (const artsample_t *const *d_u, const artsample_t *const *d_v, const int *numFrames,
+                                  const int *firstLags, const int *numLags, double *const *d_sums, int n, void *hipStream);
+
 /* ---- time stretcher, device pointers (stretch.h) ---- */
 void stretchHipSetStream (Stretch *cxt, void *hipStream);
 /* as stretchProcess / stretchFlush with `samples` / `output` in device memory; both wait for the call to finish (the frame

@@ -15,6 +15,7 @@ from .api import (  # noqa: F401
     biquad_batch_device, ingest_batch_device, extrapolate_batch_device, process_and_flush_batch_device,
     process_batch_device, process_batch_planar_device, process_and_flush_batch_planar_device, ClipResampler,
     process_schedule_batch_device, process_schedule_batch_planar_device,
+    process_schedule_clips_planar_device, adjoint_schedule_clips_planar_device, ClipWarper,
     decimate_batch_planar_device, decimate_clips_planar_device, process_and_flush_clips_planar_device, adjoint_clips_planar_device, ClipDecimator, biquad_batch_planar_device, biquad_clips_planar_device, ClipFilter,
     biquad_filter_clips_planar_device, lag_products_batch_device, ClipBiquad,
     STRETCH_FAST_FLAG, STRETCH_DUAL_FLAG, Stretcher, stretch_clips_batch_planar_device, ClipStretcher,

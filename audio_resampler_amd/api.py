@@ -197,6 +197,8 @@ def _bind(width):
         "resampleProcessSchedulePlanarDevice": (C.c_int, [RP, C.c_int, ptr, C.c_long, ptr, ptr, C.c_long, ptr, ptr, C.c_int, ptr]),
         "resampleProcessScheduleBatchInterleavedDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleProcessScheduleBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleProcessScheduleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr, ptr]),
+        "resampleAdjointScheduleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
     }
 
     _state = {"lib": None}
@@ -622,7 +624,8 @@ def _bind(width):
             _state["clip_grad"] = ClipResampleGrad
         return _state["clip_grad"]
 
-    def _schedule_batch(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last):
+    def _schedule_batch(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last, clips=None):
+        """(clips: None, or the clips entry's from_start)"""
         n = len(resamplers)
         if not (len(d_ins) == len(n_ins) == len(d_outs) == len(caps) == len(ratios) == n):
             raise ValueError("one entry per stream in every list")
@@ -642,7 +645,11 @@ def _bind(width):
                 (C.c_void_p * m)(*[None if d is None else _dev_ptr(d) for d in d_ins])]
         outs = (C.c_void_p * m)(*[_dev_ptr(d) for d in d_outs])
         tail = [table(rates), None if flush_last is None else (C.c_int * m)(*[1 if f else 0 for f in flush_last]), table(res), made]
-        if in_pitches is None and out_pitches is None:
+        if clips is not None:
+            name = "resampleProcessScheduleClipsPlanarDevice"
+            rc = lib().resampleProcessScheduleClipsPlanarDevice(*head, pitches(in_pitches), table(frames), outs, pitches(out_pitches), table(room),
+                                                                *tail[:2], 1 if clips else 0, *tail[2:])
+        elif in_pitches is None and out_pitches is None:
             name = "resampleProcessScheduleBatchInterleavedDevice"
             rc = lib().resampleProcessScheduleBatchInterleavedDevice(*head, table(frames), outs, table(room), *tail)
         else:
@@ -665,6 +672,164 @@ def _bind(width):
         if in_pitches is None and out_pitches is None:
             in_pitches = [0] * len(resamplers)
         return _schedule_batch(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last)
+
+    def process_schedule_clips_planar_device(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last=None, from_start=False):
+        """resampleProcessScheduleClipsPlanarDevice: process_schedule_batch_planar_device, with from_start every context first as after its
+        reset() — the contexts on the first one's stream put back by one zeroing launch for all of them (it counts as one launch).
+        Returns (launches, [(blocks_made_i, [(input_used, output_generated), ...]), ...]); raises if a launch failed."""
+        return _schedule_batch(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last, clips=bool(from_start))
+
+    def adjoint_schedule_clips_planar_device(resamplers, d_gouts, gout_pitches, n_outs, d_gins, gin_pitches, n_ins, ratios):
+        """resampleAdjointScheduleClipsPlanarDevice: the gradient of whole clips made block by block.  n_ins[i] and ratios[i] are clip i's
+        blocks (frames and ratio of each); frames 0 .. sum(n_ins[i])-1 of every channel of d_gins[i] are set to the transpose of the
+        schedule clips entry's map (a fresh context of resamplers[i]'s parameters, the blocks in turn, then the flush) applied to the first
+        n_outs[i] frames of d_gouts[i]; pitches as in process_batch_planar_device.  The contexts are only read, and one may be listed any
+        number of times.  Returns the launch count (raises if the call returned -1)."""
+        n = len(resamplers)
+        if not (len(d_gouts) == len(n_outs) == len(d_gins) == len(n_ins) == len(ratios) == n):
+            raise ValueError("one entry per clip in every list")
+        if any(len(n_ins[i]) != len(ratios[i]) for i in range(n)):
+            raise ValueError("n_ins[i] and ratios[i] must have one entry per block")
+        m = max(n, 1)
+        counts = [len(v) for v in n_ins]
+        frames = [(C.c_int * max(len(v), 1))(*[int(q) for q in v]) for v in n_ins]
+        rates = [(C.c_double * max(len(v), 1))(*[float(q) for q in v]) for v in ratios]
+        table = lambda arrays: (C.c_void_p * m)(*[C.cast(a, C.c_void_p) for a in arrays])
+        pitches = lambda v: None if v is None else (C.c_long * m)(*[int(q) for q in v])
+        rc = lib().resampleAdjointScheduleClipsPlanarDevice(
+            (C.c_void_p * m)(*[C.cast(r.p, C.c_void_p) for r in resamplers]), n, (C.c_int * m)(*counts),
+            (C.c_void_p * m)(*[_dev_ptr(d) for d in d_gouts]), pitches(gout_pitches), (C.c_int * m)(*[int(v) for v in n_outs]),
+            (C.c_void_p * m)(*[_dev_ptr(d) for d in d_gins]), pitches(gin_pitches), table(frames), table(rates))
+        if rc < 0:
+            raise RuntimeError("resampleAdjointScheduleClipsPlanarDevice failed")
+        return rc
+
+    def _clip_warp_grad():
+        """the torch.autograd.Function that attaches a ClipWarper's output to the graph (made on first use: torch is imported late)"""
+        if "warp_grad" not in _state:
+            import torch
+
+            class ClipWarpGrad(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, x, y, clip, blocks, rates, made):
+                    ctx.clip, ctx.blocks, ctx.rates, ctx.made, ctx.x_shape = clip, blocks, rates, made, x.shape
+                    return y.view_as(y)
+
+                @staticmethod
+                @torch.autograd.function.once_differentiable
+                def backward(ctx, gy):
+                    clip = ctx.clip
+                    B, Cn, T = ctx.x_shape
+                    if not B:                                     # (no clip: no context was ever needed)
+                        return torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device), None, None, None, None, None
+                    if not clip.pool:
+                        raise RuntimeError("the ClipWarper was closed before backward")
+                    if (gy.shape[2] and gy.stride(2) != 1) or (Cn > 1 and gy.stride(1) < gy.shape[2]) or (B > 1 and gy.stride(0) < 1):
+                        gy = gy.contiguous()                      # (frames of a channel consecutive, planes and clips apart)
+                    gx = torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device)     # (zero at and past lengths[i])
+                    clip.pool[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
+                    size = gy.element_size()
+                    gy_pitch, gx_pitch = (gy.stride(1), gx.stride(1)) if Cn > 1 else (0, 0)
+                    adjoint_schedule_clips_planar_device(
+                        [clip.pool[0]] * B, [gy.data_ptr() + i * gy.stride(0) * size for i in range(B)], [gy_pitch] * B, ctx.made,
+                        [gx.data_ptr() + i * gx.stride(0) * size for i in range(B)], [gx_pitch] * B, ctx.blocks, ctx.rates)
+                    return gx, None, None, None, None, None
+
+            _state["warp_grad"] = ClipWarpGrad
+        return _state["warp_grad"]
+
+    class ClipWarper:
+        """Whole clips, channels-first, at a rate that changes inside the clip: x [B, C, T] (or [C, T]) on the GPU and a ratio per block of
+        `block` frames in, (y [B, C, Tout_max], out_lengths) out — one resampleProcessScheduleClipsPlanarDevice call per pool on the
+        tensor's own rows.  Clip i's block k is frames [k * block, min((k + 1) * block, lengths[i])) at ratios[i][k] (output rate over input
+        rate, as resampleProcess takes it); clip i is what a fresh context makes of those blocks in turn and then of the flush (an empty
+        clip: the flush's outputs alone); y[i, :, out_lengths[i]:] is zero.  `ratios` holds host values: a scalar, [B] or [B, K] with
+        K >= ceil(max(lengths) / block) (a list, a numpy array or a CPU tensor; a CUDA tensor is downloaded once).
+        Differentiable once with respect to the samples: where x requires grad (and grad mode is on) y is attached to the graph, and
+        backward is ONE resampleAdjointScheduleClipsPlanarDevice call on the rows of grad_y, zero at and past lengths[i].  The ratio curve
+        gets no gradient: a `ratios` tensor that requires grad is refused.  Without gradients the call is the forward alone."""
+
+        def __init__(self, channels, taps=380, filters=380, flags=BLACKMAN_HARRIS | SUBSAMPLE_INTERPOLATE | INCLUDE_LOWPASS, lowpass_ratio=0.0,
+                     block=1024, max_batch=1024):
+            if flags & EXTRAPOLATE_ENDPOINTS:
+                raise ValueError("ClipWarper: EXTRAPOLATE_ENDPOINTS is not linear in the samples (no adjoint)")
+            if int(block) < 1:
+                raise ValueError("ClipWarper: block must be at least one frame")
+            self.channels, self.taps, self.block, self.max_batch = channels, taps, int(block), max(1, int(max_batch))
+            self._init = (channels, taps, filters, float(lowpass_ratio), flags)
+            self.pool = []
+
+        def close(self):
+            for r in self.pool:
+                r.close()
+            self.pool = []
+
+        def blocks(self, lengths, ratios):
+            """([frames of every block of clip i], [their ratios]) — the host part of a call, with its checks"""
+            B = len(lengths)
+            if getattr(ratios, "requires_grad", False):
+                raise ValueError("ClipWarper: ratios that require grad: the ratio curve has no gradient (it would silently be zero)")
+            if hasattr(ratios, "detach"):
+                ratios = ratios.detach().cpu().numpy()
+            r = np.asarray(ratios, dtype=np.float64)
+            need = [max(1, -(-n // self.block)) for n in lengths]
+            if r.ndim == 0:
+                r = np.broadcast_to(r, (B, max(need, default=1)))
+            elif r.ndim == 1 and r.shape[0] == B:
+                r = np.broadcast_to(r[:, None], (B, max(need, default=1)))
+            elif r.ndim != 2 or r.shape[0] != B or r.shape[1] < max(need, default=1):
+                raise ValueError("ratios: a scalar, [B] or [B, K] with K >= ceil(max(lengths) / block)")
+            frames = [[min(self.block, n - k * self.block) for k in range(need[i])] if n else [0] for i, n in enumerate(lengths)]
+            rates = [[float(v) for v in r[i, :need[i]]] for i in range(B)]
+            if any(not (v > 0.0 and v < float("inf")) for row in rates for v in row):
+                raise ValueError("ratios must be finite and > 0")
+            return frames, rates
+
+        def __call__(self, x, ratios, lengths=None):
+            import torch
+            if x.dim() == 2:
+                x = x.unsqueeze(0)
+            if x.dim() != 3 or x.shape[1] != self.channels or x.dtype != getattr(torch, smp_torch):
+                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
+            B, Cn, T = x.shape
+            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
+                raise ValueError("lengths: one entry per clip, 0 .. T")
+            frames, rates = self.blocks(lengths, ratios)
+            if not x.is_cuda:
+                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
+            if x.shape[2] and x.stride(2) != 1:
+                x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
+            while len(self.pool) < min(B, self.max_batch):
+                self.pool.append(Resampler(*self._init))
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            for r in self.pool[:min(B, self.max_batch)]:
+                r.set_stream(stream)
+            # room so that no block is cut: a block of n frames moves the position by at most n frames past where the block before left it
+            # (not behind the input), the flush by half a window more
+            caps = [[int((n + 2) * q) + 4 for n, q in zip(f, r)] for f, r in zip(frames, rates)]
+            for c, f, r in zip(caps, frames, rates):
+                c[-1] = int((f[-1] + self.taps // 2 + 2) * r[-1]) + 4
+            y = torch.zeros(B, Cn, max((sum(c) for c in caps), default=0), dtype=x.dtype, device=x.device)
+            size = x.element_size()
+            xp, yp = x.data_ptr(), y.data_ptr()
+            in_pitch, out_pitch = (x.stride(1), y.stride(1)) if Cn > 1 else (0, 0)      # (one channel: the same call in either layout)
+            made = []
+            for b0 in range(0, B, self.max_batch):
+                idx = range(b0, min(B, b0 + self.max_batch))
+                _, got = process_schedule_clips_planar_device(
+                    self.pool[:len(idx)], [xp + i * x.stride(0) * size for i in idx], [in_pitch] * len(idx), [frames[i] for i in idx],
+                    [yp + i * y.stride(0) * size for i in idx], [out_pitch] * len(idx), [caps[i] for i in idx], [rates[i] for i in idx],
+                    flush_last=[True] * len(idx), from_start=True)
+                for i, (blocks_made, res) in zip(idx, got):
+                    if blocks_made != len(frames[i]) or any(used != n for (used, _), n in zip(res, frames[i])):
+                        raise RuntimeError(f"ClipWarper: clip {i} was cut short ({blocks_made} of {len(frames[i])} blocks made)")
+                    made.append(sum(g for _, g in res))
+            out_lengths = torch.tensor(made, dtype=torch.int64)
+            y = y[:, :, :max(made, default=0)]
+            if x.requires_grad and torch.is_grad_enabled():      # (the samples above are the detached call's; backward is the adjoint kernel)
+                y = _clip_warp_grad().apply(x, y, self, frames, rates, made)
+            return y, out_lengths
 
     class ClipResampler:
         """Whole clips, channels-first, from one fixed rate to another: x [B, C, T] (or [C, T]) on the GPU in, (y [B, C, Tout_max],

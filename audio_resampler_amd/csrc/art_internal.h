@@ -260,6 +260,34 @@ size_t arthip_fir_adjoint_bytes (int nitems, int nsegs);
  * by variant) and the nsegs segments go to d_table (device memory of arthip_fir_adjoint_bytes bytes, reused call after call: stream order protects
  * it) in one upload.  Returns the number of launches enqueued, or -1 (a launch failed; nothing enqueued where the upload could not be made). */
 int arthip_fir_adjoint (const ArtAdjItem *items, int n, const ArtamdSegment *segs, int nsegs, void *d_table, void *stream);
+/* ... of clips made block by block (resampleAdjointScheduleClipsPlanarDevice; fir_adjoint_blocks_kernel): any number of phases per clip, one planned
+ * call each — the blocks' process calls in turn, each at its own ratio, then the flush — in a phase table beside the items.  Phase k's linear
+ * space holds input frame j at H + j - start; it reads no frame at or past `end` and nothing below `floor`.  start and end do not decrease
+ * from one phase of a clip to the next. */
+typedef struct {
+    double ratio;                        /* the effective ratio of the phase's call (locate: a.ratio) */
+    unsigned int outputs;                /* output frames of the phase */
+    unsigned int first_output;           /* its first output among the clip's */
+    int seg_first, seg_count;            /* its segments in the call's segment list */
+    int start, end;                      /* input frames of the clip before the phase's call, and with it (the flush: in_frames both) */
+    int floor;                           /* max (0, the call's lin_floor) */
+    int pad;
+} ArtAdjPhase;
+typedef struct {
+    const art_s *bank;                   /* device, (F+1) x T */
+    const art_s *gy;                     /* gradient of the outputs: gy_frames frames, the rest of the clip's outputs count as zero */
+    art_s *gx;                           /* gradient of the inputs: in_frames frames are SET */
+    long gy_pitch, gx_pitch;             /* samples between planes; 0: that side interleaved */
+    unsigned int gy_frames;
+    unsigned int tile0;                  /* first tile of the item in its launch (filled by arthip_fir_adjoint_blocks) */
+    int phase_first, phase_count;        /* the clip's phases in the call's phase table (>= 2; the last is the flush) */
+    int in_frames, C, T, F;              /* in_frames > 0 */
+    int interpolate, lowpass;
+} ArtAdjBlocksItem;
+size_t arthip_fir_adjoint_blocks_bytes (int nitems, int nphases, int nsegs);
+/* as arthip_fir_adjoint: one launch per kernel variant present; items, phases and segments go to d_table in one upload */
+int arthip_fir_adjoint_blocks (const ArtAdjBlocksItem *items, int n, const ArtAdjPhase *phases, int nphases, const ArtamdSegment *segs, int nsegs,
+                               void *d_table, void *stream);
 /* the upkeep every launch of a rational-ratio stream does for the rows kept across calls (arthip_fir calls it itself) */
 void arthip_fir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs);
 /* new_hist[H][C] = last H frames of (hist ++ in[0..appended)); in may be NULL => zeros appended */

@@ -2004,6 +2004,128 @@ out:
     return rc;
 }
 
+/* resampleAdjointScheduleClipsPlanarDevice (art_hip.h): the same for a clip made block by block — K process calls, each at its own ratio, then the
+ * flush, replayed one after the other on ONE fresh position: K + 1 phases where the entry above has two.  Every replay keeps its own ratio,
+ * segment slice, output count, first output among the clip's, the frames in front of it and its floor (ArtAdjPhase). */
+typedef struct { ArtAdjPhase *phases; int count, cap; } AdjointPhases;
+
+static ArtAdjPhase *adjoint_phase_new (AdjointPhases *list)
+{
+    if (list->count == list->cap) {
+        ArtAdjPhase *grown = realloc (list->phases, sizeof (ArtAdjPhase) * ((size_t) list->cap * 2 + 64));
+        if (!grown) return NULL;
+        list->phases = grown; list->cap = list->cap * 2 + 64;
+    }
+    ArtAdjPhase *ph = &list->phases [list->count++];
+    memset (ph, 0, sizeof (*ph));
+    return ph;
+}
+
+/* the clip a fresh context of cxt's parameters would make of the blocks; 0, -1 out of memory, -2 a clip the entry refuses (a ratio no call
+ * can be made at, more outputs than an int counts) */
+static int adjoint_plan_blocks (const Resample *cxt, int numBlocks, const int *frames, const double *ratios, ArtAdjBlocksItem *it,
+                                unsigned long *outputs, AdjointPhases *phases, AdjointSegs *list)
+{
+    ArtamdPosition pos;
+    ResampleResult res;
+    int lin_floor, before = 0;
+    unsigned long made = 0;
+    const int fixed = (cxt->flags & RESAMPLE_FIXED_RATIO) != 0;
+    double ratio = cxt->fixedRatio;
+
+    /* (the position resampleReset leaves) */
+    pos.numTaps = cxt->numTaps; pos.numFilters = cxt->numFilters; pos.flags = cxt->flags & ~(RESAMPLER_FLUSHED | EXTRAPOLATE_PREFILL);
+    pos.inputIndex = cxt->numTaps; pos.floorActive = 0; pos.outputOffset = cxt->numTaps / 2; pos.fixedRatio = cxt->fixedRatio;
+
+    memset (it, 0, sizeof (*it));
+    it->phase_first = phases->count;
+    for (int k = 0; k <= numBlocks; ++k) {                 /* (k == numBlocks: the flush's call of silence, at the last block's ratio) */
+        const int flush = k == numBlocks, nIn = flush ? -1 : frames [k];
+        ArtAdjPhase *ph = adjoint_phase_new (phases);
+        if (!ph) return -1;
+        if (!flush && !fixed) ratio = ratios [k];
+        if (made > (unsigned long) INT_MAX) return -2;
+        ph->seg_first = list->count;
+        if ((ph->seg_count = adjoint_plan_call (&pos, nIn, flush ? INT_MAX - (int) made : INT_MAX, ratio, &res, &lin_floor, list)) < 0) return -1;
+        if (!flush && (int) res.input_used != nIn) return -2;          /* (with that much room: a ratio that is not > 0) */
+        ph->ratio = ratio;
+        ph->outputs = res.output_generated; ph->first_output = (unsigned int) made;
+        ph->start = before; ph->end = flush ? before : before + nIn;
+        ph->floor = lin_floor > 0 ? lin_floor : 0;
+        made += res.output_generated;
+        if (!flush) before += nIn;
+    }
+    if (made > (unsigned long) INT_MAX) return -2;
+    it->phase_count = numBlocks + 1;
+    *outputs = made;
+
+    it->bank = cxt->hip->d_bank;
+    it->in_frames = before; it->C = cxt->numChannels; it->T = cxt->numTaps; it->F = cxt->numFilters;
+    it->interpolate = (cxt->flags & SUBSAMPLE_INTERPOLATE) != 0;
+    it->lowpass = (cxt->flags & INCLUDE_LOWPASS) != 0;
+    return 0;
+}
+
+int resampleAdjointScheduleClipsPlanarDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
+        artsample_t *const *d_gradInputs, const long *gradInputPitches,
+        const int *const *numInputFrames, const double *const *ratios)
+{
+    if (n <= 0) return 0;
+    if (!cxts || !numBlocks || !d_gradOutputs || !numOutputFrames || !d_gradInputs || !numInputFrames || !ratios) return -1;
+    for (int i = 0; i < n; ++i) if (!cxts [i]) return -1;
+
+    struct artamd_resampler *lead = cxts [0]->hip;
+    for (int i = 0; i < n; ++i) {
+        const struct artamd_resampler *hip = cxts [i]->hip;
+        if ((cxts [i]->flags & EXTRAPOLATE_ENDPOINTS) || hip->nshards || hip->device != lead->device || hip->stream != lead->stream) return -1;
+        if (numBlocks [i] <= 0) continue;
+        if (!numInputFrames [i] || numOutputFrames [i] < 0) return -1;
+        if (!ratios [i] && !(cxts [i]->flags & RESAMPLE_FIXED_RATIO)) return -1;
+        long frames = 0;
+        for (int k = 0; k < numBlocks [i]; ++k) {
+            if (numInputFrames [i] [k] < 0) return -1;
+            if ((frames += numInputFrames [i] [k]) > INT_MAX) return -1;
+        }
+        if (frames > 0 && (!d_gradOutputs [i] || !d_gradInputs [i])) return -1;
+    }
+
+    /* every item with blocks is planned (numOutputFrames [i] <= M_i is asked of an empty clip too); the empty ones are no items of the launches */
+    ArtAdjBlocksItem *items = malloc (sizeof (ArtAdjBlocksItem) * (size_t) n);
+    AdjointSegs list = { NULL, 0, 0 };
+    AdjointPhases phases = { NULL, 0, 0 };
+    int live = 0, rc = -1, refused = 0;
+    if (!items) goto out;
+    for (int i = 0; i < n; ++i) {
+        if (numBlocks [i] <= 0) continue;
+        ArtAdjBlocksItem *it = &items [live];
+        const int kept = list.count, kept_phases = phases.count;
+        unsigned long outputs = 0;
+        const int planned = adjoint_plan_blocks (cxts [i], numBlocks [i], numInputFrames [i], ratios [i], it, &outputs, &phases, &list);
+        if (planned) { refused = planned == -2; goto out; }
+        if ((unsigned long) numOutputFrames [i] > outputs) { refused = 1; goto out; }
+        if (!it->in_frames) { list.count = kept; phases.count = kept_phases; continue; }
+        it->gy = d_gradOutputs [i]; it->gy_pitch = gradOutputPitches ? gradOutputPitches [i] : 0; it->gy_frames = (unsigned int) numOutputFrames [i];
+        it->gx = d_gradInputs [i]; it->gx_pitch = gradInputPitches ? gradInputPitches [i] : 0;
+        ++live;
+    }
+    if (!live) { rc = 0; goto out; }
+
+    {
+        ENTER_DEVICE (lead);
+        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_adjoint_blocks_bytes (live, phases.count, list.count));
+        rc = lead->d_batch ? arthip_fir_adjoint_blocks (items, live, phases.phases, phases.count, list.segs, list.count, lead->d_batch, lead->stream) : -1;
+        if (rc < 0) fprintf (stderr, "artamd: resample schedule adjoint: launch failed: %s\n", arthip_last_error ());
+        LEAVE_DEVICE (lead);
+    }
+out:
+    if (rc < 0 && !refused) artamd_note_failure ("resampler: a launch of the schedule clips adjoint failed");
+    free (items);
+    free (phases.phases);
+    free (list.segs);
+    return rc;
+}
+
 /* ---- consecutive blocks of one stream, one launch --------------------------------------------------------------------
  * An ASRC loop makes a call per block with that block's ratio; each call is a launch with its own planning, staging and launch floor.
  * Where the caller knows the next blocks' ratios, resampleProcessScheduleInterleavedDevice plans them one after the other on the context
@@ -2244,15 +2366,22 @@ typedef struct {
     int cut;                             /* the run was cut at RUN_FRAMES_MAX: its next block is the next round's first */
 } SchedStream;
 
+/* what the batch entries refuse before anything is touched (n > 0): a NULL context, one listed twice, a negative frame count */
+static int schedule_refused (Resample *const *cxts, int n, const int *numBlocks, const int *const *numInputFrames)
+{
+    if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample schedule", "context")) return -1;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < numBlocks [i]; ++k) if (numInputFrames [i] [k] < 0) return -1;
+    return 0;
+}
+
 static int schedule_batch (Resample *const *cxts, int n, const int *numBlocks, const artsample_t *const *d_inputs, const long *in_pitches,
                            const int *const *numInputFrames, artsample_t *const *d_outputs, const long *out_pitches,
                            const int *const *numOutputFrames, const double *const *ratios, const int *flushLast,
                            ResampleResult *const *results, int *blocksMade)
 {
     if (n <= 0) return 0;
-    if (artamd_batch_distinct ((const void *const *) cxts, n, stamp_of, "resample schedule", "context")) return -1;
-    for (int i = 0; i < n; ++i)
-        for (int k = 0; k < numBlocks [i]; ++k) if (numInputFrames [i] [k] < 0) return -1;
+    if (schedule_refused (cxts, n, numBlocks, numInputFrames)) return -1;
 
     struct artamd_resampler *lead = cxts [0]->hip;
     SchedStream *st = calloc ((size_t) n, sizeof (SchedStream));
@@ -2374,6 +2503,34 @@ int resampleProcessScheduleBatchPlanarDevice (Resample *const *cxts, int n, cons
         const double *const *ratios, const int *flushLast, ResampleResult *const *results, int *blocksMade)
 {
     return schedule_batch (cxts, n, numBlocks, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, flushLast, results, blocksMade);
+}
+
+/* ... whole clips from a fresh start: the contexts put back as resampleProcessAndFlushClipsPlanarDevice puts them back (batch_from_start), after
+ * the schedule's own refusals and in front of its launches */
+int resampleProcessScheduleClipsPlanarDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *const *numInputFrames,
+        artsample_t *const *d_outputs, const long *outputPitches, const int *const *numOutputFrames,
+        const double *const *ratios, const int *flushLast, int fromStart, ResampleResult *const *results, int *blocksMade)
+{
+    int zeroing = 0;
+    if (fromStart && n > 0) {
+        if (schedule_refused (cxts, n, numBlocks, numInputFrames)) return -1;       /* (schedule_batch asks again: the same list) */
+        struct artamd_resampler *lead = cxts [0]->hip;
+        ENTER_DEVICE (lead);
+        const int failed = batch_from_start (cxts, n);
+        LEAVE_DEVICE (lead);
+        if (failed) {
+            artamd_note_failure ("resampler: the schedule clips entry could not put its contexts back (nothing enqueued)");
+            return -1;
+        }
+        /* (the zeroing launch: made if a context shares it — batch_from_start's own condition) */
+        for (int i = 0; i < n && !zeroing; ++i) {
+            const struct artamd_resampler *hip = cxts [i]->hip;
+            zeroing = !hip->nshards && hip->stream == lead->stream && hip->device == lead->device;
+        }
+    }
+    const int rc = schedule_batch (cxts, n, numBlocks, d_inputs, inputPitches, numInputFrames, d_outputs, outputPitches, numOutputFrames, ratios, flushLast, results, blocksMade);
+    return rc < 0 ? -1 : rc + zeroing;
 }
 
 /* what a call would consume / produce, without touching the context */

@@ -306,6 +306,51 @@ int resampleAdjointClipsPlanarDevice (Resample *const *cxts, int n,
         const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
         artsample_t *const *d_gradInputs, const long *gradInputPitches, const int *numInputFrames,
         const double *ratios);
+/* Whole clips at a rate that changes inside the clip, from a fresh start: exactly resampleReset (cxts [i]) for every i when fromStart != 0,
+ * then resampleProcessScheduleBatchPlanarDevice on the same arguments — the same results, samples, blocksMade and observable context state.
+ * With fromStart == 0 it is that entry.  The reset is resampleProcessAndFlushClipsPlanarDevice's: the host part resampleReset's own, the
+ * device part ONE grouped zeroing launch (zero_runs_group_kernel) over both history buffers of every context that shares cxts [0]'s stream
+ * and device and is not sharded, its table in the lead context's batch table — instead of two memsets and a host trip per clip; sharded
+ * contexts and contexts on another stream or device get their own resampleReset.
+ * Refusals as in the schedule batch entry (-1 with nothing enqueued and nothing counted: a NULL context, one listed twice, a negative
+ * numInputFrames [i][k]), before any context is reset.  If the zeroing launch cannot be made the call returns -1 with no context reset and
+ * nothing enqueued (counted once in artamdErrorCount).  After a failure of one of the schedule's own launches the contexts it did not reach
+ * stand as after resampleReset.  Returns the number of launches enqueued, the zeroing launch counting as one. */
+int resampleProcessScheduleClipsPlanarDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *const *numInputFrames,
+        artsample_t *const *d_outputs, const long *outputPitches, const int *const *numOutputFrames,
+        const double *const *ratios, const int *flushLast, int fromStart,
+        ResampleResult *const *results, int *blocksMade);
+/* The gradient of such clips with respect to their samples: the adjoint of what the entry above computes for item i, per channel, with
+ * fromStart = 1, flushLast [i] = 1 and room to spare on a context of cxts [i]'s taps, filters, low-pass and flags — numBlocks [i] process
+ * calls of numInputFrames [i][k] frames at ratios [i][k], then the flush (at the last block's ratio).  With N_i the sum of the blocks'
+ * frames and M_i the total output, frames 0 .. N_i - 1 of every plane of d_gradInputs [i] are SET to A_i^T gy_i, gy_i the first
+ * numOutputFrames [i] frames of d_gradOutputs [i] (output frames past that count as zero gradient); nothing else is written.  Pitches as
+ * in resampleAdjointClipsPlanarDevice.  For RESAMPLE_FIXED_RATIO contexts `ratios` is ignored (ratios [i] may be NULL), as the forward
+ * ignores it.  The ratios get no gradient.
+ * The clip is K + 1 phases, each linear in the samples: K + 1 artamdPlanCall replays on one fresh position (every process call with all
+ * the room an int counts, the last the flush's call of silence), each with its own ratio, segments, output count and floor.  Phase k sees
+ * input frame j at linear index H + j - s_k (s_k: the frames of the blocks before it; the flush: N_i) and reads nothing below
+ * max (0, its floor).  The weight of output n on input j is resampleAdjointClipsPlanarDevice's in all three cases (interpolating, nearest
+ * filter, pass-through), every output placed by locate () from its own block's segments and ratio, and gx [j] is the sum over the clip's
+ * outputs in ascending order — block by block, then the flush — one fused multiply-add per term in artsample_t (zero weights between a
+ * frame's own terms as there).  gx [j] is the same bit for bit whatever the batch, the item's place, the layout, the pitch or the tile;
+ * numBlocks [i] = 1 gives resampleAdjointClipsPlanarDevice's bits.  The kernel (fir_adjoint_blocks_kernel) gathers: a workgroup owns a
+ * tile of input frames, finds the contiguous range of phases that can touch it by bisection, takes them in groups of 32 (two lanes per
+ * phase bisect its output range) and walks each phase as the two-phase kernel does; no atomics.
+ * The contexts are only READ, and a context may be listed any number of times.  Asynchronous on the stream of cxts [0]; the items, phases
+ * and segments ride in the lead context's batch table in one upload: no allocation on the device once warm.
+ * Returns the number of launches enqueued, one per kernel variant present (channel-group width x interpolating or not); 0 for n <= 0 or
+ * when every item has N_i == 0 or numBlocks [i] <= 0 (such an item writes nothing).  -1 with nothing enqueued and nothing counted for a
+ * NULL context, a NULL buffer of an item with N_i > 0, a NULL block array of an item with numBlocks [i] > 0 (numInputFrames [i]; ratios [i]
+ * unless the context is RESAMPLE_FIXED_RATIO — stricter than N_i > 0: an empty clip's M_i depends on its ratio too), a negative count, a ratio that is not > 0, N_i or the clip's
+ * output count not fitting an int, numOutputFrames [i] > M_i, a context with EXTRAPOLATE_ENDPOINTS, a sharded context, a context on
+ * another device or stream than cxts [0].  -1 if a launch failed (counted once in artamdErrorCount): the gradient buffers are then
+ * unspecified.  Gradient inputs must not overlap gradient outputs (not checked). */
+int resampleAdjointScheduleClipsPlanarDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
+        artsample_t *const *d_gradInputs, const long *gradInputPitches,
+        const int *const *numInputFrames, const double *const *ratios);
 
 /* ---- host-only building blocks (no GPU needed; used by the CPU test-suite) ---- */
 /* (numFilters+1) x numTaps bank exactly as resampleInit builds it (reference resampler.c:149-168, 1090-1133) */

@@ -592,6 +592,23 @@ def _bind(width):
             raise RuntimeError("resampleAdjointClipsPlanarDevice failed")
         return rc
 
+    def _clip_backward(entry, clip, owner, x_shape, gy, made, n_ins, ratios):
+        """gx [B, C, T] of a clip class's backward: gy's rows handed as they lie to `entry` (one of the two adjoint wrappers above and below)
+        on the first context of `clip` (an `owner`), clip i's frames and ratio or ratios n_ins[i] and ratios[i]"""
+        import torch
+        B, Cn, T = x_shape
+        if not clip.pool:
+            raise RuntimeError(f"the {owner} was closed before backward")
+        if (gy.shape[2] and gy.stride(2) != 1) or (Cn > 1 and gy.stride(1) < gy.shape[2]) or (B > 1 and gy.stride(0) < 1):
+            gy = gy.contiguous()                                  # (frames of a channel consecutive, planes and clips apart)
+        gx = torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device)     # (zero at and past lengths[i])
+        clip.pool[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
+        size = gy.element_size()
+        gy_pitch, gx_pitch = (gy.stride(1), gx.stride(1)) if Cn > 1 else (0, 0)
+        entry([clip.pool[0]] * B, [gy.data_ptr() + i * gy.stride(0) * size for i in range(B)], [gy_pitch] * B, made,
+              [gx.data_ptr() + i * gx.stride(0) * size for i in range(B)], [gx_pitch] * B, n_ins, ratios)
+        return gx
+
     def _clip_resample_grad():
         """the torch.autograd.Function that attaches a ClipResampler's output to the graph (made on first use: torch is imported late)"""
         if "clip_grad" not in _state:
@@ -606,19 +623,8 @@ def _bind(width):
                 @staticmethod
                 @torch.autograd.function.once_differentiable
                 def backward(ctx, gy):
-                    clip, lengths, made = ctx.clip, ctx.lengths, ctx.made
-                    B, Cn, T = ctx.x_shape
-                    if not clip.pool:
-                        raise RuntimeError("the ClipResampler was closed before backward")
-                    if (gy.shape[2] and gy.stride(2) != 1) or (Cn > 1 and gy.stride(1) < gy.shape[2]) or (B > 1 and gy.stride(0) < 1):
-                        gy = gy.contiguous()                      # (frames of a channel consecutive, planes and clips apart)
-                    gx = torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device)     # (zero at and past lengths[i])
-                    clip.pool[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
-                    size = gy.element_size()
-                    gy_pitch, gx_pitch = (gy.stride(1), gx.stride(1)) if Cn > 1 else (0, 0)
-                    adjoint_clips_planar_device(
-                        [clip.pool[0]] * B, [gy.data_ptr() + i * gy.stride(0) * size for i in range(B)], [gy_pitch] * B, made,
-                        [gx.data_ptr() + i * gx.stride(0) * size for i in range(B)], [gx_pitch] * B, lengths, [clip.ratio] * B)
+                    gx = _clip_backward(adjoint_clips_planar_device, ctx.clip, "ClipResampler", ctx.x_shape, gy, ctx.made, ctx.lengths,
+                                        [ctx.clip.ratio] * ctx.x_shape[0])
                     return gx, None, None, None, None
 
             _state["clip_grad"] = ClipResampleGrad
@@ -718,21 +724,9 @@ def _bind(width):
                 @staticmethod
                 @torch.autograd.function.once_differentiable
                 def backward(ctx, gy):
-                    clip = ctx.clip
-                    B, Cn, T = ctx.x_shape
-                    if not B:                                     # (no clip: no context was ever needed)
-                        return torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device), None, None, None, None, None
-                    if not clip.pool:
-                        raise RuntimeError("the ClipWarper was closed before backward")
-                    if (gy.shape[2] and gy.stride(2) != 1) or (Cn > 1 and gy.stride(1) < gy.shape[2]) or (B > 1 and gy.stride(0) < 1):
-                        gy = gy.contiguous()                      # (frames of a channel consecutive, planes and clips apart)
-                    gx = torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device)     # (zero at and past lengths[i])
-                    clip.pool[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
-                    size = gy.element_size()
-                    gy_pitch, gx_pitch = (gy.stride(1), gx.stride(1)) if Cn > 1 else (0, 0)
-                    adjoint_schedule_clips_planar_device(
-                        [clip.pool[0]] * B, [gy.data_ptr() + i * gy.stride(0) * size for i in range(B)], [gy_pitch] * B, ctx.made,
-                        [gx.data_ptr() + i * gx.stride(0) * size for i in range(B)], [gx_pitch] * B, ctx.blocks, ctx.rates)
+                    if not ctx.x_shape[0]:                        # (no clip: no context was ever needed)
+                        return torch.zeros(ctx.x_shape, dtype=gy.dtype, device=gy.device), None, None, None, None, None
+                    gx = _clip_backward(adjoint_schedule_clips_planar_device, ctx.clip, "ClipWarper", ctx.x_shape, gy, ctx.made, ctx.blocks, ctx.rates)
                     return gx, None, None, None, None, None
 
             _state["warp_grad"] = ClipWarpGrad

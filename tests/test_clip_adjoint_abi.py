@@ -1,5 +1,6 @@
 """CPU: resampleAdjointClipsPlanarDevice — exported by both libraries, declared in art_hip.h with its prototype, listed in
-EXPORTED_SYMBOLS and wrapped; n <= 0 and a NULL context are answered without a device and without a count in artamdErrorCount; the
+EXPORTED_SYMBOLS and wrapped; n <= 0 and a NULL context are answered without a device and without a count in artamdErrorCount, alike
+by this entry and by resampleAdjointScheduleClipsPlanarDevice (the same clips as one block each); the
 adjoint kernel's eight instantiations (channel-group widths 1, 2, 4, 8 x interpolating or not) are in both libraries and use no
 scratch and no spills; ClipResampler.__call__ still makes its forward call where tests/test_clips_from_start_abi.py looks for it."""
 import ctypes as C
@@ -14,6 +15,7 @@ from test_matrix_batch_abi import _kernel_notes
 PKG = os.path.dirname(os.path.abspath(A.__file__))
 LIB32, LIB64 = os.path.join(PKG, "libartamd.so"), os.path.join(PKG, "libartamd64.so")
 ADJ = "resampleAdjointClipsPlanarDevice"
+BLOCKS = "resampleAdjointScheduleClipsPlanarDevice"
 FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")
 VARIANTS = [f"fir_adjoint_kernelILi{cg}ELb{interp}EE" for cg in (1, 2, 4, 8) for interp in (0, 1)]
 
@@ -48,6 +50,24 @@ def test_refusals_need_no_device(width):
     assert adj(none, 1, None, None, None, None, None, None, None) == -1
     assert adj(none, 1, none, longs, ints, none, longs, ints, ratios) == -1
     assert L.artamdErrorCount() == errors
+
+
+def test_both_entries_answer_nothing_to_do_and_a_null_context_alike():
+    """n <= 0 is 0, a NULL context among n is -1 — wherever it stands, with every other argument in order — and neither entry needs a device
+    or counts"""
+    for width in (32, 64):
+        L = A.binding(width).lib()
+        errors = L.artamdErrorCount()
+        for n in (1, 3):
+            none = (C.c_void_p * n)(*[None] * n)
+            ints, longs, ratios = (C.c_int * n)(*[5] * n), (C.c_long * n)(*[0] * n), (C.c_double * n)(*[1.0] * n)
+            ones = (C.c_int * n)(*[1] * n)
+            frames = (C.c_void_p * n)(*[C.addressof(ints) + 4 * i for i in range(n)])
+            rates = (C.c_void_p * n)(*[C.addressof(ratios) + 8 * i for i in range(n)])
+            for count, want in ((0, 0), (-1, 0), (n, -1)):
+                assert getattr(L, ADJ)(none, count, none, longs, ints, none, longs, ints, ratios) == want
+                assert getattr(L, BLOCKS)(none, count, ones, none, longs, ints, none, longs, frames, rates) == want
+        assert L.artamdErrorCount() == errors
 
 
 def test_kernel_instantiations_are_in_both_libraries():

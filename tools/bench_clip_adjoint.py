@@ -3,7 +3,9 @@ resampleProcessAndFlushClipsPlanarDevice from a fresh start — the two do the s
 frames, 380 taps, 44.1 -> 16 kHz (160 phases, nearest filter, low-pass) and 16 -> 44.1 kHz (interpolating).  The forward runs on a pool
 of B contexts, the adjoint on the first of them for every item.
 
-    python tools/bench_clip_adjoint.py [--calls 15] [--batches 1,64,1024] [--out profiles/clip_adjoint.txt]
+    python tools/bench_clip_adjoint.py [--calls 15] [--batches 1,64,1024] [--channels 2] [--width 32] [--out profiles/clip_adjoint.txt]
+
+--channels picks the adjoint kernel's channel-group width (1, 2, 3-4, 5 and more), --width the build (32: 4-byte samples, 64: 8-byte).
 
 Per case: median wall-clock milliseconds per call between two synchronisations, after warm-up, with the 25th and 75th percentile, and
 the ratio of the medians (adjoint / forward).
@@ -18,9 +20,9 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-import audio_resampler_amd as A  # noqa: E402
+from audio_resampler_amd import binding  # noqa: E402
 
-FRAMES, CH, TAPS = 16000, 2, 380
+FRAMES, TAPS = 16000, 380
 BATCHES = (1, 64, 1024)
 RATES = ((44100.0, 16000.0), (16000.0, 44100.0))
 
@@ -39,13 +41,15 @@ def timed(fn, calls, warm=3):
     return [round(float(v), 3) for v in q]
 
 
-def case(B, src, dst, calls):
+def case(B, src, dst, calls, CH=2, width=32):
+    A = binding(width)
+    dt = torch.float64 if width == 64 else torch.float32
     flags = A.BLACKMAN_HARRIS | A.SUBSAMPLE_INTERPOLATE | A.INCLUDE_LOWPASS
     pool = [A.Resampler(CH, TAPS, TAPS, 0.0, flags, (src, dst, 0)) for _ in range(B)]
     ratio = dst / src
     cap = int((FRAMES + TAPS) * ratio) + 64
-    x = torch.randn(B, CH, FRAMES, device="cuda") * 0.25
-    y = torch.zeros(B, CH, cap, device="cuda")
+    x = torch.randn(B, CH, FRAMES, dtype=dt, device="cuda") * 0.25
+    y = torch.zeros(B, CH, cap, dtype=dt, device="cuda")
     ins = [x[i].data_ptr() for i in range(B)]
     outs = [y[i].data_ptr() for i in range(B)]
 
@@ -54,8 +58,8 @@ def case(B, src, dst, calls):
                                                        [ratio] * B, from_start=True)
 
     made = [g for _, g in forward()]
-    gy = torch.randn(B, CH, cap, device="cuda") * 0.25
-    gx = torch.zeros(B, CH, FRAMES, device="cuda")
+    gy = torch.randn(B, CH, cap, dtype=dt, device="cuda") * 0.25
+    gx = torch.zeros(B, CH, FRAMES, dtype=dt, device="cuda")
     gouts = [gy[i].data_ptr() for i in range(B)]
     gins = [gx[i].data_ptr() for i in range(B)]
 
@@ -79,12 +83,17 @@ def main():
     ap.add_argument("--calls", type=int, default=15)
     ap.add_argument("--out", default=None)
     ap.add_argument("--batches", default=",".join(str(b) for b in BATCHES))
+    ap.add_argument("--channels", type=int, default=2)
+    ap.add_argument("--width", type=int, default=32, choices=(32, 64))
     a = ap.parse_args()
+    what = "stereo clips" if a.channels == 2 else f"{a.channels}-channel clips"
+    if a.width == 64:
+        what = "8-byte samples, " + what
     lines = ["# [median, 25th, 75th percentile] ms per call; forward: the clips entry from a fresh start; adjoint: resampleAdjointClipsPlanarDevice",
-             "# stereo clips of 16,000 frames, 380 taps; device: " + torch.cuda.get_device_name(0)]
+             f"# {what} of 16,000 frames, 380 taps; device: " + torch.cuda.get_device_name(0)]
     for src, dst in RATES:
         for B in [int(v) for v in a.batches.split(",")]:
-            r = case(B, src, dst, a.calls)
+            r = case(B, src, dst, a.calls, a.channels, a.width)
             r.update(case=f"{src:g} -> {dst:g}", B=B, adjoint_over_forward=round(r["adjoint"][0] / r["forward"][0], 2))
             lines.append(json.dumps(r))
             print(lines[-1], flush=True)

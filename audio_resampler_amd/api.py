@@ -237,6 +237,44 @@ def _bind(width):
         """address of a torch CUDA tensor (or a raw int)."""
         return t if isinstance(t, int) else int(t) if isinstance(t, np.integer) else (t.data_ptr() if t is not None else None)
 
+    # -- the argument arrays of the batch entries: each takes a list or a numpy array and the entry's item count (a longer list raises
+    #    IndexError, a shorter one is filled with zeros); a wrapper below is these, its C call and its return convention --
+    def _contexts(objs, n):
+        """void *[n] of the contexts of objects with .p (a typed pointer, an address or None)"""
+        return (C.c_void_p * n)(*[p if type(p) is int or p is None else C.c_void_p.from_buffer(p).value for p in [o.p for o in objs]])
+
+    def _dev_ptrs(v, n):
+        """void *[n] of device addresses: tensors, ints or None"""
+        return (C.c_void_p * n)(*(v.tolist() if isinstance(v, np.ndarray) else map(_dev_ptr, v)))
+
+    def _ints(v, n):
+        return (C.c_int * n)(*map(int, v.tolist() if isinstance(v, np.ndarray) else v))
+
+    def _longs(v, n):
+        """long[n], or None for None (a pitch list: every item interleaved)"""
+        return None if v is None else (C.c_long * n)(*map(int, v.tolist() if isinstance(v, np.ndarray) else v))
+
+    def _doubles(v, n):
+        return (C.c_double * n)(*map(float, v.tolist() if isinstance(v, np.ndarray) else v))
+
+    def _rows(ctype, convert, lists):
+        """a ctypes array per item of `lists` (never of no element), to go into a _table"""
+        return [(ctype * max(len(v), 1))(*map(convert, v)) for v in lists]
+
+    def _flat(pairs):
+        return [v for pair in pairs for v in pair]
+
+    def _table(arrays, n):
+        """void *[n] of the addresses of per-item ctypes arrays (which the caller keeps alive)"""
+        return (C.c_void_p * n)(*map(C.addressof, arrays))
+
+    def _raw_stream(stream):
+        """a torch stream, a raw address or None (the null stream) as the address the entries take"""
+        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+
+    def _results(res, n):
+        return [(res[k].input_used, res[k].output_generated) for k in range(n)]
+
 
     class Resampler:
         """Object wrapper over the C API.  Host arrays are numpy [frames, channels] (interleaved);
@@ -375,36 +413,30 @@ def _bind(width):
             r = fn(self.p, _dev_ptr(d_in), n_in, _dev_ptr(d_out), out_cap, ratio)
             return r.input_used, r.output_generated
 
-        def process_schedule_device(self, d_in, n_ins, d_out, caps, ratios, flush_last=False):
-            """resampleProcessScheduleInterleavedDevice: blocks k = 0, 1, ... of this stream, contiguous in d_in, outputs packed in d_out
-            (which holds sum(caps) frames).  Returns (blocks_made, [(input_used, output_generated), ...]); raises if a launch failed."""
+        def _schedule(self, name, d_in, n_ins, d_out, caps, ratios, flush_last, pitches=None):
+            """the two schedule entries: the planar one takes a pitch behind each buffer"""
             n = len(n_ins)
             if len(caps) != n or len(ratios) != n:
                 raise ValueError("n_ins, caps and ratios must have one entry per block")
-            res = (ResampleResult * max(n, 1))()
-            rc = self.L.resampleProcessScheduleInterleavedDevice(
-                self.p, n, _dev_ptr(d_in), (C.c_int * max(n, 1))(*[int(v) for v in n_ins]), _dev_ptr(d_out),
-                (C.c_int * max(n, 1))(*[int(v) for v in caps]), (C.c_double * max(n, 1))(*[float(v) for v in ratios]),
-                1 if flush_last else 0, res)
+            m = max(n, 1)
+            res = (ResampleResult * m)()
+            side = lambda d, k: (_dev_ptr(d),) if pitches is None else (_dev_ptr(d), int(pitches[k]))
+            rc = getattr(self.L, name)(self.p, n, *side(d_in, 0), _ints(n_ins, m), *side(d_out, 1), _ints(caps, m), _doubles(ratios, m),
+                                       1 if flush_last else 0, res)
             if rc < 0:
-                raise RuntimeError("resampleProcessScheduleInterleavedDevice failed")
-            return rc, [(res[k].input_used, res[k].output_generated) for k in range(n)]
+                raise RuntimeError(name + " failed")
+            return rc, _results(res, n)
+
+        def process_schedule_device(self, d_in, n_ins, d_out, caps, ratios, flush_last=False):
+            """resampleProcessScheduleInterleavedDevice: blocks k = 0, 1, ... of this stream, contiguous in d_in, outputs packed in d_out
+            (which holds sum(caps) frames).  Returns (blocks_made, [(input_used, output_generated), ...]); raises if a launch failed."""
+            return self._schedule("resampleProcessScheduleInterleavedDevice", d_in, n_ins, d_out, caps, ratios, flush_last)
 
         def process_schedule_planar_device(self, d_in, in_pitch, n_ins, d_out, out_pitch, caps, ratios, flush_last=False):
             """resampleProcessSchedulePlanarDevice: process_schedule_device on channels-first buffers (pitches in samples, 0: that side
             interleaved): the blocks follow one another along every input plane, the outputs are packed along every output plane.
             Returns (blocks_made, [(input_used, output_generated), ...]); raises if a launch failed."""
-            n = len(n_ins)
-            if len(caps) != n or len(ratios) != n:
-                raise ValueError("n_ins, caps and ratios must have one entry per block")
-            res = (ResampleResult * max(n, 1))()
-            rc = self.L.resampleProcessSchedulePlanarDevice(
-                self.p, n, _dev_ptr(d_in), int(in_pitch), (C.c_int * max(n, 1))(*[int(v) for v in n_ins]), _dev_ptr(d_out), int(out_pitch),
-                (C.c_int * max(n, 1))(*[int(v) for v in caps]), (C.c_double * max(n, 1))(*[float(v) for v in ratios]),
-                1 if flush_last else 0, res)
-            if rc < 0:
-                raise RuntimeError("resampleProcessSchedulePlanarDevice failed")
-            return rc, [(res[k].input_used, res[k].output_generated) for k in range(n)]
+            return self._schedule("resampleProcessSchedulePlanarDevice", d_in, n_ins, d_out, caps, ratios, flush_last, (in_pitch, out_pitch))
 
         def process_planar_device(self, d_in, in_pitch, n_in, d_out, out_pitch, out_cap, ratio):
             r = self.L.resampleProcessPlanarDevice(self.p, _dev_ptr(d_in), in_pitch, n_in, _dev_ptr(d_out), out_pitch, out_cap, ratio)
@@ -517,63 +549,44 @@ def _bind(width):
         the general kernel runs and one grouped launch per shape for those the f32 streaming matrix kernel runs un-split on kept rows
         (matrix-size calls under preference 6, anchored calls under the cut-invariant policy; a stream's first matrix call, which
         builds its rows, and everything else is made one by one).  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
-        n = len(resamplers)
-        ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])
-        res = (ResampleResult * n)()
-        rc = lib().resampleProcessBatchInterleavedDevice(
-            ctx, n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), (C.c_int * n)(*[int(v) for v in n_ins]),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), (C.c_int * n)(*[int(v) for v in out_caps]),
-            (C.c_double * n)(*[float(v) for v in ratios]), res)
-        if rc:
-            raise RuntimeError("resampleProcessBatchInterleavedDevice failed")
-        return [(r.input_used, r.output_generated) for r in res]
+        return _batch("resampleProcessBatchInterleavedDevice", False, resamplers, d_ins, None, n_ins, d_outs, None, out_caps, ratios)
 
     def process_and_flush_batch_device(resamplers, d_ins, n_ins, d_outs, out_caps, ratios):
         """resampleProcessAndFlushBatchInterleavedDevice over a list of Resampler objects: every context's
         resampleProcessAndFlushInterleavedDevice call, the process calls (general-kernel and matrix-core calls alike, as
         process_batch_device gathers them) and then the flushes gathered into shared launches (a
         d_ins entry may be None with n_ins 0: a pure flush).  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
-        n = len(resamplers)
-        ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])
-        res = (ResampleResult * n)()
-        rc = lib().resampleProcessAndFlushBatchInterleavedDevice(
-            ctx, n, (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_ins]), (C.c_int * n)(*[int(v) for v in n_ins]),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), (C.c_int * n)(*[int(v) for v in out_caps]),
-            (C.c_double * n)(*[float(v) for v in ratios]), res)
-        if rc:
-            raise RuntimeError("resampleProcessAndFlushBatchInterleavedDevice failed")
-        return [(r.input_used, r.output_generated) for r in res]
+        return _batch("resampleProcessAndFlushBatchInterleavedDevice", False, resamplers, d_ins, None, n_ins, d_outs, None, out_caps, ratios)
 
-    def _batch_planar(name, resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios, *more):
+    def _batch(name, planar, resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios, *more):
+        """the body of the five wrappers around it: a planar entry takes a pitch array behind each side's addresses, and `more` in front
+        of the results"""
         n = len(resamplers)
-        ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])
         res = (ResampleResult * n)()
-        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
-        rc = getattr(lib(), name)(
-            ctx, n, (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_ins]), pitches(in_pitches), (C.c_int * n)(*[int(v) for v in n_ins]),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches), (C.c_int * n)(*[int(v) for v in out_caps]),
-            (C.c_double * n)(*[float(v) for v in ratios]), *more, res)
+        side = lambda d, pitches: (_dev_ptrs(d, n), _longs(pitches, n)) if planar else (_dev_ptrs(d, n),)
+        rc = getattr(lib(), name)(_contexts(resamplers, n), n, *side(d_ins, in_pitches), _ints(n_ins, n), *side(d_outs, out_pitches),
+                                  _ints(out_caps, n), _doubles(ratios, n), *more, res)
         if rc:
             raise RuntimeError(name + " failed")
-        return [(r.input_used, r.output_generated) for r in res]
+        return _results(res, n)
 
     def process_batch_planar_device(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios):
         """resampleProcessBatchPlanarDevice: process_batch_device with a pitch per buffer, in samples (channel c of item i at
         d_ins[i] + c * in_pitches[i]; 0: that side of that item interleaved; None for a pitch list: every item's is).  Calls the single
         planar call would stage are transposed by one launch in front of the FIR launches and one behind.
         Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
-        return _batch_planar("resampleProcessBatchPlanarDevice", resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios)
+        return _batch("resampleProcessBatchPlanarDevice", True, resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios)
 
     def process_and_flush_batch_planar_device(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios):
         """resampleProcessAndFlushBatchPlanarDevice: process_and_flush_batch_device on channels-first buffers (pitches as in
         process_batch_planar_device; a d_ins entry may be None with n_ins 0: a pure flush).  The flushes write behind the process
         calls' frames in every plane.  Returns [(input_used, output_generated), ...] (raises if a launch failed)."""
-        return _batch_planar("resampleProcessAndFlushBatchPlanarDevice", resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios)
+        return _batch("resampleProcessAndFlushBatchPlanarDevice", True, resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios)
 
     def process_and_flush_clips_planar_device(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios, from_start=False):
         """resampleProcessAndFlushClipsPlanarDevice: process_and_flush_batch_planar_device, with from_start every context first as after
         its reset() — the contexts on the first one's stream put back by one zeroing launch for all of them, no memset per context."""
-        return _batch_planar("resampleProcessAndFlushClipsPlanarDevice", resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios,
+        return _batch("resampleProcessAndFlushClipsPlanarDevice", True, resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, out_caps, ratios,
                              1 if from_start else 0)
 
     def adjoint_clips_planar_device(resamplers, d_gouts, gout_pitches, n_outs, d_gins, gin_pitches, n_ins, ratios):
@@ -582,53 +595,117 @@ def _bind(width):
         first n_outs[i] frames of d_gouts[i]; pitches as in process_batch_planar_device.  The contexts are only read, and one may be
         listed any number of times.  Returns the launch count (raises if the call returned -1)."""
         n = len(resamplers)
-        ctx = (C.c_void_p * n)(*[C.cast(r.p, C.c_void_p) for r in resamplers])
-        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
         rc = lib().resampleAdjointClipsPlanarDevice(
-            ctx, n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_gouts]), pitches(gout_pitches), (C.c_int * n)(*[int(v) for v in n_outs]),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_gins]), pitches(gin_pitches), (C.c_int * n)(*[int(v) for v in n_ins]),
-            (C.c_double * n)(*[float(v) for v in ratios]))
+            _contexts(resamplers, n), n, _dev_ptrs(d_gouts, n), _longs(gout_pitches, n), _ints(n_outs, n),
+            _dev_ptrs(d_gins, n), _longs(gin_pitches, n), _ints(n_ins, n), _doubles(ratios, n))
         if rc < 0:
             raise RuntimeError("resampleAdjointClipsPlanarDevice failed")
         return rc
 
-    def _clip_backward(entry, clip, owner, x_shape, gy, made, n_ins, ratios):
-        """gx [B, C, T] of a clip class's backward: gy's rows handed as they lie to `entry` (one of the two adjoint wrappers above and below)
-        on the first context of `clip` (an `owner`), clip i's frames and ratio or ratios n_ins[i] and ratios[i]"""
+    def _rows_readable(t):
+        """rows that are only read (a grad_y of the resampler adjoints): frames consecutive, planes apart; clips may overlap, but a batch
+        stride of 0 is not taken"""
+        B, Cn, T = t.shape
+        return not ((T and t.stride(2) != 1) or (Cn > 1 and t.stride(1) < T) or (B > 1 and t.stride(0) < 1))
+
+    def _rows_apart(t):
+        """rows that may be written, and every operand of the biquad and stretch entries: frames consecutive, planes and clips apart"""
+        B, Cn, T = t.shape
+        return not ((T and t.stride(2) != 1) or (Cn > 1 and t.stride(1) < T) or (B > 1 and t.stride(0) < max(Cn * T, 1)))
+
+    def _plane_ptrs(t):
+        """addresses of the planes of t [..., T] (frames consecutive) as a numpy array of t's leading shape"""
+        at = np.zeros(tuple(t.shape[:-1]), np.int64)
+        for d in range(t.dim() - 1):
+            at = at + (np.arange(t.shape[d], dtype=np.int64) * t.stride(d)).reshape([-1 if k == d else 1 for k in range(t.dim() - 1)])
+        return t.data_ptr() + at * t.element_size()
+
+    def _clip_ptrs(t):
+        """addresses of the clips of t [B, C, T], a list, and the pitch the planar entries take for them (0: one channel, the same call in
+        either layout)"""
+        base, step = t.data_ptr(), t.stride(0) * t.element_size()
+        return (list(range(base, base + t.shape[0] * step, step)) if step else [base] * t.shape[0]), (t.stride(1) if t.shape[1] > 1 else 0)
+
+    # -- the front of a clip class's call: _clip_input, _pool_ready, then per chunk of _chunks the rows of _clip_ptrs --
+    def _clip_input(x, channels, lengths, cuda=True, strided="copy"):
+        """(x as [B, C, T], B, C, T, lengths as a checked list) of a call on x [B, C, T] or [C, T].  cuda=False: the caller asks for the
+        GPU itself, later.  A stride along T other than 1 — "copy": through .contiguous() (any row pitch is taken as it is); "refuse":
+        for a call in place; "keep": the caller looks at the rows itself"""
+        import torch
+        if x.dim() == 2:
+            x = x.unsqueeze(0)
+        if x.dim() != 3 or x.shape[1] != channels or (cuda and not x.is_cuda) or x.dtype != getattr(torch, smp_torch):
+            raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {channels}, T]")
+        if strided != "keep" and x.shape[2] and x.stride(2) != 1:
+            if strided == "refuse":
+                raise ValueError("in place: the frames of a channel must be consecutive (stride 1 along T)")
+            x = x.contiguous()
+        B, Cn, T = x.shape
+        if lengths is None:
+            return x, B, Cn, T, [T] * B
+        lengths = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if len(lengths) != B or any(v < 0 or v > T for v in lengths):
+            raise ValueError("lengths: one entry per clip, 0 .. T")
+        return x, B, Cn, T, lengths
+
+    def _pool_ready(pool, need, make, stream):
+        """`pool` grown to `need` contexts with make(), and those put on `stream`"""
+        while len(pool) < need:
+            pool.append(make())
+        for p in pool[:need]:
+            p.set_stream(stream)
+
+    def _chunks(count, size):
+        """`count` items as slices of at most `size`, in order"""
+        for b0 in range(0, count, size):
+            yield slice(b0, min(count, b0 + size))
+
+    def _out_of_place(src, lengths):
+        """a new contiguous tensor for the clips of src [B, C, T] filtered up to lengths[i]: frames at and past lengths[i] go through as
+        they are, so src's values where a clip has such frames, else nothing yet"""
+        import torch
+        return src.clone(memory_format=torch.contiguous_format) if any(v < src.shape[2] for v in lengths) else \
+            torch.empty(src.shape, dtype=src.dtype, device=src.device)
+
+    def _grad_function(name, forward, backward):
+        """() -> the once-differentiable torch.autograd.Function `name` of forward(ctx, ...) and backward(ctx, grad_y), made on first use
+        (torch is imported late) and kept; every forward below notes what backward needs and returns y.view_as(y), which attaches y to the
+        graph"""
+        def made():
+            if name not in _state:
+                import torch
+                _state[name] = type(name, (torch.autograd.Function,), {
+                    "forward": staticmethod(forward), "backward": staticmethod(torch.autograd.function.once_differentiable(backward))})
+            return _state[name]
+        return made
+
+    def _clip_backward(x_shape, gy, rows_ok, lead):
+        """what an adjoint entry's backward starts from: (gx [B, C, T] of zeros, the entry's four row arguments — gy's addresses and pitches,
+        then gx's); gy's rows as they lie where rows_ok(gy), else through .contiguous(); `lead` (the context the entry takes its stream from)
+        is put on the current stream"""
         import torch
         B, Cn, T = x_shape
-        if not clip.pool:
-            raise RuntimeError(f"the {owner} was closed before backward")
-        if (gy.shape[2] and gy.stride(2) != 1) or (Cn > 1 and gy.stride(1) < gy.shape[2]) or (B > 1 and gy.stride(0) < 1):
-            gy = gy.contiguous()                                  # (frames of a channel consecutive, planes and clips apart)
+        if not rows_ok(gy):
+            gy = gy.contiguous()
         gx = torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device)     # (zero at and past lengths[i])
-        clip.pool[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
-        size = gy.element_size()
-        gy_pitch, gx_pitch = (gy.stride(1), gx.stride(1)) if Cn > 1 else (0, 0)
-        entry([clip.pool[0]] * B, [gy.data_ptr() + i * gy.stride(0) * size for i in range(B)], [gy_pitch] * B, made,
-              [gx.data_ptr() + i * gx.stride(0) * size for i in range(B)], [gx_pitch] * B, n_ins, ratios)
-        return gx
+        lead.set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
+        (gy_ptrs, gy_pitch), (gx_ptrs, gx_pitch) = _clip_ptrs(gy), _clip_ptrs(gx)
+        return gx, (gy_ptrs, [gy_pitch] * B, gx_ptrs, [gx_pitch] * B)
 
-    def _clip_resample_grad():
-        """the torch.autograd.Function that attaches a ClipResampler's output to the graph (made on first use: torch is imported late)"""
-        if "clip_grad" not in _state:
-            import torch
+    def _clip_resample_forward(ctx, x, y, clip, lengths, made):
+        ctx.clip, ctx.lengths, ctx.made, ctx.x_shape = clip, lengths, made, x.shape
+        return y.view_as(y)
 
-            class ClipResampleGrad(torch.autograd.Function):
-                @staticmethod
-                def forward(ctx, x, y, clip, lengths, made):
-                    ctx.clip, ctx.lengths, ctx.made, ctx.x_shape = clip, lengths, made, x.shape
-                    return y.view_as(y)
+    def _clip_resample_backward(ctx, gy):
+        clip = ctx.clip
+        if not clip.pool:
+            raise RuntimeError("the ClipResampler was closed before backward")
+        B = ctx.x_shape[0]
+        gx, (gy_ptrs, gy_pitches, gx_ptrs, gx_pitches) = _clip_backward(ctx.x_shape, gy, _rows_readable, clip.pool[0])
+        adjoint_clips_planar_device([clip.pool[0]] * B, gy_ptrs, gy_pitches, ctx.made, gx_ptrs, gx_pitches, ctx.lengths, [clip.ratio] * B)
+        return gx, None, None, None, None
 
-                @staticmethod
-                @torch.autograd.function.once_differentiable
-                def backward(ctx, gy):
-                    gx = _clip_backward(adjoint_clips_planar_device, ctx.clip, "ClipResampler", ctx.x_shape, gy, ctx.made, ctx.lengths,
-                                        [ctx.clip.ratio] * ctx.x_shape[0])
-                    return gx, None, None, None, None
-
-            _state["clip_grad"] = ClipResampleGrad
-        return _state["clip_grad"]
+    _clip_resample_grad = _grad_function("ClipResampleGrad", _clip_resample_forward, _clip_resample_backward)
 
     def _schedule_batch(resamplers, d_ins, in_pitches, n_ins, d_outs, out_pitches, caps, ratios, flush_last, clips=None):
         """(clips: None, or the clips entry's from_start)"""
@@ -639,31 +716,25 @@ def _bind(width):
         counts = [len(v) for v in n_ins]
         if any(len(caps[i]) != counts[i] or len(ratios[i]) != counts[i] for i in range(n)):
             raise ValueError("n_ins[i], caps[i] and ratios[i] must have one entry per block")
-        rows = lambda ctype, lists: [(ctype * max(len(v), 1))(*v) for v in lists]
-        table = lambda arrays: (C.c_void_p * m)(*[C.cast(a, C.c_void_p) for a in arrays])
-        frames = rows(C.c_int, [[int(v) for v in row] for row in n_ins])
-        room = rows(C.c_int, [[int(v) for v in row] for row in caps])
-        rates = rows(C.c_double, [[float(v) for v in row] for row in ratios])
+        frames, room, rates = _rows(C.c_int, int, n_ins), _rows(C.c_int, int, caps), _rows(C.c_double, float, ratios)
         res = [(ResampleResult * max(k, 1))() for k in counts]
         made = (C.c_int * m)()
-        pitches = lambda v: None if v is None else (C.c_long * m)(*[int(q) for q in v])
-        head = [(C.c_void_p * m)(*[C.cast(r.p, C.c_void_p) for r in resamplers]), n, (C.c_int * m)(*counts),
-                (C.c_void_p * m)(*[None if d is None else _dev_ptr(d) for d in d_ins])]
-        outs = (C.c_void_p * m)(*[_dev_ptr(d) for d in d_outs])
-        tail = [table(rates), None if flush_last is None else (C.c_int * m)(*[1 if f else 0 for f in flush_last]), table(res), made]
+        head = [_contexts(resamplers, m), n, _ints(counts, m), _dev_ptrs(d_ins, m)]
+        outs = _dev_ptrs(d_outs, m)
+        tail = [_table(rates, m), None if flush_last is None else _ints([1 if f else 0 for f in flush_last], m), _table(res, m), made]
+        planar = lambda: (*head, _longs(in_pitches, m), _table(frames, m), outs, _longs(out_pitches, m), _table(room, m))
         if clips is not None:
             name = "resampleProcessScheduleClipsPlanarDevice"
-            rc = lib().resampleProcessScheduleClipsPlanarDevice(*head, pitches(in_pitches), table(frames), outs, pitches(out_pitches), table(room),
-                                                                *tail[:2], 1 if clips else 0, *tail[2:])
+            rc = lib().resampleProcessScheduleClipsPlanarDevice(*planar(), *tail[:2], 1 if clips else 0, *tail[2:])
         elif in_pitches is None and out_pitches is None:
             name = "resampleProcessScheduleBatchInterleavedDevice"
-            rc = lib().resampleProcessScheduleBatchInterleavedDevice(*head, table(frames), outs, table(room), *tail)
+            rc = lib().resampleProcessScheduleBatchInterleavedDevice(*head, _table(frames, m), outs, _table(room, m), *tail)
         else:
             name = "resampleProcessScheduleBatchPlanarDevice"
-            rc = lib().resampleProcessScheduleBatchPlanarDevice(*head, pitches(in_pitches), table(frames), outs, pitches(out_pitches), table(room), *tail)
+            rc = lib().resampleProcessScheduleBatchPlanarDevice(*planar(), *tail)
         if rc < 0:
             raise RuntimeError(name + " failed")
-        return rc, [(made[i], [(res[i][k].input_used, res[i][k].output_generated) for k in range(counts[i])]) for i in range(n)]
+        return rc, [(made[i], _results(res[i], counts[i])) for i in range(n)]
 
     def process_schedule_batch_device(resamplers, d_ins, n_ins, d_outs, caps, ratios, flush_last=None):
         """resampleProcessScheduleBatchInterleavedDevice: Resampler.process_schedule_device for every stream of a list in one call —
@@ -698,39 +769,30 @@ def _bind(width):
             raise ValueError("n_ins[i] and ratios[i] must have one entry per block")
         m = max(n, 1)
         counts = [len(v) for v in n_ins]
-        frames = [(C.c_int * max(len(v), 1))(*[int(q) for q in v]) for v in n_ins]
-        rates = [(C.c_double * max(len(v), 1))(*[float(q) for q in v]) for v in ratios]
-        table = lambda arrays: (C.c_void_p * m)(*[C.cast(a, C.c_void_p) for a in arrays])
-        pitches = lambda v: None if v is None else (C.c_long * m)(*[int(q) for q in v])
+        frames, rates = _rows(C.c_int, int, n_ins), _rows(C.c_double, float, ratios)
         rc = lib().resampleAdjointScheduleClipsPlanarDevice(
-            (C.c_void_p * m)(*[C.cast(r.p, C.c_void_p) for r in resamplers]), n, (C.c_int * m)(*counts),
-            (C.c_void_p * m)(*[_dev_ptr(d) for d in d_gouts]), pitches(gout_pitches), (C.c_int * m)(*[int(v) for v in n_outs]),
-            (C.c_void_p * m)(*[_dev_ptr(d) for d in d_gins]), pitches(gin_pitches), table(frames), table(rates))
+            _contexts(resamplers, m), n, _ints(counts, m), _dev_ptrs(d_gouts, m), _longs(gout_pitches, m), _ints(n_outs, m),
+            _dev_ptrs(d_gins, m), _longs(gin_pitches, m), _table(frames, m), _table(rates, m))
         if rc < 0:
             raise RuntimeError("resampleAdjointScheduleClipsPlanarDevice failed")
         return rc
 
-    def _clip_warp_grad():
-        """the torch.autograd.Function that attaches a ClipWarper's output to the graph (made on first use: torch is imported late)"""
-        if "warp_grad" not in _state:
-            import torch
+    def _clip_warp_forward(ctx, x, y, clip, blocks, rates, made):
+        ctx.clip, ctx.blocks, ctx.rates, ctx.made, ctx.x_shape = clip, blocks, rates, made, x.shape
+        return y.view_as(y)
 
-            class ClipWarpGrad(torch.autograd.Function):
-                @staticmethod
-                def forward(ctx, x, y, clip, blocks, rates, made):
-                    ctx.clip, ctx.blocks, ctx.rates, ctx.made, ctx.x_shape = clip, blocks, rates, made, x.shape
-                    return y.view_as(y)
+    def _clip_warp_backward(ctx, gy):
+        import torch
+        clip, B = ctx.clip, ctx.x_shape[0]
+        if not B:                                                 # (no clip: no context was ever needed)
+            return torch.zeros(ctx.x_shape, dtype=gy.dtype, device=gy.device), None, None, None, None, None
+        if not clip.pool:
+            raise RuntimeError("the ClipWarper was closed before backward")
+        gx, (gy_ptrs, gy_pitches, gx_ptrs, gx_pitches) = _clip_backward(ctx.x_shape, gy, _rows_readable, clip.pool[0])
+        adjoint_schedule_clips_planar_device([clip.pool[0]] * B, gy_ptrs, gy_pitches, ctx.made, gx_ptrs, gx_pitches, ctx.blocks, ctx.rates)
+        return gx, None, None, None, None, None
 
-                @staticmethod
-                @torch.autograd.function.once_differentiable
-                def backward(ctx, gy):
-                    if not ctx.x_shape[0]:                        # (no clip: no context was ever needed)
-                        return torch.zeros(ctx.x_shape, dtype=gy.dtype, device=gy.device), None, None, None, None, None
-                    gx = _clip_backward(adjoint_schedule_clips_planar_device, ctx.clip, "ClipWarper", ctx.x_shape, gy, ctx.made, ctx.blocks, ctx.rates)
-                    return gx, None, None, None, None, None
-
-            _state["warp_grad"] = ClipWarpGrad
-        return _state["warp_grad"]
+    _clip_warp_grad = _grad_function("ClipWarpGrad", _clip_warp_forward, _clip_warp_backward)
 
     class ClipWarper:
         """Whole clips, channels-first, at a rate that changes inside the clip: x [B, C, T] (or [C, T]) on the GPU and a ratio per block of
@@ -781,41 +843,29 @@ def _bind(width):
 
         def __call__(self, x, ratios, lengths=None):
             import torch
-            if x.dim() == 2:
-                x = x.unsqueeze(0)
-            if x.dim() != 3 or x.shape[1] != self.channels or x.dtype != getattr(torch, smp_torch):
-                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
-            B, Cn, T = x.shape
-            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
-                raise ValueError("lengths: one entry per clip, 0 .. T")
+            # (the GPU is asked for behind the host checks, those of `ratios` included: they need none)
+            x, B, Cn, T, lengths = _clip_input(x, self.channels, lengths, cuda=False, strided="keep")
             frames, rates = self.blocks(lengths, ratios)
             if not x.is_cuda:
                 raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
             if x.shape[2] and x.stride(2) != 1:
                 x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
-            while len(self.pool) < min(B, self.max_batch):
-                self.pool.append(Resampler(*self._init))
             stream = torch.cuda.current_stream(x.device).cuda_stream
-            for r in self.pool[:min(B, self.max_batch)]:
-                r.set_stream(stream)
+            _pool_ready(self.pool, min(B, self.max_batch), lambda: Resampler(*self._init), stream)
             # room so that no block is cut: a block of n frames moves the position by at most n frames past where the block before left it
             # (not behind the input), the flush by half a window more
             caps = [[int((n + 2) * q) + 4 for n, q in zip(f, r)] for f, r in zip(frames, rates)]
             for c, f, r in zip(caps, frames, rates):
                 c[-1] = int((f[-1] + self.taps // 2 + 2) * r[-1]) + 4
             y = torch.zeros(B, Cn, max((sum(c) for c in caps), default=0), dtype=x.dtype, device=x.device)
-            size = x.element_size()
-            xp, yp = x.data_ptr(), y.data_ptr()
-            in_pitch, out_pitch = (x.stride(1), y.stride(1)) if Cn > 1 else (0, 0)      # (one channel: the same call in either layout)
+            (xs, in_pitch), (ys, out_pitch) = _clip_ptrs(x), _clip_ptrs(y)
             made = []
-            for b0 in range(0, B, self.max_batch):
-                idx = range(b0, min(B, b0 + self.max_batch))
+            for rows in _chunks(B, self.max_batch):
+                k = rows.stop - rows.start
                 _, got = process_schedule_clips_planar_device(
-                    self.pool[:len(idx)], [xp + i * x.stride(0) * size for i in idx], [in_pitch] * len(idx), [frames[i] for i in idx],
-                    [yp + i * y.stride(0) * size for i in idx], [out_pitch] * len(idx), [caps[i] for i in idx], [rates[i] for i in idx],
-                    flush_last=[True] * len(idx), from_start=True)
-                for i, (blocks_made, res) in zip(idx, got):
+                    self.pool[:k], xs[rows], [in_pitch] * k, frames[rows], ys[rows], [out_pitch] * k, caps[rows], rates[rows],
+                    flush_last=[True] * k, from_start=True)
+                for i, (blocks_made, res) in enumerate(got, rows.start):
                     if blocks_made != len(frames[i]) or any(used != n for (used, _), n in zip(res, frames[i])):
                         raise RuntimeError(f"ClipWarper: clip {i} was cut short ({blocks_made} of {len(frames[i])} blocks made)")
                     made.append(sum(g for _, g in res))
@@ -857,35 +907,19 @@ def _bind(width):
 
         def __call__(self, x, lengths=None):
             import torch
-            if x.dim() == 2:
-                x = x.unsqueeze(0)
-            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
-                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
-            if x.shape[2] and x.stride(2) != 1:
-                x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
-            B, Cn, T = x.shape
-            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
-                raise ValueError("lengths: one entry per clip, 0 .. T")
-            while len(self.pool) < min(B, self.max_batch):
-                self.pool.append(Resampler(*self._init[:5], fixed=self._init[5]))
+            x, B, Cn, T, lengths = _clip_input(x, self.channels, lengths)
             stream = torch.cuda.current_stream(x.device).cuda_stream
-            for r in self.pool[:min(B, self.max_batch)]:
-                r.set_stream(stream)
+            _pool_ready(self.pool, min(B, self.max_batch), lambda: Resampler(*self._init[:5], fixed=self._init[5]), stream)
             if any(v not in self._expected for v in lengths):
                 self.pool[0].reset()                              # (the dry run of a new length wants one context at its start)
             rooms = [self._room(v) for v in lengths]
             y = torch.zeros(B, Cn, max(rooms, default=0), dtype=x.dtype, device=x.device)
-            size = x.element_size()
-            xp, yp = x.data_ptr(), y.data_ptr()
-            in_pitch, out_pitch = (x.stride(1), y.stride(1)) if Cn > 1 else (0, 0)      # (one channel: the same call in either layout)
+            (xs, in_pitch), (ys, out_pitch) = _clip_ptrs(x), _clip_ptrs(y)
             made = []
-            for b0 in range(0, B, self.max_batch):
-                idx = range(b0, min(B, b0 + self.max_batch))
+            for rows in _chunks(B, self.max_batch):
+                k = rows.stop - rows.start
                 got = process_and_flush_clips_planar_device(
-                    self.pool[:len(idx)], [xp + i * x.stride(0) * size for i in idx], [in_pitch] * len(idx), [lengths[i] for i in idx],
-                    [yp + i * y.stride(0) * size for i in idx], [out_pitch] * len(idx), [rooms[i] for i in idx],
-                    [self.ratio] * len(idx), from_start=True)
+                    self.pool[:k], xs[rows], [in_pitch] * k, lengths[rows], ys[rows], [out_pitch] * k, rooms[rows], [self.ratio] * k, from_start=True)
                 made += [g for _, g in got]
             out_lengths = torch.tensor(made, dtype=torch.int64)
             y = y[:, :, :max(made, default=0)]
@@ -897,10 +931,7 @@ def _bind(width):
         """decimateProcessBatchInterleavedLEDevice over a list of Decimator objects: one launch per class of work for the
         contexts on the first one's stream.  Returns the launch count (raises if the call returned -1)."""
         n = len(decimators)
-        ctx = (C.c_void_p * n)(*[C.cast(d.p, C.c_void_p) for d in decimators])
-        rc = lib().decimateProcessBatchInterleavedLEDevice(
-            ctx, n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), (C.c_int * n)(*[int(v) for v in n_ins]),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]))
+        rc = lib().decimateProcessBatchInterleavedLEDevice(_contexts(decimators, n), n, _dev_ptrs(d_ins, n), _ints(n_ins, n), _dev_ptrs(d_outs, n))
         if rc < 0:
             raise RuntimeError("decimateProcessBatchInterleavedLEDevice failed")
         return rc
@@ -910,11 +941,8 @@ def _bind(width):
         d_ins[i] + c * in_pitches[i] samples, of its output at d_outs[i] + c * out_pitches[i] bytes; 0: that side of that item is
         interleaved; None for a pitch list: every item's is).  Returns the launch count (raises if the call returned -1)."""
         n = len(decimators)
-        ctx = (C.c_void_p * n)(*[C.cast(d.p, C.c_void_p) for d in decimators])
-        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
         rc = lib().decimateProcessBatchPlanarLEDevice(
-            ctx, n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), pitches(in_pitches), (C.c_int * n)(*[int(v) for v in n_ins]),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches))
+            _contexts(decimators, n), n, _dev_ptrs(d_ins, n), _longs(in_pitches, n), _ints(n_ins, n), _dev_ptrs(d_outs, n), _longs(out_pitches, n))
         if rc < 0:
             raise RuntimeError("decimateProcessBatchPlanarLEDevice failed")
         return rc
@@ -925,12 +953,9 @@ def _bind(width):
         d_clip_counts (len(decimators) uint64 / int64 entries of device memory) entry i SET to item i's count of clipped samples by
         the launches themselves, to be read with one download behind the call.  Returns the launch count (raises on -1)."""
         n = len(decimators)
-        ctx = (C.c_void_p * n)(*[C.cast(d.p, C.c_void_p) for d in decimators])
-        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
         rc = lib().decimateProcessClipsPlanarLEDevice(
-            ctx, n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), pitches(in_pitches), (C.c_int * n)(*[int(v) for v in n_ins]),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches), 1 if from_start else 0,
-            None if d_clip_counts is None else _dev_ptr(d_clip_counts))
+            _contexts(decimators, n), n, _dev_ptrs(d_ins, n), _longs(in_pitches, n), _ints(n_ins, n), _dev_ptrs(d_outs, n), _longs(out_pitches, n),
+            1 if from_start else 0, _dev_ptr(d_clip_counts))
         if rc < 0:
             raise RuntimeError("decimateProcessClipsPlanarLEDevice failed")
         return rc
@@ -964,42 +989,25 @@ def _bind(width):
 
         def __call__(self, x, lengths=None):
             import torch
-            if x.dim() == 2:
-                x = x.unsqueeze(0)
-            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
-                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
-            if x.shape[2] and x.stride(2) != 1:
-                x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
-            B, Cn, T = x.shape
-            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
-                raise ValueError("lengths: one entry per clip, 0 .. T")
-            while len(self.pool) < min(B, self.max_batch):
-                self.pool.append(Decimator(*self._init))
+            x, B, Cn, T, lengths = _clip_input(x, self.channels, lengths)
             stream = torch.cuda.current_stream(x.device).cuda_stream
-            for d in self.pool[:min(B, self.max_batch)]:
-                d.set_stream(stream)
+            _pool_ready(self.pool, min(B, self.max_batch), lambda: Decimator(*self._init), stream)
             pcm = torch.zeros(B, Cn, T * self.nbytes, dtype=torch.uint8, device=x.device)
-            size = x.element_size()
-            xp, pp = x.data_ptr(), pcm.data_ptr()
-            in_pitch, out_pitch = (x.stride(1), pcm.stride(1)) if Cn > 1 else (0, 0)     # (one channel: the same call in either layout)
+            (xs, in_pitch), (ps, out_pitch) = _clip_ptrs(x), _clip_ptrs(pcm)
             counts = torch.empty(B, dtype=torch.int64, device=x.device)     # (every entry is set by the call that takes its clip)
             self.launches = 0
-            for b0 in range(0, B, self.max_batch):
-                idx = range(b0, min(B, b0 + self.max_batch))
+            for rows in _chunks(B, self.max_batch):
+                k = rows.stop - rows.start
                 self.launches += decimate_clips_planar_device(
-                    self.pool[:len(idx)], [xp + i * x.stride(0) * size for i in idx], [in_pitch] * len(idx), [lengths[i] for i in idx],
-                    [pp + i * pcm.stride(0) for i in idx], [out_pitch] * len(idx), from_start=True,
-                    d_clip_counts=counts.data_ptr() + 8 * b0)
+                    self.pool[:k], xs[rows], [in_pitch] * k, lengths[rows], ps[rows], [out_pitch] * k, from_start=True,
+                    d_clip_counts=counts.data_ptr() + 8 * rows.start)
             return pcm, counts.cpu()
 
     def biquad_batch_device(banks, d_bufs, frames):
         """biquadBankApplyBatchInterleavedDevice over a list of BiquadBank objects: one launch per section count for the banks on
         the first one's stream.  Returns the launch count (raises if the call returned -1)."""
         n = len(banks)
-        rc = lib().biquadBankApplyBatchInterleavedDevice(
-            (C.c_void_p * n)(*[b.p for b in banks]), n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_bufs]),
-            (C.c_int * n)(*[int(v) for v in frames]))
+        rc = lib().biquadBankApplyBatchInterleavedDevice(_contexts(banks, n), n, _dev_ptrs(d_bufs, n), _ints(frames, n))
         if rc < 0:
             raise RuntimeError("biquadBankApplyBatchInterleavedDevice failed")
         return rc
@@ -1009,9 +1017,7 @@ def _bind(width):
         samples; 0: that item is interleaved; None for the list: every item is).  Returns the launch count (raises if the call
         returned -1)."""
         n = len(banks)
-        rc = lib().biquadBankApplyBatchPlanarDevice(
-            (C.c_void_p * n)(*[b.p for b in banks]), n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_bufs]),
-            None if pitches is None else (C.c_long * n)(*[int(q) for q in pitches]), (C.c_int * n)(*[int(v) for v in frames]))
+        rc = lib().biquadBankApplyBatchPlanarDevice(_contexts(banks, n), n, _dev_ptrs(d_bufs, n), _longs(pitches, n), _ints(frames, n))
         if rc < 0:
             raise RuntimeError("biquadBankApplyBatchPlanarDevice failed")
         return rc
@@ -1021,10 +1027,8 @@ def _bind(width):
         launch and three launches per section count and layout, whatever the number of banks).  from_start: every bank as after its
         reset(), without a copy per bank.  Returns the launch count (raises if the call returned -1)."""
         n = len(banks)
-        rc = lib().biquadBankApplyClipsPlanarDevice(
-            (C.c_void_p * n)(*[b.p for b in banks]), n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_bufs]),
-            None if pitches is None else (C.c_long * n)(*[int(q) for q in pitches]), (C.c_int * n)(*[int(v) for v in frames]),
-            1 if from_start else 0)
+        rc = lib().biquadBankApplyClipsPlanarDevice(_contexts(banks, n), n, _dev_ptrs(d_bufs, n), _longs(pitches, n), _ints(frames, n),
+                                                    1 if from_start else 0)
         if rc < 0:
             raise RuntimeError("biquadBankApplyClipsPlanarDevice failed")
         return rc
@@ -1036,10 +1040,8 @@ def _bind(width):
         one list per side.  The banks are only read, and one may be listed any number of times.  Returns the launch count (raises if
         the call returned -1)."""
         n = len(banks)
-        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
         rc = lib().biquadBankFilterClipsPlanarDevice(
-            (C.c_void_p * n)(*[b.p for b in banks]), n, (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), pitches(in_pitches),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches), (C.c_int * n)(*[int(v) for v in frames]),
+            _contexts(banks, n), n, _dev_ptrs(d_ins, n), _longs(in_pitches, n), _dev_ptrs(d_outs, n), _longs(out_pitches, n), _ints(frames, n),
             1 if reversed else 0)
         if rc < 0:
             raise RuntimeError("biquadBankFilterClipsPlanarDevice failed")
@@ -1047,48 +1049,38 @@ def _bind(width):
 
     def _clip_filter_rows(bank, src, dst, lengths, reversed):
         """one biquad_filter_clips_planar_device call on the rows of src [B, C, T] into those of dst, `bank` listed B times"""
-        B, Cn, _ = src.shape
-        size = src.element_size()
-        src_pitch, dst_pitch = (src.stride(1), dst.stride(1)) if Cn > 1 else (0, 0)     # (one channel: the same call in either layout)
-        return biquad_filter_clips_planar_device(
-            [bank] * B, [src.data_ptr() + i * src.stride(0) * size for i in range(B)], [src_pitch] * B,
-            [dst.data_ptr() + i * dst.stride(0) * size for i in range(B)], [dst_pitch] * B, lengths, reversed=reversed)
+        B = src.shape[0]
+        (src_ptrs, src_pitch), (dst_ptrs, dst_pitch) = _clip_ptrs(src), _clip_ptrs(dst)
+        return biquad_filter_clips_planar_device([bank] * B, src_ptrs, [src_pitch] * B, dst_ptrs, [dst_pitch] * B, lengths, reversed=reversed)
 
-    def _rows_apart(t):
-        """frames of a channel consecutive, planes and clips apart: what the planar entries take as it is"""
-        B, Cn, T = t.shape
-        return not ((T and t.stride(2) != 1) or (Cn > 1 and t.stride(1) < T) or (B > 1 and t.stride(0) < max(Cn * T, 1)))
+    def _sections_designed(sections):
+        """[("lowpass" | "highpass", frequency), ...], one to four -> [BiquadCoefficients] as biquad_lowpass / biquad_highpass design them"""
+        sections = list(sections)
+        if not 1 <= len(sections) <= 4 or any(kind not in ("lowpass", "highpass") for kind, _ in sections):
+            raise ValueError('sections: one to four of ("lowpass" | "highpass", frequency)')
+        L, designed = lib(), []
+        for kind, freq in sections:
+            designed.append(BiquadCoefficients())
+            (L.biquad_lowpass if kind == "lowpass" else L.biquad_highpass)(C.byref(designed[-1]), float(freq))
+        return designed
 
-    def _clip_filter_grad():
-        """the torch.autograd.Function that attaches a ClipFilter's out-of-place output to the graph (made on first use: torch is
-        imported late)"""
-        if "filter_grad" not in _state:
-            import torch
+    def _clip_filter_forward(ctx, x, y, clip, lengths):
+        ctx.clip, ctx.lengths = clip, lengths
+        return y.view_as(y)
 
-            class ClipFilterGrad(torch.autograd.Function):
-                @staticmethod
-                def forward(ctx, x, y, clip, lengths):
-                    ctx.clip, ctx.lengths = clip, lengths
-                    return y.view_as(y)
+    def _clip_filter_backward(ctx, gy):
+        import torch
+        clip, lengths = ctx.clip, ctx.lengths
+        if not clip.pool:
+            raise RuntimeError("the ClipFilter was closed before backward")
+        if not _rows_apart(gy):
+            gy = gy.contiguous()
+        gx = _out_of_place(gy, lengths)                           # (the gradient at and past lengths[i] goes through as the frames did)
+        clip.pool[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
+        _clip_filter_rows(clip.pool[0], gy, gx, lengths, True)
+        return gx, None, None, None
 
-                @staticmethod
-                @torch.autograd.function.once_differentiable
-                def backward(ctx, gy):
-                    clip, lengths = ctx.clip, ctx.lengths
-                    if not clip.pool:
-                        raise RuntimeError("the ClipFilter was closed before backward")
-                    if not _rows_apart(gy):
-                        gy = gy.contiguous()
-                    T = gy.shape[2]
-                    # frames at and past lengths[i] went through as they were: so does their gradient
-                    gx = gy.clone(memory_format=torch.contiguous_format) if any(v < T for v in lengths) else \
-                        torch.empty(gy.shape, dtype=gy.dtype, device=gy.device)
-                    clip.pool[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
-                    _clip_filter_rows(clip.pool[0], gy, gx, lengths, True)
-                    return gx, None, None, None
-
-            _state["filter_grad"] = ClipFilterGrad
-        return _state["filter_grad"]
+    _clip_filter_grad = _grad_function("ClipFilterGrad", _clip_filter_forward, _clip_filter_backward)
 
     class ClipFilter:
         """Whole clips, channels-first, through a cascade of one to four second-order sections, IN PLACE: x [B, C, T] (or [C, T]) on the
@@ -1107,15 +1099,11 @@ def _bind(width):
         after close().  A non-contiguous x is taken through .contiguous() on this path."""
 
         def __init__(self, channels, sections, max_batch=1024):
-            sections = list(sections)
-            if not 1 <= len(sections) <= 4 or any(kind not in ("lowpass", "highpass") for kind, _ in sections):
-                raise ValueError('sections: one to four of ("lowpass" | "highpass", frequency)')
-            self.channels, self.nsections, self.max_batch = channels, len(sections), max(1, int(max_batch))
+            designed = _sections_designed(sections)
+            self.channels, self.nsections, self.max_batch = channels, len(designed), max(1, int(max_batch))
             L = lib()
             self._sections = (Biquad * (channels * self.nsections))()
-            for s, (kind, freq) in enumerate(sections):
-                co = BiquadCoefficients()
-                (L.biquad_lowpass if kind == "lowpass" else L.biquad_highpass)(C.byref(co), float(freq))
+            for s, co in enumerate(designed):
                 for c in range(channels):
                     L.biquad_init(C.byref(self._sections[c * self.nsections + s]), C.byref(co), 1.0)
             self.pool = []
@@ -1129,54 +1117,27 @@ def _bind(width):
         def __call__(self, x, lengths=None):
             import torch
             whole = x
-            if x.dim() == 2:
-                x = x.unsqueeze(0)
-            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
-                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
             tracked = x.requires_grad and torch.is_grad_enabled()
-            if x.shape[2] and x.stride(2) != 1 and not tracked:
-                raise ValueError("in place: the frames of a channel must be consecutive (stride 1 along T)")
-            B, Cn, T = x.shape
-            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
-                raise ValueError("lengths: one entry per clip, 0 .. T")
+            # (in place a stride along T is refused: there is no copy to write back; a tracked x is taken through _rows_apart below)
+            x, B, Cn, T, lengths = _clip_input(x, self.channels, lengths, strided="keep" if tracked else "refuse")
+            make = lambda: BiquadBank(self._sections, Cn, self.nsections)
+            stream = torch.cuda.current_stream(x.device).cuda_stream
             if tracked:
                 # out of place, for autograd: x and everything the graph saved stay as they are
-                if not self.pool:
-                    self.pool.append(BiquadBank(self._sections, Cn, self.nsections))
-                self.pool[0].set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+                _pool_ready(self.pool, 1, make, stream)
                 src = x if _rows_apart(x) else x.contiguous()
                 with torch.no_grad():
-                    y = src.clone(memory_format=torch.contiguous_format) if any(v < T for v in lengths) else \
-                        torch.empty(src.shape, dtype=src.dtype, device=src.device)
+                    y = _out_of_place(src, lengths)
                     self.launches = _clip_filter_rows(self.pool[0], src, y, lengths, False) if B else 0
                 y = _clip_filter_grad().apply(src, y, self, lengths)
                 return y[0] if whole.dim() == 2 else y
-            while len(self.pool) < min(B, self.max_batch):
-                self.pool.append(BiquadBank(self._sections, Cn, self.nsections))
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            for b in self.pool[:min(B, self.max_batch)]:
-                b.set_stream(stream)
-            size, xp = x.element_size(), x.data_ptr()
-            pitch = x.stride(1) if Cn > 1 else 0                  # (one channel: the same call in either layout)
+            _pool_ready(self.pool, min(B, self.max_batch), make, stream)
+            xs, pitch = _clip_ptrs(x)
             self.launches = 0
-            for b0 in range(0, B, self.max_batch):
-                idx = range(b0, min(B, b0 + self.max_batch))
-                pool = self.pool[:len(idx)]
-                self.launches += biquad_clips_planar_device(pool, [xp + i * x.stride(0) * size for i in idx], [pitch] * len(idx),
-                                                            [lengths[i] for i in idx], from_start=True)
+            for rows in _chunks(B, self.max_batch):
+                k = rows.stop - rows.start
+                self.launches += biquad_clips_planar_device(self.pool[:k], xs[rows], [pitch] * k, lengths[rows], from_start=True)
             return whole
-
-    def _plane_ptrs(t):
-        """addresses of the planes of t [..., T] (frames consecutive) as a numpy array of t's leading shape"""
-        at = np.zeros(tuple(t.shape[:-1]), np.int64)
-        for d in range(t.dim() - 1):
-            at = at + (np.arange(t.shape[d], dtype=np.int64) * t.stride(d)).reshape([-1 if k == d else 1 for k in range(t.dim() - 1)])
-        return t.data_ptr() + at * t.element_size()
-
-    def _clip_ptrs(t):
-        """addresses of the clips of t [..., C, T] and the pitch the planar entries take for them (0: one channel)"""
-        return _plane_ptrs(t)[..., 0], (t.stride(-2) if t.shape[-2] > 1 else 0)
 
     class _BiquadBankSet:
         """the banks one set of ClipBiquad coefficient values needs, made on first use: the whole cascade; for the coefficient
@@ -1209,81 +1170,68 @@ def _bind(width):
                 b.close()
             self.banks = {}
 
-    def _clip_biquad_grad():
-        """the torch.autograd.Function of ClipBiquad (made on first use: torch is imported late)"""
-        if "biquad_grad" not in _state:
-            import torch
+    def _clip_biquad_forward(ctx, x, coefficients, y, kept, clip, banks, lengths):
+        ctx.clip, ctx.banks, ctx.lengths, ctx.generation, ctx.co = clip, banks, lengths, clip._generation, coefficients
+        ctx.save_for_backward(x, y, kept)
+        return y.view_as(y)
 
-            class ClipBiquadGrad(torch.autograd.Function):
-                @staticmethod
-                def forward(ctx, x, coefficients, y, kept, clip, banks, lengths):
-                    ctx.clip, ctx.banks, ctx.lengths, ctx.generation, ctx.co = clip, banks, lengths, clip._generation, coefficients
-                    ctx.save_for_backward(x, y, kept)
-                    return y.view_as(y)
+    def _clip_biquad_backward(ctx, gy):
+        import torch
+        clip, banks, lengths = ctx.clip, ctx.banks, ctx.lengths
+        if clip._generation != ctx.generation:
+            raise RuntimeError("the ClipBiquad was closed before backward")
+        x, y, kept = ctx.saved_tensors
+        need_x, need_co = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not _rows_apart(gy):
+            gy = gy.contiguous()
+        B, Cn, T = gy.shape
+        S = banks.nsections
+        stream = torch.cuda.current_stream(gy.device).cuda_stream
+        gx = _out_of_place(gy, lengths) if need_x else None      # (the gradient at and past lengths[i] goes through as the frames did)
+        gy_ptrs, gy_pitch = _clip_ptrs(gy)
+        clip.backward_launches = [0, 0, 0]
+        if not need_co:
+            banks.bank("full").set_stream(stream)
+            clip.backward_launches[0] = _clip_filter_rows(banks.bank("full"), gy, gx, lengths, True) if B else 0
+            return gx, None, None, None, None, None, None
+        # g_s, s = 0 .. S-1: grad_y through the reversed sections s+1 .. S (g_0 is grad_x; g_S is grad_y itself)
+        g = torch.empty((max(S - 1, 0), B, Cn, T), dtype=gy.dtype, device=gy.device)
+        outs = ([(0, gx)] if need_x else []) + [(s, g[s - 1]) for s in range(1, S)]
+        if outs and B:
+            call = [banks.bank("suffix", s) for s, _ in outs for _ in range(B)]
+            call[0].set_stream(stream)
+            optr = np.concatenate([_clip_ptrs(o)[0] for _, o in outs])
+            pitch = [gy_pitch] * len(call)
+            clip.backward_launches[0] = biquad_filter_clips_planar_device(
+                call, np.tile(gy_ptrs, len(outs)), pitch, optr, [T if Cn > 1 else 0] * len(call), lengths * len(outs), reversed=True)
+        # u_s, s = 1 .. S: g_s through the all-pole part of section s, reversed
+        u = torch.empty((S, B, Cn, T), dtype=gy.dtype, device=gy.device)
+        sums = torch.zeros((B, Cn, S, 9), dtype=torch.float64, device=gy.device)
+        if B:
+            call = [banks.bank("pole", s) for s in range(1, S + 1) for _ in range(B)]
+            call[0].set_stream(stream)
+            iptr = np.concatenate([_clip_ptrs(g[s - 1])[0] for s in range(1, S)] + [gy_ptrs])
+            ipitch = [T if Cn > 1 else 0] * ((S - 1) * B) + [gy_pitch] * B
+            clip.backward_launches[1] = biquad_filter_clips_planar_device(
+                call, iptr, ipitch, _plane_ptrs(u)[..., 0].reshape(-1), [T if Cn > 1 else 0] * (S * B), lengths * S, reversed=True)
+            # the lagged sums: per clip, channel and section (u_s, y_{s-1}, lags 0..4) and (u_s, y_s, lags 1..4)
+            up = _plane_ptrs(u).transpose(1, 2, 0)                                     # [B, C, S]
+            ys = [_plane_ptrs(x)] + [_plane_ptrs(kept[s]) for s in range(S - 1)] + [_plane_ptrs(y)]
+            before, after = np.stack(ys[:-1], axis=-1), np.stack(ys[1:], axis=-1)      # y_{s-1}, y_s: [B, C, S]
+            sp = _plane_ptrs(sums)
+            frames = np.broadcast_to(np.asarray(lengths, np.int64).reshape(B, 1, 1), (B, Cn, S))
+            rows = lambda a, b: np.concatenate([a.reshape(-1), b.reshape(-1)])
+            count = B * Cn * S
+            clip.backward_launches[2] = lag_products_batch_device(
+                rows(up, up), rows(before, after), rows(frames, frames), [0] * count + [1] * count, [5] * count + [4] * count,
+                rows(sp, sp + 5 * 8), stream=stream)
+        sums = sums.sum(0)
+        if ctx.co.dim() == 2:
+            sums = sums.sum(0)
+        sums[..., 5:] = -sums[..., 5:]
+        return gx, sums.to(dtype=ctx.co.dtype).to(ctx.co.device), None, None, None, None, None
 
-                @staticmethod
-                @torch.autograd.function.once_differentiable
-                def backward(ctx, gy):
-                    clip, banks, lengths = ctx.clip, ctx.banks, ctx.lengths
-                    if clip._generation != ctx.generation:
-                        raise RuntimeError("the ClipBiquad was closed before backward")
-                    x, y, kept = ctx.saved_tensors
-                    need_x, need_co = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-                    if not _rows_apart(gy):
-                        gy = gy.contiguous()
-                    B, Cn, T = gy.shape
-                    S = banks.nsections
-                    stream = torch.cuda.current_stream(gy.device).cuda_stream
-                    gx = None
-                    if need_x:
-                        # frames at and past lengths[i] went through as they were: so does their gradient
-                        gx = gy.clone(memory_format=torch.contiguous_format) if any(v < T for v in lengths) else \
-                            torch.empty(gy.shape, dtype=gy.dtype, device=gy.device)
-                    gy_ptrs, gy_pitch = _clip_ptrs(gy)
-                    clip.backward_launches = [0, 0, 0]
-                    if not need_co:
-                        banks.bank("full").set_stream(stream)
-                        clip.backward_launches[0] = _clip_filter_rows(banks.bank("full"), gy, gx, lengths, True) if B else 0
-                        return gx, None, None, None, None, None, None
-                    # g_s, s = 0 .. S-1: grad_y through the reversed sections s+1 .. S (g_0 is grad_x; g_S is grad_y itself)
-                    g = torch.empty((max(S - 1, 0), B, Cn, T), dtype=gy.dtype, device=gy.device)
-                    outs = ([(0, gx)] if need_x else []) + [(s, g[s - 1]) for s in range(1, S)]
-                    if outs and B:
-                        call = [banks.bank("suffix", s) for s, _ in outs for _ in range(B)]
-                        call[0].set_stream(stream)
-                        optr = np.concatenate([_clip_ptrs(o)[0] for _, o in outs])
-                        pitch = [gy_pitch] * len(call)
-                        clip.backward_launches[0] = biquad_filter_clips_planar_device(
-                            call, np.tile(gy_ptrs, len(outs)), pitch, optr, [T if Cn > 1 else 0] * len(call), lengths * len(outs), reversed=True)
-                    # u_s, s = 1 .. S: g_s through the all-pole part of section s, reversed
-                    u = torch.empty((S, B, Cn, T), dtype=gy.dtype, device=gy.device)
-                    sums = torch.zeros((B, Cn, S, 9), dtype=torch.float64, device=gy.device)
-                    if B:
-                        call = [banks.bank("pole", s) for s in range(1, S + 1) for _ in range(B)]
-                        call[0].set_stream(stream)
-                        iptr = np.concatenate([_clip_ptrs(g[s - 1])[0] for s in range(1, S)] + [gy_ptrs])
-                        ipitch = [T if Cn > 1 else 0] * ((S - 1) * B) + [gy_pitch] * B
-                        clip.backward_launches[1] = biquad_filter_clips_planar_device(
-                            call, iptr, ipitch, _clip_ptrs(u)[0].reshape(-1), [T if Cn > 1 else 0] * (S * B), lengths * S, reversed=True)
-                        # the lagged sums: per clip, channel and section (u_s, y_{s-1}, lags 0..4) and (u_s, y_s, lags 1..4)
-                        up = _plane_ptrs(u).transpose(1, 2, 0)                                     # [B, C, S]
-                        ys = [_plane_ptrs(x)] + [_plane_ptrs(kept[s]) for s in range(S - 1)] + [_plane_ptrs(y)]
-                        before, after = np.stack(ys[:-1], axis=-1), np.stack(ys[1:], axis=-1)      # y_{s-1}, y_s: [B, C, S]
-                        sp = _plane_ptrs(sums)
-                        frames = np.broadcast_to(np.asarray(lengths, np.int64).reshape(B, 1, 1), (B, Cn, S))
-                        rows = lambda a, b: np.concatenate([a.reshape(-1), b.reshape(-1)])
-                        count = B * Cn * S
-                        clip.backward_launches[2] = lag_products_batch_device(
-                            rows(up, up), rows(before, after), rows(frames, frames), [0] * count + [1] * count, [5] * count + [4] * count,
-                            rows(sp, sp + 5 * 8), stream=stream)
-                    sums = sums.sum(0)
-                    if ctx.co.dim() == 2:
-                        sums = sums.sum(0)
-                    sums[..., 5:] = -sums[..., 5:]
-                    return gx, sums.to(dtype=ctx.co.dtype).to(ctx.co.device), None, None, None, None, None
-
-            _state["biquad_grad"] = ClipBiquadGrad
-        return _state["biquad_grad"]
+    _clip_biquad_grad = _grad_function("ClipBiquadGrad", _clip_biquad_forward, _clip_biquad_backward)
 
     class ClipBiquad:
         """Whole clips, channels-first, through a cascade of one to four sections whose COEFFICIENTS can be learnt: x [B, C, T] (or
@@ -1330,15 +1278,7 @@ def _bind(width):
             """[("lowpass" | "highpass", frequency), ...] -> tensor [S, 9] of the build's dtype (on the CPU; needs no GPU): the values
             ClipFilter builds for the same sections"""
             import torch
-            sections = list(sections)
-            if not 1 <= len(sections) <= 4 or any(kind not in ("lowpass", "highpass") for kind, _ in sections):
-                raise ValueError('sections: one to four of ("lowpass" | "highpass", frequency)')
-            L = lib()
-            rows = []
-            for kind, freq in sections:
-                co = BiquadCoefficients()
-                (L.biquad_lowpass if kind == "lowpass" else L.biquad_highpass)(C.byref(co), float(freq))
-                rows.append([getattr(co, n) for n, _ in BiquadCoefficients._fields_])
+            rows = [[getattr(co, n) for n, _ in BiquadCoefficients._fields_] for co in _sections_designed(sections)]
             return torch.tensor(rows, dtype=getattr(torch, smp_torch))
 
         def close(self):
@@ -1362,14 +1302,7 @@ def _bind(width):
         def __call__(self, x, lengths=None):
             import torch
             whole = x
-            if x.dim() == 2:
-                x = x.unsqueeze(0)
-            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
-                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
-            B, Cn, T = x.shape
-            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
-                raise ValueError("lengths: one entry per clip, 0 .. T")
+            x, B, Cn, T, lengths = _clip_input(x, self.channels, lengths, strided="keep")     # (the rows: _rows_apart below)
             banks = self._bank_set()
             S = banks.nsections
             grad = torch.is_grad_enabled()
@@ -1377,8 +1310,7 @@ def _bind(width):
             stream = torch.cuda.current_stream(x.device).cuda_stream
             src = x if _rows_apart(x) else x.contiguous()
             with torch.no_grad():
-                y = src.clone(memory_format=torch.contiguous_format) if any(v < T for v in lengths) else \
-                    torch.empty(src.shape, dtype=src.dtype, device=src.device)
+                y = _out_of_place(src, lengths)
                 kept = None
                 self.launches = 0
                 if not track_co:
@@ -1426,12 +1358,10 @@ def _bind(width):
         may be None with n_ins 0).  out_caps in frames, at least artamdStretchClipCapacity each.  from_start: every context first put
         where stretchInit left it.  Returns the frames made per clip (raises if the call returned -1)."""
         n = len(ctxs)
-        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
         produced = (C.c_int * max(n, 1))()
         rc = lib().stretchProcessAndFlushBatchPlanarDevice(
-            (C.c_void_p * n)(*[c.p for c in ctxs]), n, (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_ins]), pitches(in_pitches),
-            (C.c_int * n)(*[int(v) for v in n_ins]), (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches),
-            (C.c_int * n)(*[int(v) for v in out_caps]), (C.c_double * n)(*[float(v) for v in ratios]), 1 if from_start else 0, produced)
+            _contexts(ctxs, n), n, _dev_ptrs(d_ins, n), _longs(in_pitches, n), _ints(n_ins, n), _dev_ptrs(d_outs, n), _longs(out_pitches, n),
+            _ints(out_caps, n), _doubles(ratios, n), 1 if from_start else 0, produced)
         if rc < 0:
             raise RuntimeError("stretchProcessAndFlushBatchPlanarDevice failed")
         return list(produced[:n])
@@ -1444,14 +1374,10 @@ def _bind(width):
         for a single stage), log_caps: per clip a pair of capacities in segments, at least artamdStretchLogCapacity each.  Returns
         (frames made per clip, (segments of stage 1, of stage 2) per clip); raises if the call returned -1."""
         n = len(ctxs)
-        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
         produced, counts = (C.c_int * max(n, 1))(), (C.c_int * max(2 * n, 1))()
         rc = lib().stretchProcessAndFlushLoggedBatchPlanarDevice(
-            (C.c_void_p * n)(*[c.p for c in ctxs]), n, (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_ins]), pitches(in_pitches),
-            (C.c_int * n)(*[int(v) for v in n_ins]), (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), pitches(out_pitches),
-            (C.c_int * n)(*[int(v) for v in out_caps]), (C.c_double * n)(*[float(v) for v in ratios]), produced,
-            (C.c_void_p * (2 * n))(*[None if d is None else _dev_ptr(d) for pair in d_logs for d in pair]),
-            (C.c_int * (2 * n))(*[int(v) for pair in log_caps for v in pair]), counts)
+            _contexts(ctxs, n), n, _dev_ptrs(d_ins, n), _longs(in_pitches, n), _ints(n_ins, n), _dev_ptrs(d_outs, n), _longs(out_pitches, n),
+            _ints(out_caps, n), _doubles(ratios, n), produced, _dev_ptrs(_flat(d_logs), 2 * n), _ints(_flat(log_caps), 2 * n), counts)
         if rc < 0:
             raise RuntimeError("stretchProcessAndFlushLoggedBatchPlanarDevice failed")
         return list(produced[:n]), [(counts[2 * i], counts[2 * i + 1]) for i in range(n)]
@@ -1462,51 +1388,30 @@ def _bind(width):
         applied to the first n_outs[i] frames of d_gouts[i]; pitches as in stretch_clips_batch_planar_device.  The contexts are only read,
         and one may be listed any number of times.  Returns the launch count (raises if the call returned -1)."""
         n = len(ctxs)
-        pitches = lambda v: None if v is None else (C.c_long * n)(*[int(q) for q in v])
         rc = lib().stretchAdjointClipsPlanarDevice(
-            (C.c_void_p * n)(*[c.p for c in ctxs]), n,
-            (C.c_void_p * (2 * n))(*[None if d is None else _dev_ptr(d) for pair in d_logs for d in pair]),
-            (C.c_int * (2 * n))(*[int(v) for pair in log_counts for v in pair]),
-            (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_gouts]), pitches(gout_pitches), (C.c_int * n)(*[int(v) for v in n_outs]),
-            (C.c_void_p * n)(*[None if d is None else _dev_ptr(d) for d in d_gins]), pitches(gin_pitches), (C.c_int * n)(*[int(v) for v in n_ins]))
+            _contexts(ctxs, n), n, _dev_ptrs(_flat(d_logs), 2 * n), _ints(_flat(log_counts), 2 * n),
+            _dev_ptrs(d_gouts, n), _longs(gout_pitches, n), _ints(n_outs, n), _dev_ptrs(d_gins, n), _longs(gin_pitches, n), _ints(n_ins, n))
         if rc < 0:
             raise RuntimeError("stretchAdjointClipsPlanarDevice failed")
         return rc
 
-    def _clip_stretch_grad():
-        """the torch.autograd.Function that attaches a ClipStretcher's output to the graph (made on first use: torch is imported late)"""
-        if "stretch_grad" not in _state:
-            import torch
+    def _clip_stretch_forward(ctx, x, y, clip, record):
+        ctx.clip, ctx.record, ctx.x_shape = clip, record, x.shape
+        return y.view_as(y)
 
-            class ClipStretchGrad(torch.autograd.Function):
-                @staticmethod
-                def forward(ctx, x, y, clip, record):
-                    ctx.clip, ctx.record, ctx.x_shape = clip, record, x.shape
-                    return y.view_as(y)
+    def _clip_stretch_backward(ctx, gy):
+        import torch
+        owners, logs, counts, lengths, made, _ = ctx.record   # (logs: addresses inside the device tensor the record keeps alive)
+        if any(o.p is None for o in owners):
+            raise RuntimeError("the ClipStretcher was closed before backward")
+        if not owners:                                        # (no clip: no context to take a stream from)
+            return torch.zeros(ctx.x_shape, dtype=gy.dtype, device=gy.device), None, None, None
+        gx, (gy_ptrs, gy_pitches, gx_ptrs, gx_pitches) = _clip_backward(ctx.x_shape, gy, _rows_apart, owners[0])
+        stretch_adjoint_clips_planar_device(owners, logs, counts, gy_ptrs, gy_pitches, [min(m, gy.shape[2]) for m in made],
+                                            gx_ptrs, gx_pitches, lengths)
+        return gx, None, None, None
 
-                @staticmethod
-                @torch.autograd.function.once_differentiable
-                def backward(ctx, gy):
-                    clip = ctx.clip
-                    owners, logs, counts, lengths, made, _ = ctx.record   # (logs: addresses inside the device tensor the record keeps alive)
-                    B, Cn, T = ctx.x_shape
-                    if any(o.p is None for o in owners):
-                        raise RuntimeError("the ClipStretcher was closed before backward")
-                    if not _rows_apart(gy):
-                        gy = gy.contiguous()
-                    gx = torch.zeros(B, Cn, T, dtype=gy.dtype, device=gy.device)     # (zero at and past lengths[i])
-                    if B:
-                        owners[0].set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
-                        size = gy.element_size()
-                        gy_pitch, gx_pitch = (gy.stride(1), gx.stride(1)) if Cn > 1 else (0, 0)
-                        stretch_adjoint_clips_planar_device(
-                            owners, logs, counts, [gy.data_ptr() + i * gy.stride(0) * size for i in range(B)], [gy_pitch] * B,
-                            [min(m, gy.shape[2]) for m in made],
-                            [gx.data_ptr() + i * gx.stride(0) * size for i in range(B)], [gx_pitch] * B, lengths)
-                    return gx, None, None, None
-
-            _state["stretch_grad"] = ClipStretchGrad
-        return _state["stretch_grad"]
+    _clip_stretch_grad = _grad_function("ClipStretchGrad", _clip_stretch_forward, _clip_stretch_backward)
 
     class ClipStretcher:
         """Whole clips, channels-first, stretched in time without a change of pitch: x [B, C, T] (or [C, T]) on the GPU and a ratio
@@ -1555,18 +1460,9 @@ def _bind(width):
 
         def __call__(self, x, ratio, lengths=None):
             import torch
-            if x.dim() == 2:
-                x = x.unsqueeze(0)
-            if x.dim() != 3 or x.shape[1] != self.channels or not x.is_cuda or x.dtype != getattr(torch, smp_torch):
-                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
-            if x.shape[2] and x.stride(2) != 1:
-                x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
-            B, Cn, T = x.shape
+            x, B, Cn, T, lengths = _clip_input(x, self.channels, lengths)
             if Cn > 1 and x.stride(1) < T:
                 x = x.contiguous()                                # (a broadcast channel dimension: a pitch of 0 would mean interleaved)
-            lengths = [T] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lengths) != B or any(v < 0 or v > T for v in lengths):
-                raise ValueError("lengths: one entry per clip, 0 .. T")
             if hasattr(ratio, "tolist"):
                 ratio = ratio.tolist()
             ratios = [float(v) for v in ratio] if isinstance(ratio, (list, tuple)) else [float(ratio)] * B
@@ -1602,21 +1498,16 @@ def _bind(width):
                 counts = [(0, 0)] * B
             stream = torch.cuda.current_stream(x.device).cuda_stream
             y = torch.zeros(B, Cn, max(rooms, default=0), dtype=x.dtype, device=x.device)
-            size = x.element_size()
-            xp, yp = x.data_ptr(), y.data_ptr()
-            in_pitch, out_pitch = (x.stride(1), y.stride(1)) if Cn > 1 else (0, 0)      # (one channel: the same call in either layout)
+            (xs, in_pitch), (ys, out_pitch) = _clip_ptrs(x), _clip_ptrs(y)
             made = [0] * B
             for flags, idx in groups.items():
                 pool = self.pools.setdefault(flags, [])
-                while len(pool) < min(len(idx), self.max_batch):
-                    pool.append(Stretcher(self.shortest, self.longest, Cn, flags))
-                for s in pool[:min(len(idx), self.max_batch)]:
-                    s.set_stream(stream)
-                for b0 in range(0, len(idx), self.max_batch):
-                    part = idx[b0:b0 + self.max_batch]
-                    args = (pool[:len(part)], [xp + i * x.stride(0) * size for i in part], [in_pitch] * len(part), [lengths[i] for i in part],
-                            [yp + i * y.stride(0) * size for i in part], [out_pitch] * len(part), [rooms[i] for i in part],
-                            [ratios[i] for i in part])
+                _pool_ready(pool, min(len(idx), self.max_batch), lambda: Stretcher(self.shortest, self.longest, Cn, flags), stream)
+                for rows in _chunks(len(idx), self.max_batch):
+                    part = idx[rows]
+                    k = len(part)
+                    args = (pool[:k], [xs[i] for i in part], [in_pitch] * k, [lengths[i] for i in part],
+                            [ys[i] for i in part], [out_pitch] * k, [rooms[i] for i in part], [ratios[i] for i in part])
                     if logged:
                         got, cnt = stretch_clips_logged_batch_planar_device(*args, [log_ptrs[i] for i in part], [caps[i] for i in part])
                         for i, c in zip(part, cnt):
@@ -1645,11 +1536,8 @@ def _bind(width):
         counts[i]), all in one launch on `stream` (a torch stream, a raw address or None: the null stream).  Returns the launch
         count (raises if the call returned -1)."""
         n = len(d_ins)
-        st = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
-        rc = lib().floatIntegersBatchLEDevice(
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_ins]), (C.c_double * n)(*[float(v) for v in gains]),
-            (C.c_int * n)(*[int(v) for v in bits]), (C.c_int * n)(*[int(v) for v in nbytes]), (C.c_int * n)(*[int(v) for v in strides]),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), (C.c_int * n)(*[int(v) for v in counts]), n, st)
+        rc = lib().floatIntegersBatchLEDevice(_dev_ptrs(d_ins, n), _doubles(gains, n), _ints(bits, n), _ints(nbytes, n), _ints(strides, n),
+                                              _dev_ptrs(d_outs, n), _ints(counts, n), n, _raw_stream(stream))
         if rc < 0:
             raise RuntimeError("floatIntegersBatchLEDevice failed")
         return rc
@@ -1659,11 +1547,8 @@ def _bind(width):
         extras[i] samples to d_outs[i] (same stride): past the newest, or before the oldest (nearest first) where backward[i], all in
         one launch on `stream` (a torch stream, a raw address or None: the null stream).  Raises if the call returned -1."""
         n = len(d_known)
-        st = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
-        rc = lib().artamdExtrapolateBatchDevice(
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_known]), (C.c_int * n)(*[int(v) for v in counts]),
-            (C.c_int * n)(*[int(v) for v in strides]), (C.c_int * n)(*[int(bool(v)) for v in backward]),
-            (C.c_void_p * n)(*[_dev_ptr(d) for d in d_outs]), (C.c_int * n)(*[int(v) for v in extras]), n, st)
+        rc = lib().artamdExtrapolateBatchDevice(_dev_ptrs(d_known, n), _ints(counts, n), _ints(strides, n), _ints([bool(v) for v in backward], n),
+                                                _dev_ptrs(d_outs, n), _ints(extras, n), n, _raw_stream(stream))
         if rc < 0:
             raise RuntimeError("artamdExtrapolateBatchDevice failed")
         return rc
@@ -1674,13 +1559,12 @@ def _bind(width):
         torch stream, a raw address or None: the null stream).  Rows are planes with stride 1; the lists may be numpy arrays of
         addresses and counts.  Returns the launch count (raises if the call returned -1)."""
         n = len(d_us)
-        st = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
         ptrs = lambda v: np.ascontiguousarray(v if isinstance(v, np.ndarray) else [_dev_ptr(d) or 0 for d in v], dtype=np.uintp)
         ints = lambda v: np.ascontiguousarray(v, dtype=np.intc)
         keep = [ptrs(d_us), ptrs(d_vs), ints(frames), ints(first_lags), ints(num_lags), ptrs(d_sums)]
         if any(len(a) != n for a in keep):
             raise ValueError("lag_products_batch_device: one entry per row in every list")
-        rc = lib().artamdLagProductsBatchDevice(*[a.ctypes.data for a in keep[:5]], keep[5].ctypes.data, n, st)
+        rc = lib().artamdLagProductsBatchDevice(*[a.ctypes.data for a in keep[:5]], keep[5].ctypes.data, n, _raw_stream(stream))
         if rc < 0:
             raise RuntimeError("artamdLagProductsBatchDevice failed")
         return rc

@@ -445,9 +445,6 @@ static void bank_sharded_call (BiquadBank *b, artsample_t *d_buffer, long pitch,
     if (prev >= 0) arthip_set_device (prev);
 }
 
-/* a bank's call can go into launches on `lead`'s stream: an ordinary bank on the same stream and device */
-static int bank_shares_launch (const BiquadBank *b, const BiquadBank *lead) { return !b->nshards && b->stream == lead->stream && b->device == lead->device; }
-
 /* Where a call's input is set aside: *lead samples into the copy buffer, its planes the returned pitch apart (the caller's pitch
  * modulo q, the samples of 16 bytes, and at least `frames`): the copy and its every plane start at the caller's address modulo 16. */
 static long aside_placement (const void *base, long pitch, int frames, size_t *lead)
@@ -843,8 +840,23 @@ static void dec_swap_if (Decimate *cxt, int rc)
     if (rc == 1) { uint32_t *t = cxt->hip->d_gens; cxt->hip->d_gens = cxt->hip->d_gens_alt; cxt->hip->d_gens_alt = t; }
 }
 
-static int dec_reserve (Decimate *cxt, size_t in_bytes, size_t out_bytes);
-static void clip_copy_item (ArtCopyRows *it, const void *src, long src_pitch, void *dst, long dst_pitch, long width, long rows, long task0);
+/* a context's staging buffers, device and page-locked, for a call of that many bytes in and out */
+static int dec_reserve (Decimate *cxt, size_t in_bytes, size_t out_bytes)
+{
+    struct artamd_decimator *hip = cxt->hip;
+    in_bytes += 16; out_bytes += 16;                    /* (copy kernels move whole words) */
+    if (in_bytes > hip->in_cap) { arthip_free (hip->d_in); hip->in_cap = in_bytes * 2; if (!(hip->d_in = arthip_malloc (hip->in_cap))) { hip->in_cap = 0; return -1; } }
+    if (out_bytes > hip->out_cap) { arthip_free (hip->d_out); hip->out_cap = out_bytes * 2; if (!(hip->d_out = arthip_malloc (hip->out_cap))) { hip->out_cap = 0; return -1; } }
+    if (in_bytes <= DEC_KERNEL_COPY_LIMIT && in_bytes > hip->h_in_cap) {
+        arthip_host_free (hip->h_in); hip->h_in_cap = in_bytes * 2;
+        if (!(hip->h_in = arthip_host_alloc (hip->h_in_cap))) { hip->h_in_cap = 0; return -1; }
+    }
+    if (out_bytes <= DEC_KERNEL_COPY_LIMIT && out_bytes > hip->h_out_cap) {
+        arthip_host_free (hip->h_out); hip->h_out_cap = out_bytes * 2;
+        if (!(hip->h_out = arthip_host_alloc (hip->h_out_cap))) { hip->h_out_cap = 0; return -1; }
+    }
+    return 0;
+}
 
 /* a leaf context's call with a pitch on either side (0: interleaved); a one-channel context is the same call in either layout */
 static void dec_leaf_pitched (Decimate *cxt, const art_s *d_input, long in_pitch, int frames, unsigned char *d_output, long out_pitch)
@@ -950,6 +962,80 @@ void decimateHipReset (Decimate *cxt)
 }
 
 /* ------------------------------------------------------------------------------------------
+ * What the entries that gather many calls share (the decimator's batch / clips body, the biquad batch, clips and filter-clips
+ * entries below).  Each goes route -> place -> fill -> upload -> launch: the items it cannot take are made as their single calls, the
+ * others are counted into classes; every class gets a 16-byte aligned slice of ONE table, whose records are filled in place (zeroed
+ * memory: a record built elsewhere and copied in would bring its padding bytes along); every present class is launched from its slice.
+ * ---------------------------------------------------------------------------------------- */
+
+/* a call can go into launches on `lead`'s stream: an ordinary bank (context) on the same stream and device */
+static int bank_shares_launch (const BiquadBank *b, const BiquadBank *lead) { return !b->nshards && b->stream == lead->stream && b->device == lead->device; }
+static int dec_shares_launch (const struct artamd_decimator *hip, const struct artamd_decimator *lead) { return !hip->nshards && hip->stream == lead->stream && hip->device == lead->device; }
+
+/* item i's pitch on a side: 0 (interleaved) without a list, and for one channel (the same call in either layout) */
+static long item_pitch (const long *pitches, int i, int C) { return pitches && C > 1 ? pitches [i] : 0; }
+
+/* one side of a lane, channel c of an item of C channels: where it starts, in the units the side's pitch is counted in (a sample is
+ * `width` of them), and the frames between its samples */
+typedef struct { long offset; int stride; } LaneSide;
+static inline LaneSide lane_side (long pitch, int c, int C, int width) { const LaneSide s = { pitch ? c * pitch : (long) c * width, pitch ? 1 : C }; return s; }
+
+/* the next slice of a table that holds *bytes so far, for `count` records of `size` bytes: its offset; *bytes moves on to the next 16 */
+static size_t table_slice (size_t *bytes, size_t size, size_t count) { const size_t at = *bytes; *bytes += (size * count + 15) & ~(size_t) 15; return at; }
+
+/* ... and a serial class's, which holds s->count lanes: `lanes` per workgroup when forced (the measurements of the rules; 64 at most),
+ * else what `rule` gives the class; the count goes up to whole workgroups (empty lanes), *maxlanes to the most of any class */
+static void serial_slice (ArtBatchSlice *s, int lanes, int (*rule) (int), size_t lane_size, size_t *bytes, int *maxlanes)
+{
+    s->lanes = lanes > 0 ? (lanes < 64 ? lanes : 64) : rule (s->count);
+    s->count = (s->count + s->lanes - 1) / s->lanes * s->lanes;
+    if (s->count > *maxlanes) *maxlanes = s->count;
+    s->offset = table_slice (bytes, lane_size, (size_t) s->count);
+}
+
+typedef struct { int item, channel, frames; } LaneRef;
+static int lane_order (const void *pa, const void *pb)     /* longest first; then list order, channel order (a total order) */
+{
+    const LaneRef *a = pa, *b = pb;
+    if (a->frames != b->frames) return a->frames > b->frames ? -1 : 1;
+    if (a->item != b->item) return a->item < b->item ? -1 : 1;
+    return a->channel < b->channel ? -1 : a->channel > b->channel;
+}
+
+/* every channel of every item of class k (cls_of [i] == k; channels_of (items [i]) of them, frames [i] long), in that order; their number */
+static int bank_channels (const void *bank) { return ((const BiquadBank *) bank)->C; }
+static int dec_channels (const void *cxt) { return ((const Decimate *) cxt)->numChannels; }
+static int class_lanes (LaneRef *refs, int k, int n, const int *cls_of, const void *const *items, int (*channels_of) (const void *item), const int *frames)
+{
+    int m = 0;
+    for (int i = 0; i < n; ++i)
+        if (cls_of [i] == k)
+            for (int c = 0, C = channels_of (items [i]); c < C; ++c) { refs [m].item = i; refs [m].channel = c; refs [m].frames = frames [i]; ++m; }
+    qsort (refs, (size_t) m, sizeof (LaneRef), lane_order);
+    return m;
+}
+
+/* one strided copy of a grouped copy launch (arthip_copy_rows_launch) and the tasks a row of `width` words takes */
+static long copy_groups (long width) { return (width + 3) / 4 + 1; }
+static void clip_copy_item (ArtCopyRows *it, const void *src, long src_pitch, void *dst, long dst_pitch, long width, long rows, long task0)
+{
+    it->src = src; it->dst = dst; it->src_pitch = src_pitch; it->dst_pitch = dst_pitch;
+    it->width = width; it->rows = rows; it->groups = copy_groups (width); it->task0 = task0;
+}
+
+/* The tail.  The finished table goes up to the leading item's buffer for it on `stream`: the buffer is grown first (cap NULL: it has
+ * been, with the entry's scratch, whose addresses the fill needed).  0, or -1 with `failure` reported */
+static int table_to_device (const char *failure, const void *table, size_t bytes, void **d_table, size_t *cap, void *stream)
+{
+    if (cap) *d_table = arthip_grow (*d_table, cap, bytes);
+    if (*d_table && !arthip_table_upload (table, bytes, *d_table, stream)) return 0;
+    pcm_fail (failure);
+    return -1;
+}
+/* ... and a launch's result goes into the entry's tally: 0 and `made` launches more, or -1 with `failure` reported (the loops over the classes stay with the entries) */
+static int launched (int failed, const char *failure, int made, int *launches) { if (failed) pcm_fail (failure); else *launches += made; return failed ? -1 : 0; }
+
+/* ------------------------------------------------------------------------------------------
  * Many contexts, one launch per class of work
  *
  * Classes: the time-parallel form (no noise shaping, >= 64 frames: the single call's decimate_parallel_kernel), by dither on or
@@ -957,16 +1043,7 @@ void decimateHipReset (Decimate *cxt)
  * by frame count (a workgroup runs until its longest lane ends) and cut into workgroups of arthip_decimate_batch_lanes () lanes.
  * ---------------------------------------------------------------------------------------- */
 #define DEC_BATCH_CLASSES 12                       /* 2 time-parallel + 5 orders x 2 */
-
-typedef struct { int ctx, channel, frames; } DecLaneRef;
-
-static int lane_order (const void *pa, const void *pb)     /* longest first; then list order, channel order (a total order) */
-{
-    const DecLaneRef *a = pa, *b = pb;
-    if (a->frames != b->frames) return a->frames > b->frames ? -1 : 1;
-    if (a->ctx != b->ctx) return a->ctx < b->ctx ? -1 : 1;
-    return a->channel < b->channel ? -1 : a->channel > b->channel;
-}
+#define DEC_ONLY_PUT_BACK (-2)                     /* for a class: no frames, fromStart — the one grouped copy of such contexts restores it */
 
 static unsigned long *dec_stamp (const void *cxt) { return &((const Decimate *) cxt)->hip->batch_stamp; }
 
@@ -978,10 +1055,119 @@ static void dec_host_from_start (Decimate *cxt)
     dec_fresh_mirrors (cxt);
 }
 
-/* where the image (d_state0) holds what `live` points to in the state block */
-static const void *dec_image_of (const struct artamd_decimator *hip, const void *live)
+/* where a record's first state is read from: the live state itself, or with fromStart where the image (d_state0) of `image` holds it */
+static const void *dec_first_state (const struct artamd_decimator *image, const void *live) { return live && image ? image->d_state0 + ((const unsigned char *) live - image->d_state) : live; }
+/* an item's plan: its kernel arguments, its pitches (0: that side interleaved) and, for its records, the context whose image holds
+ * its first state (dec_first_state's) and where its clipped samples are counted (its entry of d_clipCounts, or NULL) */
+typedef struct { ArtDecArgs a; long in_pitch, out_pitch; const struct artamd_decimator *image; unsigned long long *item_clipped; } DecPlan;
+/* the tasks of a context's call in a time-parallel launch */
+static long dec_tasks (int C, int frames) { return (long) C * ((frames + ART_DEC_SEG - 1) / ART_DEC_SEG); }
+
+/* route: a context that `lead`'s launches cannot take makes its single call, after its own reset with fromStart, and its clip count
+ * goes up from the host; the launches made (0: no frames) */
+static int dec_side_call (Decimate *cxt, const struct artamd_decimator *lead, const DecPlan *p, const artsample_t *d_input, int frames, unsigned char *d_output, int fromStart)
 {
-    return live ? hip->d_state0 + ((const unsigned char *) live - hip->d_state) : NULL;
+    if (fromStart) decimateHipReset (cxt);
+    if (frames <= 0) return 0;
+    const long before = p->item_clipped ? decimateHipClipped (cxt) : 0;
+    decimateProcessPlanarLEDevice (cxt, d_input, p->in_pitch, frames, d_output, p->out_pitch);
+    if (p->item_clipped) {         /* (synchronises: the read-backs, and the upload from this frame) */
+        const unsigned long long made = (unsigned long long)(decimateHipClipped (cxt) - before);
+        ENTER_DEVICE (lead);
+        if (arthip_h2d (p->item_clipped, &made, sizeof (made), lead->stream) || arthip_sync (lead->stream))
+            pcm_fail ("decimate clips: a clip count could not be uploaded");
+        LEAVE_DEVICE (lead);
+    }
+    return 1;
+}
+
+/* route: the contexts these launches cannot take are made as their single calls, in list order (their number is returned); the
+ * others get their arguments, their class (cls_of [i]; -1: nothing to do) and are counted into it, or into *nrestore */
+static int dec_route (Decimate *const *cxts, int n, const artsample_t *const *d_inputs, const int *frames, unsigned char *const *d_outputs, int fromStart,
+                      DecPlan *plan, int *cls_of, ArtDecClass *cls, int *nrestore)
+{
+    const struct artamd_decimator *lead = cxts [0]->hip;
+    int side = 0;
+    for (int i = 0; i < n; ++i) {
+        cls_of [i] = -1;
+        if (!dec_shares_launch (cxts [i]->hip, lead)) { side += dec_side_call (cxts [i], lead, &plan [i], d_inputs [i], frames [i], d_outputs [i], fromStart); continue; }
+        if (frames [i] <= 0) { if (fromStart) { cls_of [i] = DEC_ONLY_PUT_BACK; ++*nrestore; } continue; }
+        ArtDecArgs *a = &plan [i].a;
+        dec_args (cxts [i], a);
+        if (fromStart && a->gens > a->gens_next) { uint32_t *t = a->gens; a->gens = a->gens_next; a->gens_next = t; }       /* as dec_host_from_start will leave them */
+        cls_of [i] = frames [i] >= 64 && !a->shaping_on ? (a->dither_on != 0)
+                   : 2 + 2 * (a->shaping_on ? (a->shaping_order >= 1 && a->shaping_order <= 4 ? a->shaping_order : 4) : 0) + (a->dither_on != 0);
+        ArtDecClass *c = &cls [cls_of [i]];
+        if (plan [i].in_pitch || plan [i].out_pitch) c->pitched = 1;
+        if (c->serial) c->slice.count += a->C;
+        else { c->tasks += dec_tasks (a->C, frames [i]); c->slice.count++; }
+    }
+    return side;
+}
+
+/* place: the table's slices — the copies of the `nrestore` contexts that are only put back, then every present class's records; its bytes */
+static size_t dec_layout (ArtDecClass *cls, int nrestore, int lanes, size_t lane_size, size_t task_size, int *maxlanes)
+{
+    size_t bytes = 0;
+    table_slice (&bytes, sizeof (ArtCopyRows), (size_t) nrestore);
+    for (int k = 0; k < DEC_BATCH_CLASSES; ++k)
+        if (!cls [k].serial) cls [k].slice.offset = table_slice (&bytes, task_size, (size_t) cls [k].slice.count);
+        else if (cls [k].slice.count) serial_slice (&cls [k].slice, lanes, arthip_decimate_batch_lanes, lane_size, &bytes, maxlanes);
+    return bytes;
+}
+
+/* fill: an item's record of a time-parallel class at `rec` (clips: the clips entry's) */
+static void dec_fill_task (unsigned char *rec, int clips, const DecPlan *p, const art_s *d_input, unsigned char *d_output, int frames, long task0)
+{
+    const ArtDecArgs *a = &p->a;
+    ArtDecTask *it = clips ? &((ArtDecClipTask *) rec)->task : (ArtDecTask *) rec;
+    it->in = d_input; it->out = d_output;
+    it->feedback = (art_s *) dec_first_state (p->image, a->feedback); it->gens = (uint32_t *) dec_first_state (p->image, a->gens);       /* (both are only read by this form) */
+    it->gens_next = a->gens_next; it->clipped = a->clipped;
+    it->task0 = task0; it->scale = a->scale;
+    it->C = a->C; it->frames = frames; it->bits = a->bits; it->bytes = a->bytes; it->dither_type = a->dither_type;
+    it->in_pitch = p->in_pitch; it->out_pitch = p->out_pitch;
+    if (clips) { ArtDecClipTask *ct = (ArtDecClipTask *) rec; ct->task0 = task0; ct->item_clipped = p->item_clipped; }
+}
+
+/* fill: channel c of an item as a lane of a serial class at `rec` */
+static void dec_fill_lane (unsigned char *rec, int clips, const DecPlan *p, const art_s *d_input, unsigned char *d_output, int frames, int c)
+{
+    const ArtDecArgs *a = &p->a;
+    ArtDecLane *l = clips ? &((ArtDecClipLane *) rec)->lane : (ArtDecLane *) rec;
+    const LaneSide in = lane_side (p->in_pitch, c, a->C, 1), out = lane_side (p->out_pitch, c, a->C, a->bytes);
+    l->in = d_input + in.offset; l->out = d_output + out.offset;
+    l->feedback = a->feedback + c;
+    l->gen = a->dither_on ? a->gens + c : NULL;
+    l->shaper = a->shaping_on ? a->shapers + c : NULL;
+    l->clipped = a->clipped; l->scale = a->scale;
+    l->stride = in.stride; l->out_stride = out.stride; l->frames = frames; l->bits = a->bits; l->bytes = a->bytes; l->dither_type = a->dither_type;
+    if (clips) {
+        ArtDecClipLane *cl = (ArtDecClipLane *) rec;
+        cl->feedback_from = dec_first_state (p->image, l->feedback); cl->gen_from = dec_first_state (p->image, l->gen);
+        cl->shaper_from = dec_first_state (p->image, l->shaper); cl->item_clipped = p->item_clipped;
+    }
+}
+
+/* launch: the grouped copy of the contexts that are only put back, then every present class; after each, what it leaves on the host side.  0 or -1 (reported) */
+static int dec_launch (Decimate *const *cxts, int n, const int *cls_of, const ArtDecClass *cls, int nrestore, long restore_tasks, int fromStart,
+                       const struct artamd_decimator *lead, int *launches)
+{
+    if (nrestore) {
+        if (launched (arthip_copy_rows_launch (lead->d_batch, nrestore, restore_tasks, lead->stream), "decimate clips: launch failed", 1, launches)) return -1;
+        for (int i = 0; i < n; ++i)
+            if (cls_of [i] == DEC_ONLY_PUT_BACK) dec_host_from_start (cxts [i]);
+    }
+    for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
+        if (!cls [k].slice.count) continue;
+        if (launched (arthip_decimate_batch_launch (&cls [k], lead->d_batch, lead->stream), "decimate batch: launch failed", 1, launches)) return -1;
+        for (int i = 0; i < n; ++i) {
+            if (cls_of [i] != k) continue;
+            if (fromStart) dec_host_from_start (cxts [i]);         /* the launch read the image and wrote the live state */
+            if (!cls [k].serial) dec_swap_if (cxts [i], 1);        /* the time-parallel form left the generator state in gens_next */
+        }
+    }
+    return 0;
 }
 
 /* lanes > 0: every serial class gets that many lanes per workgroup (the measurements of the rule); 0: the rule.
@@ -992,27 +1178,21 @@ int artamd_decimate_clips_planar (Decimate *const *cxts, int n, const artsample_
 {
     if (n <= 0) return 0;
     if (artamd_batch_distinct ((const void *const *) cxts, n, dec_stamp, "decimate", "context")) return -1;
-
     const int clips = fromStart || d_clipCounts;                   /* the clips entry's records and instantiations */
     const size_t lane_size = clips ? sizeof (ArtDecClipLane) : sizeof (ArtDecLane), task_size = clips ? sizeof (ArtDecClipTask) : sizeof (ArtDecTask);
     struct artamd_decimator *lead = cxts [0]->hip;
-    ArtDecArgs *args = malloc (sizeof (ArtDecArgs) * (size_t) n);
+    DecPlan *plan = malloc (sizeof (DecPlan) * (size_t) n);
     int *cls_of = malloc (sizeof (int) * (size_t) n);
-    long *pitch = malloc (sizeof (long) * 2 * (size_t) n);         /* [2 i]: item i's input pitch, [2 i + 1]: its output pitch (0: interleaved) */
-    ArtDecClass cls [DEC_BATCH_CLASSES];
-    DecLaneRef *refs = NULL;
-    unsigned char *table = NULL;
-    int launches = 0, rc = -1, most = 0, nrestore = 0;
+    ArtDecClass cls [DEC_BATCH_CLASSES] = { { 0 } };
+    LaneRef *refs = NULL; unsigned char *table = NULL;
+    int launches = 0, rc = -1, nrestore = 0, maxlanes = 0;
     long restore_tasks = 0;
-    if (!args || !cls_of || !pitch) { pcm_fail ("decimate batch: out of host memory"); goto out; }
-    memset (cls, 0, sizeof (cls));
-    for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
-        cls [k].serial = k >= 2;
-        cls [k].order = k >= 2 ? (k - 2) / 2 : 0;
-        cls [k].dither = k >= 2 ? (k - 2) & 1 : k;
-        cls [k].clips = clips;
+    if (!plan || !cls_of) { pcm_fail ("decimate batch: out of host memory"); goto out; }
+    for (int k = 0; k < DEC_BATCH_CLASSES; ++k) { cls [k].serial = k >= 2; cls [k].order = k >= 2 ? (k - 2) / 2 : 0; cls [k].dither = k >= 2 ? (k - 2) & 1 : k; cls [k].clips = clips; }
+    for (int i = 0; i < n; ++i) {
+        plan [i].in_pitch = item_pitch (inputPitches, i, cxts [i]->numChannels); plan [i].out_pitch = item_pitch (outputPitches, i, cxts [i]->numChannels);
+        plan [i].image = fromStart ? cxts [i]->hip : NULL; plan [i].item_clipped = d_clipCounts ? &d_clipCounts [i] : NULL;
     }
-
     if (d_clipCounts) {            /* every entry 0, in stream order before anything is counted */
         ENTER_DEVICE (lead);
         const int failed = arthip_zero (d_clipCounts, sizeof (unsigned long long) * (size_t) n, lead->stream);
@@ -1021,158 +1201,44 @@ int artamd_decimate_clips_planar (Decimate *const *cxts, int n, const artsample_
         ++launches;
     }
 
-    /* the contexts this launch cannot take are made as their single calls, in list order */
-    for (int i = 0; i < n; ++i) {
-        struct artamd_decimator *hip = cxts [i]->hip;
-        const int frames = numInputFrames [i];
-        cls_of [i] = -1;
-        const int planes = cxts [i]->numChannels > 1;              /* (one channel: the same call in either layout) */
-        const long ip = pitch [2 * i] = planes && inputPitches ? inputPitches [i] : 0;
-        const long op = pitch [2 * i + 1] = planes && outputPitches ? outputPitches [i] : 0;
-        if (hip->nshards || hip->stream != lead->stream || hip->device != lead->device) {
-            if (fromStart) decimateHipReset (cxts [i]);
-            if (frames <= 0) continue;
-            const long before = d_clipCounts ? decimateHipClipped (cxts [i]) : 0;
-            decimateProcessPlanarLEDevice (cxts [i], d_inputs [i], ip, frames, d_outputs [i], op);
-            ++launches;
-            if (d_clipCounts) {    /* (synchronises: the read-backs, and the upload from this frame) */
-                const unsigned long long made = (unsigned long long)(decimateHipClipped (cxts [i]) - before);
-                ENTER_DEVICE (lead);
-                if (arthip_h2d (&d_clipCounts [i], &made, sizeof (made), lead->stream) || arthip_sync (lead->stream))
-                    pcm_fail ("decimate clips: a clip count could not be uploaded");
-                LEAVE_DEVICE (lead);
-            }
-            continue;
-        }
-        if (frames <= 0) {
-            cls_of [i] = fromStart ? -2 : -1;                      /* -2: only put back, by the one grouped copy of such contexts */
-            if (fromStart) { ++nrestore; restore_tasks += ((long)(hip->state_bytes - 16) / 4 + 3) / 4 + 1; }
-            continue;
-        }
-        ArtDecArgs *a = &args [i];
-        dec_args (cxts [i], a);
-        if (fromStart && a->gens > a->gens_next) { uint32_t *t = a->gens; a->gens = a->gens_next; a->gens_next = t; }       /* as dec_host_from_start will leave them */
-        const int k = frames >= 64 && !a->shaping_on ? (a->dither_on != 0)
-                    : 2 + 2 * (a->shaping_on ? (a->shaping_order >= 1 && a->shaping_order <= 4 ? a->shaping_order : 4) : 0) + (a->dither_on != 0);
-        cls_of [i] = k;
-        if (ip || op) cls [k].pitched = 1;
-        if (cls [k].serial) { cls [k].slice.count += a->C; if (a->C > most) most = a->C; }
-        else { cls [k].tasks += (long) a->C * ((frames + ART_DEC_SEG - 1) / ART_DEC_SEG); cls [k].slice.count++; }
-    }
-
-    /* the table: the contexts that are only put back, then every present class's items, 16-byte aligned slices */
-    size_t bytes = (sizeof (ArtCopyRows) * (size_t) nrestore + 15) & ~(size_t) 15;
-    int maxlanes = 0;
-    for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
-        if (!cls [k].slice.count) continue;
-        if (cls [k].serial) {
-            cls [k].slice.lanes = lanes > 0 ? (lanes < 64 ? lanes : 64) : arthip_decimate_batch_lanes (cls [k].slice.count);
-            cls [k].slice.count = (cls [k].slice.count + cls [k].slice.lanes - 1) / cls [k].slice.lanes * cls [k].slice.lanes;      /* (+ empty lanes) */
-            if (cls [k].slice.count > maxlanes) maxlanes = cls [k].slice.count;
-        }
-        cls [k].slice.offset = bytes;
-        bytes += ((cls [k].serial ? lane_size : task_size) * (size_t) cls [k].slice.count + 15) & ~(size_t) 15;
-    }
+    launches += dec_route (cxts, n, d_inputs, numInputFrames, d_outputs, fromStart, plan, cls_of, cls, &nrestore);
+    const size_t bytes = dec_layout (cls, nrestore, lanes, lane_size, task_size, &maxlanes);
     if (!bytes) { rc = launches; goto out; }
     table = calloc (1, bytes);
-    refs = maxlanes ? malloc (sizeof (DecLaneRef) * (size_t) maxlanes) : NULL;
+    refs = maxlanes ? malloc (sizeof (LaneRef) * (size_t) maxlanes) : NULL;
     if (!table || (maxlanes && !refs)) { pcm_fail ("decimate batch: out of host memory"); goto out; }
-    if (nrestore) {
-        ArtCopyRows *it = (ArtCopyRows *) table;
-        long task0 = 0;
-        for (int i = 0; i < n; ++i) {
-            if (cls_of [i] != -2) continue;
-            const struct artamd_decimator *hip = cxts [i]->hip;    /* (all but the clip counter, as decimateHipReset) */
-            clip_copy_item (it, hip->d_state0 + 16, 0, hip->d_state + 16, 0, (long)(hip->state_bytes - 16) / 4, 1, task0);
-            task0 += it->groups;
-            ++it;
-        }
+
+    ArtCopyRows *back = (ArtCopyRows *) table;                      /* the contexts without frames: all but the clip counter, as decimateHipReset */
+    for (int i = 0, left = nrestore; left; ++i) {
+        if (cls_of [i] != DEC_ONLY_PUT_BACK) continue;
+        const struct artamd_decimator *hip = cxts [i]->hip;
+        clip_copy_item (back, hip->d_state0 + 16, 0, hip->d_state + 16, 0, (long)(hip->state_bytes - 16) / 4, 1, restore_tasks);
+        restore_tasks += back++->groups; --left;
     }
     for (int k = 0; k < DEC_BATCH_CLASSES; ++k) {
+        unsigned char *rec = table + cls [k].slice.offset;
+        long task0 = 0;
         if (!cls [k].slice.count) continue;
-        if (!cls [k].serial) {
-            long task0 = 0;
-            for (int i = 0, j = 0; i < n; ++i) {
-                if (cls_of [i] != k) continue;
-                const ArtDecArgs *a = &args [i];
-                unsigned char *const rec = table + cls [k].slice.offset + task_size * (size_t) j++;
-                ArtDecTask *it = clips ? &((ArtDecClipTask *) rec)->task : (ArtDecTask *) rec;
-                it->in = d_inputs [i]; it->out = d_outputs [i];
-                it->feedback = a->feedback; it->gens = a->gens; it->gens_next = a->gens_next; it->clipped = a->clipped;
-                it->task0 = task0; it->scale = a->scale;
-                it->C = a->C; it->frames = numInputFrames [i]; it->bits = a->bits; it->bytes = a->bytes; it->dither_type = a->dither_type;
-                it->in_pitch = pitch [2 * i]; it->out_pitch = pitch [2 * i + 1];
-                if (clips) {
-                    ArtDecClipTask *ct = (ArtDecClipTask *) rec;
-                    ct->task0 = task0; ct->item_clipped = d_clipCounts ? &d_clipCounts [i] : NULL;
-                    if (fromStart) {                               /* both are only read by this form */
-                        it->feedback = (art_s *) dec_image_of (cxts [i]->hip, a->feedback);
-                        it->gens = (uint32_t *) dec_image_of (cxts [i]->hip, a->gens);
-                    }
-                }
-                task0 += (long) a->C * ((numInputFrames [i] + ART_DEC_SEG - 1) / ART_DEC_SEG);
+        if (cls [k].serial) {
+            const int m = class_lanes (refs, k, n, cls_of, (const void *const *) cxts, dec_channels, numInputFrames);
+            for (int j = 0; j < m; ++j, rec += lane_size) {         /* (the padding lanes stay zero: 0 frames) */
+                const int i = refs [j].item;
+                dec_fill_lane (rec, clips, &plan [i], d_inputs [i], d_outputs [i], numInputFrames [i], refs [j].channel);
             }
-            continue;
         }
-        int m = 0;
-        for (int i = 0; i < n; ++i)
-            if (cls_of [i] == k)
-                for (int c = 0; c < args [i].C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numInputFrames [i]; ++m; }
-        qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
-        for (int j = 0; j < m; ++j) {                                       /* (the padding lanes stay zero: 0 frames) */
-            const int i = refs [j].ctx, c = refs [j].channel;
-            const ArtDecArgs *a = &args [i];
-            const long ip = pitch [2 * i], op = pitch [2 * i + 1];
-            unsigned char *const rec = table + cls [k].slice.offset + lane_size * (size_t) j;
-            ArtDecLane *l = clips ? &((ArtDecClipLane *) rec)->lane : (ArtDecLane *) rec;
-            l->in = d_inputs [i] + (ip ? c * ip : c); l->out = d_outputs [i] + (op ? c * op : (long) c * a->bytes);
-            l->feedback = a->feedback + c;
-            l->gen = a->dither_on ? a->gens + c : NULL;
-            l->shaper = a->shaping_on ? a->shapers + c : NULL;
-            l->clipped = a->clipped; l->scale = a->scale;
-            l->stride = ip ? 1 : a->C; l->out_stride = op ? 1 : a->C; l->frames = numInputFrames [i]; l->bits = a->bits; l->bytes = a->bytes; l->dither_type = a->dither_type;
-            if (clips) {
-                ArtDecClipLane *cl = (ArtDecClipLane *) rec;
-                const struct artamd_decimator *hip = cxts [i]->hip;
-                cl->feedback_from = fromStart ? dec_image_of (hip, l->feedback) : l->feedback;
-                cl->gen_from = fromStart ? dec_image_of (hip, l->gen) : l->gen;
-                cl->shaper_from = fromStart ? dec_image_of (hip, l->shaper) : l->shaper;
-                cl->item_clipped = d_clipCounts ? &d_clipCounts [i] : NULL;
-            }
+        else for (int i = 0; i < n; ++i) {
+            if (cls_of [i] != k) continue;
+            dec_fill_task (rec, clips, &plan [i], d_inputs [i], d_outputs [i], numInputFrames [i], task0);
+            rec += task_size; task0 += dec_tasks (plan [i].a.C, numInputFrames [i]);
         }
     }
 
-    {
-        ENTER_DEVICE (lead);
-        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, bytes);
-        if (!lead->d_batch || arthip_table_upload (table, bytes, lead->d_batch, lead->stream))
-            pcm_fail ("decimate batch: the table could not be uploaded (nothing launched)");
-        else {
-            rc = 0;
-            if (nrestore) {
-                if (arthip_copy_rows_launch (lead->d_batch, nrestore, restore_tasks, lead->stream)) { pcm_fail ("decimate clips: launch failed"); rc = -1; }
-                else {
-                    ++launches;
-                    for (int i = 0; i < n; ++i)
-                        if (cls_of [i] == -2) dec_host_from_start (cxts [i]);
-                }
-            }
-            for (int k = 0; k < DEC_BATCH_CLASSES && !rc; ++k) {
-                if (!cls [k].slice.count) continue;
-                if (arthip_decimate_batch_launch (&cls [k], lead->d_batch, lead->stream)) { pcm_fail ("decimate batch: launch failed"); rc = -1; break; }
-                ++launches;
-                for (int i = 0; i < n; ++i) {
-                    if (cls_of [i] != k) continue;
-                    if (fromStart) dec_host_from_start (cxts [i]);         /* the launch read the image and wrote the live state */
-                    if (!cls [k].serial) dec_swap_if (cxts [i], 1);        /* the time-parallel form left the generator state in gens_next */
-                }
-            }
-            if (!rc) rc = launches;
-        }
-        LEAVE_DEVICE (lead);
-    }
+    ENTER_DEVICE (lead);
+    if (!table_to_device ("decimate batch: the table could not be uploaded (nothing launched)", table, bytes, &lead->d_batch, &lead->batch_cap, lead->stream) &&
+        !dec_launch (cxts, n, cls_of, cls, nrestore, restore_tasks, fromStart, lead, &launches)) rc = launches;
+    LEAVE_DEVICE (lead);
 out:
-    free (args); free (cls_of); free (pitch); free (refs); free (table);
+    free (plan); free (cls_of); free (refs); free (table);
     return rc;
 }
 
@@ -1226,6 +1292,13 @@ int artamd_biquad_batch (BiquadBank *const *banks, int n, artsample_t *const *d_
     return artamd_biquad_batch_planar (banks, n, d_buffers, NULL, numFrames, lanes, serialMax);
 }
 
+/* place: the slices of the serial classes (section counts 1 - 4: cls [S - 1]) that have lanes, from *bytes on */
+static void bq_serial_layout (ArtBqClass *cls, int lanes, size_t lane_size, size_t *bytes, int *maxlanes)
+{
+    for (int k = 0; k < 4; ++k)
+        if (cls [k].slice.count) { cls [k].S = k + 1; serial_slice (&cls [k].slice, lanes, arthip_biquad_batch_lanes, lane_size, bytes, maxlanes); }
+}
+
 /* pitches: NULL (every item interleaved) or a pitch per item, 0 for an interleaved one (biquadBankApplyPlanarDevice's) */
 int artamd_biquad_batch_planar (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches, const int *numFrames,
                                 int lanes, int serialMax)
@@ -1233,82 +1306,48 @@ int artamd_biquad_batch_planar (BiquadBank *const *banks, int n, artsample_t *co
     if (n <= 0) return 0;
     if (artamd_batch_distinct ((const void *const *) banks, n, bank_stamp, "biquad", "bank")) return -1;
     if (serialMax < 0) serialMax = BQ_BATCH_SERIAL_MAX;
-
     BiquadBank *lead = banks [0];
-    int *gathered = malloc (sizeof (int) * (size_t) n);
-    ArtBqClass cls [4];
-    DecLaneRef *refs = NULL;
-    unsigned char *table = NULL;
+    int *cls_of = malloc (sizeof (int) * (size_t) n);
+    ArtBqClass cls [4] = { { 0 } };
+    LaneRef *refs = NULL; unsigned char *table = NULL;
     int launches = 0, rc = -1, maxlanes = 0;
-    if (!gathered) { pcm_fail ("biquad batch: out of host memory"); goto out; }
-    memset (cls, 0, sizeof (cls));
-
-    /* the calls this launch cannot take are made as their single calls, in list order */
+    size_t bytes = 0;
+    if (!cls_of) { pcm_fail ("biquad batch: out of host memory"); goto out; }
+    /* route: the calls this launch cannot take are made as their single calls, in list order; the others are counted into their
+     * class, cls_of [i] = S - 1 (-1: not gathered) */
     for (int i = 0; i < n; ++i) {
         BiquadBank *b = banks [i];
-        gathered [i] = 0;
+        cls_of [i] = -1;
         if (numFrames [i] <= 0) continue;
-        if (!bank_shares_launch (b, lead) || gathered_chunk (b->S, b->warmup, numFrames [i], serialMax)) {
-            biquadBankApplyPlanarDevice (b, d_buffers [i], pitches ? pitches [i] : 0, numFrames [i]);       /* (pitch 0: the interleaved call) */
-            ++launches;
-            continue;
-        }
-        gathered [i] = 1;
-        cls [b->S - 1].slice.count += b->C;
+        if (bank_shares_launch (b, lead) && !gathered_chunk (b->S, b->warmup, numFrames [i], serialMax)) cls [cls_of [i] = b->S - 1].slice.count += b->C;
+        else { biquadBankApplyPlanarDevice (b, d_buffers [i], item_pitch (pitches, i, b->C), numFrames [i]); ++launches; }       /* (pitch 0: the interleaved call) */
     }
-
-    /* the table: every present class's lanes (+ empty lanes up to whole workgroups), 16-byte aligned slices */
-    size_t bytes = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (!cls [k].slice.count) continue;
-        cls [k].S = k + 1;
-        cls [k].slice.lanes = lanes > 0 ? (lanes < 64 ? lanes : 64) : arthip_biquad_batch_lanes (cls [k].slice.count);
-        cls [k].slice.count = (cls [k].slice.count + cls [k].slice.lanes - 1) / cls [k].slice.lanes * cls [k].slice.lanes;
-        if (cls [k].slice.count > maxlanes) maxlanes = cls [k].slice.count;
-        cls [k].slice.offset = bytes;
-        bytes += (sizeof (ArtBqLane) * (size_t) cls [k].slice.count + 15) & ~(size_t) 15;
-    }
+    bq_serial_layout (cls, lanes, sizeof (ArtBqLane), &bytes, &maxlanes);
     if (!bytes) { rc = launches; goto out; }
     table = calloc (1, bytes);
-    refs = malloc (sizeof (DecLaneRef) * (size_t) maxlanes);
+    refs = malloc (sizeof (LaneRef) * (size_t) maxlanes);
     if (!table || !refs) { pcm_fail ("biquad batch: out of host memory"); goto out; }
     for (int k = 0; k < 4; ++k) {
         if (!cls [k].slice.count) continue;
-        int m = 0;
-        for (int i = 0; i < n; ++i)
-            if (gathered [i] && banks [i]->S == k + 1)
-                for (int c = 0; c < banks [i]->C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numFrames [i]; ++m; }
-        qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
+        const int m = class_lanes (refs, k, n, cls_of, (const void *const *) banks, bank_channels, numFrames);
         ArtBqLane *l = (ArtBqLane *)(table + cls [k].slice.offset);         /* (the padding lanes stay zero: 0 frames) */
         for (int j = 0; j < m; ++j) {
-            const BiquadBank *b = banks [refs [j].ctx];
-            const int c = refs [j].channel;
+            const int i = refs [j].item, c = refs [j].channel;
+            const BiquadBank *b = banks [i];
+            const LaneSide at = lane_side (item_pitch (pitches, i, b->C), c, b->C, 1);
             l [j].sections = b->d_sections + (size_t) c * b->S;
-            const long pitch = pitches && b->C > 1 ? pitches [refs [j].ctx] : 0;
-            l [j].buf = d_buffers [refs [j].ctx] + (pitch ? (size_t) c * pitch : (size_t) c);
-            l [j].stride = pitch ? 1 : b->C;
-            l [j].frames = refs [j].frames;
+            l [j].buf = d_buffers [i] + at.offset; l [j].stride = at.stride; l [j].frames = refs [j].frames;
         }
     }
 
-    {
-        ENTER_DEVICE (lead);
-        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, bytes);
-        if (!lead->d_batch || arthip_table_upload (table, bytes, lead->d_batch, lead->stream))
-            pcm_fail ("biquad batch: the table could not be uploaded (nothing launched)");
-        else {
-            rc = 0;
-            for (int k = 0; k < 4; ++k) {
-                if (!cls [k].slice.count) continue;
-                if (arthip_biquad_batch_launch (&cls [k], lead->d_batch, lead->stream)) { pcm_fail ("biquad batch: launch failed"); rc = -1; break; }
-                ++launches;
-            }
-            if (!rc) rc = launches;
-        }
-        LEAVE_DEVICE (lead);
-    }
+    ENTER_DEVICE (lead);
+    rc = table_to_device ("biquad batch: the table could not be uploaded (nothing launched)", table, bytes, &lead->d_batch, &lead->batch_cap, lead->stream);
+    for (int k = 0; k < 4 && !rc; ++k)
+        if (cls [k].slice.count) rc = launched (arthip_biquad_batch_launch (&cls [k], lead->d_batch, lead->stream), "biquad batch: launch failed", 1, &launches);
+    if (!rc) rc = launches;
+    LEAVE_DEVICE (lead);
 out:
-    free (gathered); free (refs); free (table);
+    free (cls_of); free (refs); free (table);
     return rc;
 }
 
@@ -1376,12 +1415,16 @@ static void clip_place (ClipPlace *p, ArtBqClipClass *classes, const BiquadBank 
     c->tasks += (long) b->C * p->K; c->channels += b->C;
 }
 
-/* the table's slices of one round's classes from `bytes` on, 16-byte aligned; the bytes behind them */
-static size_t clip_classes_layout (ArtBqClipClass *classes, size_t bytes)
+/* the table's slices, per round its copies (the in-place entry's), then its classes' items; the bytes, and the most bytes a round
+ * sets aside and keeps as chunk states */
+static size_t clip_rounds_layout (ClipRound *rounds, int nrounds, size_t *tmp_need, size_t *spec_need)
 {
-    for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
-        classes [k].offset = bytes;
-        bytes += (sizeof (ArtBqClip) * (size_t) classes [k].count + 15) & ~(size_t) 15;
+    size_t bytes = 0;
+    for (ClipRound *r = rounds; r < rounds + nrounds; ++r) {
+        r->copy_offset = table_slice (&bytes, sizeof (ArtCopyRows), (size_t) r->ncopy);
+        for (int k = 0; k < BQ_CLIP_CLASSES; ++k) r->cls [k].offset = table_slice (&bytes, sizeof (ArtBqClip), (size_t) r->cls [k].count);
+        if (r->tmp_bytes > *tmp_need) *tmp_need = r->tmp_bytes;
+        if (r->spec_bytes > *spec_need) *spec_need = r->spec_bytes;
     }
     return bytes;
 }
@@ -1396,10 +1439,81 @@ static ArtBqClip *clip_item (unsigned char *table, const ArtBqClipClass *classes
     return it;
 }
 
-static void clip_copy_item (ArtCopyRows *it, const void *src, long src_pitch, void *dst, long dst_pitch, long width, long rows, long task0)
+/* the 4-byte words of a sample and of a bank's sections (what the grouped copy that puts a bank back moves) */
+#define WORDS_PER_SAMPLE ((long)(sizeof (art_s) / 4))
+static long bank_words (const BiquadBank *b) { return (long)(sizeof (Biquad) / 4) * b->C * b->S; }
+
+/* route: every call's kind and, for a time-parallel one, its chunk length.  A lone time-parallel call gains nothing from the table
+ * (measured, profiles/biquad_clips.txt: 4 us behind its single call): it is made as that call */
+static void clips_route (BiquadBank *const *banks, int n, const long *pitches, const int *numFrames, ClipPlan *plan)
 {
-    it->src = src; it->dst = dst; it->src_pitch = src_pitch; it->dst_pitch = dst_pitch;
-    it->width = width; it->rows = rows; it->groups = (width + 3) / 4 + 1; it->task0 = task0;
+    int ngathered = 0, only = -1;
+    for (int i = 0; i < n; ++i) {
+        const BiquadBank *b = banks [i];
+        ClipPlan *p = &plan [i];
+        p->pitch = item_pitch (pitches, i, b->C);
+        if (!bank_shares_launch (b, banks [0])) p->at.kind = CLIP_SIDE;
+        else if ((p->at.L = gathered_chunk (b->S, b->warmup, numFrames [i], BQ_BATCH_SERIAL_MAX)) != 0) { p->at.kind = CLIP_GATHERED; ++ngathered; only = i; }
+        else p->at.kind = numFrames [i] > 0 ? CLIP_SERIAL : CLIP_SKIP;
+    }
+    if (ngathered == 1) plan [only].at.kind = CLIP_SIDE;
+}
+
+/* place: an item's copy takes the next slot and `tasks` tasks of a round's copy launch */
+static void clips_place_copy (ClipPlan *p, ClipRound *r, long tasks) { p->copy_slot = r->ncopy++; p->copy_task0 = r->copy_tasks; r->copy_tasks += tasks; }
+
+/* place: a gathered item in the last of the `nrounds` rounds, or in a new one when its copy would take that one beyond `bound` bytes;
+ * the rounds there are now.  The copy is placed as the single call's (an interleaved item's copy then moves 16 bytes at a time too) */
+static int clips_place (ClipPlan *p, ClipRound *rounds, int nrounds, const BiquadBank *b, const artsample_t *d_buffer, int frames, size_t bound)
+{
+    const size_t q = 16 / sizeof (art_s);
+    p->dense = aside_placement (d_buffer, p->pitch, frames, &p->lead);
+    if (!p->pitch) p->dense = (long) frames * b->C;
+    const size_t samples = ((p->pitch ? (size_t) p->dense * b->C : (size_t) p->dense) + p->lead + (q - 1)) & ~(q - 1);
+    const size_t states = (arthip_biquad_spec_scratch (b->C, b->S, frames, p->at.L) + 255) & ~(size_t) 255;
+    ClipRound *r = &rounds [nrounds - 1];
+    if (r->tmp_bytes && r->tmp_bytes + samples * sizeof (art_s) > bound) r = &rounds [nrounds++];
+    p->at.round = (int)(r - rounds);
+    p->tmp_at = r->tmp_bytes / sizeof (art_s) + p->lead; r->tmp_bytes += samples * sizeof (art_s);
+    p->at.spec_at = r->spec_bytes; r->spec_bytes += states;
+    clip_place (&p->at, r->cls, b, frames, p->pitch != 0);
+    clips_place_copy (p, r, p->pitch ? b->C * copy_groups (frames * WORDS_PER_SAMPLE) : copy_groups (p->dense * WORDS_PER_SAMPLE));
+    return nrounds;
+}
+
+/* fill: a gathered item's copy aside (into the lead's d_clips_tmp) and its record, in its round `r`'s slices */
+static void clips_fill_item (unsigned char *table, const ClipRound *r, const ClipPlan *p, const BiquadBank *b, artsample_t *d_buffer, int frames,
+                             int fromStart, const BiquadBank *lead)
+{
+    art_s *const aside = (art_s *) lead->d_clips_tmp + p->tmp_at;
+    ArtCopyRows *copy = (ArtCopyRows *)(table + r->copy_offset) + p->copy_slot;
+    if (p->pitch) clip_copy_item (copy, d_buffer, p->pitch * WORDS_PER_SAMPLE, aside, p->dense * WORDS_PER_SAMPLE, frames * WORDS_PER_SAMPLE, b->C, p->copy_task0);
+    else clip_copy_item (copy, d_buffer, 0, aside, 0, p->dense * WORDS_PER_SAMPLE, 1, p->copy_task0);
+    ArtBqClip *it = clip_item (table, r->cls, &p->at, b, frames, (char *) lead->d_clips_spec + p->at.spec_at);
+    it->from = fromStart ? b->d_sections0 : b->d_sections; it->sections = b->d_sections;
+    it->in = aside; it->out = d_buffer;
+    it->in_stride = p->pitch ? p->dense : b->C; it->out_stride = p->pitch ? p->pitch : b->C;
+    it->first_bad = b->d_first_bad; it->repairs = b->d_repairs;
+}
+
+/* launch: round after round its copy launch, then its classes' from lead->d_clips; behind the first round's copy launch (their
+ * sections are put back) what the batch entry gathers goes to it, in one call.  0, or -1 (reported) */
+static int clips_launch (const ClipRound *rounds, int nrounds, const BiquadBank *lead, BiquadBank *const *sbanks, int nserial, artsample_t *const *sbufs,
+                         const long *spitches, const int *sframes, int *launches)
+{
+    for (int r = 0; r < nrounds; ++r) {
+        const ClipRound *rd = &rounds [r];
+        if (rd->ncopy && launched (arthip_copy_rows_launch ((const char *) lead->d_clips + rd->copy_offset, rd->ncopy, rd->copy_tasks, lead->stream),
+                                   "biquad clips: launch failed", 1, launches)) return -1;
+        if (r == 0 && nserial) {
+            const int made = artamd_biquad_batch_planar (sbanks, nserial, sbufs, spitches, sframes, 0, -1);
+            if (made < 0) return -1;
+            *launches += made;
+        }
+        for (int k = 0; k < BQ_CLIP_CLASSES; ++k)
+            if (rd->cls [k].count && launched (arthip_biquad_clips_launch (&rd->cls [k], lead->d_clips, lead->stream), "biquad clips: launch failed", 3, launches)) return -1;
+    }
+    return 0;
 }
 
 int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *const *d_buffers, const long *pitches, const int *numFrames,
@@ -1408,32 +1522,17 @@ int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *co
     if (n <= 0) return 0;
     if (artamd_batch_distinct ((const void *const *) banks, n, bank_stamp, "biquad clips", "bank")) return -1;
     const size_t bound = roundBytes > 0 ? (size_t) roundBytes : BQ_CLIPS_ROUND_BYTES;
-    const long q = 16 / (long) sizeof (art_s), wps = (long)(sizeof (art_s) / 4);
-
     BiquadBank *lead = banks [0];
     ClipPlan *plan = calloc ((size_t) n, sizeof (ClipPlan));
     ClipRound *rounds = calloc ((size_t) n + 1, sizeof (ClipRound));
-    BiquadBank **sbanks = malloc (sizeof (BiquadBank *) * (size_t) n);
+    BiquadBank **sbanks = malloc (sizeof (BiquadBank *) * (size_t) n);         /* what goes to the batch entry: banks, buffers, pitches, frames */
     artsample_t **sbufs = malloc (sizeof (artsample_t *) * (size_t) n);
     long *spitches = malloc (sizeof (long) * (size_t) n);
     int *sframes = malloc (sizeof (int) * (size_t) n);
     unsigned char *table = NULL;
-    int launches = 0, rc = -1, nrounds = 1, nserial = 0, ngathered = 0, only = -1;
+    int launches = 0, rc = -1, nrounds = 1, nserial = 0;
     if (!plan || !rounds || !sbanks || !sbufs || !spitches || !sframes) { pcm_fail ("biquad clips: out of host memory"); goto out; }
-
-    /* every call's route.  A lone time-parallel call gains nothing from the table (measured, profiles/biquad_clips.txt: 4 us behind
-     * its single call): it is made as that call */
-    for (int i = 0; i < n; ++i) {
-        const BiquadBank *b = banks [i];
-        ClipPlan *p = &plan [i];
-        const int frames = numFrames [i];
-        p->pitch = pitches && b->C > 1 ? pitches [i] : 0;                    /* (one channel: the same call in either layout) */
-        if (!bank_shares_launch (b, lead)) p->at.kind = CLIP_SIDE;
-        else if ((p->at.L = gathered_chunk (b->S, b->warmup, frames, BQ_BATCH_SERIAL_MAX)) != 0) { p->at.kind = CLIP_GATHERED; ++ngathered; only = i; }
-        else p->at.kind = frames > 0 ? CLIP_SERIAL : CLIP_SKIP;
-    }
-    if (ngathered == 1) plan [only].at.kind = CLIP_SIDE;
-
+    clips_route (banks, n, pitches, numFrames, plan);
     /* the calls these launches cannot take are made as their single calls, in list order; the others get their places */
     for (int i = 0; i < n; ++i) {
         BiquadBank *b = banks [i];
@@ -1444,98 +1543,37 @@ int artamd_biquad_clips_planar (BiquadBank *const *banks, int n, artsample_t *co
             if (frames > 0) { biquadBankApplyPlanarDevice (b, d_buffers [i], p->pitch, frames); ++launches; }
             continue;
         }
-        if (p->at.kind == CLIP_GATHERED) {
-            /* the set-aside copy: placed as the single call's (an interleaved item's copy then moves 16 bytes at a time too) */
-            p->dense = aside_placement (d_buffers [i], p->pitch, frames, &p->lead);
-            if (!p->pitch) p->dense = (long) frames * b->C;
-            const size_t samples = ((p->pitch ? (size_t) p->dense * b->C : (size_t) p->dense) + p->lead + (size_t)(q - 1)) & ~(size_t)(q - 1);
-            const size_t states = (arthip_biquad_spec_scratch (b->C, b->S, frames, p->at.L) + 255) & ~(size_t) 255;
-            ClipRound *r = &rounds [nrounds - 1];
-            if (r->tmp_bytes && r->tmp_bytes + samples * sizeof (art_s) > bound) r = &rounds [nrounds++];
-            p->at.round = (int)(r - rounds);
-            p->tmp_at = r->tmp_bytes / sizeof (art_s) + p->lead; r->tmp_bytes += samples * sizeof (art_s);
-            p->at.spec_at = r->spec_bytes; r->spec_bytes += states;
-            clip_place (&p->at, r->cls, b, frames, p->pitch != 0);
-            p->copy_slot = r->ncopy++; p->copy_task0 = r->copy_tasks;
-            r->copy_tasks += p->pitch ? (long) b->C * (((long) frames * wps + 3) / 4 + 1) : (p->dense * wps + 3) / 4 + 1;
-            continue;
-        }
+        if (p->at.kind == CLIP_GATHERED) { nrounds = clips_place (p, rounds, nrounds, b, d_buffers [i], frames, bound); continue; }
         if (p->at.kind == CLIP_SERIAL) { sbanks [nserial] = b; sbufs [nserial] = d_buffers [i]; spitches [nserial] = p->pitch; sframes [nserial] = frames; ++nserial; }
-        if (fromStart) {                                                     /* its sections are put back by the first round's copy launch */
-            p->copy_slot = rounds [0].ncopy++; p->copy_task0 = rounds [0].copy_tasks;
-            rounds [0].copy_tasks += ((long)(sizeof (Biquad) / 4) * b->C * b->S + 3) / 4 + 1;
-        }
+        if (fromStart) clips_place_copy (p, &rounds [0], copy_groups (bank_words (b)));      /* its sections are put back by the first round's copy launch */
     }
 
-    /* the table: per round its copies, then its classes' items; 16-byte aligned slices */
-    size_t bytes = 0, tmp_need = 0, spec_need = 0;
-    for (int r = 0; r < nrounds; ++r) {
-        rounds [r].copy_offset = bytes;
-        bytes += (sizeof (ArtCopyRows) * (size_t) rounds [r].ncopy + 15) & ~(size_t) 15;
-        bytes = clip_classes_layout (rounds [r].cls, bytes);
-        if (rounds [r].tmp_bytes > tmp_need) tmp_need = rounds [r].tmp_bytes;
-        if (rounds [r].spec_bytes > spec_need) spec_need = rounds [r].spec_bytes;
-    }
+    size_t tmp_need = 0, spec_need = 0;
+    const size_t bytes = clip_rounds_layout (rounds, nrounds, &tmp_need, &spec_need);
     if (!bytes && !nserial) { rc = launches; goto out; }
 
-    {
-        ENTER_DEVICE (lead);
-        rc = 0;
-        if (bytes) {
-            table = calloc (1, bytes);
-            lead->d_clips = arthip_grow (lead->d_clips, &lead->clips_cap, bytes);
-            if (tmp_need) lead->d_clips_tmp = arthip_grow (lead->d_clips_tmp, &lead->clips_tmp_cap, tmp_need);
-            if (spec_need) lead->d_clips_spec = arthip_grow (lead->d_clips_spec, &lead->clips_spec_cap, spec_need);
-            if (!table || !lead->d_clips || (tmp_need && !lead->d_clips_tmp) || (spec_need && !lead->d_clips_spec)) {
-                pcm_fail ("biquad clips: out of memory for the table or the scratch (nothing of the gathered calls launched)");
-                rc = -1;
-            }
-        }
-        for (int i = 0; i < n && !rc && bytes; ++i) {
-            const ClipPlan *p = &plan [i];
-            BiquadBank *b = banks [i];
-            if (p->at.kind == CLIP_SIDE) continue;
-            if (p->at.kind != CLIP_GATHERED) {
-                if (fromStart)
-                    clip_copy_item ((ArtCopyRows *)(table + rounds [0].copy_offset) + p->copy_slot, b->d_sections0, 0, b->d_sections, 0,
-                                    (long)(sizeof (Biquad) / 4) * b->C * b->S, 1, p->copy_task0);
-                continue;
-            }
-            const ClipRound *r = &rounds [p->at.round];
-            art_s *const aside = (art_s *) lead->d_clips_tmp + p->tmp_at;
-            if (p->pitch) clip_copy_item ((ArtCopyRows *)(table + r->copy_offset) + p->copy_slot, d_buffers [i], p->pitch * wps, aside, p->dense * wps,
-                                          (long) numFrames [i] * wps, b->C, p->copy_task0);
-            else clip_copy_item ((ArtCopyRows *)(table + r->copy_offset) + p->copy_slot, d_buffers [i], 0, aside, 0, p->dense * wps, 1, p->copy_task0);
-            ArtBqClip *it = clip_item (table, r->cls, &p->at, b, numFrames [i], (char *) lead->d_clips_spec + p->at.spec_at);
-            it->from = fromStart ? b->d_sections0 : b->d_sections; it->sections = b->d_sections;
-            it->in = aside; it->out = d_buffers [i];
-            it->in_stride = p->pitch ? p->dense : b->C; it->out_stride = p->pitch ? p->pitch : b->C;
-            it->first_bad = b->d_first_bad; it->repairs = b->d_repairs;
-        }
-        if (!rc && bytes && arthip_table_upload (table, bytes, lead->d_clips, lead->stream)) {
-            pcm_fail ("biquad clips: the table could not be uploaded (nothing of the gathered calls launched)");
+    ENTER_DEVICE (lead);
+    rc = 0;
+    if (bytes) {
+        table = calloc (1, bytes);
+        lead->d_clips = arthip_grow (lead->d_clips, &lead->clips_cap, bytes);
+        if (tmp_need) lead->d_clips_tmp = arthip_grow (lead->d_clips_tmp, &lead->clips_tmp_cap, tmp_need);
+        if (spec_need) lead->d_clips_spec = arthip_grow (lead->d_clips_spec, &lead->clips_spec_cap, spec_need);
+        if (!table || !lead->d_clips || (tmp_need && !lead->d_clips_tmp) || (spec_need && !lead->d_clips_spec)) {
+            pcm_fail ("biquad clips: out of memory for the table or the scratch (nothing of the gathered calls launched)");
             rc = -1;
         }
-        for (int r = 0; r < nrounds && !rc; ++r) {
-            const ClipRound *rd = &rounds [r];
-            if (rd->ncopy) {
-                if (arthip_copy_rows_launch ((const char *) lead->d_clips + rd->copy_offset, rd->ncopy, rd->copy_tasks, lead->stream)) { pcm_fail ("biquad clips: launch failed"); rc = -1; break; }
-                ++launches;
-            }
-            if (r == 0 && nserial) {               /* what the batch entry gathers, there (behind the copy launch: their sections are put back) */
-                const int made = artamd_biquad_batch_planar (sbanks, nserial, sbufs, spitches, sframes, 0, -1);
-                if (made < 0) { rc = -1; break; }
-                launches += made;
-            }
-            for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
-                if (!rd->cls [k].count) continue;
-                if (arthip_biquad_clips_launch (&rd->cls [k], lead->d_clips, lead->stream)) { pcm_fail ("biquad clips: launch failed"); rc = -1; break; }
-                launches += 3;
-            }
-        }
-        if (!rc) rc = launches;
-        LEAVE_DEVICE (lead);
     }
+    for (int i = 0; i < n && !rc && bytes; ++i) {
+        const ClipPlan *p = &plan [i];
+        const BiquadBank *b = banks [i];
+        if (p->at.kind == CLIP_GATHERED) clips_fill_item (table, &rounds [p->at.round], p, b, d_buffers [i], numFrames [i], fromStart, lead);
+        else if (p->at.kind != CLIP_SIDE && fromStart)
+            clip_copy_item ((ArtCopyRows *)(table + rounds [0].copy_offset) + p->copy_slot, b->d_sections0, 0, b->d_sections, 0, bank_words (b), 1, p->copy_task0);
+    }
+    if (!rc && bytes) rc = table_to_device ("biquad clips: the table could not be uploaded (nothing of the gathered calls launched)", table, bytes, &lead->d_clips, NULL, lead->stream);
+    if (!rc) rc = clips_launch (rounds, nrounds, lead, sbanks, nserial, sbufs, spitches, sframes, &launches) ? -1 : launches;
+    LEAVE_DEVICE (lead);
 out:
     free (plan); free (rounds); free (sbanks); free (sbufs); free (spitches); free (sframes); free (table);
     return rc;
@@ -1557,141 +1595,118 @@ int biquadBankApplyClipsPlanarDevice (BiquadBank *const *banks, int n, artsample
  * Rounds are cut on the chunk-state bytes, the only scratch; each item's mismatch flags (C ints) lie behind its chunk states and
  * are armed by the speculative launch.  One table for the whole call: per round its classes' items, then the serial classes' lanes.
  * ---------------------------------------------------------------------------------------- */
-typedef struct { ClipPlace at; long in_pitch, out_pitch; size_t flags_at; } FilterPlan;
-typedef struct { size_t spec_bytes; ArtBqClipClass cls [BQ_CLIP_CLASSES]; } FilterRound;
+typedef struct { ClipPlace at; long in_pitch, out_pitch; size_t flags_at; } FilterPlan;       /* (the rounds are ClipRounds without copies) */
 
 /* samples from the first to behind the last one of an item's side */
 static size_t filter_extent (int C, long pitch, int frames) { return pitch ? (size_t)(C - 1) * (size_t) pitch + (size_t) frames : (size_t) frames * C; }
+
+/* the refusals: before anything is allocated or enqueued, and not counted */
+static int filter_refuses (BiquadBank *const *banks, int n, const artsample_t *const *d_ins, const long *in_pitches, artsample_t *const *d_outs,
+                           const long *out_pitches, const int *numFrames)
+{
+    for (int i = 0; i < n; ++i) {
+        const BiquadBank *b = banks [i];
+        if (numFrames [i] <= 0) continue;
+        if (!b || !d_ins [i] || !d_outs [i] || b->nshards || b->device != banks [0]->device) return 1;
+        const long ip = item_pitch (in_pitches, i, b->C), op = item_pitch (out_pitches, i, b->C);
+        if (!ip != !op || ip < 0 || op < 0 || (ip && ip < numFrames [i]) || (op && op < numFrames [i])) return 1;
+        const uintptr_t in0 = (uintptr_t) d_ins [i], in1 = in0 + filter_extent (b->C, ip, numFrames [i]) * sizeof (art_s);
+        const uintptr_t out0 = (uintptr_t) d_outs [i], out1 = out0 + filter_extent (b->C, op, numFrames [i]) * sizeof (art_s);
+        if (in0 < out1 && out0 < in1) return 1;
+    }
+    return banks [0]->nshards != 0;
+}
+
+/* launch: the serial classes, then round after round its classes, from lead->d_clips.  0, or -1 (reported) */
+static int filter_launch (const ArtBqClass *ser, const ClipRound *rounds, int nrounds, int reversed, const BiquadBank *lead, int *launches)
+{
+    for (int k = 0; k < 4; ++k)
+        if (ser [k].slice.count && launched (arthip_biquad_filter_batch_launch (&ser [k], lead->d_clips, reversed, lead->stream),
+                                             "biquad filter clips: launch failed", 1, launches)) return -1;
+    for (int r = 0; r < nrounds; ++r)
+        for (int k = 0; k < BQ_CLIP_CLASSES; ++k)
+            if (rounds [r].cls [k].count && launched (arthip_biquad_filter_clips_launch (&rounds [r].cls [k], lead->d_clips, reversed, lead->stream),
+                                                      "biquad filter clips: launch failed", 3, launches)) return -1;
+    return 0;
+}
 
 int artamd_biquad_filter_clips_planar (BiquadBank *const *banks, int n, const artsample_t *const *d_ins, const long *in_pitches,
                                        artsample_t *const *d_outs, const long *out_pitches, const int *numFrames, int reversed, long roundBytes)
 {
     if (n <= 0) return 0;
     if (!banks || !banks [0] || !numFrames || !d_ins || !d_outs) return -1;
+    if (filter_refuses (banks, n, d_ins, in_pitches, d_outs, out_pitches, numFrames)) return -1;
     const size_t bound = roundBytes > 0 ? (size_t) roundBytes : BQ_CLIPS_ROUND_BYTES;
     BiquadBank *lead = banks [0];
-
-    /* the refusals: before anything is allocated or enqueued, and not counted */
-    for (int i = 0; i < n; ++i) {
-        const BiquadBank *b = banks [i];
-        if (numFrames [i] <= 0) continue;
-        if (!b || !d_ins [i] || !d_outs [i] || b->nshards || b->device != lead->device) return -1;
-        const long ip = in_pitches && b->C > 1 ? in_pitches [i] : 0, op = out_pitches && b->C > 1 ? out_pitches [i] : 0;
-        if (!ip != !op || ip < 0 || op < 0 || (ip && ip < numFrames [i]) || (op && op < numFrames [i])) return -1;
-        const uintptr_t in0 = (uintptr_t) d_ins [i], in1 = in0 + filter_extent (b->C, ip, numFrames [i]) * sizeof (art_s);
-        const uintptr_t out0 = (uintptr_t) d_outs [i], out1 = out0 + filter_extent (b->C, op, numFrames [i]) * sizeof (art_s);
-        if (in0 < out1 && out0 < in1) return -1;
-    }
-    if (lead->nshards) return -1;
-
     FilterPlan *plan = calloc ((size_t) n, sizeof (FilterPlan));
-    FilterRound *rounds = calloc ((size_t) n + 1, sizeof (FilterRound));
-    DecLaneRef *refs = NULL;
-    unsigned char *table = NULL;
-    ArtBqClass ser [4];
+    ClipRound *rounds = calloc ((size_t) n + 1, sizeof (ClipRound));
+    int *ser_of = malloc (sizeof (int) * (size_t) n);                /* an item's serial class, S - 1, or -1 */
+    LaneRef *refs = NULL; unsigned char *table = NULL;
+    ArtBqClass ser [4] = { { 0 } };
     int launches = 0, rc = -1, nrounds = 1, maxlanes = 0;
-    memset (ser, 0, sizeof (ser));
-    if (!plan || !rounds) { pcm_fail ("biquad filter clips: out of host memory"); goto out; }
-
+    if (!plan || !rounds || !ser_of) { pcm_fail ("biquad filter clips: out of host memory"); goto out; }
     /* every item's route (the clips entry's rule) and place */
     for (int i = 0; i < n; ++i) {
         const BiquadBank *b = banks [i];
         FilterPlan *p = &plan [i];
         const int frames = numFrames [i];
+        ser_of [i] = -1;
         if (frames <= 0) { p->at.kind = CLIP_SKIP; continue; }
-        p->in_pitch = in_pitches && b->C > 1 ? in_pitches [i] : 0;              /* (one channel: the same call in either layout) */
-        p->out_pitch = out_pitches && b->C > 1 ? out_pitches [i] : 0;
-        if ((p->at.L = gathered_chunk (b->S, b->warmup, frames, BQ_BATCH_SERIAL_MAX)) != 0) {
-            p->at.kind = CLIP_GATHERED;
-            const size_t states = arthip_biquad_spec_scratch (b->C, b->S, frames, p->at.L);         /* (a multiple of 32 bytes: the flags lie aligned behind it) */
-            const size_t need = (states + sizeof (int) * (size_t) b->C + 255) & ~(size_t) 255;
-            FilterRound *r = &rounds [nrounds - 1];
-            if (r->spec_bytes && r->spec_bytes + need > bound) r = &rounds [nrounds++];
-            p->at.round = (int)(r - rounds);
-            p->at.spec_at = r->spec_bytes; p->flags_at = p->at.spec_at + states; r->spec_bytes += need;
-            clip_place (&p->at, r->cls, b, frames, p->in_pitch != 0);
-        }
-        else { p->at.kind = CLIP_SERIAL; ser [b->S - 1].slice.count += b->C; }
+        p->in_pitch = item_pitch (in_pitches, i, b->C); p->out_pitch = item_pitch (out_pitches, i, b->C);
+        if ((p->at.L = gathered_chunk (b->S, b->warmup, frames, BQ_BATCH_SERIAL_MAX)) == 0) { p->at.kind = CLIP_SERIAL; ser [ser_of [i] = b->S - 1].slice.count += b->C; continue; }
+        p->at.kind = CLIP_GATHERED;
+        const size_t states = arthip_biquad_spec_scratch (b->C, b->S, frames, p->at.L);         /* (a multiple of 32 bytes: the flags lie aligned behind it) */
+        const size_t need = (states + sizeof (int) * (size_t) b->C + 255) & ~(size_t) 255;
+        ClipRound *r = &rounds [nrounds - 1];
+        if (r->spec_bytes && r->spec_bytes + need > bound) r = &rounds [nrounds++];
+        p->at.round = (int)(r - rounds);
+        p->at.spec_at = r->spec_bytes; p->flags_at = p->at.spec_at + states; r->spec_bytes += need;
+        clip_place (&p->at, r->cls, b, frames, p->in_pitch != 0);
     }
 
-    /* the table: per round its classes' items, then the serial classes' lanes (+ empty lanes up to whole workgroups); 16-byte aligned slices */
-    size_t bytes = 0, spec_need = 0;
-    for (int r = 0; r < nrounds; ++r) {
-        bytes = clip_classes_layout (rounds [r].cls, bytes);
-        if (rounds [r].spec_bytes > spec_need) spec_need = rounds [r].spec_bytes;
-    }
-    for (int k = 0; k < 4; ++k) {
-        if (!ser [k].slice.count) continue;
-        ser [k].S = k + 1;
-        ser [k].slice.lanes = arthip_biquad_batch_lanes (ser [k].slice.count);
-        ser [k].slice.count = (ser [k].slice.count + ser [k].slice.lanes - 1) / ser [k].slice.lanes * ser [k].slice.lanes;
-        if (ser [k].slice.count > maxlanes) maxlanes = ser [k].slice.count;
-        ser [k].slice.offset = bytes;
-        bytes += (sizeof (ArtBqFilterLane) * (size_t) ser [k].slice.count + 15) & ~(size_t) 15;
-    }
+    /* the table: per round its classes' items, then the serial classes' lanes */
+    size_t tmp_need = 0, spec_need = 0, bytes = clip_rounds_layout (rounds, nrounds, &tmp_need, &spec_need);
+    bq_serial_layout (ser, 0, sizeof (ArtBqFilterLane), &bytes, &maxlanes);
     if (!bytes) { rc = 0; goto out; }
     table = calloc (1, bytes);
-    refs = malloc (sizeof (DecLaneRef) * (size_t)(maxlanes ? maxlanes : 1));
+    refs = malloc (sizeof (LaneRef) * (size_t)(maxlanes ? maxlanes : 1));
     if (!table || !refs) { pcm_fail ("biquad filter clips: out of host memory"); goto out; }
 
-    {
-        ENTER_DEVICE (lead);
-        rc = 0;
-        lead->d_clips = arthip_grow (lead->d_clips, &lead->clips_cap, bytes);
-        if (spec_need) lead->d_clips_spec = arthip_grow (lead->d_clips_spec, &lead->clips_spec_cap, spec_need);
-        if (!lead->d_clips || (spec_need && !lead->d_clips_spec)) {
-            pcm_fail ("biquad filter clips: out of memory for the table or the chunk states (nothing launched)");
-            rc = -1;
-        }
-        for (int i = 0; i < n && !rc; ++i) {
-            const FilterPlan *p = &plan [i];
-            const BiquadBank *b = banks [i];
-            if (p->at.kind != CLIP_GATHERED) continue;
-            ArtBqClip *it = clip_item (table, rounds [p->at.round].cls, &p->at, b, numFrames [i], (char *) lead->d_clips_spec + p->at.spec_at);
-            it->from = b->d_sections0; it->sections = NULL;
-            it->in = d_ins [i]; it->out = d_outs [i];
-            it->in_stride = p->in_pitch ? p->in_pitch : b->C; it->out_stride = p->out_pitch ? p->out_pitch : b->C;
-            it->first_bad = (int *)((char *) lead->d_clips_spec + p->flags_at); it->repairs = lead->d_repairs;
-        }
-        for (int k = 0; k < 4 && !rc; ++k) {
-            if (!ser [k].slice.count) continue;
-            int m = 0;
-            for (int i = 0; i < n; ++i)
-                if (plan [i].at.kind == CLIP_SERIAL && banks [i]->S == k + 1)
-                    for (int c = 0; c < banks [i]->C; ++c) { refs [m].ctx = i; refs [m].channel = c; refs [m].frames = numFrames [i]; ++m; }
-            qsort (refs, (size_t) m, sizeof (DecLaneRef), lane_order);
-            ArtBqFilterLane *l = (ArtBqFilterLane *)(table + ser [k].slice.offset);      /* (the padding lanes stay zero: 0 frames) */
-            for (int j = 0; j < m; ++j) {
-                const int i = refs [j].ctx, c = refs [j].channel;
-                const BiquadBank *b = banks [i];
-                const FilterPlan *p = &plan [i];
-                l [j].sections = b->d_sections0 + (size_t) c * b->S;
-                l [j].in = d_ins [i] + (p->in_pitch ? (size_t) c * p->in_pitch : (size_t) c);
-                l [j].out = d_outs [i] + (p->out_pitch ? (size_t) c * p->out_pitch : (size_t) c);
-                l [j].in_stride = p->in_pitch ? 1 : b->C; l [j].out_stride = p->out_pitch ? 1 : b->C;
-                l [j].frames = refs [j].frames;
-            }
-        }
-        if (!rc && arthip_table_upload (table, bytes, lead->d_clips, lead->stream)) {
-            pcm_fail ("biquad filter clips: the table could not be uploaded (nothing launched)");
-            rc = -1;
-        }
-        for (int k = 0; k < 4 && !rc; ++k) {
-            if (!ser [k].slice.count) continue;
-            if (arthip_biquad_filter_batch_launch (&ser [k], lead->d_clips, reversed != 0, lead->stream)) { pcm_fail ("biquad filter clips: launch failed"); rc = -1; break; }
-            ++launches;
-        }
-        for (int r = 0; r < nrounds && !rc; ++r)
-            for (int k = 0; k < BQ_CLIP_CLASSES; ++k) {
-                if (!rounds [r].cls [k].count) continue;
-                if (arthip_biquad_filter_clips_launch (&rounds [r].cls [k], lead->d_clips, reversed != 0, lead->stream)) { pcm_fail ("biquad filter clips: launch failed"); rc = -1; break; }
-                launches += 3;
-            }
-        if (!rc) rc = launches;
-        LEAVE_DEVICE (lead);
+    ENTER_DEVICE (lead);
+    rc = 0;
+    lead->d_clips = arthip_grow (lead->d_clips, &lead->clips_cap, bytes);
+    if (spec_need) lead->d_clips_spec = arthip_grow (lead->d_clips_spec, &lead->clips_spec_cap, spec_need);
+    if (!lead->d_clips || (spec_need && !lead->d_clips_spec)) {
+        pcm_fail ("biquad filter clips: out of memory for the table or the chunk states (nothing launched)");
+        rc = -1;
     }
+    for (int i = 0; i < n && !rc; ++i) {         /* the gathered items: chunk states and, behind them, flags in the lead's d_clips_spec */
+        const FilterPlan *p = &plan [i];
+        const BiquadBank *b = banks [i];
+        if (p->at.kind != CLIP_GATHERED) continue;
+        ArtBqClip *it = clip_item (table, rounds [p->at.round].cls, &p->at, b, numFrames [i], (char *) lead->d_clips_spec + p->at.spec_at);
+        it->from = b->d_sections0; it->sections = NULL;
+        it->in = d_ins [i]; it->out = d_outs [i];
+        it->in_stride = p->in_pitch ? p->in_pitch : b->C; it->out_stride = p->out_pitch ? p->out_pitch : b->C;
+        it->first_bad = (int *)((char *) lead->d_clips_spec + p->flags_at); it->repairs = lead->d_repairs;
+    }
+    for (int k = 0; k < 4 && !rc; ++k) {
+        if (!ser [k].slice.count) continue;
+        const int m = class_lanes (refs, k, n, ser_of, (const void *const *) banks, bank_channels, numFrames);
+        ArtBqFilterLane *l = (ArtBqFilterLane *)(table + ser [k].slice.offset);      /* (the padding lanes stay zero: 0 frames) */
+        for (int j = 0; j < m; ++j) {
+            const int i = refs [j].item, c = refs [j].channel, C = banks [i]->C;
+            const LaneSide in = lane_side (plan [i].in_pitch, c, C, 1), out = lane_side (plan [i].out_pitch, c, C, 1);
+            l [j].sections = banks [i]->d_sections0 + (size_t) c * banks [i]->S;
+            l [j].in = d_ins [i] + in.offset; l [j].out = d_outs [i] + out.offset;
+            l [j].in_stride = in.stride; l [j].out_stride = out.stride; l [j].frames = refs [j].frames;
+        }
+    }
+    if (!rc) rc = table_to_device ("biquad filter clips: the table could not be uploaded (nothing launched)", table, bytes, &lead->d_clips, NULL, lead->stream);
+    if (!rc) rc = filter_launch (ser, rounds, nrounds, reversed != 0, lead, &launches) ? -1 : launches;
+    LEAVE_DEVICE (lead);
 out:
-    free (plan); free (rounds); free (refs); free (table);
+    free (plan); free (rounds); free (ser_of); free (refs); free (table);
     return rc;
 }
 
@@ -1719,23 +1734,6 @@ long decimateHipClipped (Decimate *cxt)
     arthip_sync (cxt->hip->stream);
     LEAVE_DEVICE (cxt->hip);
     return (long) total;
-}
-
-static int dec_reserve (Decimate *cxt, size_t in_bytes, size_t out_bytes)
-{
-    struct artamd_decimator *hip = cxt->hip;
-    in_bytes += 16; out_bytes += 16;                    /* (copy kernels move whole words) */
-    if (in_bytes > hip->in_cap) { arthip_free (hip->d_in); hip->in_cap = in_bytes * 2; if (!(hip->d_in = arthip_malloc (hip->in_cap))) { hip->in_cap = 0; return -1; } }
-    if (out_bytes > hip->out_cap) { arthip_free (hip->d_out); hip->out_cap = out_bytes * 2; if (!(hip->d_out = arthip_malloc (hip->out_cap))) { hip->out_cap = 0; return -1; } }
-    if (in_bytes <= DEC_KERNEL_COPY_LIMIT && in_bytes > hip->h_in_cap) {
-        arthip_host_free (hip->h_in); hip->h_in_cap = in_bytes * 2;
-        if (!(hip->h_in = arthip_host_alloc (hip->h_in_cap))) { hip->h_in_cap = 0; return -1; }
-    }
-    if (out_bytes <= DEC_KERNEL_COPY_LIMIT && out_bytes > hip->h_out_cap) {
-        arthip_host_free (hip->h_out); hip->h_out_cap = out_bytes * 2;
-        if (!(hip->h_out = arthip_host_alloc (hip->h_out_cap))) { hip->h_out_cap = 0; return -1; }
-    }
-    return 0;
 }
 
 /* after a host-pointer call: bring back the output (out_bytes from d_out; NULL destination: the caller fetched it itself)

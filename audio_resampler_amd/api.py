@@ -199,6 +199,7 @@ def _bind(width):
         "resampleProcessScheduleBatchPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleProcessScheduleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr, ptr]),
         "resampleAdjointScheduleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleRateGradientScheduleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
     }
 
     _state = {"lib": None}
@@ -1569,7 +1570,9 @@ def _bind(width):
             raise RuntimeError("artamdLagProductsBatchDevice failed")
         return rc
 
-    return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k != "width"}, width=width)
+    # (_private: the helpers above for the modules beside this one — rate_grad.py — which add to the binding without copying them)
+    return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k != "width"}, width=width,
+                                 _private=types.SimpleNamespace(**{k: v for k, v in locals().items() if k.startswith("_") and callable(v)}))
 
 
 _bound = {}
@@ -1589,4 +1592,4 @@ def wide():
     return binding(64)
 
 
-globals().update({k: v for k, v in vars(binding(32)).items() if k != "width"})      # module level = the 4-byte build
+globals().update({k: v for k, v in vars(binding(32)).items() if k not in ("width", "_private")})      # module level = the 4-byte build

@@ -288,6 +288,31 @@ size_t arthip_fir_adjoint_blocks_bytes (int nitems, int nphases, int nsegs);
 /* as arthip_fir_adjoint: one launch per kernel variant present; items, phases and segments go to d_table in one upload */
 int arthip_fir_adjoint_blocks (const ArtAdjBlocksItem *items, int n, const ArtAdjPhase *phases, int nphases, const ArtamdSegment *segs, int nsegs,
                                void *d_table, void *stream);
+/* ---- fir_rate_grad.hip: the gradient of such clips with respect to their blocks' ratios (resampleRateGradientScheduleClipsPlanarDevice) ----
+ * An item is one clip on an interpolating context: its phases are the blocks adjoint's (the same ArtAdjPhase table, the last the flush), its
+ * samples are read where that kernel writes gx.  The first launch's tasks are tiles of ART_RATE_TILE consecutive outputs of one phase; a
+ * phase without outputs has none. */
+#define ART_RATE_TILE 256
+typedef struct {
+    const art_s *bank;                   /* device, (F+1) x T */
+    const art_s *x;                      /* the clip's samples: in_frames frames */
+    const art_s *gy;                     /* gradient of the outputs: gy_frames frames, the rest of the clip's outputs count as zero */
+    double *grad;                        /* phase_count - 1 doubles are SET: dL/dr of every block */
+    long x_pitch, gy_pitch;              /* samples between planes; 0: that side interleaved */
+    unsigned int gy_frames;
+    int phase_first, phase_count;        /* the clip's phases in the call's phase table (>= 2; the last is the flush) */
+    int in_frames, C, T, F;              /* in_frames >= 0 (an empty clip: gy_frames 0, a zero for its block) */
+    int pad;
+} ArtRateItem;
+size_t arthip_fir_rate_grad_bytes (int nitems, int nphases, int nsegs, unsigned long tiles);
+/* ceil (outputs / ART_RATE_TILE) summed over the phases: what the call's scratch holds a pair of doubles for */
+unsigned long arthip_fir_rate_grad_tiles (const ArtAdjPhase *phases, int nphases);
+/* Two launches — the tiles' partial sums, then one wave per clip (one launch where no phase has an output).  Items, phases, the phases' first
+ * tasks and the segments go to d_table (device memory of arthip_fir_rate_grad_bytes bytes, reused call after call: stream order protects it) in
+ * one upload; the partials follow them there.  Returns the number of launches enqueued, or -1 (a launch failed; nothing enqueued where the
+ * upload could not be made). */
+int arthip_fir_rate_grad (const ArtRateItem *items, int n, const ArtAdjPhase *phases, int nphases, const ArtamdSegment *segs, int nsegs,
+                          void *d_table, void *stream);
 /* the upkeep every launch of a rational-ratio stream does for the rows kept across calls (arthip_fir calls it itself) */
 void arthip_fir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs);
 /* new_hist[H][C] = last H frames of (hist ++ in[0..appended)); in may be NULL => zeros appended */

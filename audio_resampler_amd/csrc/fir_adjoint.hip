@@ -24,10 +24,6 @@ constexpr int ADJ_CHUNK = 256;           // outputs per trip through the LDS
 constexpr int ADJ_UNROLL = 4;            // outputs whose coefficient loads are in flight together
 static_assert (ADJ_CHUNK % ADJ_UNROLL == 0, "whole groups per chunk");
 
-// what locate () reads of its arguments, and the phase's segments where the upload left them
-struct AdjRate { double ratio; int F; };
-struct AdjSegs { int count; const unsigned int *first; const int *lin_base; const double *base; };
-
 // window start of output n (linear index of its first tap)
 template <bool INTERP>
 __device__ __forceinline__ int adj_window (const AdjRate &r, const AdjSegs &s, unsigned int n, int half)

@@ -113,6 +113,11 @@ __device__ __forceinline__ art_s direct_sample (const ArtFirArgs &a, int lin_flo
     return (art_s)(left + right);
 }
 
+// what locate () reads of its arguments, and a planned call's segments where an upload left them in device memory (fir_adjoint.hip,
+// fir_rate_grad.hip: the kernels that place a whole clip's outputs phase by phase)
+struct AdjRate { double ratio; int F; };
+struct AdjSegs { int count; const unsigned int *first; const int *lin_base; const double *base; };
+
 // Cross-lane reduction of NV per-lane partial sums, carried out in fp64 so that the handful of
 // large-magnitude additions near the root of the tree do not each cost half a float ulp.
 // Halving butterfly: at every level half of the values change hands, so NV values cost

@@ -2066,6 +2066,52 @@ static int adjoint_plan_blocks (const Resample *cxt, int numBlocks, const int *f
     return 0;
 }
 
+/* What both gradient entries of such clips refuse before anything is planned, the same way: 1 for a NULL context, a context with
+ * EXTRAPOLATE_ENDPOINTS, a sharded one, one on another device or stream than cxts [0], and per item with blocks a NULL block array, a negative
+ * count, more than INT_MAX frames, or a NULL buffer (`one` [i], `other` [i]: the entry's two sample buffers) where the clip has frames. */
+static int clip_blocks_refused (Resample *const *cxts, int n, const int *numBlocks, const int *numOutputFrames, const int *const *numInputFrames,
+                                const double *const *ratios, const void *const *one, const void *const *other)
+{
+    for (int i = 0; i < n; ++i) if (!cxts [i]) return 1;
+
+    const struct artamd_resampler *lead = cxts [0]->hip;
+    for (int i = 0; i < n; ++i) {
+        const struct artamd_resampler *hip = cxts [i]->hip;
+        if ((cxts [i]->flags & EXTRAPOLATE_ENDPOINTS) || hip->nshards || hip->device != lead->device || hip->stream != lead->stream) return 1;
+        if (numBlocks [i] <= 0) continue;
+        if (!numInputFrames [i] || numOutputFrames [i] < 0) return 1;
+        if (!ratios [i] && !(cxts [i]->flags & RESAMPLE_FIXED_RATIO)) return 1;
+        long frames = 0;
+        for (int k = 0; k < numBlocks [i]; ++k) {
+            if (numInputFrames [i] [k] < 0) return 1;
+            if ((frames += numInputFrames [i] [k]) > INT_MAX) return 1;
+        }
+        if (frames > 0 && (!one [i] || !other [i])) return 1;
+    }
+    return 0;
+}
+
+/* The phase replay of both entries: every item with blocks is planned (numOutputFrames [i] <= M_i is asked of an empty clip too) into items
+ * [0, live), `which` [q] the call's index of item q; an empty clip is an item only where keep_empty.  Returns live, or -1 (out of memory) or -2
+ * (refused: a clip adjoint_plan_blocks refuses, numOutputFrames [i] > M_i). */
+static int clip_blocks_plan (Resample *const *cxts, int n, const int *numBlocks, const int *numOutputFrames, const int *const *numInputFrames,
+                             const double *const *ratios, int keep_empty, ArtAdjBlocksItem *items, int *which, AdjointPhases *phases, AdjointSegs *list)
+{
+    int live = 0;
+    for (int i = 0; i < n; ++i) {
+        if (numBlocks [i] <= 0) continue;
+        ArtAdjBlocksItem *it = &items [live];
+        const int kept = list->count, kept_phases = phases->count;
+        unsigned long outputs = 0;
+        const int planned = adjoint_plan_blocks (cxts [i], numBlocks [i], numInputFrames [i], ratios [i], it, &outputs, phases, list);
+        if (planned) return planned;
+        if ((unsigned long) numOutputFrames [i] > outputs) return -2;
+        if (!it->in_frames && !keep_empty) { list->count = kept; phases->count = kept_phases; continue; }
+        which [live++] = i;
+    }
+    return live;
+}
+
 int resampleAdjointScheduleClipsPlanarDevice (Resample *const *cxts, int n, const int *numBlocks,
         const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
         artsample_t *const *d_gradInputs, const long *gradInputPitches,
@@ -2073,41 +2119,24 @@ int resampleAdjointScheduleClipsPlanarDevice (Resample *const *cxts, int n, cons
 {
     if (n <= 0) return 0;
     if (!cxts || !numBlocks || !d_gradOutputs || !numOutputFrames || !d_gradInputs || !numInputFrames || !ratios) return -1;
-    for (int i = 0; i < n; ++i) if (!cxts [i]) return -1;
+    if (clip_blocks_refused (cxts, n, numBlocks, numOutputFrames, numInputFrames, ratios, (const void *const *) d_gradOutputs, (const void *const *) d_gradInputs))
+        return -1;
 
+    /* the empty clips are no items of the launches */
     struct artamd_resampler *lead = cxts [0]->hip;
-    for (int i = 0; i < n; ++i) {
-        const struct artamd_resampler *hip = cxts [i]->hip;
-        if ((cxts [i]->flags & EXTRAPOLATE_ENDPOINTS) || hip->nshards || hip->device != lead->device || hip->stream != lead->stream) return -1;
-        if (numBlocks [i] <= 0) continue;
-        if (!numInputFrames [i] || numOutputFrames [i] < 0) return -1;
-        if (!ratios [i] && !(cxts [i]->flags & RESAMPLE_FIXED_RATIO)) return -1;
-        long frames = 0;
-        for (int k = 0; k < numBlocks [i]; ++k) {
-            if (numInputFrames [i] [k] < 0) return -1;
-            if ((frames += numInputFrames [i] [k]) > INT_MAX) return -1;
-        }
-        if (frames > 0 && (!d_gradOutputs [i] || !d_gradInputs [i])) return -1;
-    }
-
-    /* every item with blocks is planned (numOutputFrames [i] <= M_i is asked of an empty clip too); the empty ones are no items of the launches */
     ArtAdjBlocksItem *items = malloc (sizeof (ArtAdjBlocksItem) * (size_t) n);
+    int *which = malloc (sizeof (int) * (size_t) n);
     AdjointSegs list = { NULL, 0, 0 };
     AdjointPhases phases = { NULL, 0, 0 };
     int live = 0, rc = -1, refused = 0;
-    if (!items) goto out;
-    for (int i = 0; i < n; ++i) {
-        if (numBlocks [i] <= 0) continue;
-        ArtAdjBlocksItem *it = &items [live];
-        const int kept = list.count, kept_phases = phases.count;
-        unsigned long outputs = 0;
-        const int planned = adjoint_plan_blocks (cxts [i], numBlocks [i], numInputFrames [i], ratios [i], it, &outputs, &phases, &list);
-        if (planned) { refused = planned == -2; goto out; }
-        if ((unsigned long) numOutputFrames [i] > outputs) { refused = 1; goto out; }
-        if (!it->in_frames) { list.count = kept; phases.count = kept_phases; continue; }
+    if (!items || !which) goto out;
+    live = clip_blocks_plan (cxts, n, numBlocks, numOutputFrames, numInputFrames, ratios, 0, items, which, &phases, &list);
+    if (live < 0) { refused = live == -2; goto out; }
+    for (int q = 0; q < live; ++q) {
+        ArtAdjBlocksItem *it = &items [q];
+        const int i = which [q];
         it->gy = d_gradOutputs [i]; it->gy_pitch = gradOutputPitches ? gradOutputPitches [i] : 0; it->gy_frames = (unsigned int) numOutputFrames [i];
         it->gx = d_gradInputs [i]; it->gx_pitch = gradInputPitches ? gradInputPitches [i] : 0;
-        ++live;
     }
     if (!live) { rc = 0; goto out; }
 
@@ -2121,6 +2150,70 @@ int resampleAdjointScheduleClipsPlanarDevice (Resample *const *cxts, int n, cons
 out:
     if (rc < 0 && !refused) artamd_note_failure ("resampler: a launch of the schedule clips adjoint failed");
     free (items);
+    free (which);
+    free (phases.phases);
+    free (list.segs);
+    return rc;
+}
+
+/* resampleRateGradientScheduleClipsPlanarDevice (art_hip.h): the gradient of the same clips with respect to their blocks' ratios, from the same
+ * phase replay; fir_rate_grad.hip reads the samples where the adjoint writes their gradient.  An empty clip is an item too (its block gets
+ * a zero), with no gradient frames to read. */
+int resampleRateGradientScheduleClipsPlanarDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_inputs, const long *inputPitches,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
+        const int *const *numInputFrames, const double *const *ratios,
+        double *const *d_gradRatios)
+{
+    if (n <= 0) return 0;
+    if (!cxts || !numBlocks || !d_inputs || !d_gradOutputs || !numOutputFrames || !numInputFrames || !ratios || !d_gradRatios) return -1;
+    if (clip_blocks_refused (cxts, n, numBlocks, numOutputFrames, numInputFrames, ratios, (const void *const *) d_gradOutputs, (const void *const *) d_inputs))
+        return -1;
+    for (int i = 0; i < n; ++i) {
+        /* (without interpolation an output does not move with the ratio until it changes rows: a gradient of zero almost everywhere; a
+         * fixed-ratio context ignores the ratios it would be the gradient of) */
+        if (!(cxts [i]->flags & SUBSAMPLE_INTERPOLATE) || (cxts [i]->flags & RESAMPLE_FIXED_RATIO)) return -1;
+        if (numBlocks [i] > 0 && !d_gradRatios [i]) return -1;
+    }
+
+    struct artamd_resampler *lead = cxts [0]->hip;
+    ArtAdjBlocksItem *planned = malloc (sizeof (ArtAdjBlocksItem) * (size_t) n);
+    ArtRateItem *items = malloc (sizeof (ArtRateItem) * (size_t) n);
+    int *which = malloc (sizeof (int) * (size_t) n);
+    AdjointSegs list = { NULL, 0, 0 };
+    AdjointPhases phases = { NULL, 0, 0 };
+    int live = 0, rc = -1, refused = 0;
+    if (!planned || !items || !which) goto out;
+    live = clip_blocks_plan (cxts, n, numBlocks, numOutputFrames, numInputFrames, ratios, 1, planned, which, &phases, &list);
+    if (live < 0) { refused = live == -2; goto out; }
+    if (arthip_fir_rate_grad_tiles (phases.phases, phases.count) > (unsigned long) INT_MAX) { refused = 1; goto out; }
+    for (int q = 0; q < live; ++q) {
+        const ArtAdjBlocksItem *from = &planned [q];
+        ArtRateItem *it = &items [q];
+        const int i = which [q];
+        memset (it, 0, sizeof (*it));
+        it->bank = from->bank; it->in_frames = from->in_frames; it->C = from->C; it->T = from->T; it->F = from->F;
+        it->phase_first = from->phase_first; it->phase_count = from->phase_count;
+        it->x = d_inputs [i]; it->x_pitch = inputPitches ? inputPitches [i] : 0;
+        it->gy = d_gradOutputs [i]; it->gy_pitch = gradOutputPitches ? gradOutputPitches [i] : 0;
+        it->gy_frames = from->in_frames ? (unsigned int) numOutputFrames [i] : 0;
+        it->grad = d_gradRatios [i];
+    }
+    if (!live) { rc = 0; goto out; }
+
+    {
+        ENTER_DEVICE (lead);
+        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap,
+                                     arthip_fir_rate_grad_bytes (live, phases.count, list.count, arthip_fir_rate_grad_tiles (phases.phases, phases.count)));
+        rc = lead->d_batch ? arthip_fir_rate_grad (items, live, phases.phases, phases.count, list.segs, list.count, lead->d_batch, lead->stream) : -1;
+        if (rc < 0) fprintf (stderr, "artamd: resample rate gradient: launch failed: %s\n", arthip_last_error ());
+        LEAVE_DEVICE (lead);
+    }
+out:
+    if (rc < 0 && !refused) artamd_note_failure ("resampler: a launch of the schedule clips rate gradient failed");
+    free (planned);
+    free (items);
+    free (which);
     free (phases.phases);
     free (list.segs);
     return rc;

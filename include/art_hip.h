@@ -327,7 +327,7 @@ int resampleProcessScheduleClipsPlanarDevice (Resample *const *cxts, int n, cons
  * frames and M_i the total output, frames 0 .. N_i - 1 of every plane of d_gradInputs [i] are SET to A_i^T gy_i, gy_i the first
  * numOutputFrames [i] frames of d_gradOutputs [i] (output frames past that count as zero gradient); nothing else is written.  Pitches as
  * in resampleAdjointClipsPlanarDevice.  For RESAMPLE_FIXED_RATIO contexts `ratios` is ignored (ratios [i] may be NULL), as the forward
- * ignores it.  The ratios get no gradient.
+ * ignores it.  The ratios get no gradient here: resampleRateGradientScheduleClipsPlanarDevice, below, is theirs.
  * The clip is K + 1 phases, each linear in the samples: K + 1 artamdPlanCall replays on one fresh position (every process call with all
  * the room an int counts, the last the flush's call of silence), each with its own ratio, segments, output count and floor.  Phase k sees
  * input frame j at linear index H + j - s_k (s_k: the frames of the blocks before it; the flush: N_i) and reads nothing below
@@ -351,6 +351,43 @@ int resampleAdjointScheduleClipsPlanarDevice (Resample *const *cxts, int n, cons
         const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
         artsample_t *const *d_gradInputs, const long *gradInputPitches,
         const int *const *numInputFrames, const double *const *ratios);
+/* The gradient of the same clips with respect to their blocks' RATIOS, on contexts with SUBSAMPLE_INTERPOLATE: the clip of item i as in the
+ * entry above (a fresh context of cxts [i]'s parameters, the blocks in turn, then the flush at the last block's ratio), x_i the first N_i
+ * frames of every plane of d_inputs [i], gy_i the first numOutputFrames [i] frames of d_gradOutputs [i] (output frames past that count as
+ * zero gradient and are not read; frames of x_i past N_i are not read).  The numBlocks [i] doubles of d_gradRatios [i] (device memory) are
+ * SET to dL/d ratios [i][k] for L = sum gy_i y_i; nothing else is written.  An item with numBlocks [i] <= 0 writes nothing; an empty clip
+ * (one block of no frames) gets a zero.  Pitches as in resampleAdjointClipsPlanarDevice.
+ * The clip is the K + 1 phases of the entry above; write rho_k for phase k's ratio (rho_k = r_k for k < K, rho_K = r_{K-1}: the flush) and
+ * n_k for its output count.  Output n of phase k sits at p = o_k + n / rho_k (n ? n / ratio : 0, as locate () evaluates it), with
+ * o_{k+1} = o_k + n_k / rho_k.  It is the lerp of the dot products with bank rows fi and fi + 1, fi = floor (frac (p) F), so it is
+ * piecewise linear in p with the slope D = F sum_t (bank [fi + 1][t] - bank [fi][t]) x [ip + t].  THE KINK: on an exact filter boundary
+ * (frac F an integer) the derivative is the slope of the cell the forward used — the one locate ()'s floor picks, the upper — and no
+ * average is taken.  The output counts n_k, piecewise constant in the ratios, are held fixed.  Then, over the channels and the phase's
+ * outputs, S0_k = sum gy D and S1_k = sum n gy D give
+ *     dL/d rho_k = -(S1_k + n_k sum_{m > k} S0_m) / rho_k^2,   dL/d r_k = dL/d rho_k (k < K - 1),   dL/d r_{K-1} = dL/d rho_{K-1} + dL/d rho_K.
+ * THE TERM ORDER, in fp64 in both builds: per output and channel D = F * (one chain of fused multiply-adds of
+ * ((double) bank [fi + 1][t] - (double) bank [fi][t]) and (double) x, t ascending over the taps the phase may read — a tap before the
+ * clip, at or past the phase's end or below its floor is left out, not multiplied by zero, so a non-finite neighbour stays out);
+ * v = (double) gy * D; the output's pair is (sum_ch v, n * sum_ch v), the channels in order.  The pairs of a tile of 256 consecutive
+ * outputs of a phase are added by a butterfly over each wave of 64 and the four waves in order; a phase's tiles in ascending order; the
+ * S0 of the phases behind phase k one by one from the flush down; then 0 - (S1_k + n_k * behind) / (rho_k * rho_k), and for the last
+ * block dL/d rho_{K-1} + dL/d rho_K in that order.  No atomics: the result is the same bit for bit whatever the batch, the item's place
+ * in it, the layout, the pitch or the stream.
+ * Two launches (fir_rate_grad.hip: the tiles' partial sums in one flattened task space over the call, then one wave per clip); a phase
+ * without outputs has no tile, and a call none of whose phases has an output is the second launch alone.
+ * The contexts are only READ, and a context may be listed any number of times.  Asynchronous on the stream of cxts [0]; the items, phases
+ * and segments ride in the lead context's batch table in one upload and the tiles' partial sums lie behind them there: no allocation on
+ * the device once warm.
+ * Returns the number of launches enqueued; 0 for n <= 0 or when every item has numBlocks [i] <= 0.  -1 with nothing enqueued and nothing
+ * counted for everything the entry above refuses (d_inputs in the place of its d_gradInputs), a NULL d_gradRatios [i] of an item with
+ * blocks, a context without SUBSAMPLE_INTERPOLATE (the nearest filter does not move with the ratio: the gradient would be zero almost
+ * everywhere) and a RESAMPLE_FIXED_RATIO context (it ignores the ratios).  -1 if a launch failed (counted once in artamdErrorCount): the
+ * gradient buffers are then unspecified. */
+int resampleRateGradientScheduleClipsPlanarDevice (Resample *const *cxts, int n, const int *numBlocks,
+        const artsample_t *const *d_inputs, const long *inputPitches,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
+        const int *const *numInputFrames, const double *const *ratios,
+        double *const *d_gradRatios);
 
 /* ---- host-only building blocks (no GPU needed; used by the CPU test-suite) ---- */
 /* (numFilters+1) x numTaps bank exactly as resampleInit builds it (reference resampler.c:149-168, 1090-1133) */

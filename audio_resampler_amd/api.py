@@ -200,6 +200,9 @@ def _bind(width):
         "resampleProcessScheduleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, C.c_int, ptr, ptr]),
         "resampleAdjointScheduleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleRateGradientScheduleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleSampleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleSampleAdjointClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleSamplePositionGradientClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
     }
 
     _state = {"lib": None}

@@ -15,14 +15,10 @@
 // accumulation's explicit one.
 #include <cstring>
 #include "fir_common.hip.h"
+#include "fir_adjoint_walk.hip.h"        // ADJ_TILE, ADJ_CHUNK, ADJ_UNROLL and adj_walk: the blocks kernel's walk, shared with fir_sample.hip
 #include "staging.hip.h"
 
 namespace {
-
-constexpr int ADJ_TILE = 256;            // input frames per workgroup = its threads
-constexpr int ADJ_CHUNK = 256;           // outputs per trip through the LDS
-constexpr int ADJ_UNROLL = 4;            // outputs whose coefficient loads are in flight together
-static_assert (ADJ_CHUNK % ADJ_UNROLL == 0, "whole groups per chunk");
 
 // window start of output n (linear index of its first tap)
 template <bool INTERP>
@@ -41,83 +37,6 @@ __device__ int adj_first_above (const AdjRate &r, const AdjSegs &s, unsigned int
         if (adj_window<INTERP> (r, s, mid, half) > bound) hi = mid; else lo = mid + 1;
     }
     return (int) lo;
-}
-
-// One phase's share of a lane's sum: the outputs [n_begin, n_end) of the phase (g0: its first output among the clip's), whose windows may hold the
-// lane's frame at linear index `lin` of the phase's space (live: the lane has a frame there at all), in chunks of ADJ_CHUNK through the LDS.
-// Every thread of the workgroup calls it with the same range.  It is fir_adjoint_kernel's chunk loop line for line, and written so that that
-// kernel could call it too (Item: ArtAdjItem or ArtAdjBlocksItem — bank, gy, gy_pitch, gy_frames, C, T, F, lowpass); it does not, because with
-// the call in place the compiler allocates that kernel's registers differently (1-3 SGPRs more in thirteen of the sixteen
-// instantiations, +-2 VGPRs in three: profiles/clip_warp.txt), and the two-phase kernel keeps the code object it was measured with.
-// A change to the arithmetic is made in both places; tests/test_gpu_clip_warp.py holds the two kernels to the same bits on one-block
-// clips.
-template <int CG, bool INTERP, typename Item>
-__device__ __forceinline__ void adj_walk (art_s (&acc) [CG], const Item &it, const AdjRate &rate, const AdjSegs &segs, int ch0, int tid, int lin, bool live,
-                                          unsigned int g0, int n_begin, int n_end, int *s_w, int *s_row, int *s_pass, double *s_f0, double *s_f1, art_s *s_gy)
-{
-    const art_s *const bank = it.bank;
-    const int T = it.T, half = T / 2;
-
-    for (int n0 = n_begin; n0 < n_end; n0 += ADJ_CHUNK) {
-        const int cnt = min (ADJ_CHUNK, n_end - n0);
-        __syncthreads ();                          // (the chunk before is done with)
-        if (tid < cnt) {
-            const Pos pos = locate<INTERP> (rate, segs, (unsigned int)(n0 + tid));
-            s_w [tid] = pos.ip - half + 1;
-            s_row [tid] = pos.fi * T;
-            if (INTERP) { s_f0 [tid] = 1.0 - pos.frac; s_f1 [tid] = pos.frac; }
-            else s_pass [tid] = (!it.lowpass && (pos.fi % it.F) == 0) ? half - 1 + pos.fi / it.F : -1;
-        }
-        // gy of the chunk for the channel group: zero past the frames handed in, past the item's channels and — the loop below takes whole
-        // groups of ADJ_UNROLL outputs — past the chunk's last output up to the end of its group
-        const int cntu = (cnt + ADJ_UNROLL - 1) / ADJ_UNROLL * ADJ_UNROLL;
-        for (int e = tid; e < cntu * CG; e += ADJ_TILE) {
-            int i, c;
-            if (it.gy_pitch) { c = e / cntu; i = e - c * cntu; } else { i = e / CG; c = e - i * CG; }
-            const unsigned int g = g0 + (unsigned int)(n0 + i);
-            art_s v = 0;
-            if (i < cnt && ch0 + c < it.C && g < it.gy_frames)
-                v = it.gy_pitch ? it.gy [(size_t)(ch0 + c) * it.gy_pitch + g] : it.gy [(size_t) g * it.C + ch0 + c];
-            s_gy [i * CG + c] = v;
-        }
-        __syncthreads ();
-
-        // ADJ_UNROLL outputs at a time, without a branch inside a group: which of them this lane has a term for, their coefficient loads all
-        // in flight together, then one fused multiply-add per output in order — with the weight, or with a weight of zero where the lane has
-        // no term, which leaves a sum of finite terms exactly as it was (w * gy = +-0, and s + +-0 = s, +0 for s = +0).  A lane's chain is
-        // serial by definition: a lone clip has little else to hide a trip to the LDS or the cache behind.  A lane without a term reads tap 0
-        // of row 0; a group no lane of the wave has a term for is skipped (short filters: most of a chunk lies outside a wave's 64 frames).
-        for (int i0 = 0; i0 < cnt; i0 += ADJ_UNROLL) {    // (i0 + u < ADJ_CHUNK; positions past cnt are stale, and masked)
-            bool ok [ADJ_UNROLL];
-            int at [ADJ_UNROLL];
-            bool any = false;
-#pragma unroll
-            for (int u = 0; u < ADJ_UNROLL; ++u) {
-                const int k = lin - s_w [i0 + u], row = s_row [i0 + u];
-                ok [u] = live && i0 + u < cnt && (unsigned int) k < (unsigned int) T;
-                if constexpr (!INTERP) { const int pass = s_pass [i0 + u]; if (pass >= 0 && k != pass) ok [u] = false; }
-                at [u] = ok [u] ? row + k : 0;
-                any = any || ok [u];
-            }
-            if (!__any (any)) continue;
-            art_s w [ADJ_UNROLL];
-#pragma unroll
-            for (int u = 0; u < ADJ_UNROLL; ++u) {
-                const art_s *h = bank + at [u];
-                art_s v;
-                if constexpr (INTERP) {
-                    const double left = (double) h [0] * s_f0 [i0 + u], right = (double) h [T] * s_f1 [i0 + u];
-                    v = (art_s)(left + right);
-                }
-                else v = s_pass [i0 + u] >= 0 ? (art_s) 1 : h [0];
-                w [u] = ok [u] ? v : (art_s) 0;
-            }
-#pragma unroll
-            for (int u = 0; u < ADJ_UNROLL; ++u)
-#pragma unroll
-                for (int c = 0; c < CG; ++c) acc [c] = fused (w [u], s_gy [(i0 + u) * CG + c], acc [c]);
-        }
-    }
 }
 
 template <int CG, bool INTERP>
@@ -250,7 +169,7 @@ void fir_adjoint_kernel (const ArtAdjItem *items, int count, const double *seg_b
 // nothing below its floor or at or past end_k.  start and end do not decrease from phase to phase, so the phases that can touch the tile
 // (end > j0, start - H <= j1 - 1) are one contiguous range, found by bisection.  They are taken ADJ_GROUP at a time: two lanes per phase
 // bisect its output range into a table of fixed size, so the LDS does not depend on the block count; a phase without outputs (a tiny
-// block) or without an output on the tile costs its two bisections and is skipped.  Inside a phase the walk is adj_walk, as above; the
+// block) or without an output on the tile costs its two bisections and is skipped.  Inside a phase the walk is adj_walk (fir_adjoint_walk.hip.h: the chunk loop above, shared with fir_sample.hip); the
 // phases in order give the lane's terms in ascending output order.
 constexpr int ADJ_GROUP = 32;            // phases whose ranges are bisected together
 static_assert (2 * ADJ_GROUP <= ADJ_TILE, "two lanes per phase of a group");

@@ -2066,11 +2066,9 @@ static int adjoint_plan_blocks (const Resample *cxt, int numBlocks, const int *f
     return 0;
 }
 
-/* What both gradient entries of such clips refuse before anything is planned, the same way: 1 for a NULL context, a context with
- * EXTRAPOLATE_ENDPOINTS, a sharded one, one on another device or stream than cxts [0], and per item with blocks a NULL block array, a negative
- * count, more than INT_MAX frames, or a NULL buffer (`one` [i], `other` [i]: the entry's two sample buffers) where the clip has frames. */
-static int clip_blocks_refused (Resample *const *cxts, int n, const int *numBlocks, const int *numOutputFrames, const int *const *numInputFrames,
-                                const double *const *ratios, const void *const *one, const void *const *other)
+/* The contexts no entry that only reads them takes (the gradient entries of such clips, and the sampling entries further down): 1 for a NULL
+ * context, a context with EXTRAPOLATE_ENDPOINTS, a sharded one, one on another device or stream than cxts [0]. */
+static int clip_contexts_refused (Resample *const *cxts, int n)
 {
     for (int i = 0; i < n; ++i) if (!cxts [i]) return 1;
 
@@ -2078,6 +2076,19 @@ static int clip_blocks_refused (Resample *const *cxts, int n, const int *numBloc
     for (int i = 0; i < n; ++i) {
         const struct artamd_resampler *hip = cxts [i]->hip;
         if ((cxts [i]->flags & EXTRAPOLATE_ENDPOINTS) || hip->nshards || hip->device != lead->device || hip->stream != lead->stream) return 1;
+    }
+    return 0;
+}
+
+/* What both gradient entries of such clips refuse before anything is planned, the same way: 1 for the contexts above, and per item with blocks
+ * a NULL block array, a negative
+ * count, more than INT_MAX frames, or a NULL buffer (`one` [i], `other` [i]: the entry's two sample buffers) where the clip has frames. */
+static int clip_blocks_refused (Resample *const *cxts, int n, const int *numBlocks, const int *numOutputFrames, const int *const *numInputFrames,
+                                const double *const *ratios, const void *const *one, const void *const *other)
+{
+    if (clip_contexts_refused (cxts, n)) return 1;
+
+    for (int i = 0; i < n; ++i) {
         if (numBlocks [i] <= 0) continue;
         if (!numInputFrames [i] || numOutputFrames [i] < 0) return 1;
         if (!ratios [i] && !(cxts [i]->flags & RESAMPLE_FIXED_RATIO)) return 1;
@@ -2217,6 +2228,98 @@ out:
     free (phases.phases);
     free (list.segs);
     return rc;
+}
+
+/* ---- whole clips at a position curve in device memory ------------------------------------------------------------------
+ * resampleSampleClipsPlanarDevice, resampleSampleAdjointClipsPlanarDevice, resampleSamplePositionGradientClipsPlanarDevice (art_hip.h): no
+ * planner and no context state — a context supplies its bank and flags, every output's position comes from the caller's curve, and
+ * fir_sample.hip does the rest in one launch.  The three entries are one function: `what` says which buffers an item needs (d_in: x;
+ * d_gy; d_out: y or gx; d_gp) and when it is part of the launch. */
+static int sample_entry (int what, const char *name, Resample *const *cxts, int n,
+                         const art_s *const *d_in, const long *inPitches, const int *numInputFrames,
+                         const double *const *d_positions, const int *numOutputFrames,
+                         const art_s *const *d_gy, const long *gyPitches, art_s *const *d_out, const long *outPitches, double *const *d_gp)
+{
+    const int reads_in = what != ART_SAMPLE_ADJOINT, reads_gy = what != ART_SAMPLE_FORWARD, writes_out = what != ART_SAMPLE_SLOPE;
+
+    if (n <= 0) return 0;
+    if (!cxts || !numInputFrames || !d_positions || !numOutputFrames || (reads_in && !d_in) || (reads_gy && !d_gy) || (writes_out && !d_out) ||
+        (!writes_out && !d_gp)) return -1;
+    if (clip_contexts_refused (cxts, n)) return -1;
+    for (int i = 0; i < n; ++i) {
+        const int nIn = numInputFrames [i], nOut = numOutputFrames [i];
+        if (nIn < 0 || nOut < 0 || nIn > INT_MAX - 2 * cxts [i]->numTaps) return -1;
+        /* (the slope of a nearest-filter context is zero almost everywhere) */
+        if (what == ART_SAMPLE_SLOPE && !(cxts [i]->flags & SUBSAMPLE_INTERPOLATE)) return -1;
+        if (!nOut || (what == ART_SAMPLE_ADJOINT && !nIn)) continue;
+        if (!d_positions [i] || (reads_in && nIn && !d_in [i]) || (reads_gy && !d_gy [i]) || (writes_out && !d_out [i]) || (!writes_out && !d_gp [i]))
+            return -1;
+    }
+
+    struct artamd_resampler *lead = cxts [0]->hip;
+    ArtSampleItem *items = malloc (sizeof (ArtSampleItem) * (size_t) n);
+    unsigned long tasks = 0;
+    int live = 0, rc = -1, refused = 0;
+    if (!items) goto out;
+    for (int i = 0; i < n; ++i) {
+        const Resample *cxt = cxts [i];
+        ArtSampleItem *it = &items [live];
+        if (!numOutputFrames [i] || (what == ART_SAMPLE_ADJOINT && !numInputFrames [i])) continue;     /* (no task: no item) */
+        memset (it, 0, sizeof (*it));
+        it->bank = cxt->hip->d_bank; it->pos = d_positions [i];
+        it->gy_frames = (unsigned int) numOutputFrames [i]; it->in_frames = numInputFrames [i];
+        it->C = cxt->numChannels; it->T = cxt->numTaps; it->F = cxt->numFilters;
+        it->interpolate = (cxt->flags & SUBSAMPLE_INTERPOLATE) != 0;
+        it->lowpass = (cxt->flags & INCLUDE_LOWPASS) != 0;
+        if (reads_in) { it->in = d_in [i]; it->in_pitch = inPitches ? inPitches [i] : 0; }
+        if (reads_gy) { it->gy = d_gy [i]; it->gy_pitch = gyPitches ? gyPitches [i] : 0; }
+        if (writes_out) { it->out = d_out [i]; it->out_pitch = outPitches ? outPitches [i] : 0; }
+        else it->gp = d_gp [i];
+        tasks += arthip_fir_sample_tasks (it, what);
+        ++live;
+    }
+    if (tasks > (unsigned long) INT_MAX) { refused = 1; goto out; }
+    if (!live) { rc = 0; goto out; }
+
+    {
+        ENTER_DEVICE (lead);
+        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_sample_bytes (live));
+        rc = lead->d_batch ? arthip_fir_sample (items, live, what, lead->d_batch, lead->stream) : -1;
+        if (rc < 0) fprintf (stderr, "artamd: %s: launch failed: %s\n", name, arthip_last_error ());
+        LEAVE_DEVICE (lead);
+    }
+out:
+    if (rc < 0 && !refused) artamd_note_failure ("resampler: a launch of the clips sampler failed");
+    free (items);
+    return rc;
+}
+
+int resampleSampleClipsPlanarDevice (Resample *const *cxts, int n,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *numInputFrames,
+        const double *const *d_positions, const int *numOutputFrames,
+        artsample_t *const *d_outputs, const long *outputPitches)
+{
+    return sample_entry (ART_SAMPLE_FORWARD, "resample sample", cxts, n, d_inputs, inputPitches, numInputFrames, d_positions, numOutputFrames,
+                         NULL, NULL, d_outputs, outputPitches, NULL);
+}
+
+int resampleSampleAdjointClipsPlanarDevice (Resample *const *cxts, int n,
+        const double *const *d_positions, const int *numOutputFrames,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
+        artsample_t *const *d_gradInputs, const long *gradInputPitches, const int *numInputFrames)
+{
+    return sample_entry (ART_SAMPLE_ADJOINT, "resample sample adjoint", cxts, n, NULL, NULL, numInputFrames, d_positions, numOutputFrames,
+                         d_gradOutputs, gradOutputPitches, d_gradInputs, gradInputPitches, NULL);
+}
+
+int resampleSamplePositionGradientClipsPlanarDevice (Resample *const *cxts, int n,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *numInputFrames,
+        const double *const *d_positions, const int *numOutputFrames,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
+        double *const *d_gradPositions)
+{
+    return sample_entry (ART_SAMPLE_SLOPE, "resample sample position gradient", cxts, n, d_inputs, inputPitches, numInputFrames, d_positions,
+                         numOutputFrames, d_gradOutputs, gradOutputPitches, NULL, NULL, d_gradPositions);
 }
 
 /* ---- consecutive blocks of one stream, one launch --------------------------------------------------------------------

@@ -388,6 +388,56 @@ int resampleRateGradientScheduleClipsPlanarDevice (Resample *const *cxts, int n,
         const artsample_t *const *d_gradOutputs, const long *gradOutputPitches, const int *numOutputFrames,
         const int *const *numInputFrames, const double *const *ratios,
         double *const *d_gradRatios);
+/* Whole clips at a POSITION CURVE that lies in device memory — the 1-D, windowed-sinc counterpart of grid_sample: output m of item i is
+ * the context's own interpolator evaluated at d_positions [i][m], a double in input frames.  No planner, no context state, no history:
+ * cxts [i] supplies T = numTaps, half = T / 2, F = numFilters, its bank and its flags, and is only READ (a context may be listed any
+ * number of times; a RESAMPLE_FIXED_RATIO context is taken, only its bank is used).  The output count is the curve's length.
+ * For a position p and the N = numInputFrames [i] frames of channel c: whole = floor (p), fr = (p - whole) * F (neither fused); on a
+ * SUBSAMPLE_INTERPOLATE context fi = floor (fr), frac = fr - fi, else fi = floor (fr + 0.5), frac = 0; tap t in [0, T) reads input frame
+ * whole - half + 1 + t.  This is the position arithmetic of resampleProcess with the offset p: p = 0 is a fresh context's position after
+ * resampleAdvancePosition (taps / 2), output m centred on input frame p [m]; p [m] = m / ratio resamples aligned, p [m] = m / ratio - taps / 2
+ * is what the clips entries make.  Frames below 0 or at and past N are silence, and their taps are LEFT OUT, not multiplied by zero: a NaN
+ * past the clip or in row padding is never read.  A position that is not finite, or with p < -(half + 1) or p >= N + half (compared on
+ * the double, before any conversion to int), yields exactly 0, reads nothing and has no term in either gradient.  (Where p - whole rounds
+ * up to 1 — a tiny negative p — fi = F is taken as fi = F - 1, frac = 1: the same value, rows inside the bank.)
+ *   forward   y [c, m] = (artsample_t)(s0 * (1 - frac) + s1 * frac), s0 and s1 the fp64 dot products with bank rows fi and fi + 1 (one
+ *             chain of fused multiply-adds each, t ascending); a nearest-filter context uses s0 alone, and its pass-through case (no
+ *             INCLUDE_LOWPASS, fi a multiple of F) is a copy of frame whole + fi / F.
+ *   adjoint   gx = A^T gy for the weights A [m, j] = (artsample_t)(h0 * (1 - frac) + h1 * frac) of resampleAdjointClipsPlanarDevice: frames
+ *             0 .. N - 1 of every plane of d_gradInputs [i] are SET, the terms added in ascending m, one fused multiply-add each, in
+ *             artsample_t.  PRECONDITION: the item's positions do not decrease in m (positions without a window may lie anywhere a
+ *             non-decreasing curve of doubles allows; a NaN counts as +infinity).  The outputs whose windows hold frame j are then one
+ *             range, found by bisection on the position array itself.  On a curve that decreases somewhere the result is unspecified;
+ *             every read and write still stays inside the item's buffers.  (Sort the curve, and gy with it: A^T does not care about the
+ *             outputs' order.)
+ *   position gradient   the numOutputFrames [i] doubles of d_gradPositions [i] are SET to gp [m] = sum_c gy [c, m] D [c, m] in fp64,
+ *             D = F * (one chain of fused multiply-adds of ((double) bank [fi + 1][t] - (double) bank [fi][t]) and (double) x, t
+ *             ascending), the channels in order: the slope of the cell floor picks — no average on a filter boundary, and nothing held
+ *             fixed.  Contexts with SUBSAMPLE_INTERPOLATE only.
+ * Positions are doubles in both sample widths.  Pitches as in resampleProcessBatchPlanarDevice (0, or a NULL pitch list: interleaved).
+ * One launch per entry (fir_sample.hip) over one flattened task space — tiles of 256 outputs, or of 256 input frames per channel group —
+ * so one long clip and a thousand short ones spread alike; no atomics: every value is the same bit for bit whatever the batch, the
+ * item's place in it, the layout, the pitches or the stream.  Asynchronous on the stream of cxts [0]; the items ride in the lead
+ * context's batch table.  An item without outputs (the adjoint: or without input frames) is no part of the launch and nothing of it is
+ * written: the adjoint zeroes nothing.
+ * Returns the number of launches enqueued: 1, or 0 for n <= 0 or when no item is part of the launch.  -1 with nothing enqueued and nothing
+ * counted for a NULL context, a context with EXTRAPOLATE_ENDPOINTS, a sharded context, a context on another device or stream than
+ * cxts [0], a negative count, numInputFrames [i] > INT_MAX - 2 T, a NULL buffer of an item that is part of the launch (d_inputs [i] only
+ * where it has frames), more tiles than an int counts, and — the position gradient — a context without SUBSAMPLE_INTERPOLATE.  -1 if the
+ * launch failed (counted once in artamdErrorCount): the outputs are then unspecified.  Outputs must not overlap inputs (not checked). */
+int resampleSampleClipsPlanarDevice (Resample *const *cxts, int n,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *numInputFrames,
+        const double *const *d_positions, const int *numOutputFrames,
+        artsample_t *const *d_outputs, const long *outputPitches);
+int resampleSampleAdjointClipsPlanarDevice (Resample *const *cxts, int n,
+        const double *const *d_positions, const int *numOutputFrames,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
+        artsample_t *const *d_gradInputs, const long *gradInputPitches, const int *numInputFrames);
+int resampleSamplePositionGradientClipsPlanarDevice (Resample *const *cxts, int n,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *numInputFrames,
+        const double *const *d_positions, const int *numOutputFrames,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
+        double *const *d_gradPositions);
 
 /* ---- host-only building blocks (no GPU needed; used by the CPU test-suite) ---- */
 /* (numFilters+1) x numTaps bank exactly as resampleInit builds it (reference resampler.c:149-168, 1090-1133) */

@@ -203,6 +203,9 @@ def _bind(width):
         "resampleSampleClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleSampleAdjointClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
         "resampleSamplePositionGradientClipsPlanarDevice": (C.c_int, [ptr, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleSampleBandClipsPlanarDevice": (C.c_int, [ptr, C.c_int, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleSampleBandAdjointClipsPlanarDevice": (C.c_int, [ptr, C.c_int, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
+        "resampleSampleBandGradientsClipsPlanarDevice": (C.c_int, [ptr, C.c_int, C.c_int, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
     }
 
     _state = {"lib": None}

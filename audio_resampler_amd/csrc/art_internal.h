@@ -340,6 +340,25 @@ size_t arthip_fir_sample_bytes (int nitems);
  * memory of arthip_fir_sample_bytes bytes, reused call after call: stream order protects it) in one upload.  Returns 1, 0 for n <= 0, or -1 (the
  * launch failed; nothing enqueued where the upload could not be made). */
 int arthip_fir_sample (const ArtSampleItem *items, int n, int what, void *d_table, void *stream);
+/* ---- fir_band.hip: the same clips on a LADDER of banks, a level per output (resampleSampleBand*ClipsPlanarDevice) ----
+ * An item of its own, so that the unbanded path's stays as small as it is: `rungs` banks of one shape (interpolating contexts only) and a
+ * curve of gy_frames levels beside the positions.  Launches, tasks and tiles as above; ART_SAMPLE_SLOPE writes gp, gl or both — whichever
+ * is not NULL (the same in every item of a launch: the entry's lists). */
+#define ART_BAND_RUNGS 8
+typedef struct {
+    const art_s *bank [ART_BAND_RUNGS];  /* device, (F+1) x T each; [0, rungs) */
+    const double *pos, *level;           /* the two curves: gy_frames doubles each */
+    const art_s *in, *gy;
+    art_s *out;
+    double *gp, *gl;                     /* slope: gy_frames doubles are SET in each that is there */
+    long in_pitch, gy_pitch, out_pitch;
+    unsigned int gy_frames, task0;
+    int in_frames, C, T, F;
+    int rungs, pad;
+} ArtBandItem;
+unsigned long arthip_fir_band_tasks (const ArtBandItem *it, int what);
+size_t arthip_fir_band_bytes (int nitems);
+int arthip_fir_band (const ArtBandItem *items, int n, int what, void *d_table, void *stream);
 /* the upkeep every launch of a rational-ratio stream does for the rows kept across calls (arthip_fir calls it itself) */
 void arthip_fir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs);
 /* new_hist[H][C] = last H frames of (hist ++ in[0..appended)); in may be NULL => zeros appended */

@@ -1,7 +1,7 @@
 #pragma once
-// fir_adjoint_walk.hip.h — the chunk walk of the gather adjoints (gfx950): fir_adjoint.hip's blocks kernel and fir_sample.hip's adjoint share
+// fir_adjoint_walk.hip.h — the chunk walk of the gather adjoints (gfx950): fir_adjoint.hip's blocks kernel, fir_sample.hip's adjoint and fir_band.hip's share
 // this one copy, each with its own source of output positions: adj_walk asks adj_locate<INTERP> (rate, segs, n), an overload set — the one
-// below for a planned phase, fir_sample.hip's for an entry of a position array (found at instantiation, through its argument types).  With the
+// below for a planned phase, fir_sample_common.hip.h's for an entry of a position array (found at instantiation, through its argument types).  With the
 // source as a pair of operands passed on as locate ()'s were, fir_adjoint.hip's device code is what it was before the walk moved here,
 // instruction for instruction in both widths (a functor that holds the pair moved one conversion and renumbered a scalar register in the
 // blocks kernel's eight instantiations).  Compiled with -ffp-contract=off, as both are.
@@ -27,11 +27,18 @@ __device__ __forceinline__ Pos adj_locate (const AdjRate &rate, const AdjSegs &s
 // instantiations, +-2 VGPRs in three: profiles/clip_warp.txt), and the two-phase kernel keeps the code object it was measured with.
 // A change to the arithmetic is made in both places; tests/test_gpu_clip_warp.py holds the two kernels to the same bits on one-block
 // clips.
-template <int CG, bool INTERP, typename Item, typename Rate, typename Segs>
+// BAND (fir_band.hip; INTERP only): the item holds a ladder of banks of one shape, it.bank [0 .. K), and adj_level (segs, n, rung, lam) gives
+// output n's rung L and blend lam: its weight is rung L's where lam == 0 — the line below, on that bank — and elsewhere
+// (art_s)(w_L * (1.0 - lam) + w_{L+1} * lam) with w_k = h0 * f0 + h1 * f1 of rung k unrounded, in double.  Two more rows of the chunk in the
+// LDS (s_rung, s_lam).  Without BAND nothing of this is compiled: the other instantiations are what they were.
+template <int CG, bool INTERP, bool BAND = false, typename Item, typename Rate, typename Segs>
 __device__ __forceinline__ void adj_walk (art_s (&acc) [CG], const Item &it, const Rate &rate, const Segs &segs, int ch0, int tid, int lin, bool live,
-                                          unsigned int g0, int n_begin, int n_end, int *s_w, int *s_row, int *s_pass, double *s_f0, double *s_f1, art_s *s_gy)
+                                          unsigned int g0, int n_begin, int n_end, int *s_w, int *s_row, int *s_pass, double *s_f0, double *s_f1, art_s *s_gy,
+                                          int *s_rung = nullptr, double *s_lam = nullptr)
 {
-    const art_s *const bank = it.bank;
+    static_assert (INTERP || !BAND, "a ladder is blended on interpolating banks only");
+    const art_s *bank = nullptr;
+    if constexpr (!BAND) bank = it.bank;
     const int T = it.T, half = T / 2;
 
     for (int n0 = n_begin; n0 < n_end; n0 += ADJ_CHUNK) {
@@ -41,7 +48,8 @@ __device__ __forceinline__ void adj_walk (art_s (&acc) [CG], const Item &it, con
             const Pos pos = adj_locate<INTERP> (rate, segs, (unsigned int)(n0 + tid));
             s_w [tid] = pos.ip - half + 1;
             s_row [tid] = pos.fi * T;
-            if (INTERP) { s_f0 [tid] = 1.0 - pos.frac; s_f1 [tid] = pos.frac; }
+            if constexpr (BAND) adj_level (segs, (unsigned int)(n0 + tid), s_rung [tid], s_lam [tid]);
+            if constexpr (INTERP) { s_f0 [tid] = 1.0 - pos.frac; s_f1 [tid] = pos.frac; }
             else s_pass [tid] = (!it.lowpass && (pos.fi % it.F) == 0) ? half - 1 + pos.fi / it.F : -1;
         }
         // gy of the chunk for the channel group: zero past the frames handed in, past the item's channels and — the loop below takes whole
@@ -77,16 +85,39 @@ __device__ __forceinline__ void adj_walk (art_s (&acc) [CG], const Item &it, con
             }
             if (!__any (any)) continue;
             art_s w [ADJ_UNROLL];
+            if constexpr (BAND) {
+                // (what a group's outputs ask is the same for every lane: a group on whole rungs loads what the unbanded walk loads)
+                bool blend = false;
 #pragma unroll
-            for (int u = 0; u < ADJ_UNROLL; ++u) {
-                const art_s *h = bank + at [u];
-                art_s v;
-                if constexpr (INTERP) {
+                for (int u = 0; u < ADJ_UNROLL; ++u) blend = blend || (i0 + u < cnt && s_lam [i0 + u] != 0.0);
+#pragma unroll
+                for (int u = 0; u < ADJ_UNROLL; ++u) {
+                    const int rung = i0 + u < cnt ? s_rung [i0 + u] : 0;
+                    const double lam = i0 + u < cnt ? s_lam [i0 + u] : 0.0;
+                    const art_s *h = it.bank [rung] + at [u];
                     const double left = (double) h [0] * s_f0 [i0 + u], right = (double) h [T] * s_f1 [i0 + u];
-                    v = (art_s)(left + right);
+                    double v = left + right;
+                    if (blend) {
+                        const art_s *g = it.bank [lam != 0.0 ? rung + 1 : rung] + at [u];
+                        const double left1 = (double) g [0] * s_f0 [i0 + u], right1 = (double) g [T] * s_f1 [i0 + u];
+                        const double lower = v * (1.0 - lam), upper = (left1 + right1) * lam;
+                        if (lam != 0.0) v = lower + upper;
+                    }
+                    w [u] = ok [u] ? (art_s) v : (art_s) 0;
                 }
-                else v = s_pass [i0 + u] >= 0 ? (art_s) 1 : h [0];
-                w [u] = ok [u] ? v : (art_s) 0;
+            }
+            else {
+#pragma unroll
+                for (int u = 0; u < ADJ_UNROLL; ++u) {
+                    const art_s *h = bank + at [u];
+                    art_s v;
+                    if constexpr (INTERP) {
+                        const double left = (double) h [0] * s_f0 [i0 + u], right = (double) h [T] * s_f1 [i0 + u];
+                        v = (art_s)(left + right);
+                    }
+                    else v = s_pass [i0 + u] >= 0 ? (art_s) 1 : h [0];
+                    w [u] = ok [u] ? v : (art_s) 0;
+                }
             }
 #pragma unroll
             for (int u = 0; u < ADJ_UNROLL; ++u)

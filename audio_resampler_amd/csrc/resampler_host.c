@@ -2322,6 +2322,105 @@ int resampleSamplePositionGradientClipsPlanarDevice (Resample *const *cxts, int 
                          numOutputFrames, d_gradOutputs, gradOutputPitches, NULL, NULL, d_gradPositions);
 }
 
+/* ---- the same clips on a ladder of banks, a level per output ---------------------------------------------------------------
+ * resampleSampleBandClipsPlanarDevice, resampleSampleBandAdjointClipsPlanarDevice, resampleSampleBandGradientsClipsPlanarDevice (art_hip.h):
+ * rung k of clip i is cxts [i * numRungs + k]; the levels lie beside the positions, and fir_band.hip does the rest in one launch.  One
+ * function again: the sampling entries' checks per clip on its rung 0, the ladder's on top.  The gradients entry takes d_gp, d_gl or
+ * both. */
+static int band_entry (int what, const char *name, Resample *const *cxts, int n, int numRungs,
+                       const art_s *const *d_in, const long *inPitches, const int *numInputFrames,
+                       const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
+                       const art_s *const *d_gy, const long *gyPitches, art_s *const *d_out, const long *outPitches,
+                       double *const *d_gp, double *const *d_gl)
+{
+    const int reads_in = what != ART_SAMPLE_ADJOINT, reads_gy = what != ART_SAMPLE_FORWARD, writes_out = what != ART_SAMPLE_SLOPE;
+
+    if (n <= 0) return 0;
+    if (numRungs < 1 || numRungs > ART_BAND_RUNGS || n > INT_MAX / ART_BAND_RUNGS) return -1;
+    if (!cxts || !numInputFrames || !d_positions || !d_levels || !numOutputFrames || (reads_in && !d_in) || (reads_gy && !d_gy) ||
+        (writes_out && !d_out) || (!writes_out && !d_gp && !d_gl)) return -1;
+    if (clip_contexts_refused (cxts, n * numRungs)) return -1;
+    for (int i = 0; i < n; ++i) {
+        const Resample *lead = cxts [i * numRungs];
+        const int nIn = numInputFrames [i], nOut = numOutputFrames [i];
+        for (int k = 0; k < numRungs; ++k) {
+            const Resample *rung = cxts [i * numRungs + k];
+            if (rung->numChannels != lead->numChannels || rung->numTaps != lead->numTaps || rung->numFilters != lead->numFilters) return -1;
+            /* (two rungs are blended value by value of one interpolation cell: both interpolate) */
+            if (!(rung->flags & SUBSAMPLE_INTERPOLATE)) return -1;
+        }
+        if (nIn < 0 || nOut < 0 || nIn > INT_MAX - 2 * lead->numTaps) return -1;
+        if (!nOut || (what == ART_SAMPLE_ADJOINT && !nIn)) continue;
+        if (!d_positions [i] || !d_levels [i] || (reads_in && nIn && !d_in [i]) || (reads_gy && !d_gy [i]) || (writes_out && !d_out [i]) ||
+            (d_gp && !d_gp [i]) || (d_gl && !d_gl [i])) return -1;
+    }
+
+    struct artamd_resampler *lead = cxts [0]->hip;
+    ArtBandItem *items = malloc (sizeof (ArtBandItem) * (size_t) n);
+    unsigned long tasks = 0;
+    int live = 0, rc = -1, refused = 0;
+    if (!items) goto out;
+    for (int i = 0; i < n; ++i) {
+        const Resample *cxt = cxts [i * numRungs];
+        ArtBandItem *it = &items [live];
+        if (!numOutputFrames [i] || (what == ART_SAMPLE_ADJOINT && !numInputFrames [i])) continue;     /* (no task: no item) */
+        memset (it, 0, sizeof (*it));
+        for (int k = 0; k < numRungs; ++k) it->bank [k] = cxts [i * numRungs + k]->hip->d_bank;
+        it->rungs = numRungs;
+        it->pos = d_positions [i]; it->level = d_levels [i];
+        it->gy_frames = (unsigned int) numOutputFrames [i]; it->in_frames = numInputFrames [i];
+        it->C = cxt->numChannels; it->T = cxt->numTaps; it->F = cxt->numFilters;
+        if (reads_in) { it->in = d_in [i]; it->in_pitch = inPitches ? inPitches [i] : 0; }
+        if (reads_gy) { it->gy = d_gy [i]; it->gy_pitch = gyPitches ? gyPitches [i] : 0; }
+        if (writes_out) { it->out = d_out [i]; it->out_pitch = outPitches ? outPitches [i] : 0; }
+        else { it->gp = d_gp ? d_gp [i] : NULL; it->gl = d_gl ? d_gl [i] : NULL; }
+        tasks += arthip_fir_band_tasks (it, what);
+        ++live;
+    }
+    if (tasks > (unsigned long) INT_MAX) { refused = 1; goto out; }
+    if (!live) { rc = 0; goto out; }
+
+    {
+        ENTER_DEVICE (lead);
+        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_band_bytes (live));
+        rc = lead->d_batch ? arthip_fir_band (items, live, what, lead->d_batch, lead->stream) : -1;
+        if (rc < 0) fprintf (stderr, "artamd: %s: launch failed: %s\n", name, arthip_last_error ());
+        LEAVE_DEVICE (lead);
+    }
+out:
+    if (rc < 0 && !refused) artamd_note_failure ("resampler: a launch of the banded clips sampler failed");
+    free (items);
+    return rc;
+}
+
+int resampleSampleBandClipsPlanarDevice (Resample *const *cxts, int n, int numRungs,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *numInputFrames,
+        const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
+        artsample_t *const *d_outputs, const long *outputPitches)
+{
+    return band_entry (ART_SAMPLE_FORWARD, "resample sample band", cxts, n, numRungs, d_inputs, inputPitches, numInputFrames, d_positions, d_levels,
+                       numOutputFrames, NULL, NULL, d_outputs, outputPitches, NULL, NULL);
+}
+
+int resampleSampleBandAdjointClipsPlanarDevice (Resample *const *cxts, int n, int numRungs,
+        const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
+        artsample_t *const *d_gradInputs, const long *gradInputPitches, const int *numInputFrames)
+{
+    return band_entry (ART_SAMPLE_ADJOINT, "resample sample band adjoint", cxts, n, numRungs, NULL, NULL, numInputFrames, d_positions, d_levels,
+                       numOutputFrames, d_gradOutputs, gradOutputPitches, d_gradInputs, gradInputPitches, NULL, NULL);
+}
+
+int resampleSampleBandGradientsClipsPlanarDevice (Resample *const *cxts, int n, int numRungs,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *numInputFrames,
+        const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
+        double *const *d_gradPositions, double *const *d_gradLevels)
+{
+    return band_entry (ART_SAMPLE_SLOPE, "resample sample band gradients", cxts, n, numRungs, d_inputs, inputPitches, numInputFrames, d_positions,
+                       d_levels, numOutputFrames, d_gradOutputs, gradOutputPitches, NULL, NULL, d_gradPositions, d_gradLevels);
+}
+
 /* ---- consecutive blocks of one stream, one launch --------------------------------------------------------------------
  * An ASRC loop makes a call per block with that block's ratio; each call is a launch with its own planning, staging and launch floor.
  * Where the caller knows the next blocks' ratios, resampleProcessScheduleInterleavedDevice plans them one after the other on the context

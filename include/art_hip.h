@@ -438,6 +438,45 @@ int resampleSamplePositionGradientClipsPlanarDevice (Resample *const *cxts, int 
         const double *const *d_positions, const int *numOutputFrames,
         const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
         double *const *d_gradPositions);
+/* The same clips BAND-LIMITED PER OUTPUT from a ladder of banks — what a mip chain is to a texture sampler: where the curve steps faster
+ * than one input frame per output, a bank of a lower cut-off keeps the clip from aliasing there, and only there.  cxts holds n * numRungs
+ * contexts: rung k of item i is cxts [i * numRungs + k], numRungs = K in 1 .. 8, rung 0 the widest bank by convention — the entries do not
+ * look at cut-offs: level k MEANS rung k.  The rungs of an item agree in channels, taps and filters, and every one has SUBSAMPLE_INTERPOLATE
+ * (INCLUDE_LOWPASS may differ: resampleInit clears it on a bank without low-pass).  The contexts are only read.  d_levels [i] holds
+ * numOutputFrames [i] doubles beside the positions.  The level l of an output:
+ *     !(l > 0) — a NaN, -0.0, a negative: L = 0, lam = 0;   l >= K - 1: L = K - 1, lam = 0;   else L = floor (l), lam = l - L.
+ * The position arithmetic, the windows and the no-window rule are the sampling entries' above.  With a_k = s0 * (1 - frac) + s1 * frac of
+ * rung k in fp64 (the sampling forward's chains and its lerp before the rounding), w_k = h0 * (1 - frac) + h1 * frac in fp64 and D_k the
+ * position gradient's D on rung k:
+ *   forward    y = (artsample_t) a_L where lam == 0 — rung L + 1 is not read, and the result is resampleSampleClipsPlanarDevice's on rung
+ *              L's context bit for bit — else y = (artsample_t)(a_L * (1.0 - lam) + a_{L+1} * lam), nothing fused beyond the chains.
+ *              Without a window: exactly 0, nothing read.
+ *   adjoint    the transpose: the weight of (output, tap) is rung L's (artsample_t) w_L where lam == 0, else
+ *              (artsample_t)(w_L * (1.0 - lam) + w_{L+1} * lam); order, bisection and PRECONDITION (positions that do not decrease) as
+ *              resampleSampleAdjointClipsPlanarDevice.  The levels may be anything.
+ *   gradients  gp [m] = sum_c gy * D, D = D_L where lam == 0 (resampleSamplePositionGradientClipsPlanarDevice's bits on rung L), else
+ *              D_L * (1.0 - lam) + D_{L+1} * lam.  glevel [m] = sum_c gy [c, m] * (a_{j+1} - a_j), j = min (L, K - 2), for
+ *              0 <= l <= K - 1, -0.0 included: the closed ends pass the gradient, as a clamp's do, so a level that starts on a rung can
+ *              leave it; exactly 0 for l < 0, l > K - 1, a NaN, K = 1 and an output without a window.  d_gradPositions or d_gradLevels
+ *              may be NULL — not wanted; the value chains run only where d_gradLevels is given.
+ * One launch per entry (fir_band.hip), the sampling entries' task spaces; an output reads the one or two banks it needs.  The result does
+ * not depend on the batch, the layout, the pitches or the stream.  Pitches, n <= 0, the return value (1 or 0 launches) and items without
+ * outputs as in the sampling entries.  -1 with nothing enqueued and nothing counted: numRungs outside 1 .. 8, a rung that differs from its
+ * item's rung 0 in channels, taps or filters, a rung without SUBSAMPLE_INTERPOLATE, everything the sampling entries refuse (for any rung;
+ * d_levels [i] as d_positions [i]), and d_gradPositions and d_gradLevels both NULL. */
+int resampleSampleBandClipsPlanarDevice (Resample *const *cxts, int n, int numRungs,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *numInputFrames,
+        const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
+        artsample_t *const *d_outputs, const long *outputPitches);
+int resampleSampleBandAdjointClipsPlanarDevice (Resample *const *cxts, int n, int numRungs,
+        const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
+        artsample_t *const *d_gradInputs, const long *gradInputPitches, const int *numInputFrames);
+int resampleSampleBandGradientsClipsPlanarDevice (Resample *const *cxts, int n, int numRungs,
+        const artsample_t *const *d_inputs, const long *inputPitches, const int *numInputFrames,
+        const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
+        const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
+        double *const *d_gradPositions, double *const *d_gradLevels);
 
 /* ---- host-only building blocks (no GPU needed; used by the CPU test-suite) ---- */
 /* (numFilters+1) x numTaps bank exactly as resampleInit builds it (reference resampler.c:149-168, 1090-1133) */

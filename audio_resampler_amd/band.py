@@ -9,22 +9,20 @@ neighbouring rungs and their blend: level k means rung k, level k + lam the blen
 the one or two banks an output needs.  Positions as in audio_resampler_amd.sampler: doubles in input frames, p = 0 aligned.
 
 The names live beside the binding (audio_resampler_amd.api) and beside audio_resampler_amd.sampler, in neither: `binding(width)` here
-returns a namespace of them for that sample width; the module level is the 4-byte build."""
+returns a namespace of them for that sample width, built on the curve helpers sampler.binding(width) hands out under `_private` — the list
+and curve checks, the rows, the sort of a curve that decreases — so that only what is the ladder's stands here; the module level is the
+4-byte build."""
 import math
 import types
 
-from . import api
+from . import api, sampler
 
 
 def _bind(width):
     B = api.binding(width)
     P = B._private
-    smp_torch = "float64" if width == 64 else "float32"
-
-    def _one_per_clip(n, *lists):
-        if any(v is not None and len(v) != n for v in lists):
-            raise ValueError("one entry per clip in every list")
-        return max(n, 1)
+    S = sampler.binding(width)._private                           # (the curve helpers: ClipSampler's own)
+    _one_per_clip, _curve_ptrs = S._one_per_clip, S._curve_ptrs
 
     def _ladder(resamplers, rungs):
         """the contexts of a call: `resamplers` holds len / rungs clips' ladders, rung k of clip i at [i * rungs + k]"""
@@ -80,10 +78,6 @@ def _bind(width):
             raise RuntimeError("resampleSampleBandGradientsClipsPlanarDevice failed")
         return rc
 
-    def _curve_ptrs(p):
-        """addresses of the rows of p [B, M] (float64, consecutive along M; a broadcast curve is one row listed B times)"""
-        return [p.data_ptr() + i * p.stride(0) * 8 for i in range(p.shape[0])]
-
     def _forward(ctx, x, p, lev, clip, lengths, outs):
         ctx.save_for_backward(x, p, lev)                          # (an edit of any in place before backward is caught)
         ctx.clip, ctx.lengths, ctx.outs = clip, lengths, outs
@@ -108,15 +102,8 @@ def _bind(width):
             rung.set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
         ladder, K = clip.pool * B_, len(clip.pool)
         if need_x:
-            # ClipSampler's rule: the adjoint kernel bisects the curve, so a curve that decreases within out_lengths is sorted — stably,
-            # what lies past out_lengths moved to the end — and gy AND THE LEVELS gathered into the same order: A^T does not care about
-            # the outputs' order, as long as every output keeps its own level
-            past = torch.arange(M, device=p.device)[None, :] >= torch.tensor(outs, device=p.device)[:, None]
-            curve, g, lv = p, gy, lev
-            if not bool(((p[:, 1:] >= p[:, :-1]) | past[:, 1:]).all()):
-                curve, order = torch.sort(p.masked_fill(past, float("inf")), dim=1, stable=True)
-                g = torch.gather(gy, 2, order[:, None, :].expand(-1, gy.shape[1], -1))
-                lv = torch.gather(lev, 1, order)
+            # ClipSampler's rule: a curve that decreases within out_lengths is sorted, and gy AND THE LEVELS gathered into the same order
+            curve, g, lv = S._monotone(p, outs, gy, lev)
             (g_ptrs, g_pitch), (gx_ptrs, gx_pitch) = P._clip_ptrs(g), P._clip_ptrs(gx)
             sample_band_adjoint_clips_planar_device(ladder, K, _curve_ptrs(curve), _curve_ptrs(lv), outs, g_ptrs, [g_pitch] * B_, gx_ptrs, [gx_pitch] * B_,
                                                     lengths)
@@ -200,30 +187,15 @@ def _bind(width):
                 level = level + ((self._log[k] - at) / (self._log[k] - self._log[k + 1])).clamp(0.0, 1.0)
             return torch.where(m < n, level, torch.zeros_like(level))
 
-        def _curve(self, positions, B_):
-            import torch
-            if not torch.is_tensor(positions) or positions.dtype not in (torch.float32, torch.float64) or positions.dim() not in (1, 2) or \
-                    (positions.dim() == 2 and B_ is not None and positions.shape[0] != B_):
-                raise ValueError("positions: a float32 or float64 tensor [B, M] or [M]")
-
-        @staticmethod
-        def _outs(out_lengths, B_, M):
-            if out_lengths is None:
-                return [M] * B_
-            outs = [int(v) for v in (out_lengths.tolist() if hasattr(out_lengths, "tolist") else out_lengths)]
-            if len(outs) != B_ or any(v < 0 or v > M for v in outs):
-                raise ValueError("out_lengths: one entry per clip, 0 .. M")
-            return outs
-
         def levels_of(self, positions, out_lengths=None):
             """what levels=None uses for this curve: [B, M] float64 on the positions' device, no graph attached (B = len(out_lengths), or
             1, for positions [M]); zero at and past out_lengths[i]"""
             import torch
-            self._curve(positions, None)
+            S._check_positions(positions, None)
             p = positions.detach()
             if p.dim() == 1:
                 p = p[None, :].expand(1 if out_lengths is None else len(out_lengths), p.shape[0])
-            return self._levels(p.to(torch.float64), self._outs(out_lengths, p.shape[0], p.shape[1]))
+            return self._levels(p.to(torch.float64), S._outs(out_lengths, p.shape[0], p.shape[1]))
 
         def _sample(self, x, p, lev, lengths, outs):
             """the forward launch: x [B, C, T], p and lev [B, M] float64 on the GPU, detached"""
@@ -242,35 +214,20 @@ def _bind(width):
             import torch
             # (the GPU is asked for behind the host checks: they need none)
             x, B_, Cn, T, lengths = P._clip_input(x, self.channels, lengths, cuda=False, strided="keep")
-            self._curve(positions, B_)
+            S._check_positions(positions, B_)
             M = positions.shape[-1]
-            outs = self._outs(out_lengths, B_, M)
+            outs = S._outs(out_lengths, B_, M)
             if levels is not None and (not torch.is_tensor(levels) or levels.dtype not in (torch.float32, torch.float64) or levels.dim() not in (1, 2) or
                                        levels.shape[-1] != M or (levels.dim() == 2 and levels.shape[0] != B_)):
                 raise ValueError("levels: a float32 or float64 tensor [B, M] or [M], or None")
-            if not x.is_cuda:
-                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
-            if positions.device != x.device:
-                raise ValueError("positions: on the samples' device (they are not downloaded)")
-            if levels is not None and levels.device != x.device:
-                raise ValueError("levels: on the samples' device (they are not downloaded)")
-            if x.shape[2] and x.stride(2) != 1:
-                x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
-
-            def rows(t):
-                # torch ops in front of the custom function: autograd sums a broadcast curve's gradient back and narrows it to the caller's dtype
-                t = t if t.dim() == 2 else t[None, :].expand(B_, M)
-                if t.dtype != torch.float64:
-                    t = t.to(torch.float64)
-                return t.contiguous() if M > 1 and t.stride(1) != 1 else t
-
-            p = rows(positions)
-            lev = self._levels(p.detach(), outs) if levels is None else rows(levels)
+            x = S._on_device(x, self.channels, positions=positions, levels=levels)
+            p = S._rows(positions, B_, M)
+            lev = self._levels(p.detach(), outs) if levels is None else S._rows(levels, B_, M)
             if torch.is_grad_enabled() and (x.requires_grad or p.requires_grad or lev.requires_grad):
                 return _clip_band_grad().apply(x, p, lev, self, lengths, outs)
             return self._sample(x.detach(), p.detach(), lev.detach(), lengths, outs)
 
-    return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k not in ("width", "B", "P", "smp_torch")}, width=width)
+    return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k not in ("width", "B", "P", "S")}, width=width)
 
 
 _bound = {}

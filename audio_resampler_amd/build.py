@@ -19,10 +19,10 @@ OUT = os.path.join(HERE, "libartamd.so")
 OUT64 = os.path.join(HERE, "libartamd64.so")
 
 C_SOURCES = ["resampler_host.c", "pcm_host.c", "extrapolate_host.c", "stretch_host.c", "lag_products_host.c"]
-HIP_SOURCES = ["device_rt.hip", "extrapolate_kernels.hip", "fir_general.hip", "fir_adjoint.hip", "fir_rate_grad.hip", "fir_sample.hip", "fir_band.hip", "fir_matrix.hip", "fir_matrix_i8.hip", "fir_matrix64.hip", "fir_dispatch.hip", "layout_kernels.hip", "pcm_kernels.hip", "stretch_kernels.hip", "stretch_adjoint.hip", "lag_products.hip"]
+HIP_SOURCES = ["device_rt.hip", "extrapolate_kernels.hip", "fir_general.hip", "fir_adjoint.hip", "fir_rate_grad.hip", "fir_sample.hip", "fir_matrix.hip", "fir_matrix_i8.hip", "fir_matrix64.hip", "fir_dispatch.hip", "layout_kernels.hip", "pcm_kernels.hip", "stretch_kernels.hip", "stretch_adjoint.hip", "lag_products.hip"]
 # per-file extra flags (tried: -fno-slp-vectorize on pcm_kernels.hip — 10 % slower, so none)
 EXTRA_FLAGS = {}
-HEADERS = [os.path.join(CSRC, h) for h in ("art_internal.h", "fir_internal.h", "fir_common.hip.h", "fir_adjoint_walk.hip.h", "fir_sample_common.hip.h", "fir_matrix_common.hip.h", "fir_matrix_stream.hip.h", "fir_matrix_stream_body.inc", "fir_i8_tile32.inc", "pcm_dec_serial_row.inc", "staging.hip.h")] + [os.path.join(INC, h) for h in ("art_hip.h", "resampler.h", "biquad.h", "decimator.h", "stretch.h")]
+HEADERS = [os.path.join(CSRC, h) for h in ("art_internal.h", "fir_internal.h", "fir_common.hip.h", "fir_adjoint_walk.hip.h", "fir_matrix_common.hip.h", "fir_matrix_stream.hip.h", "fir_matrix_stream_body.inc", "fir_i8_tile32.inc", "pcm_dec_serial_row.inc", "staging.hip.h")] + [os.path.join(INC, h) for h in ("art_hip.h", "resampler.h", "biquad.h", "decimator.h", "stretch.h")]
 
 
 def _stale(target, deps):

@@ -313,52 +313,37 @@ unsigned long arthip_fir_rate_grad_tiles (const ArtAdjPhase *phases, int nphases
  * upload could not be made). */
 int arthip_fir_rate_grad (const ArtRateItem *items, int n, const ArtAdjPhase *phases, int nphases, const ArtamdSegment *segs, int nsegs,
                           void *d_table, void *stream);
-/* ---- fir_sample.hip: whole clips at a position curve in device memory (resampleSample*ClipsPlanarDevice) ----
+/* ---- fir_sample.hip: whole clips at a position curve in device memory (resampleSample*ClipsPlanarDevice, resampleSampleBand*ClipsPlanarDevice) ----
  * An item is one clip and its curve of `gy_frames` positions (doubles, in input frames; p = 0 is centred on frame 0).  One struct serves the
- * three launches: the forward reads in and writes out = y; the adjoint reads gy and writes out = gx; the slope reads in and gy and writes gp.
+ * three launches of both families: the forward reads in and writes out = y; the adjoint reads gy and writes out = gx; the slope reads in and
+ * gy and writes gp — on the banded entries gp, gl or both, whichever is not NULL (the same in every item of a launch: the entry's lists).
+ * The unbanded entries' item has its context's bank as rung 0, rungs = 1 and no levels; a banded item holds a LADDER of `rungs` banks of one
+ * shape (interpolating contexts only) and a curve of gy_frames levels beside the positions.
  * The forward's and the slope's tasks are tiles of ART_SAMPLE_TILE consecutive outputs, the adjoint's tiles of ART_SAMPLE_TILE consecutive
  * input frames times the item's channel groups; an item is in a launch only if it has a task. */
 #define ART_SAMPLE_TILE 256
+#define ART_BAND_RUNGS 8
 enum { ART_SAMPLE_FORWARD, ART_SAMPLE_ADJOINT, ART_SAMPLE_SLOPE };
 typedef struct {
-    const art_s *bank;                   /* device, (F+1) x T */
-    const double *pos;                   /* the curve: gy_frames doubles */
+    const art_s *bank [ART_BAND_RUNGS];  /* device, (F+1) x T each; [0, rungs) */
+    const double *pos, *level;           /* the curve: gy_frames doubles; the levels beside it (NULL: the unbanded entries) */
     const art_s *in;                     /* the clip's samples: in_frames frames (forward, slope) */
     const art_s *gy;                     /* gradient of the outputs: gy_frames frames (adjoint, slope) */
     art_s *out;                          /* forward: y, gy_frames frames are SET; adjoint: gx, in_frames frames are SET */
-    double *gp;                          /* slope: gy_frames doubles are SET */
+    double *gp, *gl;                     /* slope: gy_frames doubles are SET in each that is there */
     long in_pitch, gy_pitch, out_pitch;  /* samples between planes; 0: that side interleaved */
     unsigned int gy_frames;              /* M: the curve's length = the clip's outputs */
     unsigned int task0;                  /* first task of the item in its launch (filled by arthip_fir_sample) */
     int in_frames, C, T, F;
-    int interpolate, lowpass;
+    int rungs, interpolate, lowpass, pad;
 } ArtSampleItem;
 /* tasks of one item in launch `what` (0: the item is no part of it) */
 unsigned long arthip_fir_sample_tasks (const ArtSampleItem *it, int what);
 size_t arthip_fir_sample_bytes (int nitems);
-/* ONE launch of kernel `what` over the items (every one with a task at least; their tasks' sum fits an int).  The items go to d_table (device
- * memory of arthip_fir_sample_bytes bytes, reused call after call: stream order protects it) in one upload.  Returns 1, 0 for n <= 0, or -1 (the
- * launch failed; nothing enqueued where the upload could not be made). */
-int arthip_fir_sample (const ArtSampleItem *items, int n, int what, void *d_table, void *stream);
-/* ---- fir_band.hip: the same clips on a LADDER of banks, a level per output (resampleSampleBand*ClipsPlanarDevice) ----
- * An item of its own, so that the unbanded path's stays as small as it is: `rungs` banks of one shape (interpolating contexts only) and a
- * curve of gy_frames levels beside the positions.  Launches, tasks and tiles as above; ART_SAMPLE_SLOPE writes gp, gl or both — whichever
- * is not NULL (the same in every item of a launch: the entry's lists). */
-#define ART_BAND_RUNGS 8
-typedef struct {
-    const art_s *bank [ART_BAND_RUNGS];  /* device, (F+1) x T each; [0, rungs) */
-    const double *pos, *level;           /* the two curves: gy_frames doubles each */
-    const art_s *in, *gy;
-    art_s *out;
-    double *gp, *gl;                     /* slope: gy_frames doubles are SET in each that is there */
-    long in_pitch, gy_pitch, out_pitch;
-    unsigned int gy_frames, task0;
-    int in_frames, C, T, F;
-    int rungs, pad;
-} ArtBandItem;
-unsigned long arthip_fir_band_tasks (const ArtBandItem *it, int what);
-size_t arthip_fir_band_bytes (int nitems);
-int arthip_fir_band (const ArtBandItem *items, int n, int what, void *d_table, void *stream);
+/* ONE launch of kernel `what` — `band`: of the banded family — over the items (every one with a task at least; their tasks' sum fits an int).
+ * The items go to d_table (device memory of arthip_fir_sample_bytes bytes, reused call after call: stream order protects it) in one upload.
+ * Returns 1, 0 for n <= 0, or -1 (the launch failed; nothing enqueued where the upload could not be made). */
+int arthip_fir_sample (const ArtSampleItem *items, int n, int what, int band, void *d_table, void *stream);
 /* the upkeep every launch of a rational-ratio stream does for the rows kept across calls (arthip_fir calls it itself) */
 void arthip_fir_rows_touch (const ArtFirArgs *a, const ArtSegTable *segs);
 /* new_hist[H][C] = last H frames of (hist ++ in[0..appended)); in may be NULL => zeros appended */

@@ -1,7 +1,7 @@
 #pragma once
-// fir_adjoint_walk.hip.h — the chunk walk of the gather adjoints (gfx950): fir_adjoint.hip's blocks kernel, fir_sample.hip's adjoint and fir_band.hip's share
+// fir_adjoint_walk.hip.h — the chunk walk of the gather adjoints (gfx950): fir_adjoint.hip's blocks kernel and fir_sample.hip's two adjoints share
 // this one copy, each with its own source of output positions: adj_walk asks adj_locate<INTERP> (rate, segs, n), an overload set — the one
-// below for a planned phase, fir_sample_common.hip.h's for an entry of a position array (found at instantiation, through its argument types).  With the
+// below for a planned phase, fir_sample.hip's for an entry of a position array (found at instantiation, through its argument types).  With the
 // source as a pair of operands passed on as locate ()'s were, fir_adjoint.hip's device code is what it was before the walk moved here,
 // instruction for instruction in both widths (a functor that holds the pair moved one conversion and renumbered a scalar register in the
 // blocks kernel's eight instantiations).  Compiled with -ffp-contract=off, as both are.
@@ -18,6 +18,11 @@ static_assert (ADJ_CHUNK % ADJ_UNROLL == 0, "whole groups per chunk");
 template <bool INTERP>
 __device__ __forceinline__ Pos adj_locate (const AdjRate &rate, const AdjSegs &segs, unsigned int n) { return locate<INTERP> (rate, segs, n); }
 
+// the one bank of an unbanded walk: a planned item's, or rung 0 of a curve item's ladder (its only rung there) — settled at compile time
+template <typename Item>
+__device__ __forceinline__ const art_s *adj_bank (const Item &it) { return it.bank; }
+__device__ __forceinline__ const art_s *adj_bank (const ArtSampleItem &it) { return it.bank [0]; }
+
 // One phase's share of a lane's sum: the outputs [n_begin, n_end) of the phase (g0: its first output among the clip's), whose windows may hold the
 // lane's frame at linear index `lin` of the phase's space (live: the lane has a frame there at all), in chunks of ADJ_CHUNK through the LDS.
 // Every thread of the workgroup calls it with the same range.  adj_locate<INTERP> (rate, segs, n) is output n's Pos, ip in the space `lin`
@@ -27,7 +32,7 @@ __device__ __forceinline__ Pos adj_locate (const AdjRate &rate, const AdjSegs &s
 // instantiations, +-2 VGPRs in three: profiles/clip_warp.txt), and the two-phase kernel keeps the code object it was measured with.
 // A change to the arithmetic is made in both places; tests/test_gpu_clip_warp.py holds the two kernels to the same bits on one-block
 // clips.
-// BAND (fir_band.hip; INTERP only): the item holds a ladder of banks of one shape, it.bank [0 .. K), and adj_level (segs, n, rung, lam) gives
+// BAND (fir_sample.hip's banded adjoint; INTERP only): the item holds a ladder of banks of one shape, it.bank [0 .. K), and adj_level (segs, n, rung, lam) gives
 // output n's rung L and blend lam: its weight is rung L's where lam == 0 — the line below, on that bank — and elsewhere
 // (art_s)(w_L * (1.0 - lam) + w_{L+1} * lam) with w_k = h0 * f0 + h1 * f1 of rung k unrounded, in double.  Two more rows of the chunk in the
 // LDS (s_rung, s_lam).  Without BAND nothing of this is compiled: the other instantiations are what they were.
@@ -38,7 +43,7 @@ __device__ __forceinline__ void adj_walk (art_s (&acc) [CG], const Item &it, con
 {
     static_assert (INTERP || !BAND, "a ladder is blended on interpolating banks only");
     const art_s *bank = nullptr;
-    if constexpr (!BAND) bank = it.bank;
+    if constexpr (!BAND) bank = adj_bank (it);
     const int T = it.T, half = T / 2;
 
     for (int n0 = n_begin; n0 < n_end; n0 += ADJ_CHUNK) {

@@ -2231,29 +2231,43 @@ out:
 }
 
 /* ---- whole clips at a position curve in device memory ------------------------------------------------------------------
- * resampleSampleClipsPlanarDevice, resampleSampleAdjointClipsPlanarDevice, resampleSamplePositionGradientClipsPlanarDevice (art_hip.h): no
- * planner and no context state — a context supplies its bank and flags, every output's position comes from the caller's curve, and
- * fir_sample.hip does the rest in one launch.  The three entries are one function: `what` says which buffers an item needs (d_in: x;
- * d_gy; d_out: y or gx; d_gp) and when it is part of the launch. */
-static int sample_entry (int what, const char *name, Resample *const *cxts, int n,
+ * resampleSampleClipsPlanarDevice, resampleSampleAdjointClipsPlanarDevice, resampleSamplePositionGradientClipsPlanarDevice and, on a LADDER of
+ * banks with a level per output, resampleSampleBandClipsPlanarDevice, resampleSampleBandAdjointClipsPlanarDevice,
+ * resampleSampleBandGradientsClipsPlanarDevice (art_hip.h): no planner and no context state — a context supplies its bank and flags, every
+ * output's position comes from the caller's curve, and fir_sample.hip does the rest in one launch.  The six entries are one function: `what`
+ * says which buffers an item needs (d_in: x; d_gy; d_out: y or gx; d_gp, d_gl) and when it is part of the launch, `band` which family
+ * calls; the unbanded three bring numRungs = 0 and no d_levels, one context per clip.  On the banded three rung k of clip i is
+ * cxts [i * numRungs + k], the levels lie beside the positions, the per-clip checks are made on rung 0 with the ladder's on top, and the
+ * gradients entry takes d_gp, d_gl or both. */
+static int sample_entry (int what, int band, const char *name, Resample *const *cxts, int n, int numRungs,
                          const art_s *const *d_in, const long *inPitches, const int *numInputFrames,
-                         const double *const *d_positions, const int *numOutputFrames,
-                         const art_s *const *d_gy, const long *gyPitches, art_s *const *d_out, const long *outPitches, double *const *d_gp)
+                         const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
+                         const art_s *const *d_gy, const long *gyPitches, art_s *const *d_out, const long *outPitches,
+                         double *const *d_gp, double *const *d_gl)
 {
     const int reads_in = what != ART_SAMPLE_ADJOINT, reads_gy = what != ART_SAMPLE_FORWARD, writes_out = what != ART_SAMPLE_SLOPE;
+    const int rungs = band ? numRungs : 1;
 
     if (n <= 0) return 0;
-    if (!cxts || !numInputFrames || !d_positions || !numOutputFrames || (reads_in && !d_in) || (reads_gy && !d_gy) || (writes_out && !d_out) ||
-        (!writes_out && !d_gp)) return -1;
-    if (clip_contexts_refused (cxts, n)) return -1;
+    if (band && (numRungs < 1 || numRungs > ART_BAND_RUNGS || n > INT_MAX / ART_BAND_RUNGS)) return -1;
+    if (!cxts || !numInputFrames || !d_positions || (band && !d_levels) || !numOutputFrames || (reads_in && !d_in) || (reads_gy && !d_gy) ||
+        (writes_out && !d_out) || (!writes_out && !d_gp && !d_gl)) return -1;
+    if (clip_contexts_refused (cxts, n * rungs)) return -1;
     for (int i = 0; i < n; ++i) {
+        const Resample *lead = cxts [i * rungs];
         const int nIn = numInputFrames [i], nOut = numOutputFrames [i];
-        if (nIn < 0 || nOut < 0 || nIn > INT_MAX - 2 * cxts [i]->numTaps) return -1;
+        for (int k = 0; band && k < rungs; ++k) {
+            const Resample *rung = cxts [i * rungs + k];
+            if (rung->numChannels != lead->numChannels || rung->numTaps != lead->numTaps || rung->numFilters != lead->numFilters) return -1;
+            /* (two rungs are blended value by value of one interpolation cell: both interpolate) */
+            if (!(rung->flags & SUBSAMPLE_INTERPOLATE)) return -1;
+        }
+        if (nIn < 0 || nOut < 0 || nIn > INT_MAX - 2 * lead->numTaps) return -1;
         /* (the slope of a nearest-filter context is zero almost everywhere) */
-        if (what == ART_SAMPLE_SLOPE && !(cxts [i]->flags & SUBSAMPLE_INTERPOLATE)) return -1;
+        if (what == ART_SAMPLE_SLOPE && !(lead->flags & SUBSAMPLE_INTERPOLATE)) return -1;
         if (!nOut || (what == ART_SAMPLE_ADJOINT && !nIn)) continue;
-        if (!d_positions [i] || (reads_in && nIn && !d_in [i]) || (reads_gy && !d_gy [i]) || (writes_out && !d_out [i]) || (!writes_out && !d_gp [i]))
-            return -1;
+        if (!d_positions [i] || (band && !d_levels [i]) || (reads_in && nIn && !d_in [i]) || (reads_gy && !d_gy [i]) || (writes_out && !d_out [i]) ||
+            (d_gp && !d_gp [i]) || (d_gl && !d_gl [i])) return -1;
     }
 
     struct artamd_resampler *lead = cxts [0]->hip;
@@ -2262,11 +2276,13 @@ static int sample_entry (int what, const char *name, Resample *const *cxts, int 
     int live = 0, rc = -1, refused = 0;
     if (!items) goto out;
     for (int i = 0; i < n; ++i) {
-        const Resample *cxt = cxts [i];
+        const Resample *cxt = cxts [i * rungs];
         ArtSampleItem *it = &items [live];
         if (!numOutputFrames [i] || (what == ART_SAMPLE_ADJOINT && !numInputFrames [i])) continue;     /* (no task: no item) */
         memset (it, 0, sizeof (*it));
-        it->bank = cxt->hip->d_bank; it->pos = d_positions [i];
+        for (int k = 0; k < rungs; ++k) it->bank [k] = cxts [i * rungs + k]->hip->d_bank;
+        it->rungs = rungs;
+        it->pos = d_positions [i]; it->level = band ? d_levels [i] : NULL;
         it->gy_frames = (unsigned int) numOutputFrames [i]; it->in_frames = numInputFrames [i];
         it->C = cxt->numChannels; it->T = cxt->numTaps; it->F = cxt->numFilters;
         it->interpolate = (cxt->flags & SUBSAMPLE_INTERPOLATE) != 0;
@@ -2274,7 +2290,7 @@ static int sample_entry (int what, const char *name, Resample *const *cxts, int 
         if (reads_in) { it->in = d_in [i]; it->in_pitch = inPitches ? inPitches [i] : 0; }
         if (reads_gy) { it->gy = d_gy [i]; it->gy_pitch = gyPitches ? gyPitches [i] : 0; }
         if (writes_out) { it->out = d_out [i]; it->out_pitch = outPitches ? outPitches [i] : 0; }
-        else it->gp = d_gp [i];
+        else { it->gp = d_gp ? d_gp [i] : NULL; it->gl = d_gl ? d_gl [i] : NULL; }
         tasks += arthip_fir_sample_tasks (it, what);
         ++live;
     }
@@ -2284,12 +2300,13 @@ static int sample_entry (int what, const char *name, Resample *const *cxts, int 
     {
         ENTER_DEVICE (lead);
         lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_sample_bytes (live));
-        rc = lead->d_batch ? arthip_fir_sample (items, live, what, lead->d_batch, lead->stream) : -1;
+        rc = lead->d_batch ? arthip_fir_sample (items, live, what, band, lead->d_batch, lead->stream) : -1;
         if (rc < 0) fprintf (stderr, "artamd: %s: launch failed: %s\n", name, arthip_last_error ());
         LEAVE_DEVICE (lead);
     }
 out:
-    if (rc < 0 && !refused) artamd_note_failure ("resampler: a launch of the clips sampler failed");
+    if (rc < 0 && !refused)
+        artamd_note_failure (band ? "resampler: a launch of the banded clips sampler failed" : "resampler: a launch of the clips sampler failed");
     free (items);
     return rc;
 }
@@ -2299,8 +2316,8 @@ int resampleSampleClipsPlanarDevice (Resample *const *cxts, int n,
         const double *const *d_positions, const int *numOutputFrames,
         artsample_t *const *d_outputs, const long *outputPitches)
 {
-    return sample_entry (ART_SAMPLE_FORWARD, "resample sample", cxts, n, d_inputs, inputPitches, numInputFrames, d_positions, numOutputFrames,
-                         NULL, NULL, d_outputs, outputPitches, NULL);
+    return sample_entry (ART_SAMPLE_FORWARD, 0, "resample sample", cxts, n, 0, d_inputs, inputPitches, numInputFrames, d_positions, NULL, numOutputFrames,
+                         NULL, NULL, d_outputs, outputPitches, NULL, NULL);
 }
 
 int resampleSampleAdjointClipsPlanarDevice (Resample *const *cxts, int n,
@@ -2308,8 +2325,8 @@ int resampleSampleAdjointClipsPlanarDevice (Resample *const *cxts, int n,
         const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
         artsample_t *const *d_gradInputs, const long *gradInputPitches, const int *numInputFrames)
 {
-    return sample_entry (ART_SAMPLE_ADJOINT, "resample sample adjoint", cxts, n, NULL, NULL, numInputFrames, d_positions, numOutputFrames,
-                         d_gradOutputs, gradOutputPitches, d_gradInputs, gradInputPitches, NULL);
+    return sample_entry (ART_SAMPLE_ADJOINT, 0, "resample sample adjoint", cxts, n, 0, NULL, NULL, numInputFrames, d_positions, NULL, numOutputFrames,
+                         d_gradOutputs, gradOutputPitches, d_gradInputs, gradInputPitches, NULL, NULL);
 }
 
 int resampleSamplePositionGradientClipsPlanarDevice (Resample *const *cxts, int n,
@@ -2318,79 +2335,8 @@ int resampleSamplePositionGradientClipsPlanarDevice (Resample *const *cxts, int 
         const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
         double *const *d_gradPositions)
 {
-    return sample_entry (ART_SAMPLE_SLOPE, "resample sample position gradient", cxts, n, d_inputs, inputPitches, numInputFrames, d_positions,
-                         numOutputFrames, d_gradOutputs, gradOutputPitches, NULL, NULL, d_gradPositions);
-}
-
-/* ---- the same clips on a ladder of banks, a level per output ---------------------------------------------------------------
- * resampleSampleBandClipsPlanarDevice, resampleSampleBandAdjointClipsPlanarDevice, resampleSampleBandGradientsClipsPlanarDevice (art_hip.h):
- * rung k of clip i is cxts [i * numRungs + k]; the levels lie beside the positions, and fir_band.hip does the rest in one launch.  One
- * function again: the sampling entries' checks per clip on its rung 0, the ladder's on top.  The gradients entry takes d_gp, d_gl or
- * both. */
-static int band_entry (int what, const char *name, Resample *const *cxts, int n, int numRungs,
-                       const art_s *const *d_in, const long *inPitches, const int *numInputFrames,
-                       const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
-                       const art_s *const *d_gy, const long *gyPitches, art_s *const *d_out, const long *outPitches,
-                       double *const *d_gp, double *const *d_gl)
-{
-    const int reads_in = what != ART_SAMPLE_ADJOINT, reads_gy = what != ART_SAMPLE_FORWARD, writes_out = what != ART_SAMPLE_SLOPE;
-
-    if (n <= 0) return 0;
-    if (numRungs < 1 || numRungs > ART_BAND_RUNGS || n > INT_MAX / ART_BAND_RUNGS) return -1;
-    if (!cxts || !numInputFrames || !d_positions || !d_levels || !numOutputFrames || (reads_in && !d_in) || (reads_gy && !d_gy) ||
-        (writes_out && !d_out) || (!writes_out && !d_gp && !d_gl)) return -1;
-    if (clip_contexts_refused (cxts, n * numRungs)) return -1;
-    for (int i = 0; i < n; ++i) {
-        const Resample *lead = cxts [i * numRungs];
-        const int nIn = numInputFrames [i], nOut = numOutputFrames [i];
-        for (int k = 0; k < numRungs; ++k) {
-            const Resample *rung = cxts [i * numRungs + k];
-            if (rung->numChannels != lead->numChannels || rung->numTaps != lead->numTaps || rung->numFilters != lead->numFilters) return -1;
-            /* (two rungs are blended value by value of one interpolation cell: both interpolate) */
-            if (!(rung->flags & SUBSAMPLE_INTERPOLATE)) return -1;
-        }
-        if (nIn < 0 || nOut < 0 || nIn > INT_MAX - 2 * lead->numTaps) return -1;
-        if (!nOut || (what == ART_SAMPLE_ADJOINT && !nIn)) continue;
-        if (!d_positions [i] || !d_levels [i] || (reads_in && nIn && !d_in [i]) || (reads_gy && !d_gy [i]) || (writes_out && !d_out [i]) ||
-            (d_gp && !d_gp [i]) || (d_gl && !d_gl [i])) return -1;
-    }
-
-    struct artamd_resampler *lead = cxts [0]->hip;
-    ArtBandItem *items = malloc (sizeof (ArtBandItem) * (size_t) n);
-    unsigned long tasks = 0;
-    int live = 0, rc = -1, refused = 0;
-    if (!items) goto out;
-    for (int i = 0; i < n; ++i) {
-        const Resample *cxt = cxts [i * numRungs];
-        ArtBandItem *it = &items [live];
-        if (!numOutputFrames [i] || (what == ART_SAMPLE_ADJOINT && !numInputFrames [i])) continue;     /* (no task: no item) */
-        memset (it, 0, sizeof (*it));
-        for (int k = 0; k < numRungs; ++k) it->bank [k] = cxts [i * numRungs + k]->hip->d_bank;
-        it->rungs = numRungs;
-        it->pos = d_positions [i]; it->level = d_levels [i];
-        it->gy_frames = (unsigned int) numOutputFrames [i]; it->in_frames = numInputFrames [i];
-        it->C = cxt->numChannels; it->T = cxt->numTaps; it->F = cxt->numFilters;
-        if (reads_in) { it->in = d_in [i]; it->in_pitch = inPitches ? inPitches [i] : 0; }
-        if (reads_gy) { it->gy = d_gy [i]; it->gy_pitch = gyPitches ? gyPitches [i] : 0; }
-        if (writes_out) { it->out = d_out [i]; it->out_pitch = outPitches ? outPitches [i] : 0; }
-        else { it->gp = d_gp ? d_gp [i] : NULL; it->gl = d_gl ? d_gl [i] : NULL; }
-        tasks += arthip_fir_band_tasks (it, what);
-        ++live;
-    }
-    if (tasks > (unsigned long) INT_MAX) { refused = 1; goto out; }
-    if (!live) { rc = 0; goto out; }
-
-    {
-        ENTER_DEVICE (lead);
-        lead->d_batch = arthip_grow (lead->d_batch, &lead->batch_cap, arthip_fir_band_bytes (live));
-        rc = lead->d_batch ? arthip_fir_band (items, live, what, lead->d_batch, lead->stream) : -1;
-        if (rc < 0) fprintf (stderr, "artamd: %s: launch failed: %s\n", name, arthip_last_error ());
-        LEAVE_DEVICE (lead);
-    }
-out:
-    if (rc < 0 && !refused) artamd_note_failure ("resampler: a launch of the banded clips sampler failed");
-    free (items);
-    return rc;
+    return sample_entry (ART_SAMPLE_SLOPE, 0, "resample sample position gradient", cxts, n, 0, d_inputs, inputPitches, numInputFrames, d_positions, NULL,
+                         numOutputFrames, d_gradOutputs, gradOutputPitches, NULL, NULL, d_gradPositions, NULL);
 }
 
 int resampleSampleBandClipsPlanarDevice (Resample *const *cxts, int n, int numRungs,
@@ -2398,8 +2344,8 @@ int resampleSampleBandClipsPlanarDevice (Resample *const *cxts, int n, int numRu
         const double *const *d_positions, const double *const *d_levels, const int *numOutputFrames,
         artsample_t *const *d_outputs, const long *outputPitches)
 {
-    return band_entry (ART_SAMPLE_FORWARD, "resample sample band", cxts, n, numRungs, d_inputs, inputPitches, numInputFrames, d_positions, d_levels,
-                       numOutputFrames, NULL, NULL, d_outputs, outputPitches, NULL, NULL);
+    return sample_entry (ART_SAMPLE_FORWARD, 1, "resample sample band", cxts, n, numRungs, d_inputs, inputPitches, numInputFrames, d_positions, d_levels,
+                         numOutputFrames, NULL, NULL, d_outputs, outputPitches, NULL, NULL);
 }
 
 int resampleSampleBandAdjointClipsPlanarDevice (Resample *const *cxts, int n, int numRungs,
@@ -2407,8 +2353,8 @@ int resampleSampleBandAdjointClipsPlanarDevice (Resample *const *cxts, int n, in
         const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
         artsample_t *const *d_gradInputs, const long *gradInputPitches, const int *numInputFrames)
 {
-    return band_entry (ART_SAMPLE_ADJOINT, "resample sample band adjoint", cxts, n, numRungs, NULL, NULL, numInputFrames, d_positions, d_levels,
-                       numOutputFrames, d_gradOutputs, gradOutputPitches, d_gradInputs, gradInputPitches, NULL, NULL);
+    return sample_entry (ART_SAMPLE_ADJOINT, 1, "resample sample band adjoint", cxts, n, numRungs, NULL, NULL, numInputFrames, d_positions, d_levels,
+                         numOutputFrames, d_gradOutputs, gradOutputPitches, d_gradInputs, gradInputPitches, NULL, NULL);
 }
 
 int resampleSampleBandGradientsClipsPlanarDevice (Resample *const *cxts, int n, int numRungs,
@@ -2417,8 +2363,8 @@ int resampleSampleBandGradientsClipsPlanarDevice (Resample *const *cxts, int n, 
         const artsample_t *const *d_gradOutputs, const long *gradOutputPitches,
         double *const *d_gradPositions, double *const *d_gradLevels)
 {
-    return band_entry (ART_SAMPLE_SLOPE, "resample sample band gradients", cxts, n, numRungs, d_inputs, inputPitches, numInputFrames, d_positions,
-                       d_levels, numOutputFrames, d_gradOutputs, gradOutputPitches, NULL, NULL, d_gradPositions, d_gradLevels);
+    return sample_entry (ART_SAMPLE_SLOPE, 1, "resample sample band gradients", cxts, n, numRungs, d_inputs, inputPitches, numInputFrames, d_positions,
+                         d_levels, numOutputFrames, d_gradOutputs, gradOutputPitches, NULL, NULL, d_gradPositions, d_gradLevels);
 }
 
 /* ---- consecutive blocks of one stream, one launch --------------------------------------------------------------------

@@ -8,7 +8,8 @@ clip classes' output (ClipResampler, ClipWarper: their lead-in of half a filter 
 or an alignment path are torch expressions in front of the call, and autograd carries dL/dp to them.
 
 The names live beside the binding (audio_resampler_amd.api), not in it: `binding(width)` here returns a namespace of them for that sample
-width, built on api.binding(width) and on the helpers it hands out under `_private`; the module level is the 4-byte build."""
+width, built on api.binding(width) and on the helpers it hands out under `_private`, and handing out its own curve helpers the same way
+(audio_resampler_amd.band builds on them); the module level is the 4-byte build."""
 import types
 
 from . import api
@@ -71,6 +72,53 @@ def _bind(width):
         """addresses of the rows of p [B, M] (float64, consecutive along M; a broadcast curve is one row listed B times)"""
         return [p.data_ptr() + i * p.stride(0) * 8 for i in range(p.shape[0])]
 
+    def _monotone(p, outs, gy, *along):
+        """(curve, gy, *along) in an order the adjoint kernels take: they bisect the curve, so they want positions that do not decrease.
+        The check runs on the device, within outs; its one boolean is all that comes back.  A curve that fails it (reverse playback,
+        scratching, a NaN) is sorted — stably, what lies past outs moved to the end first — and gy [B, C, M] and every tensor [B, M] of
+        `along` gathered into the same order: A sums over the outputs, so A^T does not care about their order, as long as every output
+        keeps what belongs to it."""
+        import torch
+        M = p.shape[1]
+        past = torch.arange(M, device=p.device)[None, :] >= torch.tensor(outs, device=p.device)[:, None]
+        if bool(((p[:, 1:] >= p[:, :-1]) | past[:, 1:]).all()):
+            return (p, gy) + along
+        curve, order = torch.sort(p.masked_fill(past, float("inf")), dim=1, stable=True)
+        return (curve, torch.gather(gy, 2, order[:, None, :].expand(-1, gy.shape[1], -1))) + tuple(torch.gather(t, 1, order) for t in along)
+
+    def _check_positions(positions, B_):
+        import torch
+        if not torch.is_tensor(positions) or positions.dtype not in (torch.float32, torch.float64) or positions.dim() not in (1, 2) or \
+                (positions.dim() == 2 and B_ is not None and positions.shape[0] != B_):
+            raise ValueError("positions: a float32 or float64 tensor [B, M] or [M]")
+
+    def _outs(out_lengths, B_, M):
+        if out_lengths is None:
+            return [M] * B_
+        outs = [int(v) for v in (out_lengths.tolist() if hasattr(out_lengths, "tolist") else out_lengths)]
+        if len(outs) != B_ or any(v < 0 or v > M for v in outs):
+            raise ValueError("out_lengths: one entry per clip, 0 .. M")
+        return outs
+
+    def _on_device(x, channels, **curves):
+        """the samples on the GPU with consecutive frames, and every curve given (by its name in the message) beside them"""
+        if not x.is_cuda:
+            raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {channels}, T]")
+        for name, t in curves.items():
+            if t is not None and t.device != x.device:
+                raise ValueError(f"{name}: on the samples' device (they are not downloaded)")
+        # (frames of a channel must be consecutive; any row pitch is taken as it is)
+        return x.contiguous() if x.shape[2] and x.stride(2) != 1 else x
+
+    def _rows(t, B_, M):
+        """t [B, M] or [M] as float64 rows [B, M], consecutive along M — torch ops in front of the custom function: autograd sums a
+        broadcast curve's gradient back and narrows it to the caller's dtype"""
+        import torch
+        t = t if t.dim() == 2 else t[None, :].expand(B_, M)
+        if t.dtype != torch.float64:
+            t = t.to(torch.float64)
+        return t.contiguous() if M > 1 and t.stride(1) != 1 else t
+
     def _forward(ctx, x, p, clip, lengths, outs):
         ctx.save_for_backward(x, p)                               # (an edit of either in place before backward is caught)
         ctx.clip, ctx.lengths, ctx.outs = clip, lengths, outs
@@ -93,15 +141,7 @@ def _bind(width):
             gy = gy.contiguous()
         lead.set_stream(torch.cuda.current_stream(gy.device).cuda_stream)
         if need_x:
-            # the adjoint kernel bisects the curve: it wants positions that do not decrease.  The check runs on the device, within
-            # out_lengths; its one boolean is all that comes back.  A curve that fails it (reverse playback, scratching, a NaN) is sorted
-            # — stably, what lies past out_lengths moved to the end first — and gy gathered into the same order: A sums over the outputs,
-            # so A^T does not care about their order.
-            past = torch.arange(M, device=p.device)[None, :] >= torch.tensor(outs, device=p.device)[:, None]
-            curve, g = p, gy
-            if not bool(((p[:, 1:] >= p[:, :-1]) | past[:, 1:]).all()):
-                curve, order = torch.sort(p.masked_fill(past, float("inf")), dim=1, stable=True)
-                g = torch.gather(gy, 2, order[:, None, :].expand(-1, gy.shape[1], -1))
+            curve, g = _monotone(p, outs, gy)
             (g_ptrs, g_pitch), (gx_ptrs, gx_pitch) = P._clip_ptrs(g), P._clip_ptrs(gx)
             sample_adjoint_clips_planar_device([lead] * B_, _curve_ptrs(curve), outs, g_ptrs, [g_pitch] * B_, gx_ptrs, [gx_pitch] * B_, lengths)
         if need_p:
@@ -163,36 +203,22 @@ def _bind(width):
             import torch
             # (the GPU is asked for behind the host checks: they need none)
             x, B_, Cn, T, lengths = P._clip_input(x, self.channels, lengths, cuda=False, strided="keep")
-            if not torch.is_tensor(positions) or positions.dtype not in (torch.float32, torch.float64) or positions.dim() not in (1, 2) or \
-                    (positions.dim() == 2 and positions.shape[0] != B_):
-                raise ValueError("positions: a float32 or float64 tensor [B, M] or [M]")
+            _check_positions(positions, B_)
             M = positions.shape[-1]
-            if out_lengths is None:
-                outs = [M] * B_
-            else:
-                outs = [int(v) for v in (out_lengths.tolist() if hasattr(out_lengths, "tolist") else out_lengths)]
-                if len(outs) != B_ or any(v < 0 or v > M for v in outs):
-                    raise ValueError("out_lengths: one entry per clip, 0 .. M")
+            outs = _outs(out_lengths, B_, M)
             grad = torch.is_grad_enabled()
             if grad and positions.requires_grad and not self.flags & api.SUBSAMPLE_INTERPOLATE:
                 raise ValueError("ClipSampler: without SUBSAMPLE_INTERPOLATE the position gradient is zero almost everywhere")
-            if not x.is_cuda:
-                raise ValueError(f"expected a CUDA {smp_torch} tensor [B, {self.channels}, T]")
-            if positions.device != x.device:
-                raise ValueError("positions: on the samples' device (they are not downloaded)")
-            if x.shape[2] and x.stride(2) != 1:
-                x = x.contiguous()                                # (frames of a channel must be consecutive; any row pitch is taken as it is)
-            # torch ops in front of the custom function: autograd sums a broadcast curve's gradient back and narrows it to the caller's dtype
-            p = positions if positions.dim() == 2 else positions[None, :].expand(B_, M)
-            if p.dtype != torch.float64:
-                p = p.to(torch.float64)
-            if M > 1 and p.stride(1) != 1:
-                p = p.contiguous()
+            x = _on_device(x, self.channels, positions=positions)
+            p = _rows(positions, B_, M)
             if grad and (x.requires_grad or p.requires_grad):
                 return _clip_sample_grad().apply(x, p, self, lengths, outs)
             return self._sample(x.detach(), p.detach(), lengths, outs)
 
-    return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k not in ("width", "B", "P", "smp_torch")}, width=width)
+    _private = types.SimpleNamespace(_one_per_clip=_one_per_clip, _curve_ptrs=_curve_ptrs, _monotone=_monotone, _check_positions=_check_positions,
+                                     _outs=_outs, _on_device=_on_device, _rows=_rows)       # (what audio_resampler_amd.band builds on)
+    return types.SimpleNamespace(**{k: v for k, v in locals().items() if not k.startswith("_") and k not in ("width", "B", "P", "smp_torch")}, width=width,
+                                 _private=_private)
 
 
 _bound = {}
@@ -204,4 +230,4 @@ def binding(width=32):
     return _bound[width]
 
 
-globals().update({k: v for k, v in vars(binding(32)).items() if k != "width"})      # module level = the 4-byte build
+globals().update({k: v for k, v in vars(binding(32)).items() if k not in ("width", "_private")})      # module level = the 4-byte build

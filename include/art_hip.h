@@ -459,7 +459,7 @@ int resampleSamplePositionGradientClipsPlanarDevice (Resample *const *cxts, int 
  *              0 <= l <= K - 1, -0.0 included: the closed ends pass the gradient, as a clamp's do, so a level that starts on a rung can
  *              leave it; exactly 0 for l < 0, l > K - 1, a NaN, K = 1 and an output without a window.  d_gradPositions or d_gradLevels
  *              may be NULL — not wanted; the value chains run only where d_gradLevels is given.
- * One launch per entry (fir_band.hip), the sampling entries' task spaces; an output reads the one or two banks it needs.  The result does
+ * One launch per entry (fir_sample.hip), the sampling entries' task spaces; an output reads the one or two banks it needs.  The result does
  * not depend on the batch, the layout, the pitches or the stream.  Pitches, n <= 0, the return value (1 or 0 launches) and items without
  * outputs as in the sampling entries.  -1 with nothing enqueued and nothing counted: numRungs outside 1 .. 8, a rung that differs from its
  * item's rung 0 in channels, taps or filters, a rung without SUBSAMPLE_INTERPOLATE, everything the sampling entries refuse (for any rung;

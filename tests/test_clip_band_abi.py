@@ -14,6 +14,7 @@ import audio_resampler_amd as A
 from audio_resampler_amd import band, sampler
 import _band_ref as BR
 from test_matrix_batch_abi import _kernel_notes
+from test_clip_sampler_abi import rows_against_the_parents
 
 PKG = os.path.dirname(os.path.abspath(A.__file__))
 LIB32, LIB64 = os.path.join(PKG, "libartamd.so"), os.path.join(PKG, "libartamd64.so")
@@ -155,6 +156,12 @@ def test_kernels_use_no_scratch_no_spills_and_a_constant_lds(tmp_path, monkeypat
         sample_bytes = 8 if lib == LIB64 else 4
         assert int(f["group_segment_fixed_size"]) == (256 * (3 * 4 + 3 * 8 + 4 * sample_bytes) + 8 if "adjoint" in s else 0), (s, f)
         assert int(f["vgpr_count"]) <= 128, (s, f)               # (room for four waves per SIMD at least)
+
+
+@pytest.mark.parametrize("width", [32, 64])
+def test_kernels_keep_the_parent_commits_rows(tmp_path, monkeypatch, width):
+    """(the banded maps' 128 VGPRs at most are held by the test above)"""
+    rows_against_the_parents(tmp_path, monkeypatch, width, KERNELS)
 
 
 @pytest.mark.parametrize("width", [32, 64])

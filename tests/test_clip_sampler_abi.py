@@ -3,6 +3,7 @@ both widths and wrapped (audio_resampler_amd.sampler); n <= 0 and the refusals t
 kernels are in both libraries without scratch or spills; the new module adds no name to the binding; ClipSampler's host-side refusals on
 CPU tensors, before any GPU is asked for."""
 import ctypes as C
+import json
 import os
 import re
 
@@ -135,6 +136,33 @@ def test_kernels_use_no_scratch_no_spills_and_a_constant_lds(tmp_path, monkeypat
         sample_bytes = 8 if lib == LIB64 else 4
         assert int(f["group_segment_fixed_size"]) == (256 * (3 * 4 + 2 * 8 + 4 * sample_bytes) + 8 if "adjoint" in s else 0), (s, f)
         assert int(f["vgpr_count"]) <= 128, (s, f)               # (room for four waves per SIMD at least)
+
+
+ROW_FIELDS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")
+
+
+def rows_against_the_parents(tmp_path, monkeypatch, width, kernels):
+    """the rows of `kernels` in the library of that width against tests/golden/clip_curve_kernel_rows_parent.json (read at the parent commit with
+    this same helper): every row is the parent's — registers, LDS bytes, no scratch, no spills"""
+    import test_matrix_batch_abi
+    monkeypatch.setattr(test_matrix_batch_abi, "LIB32", LIB64 if width == 64 else LIB32)
+    notes = _kernel_notes(tmp_path)
+    stored = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clip_curve_kernel_rows_parent.json")))
+    assert len(stored["parent_commit"]) == 40 and sorted(stored[str(width)]) == sorted(("fir_sample_kernel", "fir_sample_adjoint_kernel", "fir_sample_slope_kernel",
+                                                                                       "fir_band_kernel", "fir_band_adjoint_kernel", "fir_band_slope_kernel"))
+    for kernel in kernels:
+        (symbol, f), = [(s, f) for s, f in notes.items() if kernel + "E" in s]
+        parent = stored[str(width)][kernel]
+        got = {k: int(f.get(k, 0)) for k in ROW_FIELDS}
+        print(width, kernel, got)
+        for k in ("group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"):
+            assert got[k] == parent[k] and (k == "group_segment_fixed_size" or got[k] == 0), (symbol, k)
+        assert got == parent, symbol
+
+
+@pytest.mark.parametrize("width", [32, 64])
+def test_kernels_keep_the_parent_commits_rows(tmp_path, monkeypatch, width):
+    rows_against_the_parents(tmp_path, monkeypatch, width, KERNELS)
 
 
 @pytest.mark.parametrize("width", [32, 64])
